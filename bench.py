@@ -17,6 +17,12 @@ HBM, ONE RCCL all-reduce(sum) of tf[n]; total work fixed ("scaling": "strong"). 
 under secondary.count23_strong, so the curve is value(N) / secondary.count23_strong.value(1).
 
 Other workloads (own measurements, same JSON shape): --workload count13 | count23 | lookup13 | coverage23 | ...
+
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step). --full adds everything else: CPU / reference baselines, roofline objects (instrumented launches, gather probes,
+kernel-alone runs), checks that take runs of their own, and for the default workload the secondary block (the other query set,
+config 4 at 200 M reads, 13-mer counting, the end-to-end file paths). --dump-outputs DIR writes the arrays of the last timed step
+as .npy files.
 """
 import argparse
 import json
@@ -107,6 +113,32 @@ def timed_steps(step_fn, steps, warmup, device, collective=True):
     return wall, float(np.mean(kern_ms)), kern_ms
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files of one run together
+
+
+def dump_share(n_arrays):
+    """Elements of each of `n_arrays` float64 arrays that fit DUMP_BYTES with their .npy headers."""
+    return (DUMP_BYTES - 1024 * n_arrays) // 8 // n_arrays
+
+
+def dump_outputs(out_dir, arrays, seed=12345):
+    """--dump-outputs: `arrays` (name -> device tensor the timed path returned in its last step) as out_dir/<name>.npy, float64.
+    int32 tensors are read as the library's u32 bit patterns, int64 ones as u64 values below 2^53. An array longer than its share
+    of DUMP_BYTES is replaced by its elements at a fixed, seeded sample of positions (sorted; the same from run to run)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = dump_share(len(arrays))
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        n = t.numel()
+        if n > cap:
+            pos = np.unique(np.random.default_rng(seed).integers(0, n, cap, dtype=np.int64))
+            t = t[torch.from_numpy(pos).to(t.device)]
+            log(f"bench.py: {name}.npy holds {pos.shape[0]} of {n} elements (positions: np.unique(default_rng({seed}).integers(0, {n}, {cap})))")
+        v = t.to(torch.int64) & 0xFFFFFFFF if t.dtype == torch.int32 else t
+        np.save(os.path.join(out_dir, name + ".npy"), v.cpu().numpy().astype(np.float64))
+
+
 def clean_windows(reads_t, n_reads, read_len, k):
     """Windows of k bases without an 'N' in a buffer of fixed-length records, counted with torch in slabs (independent of the library):
     what sum(counts) of a counting workload must equal when the reads are drawn from ACGT genomes with sprinkled Ns."""
@@ -120,6 +152,22 @@ def clean_windows(reads_t, n_reads, read_len, k):
         total += int((inside == 0).sum().item())
         del is_n, c, inside
     return total
+
+
+def cache_dir():
+    """Where bench.py keeps what later runs may reuse (the host-built .pf of the config-3 index, the all-13-mers .pf) and the files of
+    its CPU legs: <repo>/.cache when the tree is writable, else $XDG_CACHE_HOME (default ~/.cache)/aindex_amd, else a directory of
+    this user under the system temporary directory. A checkout the benchmark may not write to is a supported setup."""
+    import tempfile
+    user_cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    for d in (os.path.join(ROOT, ".cache"), os.path.join(user_cache, "aindex_amd"), os.path.join(tempfile.gettempdir(), f"aindex_amd_bench_{os.getuid()}")):
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    raise SystemExit("bench.py: no writable cache directory (tried the checkout, the user cache and the temporary directory)")
 
 
 def scratch_dir(need_bytes, cache):
@@ -552,9 +600,10 @@ def tf_checksum(tf_t):
     return {"sum": int(t.sum().item()), "weighted": int(((t * w).sum() & 0x7FFFFFFFFFFFFFFF).item())}
 
 
-def measure_lookup23(ix, g, qset, queries, rank, world, dev, steps, warmup, gather_probe):
+def measure_lookup23(ix, g, qset, queries, rank, world, dev, steps, warmup, gather_probe, full=True):
     """One query set of SURVEY 8(d) through aix_tf_batch_ascii_dev: Q_rand = uniform-random 23-mers (seed 7; ~all absent),
-    Q_mix = 50 % genome windows on a random strand + 50 % random (seed 8). Queries are generated in HBM; every rank its own."""
+    Q_mix = 50 % genome windows on a random strand + 50 % random (seed 8). Queries are generated in HBM; every rank its own.
+    full=False: the timed steps alone (no instrumented launch, no roofline, no gather probe)."""
     import torch
     from aindex_amd import engine
     if qset == "Q_mix":
@@ -565,6 +614,16 @@ def measure_lookup23(ix, g, qset, queries, rank, world, dev, steps, warmup, gath
     wall, kern_ms, _ = timed_steps(lambda: ix.tf_ascii_t(q, res), steps, warmup, dev)
     hf = int((res != 0).sum().item()) / queries
     info = ix.info
+    cfg = {"workload": f"configs[2]: 23-mer batch lookup (aix_tf_batch_ascii_dev), {qset}: " +
+                       ("50 % windows of the indexed genome on a random strand + 50 % uniform-random 23-mers (seed 8)" if qset == "Q_mix"
+                        else "uniform-random 23-mer ASCII queries (seed 7)") + ", resident in HBM",
+           "query_set": qset, "query_seed": 8 if qset == "Q_mix" else 7, "queries_per_step_per_gpu": queries, "index_keys": ix.n,
+           "hit_fraction": hf, "bucket_table": bool(info["bucket_table"]), "bucket_lanes": info["bucket_lanes"], "buckets": info["buckets"],
+           "bucket_unfiled_keys": info["bucket_unfiled_keys"], "canonical_only": bool(info["canonical_only"]),
+           "absence_filter_words": info["absence_filter_words"], "index_hbm_bytes": info["device_bytes"]}
+    m = {"value": world * queries * steps / wall, "ms_per_step": wall / steps * 1e3, "config": cfg, "_q": q, "_res": res}
+    if not full:
+        return m
     # what the kernel touches (instrumented launch of the same kernel, same settings), per query: MPHF records, key records,
     # evaluations carried through to the rank, bucket lines of the verification table
     li = ix.lines_ascii_t(q).to(torch.int64)
@@ -605,16 +664,9 @@ def measure_lookup23(ix, g, qset, queries, rank, world, dev, steps, warmup, gath
     if tr:
         roof["traffic"] = tr.get("bytes_per_launch")
         roof["traffic_source"] = tr.get("source")
-    cfg = {"workload": f"configs[2]: 23-mer batch lookup (aix_tf_batch_ascii_dev), {qset}: " +
-                       ("50 % windows of the indexed genome on a random strand + 50 % uniform-random 23-mers (seed 8)" if qset == "Q_mix"
-                        else "uniform-random 23-mer ASCII queries (seed 7)") + ", resident in HBM",
-           "query_set": qset, "query_seed": 8 if qset == "Q_mix" else 7, "queries_per_step_per_gpu": queries, "index_keys": ix.n,
-           "hit_fraction": hf, "bucket_table": bool(info["bucket_table"]), "bucket_lanes": info["bucket_lanes"], "buckets": info["buckets"],
-           "bucket_unfiled_keys": info["bucket_unfiled_keys"], "canonical_only": bool(info["canonical_only"]),
-           "absence_filter_words": info["absence_filter_words"], "filter_words_per_query": filter_words,
-           "bucket_lines_per_query": bucket_lines, "mphf_records_read_per_query": mphf_recs, "key_records_read_per_query": key_recs,
-           "completed_evaluations_per_query": completed, "index_hbm_bytes": info["device_bytes"]}
-    return {"value": world * queries * steps / wall, "ms_per_step": wall / steps * 1e3, "roofline": roof, "config": cfg, "_q": q, "_res": res}
+    cfg.update({"filter_words_per_query": filter_words, "bucket_lines_per_query": bucket_lines, "mphf_records_read_per_query": mphf_recs,
+                "key_records_read_per_query": key_recs, "completed_evaluations_per_query": completed})
+    return {**m, "roofline": roof}
 
 
 _FLAGS = {}
@@ -711,19 +763,32 @@ def cpu_baseline_count23(ix, g, pf, dev, cache, ns=100_000):
     return {"value": ns / dt, "unit": "reads/s", "cores": 1, "kind": "port", "sample": f"first {ns} reads of the workload (seed 41)"}
 
 
-def measure_count23_strong(ix, g, rank, world, dev, total_reads, steps, warmup):
+def measure_count23_strong(ix, g, rank, world, dev, total_reads, steps, warmup, full=True, dump=None):
     """BASELINE configs[3] / SURVEY 8(d) config 4: `total_reads` reads x 150 bp (seed 41, 50 % reverse strand, 0.1 % N) cut
     into `world` contiguous read ranges; rank r generates ITS range in its own HBM (nothing comes from the host), histograms it
     against the fixed MPHF index (k_count23_fixed, true canonical form) and ONE all-reduce(sum) merges tf[n] (RCCL over xGMI
-    under "nccl"). Total work is fixed as `world` grows."""
+    under "nccl"). Total work is fixed as `world` grows. full=False: the timed steps alone (no kernel-alone run, no all-reduce
+    timing, no check of sum(tf), no single-GPU comparison); `dump` receives the histogram of the last timed step."""
     import torch
+    import torch.distributed as dist
     from aindex_amd import dist as adist, engine, _lib
     lo, hi = adist.shard_range(total_reads, rank, world)
     reads = engine.synth_reads_t(41, g, hi - lo, 150, rc_half=True, n_rate_ppm=1000, first_read=lo)
     tf = torch.zeros(ix.n, dtype=torch.int32, device=f"cuda:{dev}")
     step = lambda: adist.count23_sharded_t(ix, reads, _lib.CANON_TRUE_RC, tf)
     wall, kern_ms, _ = timed_steps(step, steps, warmup, dev)
+    if dump:
+        dump({"tf": tf})
     digest = tf_checksum(tf)
+    backend = dist.get_backend() if (dist.is_available() and dist.is_initialized()) else "none"
+    r = {"metric": "reads_per_sec_23mer_count_fixed_mphf", "value": total_reads * steps / wall, "unit": "reads/s",
+         "scaling": "strong", "total_reads": total_reads, "reads_this_rank": hi - lo, "ms_per_step": wall / steps * 1e3,
+         "collective": f"all_reduce(sum) of int32 tf[{ix.n}]" if backend != "none" else "none (1 rank)",
+         "backend": backend, "collective_ranks": world if backend != "none" else 1, "kernel": "aix_count23_fixed_dev",
+         "counting_backend": {1: "memory-side atomics", 2: "slot stream + LDS histogram", 3: "distinct k-mers first (K1), one probe per distinct k-mer"}.get(ix.info["count23_backend"], "none"),
+         "histogram_passes": ix.info["count23_passes"], "tf_digest": digest, "one_device_rehearsal": bool(os.environ.get("AIX_BENCH_ONE_DEVICE"))}
+    if not full:
+        return r
     ar_ms = 0.0
     if world > 1 or os.environ.get("AIX_FORCE_DIST"):
         scratch = tf.clone()
@@ -736,8 +801,6 @@ def measure_count23_strong(ix, g, rank, world, dev, total_reads, steps, warmup):
     # counted independently with torch on each rank's own reads
     clean = torch.tensor([clean_windows(reads, hi - lo, 150, 23)], dtype=torch.int64, device=reads.device)
     del reads
-    import torch.distributed as dist
-    backend = dist.get_backend() if (dist.is_available() and dist.is_initialized()) else "none"
     adist.all_reduce_sum_(clean)
     if int(clean.item()) != digest["sum"]:
         raise SystemExit(f"count23_strong: sum(tf) = {digest['sum']}, windows without N = {int(clean.item())}")
@@ -761,16 +824,10 @@ def measure_count23_strong(ix, g, rank, world, dev, total_reads, steps, warmup):
             except Exception as e:  # pragma: no cover
                 one = {"error": f"{type(e).__name__}: {e}"}
         adist.barrier()
-    return {"metric": "reads_per_sec_23mer_count_fixed_mphf", "value": total_reads * steps / wall, "unit": "reads/s",
-            **({"same_workload_on_one_gpu": one} if one else {}),
-            "scaling": "strong", "total_reads": total_reads, "reads_this_rank": hi - lo, "ms_per_step": wall / steps * 1e3,
-            "allreduce_ms": ar_ms, "allreduce_bytes": 4 * ix.n, "collective": f"all_reduce(sum) of int32 tf[{ix.n}]" if backend != "none" else "none (1 rank)",
-            "backend": backend, "collective_ranks": world if backend != "none" else 1,
-            "kernel": "aix_count23_fixed_dev", "kernel_ms_this_rank": k_ms, "windows_this_rank": windows_rank,
-            "counting_backend": {1: "memory-side atomics", 2: "slot stream + LDS histogram", 3: "distinct k-mers first (K1), one probe per distinct k-mer"}.get(ix.info["count23_backend"], "none"),
-            "histogram_passes": ix.info["count23_passes"],
-            "windows_counted_all_ranks": digest["sum"], "windows_without_N_all_ranks": int(clean.item()), "tf_digest": digest,
-            "one_device_rehearsal": bool(os.environ.get("AIX_BENCH_ONE_DEVICE"))}
+    r.update({**({"same_workload_on_one_gpu": one} if one else {}), "allreduce_ms": ar_ms, "allreduce_bytes": 4 * ix.n,
+              "kernel_ms_this_rank": k_ms, "windows_this_rank": windows_rank,
+              "windows_counted_all_ranks": digest["sum"], "windows_without_N_all_ranks": int(clean.item())})
+    return r
 
 
 def run_selftest(a, real_stdout):
@@ -830,7 +887,16 @@ def main():
     ap.add_argument("--bucket-lanes", type=int, default=0, choices=[0, 1, 2, 4, 8], help="lanes that share one bucket read (0: the library's default)")
     ap.add_argument("--gpu-builder", action="store_true", help="build the MPHF on the GPU (parallel peeling) instead of the host")
     ap.add_argument("--query-mix", action="store_true", help="Q_mix: 50 %% genome windows on a random strand + 50 %% random (seed 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU / reference baselines, roofline objects (instrumented "
+                         "launches, gather probes, kernel-alone runs), checks that take runs of their own, and the default workload's secondary "
+                         "block (the other query set, config 4 at 200 M reads, 13-mer counting, the end-to-end file paths)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last step returned as DIR/<name>.npy (float64; a fixed, seeded sample "
+                         "of a larger array; 64 MB at most in all)")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload in ("e2e13", "e2e23", "selftest"):
+        ap.error(f"--dump-outputs: the {a.workload} workload has no timed steps whose arrays it could write")
     if a.probe_path:
         os.environ["AIX_COUNT23_VIA_K1"] = "0"
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -859,26 +925,41 @@ def main():
         local = 0
     torch.cuda.set_device(local)
     dev = local
-    cache = os.path.join(ROOT, ".cache")
+    cache = cache_dir()
+    pf13_default = os.path.join(ROOT, "data", "all_13mers.pf")
+    if not os.environ.get("AIX_PF13") and not os.path.exists(pf13_default) and not os.access(os.path.join(ROOT, "data") if os.path.isdir(os.path.join(ROOT, "data")) else ROOT, os.W_OK):
+        os.environ["AIX_PF13"] = os.path.join(cache, "all_13mers.pf")       # built on first use; the checkout's data/ is read-only here
     out = {"n_gpus": world, "steps": a.steps, "warmup": a.warmup, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "data": "synthetic"}
+    cpu_baseline = a.full and not a.no_cpu_baseline
+    gather_probe = a.full and not a.no_gather_probe
+
+    def dump(arrays):
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, arrays)
 
     if a.workload == "lookup23":
         ix, g, keys, counts, pf = build_index23(a.genome, rank, world, dev, cache, a.gpu_builder)
         del keys, counts
         apply_ab_switches(ix, a)
         qset = "Q_mix" if a.query_mix else "Q_rand"
-        m = measure_lookup23(ix, g, qset, a.queries, rank, world, dev, a.steps, a.warmup, not a.no_gather_probe)
+        m = measure_lookup23(ix, g, qset, a.queries, rank, world, dev, a.steps, a.warmup, gather_probe, a.full)
         q, res = m.pop("_q"), m.pop("_res")
+        if a.dump_outputs:
+            # Q_rand answers are almost all 0: the hits (position in the batch, answer) are written beside the sample
+            hit = torch.nonzero(res).reshape(-1)[: dump_share(3)]
+            dump({"tf": res, "tf_hit_position": hit, "tf_hit": res[hit]})
+            del hit
         value = m["value"]
         out.update({"metric": "kmer_lookups_per_sec_23mer_batch", "value": value, "unit": "lookups/s", "ms_per_step": m["ms_per_step"], "dtype": "u64",
                     "config": {**m["config"], "genome_bp": a.genome, "parallelism": f"replica x{world}"},
-                    "roofline": m["roofline"]})
-        # BASELINE.json.published is {}; the reference's README figure is kept for orientation only (hardware unstated,
-        # measured through Python list[str] on an unshipped index), so vs_baseline stays null
-        out["published_reference_rate"] = {"value": 2.3e6, "unit": "lookups/s", "source": "reference README.md:14,480,596 (BASELINE.md section 1)",
-                                           "ratio": value / 2.3e6}
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+                    **({"roofline": m["roofline"]} if a.full else {})})
+        if a.full:
+            # BASELINE.json.published is {}; the reference's README figure is kept for orientation only (hardware unstated,
+            # measured through Python list[str] on an unshipped index), so vs_baseline stays null
+            out["published_reference_rate"] = {"value": 2.3e6, "unit": "lookups/s", "source": "reference README.md:14,480,596 (BASELINE.md section 1)",
+                                               "ratio": value / 2.3e6}
+        if rank == 0 and world == 1 and cpu_baseline:
             s_ = min(a.cpu_sample, a.queries)
             qs = q[: s_ * 23].cpu().numpy()
             cb = cpu_baseline_lookup23(ix, pf, qs, res[:s_].cpu().numpy().view(np.uint32), os.path.join(cache, "cpu"))
@@ -888,7 +969,7 @@ def main():
             out["cpu_baseline_extra"] = {k: v for k, v in cb.items()}
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         del q, res
-        if not a.no_secondary:
+        if a.full and not a.no_secondary:
             sec = {}
             # the other query set of SURVEY 8(d): Q_mix (50 % hits) when the headline is Q_rand, and the other way round
             try:
@@ -942,7 +1023,7 @@ def main():
             if rank == 0 and world == 1 and not a.no_e2e:
                 try:
                     from aindex_amd.builder import all_13mers_pf_path as pf13_path
-                    sec["e2e13"] = measure_e2e13(dev, cache, a.e2e_gb, pf13_path(), with_reference=not a.no_cpu_baseline)
+                    sec["e2e13"] = measure_e2e13(dev, cache, a.e2e_gb, pf13_path(), with_reference=cpu_baseline)
                 except Exception as e:  # pragma: no cover
                     sec["e2e13"] = {"error": f"{type(e).__name__}: {e}"}
                 try:
@@ -953,7 +1034,7 @@ def main():
 
     elif a.workload == "e2e13":
         from aindex_amd.builder import all_13mers_pf_path as pf13_path
-        r = measure_e2e13(dev, cache, a.e2e_gb, pf13_path(), with_reference=not a.no_cpu_baseline)
+        r = measure_e2e13(dev, cache, a.e2e_gb, pf13_path(), with_reference=cpu_baseline)
         cb = r.pop("cpu_baseline", None)
         out.update({"metric": "reads_per_sec_count_kmers13_tool_end_to_end", "value": r["value"], "unit": "reads/s", "ms_per_step": r["seconds"] * 1e3, "steps": 1, "warmup": 0,
                     "dtype": "u64", "config": {"workload": f"bin/count_kmers13 on a {r['file_bytes'] / 1e9:.2f} GB PLAIN reads file (150 bp, seed 14) in {r['scratch']}: "
@@ -986,6 +1067,7 @@ def main():
         res = torch.empty(a.queries, dtype=torch.int32, device=f"cuda:{dev}")
         step = lambda: ix.tf_ascii_t(q, res)
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"tf": res})
         bpq = 13.0 + 8.0 + 4.0     # what the kernel requests: the query in, ONE 8-byte read of the code-ordered table, the answer out
         achieved = bpq * a.queries / (kern_ms * 1e-3) / 1e9
         out.update({"metric": "kmer_lookups_per_sec_13mer_batch", "value": world * a.queries * a.steps / wall, "unit": "lookups/s",
@@ -1009,13 +1091,14 @@ def main():
             ix.count13_t(reads, tf)
             adist.all_reduce_sum_(tf)
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"tf": tf})
         windows = a.reads * (150 - 12)
         # requested by the three kernels: input once, a 2-byte payload per window written by the split and read by the histogram,
         # the 4^13 u64 table cleared and written through the permutation (4 B per slot read for the permutation)
         requested = a.reads * 151 + windows * 4.0 + (4 ** 13) * (8.0 + 8.0 + 4.0)
         achieved = requested / (kern_ms * 1e-3) / 1e9
         cb = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and cpu_baseline:
             cb = cpu_baseline_count13(ix, reads, min(a.cpu_reads, a.reads), os.path.join(cache, "cpu13"), pf13_path())
         out.update({"metric": "reads_per_sec_13mer_count", "value": world * a.reads * a.steps / wall, "unit": "reads/s",
                     "ms_per_step": wall / a.steps * 1e3, "dtype": "u64",
@@ -1036,7 +1119,7 @@ def main():
         ix, g, keys, counts, pf = build_index23(a.genome, rank, world, dev, cache)
         del keys, counts
         apply_ab_switches(ix, a)
-        r = measure_count23_strong(ix, g, rank, world, dev, a.total_reads, a.steps, a.warmup)
+        r = measure_count23_strong(ix, g, rank, world, dev, a.total_reads, a.steps, a.warmup, a.full, dump)
         out.update({"metric": r["metric"], "value": r["value"], "unit": r["unit"], "scaling": "strong", "ms_per_step": r["ms_per_step"], "dtype": "u64",
                     "config": {"workload": f"configs[3]: 23-mer counting, {a.total_reads} synthetic 150 bp reads (seed 41) in {world} contiguous read ranges, "
                                            "histogram against the fixed MPHF index + all-reduce(sum) of tf[]",
@@ -1044,16 +1127,18 @@ def main():
                                "parallelism": f"reads sharded x{world}, index replicated", "backend": r["backend"], "collective": r["collective"],
                                "counting_backend": r["counting_backend"], "histogram_passes": r["histogram_passes"],
                                "collective_ranks": r["collective_ranks"], "one_device_rehearsal": r["one_device_rehearsal"]},
-                    **({"same_workload_on_one_gpu": r["same_workload_on_one_gpu"]} if "same_workload_on_one_gpu" in r else {}),
-                    "allreduce_ms": r["allreduce_ms"], "allreduce_bytes": r["allreduce_bytes"], "tf_digest": r["tf_digest"],
-                    "windows_counted_all_ranks": r["windows_counted_all_ranks"],
-                    "roofline": {**count23_roofline(ix, r["windows_this_rank"], r["reads_this_rank"], r["kernel_ms_this_rank"]),
-                                 "calls_in_process": a.steps + a.warmup + 2}})
-        tr = load_pmc_traffic("count23", reads_per_launch=r["reads_this_rank"])
-        if tr:
-            out["roofline"]["traffic"] = tr.get("bytes_per_launch")
-            out["roofline"]["traffic_source"] = tr.get("source")
-        if rank == 0 and not a.no_cpu_baseline and world == 1:
+                    "tf_digest": r["tf_digest"]})
+        if a.full:
+            out.update({**({"same_workload_on_one_gpu": r["same_workload_on_one_gpu"]} if "same_workload_on_one_gpu" in r else {}),
+                        "allreduce_ms": r["allreduce_ms"], "allreduce_bytes": r["allreduce_bytes"],
+                        "windows_counted_all_ranks": r["windows_counted_all_ranks"],
+                        "roofline": {**count23_roofline(ix, r["windows_this_rank"], r["reads_this_rank"], r["kernel_ms_this_rank"]),
+                                     "calls_in_process": a.steps + a.warmup + 2}})
+            tr = load_pmc_traffic("count23", reads_per_launch=r["reads_this_rank"])
+            if tr:
+                out["roofline"]["traffic"] = tr.get("bytes_per_launch")
+                out["roofline"]["traffic_source"] = tr.get("source")
+        if rank == 0 and cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_count23(ix, g, pf, dev, cache)
 
     elif a.workload == "count23":
@@ -1063,27 +1148,29 @@ def main():
         tf = torch.zeros(ix.n, dtype=torch.int32, device=f"cuda:{dev}")
         step = lambda: adist.count23_sharded_t(ix, reads, _lib.CANON_TRUE_RC, tf)
         wall, _, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"tf": tf})
         digest = tf_checksum(tf)
-        _, kern_ms, _ = timed_steps(lambda: ix.count23_fixed_t(reads, _lib.CANON_TRUE_RC, tf), 3, 0, dev)     # the kernel alone
         windows = a.reads * (150 - 22)
         backend_ran = ix.info["count23_backend"]                        # of the timed calls (the CPU-baseline leg below counts a short sample through another one)
-        roof23 = count23_roofline(ix, windows, a.reads, kern_ms)
-        cb23 = cpu_baseline_count23(ix, g, pf, dev, cache) if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None
-        out.update({**({"cpu_baseline": cb23} if cb23 else {}),
-                    "metric": "reads_per_sec_23mer_count_fixed_mphf", "value": world * a.reads * a.steps / wall, "unit": "reads/s",
+        out.update({"metric": "reads_per_sec_23mer_count_fixed_mphf", "value": world * a.reads * a.steps / wall, "unit": "reads/s",
                     "ms_per_step": wall / a.steps * 1e3, "dtype": "u64",
                     "config": {"workload": "configs[3]-shaped: 23-mer histogram against a fixed MPHF, 150 bp reads, + all-reduce(sum) of tf[]; per-rank reads fixed (weak)",
                                "reads_per_step_per_gpu": a.reads, "index_keys": ix.n,
                                "counting_backend": {1: "memory-side atomics", 2: "slot stream + LDS histogram",
                                                     3: "distinct k-mers first (K1), one probe per distinct k-mer"}.get(backend_ran, "none")},
-                    "tf_digest": digest,
-                    "roofline": {**roof23,
-                                 "calls_in_process": a.steps + a.warmup + 3 + (1 if cb23 else 0)}})      # for the per-call normalisation of the PMC passes
-        tr = load_pmc_traffic("count23", reads_per_launch=a.reads) if backend_ran == 2 else None      # the PMC passes profile the probe path (--probe-path)
-        if tr:
-            out["roofline"]["traffic"] = tr.get("bytes_per_launch")
-            out["roofline"]["traffic_source"] = tr.get("source")
-        if not a.no_gather_probe and backend_ran != 3:                   # (back end 3 reads no table line per window)
+                    "tf_digest": digest})
+        if a.full:
+            _, kern_ms, _ = timed_steps(lambda: ix.count23_fixed_t(reads, _lib.CANON_TRUE_RC, tf), 3, 0, dev)     # the kernel alone
+            roof23 = count23_roofline(ix, windows, a.reads, kern_ms)
+            cb23 = cpu_baseline_count23(ix, g, pf, dev, cache) if (rank == 0 and world == 1 and cpu_baseline) else None
+            out.update({**({"cpu_baseline": cb23} if cb23 else {}),
+                        "roofline": {**roof23,
+                                     "calls_in_process": a.steps + a.warmup + 3 + (1 if cb23 else 0)}})      # for the per-call normalisation of the PMC passes
+            tr = load_pmc_traffic("count23", reads_per_launch=a.reads) if backend_ran == 2 else None      # the PMC passes profile the probe path (--probe-path)
+            if tr:
+                out["roofline"]["traffic"] = tr.get("bytes_per_launch")
+                out["roofline"]["traffic_source"] = tr.get("source")
+        if gather_probe and backend_ran != 3:                           # (back end 3 reads no table line per window)
             peak_acc = gather_roofline(dev)
             acc = out["roofline"]["lines_per_window"]
             ach = windows * acc / (kern_ms * 1e-3)
@@ -1101,6 +1188,7 @@ def main():
         outp = torch.zeros(a.seqs * per, dtype=torch.int32, device=f"cuda:{dev}")
         step = lambda: ix.coverage_t(seqs, offs, ooffs, a.seqs * per, 0, outp)
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"coverage": outp})
         positions = a.seqs * per
         nzf = int(torch.count_nonzero(outp).item()) / outp.numel()
         if nzf < 0.97:                                              # windows without N are keys: (1 - 0.001)^23 = 0.977; a line over a wrong profile is not a measurement
@@ -1108,7 +1196,7 @@ def main():
         pp = ix.probe_profile()
         achieved = positions * (1.0 + pp["bytes_per_hit_probe"] + 4.0) / (kern_ms * 1e-3) / 1e9     # 1 B of sequence + one probe + the 4-byte answer per position
         cb = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and cpu_baseline:
             cb = cpu_baseline_coverage23(ix, pf, seqs, L, outp, per, 40, os.path.join(cache, "cpucov"))
         out.update({"metric": "sequences_per_sec_coverage_23mer", "value": world * a.seqs * a.steps / wall, "unit": "sequences/s",
                     "ms_per_step": wall / a.steps * 1e3, "dtype": "u64",
@@ -1124,7 +1212,7 @@ def main():
         if tr:
             out["roofline"]["traffic"] = tr.get("bytes_per_launch")
             out["roofline"]["traffic_source"] = tr.get("source")
-        if not a.no_gather_probe:
+        if gather_probe:
             peak_acc = gather_roofline(dev)
             nzf = out["config"]["nonzero_fraction"]
             acc = pp["lines_per_hit_probe"]                          # one bucket line (or 3 MPHF records + the key record) per position
@@ -1147,6 +1235,7 @@ def main():
         outp = torch.zeros(a.seqs * per, dtype=torch.int32, device=f"cuda:{dev}")
         step = lambda: ix.coverage_t(seqs, offs, ooffs, a.seqs * per, 0, outp)
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"coverage": outp})
         positions = a.seqs * per
         nzf13 = int(torch.count_nonzero(outp).item()) / outp.numel()
         if nzf13 < 0.97:                                            # forward reads of the counted genome: every window without N has a count
@@ -1167,6 +1256,7 @@ def main():
         step = lambda: res.__setitem__("o", counting.count_distinct_t(reads, 23, _lib.CANON_REF_X86, 1))
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
         keys_t, counts_t = res["o"]
+        dump({"keys": keys_t, "counts": counts_t})
         windows = a.reads * (150 - 22)
         counted, clean = int(counts_t.to(torch.int64).sum().item()), clean_windows(reads, a.reads, 150, 23)
         if counted != clean:                                        # every window without N is counted exactly once, whatever the number of pieces merged
@@ -1181,7 +1271,7 @@ def main():
         requested = a.reads * 151 + positions_n * per_pos + (24.0 * distinct_n if msd else 12.0 * distinct_n)
         achieved = requested / (kern_ms * 1e-3) / 1e9
         cb = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and cpu_baseline:
             ns = min(a.cpu_reads, a.reads)
             sk, sc = counting.count_distinct_t(reads[: ns * 151], 23, _lib.CANON_REF_X86, 1)
             cb = cpu_baseline_distinct23(reads, ns, sk.cpu().numpy().view(np.uint64), sc.cpu().numpy(), os.path.join(cache, "cpukc"))
@@ -1224,15 +1314,20 @@ def main():
         step = lambda: res.__setitem__("o", ix.positions_fill_t(reads_t))
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
         indices_t, pos_t = res["o"]
-        # host-buffer twin of the same call (PCIe inclusive: reads in, .indices.bin / .index.bin images out), checked equal
-        host_bytes = reads_t.cpu().numpy().tobytes()
-        t0 = time.perf_counter()
-        indices, pos = ix.positions_fill(host_bytes)
-        host_dt = time.perf_counter() - t0
-        assert np.array_equal(indices, indices_t.cpu().numpy().view(np.uint64)) and np.array_equal(pos, pos_t.cpu().numpy().view(np.uint64))
+        dump({"indices": indices_t, "positions": pos_t})
+        positions_total, filled = int(indices_t[-1].item()), int((pos_t != 0).sum().item())
+        twin = {}
+        if a.full:
+            # host-buffer twin of the same call (PCIe inclusive: reads in, .indices.bin / .index.bin images out), checked equal
+            host_bytes = reads_t.cpu().numpy().tobytes()
+            t0 = time.perf_counter()
+            indices, pos = ix.positions_fill(host_bytes)
+            host_dt = time.perf_counter() - t0
+            assert np.array_equal(indices, indices_t.cpu().numpy().view(np.uint64)) and np.array_equal(pos, pos_t.cpu().numpy().view(np.uint64))
+            twin = {"host_buffer_call_ms": host_dt * 1e3, "host_buffer_reads_per_s": a.reads / host_dt}
         cbp = None
         exe = os.path.join(ROOT, "oracle", "_ref", "compute_aindex")
-        if rank == 0 and world == 1 and not a.no_cpu_baseline and os.path.exists(exe):
+        if rank == 0 and world == 1 and cpu_baseline and os.path.exists(exe):
             # the reference's own tool (one thread: its multi-thread slot order is schedule dependent) on a sample of the same
             # reads against the same index files; its .index.bin must equal ours byte for byte. Wall clock of the whole run
             # (it loads the index first: ~1 s of the total).
@@ -1270,15 +1365,14 @@ def main():
         pp = ix.probe_profile()
         msd = os.environ.get("AIX_A2_MSD", "1") != "0" and windows >= (1 << 22)
         grouping_bytes = 44.0 if msd else 4 * 16.0
-        achieved = (windows * (1.0 + 4.0 + pp["bytes_per_hit_probe"] + grouping_bytes) + 8.0 * int(indices[-1])) / (kern_ms * 1e-3) / 1e9
+        achieved = (windows * (1.0 + 4.0 + pp["bytes_per_hit_probe"] + grouping_bytes) + 8.0 * positions_total) / (kern_ms * 1e-3) / 1e9
         out.update({**({"cpu_baseline": cbp} if cbp else {}),
                     "metric": "reads_per_sec_positions_fill_23mer", "value": world * a.reads * a.steps / wall, "unit": "reads/s",
                     "ms_per_step": wall / a.steps * 1e3, "dtype": "u64",
                     "config": {"workload": "A1+A2: positions index of 150 bp reads (resident in HBM) against the fixed 23-mer index; tf = occurrences in the "
                                            + ("reads (every found window placed)" if a.positions_tf == "reads" else "genome (first occurrences only)"),
                                "positions_tf": a.positions_tf,
-                               "reads": a.reads, "windows": windows, "positions_total": int(indices[-1]), "filled": int((pos != 0).sum()),
-                               "host_buffer_call_ms": host_dt * 1e3, "host_buffer_reads_per_s": a.reads / host_dt},
+                               "reads": a.reads, "windows": windows, "positions_total": positions_total, "filled": filled, **twin},
                     "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                                  "kernel": ("k_a2_probe + k_k1_split<A2Keys> + k_k1_count + k_k1_scatter<u64> + k_a2_final (two-level MSD partition + per-bucket LDS stage)"
                                             if msd else "k_a2_probe + rocprim radix_sort_pairs + k_a2_first/k_a2_place"),
@@ -1304,6 +1398,7 @@ def main():
         res = {}
         step = lambda: res.__setitem__("o", counting.normalize_t(raw, _lib.FMT_FASTQ, 0))
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"plain": res["o"]})
         assert res["o"].numel() == a.reads * 151
         nbytes = raw.numel()
         out.update({"metric": "bytes_per_sec_fastq_normalise", "value": nbytes * a.steps / wall, "unit": "B/s", "ms_per_step": wall / a.steps * 1e3, "dtype": "u8",
@@ -1321,6 +1416,7 @@ def main():
         sp = vp(torch.cuda.current_stream().cuda_stream)
         step = lambda: check(lib().aix_bench_gather_dev(vp(table.data_ptr()), nel, a.elem, a.unroll, a.queries, 99, vp(sink.data_ptr()), sp))
         wall, kern_ms, _ = timed_steps(step, a.steps, a.warmup, dev)
+        dump({"sink": sink})
         rate = a.queries / (kern_ms * 1e-3)
         out.update({"metric": "random_gather_accesses_per_sec", "value": rate, "unit": "accesses/s", "ms_per_step": wall / a.steps * 1e3, "dtype": f"u{a.elem * 8}",
                     "config": {"workload": f"uniform-random {a.elem}-byte gather over {a.table_mib} MiB, {a.unroll} in flight per lane", "accesses": a.queries},

@@ -67,11 +67,11 @@ def test_builder_rejects_duplicates():
         builder.build_pf(["ACGTACGTACGTACGTACGTACG"] * 4)
 
 
-def test_builder_random_sets_are_minimal_perfect():
+def test_builder_random_sets_are_minimal_perfect(tmp_path):
     for n, seed in ((1, 1), (3, 2), (37, 3), (5000, 4)):   # n=2 gives hash domain 1: never peelable, also in the reference
         kmers = np.unique(synth.random_kmers_ascii(seed, n, 23), axis=0)
         pf = builder.build_pf_fixed(kmers, 23)
-        path = f"/tmp/aix_t_{n}.pf"
+        path = str(tmp_path / f"aix_t_{n}.pf")
         open(path, "wb").write(pf)
         m = O.OracleMphf(path)
         got = sorted(m.lookup(bytes(k)) for k in kmers)
