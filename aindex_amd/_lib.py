@@ -21,6 +21,8 @@ AIX_OK = 0
 AIX_ERR_CONFLICT = -12
 AIX_ERR_ARG = -1
 AIX_ERR_FORMAT = -3
+AIX_ERR_NOMEM = -4
+AIX_ERR_UNSUPPORTED = -6
 FMT_AUTO, FMT_PLAIN, FMT_FASTA, FMT_FASTQ = -1, 0, 1, 2
 CANON_NONE, CANON_REF_X86, CANON_TRUE_RC = 0, 1, 2
 TOTAL_13MERS = 4 ** 13
@@ -38,7 +40,8 @@ class Info(C.Structure):
                 ("hash_domain", C.c_uint64), ("seed", C.c_uint64), ("bitpairs", C.c_uint64),
                 ("device_bytes", C.c_uint64), ("canonical_only", C.c_uint32), ("bucket_table", C.c_uint32),
                 ("buckets", C.c_uint64), ("bucket_unfiled_keys", C.c_uint64), ("bucket_lanes", C.c_uint32), ("absence_filter_words", C.c_uint32),
-                ("minimizer_lines", C.c_uint64), ("minimizer_unfiled_keys", C.c_uint64), ("count23_backend", C.c_uint32), ("count23_passes", C.c_uint32), ("positions_backend", C.c_uint32), ("reserved0", C.c_uint32)]
+                ("minimizer_lines", C.c_uint64), ("minimizer_unfiled_keys", C.c_uint64), ("count23_backend", C.c_uint32), ("count23_passes", C.c_uint32), ("positions_backend", C.c_uint32), ("reserved0", C.c_uint32),
+                ("aindex_attached", C.c_uint32), ("ridx_on_device", C.c_uint32), ("aindex_entries", C.c_uint64), ("ridx_reads", C.c_uint64)]
 
 
 class IngestStats(C.Structure):
@@ -105,6 +108,15 @@ SIGNATURES = {
     "aix_positions_total": (i32, [vp, C.POINTER(u64)]),
     "aix_positions_fill_dev": (i32, [vp, vp, u64, u64, vp, vp, u64, vp]),
     "aix_positions_bucket_counts": (i32, [vp, vp, u64, i32, vp]),
+    "aix_aindex_attach": (i32, [vp, vp, vp, u64]),
+    "aix_aindex_attach_dev": (i32, [vp, vp, vp, u64, vp]),
+    "aix_aindex_detach": (i32, [vp]),
+    "aix_ridx_sorted_disjoint": (i32, [vp, u64]),
+    "aix_ridx_attach": (i32, [vp, vp, u64]),
+    "aix_positions_query": (i32, [vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "aix_positions_query_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_positions_locate": (i32, [vp, vp, u64, vp, vp]),
+    "aix_positions_locate_dev": (i32, [vp, vp, u64, vp, vp, vp]),
     "aix_positions_start": (i32, [vp, u64, C.POINTER(u64)]),
     "aix_positions_start_k": (i32, [vp, u64, i32, C.POINTER(u64)]),
     "aix_index_scatter_shard_codes_dev": (i32, [vp, u64, vp, vp, u64, u64, i32, vp, vp, vp, vp]),

@@ -310,6 +310,30 @@ class AIndex:
             hits.setdefault(self.get_rid(p), []).append(p - self.get_start(p))
         return hits
 
+    def get_positions_batch(self, kmers) -> List[List[int]]:
+        """[get_positions(s) for s in kmers], one GPU call."""
+        return self._wrapper.get_positions_batch(kmers)
+
+    def get_positions_array(self, kmers, max_per_kmer: int = 0, locate: bool = False):
+        """CSR arrays (offsets, positions[, rid, offset_in_read]); see AindexWrapper.get_positions_array."""
+        return self._wrapper.get_positions_array(kmers, max_per_kmer, locate)
+
+    def get_rid2poses_batch(self, kmers) -> List[dict]:
+        """[get_rid2poses(s) for s in kmers]: positions and reads resolved in one GPU call."""
+        w = self._wrapper
+        k = 13 if w._is_13mer_mode else 23
+        flat, keep = w._split_fixed(kmers, k)
+        out = [{} for _ in range(len(kmers))]
+        if keep.shape[0] == 0:
+            return out
+        off, _, rid, loc = w.get_positions_array(flat, 0, True)
+        off, rid, loc = off.tolist(), rid.tolist(), loc.tolist()
+        for j, i in enumerate(keep.tolist()):
+            hits = out[i]
+            for e in range(off[j], off[j + 1]):
+                hits.setdefault(rid[e], []).append(loc[e])
+        return out
+
     def get_reads_by_kmer(self, kmer: str, max_reads: int = 100) -> List[str]:
         """aindex.py:162-166 over get_reads_se_by_kmer (see the wrapper for the one documented deviation)."""
         if not self._wrapper.aindex_loaded:

@@ -180,6 +180,7 @@ static void destroy(aix_index* h) {
     if (h->perm13) (void)hipFree(h->perm13);
     if (h->scratch13) (void)hipFree(h->scratch13);
     if (h->work13) (void)hipFree(h->work13);
+    posquery_release(h);
     if (h->pipe) { free_host_pipe(h->pipe); h->pipe = nullptr; }
     if (h->work13_done) (void)hipEventDestroy(h->work13_done);
     for (int i = 0; i < 2; ++i) { if (h->probe_ev[i]) (void)hipEventDestroy(h->probe_ev[i]); if (h->hist_ev[i]) (void)hipEventDestroy(h->hist_ev[i]); }
@@ -558,6 +559,10 @@ extern "C" int aix_index_info(const aix_index_t* h, aix_info_t* info) {
     info->count23_backend = h->c23_backend;
     info->count23_passes = h->c23_passes;
     info->positions_backend = h->a2_backend;
+    info->aindex_attached = h->ai_attached ? (h->ai_owned ? 1u : 2u) : 0u;
+    info->ridx_on_device = h->rx_attached ? 1u : 0u;
+    info->aindex_entries = h->ai_attached ? h->ai_total : 0;
+    info->ridx_reads = h->rx_attached ? h->rx_n : 0;
     return AIX_OK;
 }
 

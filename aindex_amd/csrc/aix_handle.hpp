@@ -110,6 +110,14 @@ struct aix_index {
     uint32_t a2_backend = 0;                       // the last positions fill: bit 0 = stable radix sort, bit 1 = MSD partition (per piece)
     uint32_t c23_backend = 0, c23_passes = 0;     // the last aix_count23_fixed*: 1 = memory-side atomics, 2 = slot stream + LDS histogram; passes over the slot stream
     bool c13_atomics = false, c13_added = false;   // state of a 13-mer count in progress (between count13_begin_locked and count13_end_locked)
+    // the attached positions index (aix_posquery.hip): the .indices.bin / .index.bin images in HBM, and the .ridx intervals as three arrays
+    uint64_t* ai_indices = nullptr;                // n + 1 offsets
+    uint64_t* ai_positions = nullptr;              // ai_total entries, 1-based, 0 = empty slot
+    uint64_t ai_total = 0;
+    bool ai_attached = false, ai_owned = false;    // owned: copied by aix_aindex_attach (freed on detach); else borrowed from the caller
+    uint64_t* rx = nullptr;                        // starts[rx_n], ends[rx_n], rids[rx_n]
+    uint64_t rx_n = 0;
+    bool rx_attached = false;
 
     // the slot-stream consumers (count23's histogram path, the positions probe): two lanes per bucket line unless the caller chose a width
     IndexDev dev_slots() const {
@@ -149,6 +157,9 @@ struct aix_index {
         return d;
     }
 };
+
+// releases the attached positions index and read intervals (aix_posquery.hip); the caller has switched to the handle's device
+void posquery_release(aix_index* h);
 
 // K13 in steps (aix_api.hip); the caller holds h->count_mutex from begin to end
 int count13_begin_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s);

@@ -323,6 +323,91 @@ class Index:
               "aix_positions_fill_shard")
         return pos
 
+    # ---- batch position queries over an attached positions index (aix_posquery.hip) -----------
+    def attach_aindex(self, indices, positions):
+        """Copy the .indices.bin (n + 1) / .index.bin images (numpy arrays or memmaps, uint64) to HBM for positions_batch."""
+        ind = np.ascontiguousarray(indices, dtype=np.uint64)
+        pos = np.ascontiguousarray(positions, dtype=np.uint64)
+        if ind.shape[0] != self.n + 1:
+            raise ValueError(f"indices holds {ind.shape[0]} entries, the handle needs n + 1 = {self.n + 1}")
+        check(lib().aix_aindex_attach(self._h, _np_ptr(ind), _np_ptr(pos) if pos.shape[0] else None, pos.shape[0]), "aix_aindex_attach")
+        self._aindex_keep = None
+
+    def attach_aindex_t(self, indices_t, positions_t):
+        """Borrow device tensors (int64 bit patterns, e.g. the outputs of positions_fill_t); they are kept alive by this object."""
+        self._chk_dev(indices_t)
+        if positions_t.numel():
+            self._chk_dev(positions_t)
+        if indices_t.numel() != self.n + 1:
+            raise ValueError(f"indices holds {indices_t.numel()} entries, the handle needs n + 1 = {self.n + 1}")
+        check(lib().aix_aindex_attach_dev(self._h, vp(indices_t.data_ptr()), vp(positions_t.data_ptr()) if positions_t.numel() else None,
+                                          positions_t.numel(), _stream_ptr(self.device)), "aix_aindex_attach_dev")
+        self._aindex_keep = (indices_t, positions_t)
+
+    def detach_aindex(self):
+        check(lib().aix_aindex_detach(self._h), "aix_aindex_detach")
+        self._aindex_keep = None
+
+    def attach_ridx(self, triples) -> bool:
+        """Read intervals (rid, start, end per read) to HBM. False when they are not sorted and disjoint: nothing is attached then and
+        locate=True / locate() are refused."""
+        t = np.ascontiguousarray(triples, dtype=np.uint64).reshape(-1, 3)
+        st = lib().aix_ridx_attach(self._h, _np_ptr(t) if t.shape[0] else None, t.shape[0])
+        if st == _lib.AIX_ERR_UNSUPPORTED:
+            return False
+        check(st, "aix_ridx_attach")
+        return True
+
+    @staticmethod
+    def _take(p, n: int) -> np.ndarray:
+        try:
+            return np.frombuffer(C.string_at(p, 8 * n), dtype=np.uint64).copy() if n else np.zeros(0, np.uint64)
+        finally:
+            lib().aix_free(p)
+
+    def positions_batch(self, kmers, max_per_kmer: int = 0, locate: bool = False):
+        """(offsets[N + 1], positions[offsets[N]][, rid, offset_in_read]) as numpy uint64: list i = positions[offsets[i]:offsets[i + 1]] =
+        get_positions(kmer i), cut to max_per_kmer entries when that is > 0. `kmers`: what tf_ascii takes."""
+        a = _as_u8(kmers, self.k)
+        n = a.shape[0] // self.k
+        po, pp, pr, pl = vp(), vp(), vp(), vp()
+        check(lib().aix_positions_query(self._h, _np_ptr(a) if n else None, n, max_per_kmer, C.byref(po), C.byref(pp),
+                                        C.byref(pr) if locate else None, C.byref(pl) if locate else None), "aix_positions_query")
+        offsets = self._take(po, n + 1)
+        total = int(offsets[n])
+        out = (offsets, self._take(pp, total))
+        if locate:
+            out += (self._take(pr, total), self._take(pl, total))
+        return out
+
+    def positions_batch_t(self, kmers_t, max_per_kmer: int = 0, locate: bool = False):
+        """The same on torch tensors of the handle's device (int64 bit patterns out), on torch's current stream: one sizing call,
+        then one filling call into tensors of exactly that size."""
+        import torch
+        self._chk_dev(kmers_t)
+        n = kmers_t.numel() // self.k
+        dev = kmers_t.device
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            q = vp(kmers_t.data_ptr()) if n else None
+            check(lib().aix_positions_query_dev(self._h, q, n, max_per_kmer, vp(offsets.data_ptr()), None, None, None, 0, C.byref(total),
+                                                _stream_ptr(self.device)), "aix_positions_query_dev")
+            t = total.value
+            outs = [torch.empty(max(t, 1), dtype=torch.int64, device=dev)[:t] for _ in range(3 if locate else 1)]
+            if t:
+                check(lib().aix_positions_query_dev(self._h, q, n, max_per_kmer, vp(offsets.data_ptr()), vp(outs[0].data_ptr()),
+                                                    vp(outs[1].data_ptr()) if locate else None, vp(outs[2].data_ptr()) if locate else None, t,
+                                                    C.byref(total), _stream_ptr(self.device)), "aix_positions_query_dev")
+        return (offsets, *outs)
+
+    def locate(self, pos):
+        """(rid, start) per position: get_rid / get_start for a batch (numpy uint64 in and out)."""
+        p = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        rid, start = np.empty(p.shape[0], np.uint64), np.empty(p.shape[0], np.uint64)
+        check(lib().aix_positions_locate(self._h, _np_ptr(p), p.shape[0], _np_ptr(rid), _np_ptr(start)), "aix_positions_locate")
+        return rid, start
+
     # ---- HBM-resident (torch) entry points: asynchronous on torch's current stream ------------
     def _chk_dev(self, t):
         if not t.is_cuda or t.device.index != self.device:

@@ -628,6 +628,121 @@ class AindexWrapper:
         seg = np.asarray(self._positions[int(self._indices[h]):int(self._indices[h + 1])])
         return (seg[seg != 0] - np.uint64(1)).tolist()
 
+    # ---- batch positions (one GPU call per batch; the single-k-mer methods above are untouched) ---------------------
+    @staticmethod
+    def _split_fixed(items, k: int):
+        """Host-only helper of the list surface: (packed bytes of the items that are exactly k bytes long, their indices). The other
+        items keep an empty answer at their place, as get_positions gives them."""
+        bs = [_enc(s) for s in items]
+        keep = [i for i, b in enumerate(bs) if len(b) == k]
+        return b"".join(bs[i] for i in keep), np.asarray(keep, dtype=np.int64)
+
+    @staticmethod
+    def _spread_lists(n_items: int, keep: np.ndarray, offsets: np.ndarray, values) -> list:
+        """list of n_items lists: item keep[j] gets values[offsets[j]:offsets[j + 1]], every other item []."""
+        out = [[] for _ in range(n_items)]
+        flat = values.tolist() if isinstance(values, np.ndarray) else values
+        off = offsets.tolist()
+        for j, i in enumerate(keep.tolist()):
+            out[i] = flat[off[j]:off[j + 1]]
+        return out
+
+    def _batch_index(self):
+        """The handle and host arrays behind the batch calls of the current mode, or None when nothing is loaded (every list is [])."""
+        if self._is_13mer_mode:
+            if self._ix13 is None or getattr(self, "_positions13", None) is None:
+                return None
+            return self._ix13, self._indices13, self._positions13, 13
+        if self._ix23 is None or getattr(self, "_positions", None) is None:
+            return None
+        return self._ix23, self._indices, self._positions, 23
+
+    def _attach_for_batch(self, want_ridx: bool = False):
+        """Lazy upload of the loaded positions files (and the .ridx intervals) to the handle, once per loaded file set."""
+        b = self._batch_index()
+        if b is None:
+            return None
+        ix, ind, pos, k = b
+        key = getattr(self, "_attached_key", None)
+        if key is None or key[0] is not ix or key[1] is not ind or key[2] is not pos:
+            try:
+                ix.attach_aindex(ind, pos)
+            except _lib.AixError as e:
+                if e.status == _lib.AIX_ERR_NOMEM:
+                    raise RuntimeError(f"the positions index ({8 * (int(pos.shape[0]) + int(ind.shape[0]))} bytes) does not fit the device; "
+                                       "the single-k-mer methods still work") from e
+                raise
+            self._attached_key = (ix, ind, pos)
+            self._attached_ridx = None
+        if want_ridx:
+            starts = getattr(self, "_ridx_start", None)
+            have = getattr(self, "_attached_ridx", None)
+            if have is None or have[0] is not starts:
+                ok = False
+                if starts is not None and getattr(self, "_ridx_sorted", False):
+                    ok = ix.attach_ridx(np.stack([self._ridx_rid, starts, self._ridx_end], axis=1))
+                self._attached_ridx = (starts, ok)
+        return ix, k
+
+    def _ridx_on_device(self) -> bool:
+        return bool(getattr(self, "_attached_ridx", None) and self._attached_ridx[1])
+
+    def get_positions_array(self, kmers, max_per_kmer: int = 0, locate: bool = False):
+        """CSR form of get_positions for a packed batch (bytes / 'S<k>' / (N, k) uint8 / one joined str) or a list of k-character items:
+        (offsets uint64[N + 1], positions uint64[offsets[N]]) and, with locate=True, (rid, offset_in_read) per occurrence — get_rid(p) and
+        p - get_start(p); offset_in_read is int64 (a position one before its read's start gives -1, as the subtraction does)."""
+        k = 13 if self._is_13mer_mode else 23
+        flat = self._packed(kmers, k)
+        if flat is None and isinstance(kmers, (list, tuple)) and len(kmers) == 0:
+            flat = b""
+        if flat is None:
+            flat = self._join_fixed(kmers, k) if not isinstance(kmers, (str, bytes, bytearray, memoryview, np.ndarray)) else None
+            if flat is None:
+                raise ValueError(f"get_positions_array needs a batch of {k}-character k-mers; use get_positions_batch for mixed lengths")
+        from .engine import _as_u8
+        a = _as_u8(flat, k)
+        n = a.shape[0] // k
+        at = self._attach_for_batch(locate)
+        if at is None:
+            z = np.zeros(0, np.uint64)
+            return (np.zeros(n + 1, np.uint64), z) + ((z, z.view(np.int64)) if locate else ())
+        ix, _ = at
+        if not locate:
+            return ix.positions_batch(a, max_per_kmer)
+        if self._ridx_on_device():
+            off, pos, rid, loc = ix.positions_batch(a, max_per_kmer, True)
+            return off, pos, rid, loc.view(np.int64)
+        off, pos = ix.positions_batch(a, max_per_kmer)
+        rid, start = self.get_rid_start_batch(pos)
+        return off, pos, rid, pos.astype(np.int64) - start.astype(np.int64)
+
+    def get_positions_batch(self, kmers: List[str]) -> List[List[int]]:
+        """[get_positions(s) for s in kmers] in one GPU call; items whose length is not the mode's k give [] in place."""
+        k = 13 if self._is_13mer_mode else 23
+        if isinstance(kmers, (str, bytes, bytearray, memoryview, np.ndarray)):
+            off, pos = self.get_positions_array(kmers)
+            return self._spread_lists(off.shape[0] - 1, np.arange(off.shape[0] - 1), off, pos)
+        flat, keep = self._split_fixed(kmers, k)
+        at = self._attach_for_batch()
+        if at is None or keep.shape[0] == 0:
+            return [[] for _ in range(len(kmers))]
+        off, pos = at[0].positions_batch(flat)
+        return self._spread_lists(len(kmers), keep, off, pos)
+
+    def get_rid_start_batch(self, positions):
+        """(rid, start) uint64 arrays: get_rid(p) and get_start(p) for every p. On the GPU when the loaded .ridx is sorted and disjoint
+        (what compute_reads writes), else interval by interval on the host as get_rid does."""
+        p = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1)
+        if not self.aindex_loaded or getattr(self, "_ridx_start", None) is None or self.n_reads == 0:
+            return np.zeros(p.shape[0], np.uint64), np.zeros(p.shape[0], np.uint64)
+        at = self._attach_for_batch(True)
+        if at is not None and self._ridx_on_device():
+            return at[0].locate(p)
+        hit = [self._interval(int(x)) for x in p]
+        rid = np.array([int(self._ridx_rid[i]) if i is not None else 0 for i in hit], dtype=np.uint64)
+        start = np.array([int(self._ridx_start[i]) if i is not None else 0 for i in hit], dtype=np.uint64)
+        return rid, start
+
     def get_reads_se_by_kmer(self, kmer: str, max_reads: int = 100) -> List[str]:
         """Reads that hold an indexed occurrence of the k-mer, each read once, at most max_reads. The reference's version
         (:857-911) walks `positions[kmer_id] .. positions[kmer_id + 1]` over `indices[]` — its two arrays crossed — with the

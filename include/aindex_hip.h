@@ -71,6 +71,10 @@ typedef struct {
     uint32_t positions_backend; /* the last aix_positions_fill* call: bit 0 = a piece was grouped by the stable radix sort (short buffers, more than
                                    2^30 slots, workspace did not fit), bit 1 = by the MSD partition; 0 none yet                    */
     uint32_t reserved0;
+    uint32_t aindex_attached; /* positions index for aix_positions_query*: 0 none, 1 copied by aix_aindex_attach, 2 borrowed by aix_aindex_attach_dev */
+    uint32_t ridx_on_device;  /* 1 if aix_ridx_attach found the read intervals sorted and disjoint and put them into HBM                  */
+    uint64_t aindex_entries;  /* entries of the attached positions array (8 bytes each, plus 8 * (n + 1) of offsets)                      */
+    uint64_t ridx_reads;      /* attached read intervals (24 bytes each)                                                                  */
 } aix_info_t;
 
 const char* aix_version(void);
@@ -375,6 +379,52 @@ int aix_file_write(const char* path, const void* data, uint64_t bytes);
 /* The .ridx file ("rid\tstart\tend" per read) that compute_reads writes and AindexWrapper::load_reads_index reads back
  * (python_wrapper.cpp:261-279: `fin >> rid >> start >> end` until it fails). *out = 3 * n values, malloc'd (aix_free). */
 int aix_ridx_load(const char* path, uint64_t* n_out, uint64_t** out);
+
+/* ------------------------------------------------------------------------------------------
+ * Batch position queries: N k-mers -> every occurrence (CSR), optionally with read id and offset in the read.
+ * replaces, N at a time, AindexWrapper::get_positions / get_positions_13mer (python_wrapper.cpp:800-831, 1070-1100) with the
+ *          strand rule of PHASH_MAP::get_pfid (hash.hpp:150-170), and get_rid / get_start (python_wrapper.cpp:757-789) over
+ *          IntervalTree::query (:66-74); aindex.py:333-341 (get_rid2poses) and :162-166 (get_reads_by_kmer) loop over those.
+ * The positions index is attached to the handle first and stays in HBM. All entry points accept 23- and 13-mer handles.
+ * ------------------------------------------------------------------------------------------ */
+/* The .indices.bin (n + 1 offsets) and .index.bin (`total` entries) images that AindexWrapper::load_aindex maps
+ * (python_wrapper.cpp:361-402), copied to HBM. Checked on the device: indices[0] == 0, ascending, indices[n] <= total, else
+ * AIX_ERR_FORMAT. AIX_ERR_NOMEM when the copy does not fit (nothing is kept; an earlier attachment stays). Replaces an earlier attachment. */
+int aix_aindex_attach(aix_index_t* h, const uint64_t* indices, const uint64_t* positions, uint64_t total);
+/* The same (python_wrapper.cpp:361-402) for images already in HBM, e.g. the outputs of aix_positions_fill_dev: borrowed, the caller keeps
+ * them alive until detach / close. The same check runs on `stream`; the call returns after it. */
+int aix_aindex_attach_dev(aix_index_t* h, const uint64_t* d_indices, const uint64_t* d_positions, uint64_t total, void* stream);
+/* Drops the positions index and the read intervals (the reference unmaps in ~AindexWrapper, python_wrapper.cpp:160-226);
+ * aix_index_close does the same. */
+int aix_aindex_detach(aix_index_t* h);
+/* The intervals of a .ridx file (aix_ridx_load layout: rid, start, end per read; AindexWrapper::load_reads_index,
+ * python_wrapper.cpp:261-279). Host only, no device needed: 1 if every end >= start and every start > the end before it —
+ * what compute_reads writes — so that the first match of IntervalTree::query (:66-74) can be found by bisection; else 0. */
+int aix_ridx_sorted_disjoint(const uint64_t* triples, uint64_t n_reads);
+/* Puts such intervals (python_wrapper.cpp:261-279) into HBM for aix_positions_query* / aix_positions_locate*: AIX_OK and
+ * aix_info_t::ridx_on_device = 1. Intervals that are not sorted and disjoint: AIX_ERR_UNSUPPORTED, nothing attached (the caller resolves
+ * reads on the host). */
+int aix_ridx_attach(aix_index_t* h, const uint64_t* triples, uint64_t n_reads);
+/* get_positions (python_wrapper.cpp:800-831 / 1070-1100) for N k-mers of the handle's k (N * k bytes, host): list i =
+ * (*positions_out)[(*offsets_out)[i] .. (*offsets_out)[i + 1]) = the non-zero entries of positions[indices[h] .. min(indices[h + 1], total))
+ * minus one, in slot order, cut to the first max_per_kmer entries (0: all). 23-mers: h by get_pfid (hash.hpp:150-170), empty unless
+ * h < n and checker[h] is the code of the strand looked up; 13-mers: exactly 13 upper-case A/C/G/T, forward strand. rid_out / local_out
+ * (both or neither; need aix_ridx_attach): per entry get_rid(pos) and pos - get_start(pos) (python_wrapper.cpp:757-789; 0 and pos when
+ * no interval matches). The outputs are malloc'd (aix_free); N = 0 gives offsets = {0}. AIX_ERR_ARG when nothing is attached. */
+int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N, uint64_t max_per_kmer, uint64_t** offsets_out,
+                        uint64_t** positions_out, uint64_t** rid_out /* nullable */, uint64_t** local_out /* nullable */);
+/* device-resident twin of the above (python_wrapper.cpp:800-831). d_kmers: N * k bytes; d_offsets (N + 1) and *total_out (host) =
+ * offsets[N] are always filled; the entries are written only if *total_out <= cap (entries each of d_positions / d_rid / d_local hold),
+ * never at or beyond cap, and the call returns AIX_OK either way: size with cap = 0, then call again (the convention of
+ * aix_positions_fill with positions_out == NULL). Returns after the work has completed on `stream`. */
+int aix_positions_query_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint64_t max_per_kmer, uint64_t* d_offsets,
+                            uint64_t* d_positions, uint64_t* d_rid /* nullable */, uint64_t* d_local /* nullable */, uint64_t cap,
+                            uint64_t* total_out, void* stream);
+/* get_rid / get_start (python_wrapper.cpp:757-789) for N arbitrary positions: the first interval in file order with
+ * start <= pos + 1 and end + 1 >= pos (:66-74); rid = start = 0 when there is none (also beyond the file). Needs aix_ridx_attach
+ * (AIX_ERR_ARG otherwise). The _dev twin is asynchronous on `stream`. */
+int aix_positions_locate(aix_index_t* h, const uint64_t* pos, uint64_t N, uint64_t* rid_out, uint64_t* start_out);
+int aix_positions_locate_dev(aix_index_t* h, const uint64_t* d_pos, uint64_t N, uint64_t* d_rid_out, uint64_t* d_start_out, void* stream);
 /* The same normalisation for a buffer already in HBM (byte-identical output; the readers are finite-state transducers,
  * resolved with a parallel scan of per-chunk transition functions). format must be PLAIN, FASTA or FASTQ; d_out holds
  * len+1 bytes; *out_len is a HOST pointer; the call synchronises the stream. */
