@@ -22,6 +22,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "aix_env.hpp"
 #include "aix_internal.hpp"
 #include "aix_msd.hpp"
 
@@ -298,7 +299,7 @@ static inline uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
 static inline unsigned grid256(uint64_t work) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((work + 255) / 256, 1), 8192); }
 
 bool a2_msd_eligible(uint64_t nwin, uint64_t n) {
-    if (const char* e = getenv("AIX_A2_MSD")) return atoi(e) != 0 && nwin > 0 && nwin <= (1ull << 31) && n > 0 && n <= (1ull << 30);      // A/B and test switch
+    if (env_flag("AIX_A2_MSD")) return env_bool("AIX_A2_MSD", false) && nwin > 0 && nwin <= (1ull << 31) && n > 0 && n <= (1ull << 30);      // A/B and test switch
     return nwin >= (1ull << 22) && nwin <= (1ull << 31) && n > 0 && n <= (1ull << 30);                                                    // short buffers: fewer launches win
 }
 
@@ -312,16 +313,14 @@ hipError_t a2_msd_place(const IndexDev& ix, const uint32_t* keys, uint64_t nwin,
     while (Bh < 32 && ((n - 1) >> Bh)) ++Bh;                   // slots are < 2^Bh
     // a bucket spans 2^rbits slots and should hold ~10^3 pairs (at most nwin / n pairs per slot on average)
     uint32_t rbits = 0;
-    uint64_t target = 1024;
-    if (const char* e = getenv("AIX_A2_TARGET")) { const long v = atol(e); if (v > 0) target = (uint64_t)v; }       // A/B switch
+    const uint64_t target = (uint64_t)env_int("AIX_A2_TARGET", 1, LONG_MAX, 1024);       // A/B switch
     while (rbits < (uint32_t)A2_RBITS_MAX && ((nwin << (rbits + 1)) / n) <= target) ++rbits;
     int D2 = (int)Bh - K1_PBITS - (int)rbits;
     if (D2 > 11) { D2 = 11; rbits = Bh - K1_PBITS - 11; }
     if (D2 < 1) { D2 = 1; rbits = Bh - K1_PBITS - 1; }
     const uint32_t s2 = 32 + rbits, s1 = s2 + (uint32_t)D2, nb2 = 1u << D2;
     const uint32_t nbuckets = (uint32_t)K1_P * nb2;
-    uint32_t cap_e = A2_CAP;
-    if (const char* e = getenv("AIX_A2_TEST_CAP")) { const long v = atol(e); if (v > 0 && v < A2_CAP) cap_e = (uint32_t)v; }   // test hook: force the set-aside path
+    const uint32_t cap_e = (uint32_t)env_int("AIX_A2_TEST_CAP", 1, A2_CAP - 1, A2_CAP);   // test hook: force the set-aside path
     const uint64_t ntiles = (nwin + K1_TILE - 1) / K1_TILE;
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, K1_MAXGRID);
     const uint32_t region = (uint32_t)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P);
@@ -338,7 +337,7 @@ hipError_t a2_msd_place(const IndexDev& ix, const uint32_t* keys, uint64_t nwin,
                    o_ob = o_bbase + up256(4ull * (nbuckets + 1)), o_oo = o_ob + up256(4ull * nbuckets), o_rem = o_oo + up256(8ull * nbuckets),
                    o_parts = o_rem + up256(8ull * nwin), total = o_parts + 8ull * cap * K1_CH;
     uint8_t* w = nullptr;
-    hipError_t e = getenv("AIX_A2_TEST_NOMEM") ? hipErrorOutOfMemory : pool_alloc((void**)&w, total);      // test hook: the workspace "does not fit"
+    hipError_t e = env_flag("AIX_A2_TEST_NOMEM") ? hipErrorOutOfMemory : pool_alloc((void**)&w, total);      // test hook: the workspace "does not fit"
     if (e != hipSuccess) { if (untouched) *untouched = true; return e; }     // the workspace did not fit: the caller may take the sort path, nothing was written
     A2Over* over = (A2Over*)w;
     uint16_t* dir_part = (uint16_t*)(w + o_dirp);

@@ -16,6 +16,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "aix_env.hpp"
 #include "aix_internal.hpp"
 
 namespace aix {
@@ -397,8 +398,8 @@ struct C13Shape { int tb, wpt; unsigned maxgrid; };
 static inline C13Shape c13_shape() {
     static const C13Shape sh = [] {
         C13Shape v{1024, 32, 256};                                // one 152 KiB workgroup per CU, one per CU in the grid: measured faster than two smaller ones and than 512..1024 workgroups (4.23 / 4.28 / 4.32 / 4.33 ms at 256 / 512 / 768 / 1024)
-        if (const char* e = getenv("AIX_C13_SHAPE")) { if (e[0] == 's') v = C13Shape{512, 24, 1024}; }
-        if (const char* e = getenv("AIX_C13_GRID")) { const int g = atoi(e); if (g >= 1 && g <= 4096) v.maxgrid = (unsigned)g; }      // A/B switch: workgroups of the split
+        if (env_char("AIX_C13_SHAPE") == 's') v = C13Shape{512, 24, 1024};
+        v.maxgrid = (unsigned)env_int("AIX_C13_GRID", 1, 4096, v.maxgrid);      // A/B switch: workgroups of the split
         return v;
     }();
     return sh;
@@ -407,7 +408,7 @@ static inline C13Shape c13_shape() {
 static inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 // chunk ids one workgroup can need: TILE / 256 per tile it sorts + one partly filled chunk per partition
 static inline uint32_t chunk_region(uint64_t nwin) {
-    if (const char* e = getenv("AIX_COUNT13_TEST_REGION")) { const long v = atol(e); if (v > 0) return (uint32_t)v; }   // test hook: an undersized region must fail loudly
+    if (const long v = env_int("AIX_COUNT13_TEST_REGION", 1, LONG_MAX, 0)) return (uint32_t)v;   // test hook: an undersized region must fail loudly
     const C13Shape sh = c13_shape();
     const uint64_t tile = (uint64_t)sh.tb * sh.wpt;
     const uint64_t ntiles = (nwin + tile - 1) / tile;
@@ -442,8 +443,7 @@ static hipError_t launch_split(const SRC& src, uint64_t ntiles, unsigned grid, u
     // the next tile's loads in flight during the write-out: measured SLOWER for the 13-mer source (3.45 against 3.10 ms per 10 M reads: eleven more
     // live registers put the kernel at its 128-VGPR limit), so it is off unless asked for (A/B switch); requested right after the decode instead
     // (older than every store of the write-out): 4.27-4.42 against 4.11-4.19 ms per call, round 3. The slot source has nothing to fetch ahead
-    bool prefetch = false;
-    if (const char* pf = getenv("AIX_C13_PREFETCH")) prefetch = atoi(pf) != 0;
+    const bool prefetch = env_bool("AIX_C13_PREFETCH", false);
     // > 64 KiB of dynamic LDS needs the attribute; set per call (cheap, and correct for every device / thread)
     hipError_t e = prefetch ? hipFuncSetAttribute((const void*)k_c13_split_chunked<SRC, TB, WPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
                             : hipFuncSetAttribute((const void*)k_c13_split_chunked<SRC, TB, WPT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -505,7 +505,7 @@ hipError_t launch_histogram_slots(const uint32_t* d_slots, uint64_t nslots, void
     const uint64_t range = 1ull << range_bits;
     for (uint64_t base = 0; base < n; base += range) {
         const uint64_t m = std::min(range, n - base);
-        static const int in_regs = [] { const char* e = getenv("AIX_C23_SLOTS_REGS"); return e ? atoi(e) : 1; }();
+        static const bool in_regs = env_bool("AIX_C23_SLOTS_REGS", true);
         const hipError_t e = in_regs ? partitioned_histogram(SrcSlotsR{d_slots, nslots, (uint32_t)base, (uint32_t)m}, nslots, workspace, nullptr, nullptr, nullptr, 1, tf_out + base, m, s)
                                      : partitioned_histogram(SrcSlots{d_slots, nslots, (uint32_t)base, (uint32_t)m}, nslots, workspace, nullptr, nullptr, nullptr, 1, tf_out + base, m, s);
         if (e != hipSuccess) return e;

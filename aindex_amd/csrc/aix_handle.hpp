@@ -1,5 +1,5 @@
 // aix_handle.hpp — private to the library: the index handle resident in HBM, the error / device / scratch helpers shared by the
-// translation units that implement the C ABI (aix_api.hip, aix_ingest.hip).
+// translation units that implement the C ABI (aix_api.hip and one file per subsystem).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,8 +82,8 @@ struct aix_index {
     uint64_t* tf13_code = nullptr;
     uint32_t* perm13 = nullptr;
     unsigned long long* scratch13 = nullptr;   // code-ordered count table, lazily allocated
-    void* work13 = nullptr;                    // partition workspace of the atomic-free counter (grow-only)
-    uint64_t work13_bytes = 0;
+    void* count_ws = nullptr;                  // workspace of both counters (grow-only): 13-mer partitions; 23-mer slot stream + partitions
+    uint64_t count_ws_bytes = 0;
     // tiny host batches (a Python loop over index[kmer]): pinned, device-mapped staging so that a call is one memcpy into
     // host memory, one launch and one synchronise — no hipMemcpy round trips
     void* pin_in = nullptr;
@@ -93,7 +93,7 @@ struct aix_index {
     void* pin_cov = nullptr;                   // pinned, device-mapped staging of small coverage requests (kCovPin bytes)
     struct HostPipe* pipe = nullptr;           // pinned staging + streams of the large host-buffer batches (lazily built)
     std::mutex pipe_mutex;
-    hipEvent_t work13_done = nullptr;          // recorded behind every counting call: the next one (any stream) waits for it before touching the workspace
+    hipEvent_t count_done = nullptr;           // recorded behind every counting call: the next one (any stream) waits for it before touching the workspace
     hipStream_t hist_stream = nullptr;         // count23, AIX_COUNT23_HIST_CUS only: the partition + histogram kernels on their own CUs (CU-masked stream)
     hipStream_t probe_stream = nullptr;        // count23: the slot probe of piece i + 1 runs here while piece i is partitioned and added on the caller's stream
     hipEvent_t probe_ev[2] = {nullptr, nullptr}, hist_ev[2] = {nullptr, nullptr}, start_ev = nullptr;
@@ -108,7 +108,7 @@ struct aix_index {
     uint64_t pos_total = 0;                        // aix_positions_total, once computed (sum of tf[])
     bool pos_total_known = false;
     uint32_t a2_backend = 0;                       // the last positions fill: bit 0 = stable radix sort, bit 1 = MSD partition (per piece)
-    uint32_t c23_backend = 0, c23_passes = 0;     // the last aix_count23_fixed*: 1 = memory-side atomics, 2 = slot stream + LDS histogram; passes over the slot stream
+    uint32_t c23_backend = 0, c23_passes = 0;     // the last aix_count23_fixed* (stored under count_mutex): 1 = memory-side atomics, 2 = slot stream + LDS histogram, 3 = distinct k-mers first (K1); passes over the slot stream
     bool c13_atomics = false, c13_added = false;   // state of a 13-mer count in progress (between count13_begin_locked and count13_end_locked)
     // the attached positions index (aix_posquery.hip): the .indices.bin / .index.bin images in HBM, and the .ridx intervals as three arrays
     uint64_t* ai_indices = nullptr;                // n + 1 offsets
@@ -161,7 +161,12 @@ struct aix_index {
 // releases the attached positions index and read intervals (aix_posquery.hip); the caller has switched to the handle's device
 void posquery_release(aix_index* h);
 
-// K13 in steps (aix_api.hip); the caller holds h->count_mutex from begin to end
+// shared by the files that implement the ABI: device index in range (aix_index.hip); the large-batch staging of a handle is freed
+// through this one function, so that only aix_lookup.hip knows its layout
+__attribute__((visibility("hidden"))) int check_device(int device);
+__attribute__((visibility("hidden"))) void free_host_pipe(struct HostPipe* p);
+
+// K13 in steps (aix_count.hip); the caller holds h->count_mutex from begin to end
 int count13_begin_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s);
 int count13_add_locked(aix_index* h, const char* d_plain, uint64_t len, uint64_t* d_tf_out, hipStream_t s);
 int count13_end_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s);

@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "aix_env.hpp"
 #include "aix_handle.hpp"
 #include "aix_ingest.hpp"
 
@@ -99,8 +100,7 @@ HostWorkers& host_workers() {
     static HostWorkers pool([] {
         unsigned n = std::thread::hardware_concurrency();
         n = n ? std::min(12u, std::max(1u, n / 2)) : 4u;
-        if (const char* e = getenv("AIX_INGEST_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 64) n = (unsigned)v; }
-        return n - 1;                                         // + the calling thread
+        return (unsigned)env_int("AIX_INGEST_THREADS", 1, 64, n) - 1;                                        // + the calling thread
     }());
     return pool;
 }
@@ -114,7 +114,7 @@ struct PinnedPool {
     std::vector<std::pair<void*, uint64_t>> free_blocks;
     uint64_t cached = 0;
     static uint64_t limit() {
-        static const uint64_t lim = [] { const char* e = getenv("AIX_PINNED_CACHE_MB"); return (uint64_t)(e ? atol(e) : 1024) << 20; }();
+        static const uint64_t lim = (uint64_t)env_int("AIX_PINNED_CACHE_MB", LONG_MIN, LONG_MAX, 1024) << 20;
         return lim;
     }
     void* get(uint64_t bytes) {
@@ -368,11 +368,8 @@ Ingest::~Ingest() {
 uint64_t ingest_part_bytes() {
     // 256 MiB parts, three in flight: 47.5 GB/s for an 8 GB PLAIN file with warm staging blocks (64 MiB: 43.8, 12 reader threads; 8 threads:
     // 37, 4: 22 — DESIGN.md 5). Pinning a block costs ~35 ms, so a process that will stream ONE file warms the pool first (aix_ingest_warm).
-    uint64_t mb = 256;
-    if (const char* e = getenv("AIX_INGEST_PART_MB")) { const long v = atol(e); if (v >= 1 && v <= 2047) mb = (uint64_t)v; }
-    uint64_t bytes = mb << 20;
-    if (const char* e = getenv("AIX_INGEST_TEST_PART")) { const long v = atol(e); if (v >= 1) bytes = (uint64_t)v; }   // test hook: parts of a few bytes, cuts everywhere
-    return bytes;
+    const long bytes = env_int("AIX_INGEST_PART_MB", 1, 2047, 256) << 20;
+    return (uint64_t)env_int("AIX_INGEST_TEST_PART", 1, LONG_MAX, bytes);      // test hook: parts of a few bytes, cuts everywhere
 }
 
 // the source uploaded as it is into d_dst (len bytes), pipelined: host threads fill pinned part i + 1 while part i is on the wire
@@ -496,7 +493,7 @@ static int count13_source(aix_index_t* h, const ByteSource& src, int format, uin
         }
         if (!st && r < 0) st = r;
         ps.fill_stats(stats);
-        if (stats) stats->workspace_bytes = h->work13_bytes;
+        if (stats) stats->workspace_bytes = h->count_ws_bytes;
     }
     const int st2 = count13_end_locked(h, d_tf, s);
     return st ? st : st2;
@@ -516,7 +513,7 @@ static int count23_source(aix_index_t* h, const ByteSource& src, int format, int
     }
     if (!st && r < 0) st = r;
     ps.fill_stats(stats);
-    if (stats) stats->workspace_bytes = h->work13_bytes;
+    if (stats) stats->workspace_bytes = h->count_ws_bytes;
     return st;
 }
 
@@ -756,8 +753,7 @@ __global__ void k_move_tail(uint8_t* __restrict__ buf, uint64_t fill, uint32_t k
 static int distinct_source(const ByteSource& src, int format, int k, int canon_mode, uint64_t min_count, int device, hipStream_t s, uint64_t** dk, uint64_t** dc,
                            uint64_t* n_out, aix_ingest_stats_t* stats) {
     *dk = nullptr; *dc = nullptr; *n_out = 0;
-    uint64_t piece_win = 1ull << 30;                          // as distinct_from_plain (aix_merge.hip)
-    if (const char* e = getenv("AIX_DISTINCT_PIECE")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v <= (1ull << 31)) piece_win = v; }   // test hook: merges at small sizes
+    const uint64_t piece_win = env_distinct_piece();         // as distinct_from_plain (aix_merge.hip); test hook: merges at small sizes
     PlainStream ps(src, format, 1, k, device, s);
     int st = ps.start();
     if (st) return st;

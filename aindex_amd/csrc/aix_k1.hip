@@ -24,6 +24,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "aix_env.hpp"
 #include "aix_internal.hpp"
 #include "aix_msd.hpp"
 
@@ -266,7 +267,7 @@ __global__ void __launch_bounds__(256) k_k1_gather(const uint64_t* __restrict__ 
 static inline uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
 
 bool k1_msd_eligible(uint64_t nwin, int k) {
-    if (getenv("AIX_K1_ROCPRIM") != nullptr) return false;      // A/B switch: the radix-sort path
+    if (env_flag("AIX_K1_ROCPRIM")) return false;      // A/B switch: the radix-sort path
     return k >= 9 && k <= 23 && nwin > 0 && nwin <= (1ull << 31);
 }
 
@@ -289,8 +290,7 @@ hipError_t distinct_from_codes_msd(uint64_t* d_codes, uint64_t nwin, int k, uint
     const uint32_t nbuckets = (uint32_t)K1_P * nb2;
     const uint64_t ntiles = (nwin + K1_TILE - 1) / K1_TILE;
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, K1_MAXGRID);
-    uint32_t region = (uint32_t)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P);
-    if (const char* e = getenv("AIX_K1_TEST_REGION")) { const long v = atol(e); if (v > 0) region = (uint32_t)v; }   // test hook: an undersized region must fail loudly
+    const uint32_t region = (uint32_t)env_int("AIX_K1_TEST_REGION", 1, LONG_MAX, (long)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P));   // test hook: an undersized region must fail loudly
     const uint32_t cap = grid * region;
     // one block: err | overflow | dir_part | dir_cnt | spart | sdesc | sort temp | bucket_cnt (nbuckets + 1) | bucket_base | distinct_m | dm_off | out32 | parts
     size_t sort_tmp = 0;

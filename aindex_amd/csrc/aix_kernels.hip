@@ -4,6 +4,7 @@
 // All kernels are HBM/latency-bound integer work (no MFMA): one query / window per lane, three
 // independent 16-byte MPHF record reads + one 16-byte key record read per probe, grid-stride
 // launches of >= 8 workgroups per CU so that ~2k probes per CU are in flight.
+#include "aix_env.hpp"
 #include "aix_internal.hpp"
 
 namespace aix {
@@ -13,7 +14,7 @@ static inline unsigned grid_for(uint64_t work, unsigned per_block = kBlock) {
     // Grid-stride kernels. Up to 8192 workgroups one trip each; beyond that a quarter of the trips' worth of workgroups — a wave keeps at
     // least four trips, which is what the lookups' FilterGauge needs to adapt — up to 256 per CU: finer workgroups balance the tail better
     // than 32 per CU did (100 M lookups 2.116 against 2.16 ms, coverage 29.9 against 31.4 ms, count23 38.3 against 38.7 ms, one box).
-    static const uint64_t per_cu = [] { const char* e = getenv("AIX_GRID_PER_CU"); const long v = e ? atol(e) : 0; return (uint64_t)(v >= 1 && v <= 1024 ? v : 256); }();   // A/B switch
+    static const uint64_t per_cu = (uint64_t)env_int("AIX_GRID_PER_CU", 1, 1024, 256);   // A/B switch
     const uint64_t need = (work + per_block - 1) / per_block, cap = 256ull * per_cu;
     uint64_t b = std::max(std::min<uint64_t>(need, 8192), need / 4);
     if (b > cap) b = cap;
@@ -1107,7 +1108,7 @@ hipError_t launch_count23_fixed(const IndexDev& ix, const uint8_t* buf, uint64_t
 template <int LPP>
 static hipError_t probe23_slots_lpp(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* slots, hipStream_t s) {
     // AIX_PROBE_LDS_PAD=bytes (experiment): unused dynamic LDS per workgroup, to run the probe at a chosen number of waves per CU
-    static const unsigned pad = [] { const char* e = getenv("AIX_PROBE_LDS_PAD"); return e ? (unsigned)atoi(e) : 0u; }();
+    static const unsigned pad = (unsigned)env_int("AIX_PROBE_LDS_PAD", INT_MIN, INT_MAX, 0);
     if (pad) {
         hipLaunchKernelGGL(k_probe23_slots<LPP>, dim3(grid_for(len - 22)), dim3(kBlock), pad, s, ix, buf, len, canon_mode, slots);
         return hipGetLastError();

@@ -17,7 +17,11 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "aix_internal.hpp"
+#include <new>
+#include <string>
+
+#include "aix_env.hpp"
+#include "aix_handle.hpp"
 
 namespace aix {
 
@@ -355,3 +359,77 @@ hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64
 }
 
 }  // namespace aix
+
+// ---------------------------------------------------------------------------------------------
+// K1: distinct canonical k-mers of a sequence file (kmer_counter replacement)
+// ---------------------------------------------------------------------------------------------
+// device-resident twin: the PLAIN buffer is already in HBM; the result stays in HBM inside an opaque object until the caller
+// has copied it into arrays of its own (two steps because the number of distinct k-mers is only known afterwards)
+struct aix_distinct { uint64_t* keys = nullptr; uint64_t* counts = nullptr; uint64_t n = 0; int device = 0; };
+
+// what the three producers share: device check, guard, the object, and `what` in front of a HIP error. run(keys, counts, n) fills the result.
+template <typename F>
+static int make_distinct(int device, const char* what, aix_distinct_t** out, F&& run) {
+    const int st = check_device(device);
+    if (st) return st;
+    DevGuard g(device);
+    aix_distinct* r = new (std::nothrow) aix_distinct();
+    if (!r) return AIX_ERR_NOMEM;
+    r->device = device;
+    const hipError_t e = run(&r->keys, &r->counts, &r->n);
+    if (e != hipSuccess) { delete r; set_last_error(std::string(what) + ": " + hipGetErrorString(e)); return AIX_ERR_HIP; }
+    *out = r;
+    return AIX_OK;
+}
+
+extern "C" int aix_count_distinct_dev(const char* d_plain, uint64_t len, int k, int canon_mode, uint64_t min_count, int device, void* stream,
+                                      aix_distinct_t** out) {
+    if (!out || (len && !d_plain) || k < 1 || k > 31 || canon_mode < 0 || canon_mode > 2) return AIX_ERR_ARG;
+    *out = nullptr;
+    return make_distinct(device, "count_distinct", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* n) {
+        return distinct_from_plain((const uint8_t*)d_plain, len, k, canon_mode, min_count ? min_count : 1, env_distinct_piece(), keys, counts, n, (hipStream_t)stream);
+    });
+}
+// K1 across GPUs: after the exchange a rank holds (key, count) pairs from every rank; equal keys are summed here
+extern "C" int aix_merge_counts_dev(const uint64_t* d_keys, const uint64_t* d_counts, uint64_t n, uint64_t min_count, int device, void* stream,
+                                    aix_distinct_t** out) {
+    if (!out || (n && (!d_keys || !d_counts))) return AIX_ERR_ARG;
+    *out = nullptr;
+    return make_distinct(device, "merge_counts", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* m) {
+        return merge_counts(d_keys, d_counts, n, min_count ? min_count : 1, keys, counts, m, (hipStream_t)stream);
+    });
+}
+// the same when the caller knows its runs: run r = entries [run_offsets[r], run_offsets[r + 1]), each sorted by key and free of repeats
+// (after the K1 exchange a rank holds one such run per peer): a tree of two-way merges, nothing is sorted
+extern "C" int aix_merge_runs_dev(const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* run_offsets, uint32_t nruns, uint64_t min_count, int device,
+                                  void* stream, aix_distinct_t** out) {
+    if (!out || !run_offsets || nruns == 0) return AIX_ERR_ARG;
+    *out = nullptr;
+    for (uint32_t r = 0; r < nruns; ++r) if (run_offsets[r + 1] < run_offsets[r]) return AIX_ERR_ARG;
+    if (run_offsets[nruns] > run_offsets[0] && (!d_keys || !d_counts)) return AIX_ERR_ARG;
+    return make_distinct(device, "merge_runs", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* m) {
+        return merge_runs(d_keys, d_counts, run_offsets, nruns, min_count ? min_count : 1, keys, counts, m, (hipStream_t)stream);
+    });
+}
+extern "C" int aix_distinct_size(const aix_distinct_t* r, uint64_t* n_out) {
+    if (!r || !n_out) return AIX_ERR_ARG;
+    *n_out = r->n;
+    return AIX_OK;
+}
+extern "C" int aix_distinct_copy_dev(const aix_distinct_t* r, uint64_t* d_keys, uint64_t* d_counts, void* stream) {
+    if (!r || (r->n && (!d_keys || !d_counts))) return AIX_ERR_ARG;
+    DevGuard g(r->device);
+    if (r->n) {
+        HIPCHK(hipMemcpyAsync(d_keys, r->keys, 8 * r->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIPCHK(hipMemcpyAsync(d_counts, r->counts, 8 * r->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    }
+    return AIX_OK;
+}
+extern "C" void aix_distinct_free(aix_distinct_t* r) {
+    if (!r) return;
+    DevGuard g(r->device);
+    if (r->keys) pool_free(r->keys);
+    if (r->counts) pool_free(r->counts);
+    delete r;
+}

@@ -14,8 +14,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "../../include/aindex_hip.h"
-#include "aix_internal.hpp"
+#include "aix_handle.hpp"
 
 namespace aix {
 
@@ -292,3 +291,76 @@ hipError_t normalise_device(const uint8_t* d_raw, uint64_t len, int format, int 
 }
 
 }  // namespace aix
+
+// ---------------------------------------------------------------------------------------------
+// record normalisation (host): readers of count_kmers13.cpp:211-272 and count_kmers.cpp:250-295
+// ---------------------------------------------------------------------------------------------
+extern "C" int aix_detect_format(const char* buf, uint64_t len) {
+    if (!buf || len == 0) return AIX_FMT_PLAIN;
+    if (buf[0] == '\n') return AIX_FMT_PLAIN;
+    if (buf[0] == '>') return AIX_FMT_FASTA;
+    if (buf[0] == '@') return AIX_FMT_FASTQ;
+    return AIX_FMT_PLAIN;
+}
+
+extern "C" int aix_normalize_reads(const char* buf, uint64_t len, int format, int fasta_mode, char* out, uint64_t* out_len) {
+    if (!out || !out_len || (len && !buf)) return AIX_ERR_ARG;
+    if (format == AIX_FMT_AUTO) format = aix_detect_format(buf, len);
+    uint64_t o = 0;
+    if (format == AIX_FMT_PLAIN) {
+        memcpy(out, buf, len);
+        o = len;
+    } else if (format == AIX_FMT_FASTQ) {                      // count_kmers13.cpp:240-257: line 4i+1
+        uint64_t pos = 0, line_no = 0;
+        while (pos < len) {
+            const char* nl = (const char*)memchr(buf + pos, '\n', len - pos);
+            const uint64_t end = nl ? (uint64_t)(nl - buf) : len;
+            if ((line_no & 3) == 1 && end > pos) { memcpy(out + o, buf + pos, end - pos); o += end - pos; out[o++] = '\n'; }
+            line_no++;
+            pos = end + 1;
+        }
+    } else if (format == AIX_FMT_FASTA && fasta_mode == 0) {  // count_kmers13.cpp:211-235
+        uint64_t pos = 0;
+        bool open = false;
+        while (pos < len) {
+            const char* nl = (const char*)memchr(buf + pos, '\n', len - pos);
+            const uint64_t end = nl ? (uint64_t)(nl - buf) : len;
+            if (end > pos) {
+                if (buf[pos] == '>') { if (open) { out[o++] = '\n'; open = false; } }
+                else { memcpy(out + o, buf + pos, end - pos); o += end - pos; open = true; }
+            }
+            pos = end + 1;
+        }
+        if (open) out[o++] = '\n';
+    } else if (format == AIX_FMT_FASTA) {                      // count_kmers.cpp:250-295: '>' anywhere opens a record
+        uint64_t i = 0;
+        while (i < len && buf[i] != '>') i++;
+        while (i < len) {
+            uint64_t end = i + 1;
+            while (end < len && buf[end] != '>') end++;
+            uint64_t j = i;
+            while (j < end && buf[j] != '\n') j++;
+            j++;
+            for (; j < end; ++j) { const char c = buf[j]; if (c != '\n' && c != '\r') out[o++] = c; }
+            out[o++] = '\n';
+            i = end;
+        }
+    } else {
+        return AIX_ERR_ARG;
+    }
+    *out_len = o;
+    return AIX_OK;
+}
+
+extern "C" int aix_normalize_reads_dev(const char* d_raw, uint64_t len, int format, int fasta_mode, char* d_out, uint64_t* out_len, void* stream) {
+    if (!out_len || (len && (!d_raw || !d_out))) return AIX_ERR_ARG;
+    if (format != AIX_FMT_PLAIN && format != AIX_FMT_FASTA && format != AIX_FMT_FASTQ) return AIX_ERR_ARG;   // no auto-detect on device buffers
+    if (format == AIX_FMT_PLAIN) {
+        if (len) HIPCHK(hipMemcpyAsync(d_out, d_raw, len, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        *out_len = len;
+        return AIX_OK;
+    }
+    HIPCHK(normalise_device((const uint8_t*)d_raw, len, format, fasta_mode, (uint8_t*)d_out, out_len, (hipStream_t)stream));
+    return AIX_OK;
+}

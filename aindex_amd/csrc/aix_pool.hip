@@ -10,6 +10,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "aix_env.hpp"
 #include "aix_internal.hpp"
 
 namespace aix {
@@ -22,8 +23,7 @@ std::unordered_map<void*, Block> g_live;
 size_t g_cached = 0;
 size_t cache_limit() {
     static const size_t lim = [] {
-        const char* e = getenv("AIX_SCRATCH_CACHE_GB");
-        const double gb = e ? atof(e) : 40.0;
+        const double gb = env_double("AIX_SCRATCH_CACHE_GB", -1e300, 1e300, 40.0);
         return (size_t)(gb < 0 ? 0 : gb * (double)(1ull << 30));
     }();
     return lim;

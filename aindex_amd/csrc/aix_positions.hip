@@ -11,7 +11,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "aix_internal.hpp"
+#include "aix_env.hpp"
+#include "aix_handle.hpp"
+#include "aix_ingest.hpp"
 
 namespace aix {
 
@@ -159,7 +161,7 @@ static void launch_a2_probe(const IndexDev& ix, const uint8_t* d_reads, uint64_t
         // lanes that share one bucket line (IndexDev::bk_lpp; the ABI hands in 2 unless the caller chose a width: like count23's slot probe,
         // nothing but a 4-byte slot leaves this kernel, and two lanes per line measured 28.5-29.9 against 29.6-30.7 ms per 5 M reads with eight,
         // three alternating repetitions on one box). AIX_A2_PROBE_LANES: A/B switch
-        static const int forced = [] { const char* e = getenv("AIX_A2_PROBE_LANES"); const int v = e ? atoi(e) : 0; return v == 2 || v == 4 || v == 8 ? v : 0; }();
+        static const int forced = [] { const long v = env_int("AIX_A2_PROBE_LANES", 2, 8, 0); return v == 2 || v == 4 || v == 8 ? (int)v : 0; }();
         const int lanes = forced ? forced : (int)ix.bk_lpp;
         if (lanes == 2) hipLaunchKernelGGL(k_a2_probe<2>, dim3(grid_of(nwin)), dim3(kB), 0, s, ix, d_reads, nwin, start, keys);
         else if (lanes == 4) hipLaunchKernelGGL(k_a2_probe<4>, dim3(grid_of(nwin)), dim3(kB), 0, s, ix, d_reads, nwin, start, keys);
@@ -378,3 +380,186 @@ hipError_t distinct_from_codes(uint64_t* d_codes /* clobbered */, uint64_t nwin,
 }
 
 }  // namespace aix
+
+// ---------------------------------------------------------------------------------------------
+// A1/A2: the entry points of the positions index. The host-pointer ones stage through HBM, run the same launch code and copy back.
+// ---------------------------------------------------------------------------------------------
+// host buffer -> HBM through the pinned, multi-threaded staging pipeline (aix_ingest.hip); returns when the bytes are on the device
+static int upload_host(const char* buf, uint64_t len, uint8_t* d_dst, int device) {
+    if (len == 0) return AIX_OK;
+    ByteSource src;
+    src.set_memory(buf, len);
+    const int st = upload_pipelined(src, d_dst, device, 0);
+    if (st) return st;
+    HIPCHK(hipStreamSynchronize(0));
+    return AIX_OK;
+}
+
+// positions_fill refuses a 13-mer tf table with an entry above 2^32 - 1 (32-bit fill counters, aix_positions.hip): that is a status, not a HIP failure
+#define POSCHK(expr)                                                                                                                     \
+    do {                                                                                                                                 \
+        hipError_t _e = (expr);                                                                                                          \
+        if (_e == hipErrorNotSupported) { (void)hipGetLastError(); set_last_error("positions: a 13-mer tf above 2^32 - 1"); return AIX_ERR_UNSUPPORTED; } \
+        if (_e != hipSuccess) { set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e)); return AIX_ERR_HIP; }                  \
+    } while (0)
+
+// first window the reference's single worker looks at (hash.cpp:973-986): the start is pushed past any
+// '\n', '~' or '?' found in the first k bytes, repeatedly
+static uint64_t a2_start(const char* c, uint64_t len, uint64_t k = 23) {
+    if (len < k) return 0;
+    uint64_t start = 0;
+    const uint64_t end = len;
+    while (start < end - k + 1) {
+        bool found = false;
+        for (uint64_t i = start; i < start + k; ++i)
+            if (c[i] == '\n' || c[i] == '~' || c[i] == '?') { start = i + 1; found = true; break; }
+        if (!found) break;
+    }
+    return start;
+}
+
+// the one call of positions_fill behind the four fill entry points: slot-stream lanes, AIX_POSITIONS_PIECE (test hook, read per call:
+// exercises the piece logic at small sizes), the back end recorded for aix_index_info
+static int fill_positions(aix_index* h, const void* d_reads, uint64_t len, uint64_t start, const void* d_indices, void* d_positions, const void* d_filled_init,
+                          uint64_t base_offset, hipStream_t s) {
+    POSCHK(positions_fill(h->dev_slots(), (const uint8_t*)d_reads, len, start, (const uint64_t*)d_indices, (uint64_t*)d_positions, env_positions_piece(),
+                          (const uint32_t*)d_filled_init, base_offset, s, &h->a2_backend));
+    return AIX_OK;
+}
+
+extern "C" int aix_positions_fill(aix_index_t* h, const char* reads, uint64_t len, uint64_t* indices_out, uint64_t* positions_out, uint64_t positions_cap,
+                                  uint64_t* total_out) {
+    if (!h || !indices_out || (len && !reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    const uint64_t n = h->n;
+    DevBuf dind;
+    HIPCHK(dind.alloc(8 * (n + 1)));
+    if (n) HIPCHK(positions_indices(h->dev(), (uint64_t*)dind.p, 0));
+    else HIPCHK(hipMemset(dind.p, 0, 8));
+    { const int ds = download_to_host(indices_out, dind.p, 8 * (n + 1), 0); if (ds) return ds; }
+    const uint64_t total = indices_out[n];
+    if (total_out) *total_out = total;
+    if (!positions_out) return AIX_OK;
+    if (positions_cap < total) return AIX_ERR_ARG;
+    if (total == 0) return AIX_OK;
+    DevBuf dreads, dpos;
+    HIPCHK(dreads.alloc(len + 8));
+    HIPCHK(dpos.alloc(8 * total));
+    HIPCHK(hipMemsetAsync(dpos.p, 0, 8 * total, 0));
+    { const int us = upload_host(reads, len, (uint8_t*)dreads.p, h->device); if (us) return us; }
+    { const int fs = fill_positions(h, dreads.p, len, a2_start(reads, len, h->k), dind.p, dpos.p, nullptr, 0, 0); if (fs) return fs; }
+    return download_to_host(positions_out, dpos.p, 8 * total, 0);
+}
+
+// device-resident twin: reads already in HBM, indices (n+1) and positions (indices[n], caller-sized through
+// aix_positions_total) written in HBM. `start` = aix_positions_start of the buffer's head (the caller holds the bytes).
+extern "C" int aix_positions_total(aix_index_t* h, uint64_t* total_out) {
+    if (!h || !total_out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    *total_out = 0;
+    if (h->n == 0) return AIX_OK;
+    if (h->pos_total_known) { *total_out = h->pos_total; return AIX_OK; }       // sum of tf[]: fixed for the life of a 23-mer handle, reset by aix_index_set_tf_13
+    DevBuf dind;
+    HIPCHK(dind.alloc(8 * (h->n + 1)));
+    HIPCHK(positions_indices(h->dev(), (uint64_t*)dind.p, 0));
+    HIPCHK(hipMemcpy(total_out, (const uint64_t*)dind.p + h->n, 8, hipMemcpyDeviceToHost));
+    h->pos_total = *total_out;
+    h->pos_total_known = true;
+    return AIX_OK;
+}
+
+extern "C" int aix_positions_fill_dev(aix_index_t* h, const char* d_reads, uint64_t len, uint64_t start, uint64_t* d_indices_out, uint64_t* d_positions_out,
+                                      uint64_t positions_cap, void* stream) {
+    if (!h || !d_indices_out || (len && !d_reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t n = h->n;
+    if (n) HIPCHK(positions_indices(h->dev(), d_indices_out, s));           // synchronises the stream
+    else HIPCHK(hipMemsetAsync(d_indices_out, 0, 8, s));
+    if (n == 0) return AIX_OK;
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_indices_out + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total == 0) return AIX_OK;
+    if (!d_positions_out || positions_cap < total) return AIX_ERR_ARG;
+    HIPCHK(hipMemsetAsync(d_positions_out, 0, 8 * total, s));
+    return fill_positions(h, d_reads, len, start, d_indices_out, d_positions_out, nullptr, 0, s);
+}
+
+extern "C" int aix_positions_start(const char* reads, uint64_t len, uint64_t* start_out) {
+    if (!start_out || (len && !reads)) return AIX_ERR_ARG;
+    *start_out = a2_start(reads, len);
+    return AIX_OK;
+}
+extern "C" int aix_positions_start_k(const char* reads, uint64_t len, int k, uint64_t* start_out) {
+    if (!start_out || (len && !reads) || (k != 13 && k != 23)) return AIX_ERR_ARG;
+    *start_out = a2_start(reads, len, (uint64_t)k);
+    return AIX_OK;
+}
+
+// A2 over shards of the reads file (multi-GPU): tally, then fill with the counters of the earlier shards
+extern "C" int aix_positions_bucket_counts(aix_index_t* h, const char* reads, uint64_t len, int first_shard, uint64_t* counts_out) {
+    if (!h || !counts_out || (len && !reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    const uint64_t n = h->n;
+    if (n == 0) return AIX_OK;
+    DevBuf dreads, dcnt;
+    HIPCHK(dreads.alloc(len + 8));
+    HIPCHK(dcnt.alloc(8 * n));
+    { const int us = upload_host(reads, len, (uint8_t*)dreads.p, h->device); if (us) return us; }
+    HIPCHK(hipMemset(dcnt.p, 0, 8 * n));
+    HIPCHK(positions_bucket_counts(h->dev_slots(), (const uint8_t*)dreads.p, len, first_shard ? a2_start(reads, len, h->k) : 0, (unsigned long long*)dcnt.p, 0));
+    return download_to_host(counts_out, dcnt.p, 8 * n, 0);
+}
+
+extern "C" int aix_positions_fill_shard(aix_index_t* h, const char* reads, uint64_t len, int first_shard, uint64_t base_offset, const uint32_t* filled_init,
+                                        uint64_t* positions_out, uint64_t positions_cap) {
+    if (!h || !positions_out || (len && !reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    const uint64_t n = h->n;
+    if (n == 0) return AIX_OK;
+    DevBuf dind, dreads, dpos, dfill;
+    HIPCHK(dind.alloc(8 * (n + 1)));
+    HIPCHK(positions_indices(h->dev(), (uint64_t*)dind.p, 0));
+    uint64_t total = 0;
+    HIPCHK(hipMemcpy(&total, (const uint64_t*)dind.p + n, 8, hipMemcpyDeviceToHost));
+    if (positions_cap < total) return AIX_ERR_ARG;
+    if (total == 0) return AIX_OK;
+    HIPCHK(dreads.alloc(len + 8));
+    HIPCHK(dpos.alloc(8 * total));
+    if (filled_init) {
+        HIPCHK(dfill.alloc(4 * n));
+        HIPCHK(hipMemcpy(dfill.p, filled_init, 4 * n, hipMemcpyHostToDevice));
+    }
+    { const int us = upload_host(reads, len, (uint8_t*)dreads.p, h->device); if (us) return us; }
+    HIPCHK(hipMemset(dpos.p, 0, 8 * total));
+    { const int fs = fill_positions(h, dreads.p, len, first_shard ? a2_start(reads, len, h->k) : 0, dind.p, dpos.p, filled_init ? dfill.p : nullptr, base_offset, 0); if (fs) return fs; }
+    return download_to_host(positions_out, dpos.p, 8 * total, 0);
+}
+
+// device-resident twins of the shard entry points (multi-GPU): a rank's share is already in HBM, the partial results stay in
+// HBM for the collectives (RCCL), nothing crosses PCIe
+extern "C" int aix_positions_indices_dev(aix_index_t* h, uint64_t* d_indices_out, void* stream) {
+    if (!h || !d_indices_out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    if (h->n == 0) { HIPCHK(hipMemsetAsync(d_indices_out, 0, 8, (hipStream_t)stream)); return AIX_OK; }
+    HIPCHK(positions_indices(h->dev(), d_indices_out, (hipStream_t)stream));
+    return AIX_OK;
+}
+
+extern "C" int aix_positions_bucket_counts_dev(aix_index_t* h, const char* d_reads, uint64_t len, uint64_t start, uint64_t* d_counts_out, void* stream) {
+    if (!h || !d_counts_out || (len && !d_reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    if (h->n == 0) return AIX_OK;
+    HIPCHK(hipMemsetAsync(d_counts_out, 0, 8 * h->n, (hipStream_t)stream));
+    HIPCHK(positions_bucket_counts(h->dev_slots(), (const uint8_t*)d_reads, len, start, (unsigned long long*)d_counts_out, (hipStream_t)stream));
+    return AIX_OK;
+}
+
+extern "C" int aix_positions_fill_shard_dev(aix_index_t* h, const char* d_reads, uint64_t len, uint64_t start, uint64_t base_offset, const uint32_t* d_filled_init,
+                                            const uint64_t* d_indices, uint64_t* d_positions, void* stream) {
+    if (!h || !d_indices || !d_positions || (len && !d_reads)) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    if (h->n == 0) return AIX_OK;
+    return fill_positions(h, d_reads, len, start, d_indices, d_positions, d_filled_init, base_offset, (hipStream_t)stream);
+}
