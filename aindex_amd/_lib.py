@@ -117,6 +117,16 @@ SIGNATURES = {
     "aix_positions_query_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_positions_locate": (i32, [vp, vp, u64, vp, vp]),
     "aix_positions_locate_dev": (i32, [vp, vp, u64, vp, vp, vp]),
+    "aix_reads_attach": (i32, [vp, vp, u64]),
+    "aix_reads_attach_dev": (i32, [vp, vp, u64, vp]),
+    "aix_reads_detach": (i32, [vp]),
+    "aix_reads_info": (i32, [vp, C.POINTER(u64 * 2)]),
+    "aix_reads_fetch": (i32, [vp, vp, vp, vp, u64, C.POINTER(vp), C.POINTER(vp)]),
+    "aix_reads_fetch_dev": (i32, [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_reads_fetch_rid": (i32, [vp, vp, u64, C.POINTER(vp), C.POINTER(vp)]),
+    "aix_reads_fetch_rid_dev": (i32, [vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_reads_by_kmers": (i32, [vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "aix_reads_by_kmers_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, u64, vp, u64, C.POINTER(u64 * 2), vp]),
     "aix_positions_start": (i32, [vp, u64, C.POINTER(u64)]),
     "aix_positions_start_k": (i32, [vp, u64, i32, C.POINTER(u64)]),
     "aix_index_scatter_shard_codes_dev": (i32, [vp, u64, vp, vp, u64, u64, i32, vp, vp, vp, vp]),

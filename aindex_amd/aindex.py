@@ -340,6 +340,28 @@ class AIndex:
             raise RuntimeError("Aindex not loaded")
         return self._wrapper.get_reads_se_by_kmer(kmer, max_reads)
 
+    def get_reads_batch(self, starts, ends, revcomp=False) -> List[str]:
+        """[get_read(s, e, revcomp) ...]: one GPU call over the reads file in HBM (revcomp: one bool or one flag per item)."""
+        return self._wrapper.get_reads_batch(starts, ends, revcomp)
+
+    def get_reads_by_rid_batch(self, rids) -> List[str]:
+        """[get_read_by_rid(r) for r in rids], one GPU call."""
+        return self._wrapper.get_reads_by_rid_batch(rids)
+
+    def get_reads_by_kmer_batch(self, kmers, max_reads: int = 100) -> List[List[str]]:
+        """[get_reads_by_kmer(s, max_reads) for s in kmers], one GPU call; wrong-length items give [] in place."""
+        if not self._wrapper.aindex_loaded:
+            raise RuntimeError("Aindex not loaded")
+        return self._wrapper.get_reads_by_kmer_batch(kmers, max_reads)
+
+    def get_reads_array(self, starts, ends, revcomp=False):
+        """CSR arrays (offsets, bytes uint8); see AindexWrapper.get_reads_array."""
+        return self._wrapper.get_reads_array(starts, ends, revcomp)
+
+    def get_reads_by_kmers_array(self, kmers, max_reads: int = 100):
+        """CSR arrays (kmer_offsets, rid, read_offsets, bytes uint8); see AindexWrapper.get_reads_by_kmers_array."""
+        return self._wrapper.get_reads_by_kmers_array(kmers, max_reads)
+
     def iter_reads(self):
         if self.reads_size == 0:                                  # aindex.py:271-278
             raise RuntimeError("Reads were not loaded.")

@@ -436,6 +436,24 @@ __device__ __forceinline__ uint32_t wave_lower_bound_pair(const uint16_t* __rest
     return lo;
 }
 
+// number of entries of the ascending array a[0 .. n) that are <= key, by ONE wave (all 64 lanes call it with the same key): 64 probes per
+// round, four rounds of independent loads for 10^7 entries (the u64 counterpart of wave_lower_bound_pair). Equal entries are allowed.
+__device__ __forceinline__ uint64_t wave_count_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t key) {
+    const uint64_t lane = threadIdx.x & 63u;
+    uint64_t lo = 0, hi = n;                                   // a[i] <= key for i < lo, a[i] > key for i >= hi
+    while (hi > lo) {
+        const uint64_t span = hi - lo, step = (span + 64) / 65;
+        const uint64_t at = lo + (lane + 1) * step - 1;
+        const bool le = at < hi && a[at] <= key;
+        const uint64_t nle = (uint64_t)__popcll(__ballot(le));
+        const uint64_t nlo = min(lo + nle * step, hi);
+        const uint64_t nhi = nle == 64 ? hi : min(hi, lo + (nle + 1) * step - 1);
+        lo = nlo;
+        hi = max(nhi, lo);
+    }
+    return lo;
+}
+
 __device__ __forceinline__ uint32_t bperm(uint32_t src_lane, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v); }
 
 // Read one 128-byte line of eight {code, tf, slot} entries per probe and compare the codes in it. All 64 lanes of the wave

@@ -118,6 +118,10 @@ struct aix_index {
     uint64_t* rx = nullptr;                        // starts[rx_n], ends[rx_n], rids[rx_n]
     uint64_t rx_n = 0;
     bool rx_attached = false;
+    // the attached reads file (aix_readsquery.hip): the .reads image in HBM
+    uint8_t* rd = nullptr;
+    uint64_t rd_len = 0;
+    bool rd_attached = false, rd_owned = false;    // owned: copied by aix_reads_attach (freed on detach); else borrowed from the caller
 
     // the slot-stream consumers (count23's histogram path, the positions probe): two lanes per bucket line unless the caller chose a width
     IndexDev dev_slots() const {
@@ -160,6 +164,14 @@ struct aix_index {
 
 // releases the attached positions index and read intervals (aix_posquery.hip); the caller has switched to the handle's device
 void posquery_release(aix_index* h);
+// the chain of aix_positions_query* (aix_posquery.hip): d_offsets (N + 1) and *total_out are always produced; entries only when
+// *total_out <= cap and d_positions is given. Synchronises `s`.
+namespace aix {
+hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
+                        uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s);
+}
+// releases the attached reads file (aix_readsquery.hip); the caller has switched to the handle's device
+void readsquery_release(aix_index* h);
 
 // shared by the files that implement the ABI: device index in range (aix_index.hip); the large-batch staging of a handle is freed
 // through this one function, so that only aix_lookup.hip knows its layout

@@ -113,6 +113,7 @@ static void destroy(aix_index* h) {
     if (h->scratch13) (void)hipFree(h->scratch13);
     if (h->count_ws) (void)hipFree(h->count_ws);
     posquery_release(h);
+    readsquery_release(h);
     if (h->pipe) { free_host_pipe(h->pipe); h->pipe = nullptr; }
     if (h->count_done) (void)hipEventDestroy(h->count_done);
     for (int i = 0; i < 2; ++i) { if (h->probe_ev[i]) (void)hipEventDestroy(h->probe_ev[i]); if (h->hist_ev[i]) (void)hipEventDestroy(h->hist_ev[i]); }

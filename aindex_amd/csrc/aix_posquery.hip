@@ -151,24 +151,7 @@ __global__ void __launch_bounds__(kB) k_pq_compact(uint64_t N, const uint64_t* _
 // ---------------------------------------------------------------------------------------------
 // 3 / 5. the flat passes
 // ---------------------------------------------------------------------------------------------
-// number of entries of the ascending array a[0 .. n) that are <= key, by ONE wave (all 64 lanes call it with the same key): 64 probes per
-// round, four rounds of independent loads for 10^7 entries (the u64 counterpart of wave_lower_bound_pair, aix_device.hpp)
-__device__ __forceinline__ uint64_t wave_count_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t key) {
-    const uint64_t lane = threadIdx.x & 63u;
-    uint64_t lo = 0, hi = n;                                   // a[i] <= key for i < lo, a[i] > key for i >= hi
-    while (hi > lo) {
-        const uint64_t span = hi - lo, step = (span + 64) / 65;
-        const uint64_t at = lo + (lane + 1) * step - 1;
-        const bool le = at < hi && a[at] <= key;
-        const uint64_t nle = (uint64_t)__popcll(__ballot(le));
-        const uint64_t nlo = min(lo + nle * step, hi);
-        const uint64_t nhi = nle == 64 ? hi : min(hi, lo + (nle + 1) * step - 1);
-        lo = nlo;
-        hi = max(nhi, lo);
-    }
-    return lo;
-}
-
+// (the tile's first list is found with wave_count_le, aix_device.hpp)
 // IntervalTree::query(pos, pos + 1) of python_wrapper.cpp:66-74 on sorted, disjoint intervals: the first interval with end + 1 >= pos, taken
 // if start <= pos + 1; rid = start = 0 otherwise (:757-789)
 __device__ __forceinline__ void pq_locate(const uint64_t* __restrict__ st, const uint64_t* __restrict__ en, const uint64_t* __restrict__ rid, uint64_t n,
@@ -295,7 +278,7 @@ static unsigned pq_flat_grid(uint64_t C) {
 }
 
 // The whole chain. d_offsets (N + 1) and *total_out are always produced; entries only when *total_out <= cap.
-static hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
+hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
                                uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s) {
     *total_out = 0;
     if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);

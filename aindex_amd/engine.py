@@ -408,6 +408,142 @@ class Index:
         check(lib().aix_positions_locate(self._h, _np_ptr(p), p.shape[0], _np_ptr(rid), _np_ptr(start)), "aix_positions_locate")
         return rid, start
 
+    # ---- batch read retrieval over an attached reads file (aix_readsquery.hip) -----------------
+    def attach_reads(self, buf):
+        """Copy the .reads image (bytes, numpy uint8 array or memmap) to HBM for fetch_reads* / reads_by_kmers."""
+        a = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        check(lib().aix_reads_attach(self._h, _np_ptr(a) if a.shape[0] else None, a.shape[0]), "aix_reads_attach")
+        self._reads_keep = None
+
+    def attach_reads_t(self, t):
+        """Borrow a uint8 device tensor (e.g. synth_reads_t output); it is kept alive by this object."""
+        if t.numel():
+            self._chk_dev(t)
+        check(lib().aix_reads_attach_dev(self._h, vp(t.data_ptr()) if t.numel() else None, t.numel(), _stream_ptr(self.device)), "aix_reads_attach_dev")
+        self._reads_keep = t
+
+    def detach_reads(self):
+        check(lib().aix_reads_detach(self._h), "aix_reads_detach")
+        self._reads_keep = None
+
+    def reads_info(self) -> Tuple[int, int]:
+        """(0 nothing / 1 copied / 2 borrowed, bytes) of the attached reads."""
+        out = (C.c_uint64 * 2)()
+        check(lib().aix_reads_info(self._h, C.byref(out)), "aix_reads_info")
+        return int(out[0]), int(out[1])
+
+    @staticmethod
+    def _take_u8(p, n: int) -> np.ndarray:
+        try:
+            return np.frombuffer(C.string_at(p, n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+        finally:
+            lib().aix_free(p)
+
+    @staticmethod
+    def _rc_arg(revcomp, n: int) -> Optional[np.ndarray]:
+        if revcomp is None or revcomp is False:
+            return None
+        if revcomp is True:
+            return np.ones(n, dtype=np.uint8)
+        r = (np.ascontiguousarray(revcomp).reshape(-1) != 0).astype(np.uint8)
+        if r.shape[0] != n:
+            raise ValueError(f"revcomp holds {r.shape[0]} flags for {n} spans")
+        return r
+
+    def fetch_reads(self, starts, ends, revcomp=None):
+        """(offsets uint64[N + 1], bytes uint8[offsets[N]]): item i = get_read(starts[i], ends[i], revcomp[i]). revcomp: None / bool / N flags."""
+        s = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        e = np.ascontiguousarray(ends, dtype=np.uint64).reshape(-1)
+        if s.shape != e.shape:
+            raise ValueError("starts and ends differ in length")
+        n = s.shape[0]
+        r = self._rc_arg(revcomp, n)
+        po, pb = vp(), vp()
+        check(lib().aix_reads_fetch(self._h, _np_ptr(s) if n else None, _np_ptr(e) if n else None, _np_ptr(r) if n else None, n, C.byref(po), C.byref(pb)),
+              "aix_reads_fetch")
+        offsets = self._take(po, n + 1)
+        return offsets, self._take_u8(pb, int(offsets[n]))
+
+    def fetch_reads_by_rid(self, rids):
+        """(offsets, bytes): item i = get_read_by_rid(rids[i]) over the intervals of attach_ridx."""
+        r = np.ascontiguousarray(rids, dtype=np.uint64).reshape(-1)
+        n = r.shape[0]
+        po, pb = vp(), vp()
+        check(lib().aix_reads_fetch_rid(self._h, _np_ptr(r) if n else None, n, C.byref(po), C.byref(pb)), "aix_reads_fetch_rid")
+        offsets = self._take(po, n + 1)
+        return offsets, self._take_u8(pb, int(offsets[n]))
+
+    def reads_by_kmers(self, kmers, max_reads: int = 100):
+        """(kmer_offsets uint64[N + 1], rid uint64[R], read_offsets uint64[R + 1], bytes uint8): the reads of k-mer i are
+        rid[kmer_offsets[i]:kmer_offsets[i + 1]], read j's bytes are bytes[read_offsets[j]:read_offsets[j + 1]]."""
+        a = _as_u8(kmers, self.k)
+        n = a.shape[0] // self.k
+        pk, pr, po, pb = vp(), vp(), vp(), vp()
+        check(lib().aix_reads_by_kmers(self._h, _np_ptr(a) if n else None, n, max_reads, C.byref(pk), C.byref(pr), C.byref(po), C.byref(pb)), "aix_reads_by_kmers")
+        koff = self._take(pk, n + 1)
+        nr = int(koff[n])
+        rid = self._take(pr, nr)
+        roff = self._take(po, nr + 1)
+        return koff, rid, roff, self._take_u8(pb, int(roff[nr]))
+
+    def _fetch_t(self, what: str, n: int, dev, call):
+        """The sizing call, then the filling call into a tensor of exactly that size (int64 offsets, uint8 bytes)."""
+        import torch
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            check(call(vp(offsets.data_ptr()), None, 0, C.byref(total)), what)
+            t = total.value
+            out = torch.empty(max(t, 1), dtype=torch.uint8, device=dev)[:t]
+            if t:
+                check(call(vp(offsets.data_ptr()), vp(out.data_ptr()), t, C.byref(total)), what)
+        return offsets, out
+
+    def fetch_reads_t(self, starts_t, ends_t, revcomp_t=None):
+        """fetch_reads on int64 device tensors (u64 bit patterns); revcomp_t: uint8 / bool tensor of N flags or None."""
+        self._chk_dev(starts_t)
+        self._chk_dev(ends_t)
+        n = starts_t.numel()
+        if ends_t.numel() != n or (revcomp_t is not None and revcomp_t.numel() != n):
+            raise ValueError("starts, ends and revcomp differ in length")
+        if revcomp_t is not None:
+            self._chk_dev(revcomp_t)
+            if revcomp_t.element_size() != 1:
+                raise ValueError("revcomp must be a uint8 or bool tensor")
+        s, e, r = vp(starts_t.data_ptr()), vp(ends_t.data_ptr()), vp(revcomp_t.data_ptr()) if revcomp_t is not None else None
+        st = _stream_ptr(self.device)
+        return self._fetch_t("aix_reads_fetch_dev", n, starts_t.device,
+                             lambda off, by, cap, tot: lib().aix_reads_fetch_dev(self._h, s if n else None, e if n else None, r if n else None, n, off, by, cap, tot, st))
+
+    def fetch_reads_by_rid_t(self, rids_t):
+        """fetch_reads_by_rid on an int64 device tensor, e.g. the rid output of positions_batch_t(..., locate=True)."""
+        self._chk_dev(rids_t)
+        n = rids_t.numel()
+        r, st = vp(rids_t.data_ptr()), _stream_ptr(self.device)
+        return self._fetch_t("aix_reads_fetch_rid_dev", n, rids_t.device,
+                             lambda off, by, cap, tot: lib().aix_reads_fetch_rid_dev(self._h, r if n else None, n, off, by, cap, tot, st))
+
+    def reads_by_kmers_t(self, kmers_t, max_reads: int = 100):
+        """reads_by_kmers on a uint8 device tensor of N * k bytes: (kmer_offsets, rid, read_offsets int64; bytes uint8) device tensors."""
+        import torch
+        self._chk_dev(kmers_t)
+        n = kmers_t.numel() // self.k
+        dev = kmers_t.device
+        koff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        tot = (C.c_uint64 * 2)()
+        q = vp(kmers_t.data_ptr()) if n else None
+        with torch.cuda.device(dev):
+            st = _stream_ptr(self.device)
+            check(lib().aix_reads_by_kmers_dev(self._h, q, n, max_reads, vp(koff.data_ptr()), None, None, 0, None, 0, C.byref(tot), st), "aix_reads_by_kmers_dev")
+            nr, nb = int(tot[0]), int(tot[1])
+            rid = torch.empty(max(nr, 1), dtype=torch.int64, device=dev)[:nr]
+            roff = torch.zeros(nr + 1, dtype=torch.int64, device=dev)
+            by = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)[:nb]
+            if nr:
+                check(lib().aix_reads_by_kmers_dev(self._h, q, n, max_reads, vp(koff.data_ptr()), vp(rid.data_ptr()), vp(roff.data_ptr()), nr,
+                                                   vp(by.data_ptr()) if nb else None, nb, C.byref(tot), st), "aix_reads_by_kmers_dev")
+        return koff, rid, roff, by
+
     # ---- HBM-resident (torch) entry points: asynchronous on torch's current stream ------------
     def _chk_dev(self, t):
         if not t.is_cuda or t.device.index != self.device:

@@ -762,6 +762,124 @@ class AindexWrapper:
                 break
         return out
 
+    # ---- batch reads (one GPU call per batch over the reads file in HBM; the single-item methods above are untouched) -----
+    def _attach_reads_for_batch(self, ix: Optional[Index] = None) -> Optional[Index]:
+        """Lazy upload of the loaded reads file to the handle of the current mode, once per loaded file. None when there is no handle or
+        no reads (the caller answers through the host methods)."""
+        if ix is None:
+            ix = self._ix13 if self._is_13mer_mode else self._ix23
+        reads = getattr(self, "_reads", None)
+        if ix is None or reads is None:
+            return None
+        key = getattr(self, "_attached_reads", None)
+        if key is None or key[0] is not ix or key[1] is not reads:
+            try:
+                ix.attach_reads(reads)
+            except _lib.AixError as e:
+                if e.status == _lib.AIX_ERR_NOMEM:
+                    raise RuntimeError(f"the reads file ({int(reads.shape[0])} bytes) does not fit the device; the single-item methods still work") from e
+                raise
+            self._attached_reads = (ix, reads)
+        return ix
+
+    @staticmethod
+    def _csr_strings(offsets: np.ndarray, data: np.ndarray) -> List[str]:
+        """latin-1 decode of every CSR item, as the single-item methods give."""
+        s = data.tobytes().decode("latin-1")
+        off = offsets.tolist()
+        return [s[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def get_reads_array(self, starts, ends, revcomp=False):
+        """CSR form of get_read for a batch: (offsets uint64[N + 1], bytes uint8[offsets[N]]); revcomp: one bool or N flags."""
+        s = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        e = np.ascontiguousarray(ends, dtype=np.uint64).reshape(-1)
+        ix = self._attach_reads_for_batch()
+        if ix is not None:
+            return ix.fetch_reads(s, e, revcomp)
+        rc = np.broadcast_to(np.asarray(revcomp, dtype=bool).reshape(-1), s.shape) if np.ndim(revcomp) else np.full(s.shape, bool(revcomp))
+        items = [self.get_read(int(a), int(b), bool(r)).encode("latin-1") for a, b, r in zip(s.tolist(), e.tolist(), rc.tolist())]
+        off = np.zeros(len(items) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
+        return off, np.frombuffer(b"".join(items), dtype=np.uint8).copy()
+
+    def get_reads_batch(self, starts, ends, revcomp=False) -> List[str]:
+        """[get_read(s, e, revcomp) for s, e in zip(starts, ends)] in one GPU call (revcomp: one bool or one flag per item)."""
+        return self._csr_strings(*self.get_reads_array(starts, ends, revcomp))
+
+    def get_reads_by_rid_batch(self, rids) -> List[str]:
+        """[get_read_by_rid(r) for r in rids] in one GPU call; through the host method when the intervals are not on the device."""
+        r = np.ascontiguousarray(rids, dtype=np.uint64).reshape(-1)
+        at = self._attach_for_batch(True)
+        if at is not None and self._ridx_on_device():
+            ix = self._attach_reads_for_batch(at[0])
+            if ix is not None:
+                return self._csr_strings(*ix.fetch_reads_by_rid(r))
+        return [self.get_read_by_rid(int(x)) for x in r.tolist()]
+
+    def get_reads_by_kmers_array(self, kmers, max_reads: int = 100):
+        """CSR form of get_reads_se_by_kmer for a packed batch or a list of k-character items: (kmer_offsets uint64[N + 1], rid uint64[R],
+        read_offsets uint64[R + 1], bytes uint8): k-mer i has the reads rid[kmer_offsets[i]:kmer_offsets[i + 1]], read j the bytes
+        bytes[read_offsets[j]:read_offsets[j + 1]]."""
+        k = 13 if self._is_13mer_mode else 23
+        flat = self._packed(kmers, k)
+        if flat is None and isinstance(kmers, (list, tuple)) and len(kmers) == 0:
+            flat = b""
+        if flat is None:
+            flat = self._join_fixed(kmers, k) if not isinstance(kmers, (str, bytes, bytearray, memoryview, np.ndarray)) else None
+            if flat is None:
+                raise ValueError(f"get_reads_by_kmers_array needs a batch of {k}-character k-mers; use get_reads_by_kmer_batch for mixed lengths")
+        from .engine import _as_u8
+        a = _as_u8(flat, k)
+        n = a.shape[0] // k
+        at = self._attach_for_batch(True) if self.aindex_loaded else None
+        ix = self._attach_reads_for_batch(at[0]) if at is not None and self._ridx_on_device() else None
+        if ix is not None:
+            return ix.reads_by_kmers(a, max_reads)
+        return self._reads_csr_host([bytes(a[i * k:(i + 1) * k]).decode("latin-1") for i in range(n)], max_reads)
+
+    def _reads_csr_host(self, kmers, max_reads: int):
+        """Host path of get_reads_by_kmers_array (intervals not on the device): the loop of get_reads_se_by_kmer, keeping the read ids."""
+        rids, items, counts = [], [], []
+        for s in kmers:
+            n0, seen = len(items), set()
+            for p in (self.get_positions(s) if self.aindex_loaded else []):
+                i = self._interval(p)
+                if i is None or i in seen:
+                    continue
+                seen.add(i)
+                r = int(self._ridx_rid[i])
+                read = self.get_read_by_rid(r)
+                if read:
+                    items.append(read.encode("latin-1"))
+                    rids.append(r)
+                if len(items) - n0 >= max_reads:
+                    break
+            counts.append(len(items) - n0)
+        koff = np.zeros(len(kmers) + 1, dtype=np.uint64)
+        koff[1:] = np.cumsum(counts, dtype=np.uint64)
+        roff = np.zeros(len(items) + 1, dtype=np.uint64)
+        roff[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
+        return koff, np.asarray(rids, dtype=np.uint64), roff, np.frombuffer(b"".join(items), dtype=np.uint8).copy()
+
+    def get_reads_by_kmer_batch(self, kmers, max_reads: int = 100) -> List[List[str]]:
+        """[get_reads_se_by_kmer(s, max_reads) for s in kmers] in one GPU call; items whose length is not the mode's k give [] in place."""
+        k = 13 if self._is_13mer_mode else 23
+        if isinstance(kmers, (str, bytes, bytearray, memoryview, np.ndarray)):
+            koff, _, roff, data = self.get_reads_by_kmers_array(kmers, max_reads)
+            return self._spread_lists(koff.shape[0] - 1, np.arange(koff.shape[0] - 1), koff, self._csr_strings(roff, data))
+        flat, keep = self._split_fixed(kmers, k)
+        if not self.aindex_loaded or keep.shape[0] == 0:
+            return [[] for _ in range(len(kmers))]
+        at = self._attach_for_batch(True)
+        if at is None:
+            return [[] for _ in range(len(kmers))]
+        ix = self._attach_reads_for_batch(at[0]) if self._ridx_on_device() else None
+        if ix is None:
+            fixed = set(keep.tolist())
+            return [self.get_reads_se_by_kmer(s, max_reads) if i in fixed else [] for i, s in enumerate(kmers)]
+        koff, _, roff, data = ix.reads_by_kmers(flat, max_reads)
+        return self._spread_lists(len(kmers), keep, koff, self._csr_strings(roff, data))
+
     def debug_kmer_tf_values(self):
         """:913-936 — for the stored k-mers at slots 1, 10, 100, ...: one line per read that holds an indexed occurrence."""
         if self._ix23 is None:

@@ -425,6 +425,53 @@ int aix_positions_query_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uin
  * (AIX_ERR_ARG otherwise). The _dev twin is asynchronous on `stream`. */
 int aix_positions_locate(aix_index_t* h, const uint64_t* pos, uint64_t N, uint64_t* rid_out, uint64_t* start_out);
 int aix_positions_locate_dev(aix_index_t* h, const uint64_t* d_pos, uint64_t N, uint64_t* d_rid_out, uint64_t* d_start_out, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Batch read retrieval: the reads file in HBM, spans / read ids / k-mers -> the reads' bytes (CSR).
+ * replaces, N at a time, AindexWrapper::get_read_by_rid (python_wrapper.cpp:666-675), get_read (:677-698) and
+ *          get_reads_se_by_kmer (:857-911); aindex.py:162-166 (get_reads_by_kmer) and iter_reads loop over those.
+ * Outputs are CSR: offsets[N + 1] into bytes laid back to back, no separators. The _dev twins follow the sizing convention of
+ * aix_positions_query_dev: offsets and the totals are always produced, the rest only when it fits the caps, nothing is written at or
+ * beyond a cap; they return after the work has completed on `stream`. Host outputs are malloc'd (aix_free).
+ * ------------------------------------------------------------------------------------------ */
+/* The .reads image that AindexWrapper::load_reads maps (python_wrapper.cpp:281-322: reads separated by '\n', mates by '~'), copied to
+ * HBM; aix_info_t::device_bytes grows by len. AIX_ERR_NOMEM when it does not fit (nothing is kept; an earlier attachment stays).
+ * Replaces an earlier attachment. */
+int aix_reads_attach(aix_index_t* h, const char* reads, uint64_t len);
+/* The same (python_wrapper.cpp:281-322) for a buffer already in HBM: borrowed, the caller keeps it alive until detach / close. Waits for
+ * `stream` first. */
+int aix_reads_attach_dev(aix_index_t* h, const char* d_reads, uint64_t len, void* stream);
+/* Drops the reads (the reference unmaps in ~AindexWrapper, python_wrapper.cpp:160-226); aix_index_close does the same.
+ * aix_aindex_detach leaves the reads attached. */
+int aix_reads_detach(aix_index_t* h);
+/* out = {0 nothing / 1 copied / 2 borrowed, bytes} of the attached reads (reads_size of python_wrapper.cpp:281-322). */
+int aix_reads_info(const aix_index_t* h, uint64_t out[2]);
+/* get_read (python_wrapper.cpp:677-698) for N (start, end, revcomp) triples: item i is empty when start >= size || end >= size ||
+ * start > end (a span that ends AT the file size is empty, as there), else the bytes [start, end); where revcomp[i] != 0 (revcomp may be
+ * NULL: none) reversed with A <-> T and C <-> G, every other byte unchanged. AIX_ERR_ARG when no reads are attached. */
+int aix_reads_fetch(aix_index_t* h, const uint64_t* start, const uint64_t* end, const uint8_t* revcomp /* nullable */, uint64_t N,
+                    uint64_t** offsets_out, char** bytes_out);
+/* device-resident twin (python_wrapper.cpp:677-698): d_offsets (N + 1) and *total_out (host) = offsets[N] always; d_bytes (cap bytes) only
+ * when *total_out <= cap. */
+int aix_reads_fetch_dev(aix_index_t* h, const uint64_t* d_start, const uint64_t* d_end, const uint8_t* d_revcomp /* nullable */, uint64_t N,
+                        uint64_t* d_offsets, char* d_bytes, uint64_t cap, uint64_t* total_out, void* stream);
+/* get_read_by_rid (python_wrapper.cpp:666-675) for N read ids: row rid of the intervals of aix_ridx_attach, bytes [start, end) clamped
+ * to the attached buffer; empty when rid >= n_reads. Needs reads and intervals attached (AIX_ERR_ARG otherwise). */
+int aix_reads_fetch_rid(aix_index_t* h, const uint64_t* rid, uint64_t N, uint64_t** offsets_out, char** bytes_out);
+int aix_reads_fetch_rid_dev(aix_index_t* h, const uint64_t* d_rid, uint64_t N, uint64_t* d_offsets, char* d_bytes, uint64_t cap,
+                            uint64_t* total_out, void* stream);   /* python_wrapper.cpp:666-675, sizing as aix_reads_fetch_dev */
+/* What get_reads_se_by_kmer (python_wrapper.cpp:857-911) intends, for N k-mers of the handle's k: for k-mer i the reads that hold one of
+ * its indexed occurrences (aix_positions_query order: slot order), each read once at its first occurrence; occurrences without an interval
+ * are skipped, empty reads are skipped and do not count, and the limit is tested after every distinct read met, so max_reads >= 1 keeps the
+ * first max_reads reads and max_reads == 0 keeps the read of the first located occurrence. Any slot order inside a bucket is handled.
+ * Reads of k-mer i: rid[kmer_offsets[i] .. kmer_offsets[i + 1]), read j's bytes at bytes[read_offsets[j] .. read_offsets[j + 1]).
+ * Needs the positions index, the intervals and the reads attached (AIX_ERR_ARG otherwise). */
+int aix_reads_by_kmers(aix_index_t* h, const char* kmers, uint64_t N, uint64_t max_reads, uint64_t** kmer_offsets_out, uint64_t** rid_out,
+                       uint64_t** read_offsets_out, char** bytes_out);
+/* device-resident twin (python_wrapper.cpp:857-911): d_kmer_offsets (N + 1) and totals_out (host) = {reads R, bytes} always; d_rid (cap_reads)
+ * and d_read_offsets (cap_reads + 1) only when R <= cap_reads, d_bytes (cap_bytes) only when that holds and bytes <= cap_bytes. */
+int aix_reads_by_kmers_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint64_t max_reads, uint64_t* d_kmer_offsets, uint64_t* d_rid,
+                           uint64_t* d_read_offsets, uint64_t cap_reads, char* d_bytes, uint64_t cap_bytes, uint64_t totals_out[2], void* stream);
+
 /* The same normalisation for a buffer already in HBM (byte-identical output; the readers are finite-state transducers,
  * resolved with a parallel scan of per-chunk transition functions). format must be PLAIN, FASTA or FASTQ; d_out holds
  * len+1 bytes; *out_len is a HOST pointer; the call synchronises the stream. */
