@@ -23,9 +23,14 @@ AIX_ERR_ARG = -1
 AIX_ERR_FORMAT = -3
 AIX_ERR_NOMEM = -4
 AIX_ERR_UNSUPPORTED = -6
+AIX_ERR_MODE = -7
 FMT_AUTO, FMT_PLAIN, FMT_FASTA, FMT_FASTQ = -1, 0, 1, 2
 CANON_NONE, CANON_REF_X86, CANON_TRUE_RC = 0, 1, 2
 TOTAL_13MERS = 4 ** 13
+DIR_NEXT, DIR_PREV, DIR_BOTH = 0, 1, 2
+WALK_GREEDY, WALK_UNITIG = 0, 1
+STOP_NAMES = ("max_steps", "dead_end", "branch", "join", "loop")   # AIX_STOP_*
+WALK_MAX_STEPS = 1 << 20
 
 
 class AixError(RuntimeError):
@@ -51,6 +56,16 @@ class IngestStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# aix_cont_t: struct CONT of debrujin.hpp as one 32-byte record
+CONT_FIELDS = [("tf", "<u4", (4,)), ("n", "<u4"), ("sum", "<u4"), ("best_tf", "<u4"), ("best_base", "<u4")]
+
+
+def cont_dtype():
+    """numpy dtype of one aix_cont_t record"""
+    import numpy as np
+    return np.dtype(CONT_FIELDS)
 
 
 _LIB = None
@@ -127,6 +142,10 @@ SIGNATURES = {
     "aix_reads_fetch_rid_dev": (i32, [vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_reads_by_kmers": (i32, [vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "aix_reads_by_kmers_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, u64, vp, u64, C.POINTER(u64 * 2), vp]),
+    "aix_neighbours": (i32, [vp, vp, vp, u64, i32, u32, vp]),
+    "aix_neighbours_dev": (i32, [vp, vp, vp, u64, i32, u32, vp, vp]),
+    "aix_walk": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp]),
+    "aix_walk_dev": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp, vp]),
     "aix_positions_start": (i32, [vp, u64, C.POINTER(u64)]),
     "aix_positions_start_k": (i32, [vp, u64, i32, C.POINTER(u64)]),
     "aix_index_scatter_shard_codes_dev": (i32, [vp, u64, vp, vp, u64, u64, i32, vp, vp, vp, vp]),

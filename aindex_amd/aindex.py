@@ -354,6 +354,18 @@ class AIndex:
             raise RuntimeError("Aindex not loaded")
         return self._wrapper.get_reads_by_kmer_batch(kmers, max_reads)
 
+    def get_next_batch(self, kmers, cutoff: int = 0) -> List[dict]:
+        """The four successors of every 23-mer with their tf (DEBRUJIN::print_next), one GPU call; see AindexWrapper.get_next_batch."""
+        return self._wrapper.get_next_batch(kmers, cutoff)
+
+    def get_prev_batch(self, kmers, cutoff: int = 0) -> List[dict]:
+        """The four predecessors of every 23-mer with their tf (DEBRUJIN::print_prev), one GPU call."""
+        return self._wrapper.get_prev_batch(kmers, cutoff)
+
+    def extend_batch(self, kmers, max_steps: int = 1000, cutoff: int = 0, mode: str = "greedy", direction: str = "next") -> list:
+        """[(extension, stop_name)] along the best continuation of every 23-mer, one GPU call per direction; see AindexWrapper.extend_batch."""
+        return self._wrapper.extend_batch(kmers, max_steps, cutoff, mode, direction)
+
     def get_reads_array(self, starts, ends, revcomp=False):
         """CSR arrays (offsets, bytes uint8); see AindexWrapper.get_reads_array."""
         return self._wrapper.get_reads_array(starts, ends, revcomp)

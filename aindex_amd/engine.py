@@ -544,6 +544,106 @@ class Index:
                                                    vp(by.data_ptr()) if nb else None, nb, C.byref(tot), st), "aix_reads_by_kmers_dev")
         return koff, rid, roff, by
 
+    # ---- De Bruijn neighbours and walks (aix_debruijn.hip) -------------------------------------
+    @staticmethod
+    def _dir(direction, both_ok: bool) -> int:
+        d = {"next": _lib.DIR_NEXT, "prev": _lib.DIR_PREV, "both": _lib.DIR_BOTH}.get(direction, direction)
+        if d not in ((_lib.DIR_NEXT, _lib.DIR_PREV, _lib.DIR_BOTH) if both_ok else (_lib.DIR_NEXT, _lib.DIR_PREV)):
+            raise ValueError(f"direction {direction!r}: 'next', 'prev'" + (" or 'both'" if both_ok else ""))
+        return d
+
+    @staticmethod
+    def _walk_mode(mode) -> int:
+        m = {"greedy": _lib.WALK_GREEDY, "unitig": _lib.WALK_UNITIG}.get(mode, mode)
+        if m not in (_lib.WALK_GREEDY, _lib.WALK_UNITIG):
+            raise ValueError(f"mode {mode!r}: 'greedy' or 'unitig'")
+        return m
+
+    def _kmers_or_codes(self, x):
+        """(codes uint64[N] or None, ascii uint8[N * 23] or None, N): a uint64 array holds 2-bit codes, everything else is what tf_ascii takes."""
+        if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+            c = np.ascontiguousarray(x).reshape(-1)
+            return c, None, c.shape[0]
+        a = _as_u8(x, 23)
+        return None, a, a.shape[0] // 23
+
+    def neighbours(self, kmers_or_codes, direction="next", cutoff: int = 0) -> np.ndarray:
+        """print_next / print_prev for a batch: a structured array (CONT_DTYPE) of N records, or of shape (N, 2) — next, prev — for "both"."""
+        d = self._dir(direction, True)
+        c, a, n = self._kmers_or_codes(kmers_or_codes)
+        out = np.zeros(n * (2 if d == _lib.DIR_BOTH else 1), dtype=_lib.cont_dtype())
+        check(lib().aix_neighbours(self._h, _np_ptr(c) if n else None, _np_ptr(a) if n else None, n, d, cutoff, _np_ptr(out) if n else None), "aix_neighbours")
+        return out.reshape(n, 2) if d == _lib.DIR_BOTH else out
+
+    def walk(self, seeds, max_steps: int, direction="next", cutoff: int = 0, mode="greedy", want_tf: bool = True):
+        """(bases uint8[S, max_steps], length uint32[S], stop uint8[S], tf uint32[S, max_steps] | None, last uint64[S]): row i holds length[i]
+        bases ('A', 'C', 'G', 'T') in the order found and 0 beyond; stop[i] indexes _lib.STOP_NAMES; last = the code the walk ended on."""
+        d, m = self._dir(direction, False), self._walk_mode(mode)
+        c, a, s = self._kmers_or_codes(seeds)
+        if not 1 <= max_steps <= _lib.WALK_MAX_STEPS:
+            raise ValueError(f"max_steps {max_steps}: 1 .. {_lib.WALK_MAX_STEPS}")
+        bases = np.zeros((s, max_steps), dtype=np.uint8)
+        tf = np.zeros((s, max_steps), dtype=np.uint32) if want_tf else None
+        length, stop, last = np.zeros(s, np.uint32), np.zeros(s, np.uint8), np.zeros(s, np.uint64)
+        check(lib().aix_walk(self._h, _np_ptr(c) if s else None, _np_ptr(a) if s else None, s, d, max_steps, cutoff, m, _np_ptr(bases), _np_ptr(length),
+                             _np_ptr(stop), _np_ptr(tf), _np_ptr(last)), "aix_walk")
+        return bases, length, stop, tf, last
+
+    def _kmers_or_codes_t(self, t):
+        import torch
+        self._chk_dev(t)                                            # device and contiguity
+        if t.dtype == torch.int64:
+            return vp(t.data_ptr()), None, t.numel()
+        if t.dtype != torch.uint8 or t.numel() % 23:
+            raise ValueError("k-mers: an int64 tensor of 2-bit codes or a uint8 tensor of N * 23 bytes")
+        return None, vp(t.data_ptr()), t.numel() // 23
+
+    def neighbours_t(self, kmers_or_codes_t, direction="next", cutoff: int = 0, out_t=None):
+        """neighbours on a device tensor (int64 codes or uint8 ASCII): int32 tensor [N, 8] ([N, 2, 8] for "both") holding the u32 words of
+        the records (tf A C G T, n, sum, best_tf, best_base), asynchronous on torch's current stream."""
+        import torch
+        d = self._dir(direction, True)
+        c, a, n = self._kmers_or_codes_t(kmers_or_codes_t)
+        shape = (n, 2, 8) if d == _lib.DIR_BOTH else (n, 8)
+        if out_t is None:
+            out_t = torch.empty(shape, dtype=torch.int32, device=kmers_or_codes_t.device)
+        elif out_t.dtype != torch.int32 or out_t.numel() != 8 * n * (2 if d == _lib.DIR_BOTH else 1) or not out_t.is_contiguous():
+            raise ValueError("out_t must be a contiguous int32 tensor of 8 words per record")
+        with torch.cuda.device(kmers_or_codes_t.device):
+            check(lib().aix_neighbours_dev(self._h, c if n else None, a if n else None, n, d, cutoff, vp(out_t.data_ptr()) if n else None,
+                                           _stream_ptr(self.device)), "aix_neighbours_dev")
+        return out_t
+
+    def walk_t(self, seeds_t, max_steps: int, direction="next", cutoff: int = 0, mode="greedy", want_tf: bool = True, bases_t=None, tf_t=None):
+        """walk on a device tensor of seeds: (bases uint8[S, max_steps], length int32[S], stop uint8[S], tf int32[S, max_steps] | None,
+        last int64[S]) device tensors, asynchronous on torch's current stream. bases_t / tf_t: caller-owned rows to write into (what lies
+        at or beyond a row's length is left as it is); fresh rows are zeroed."""
+        import torch
+        d, m = self._dir(direction, False), self._walk_mode(mode)
+        c, a, s = self._kmers_or_codes_t(seeds_t)
+        if not 1 <= max_steps <= _lib.WALK_MAX_STEPS:
+            raise ValueError(f"max_steps {max_steps}: 1 .. {_lib.WALK_MAX_STEPS}")
+        dev = seeds_t.device
+        if bases_t is None:
+            bases_t = torch.zeros((s, max_steps), dtype=torch.uint8, device=dev)
+        if tf_t is None and want_tf:
+            tf_t = torch.zeros((s, max_steps), dtype=torch.int32, device=dev)
+        for t, dt in ((bases_t, torch.uint8), (tf_t, torch.int32)):
+            if t is not None:
+                if t.dtype != dt or t.numel() != s * max_steps:
+                    raise ValueError(f"bases_t / tf_t must be uint8 / int32 tensors of S * max_steps = {s * max_steps} elements")
+                if t.numel():
+                    self._chk_dev(t)
+        length = torch.zeros(s, dtype=torch.int32, device=dev)
+        stop = torch.zeros(s, dtype=torch.uint8, device=dev)
+        last = torch.zeros(s, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().aix_walk_dev(self._h, c if s else None, a if s else None, s, d, max_steps, cutoff, m, vp(bases_t.data_ptr()) if s else None,
+                                     vp(length.data_ptr()) if s else None, vp(stop.data_ptr()) if s else None,
+                                     vp(tf_t.data_ptr()) if (tf_t is not None and s) else None, vp(last.data_ptr()) if s else None,
+                                     _stream_ptr(self.device)), "aix_walk_dev")
+        return bases_t, length, stop, tf_t, last
+
     # ---- HBM-resident (torch) entry points: asynchronous on torch's current stream ------------
     def _chk_dev(self, t):
         if not t.is_cuda or t.device.index != self.device:

@@ -880,6 +880,64 @@ class AindexWrapper:
         koff, _, roff, data = ix.reads_by_kmers(flat, max_reads)
         return self._spread_lists(len(kmers), keep, koff, self._csr_strings(roff, data))
 
+    # ---- De Bruijn neighbours and extensions (one GPU call per batch) ---------------------------------------------------
+    @staticmethod
+    def _place_conts(n_items: int, keep: np.ndarray, recs: np.ndarray) -> list:
+        """list of n_items dicts: item keep[j] gets the CONT fields of recs[j] (debrujin.hpp; best_hit as a letter), every other item {}."""
+        out = [{} for _ in range(n_items)]
+        tf, n, sm, btf, bb = recs["tf"].tolist(), recs["n"].tolist(), recs["sum"].tolist(), recs["best_tf"].tolist(), recs["best_base"].tolist()
+        for j, i in enumerate(keep.tolist()):
+            a, c, g, t = tf[j]
+            out[i] = {"A": a, "C": c, "G": g, "T": t, "n": n[j], "sum": sm[j], "best_hit": "ACGT"[bb[j]], "best_hit_tf": btf[j]}
+        return out
+
+    @staticmethod
+    def _row_strings(bases: np.ndarray, length: np.ndarray, reverse: bool) -> List[str]:
+        rows = [bases[j, :int(l)].tobytes().decode("latin-1") for j, l in enumerate(length.tolist())]
+        return [r[::-1] for r in rows] if reverse else rows
+
+    @staticmethod
+    def _place_extensions(items, keep: np.ndarray, direction: str, right=None, left=None) -> list:
+        """The answers of extend_batch: right / left = (strings in reading order, stop names) of the kept items; every other item
+        gets an empty answer of the same shape."""
+        both = direction == "both"
+        out = [("", "", "") if both else ("", "") for _ in range(len(items))]
+        for j, i in enumerate(keep.tolist()):
+            if both:
+                out[i] = (left[0][j] + _enc(items[i]).decode("latin-1") + right[0][j], left[1][j], right[1][j])
+            else:
+                one = right if direction == "next" else left
+                out[i] = (one[0][j], one[1][j])
+        return out
+
+    def _neighbours_batch(self, kmers, direction: str, cutoff: int) -> List[dict]:
+        flat, keep = self._split_fixed(kmers, 23)
+        if keep.shape[0] == 0:
+            return [{} for _ in range(len(kmers))]
+        return self._place_conts(len(kmers), keep, self._need23().neighbours(flat, direction, cutoff))
+
+    def get_next_batch(self, kmers, cutoff: int = 0) -> List[dict]:
+        """DEBRUJIN::print_next (debrujin.cpp:30-75) for a list of 23-mers: the CONT fields as a dict per item; items of another length give {}."""
+        return self._neighbours_batch(kmers, "next", cutoff)
+
+    def get_prev_batch(self, kmers, cutoff: int = 0) -> List[dict]:
+        """DEBRUJIN::print_prev (debrujin.cpp:121-167) for a list of 23-mers."""
+        return self._neighbours_batch(kmers, "prev", cutoff)
+
+    def extend_batch(self, kmers, max_steps: int = 1000, cutoff: int = 0, mode: str = "greedy", direction: str = "next") -> list:
+        """Extends every 23-mer along its best continuation (Index.walk): a list of (extension, stop_name); "prev" extensions read left to
+        right; "both" gives (left + kmer + right, stop_left, stop_right). Items of another length give empty strings in place."""
+        if direction not in ("next", "prev", "both"):
+            raise ValueError(f"direction {direction!r}: 'next', 'prev' or 'both'")
+        flat, keep = self._split_fixed(kmers, 23)
+        if keep.shape[0] == 0:
+            return self._place_extensions(kmers, keep, direction)
+        ix, res = self._need23(), {}
+        for d in (("next", "prev") if direction == "both" else (direction,)):
+            bases, length, stop, _, _ = ix.walk(flat, max_steps, d, cutoff, mode, want_tf=False)
+            res[d] = (self._row_strings(bases, length, d == "prev"), [_lib.STOP_NAMES[x] for x in stop.tolist()])
+        return self._place_extensions(kmers, keep, direction, res.get("next"), res.get("prev"))
+
     def debug_kmer_tf_values(self):
         """:913-936 — for the stored k-mers at slots 1, 10, 100, ...: one line per read that holds an indexed occurrence."""
         if self._ix23 is None:

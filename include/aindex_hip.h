@@ -472,6 +472,59 @@ int aix_reads_by_kmers(aix_index_t* h, const char* kmers, uint64_t N, uint64_t m
 int aix_reads_by_kmers_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint64_t max_reads, uint64_t* d_kmer_offsets, uint64_t* d_rid,
                            uint64_t* d_read_offsets, uint64_t cap_reads, char* d_bytes, uint64_t cap_bytes, uint64_t totals_out[2], void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * De Bruijn graph layer: the neighbours of 23-mers with their frequencies, and bounded walks along them.
+ * replaces, N at a time, DEBRUJIN::print_next / print_prev (debrujin.cpp:30-75, 121-167) over PHASH_MAP::get_freq(uint64_t)
+ *          (hash.hpp:123-140: forward strand, then the reverse complement; the forward strand wins).
+ * 23-mer handles only (AIX_ERR_MODE otherwise). A k-mer is given either as a 46-bit code (get_dna23_bitset, first base most
+ * significant; higher bits are ignored) or as 23 ASCII bytes sanitised as get_freq(std::string_view) does (hash.hpp:203-206,
+ * kmers.cpp:12-40: every byte other than upper-case A/C/G/T contributes 0 bits): exactly one of the two pointers is non-NULL.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_DIR_NEXT 0      /* successors:   ((u << 2) | b) & (2^46 - 1), debrujin.cpp:34-37 */
+#define AIX_DIR_PREV 1      /* predecessors: (u >> 2) | (b << 44),        debrujin.cpp:125-128 */
+#define AIX_DIR_BOTH 2      /* aix_neighbours* only: record 2 i = next, 2 i + 1 = prev of k-mer i */
+#define AIX_WALK_GREEDY 0   /* follow the best continuation whatever the degree */
+#define AIX_WALK_UNITIG 1   /* stop where the path branches (out-degree > 1) or joins (in-degree of the successor > 1) */
+#define AIX_STOP_MAX_STEPS 0
+#define AIX_STOP_DEAD_END  1  /* no neighbour above the cutoff */
+#define AIX_STOP_BRANCH    2
+#define AIX_STOP_JOIN      3
+#define AIX_STOP_LOOP      4  /* the next k-mer is the seed again (either strand) */
+#define AIX_WALK_MAX_STEPS 1048576ull   /* bound of max_steps */
+/* struct CONT (debrujin.hpp, filled by debrujin.cpp:30-75 / 121-167) as one 32-byte record: tf[b] = get_freq of neighbour b
+ * (A, C, G, T), set to 0 where tf[b] <= cutoff when cutoff > 0 (:44-49, inclusive); sum in u32 arithmetic (:51); n = non-zero
+ * tf[b] (:52-53); best_base (0..3) = the LAST base whose tf is >= the other three (the four overwriting ifs of :55-74: ties go
+ * to the later letter, all-zero gives T) and best_tf its tf. best_ukmer is the neighbour code of best_base and is not stored. */
+typedef struct {
+    uint32_t tf[4];
+    uint32_t n, sum, best_tf, best_base;
+} aix_cont_t;
+/* print_next / print_prev (debrujin.cpp:30-75, 121-167) for N k-mers (host pointers): out holds N records (dirs NEXT or PREV)
+ * or 2 N (BOTH: k-mer i, direction d at 2 i + d). N = 0 is AIX_OK. */
+int aix_neighbours(aix_index_t* h, const uint64_t* codes /* or NULL */, const char* ascii /* or NULL */, uint64_t N, int dirs,
+                   uint32_t cutoff, aix_cont_t* out);
+/* device-resident twin (debrujin.cpp:30-75, 121-167), asynchronous on `stream`. d_ascii: N * 23 bytes. */
+int aix_neighbours_dev(aix_index_t* h, const uint64_t* d_codes /* or NULL */, const char* d_ascii /* or NULL */, uint64_t N, int dirs,
+                       uint32_t cutoff, aix_cont_t* d_out, void* stream);
+/* S bounded walks, each a chain of print_next (dir NEXT) or print_prev (dir PREV) steps (debrujin.cpp:30-75, 121-167; the
+ * reference has no walk of its own). From cur = seed, at most max_steps (1 .. AIX_WALK_MAX_STEPS, else AIX_ERR_ARG) times:
+ * C = CONT(cur, dir, cutoff); C.n == 0 stops with DEAD_END; in UNITIG mode C.n > 1 stops with BRANCH, and
+ * CONT(C.best_ukmer, the opposite direction, cutoff).n > 1 with JOIN; min(next, revcomp(next)) == min(seed, revcomp(seed))
+ * stops with LOOP; else the base of C.best_base ('A', 'C', 'G', 'T') and C.best_tf are appended and cur = C.best_ukmer.
+ * No presence test is made on the seed. Outputs per seed i: out_len[i], out_stop[i] (AIX_STOP_*), out_last[i] = the last
+ * cur, and rows of stride max_steps: out_bases[i * max_steps + j], out_tf[i * max_steps + j] for j < out_len[i] in the order
+ * found (dir PREV: base 0 is the one left of the seed); a row is left untouched from out_len[i] on. out_tf and out_last may
+ * be NULL. S * max_steps that no buffer can hold is AIX_ERR_NOMEM before anything is allocated; S = 0 is AIX_OK. This host form
+ * uploads the caller's out_bases / out_tf rows before the kernel runs, so that what lies beyond a row's length comes back as it
+ * was: twice the transfer of the padded outputs. */
+int aix_walk(aix_index_t* h, const uint64_t* codes /* or NULL */, const char* ascii /* or NULL */, uint64_t S, int dir,
+             uint64_t max_steps, uint32_t cutoff, int mode, uint8_t* out_bases, uint32_t* out_len, uint8_t* out_stop,
+             uint32_t* out_tf /* nullable */, uint64_t* out_last /* nullable */);
+/* device-resident twin (debrujin.cpp:30-75, 121-167), asynchronous on `stream`; the loop of every seed is bounded by max_steps. */
+int aix_walk_dev(aix_index_t* h, const uint64_t* d_codes /* or NULL */, const char* d_ascii /* or NULL */, uint64_t S, int dir,
+                 uint64_t max_steps, uint32_t cutoff, int mode, uint8_t* d_bases, uint32_t* d_len, uint8_t* d_stop,
+                 uint32_t* d_tf /* nullable */, uint64_t* d_last /* nullable */, void* stream);
+
 /* The same normalisation for a buffer already in HBM (byte-identical output; the readers are finite-state transducers,
  * resolved with a parallel scan of per-chunk transition functions). format must be PLAIN, FASTA or FASTQ; d_out holds
  * len+1 bytes; *out_len is a HOST pointer; the call synchronises the stream. */
