@@ -86,7 +86,8 @@ def cont(freq, codes, direction: int, cutoff: int = 0) -> np.ndarray:
 
 
 def neighbours(freq, codes, dirs: int, cutoff: int = 0) -> np.ndarray:
-    """The layout of aix_neighbours: N records, or (N, 2) for BOTH."""
+    """The layout of aix_neighbours: N records, or (N, 2) for BOTH. Like aix_neighbours (and walk below) it ignores bits 46 .. 63 of a code."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1) & MASK46
     if dirs != BOTH:
         return cont(freq, codes, dirs, cutoff)
     return np.stack([cont(freq, codes, NEXT, cutoff), cont(freq, codes, PREV, cutoff)], axis=1)

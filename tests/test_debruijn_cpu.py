@@ -1,5 +1,7 @@
 """De Bruijn neighbours and walks, host side (no GPU): the committed reference answers against the test-side restatement over the
-oracle, the ABI surface, the public methods, the list surface's placing of wrong-length items, and the argument errors that need no device."""
+oracle, the ABI surface, the public methods, the list surface's placing of wrong-length items, and the argument errors that need no device;
+the graph cases of the GPU fuzz (tests/graph_cases.py): a scalar restatement against the vectorised one, and what the cases must contain."""
+import functools
 import json
 import os
 import re
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 import debruijn_ref as D
+import graph_cases as G
 import oracle_lib as O
 from aindex_amd import _lib
 from aindex_amd.aindex import AIndex
@@ -137,3 +140,187 @@ def test_argument_errors_that_need_no_device():
     with pytest.raises(ValueError):
         Index._walk_mode("eager")
     assert Index._dir("prev", False) == 1 and Index._dir("both", True) == 2 and Index._walk_mode("unitig") == 1
+
+
+# ------------------------------------------------------------------------------------------------
+# The graph cases of test_gpu_fuzz.py::test_fuzz_debruijn. The GPU test compares the kernels with debruijn_ref over the oracle; here
+# debruijn_ref itself is compared with a second statement of the same rules, one k-mer at a time over a dict, and the cases are shown
+# to hold the situations they were built for (a GPU test over a case without them would pass and say nothing).
+# ------------------------------------------------------------------------------------------------
+GRAPH_SEEDS = range(12)
+_M46 = (1 << 46) - 1
+
+
+class Scalar:
+    """get_freq (hash.hpp:123-140), print_next / print_prev (debrujin.cpp:30-75, 121-167) and the bounded walk of include/aindex_hip.h,
+    on Python ints over a dict of the stored codes. Nothing of debruijn_ref is called."""
+
+    def __init__(self, codes, tfs):
+        self.table = dict(zip(codes.tolist(), tfs.tolist()))
+        self.rc_cache, self.cont_cache = {}, {}
+
+    def rc(self, x):
+        y = self.rc_cache.get(x)
+        if y is None:
+            y, v = 0, x
+            for _ in range(23):                                     # the bases in reverse order, each complemented
+                y = (y << 2) | (3 - (v & 3))
+                v >>= 2
+            self.rc_cache[x] = y
+        return y
+
+    def freq(self, kmer):
+        t = self.table.get(kmer)                                    # the k-mer as given; a stored 0 counts as stored
+        if t is not None:
+            return t
+        return self.table.get(self.rc(kmer), 0)                     # not stored: its reverse complement, 0 when that is not stored either
+
+    @staticmethod
+    def neigh(kmer, direction, b):
+        return ((kmer << 2) | b) & _M46 if direction == D.NEXT else (kmer >> 2) | (b << 44)
+
+    def cont(self, kmer, direction, cutoff):
+        """(A, C, G, T, n, sum, best_hit_tf, best_hit 0..3); a pure function of its arguments, kept per k-mer (the walks of a case
+        pass through the same k-mers many times)"""
+        key = (kmer, direction, cutoff)
+        if key not in self.cont_cache:
+            self.cont_cache[key] = self._cont(kmer, direction, cutoff)
+        return self.cont_cache[key]
+
+    def _cont(self, kmer, direction, cutoff):
+        A, C, G, T = (self.freq(self.neigh(kmer, direction, b)) for b in range(4))
+        if cutoff > 0:
+            if A <= cutoff: A = 0
+            if C <= cutoff: C = 0
+            if G <= cutoff: G = 0
+            if T <= cutoff: T = 0
+        total = (A + C + G + T) & 0xFFFFFFFF                        # uint32_t sum
+        n = int(bool(A)) + int(bool(C)) + int(bool(G)) + int(bool(T))
+        best = best_tf = None
+        if A >= C and A >= G and A >= T: best, best_tf = 0, A
+        if C >= A and C >= G and C >= T: best, best_tf = 1, C
+        if G >= C and G >= A and G >= T: best, best_tf = 2, G
+        if T >= C and T >= G and T >= A: best, best_tf = 3, T
+        return A, C, G, T, n, total, best_tf, best
+
+    def walk(self, seed, direction, max_steps, cutoff, mode):
+        """(bases, stop, tf list, last)"""
+        seed &= _M46
+        cur, bases, tfs, stop = seed, [], [], D.MAX_STEPS
+        seed_c = min(seed, self.rc(seed))
+        for _ in range(max_steps):
+            c = self.cont(cur, direction, cutoff)
+            if c[4] == 0:
+                stop = D.DEAD_END
+                break
+            if mode == D.UNITIG and c[4] > 1:
+                stop = D.BRANCH
+                break
+            nxt = self.neigh(cur, direction, c[7])
+            if mode == D.UNITIG and self.cont(nxt, 1 - direction, cutoff)[4] > 1:
+                stop = D.JOIN
+                break
+            if min(nxt, self.rc(nxt)) == seed_c:
+                stop = D.LOOP
+                break
+            bases.append("ACGT"[c[7]])
+            tfs.append(c[6])
+            cur = nxt
+        return "".join(bases), stop, tfs, cur
+
+
+WALK_L = 64
+WALK_LEGS = [(d, m, c) for d in (D.NEXT, D.PREV) for m in (D.GREEDY, D.UNITIG) for c in (0, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def graph_ref(seed):
+    """The case and debruijn_ref's answers over a dict-backed freq: neighbours per (direction, cutoff), walks per (direction, mode, cutoff)."""
+    codes, tfs, seeds = G.make_graph_case(seed)
+    freq = G.dict_freq(codes, tfs)
+    nb = {(d, c): D.neighbours(freq, seeds, d, c) for d in (D.NEXT, D.PREV) for c in (0, 3)}
+    walks = {leg: D.walk(freq, seeds, leg[0], WALK_L, leg[2], leg[1]) for leg in WALK_LEGS}
+    return codes, tfs, seeds, nb, walks
+
+
+def test_graph_case_is_deterministic_and_of_the_promised_shape():
+    for seed in GRAPH_SEEDS:
+        codes, tfs, seeds = G.make_graph_case(seed)
+        again = G.make_graph_case(seed)
+        assert all(np.array_equal(a, b) for a, b in zip((codes, tfs, seeds), again))
+        assert codes.dtype == np.uint64 and tfs.dtype == np.uint32 and seeds.dtype == np.uint64 and codes.shape == tfs.shape
+        assert np.array_equal(codes, np.unique(codes)) and int(codes.max()) <= _M46
+        assert 1000 < codes.shape[0] < 10_000 and seeds.shape[0] <= 20_000
+        canonical = bool(np.all(codes <= D.revcomp(codes)))
+        assert canonical == (seed % 3 == 0), seed                   # mode 0 is the canonical fast path, the other two are not
+        high = (seeds >> np.uint64(46)) != 0
+        assert 0.03 < high.mean() < 0.07
+        stored = np.isin(seeds & D.MASK46, codes)
+        assert stored.sum() >= codes.shape[0] and (~stored & ~np.isin(D.revcomp(seeds & D.MASK46), codes)).sum() >= 500
+        assert set(G.TF_POOL.tolist()) <= set(tfs.tolist())
+
+
+@pytest.mark.parametrize("seed", GRAPH_SEEDS)
+def test_scalar_restatement_equals_the_vectorised_helper(seed):
+    """Every seed's CONT in both directions at cutoff 0 and 3, and every seed's walk in both directions and both modes at cutoff 0 and 3
+    with max_steps 1, 7 and 64, stated one k-mer at a time over a dict == debruijn_ref over a dict-backed freq."""
+    codes, tfs, seeds, nb, walks = graph_ref(seed)
+    sc = Scalar(codes, tfs)
+    kmers = (seeds & D.MASK46).tolist()
+    for (d, cutoff), recs in nb.items():
+        want = np.concatenate([recs["tf"], np.stack([recs["n"], recs["sum"], recs["best_tf"], recs["best_base"]], axis=-1)], axis=-1).tolist()
+        got = [list(sc.cont(k, d, cutoff)) for k in kmers]
+        assert got == want, (seed, d, cutoff)
+    freq = G.dict_freq(codes, tfs)
+    raw = seeds.tolist()                                            # the walk masks bits 46 .. 63 itself
+    for (d, m, cutoff), long_walk in walks.items():
+        for L in (1, 7, WALK_L):
+            bases, length, stop, tf, last = long_walk if L == WALK_L else D.walk(freq, seeds, d, L, cutoff, m)
+            got = [sc.walk(s, d, L, cutoff, m) for s in raw]
+            want = [(bytes(bases[i, :length[i]]).decode(), int(stop[i]), tf[i, :length[i]].tolist(), int(last[i])) for i in range(len(raw))]
+            assert got == want, (seed, d, m, cutoff, L)
+            assert not bases[np.arange(L)[None, :] >= length[:, None]].any()
+
+
+def test_graph_cases_hold_what_they_were_built_for():
+    """Floors over seeds 0 .. 11 together, computed from debruijn_ref alone: the situations the GPU fuzz is there to meet."""
+    stops = np.zeros((2, 5), np.int64)
+    fwd_decides = zero_shadows = wraps = zero_quads = stored_zero_quads = 0
+    ties = {2: 0, 3: 0, 4: 0}
+    at = {2: 0, 3: 0, 4: 0}
+    for seed in GRAPH_SEEDS:
+        codes, tfs, seeds, nb, walks = graph_ref(seed)
+        for (d, m, cutoff), w in walks.items():
+            stops[d] += np.bincount(w[2], minlength=5)
+        k = seeds & D.MASK46
+
+        def stored(x):                                              # (is stored, its tf)
+            i = np.minimum(np.searchsorted(codes, x), codes.shape[0] - 1)
+            return codes[i] == x, tfs[i]
+
+        for d in (D.NEXT, D.PREV):
+            probed = np.stack([D.neigh(k, d, b) for b in range(4)], axis=1)
+            f_in, f_tf = stored(probed)
+            r_in, r_tf = stored(D.revcomp(probed))
+            fwd_decides += int((f_in & r_in & (f_tf != r_tf)).sum())
+            zero_shadows += int((f_in & r_in & (f_tf == 0) & (r_tf > 0)).sum())
+            raw = nb[(d, 0)]["tf"]
+            assert np.array_equal(raw, np.where(f_in, f_tf, np.where(r_in, r_tf, 0)))
+            wraps += int((raw.astype(np.uint64).sum(axis=1) > 0xFFFFFFFF).sum())
+            for v in at:
+                at[v] += int((raw == v).sum())
+            for cutoff in (0, 3):
+                t = nb[(d, cutoff)]["tf"]
+                top = t.max(axis=1)
+                width = (t == top[:, None]).sum(axis=1)
+                for m in ties:
+                    ties[m] += int(((width == m) & (top > 0)).sum())
+                zero_quads += int((top == 0).sum())
+                stored_zero_quads += int(((top == 0) & (f_in | r_in).any(axis=1)).sum())
+    print("stops next", dict(zip(D.STOP_NAMES, stops[0].tolist())), "prev", dict(zip(D.STOP_NAMES, stops[1].tolist())))
+    print("forward decides", fwd_decides, "stored 0 shadows", zero_shadows, "sum wraps", wraps, "ties", ties, "all-zero quads", zero_quads,
+          "of them with a stored neighbour", stored_zero_quads, "tf at 2 / 3 / 4", at)
+    assert (stops >= 50).all(), stops
+    assert fwd_decides >= 200 and zero_shadows >= 50 and wraps >= 10
+    assert min(ties.values()) >= 20 and zero_quads >= 20 and stored_zero_quads >= 20
+    assert min(at.values()) >= 20

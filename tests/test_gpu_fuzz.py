@@ -1,11 +1,14 @@
 """Differential fuzzing: many small random indexes / query sets / read buffers, HIP path vs the oracle."""
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+import debruijn_ref as D
+import graph_cases as G
 import oracle_lib as O
 from aindex_amd import _lib, builder, synth
 from aindex_amd.engine import Index
@@ -45,6 +48,75 @@ def make_case(seed, tmp):
     checker.tofile(prefix + ".kmers.bin")
     tf.tofile(prefix + ".tf.bin")
     return rng, codes, keys, prefix
+
+
+def positions_reference(orc, q, oind, opos):
+    """get_positions_23mer (python_wrapper.cpp:800-831) over get_pfid (hash.hpp:150-170), one k-mer at a time: the strand looked up is
+    the raw 23 bytes if they compare bytewise <= the decode of the reverse complement of their sanitised code, else that decode; its
+    bucket is answered when the hash of those bytes is a slot whose stored code is the strand's sanitised code."""
+    q = np.ascontiguousarray(q, dtype=np.uint8).reshape(-1, 23)
+    rev = D.decode(D.revcomp(D.encode(q)))
+    checker, n = orc.checker(), orc.n
+    out = []
+    for i in range(q.shape[0]):
+        raw, rv = bytes(q[i]), bytes(rev[i])
+        strand = raw if raw <= rv else rv
+        h = orc.hash(strand)
+        if h < n and int(checker[h]) == int(D.encode(strand)[0]):
+            seg = opos[int(oind[h]):min(int(oind[h + 1]), opos.shape[0])]
+            out.append((seg[seg != 0] - np.uint64(1)).tolist())
+        else:
+            out.append([])
+    return out
+
+
+def check_positions_batch(ix, orc, q, tag):
+    """positions_batch over the ORACLE's positions arrays of a buffer that holds the queries themselves, against positions_reference;
+    ix / orc: the same index files with tf small enough for the arrays to be attached. get_pfid only ever looks up the bytewise
+    smaller strand, so a key stored as the larger strand alone has no list: 500 queries for smaller strands stored in their own slot
+    with tf > 0 are added, so that a quarter of the lists are non-empty whatever the strands of the case are. An index that stores no such key (one
+    key, stored as its larger strand) cannot give a non-empty list: there the guard is that every list is empty."""
+    checker, tf = orc.checker(), orc.tf_array()
+    clean = np.unique(checker[checker < np.uint64(4 ** 23)])
+    clean = clean[clean <= D.revcomp(clean)]
+    h = np.minimum(orc.hash_batch(D.decode(clean)), np.uint64(orc.n - 1)).astype(np.int64)     # (a corrupt checker may hold a code in a slot that is not its own)
+    reach = clean[(checker[h] == clean) & (tf[h] > 0)]
+    if reach.shape[0]:
+        q = np.concatenate([q, D.decode(np.resize(reach, 500))])
+    # where the bytewise rule and the numeric one (code <= reverse complement) part: a smaller strand A...T, whose larger strand starts
+    # with A too. The larger strand with '\n' for its first A is numerically the larger and bytewise the smaller: looked up as its raw
+    # bytes, no list. The smaller strand with 'a' for its first A is the other way round: the list of the larger strand, if stored.
+    a = D.decode(reach)
+    edge = reach[(a[:, 0] == ord("A")) & (a[:, 22] == ord("T"))][:100]
+    assert edge.shape[0] or reach.shape[0] < 200, tag
+    if edge.shape[0]:
+        large, small = D.decode(D.revcomp(edge)).copy(), D.decode(edge).copy()
+        large[:, 0], small[:, 0] = ord("\n"), ord("a")
+        q = np.concatenate([q, D.decode(edge), large, small])
+    q = np.ascontiguousarray(q)
+    buf = b"\n".join(bytes(x) for x in q) + b"\n"
+    oind, opos = orc.positions(buf)
+    want = positions_reference(orc, q, oind, opos)
+    nonempty = sum(1 for p in want if p)
+    print(tag, "position lists", len(want), "non-empty", nonempty, "entries", sum(map(len, want)), "keys with a list", reach.shape[0],
+          "of them A...T", edge.shape[0])
+    if reach.shape[0]:
+        assert 4 * nonempty >= len(want), tag
+    else:                                                          # only the smallest indexes of make_case (1 .. 7 keys, 3 trailing entries at most)
+        assert nonempty == 0 and orc.n <= 10, tag
+    ix.attach_aindex(oind, opos)
+    try:
+        for table in (True, False):
+            for filt in (True, False):
+                ix.set_bucket_table(table, 8); ix.set_absence_filter(filt)
+                for m in (0, 1, 3):
+                    off, pos = ix.positions_batch(q, max_per_kmer=m)
+                    off, pos = off.tolist(), pos.tolist()
+                    got = [pos[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+                    assert got == [p[:m] if m else p for p in want], (tag, table, filt, m)
+    finally:
+        ix.set_bucket_table(True, 8); ix.set_absence_filter(True)
+        ix.detach_aindex()
 
 
 @pytest.mark.parametrize("seed", _seeds(24))
@@ -99,6 +171,10 @@ def test_fuzz_queries_counts_positions(seed, tmp_path):
             wind, wpos = ix_small.positions_fill(buf)
             sind, spos, _ = positions_by_shards(ix_small, buf, world)
             assert np.array_equal(sind, wind) and np.array_equal(spos, wpos), (seed, world)
+            # batch position queries (the strand rule of get_pfid) on the same small-tf index, over the oracle's arrays
+            np.minimum(tfv, 3).astype(np.uint32).tofile(prefix + ".tf3.bin")
+            orc_small = O.OracleIndex23(prefix + ".pf", prefix + ".tf3.bin", prefix + ".kmers.bin")
+            check_positions_batch(ix_small, orc_small, q[:1500], ("positions", seed, seed % 3))
         n = ck.shape[0]
         perm = rng.permutation(n)                                         # the .dat order is not the slot order
         cuts = [0] + sorted(int(x) for x in rng.integers(0, n + 1, size=world - 1)) + [n]
@@ -202,11 +278,9 @@ def test_fuzz_normalise_and_distinct(seed):
             del os.environ["AIX_DISTINCT_PIECE"]
 
 
-@pytest.mark.parametrize("seed", _seeds(10))
-def test_fuzz_corrupt_index_files(seed, tmp_path):
-    """Index files that disagree with the MPHF (swapped / foreign / duplicated / out-of-range codes, short tf file,
-    extra trailing entries): the HIP path must answer exactly like the reference's evaluator on the same files."""
-    rng, codes, keys, prefix = make_case(3_000_000 + seed, str(tmp_path))
+def corrupt_index_files(rng, prefix, p2):
+    """Copy the index files of `prefix` to `p2` with a checker that disagrees with the MPHF (swapped / foreign / duplicated / out-of-range
+    codes, the reverse complement of another key), maybe extra trailing entries and a short tf file. Returns the corrupt checker."""
     checker = np.fromfile(prefix + ".kmers.bin", dtype=np.uint64)
     tf = np.fromfile(prefix + ".tf.bin", dtype=np.uint32)
     n = checker.shape[0]
@@ -227,11 +301,19 @@ def test_fuzz_corrupt_index_files(seed, tmp_path):
     if extra:
         checker = np.concatenate([checker, rng.integers(0, 4 ** 23, size=extra, dtype=np.uint64)])
         tf = np.concatenate([tf, rng.integers(1, 9, size=extra).astype(np.uint32)])
-    p2 = os.path.join(str(tmp_path), "c")
     checker.tofile(p2 + ".kmers.bin")
     tf[: max(0, tf.shape[0] - int(rng.integers(0, 3)))].tofile(p2 + ".tf.bin")          # tf file may be short (hash.cpp:431-444)
-    import shutil
     shutil.copy(prefix + ".pf", p2 + ".pf")
+    return checker
+
+
+@pytest.mark.parametrize("seed", _seeds(10))
+def test_fuzz_corrupt_index_files(seed, tmp_path):
+    """Index files that disagree with the MPHF (swapped / foreign / duplicated / out-of-range codes, short tf file,
+    extra trailing entries): the HIP path must answer exactly like the reference's evaluator on the same files."""
+    rng, codes, keys, prefix = make_case(3_000_000 + seed, str(tmp_path))
+    p2 = os.path.join(str(tmp_path), "c")
+    checker = corrupt_index_files(rng, prefix, p2)
     orc = O.OracleIndex23.from_prefix(p2)
     allc = np.unique(np.concatenate([codes, checker & np.uint64(4 ** 23 - 1)]))
     q = np.concatenate([synth.decode_kmers(allc, 23), synth.decode_kmers(synth.revcomp_codes(allc, 23), 23),
@@ -260,3 +342,229 @@ def test_fuzz_corrupt_index_files(seed, tmp_path):
         ind, pos = ix.positions_fill(buf)
         oind, opos = orc.positions(buf)
         assert np.array_equal(ind, oind) and np.array_equal(pos, opos)
+    # batch position queries on the corrupt files (one tf of the case is 2^32-1: the same files with tf <= 3, so that the arrays can be
+    # attached). Queries: the codes of the original and of the corrupt checker and their reverse complements, repeated where the index
+    # is tiny (many lists then read one bucket), and the noisy tail of q.
+    p3 = os.path.join(str(tmp_path), "c3")
+    checker.tofile(p3 + ".kmers.bin")
+    np.minimum(orc.tf_array(), 3).astype(np.uint32).tofile(p3 + ".tf.bin")
+    shutil.copy(p2 + ".pf", p3 + ".pf")
+    both = np.stack([allc, synth.revcomp_codes(allc, 23)], axis=1).reshape(-1)
+    pq = np.concatenate([synth.decode_kmers(np.resize(both, 1100), 23), q[-400:]])
+    with Index.open_23(p3 + ".pf", p3 + ".tf.bin", p3 + ".kmers.bin") as ix3:
+        check_positions_batch(ix3, O.OracleIndex23.from_prefix(p3), pq, ("positions, corrupt files", seed))
+
+
+# ------------------------------------------------------------------------------------------------
+# De Bruijn neighbours and walks (aix_debruijn.hip) on graph cases: keys with neighbours, both strands stored with different tf, stored
+# tf of 0 and of 2^32-1, ties, sums that wrap (tests/graph_cases.py; tests/test_debruijn_cpu.py shows that the cases hold all that)
+# ------------------------------------------------------------------------------------------------
+CANARY8, CANARY32 = 0xEE, 0xEEEEEEEE
+DIRTY = np.frombuffer(b"acgtnN~\n\x00" + bytes(range(0x80, 0x100)), dtype=np.uint8)
+DBJ_WALKS = [(d, m, c) for d in (D.NEXT, D.PREV) for m in (D.GREEDY, D.UNITIG) for c in (0, 3)]
+DBJ_TAILS = (1, 3, 15, 16, 17, 63, 64, 65, 255, 257)
+
+
+def _rows(recs):
+    """CONT records -> int array [..., 8]: tf A C G T, n, sum, best_tf, best_base"""
+    return np.concatenate([recs["tf"], np.stack([recs["n"], recs["sum"], recs["best_tf"], recs["best_base"]], axis=-1)], axis=-1).astype(np.int64)
+
+
+def _dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int64).copy() if a.dtype == np.uint64 else a.reshape(-1).copy()).cuda()
+
+
+def _dirty_ascii(rng, codes):
+    """The k-mers as ASCII with bytes outside upper-case ACGT (lower case, N, ~, newline, 0x00, 0x80 .. 0xFF) planted in about a tenth of them"""
+    a = D.decode(codes & D.MASK46).copy()
+    hit = np.nonzero(rng.random(a.shape[0]) < 0.1)[0]
+    for _ in range(3):                                             # one to three bytes per dirty item
+        a[hit, rng.integers(0, 23, hit.shape[0])] = DIRTY[rng.integers(0, DIRTY.shape[0], hit.shape[0])]
+        hit = hit[rng.random(hit.shape[0]) < 0.5]
+    return a
+
+
+class DbjCase:
+    """One index and one seed set: debruijn_ref's answers over `freq` (computed once per leg and kept) against the device entry points,
+    which write into canary-filled tensors 64 records / rows longer than the batch."""
+
+    def __init__(self, ix, freq, seeds, rng):
+        self.ix, self.freq = ix, freq
+        self.codes = np.ascontiguousarray(seeds)
+        self.ascii = _dirty_ascii(rng, seeds)
+        self.src = {"codes": self.codes, "ascii": D.encode(self.ascii)}     # what the reference walks from
+        self.t = {"codes": _dev(self.codes), "ascii": _dev(self.ascii)}
+        assert (self.src["ascii"] != (self.codes & D.MASK46)).mean() > 0.03
+        self._nb, self._walk = {}, {}
+
+    def nb_ref(self, form, cutoff):
+        """int64 [S, 2, 8]: next, prev"""
+        if (form, cutoff) not in self._nb:
+            self._nb[(form, cutoff)] = _rows(D.neighbours(self.freq, self.src[form], D.BOTH, cutoff))
+        return self._nb[(form, cutoff)]
+
+    def walk_ref(self, form, d, m, L, cutoff):
+        key = (form, d, m, L, cutoff)
+        if key not in self._walk:
+            self._walk[key] = D.walk(self.freq, self.src[form], d, L, cutoff, m)
+        return self._walk[key]
+
+    def neighbours(self, form, direction, cutoff, tag, count=None):
+        import torch
+        n = self.codes.shape[0] if count is None else count
+        t = self.t[form][: n * (23 if form == "ascii" else 1)]
+        recs = n * (2 if direction == D.BOTH else 1)
+        big = torch.full((recs + 64, 8), CANARY32 - (1 << 32), dtype=torch.int32, device="cuda")
+        self.ix.neighbours_t(t, direction, cutoff, out_t=big[:recs])
+        got = big.cpu().numpy().view(np.uint32)
+        assert (got[recs:] == CANARY32).all(), (tag, "records beyond the batch were written")
+        ref = self.nb_ref(form, cutoff)[:n]
+        want = ref.reshape(-1, 8) if direction == D.BOTH else ref[:, direction]
+        bad = np.nonzero((got[:recs].astype(np.int64) != want).any(axis=1))[0]
+        assert bad.shape[0] == 0, (tag, "first differing record", int(bad[0]), got[bad[0]].tolist(), want[bad[0]].tolist(), "of", bad.shape[0])
+
+    def walk(self, form, d, m, L, cutoff, want_tf, tag, count=None):
+        import torch
+        s = self.codes.shape[0] if count is None else count
+        t = self.t[form][: s * (23 if form == "ascii" else 1)]
+        bases = torch.full((s + 64, L), CANARY8, dtype=torch.uint8, device="cuda")
+        tfs = torch.full((s + 64, L), CANARY32 - (1 << 32), dtype=torch.int32, device="cuda") if want_tf else None
+        b, ln, st, tf, last = self.ix.walk_t(t, L, d, cutoff, m, want_tf=want_tf, bases_t=bases[:s], tf_t=tfs[:s] if want_tf else None)
+        assert (tf is None) == (not want_tf)
+        wb, wl, ws, wt, wlast = (x[:s] for x in self.walk_ref(form, d, m, L, cutoff))
+        inside = np.arange(L)[None, :] < wl[:, None]
+        assert np.array_equal(ln.cpu().numpy().view(np.uint32), wl), (tag, "length")
+        assert np.array_equal(st.cpu().numpy(), ws), (tag, "stop")
+        assert np.array_equal(last.cpu().numpy().view(np.uint64), wlast), (tag, "last")
+        got_b = bases.cpu().numpy()
+        assert np.array_equal(got_b[:s], np.where(inside, wb, CANARY8)), (tag, "bases up to the length, the canary from there on")
+        assert (got_b[s:] == CANARY8).all(), (tag, "rows beyond the batch were written")
+        if want_tf:
+            got_t = tfs.cpu().numpy().view(np.uint32)
+            assert np.array_equal(got_t[:s], np.where(inside, wt, CANARY32)), (tag, "tf")
+            assert (got_t[s:] == CANARY32).all(), (tag, "tf rows beyond the batch were written")
+        return ws
+
+    def every_leg(self, tag, steps=(1, 7, 64)):
+        """neighbours: NEXT / PREV / BOTH x cutoff 0, 3 x codes, dirty ASCII; walks: direction x mode x max_steps x cutoff x want_tf"""
+        for cutoff in (0, 3):
+            for form in ("codes", "ascii"):
+                for direction in (D.NEXT, D.PREV, D.BOTH):
+                    self.neighbours(form, direction, cutoff, tag + ("neighbours", form, direction, cutoff))
+        hist = np.zeros(5, np.int64)
+        for d, m, cutoff in DBJ_WALKS:
+            for L in steps:
+                for want_tf in (True, False):
+                    ws = self.walk("codes", d, m, L, cutoff, want_tf, tag + ("walk", d, m, L, cutoff, want_tf))
+                hist += np.bincount(ws, minlength=5)
+        self.walk("ascii", D.NEXT, D.UNITIG, 7, 0, True, tag + ("walk from dirty ASCII",))
+        self.walk("ascii", D.PREV, D.GREEDY, 7, 3, False, tag + ("walk from dirty ASCII",))
+        return hist
+
+
+@pytest.mark.parametrize("seed", _seeds(12))
+def test_fuzz_debruijn(seed, tmp_path, monkeypatch):
+    """De Bruijn neighbours and walks on a graph case (canonical / strand met first / mixed, a third of the keys with both strands stored
+    and different tf) == debruijn_ref over the oracle on the same files: every direction, cutoff, input form, walk mode and max_steps;
+    every absence-filter policy, verification-table shape and the canonical fast path on and off; batches of 1 .. 257 seeds."""
+    prefix, codes, tfs, seeds = G.write_graph_case(seed, str(tmp_path))
+    rng = np.random.default_rng(5_000_000 + seed)
+    freq = D.oracle_freq(O.OracleIndex23.from_prefix(prefix))
+    with Index.open_23(prefix + ".pf", prefix + ".tf.bin", prefix + ".kmers.bin") as ix:
+        assert ix.canonical_only == bool(np.all(codes <= D.revcomp(codes))) == (seed % 3 == 0)
+        case = DbjCase(ix, freq, seeds, rng)
+        tag = ("debruijn", seed, "mode", seed % 3, "keys", codes.shape[0], "seeds", seeds.shape[0])
+        hist = case.every_leg(tag)
+        print(*tag, "stop histogram of the reference", dict(zip(D.STOP_NAMES, hist.tolist())))
+        assert (hist > 0).all()
+        # the switches: one neighbours leg and one walk leg per combination
+        k = 0
+        for policy in ("0", "1", "2"):
+            monkeypatch.setenv("AIX_DBJ_FILTER", policy)
+            for table, lanes in ((True, 8), (True, 1 << (seed % 3)), (False, 0)):
+                for fast in (True, False):
+                    ix.set_bucket_table(table, lanes); ix.set_canonical_fastpath(fast)
+                    sw = tag + ("filter policy", policy, "table", table, lanes, "fast path", fast)
+                    case.neighbours("codes", D.BOTH, 3 * (k % 2), sw)
+                    d, m, cutoff = DBJ_WALKS[(k + seed) % len(DBJ_WALKS)]
+                    case.walk("codes", d, m, 64, cutoff, k % 2 == 0, sw + ("walk", d, m, cutoff))
+                    k += 1
+        assert k == 18
+        monkeypatch.delenv("AIX_DBJ_FILTER")
+        ix.set_bucket_table(True, 8); ix.set_canonical_fastpath(True)
+        # batch tails: a partial last quad group, a partial wave, a partial workgroup
+        for j, n in enumerate(DBJ_TAILS):
+            case.neighbours("codes", D.BOTH, 0, tag + ("first", n), count=n)
+            d, m, cutoff = DBJ_WALKS[(j + seed) % len(DBJ_WALKS)]
+            case.walk("codes", d, m, 7, cutoff, True, tag + ("first", n, "walk", d, m, cutoff), count=n)
+
+
+@pytest.mark.parametrize("seed", _seeds(6))
+def test_fuzz_debruijn_corrupt_index(seed, tmp_path):
+    """The corruption of test_fuzz_corrupt_index_files applied to a graph case: overflowed buckets, unfiled keys, codes with bits
+    46 .. 63 set, foreign and duplicate codes reach the quad-layout probes of the De Bruijn kernels; == debruijn_ref over the oracle on
+    the corrupt files, with the fingerprint filter and the early exit on and off."""
+    prefix, codes, tfs, seeds = G.write_graph_case(1000 + seed, str(tmp_path))
+    rng = np.random.default_rng(6_000_000 + seed)
+    p2 = os.path.join(str(tmp_path), "c")
+    checker = corrupt_index_files(rng, prefix, p2)
+    assert (checker[: codes.shape[0]] != np.fromfile(prefix + ".kmers.bin", dtype=np.uint64)).mean() > 0.03
+    # the codes the corruption brought in and their reverse complements are seeds too
+    foreign = np.setdiff1d(checker, codes)
+    seeds = np.concatenate([seeds, foreign, D.revcomp(foreign & D.MASK46)])
+    freq = D.oracle_freq(O.OracleIndex23.from_prefix(p2))
+    with Index.open_23(p2 + ".pf", p2 + ".tf.bin", p2 + ".kmers.bin") as ix:
+        case = DbjCase(ix, freq, seeds, rng)
+        for fp in (True, False):
+            for ee in (True, False):
+                ix.set_fingerprint_filter(fp); ix.set_early_exit(ee); ix.set_bucket_table(seed % 2 == 0 or fp, 8 >> (seed % 4))
+                tag = ("debruijn, corrupt files", seed, "mode", (1000 + seed) % 3, "fingerprints", fp, "early exit", ee)
+                hist = case.every_leg(tag)
+                print(*tag, "stop histogram of the reference", dict(zip(D.STOP_NAMES, hist.tolist())))
+                assert (hist > 0).all()
+
+
+def test_neighbours_second_trip_of_the_grid_stride_loop(gold, monkeypatch):
+    """k_db_neighbours runs on at most 65 536 workgroups of 64 records: from 4 194 304 records on a workgroup makes a second trip of
+    its loop, with the absence-filter state of the first. 2^21 + 37 seeds in both directions and 2^22 + 53 seeds in one: every record of
+    the second trip and 20 000 sampled ones of the first equal the helper's, and the whole output equals the same call made in chunks
+    of 2^20 seeds (HIP against HIP; batches of that size are what the other tests compare with the oracle), under the gauge policy and
+    the always-on policy of the filter.
+    k_db_walk is capped at 2^22 workgroups of 64 seeds: its loop makes a second trip from 2^28 seeds on, which no test of a few seconds
+    can reach; its trip is the body of this kernel's trip around the same probe."""
+    import torch
+    FIRST_TRIP = 65536 * 64
+    p = os.path.join(gold, "small23", "small23")
+    freq = D.oracle_freq(O.OracleIndex23.from_prefix(p), threads=8)
+    with Index.open_23(p + ".pf", p + ".tf.bin", p + ".kmers.bin") as ix:
+        checker = ix.checker_array()
+        rng = np.random.default_rng(9)
+        for n, direction, cutoff in (((1 << 21) + 37, D.BOTH, 0), (FIRST_TRIP + 53, D.NEXT, 2)):
+            per = 2 if direction == D.BOTH else 1
+            recs = n * per
+            assert recs > FIRST_TRIP
+            seeds = rng.integers(0, 1 << 46, n, dtype=np.uint64)
+            stored_at = np.concatenate([rng.choice(n - 200, n // 50, replace=False), np.arange(n - 200, n, 2)])   # about 2 %, and half of the last 200
+            keys = checker[rng.integers(0, checker.shape[0], stored_at.shape[0])]
+            seeds[stored_at] = np.where(rng.random(stored_at.shape[0]) < 0.5, keys, D.revcomp(keys))
+            t = torch.from_numpy(seeds.view(np.int64)).cuda()
+            sample = np.unique(np.concatenate([rng.integers(0, n, 20_000 // per), np.arange((FIRST_TRIP // per) - 100, n)]))
+            assert (sample * per >= FIRST_TRIP).sum() >= (37 if per == 2 else 53)
+            want = _rows(D.neighbours(freq, seeds[sample], direction, cutoff)).reshape(sample.shape[0], per * 8)
+            assert (want.reshape(-1, 8)[:, 4] > 0).mean() > 0.01
+            sample_t = torch.from_numpy(sample).cuda()
+            for policy in ("0", "1"):
+                monkeypatch.setenv("AIX_DBJ_FILTER", policy)
+                whole = ix.neighbours_t(t, direction, cutoff)
+                pieces = torch.full_like(whole, -1)
+                for lo in range(0, n, 1 << 20):
+                    ix.neighbours_t(t[lo:lo + (1 << 20)], direction, cutoff, out_t=pieces[lo:lo + (1 << 20)])
+                torch.cuda.synchronize()
+                got = whole.reshape(n, per * 8)[sample_t].cpu().numpy().view(np.uint32).astype(np.int64)
+                bad = np.nonzero((got != want).any(axis=1))[0]
+                assert bad.shape[0] == 0, (n, policy, "first differing seed", int(sample[bad[0]]), "of", bad.shape[0])
+                assert torch.equal(whole, pieces), (n, policy)
+                print("seeds", n, "records", recs, "policy", policy, "sampled seeds", sample.shape[0], "records with a neighbour",
+                      int((want.reshape(-1, 8)[:, 4] > 0).sum()))
