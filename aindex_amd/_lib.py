@@ -146,6 +146,10 @@ SIGNATURES = {
     "aix_neighbours_dev": (i32, [vp, vp, vp, u64, i32, u32, vp, vp]),
     "aix_walk": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp]),
     "aix_walk_dev": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp, vp]),
+    "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "aix_seq_hits_dev": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_seq_votes": (i32, [vp, vp, vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "aix_seq_votes_dev": (i32, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_positions_start": (i32, [vp, u64, C.POINTER(u64)]),
     "aix_positions_start_k": (i32, [vp, u64, i32, C.POINTER(u64)]),
     "aix_index_scatter_shard_codes_dev": (i32, [vp, u64, vp, vp, u64, u64, i32, vp, vp, vp, vp]),

@@ -354,6 +354,14 @@ class AIndex:
             raise RuntimeError("Aindex not loaded")
         return self._wrapper.get_reads_by_kmer_batch(kmers, max_reads)
 
+    def get_sequence_hits_array(self, seqs, max_per_kmer: int = 0):
+        """CSR arrays (seq_offsets, qoff, pos, rid, local, flag) of the seed hits of every sequence; see AindexWrapper.get_sequence_hits_array."""
+        return self._wrapper.get_sequence_hits_array(seqs, max_per_kmer)
+
+    def map_sequences(self, seqs, min_votes: int = 2, max_per_kmer: int = 0) -> List[List[tuple]]:
+        """Per sequence [(rid, strand, diag, votes, q_first, q_last)], one GPU call; see AindexWrapper.map_sequences."""
+        return self._wrapper.map_sequences(seqs, min_votes, max_per_kmer)
+
     def get_next_batch(self, kmers, cutoff: int = 0) -> List[dict]:
         """The four successors of every 23-mer with their tf (DEBRUJIN::print_next), one GPU call; see AindexWrapper.get_next_batch."""
         return self._wrapper.get_next_batch(kmers, cutoff)

@@ -170,6 +170,8 @@ namespace aix {
 hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
                         uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s);
 }
+// (the parts of that chain shared with aix_seqhits.hip — pq_resolve23_words, pq_locate, and posquery_lists = the chain behind the resolve
+// step — are declared in aix_posquery.hpp, which includes this header)
 // releases the attached reads file (aix_readsquery.hip); the caller has switched to the handle's device
 void readsquery_release(aix_index* h);
 

@@ -17,6 +17,8 @@
 //     per list; scan of kept = offsets[]
 //   5 k_pq_flat<true>    the same walk; a non-zero entry goes to offsets[i] + (its rank - rank of its list's start) when that is below
 //                        max_per_kmer, minus one (0-based); rid / offset in read by per-lane bisection of the interval ends in the same pass
+// Step 1 ends in pq_resolve23_words and steps 2 to 5 are posquery_lists (both aix_posquery.hpp): aix_seqhits.hip resolves the windows of
+// sequences with the first and runs the second on them.
 // Zeros are skipped wherever they sit (the fill leaves them wherever a window was not placed). Every size, offset and flat index is 64 bits wide.
 // No atomics; all stores are plain vector stores.
 #include <algorithm>
@@ -27,7 +29,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "aix_handle.hpp"
+#include "aix_posquery.hpp"
 
 namespace aix {
 
@@ -55,21 +57,7 @@ __global__ void __launch_bounds__(kB) k_pq_validate(const uint64_t* __restrict__
 // ---------------------------------------------------------------------------------------------
 // 1. k-mer -> bucket -> (source start, upper bound)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t pq_bswap(uint64_t x) { return __builtin_bswap64(x); }
-
-__device__ __forceinline__ void pq_emit(const uint64_t* __restrict__ indices, uint64_t total, uint64_t n, uint64_t h, uint64_t& lo, uint64_t& ub) {
-    lo = 0; ub = 0;
-    if (h < n) {
-        lo = indices[h];
-        const uint64_t hi = min(indices[h + 1], total);                         // clamped to the positions array, as get_positions_13mer does (:1091)
-        ub = hi > lo ? hi - lo : 0;
-    }
-}
-
-// PHASH_MAP::get_pfid (hash.hpp:150-170): the strand looked up is the query's raw bytes if they compare (byte-wise) <= the decode of the
-// reverse complement of their sanitised code, else that decode. Not the rule of k_a2_probe (numeric code <= rc, skip on \n ~ N): the two
-// coincide on clean upper-case ACGT only. A forward strand with bytes outside ACGT hashes its RAW bytes, which the verification table
-// cannot answer: MPHF path.
+// (pq_emit, the get_pfid strand rule and the probe behind it: pq_resolve23_words, aix_posquery.hpp)
 template <int LPP>
 __global__ void __launch_bounds__(kB) k_pq_resolve23(const IndexDev ix, const uint8_t* __restrict__ q, uint64_t N, const uint64_t* __restrict__ indices,
                                                     uint64_t total, uint64_t* __restrict__ lo_out, uint64_t* __restrict__ ub_out) {
@@ -79,33 +67,9 @@ __global__ void __launch_bounds__(kB) k_pq_resolve23(const IndexDev ix, const ui
         const bool in = i < N;
         uint64_t w0 = 0, w1 = 0, w2 = 0;
         if (in) load23(q + 23 * i, w0, w1, w2);
-        const Enc23 e = encode23_words(w0, w1, w2);                             // get_dna23_bitset: non-ACGT -> 0
-        const uint64_t r = revcomp(e.code, 23);
-        uint64_t r0, r1, r2;
-        ascii23_of_rc(e.code, r0, r1, r2);                                      // decode(reverseDNA(code))
-        const uint64_t a0 = pq_bswap(w0), b0 = pq_bswap(r0), a1 = pq_bswap(w1), b1 = pq_bswap(r1), a2 = pq_bswap(w2), b2 = pq_bswap(r2);
-        const bool fwd = a0 != b0 ? a0 < b0 : (a1 != b1 ? a1 < b1 : a2 <= b2);  // bytes <= rev, first byte most significant
-        const uint64_t want = fwd ? e.code : r;
-        const uint64_t x0 = fwd ? w0 : r0, x1 = fwd ? w1 : r1, x2 = fwd ? w2 : r2;
-        const bool tab = in && (e.valid || !fwd);                               // the hashed bytes are the ASCII of `want`
-        uint64_t a = 0, b = 0, c = 0;
-        if (in) jenkins23(x0, x1, x2, ix.m.seed, a, b, c);
-        bool mphf = in;
-        uint64_t h = ix.n;
-        if (ix.bk) {
-            const BkRes k = bucket_probe_wave<LPP>(ix.bk, ix.nb, tab, a, want);
-            if (tab) {
-                if (k.found) h = k.slot;
-                mphf = !k.found && k.overflow;
-            }
-        }
-        if (mphf) {
-            const uint64_t s = mphf_from_hash(ix.m, a, b, c);
-            if (s < ix.n && key_at(ix, s).code == want) h = s;                  // h < n and checker[h] == code of the strand looked up
-        }
+        uint64_t lo, ub;
+        pq_resolve23_words<LPP>(ix, in, w0, w1, w2, indices, total, lo, ub);
         if (in) {
-            uint64_t lo, ub;
-            pq_emit(indices, total, ix.n, h, lo, ub);
             lo_out[i] = lo;
             ub_out[i] = ub;
         }
@@ -151,24 +115,7 @@ __global__ void __launch_bounds__(kB) k_pq_compact(uint64_t N, const uint64_t* _
 // ---------------------------------------------------------------------------------------------
 // 3 / 5. the flat passes
 // ---------------------------------------------------------------------------------------------
-// (the tile's first list is found with wave_count_le, aix_device.hpp)
-// IntervalTree::query(pos, pos + 1) of python_wrapper.cpp:66-74 on sorted, disjoint intervals: the first interval with end + 1 >= pos, taken
-// if start <= pos + 1; rid = start = 0 otherwise (:757-789)
-__device__ __forceinline__ void pq_locate(const uint64_t* __restrict__ st, const uint64_t* __restrict__ en, const uint64_t* __restrict__ rid, uint64_t n,
-                                          uint64_t p, uint64_t& r, uint64_t& s) {
-    const uint64_t key = p ? p - 1 : 0;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (en[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    r = 0; s = 0;
-    if (lo < n) {
-        const uint64_t sv = st[lo];
-        if (sv <= p || sv == p + 1) { r = rid[lo]; s = sv; }
-    }
-}
-
+// (the tile's first list is found with wave_count_le, aix_device.hpp; pq_locate: aix_posquery.hpp)
 struct PqFlat {
     const uint64_t* positions;     // the attached array
     const uint64_t* ne;            // [J] k-mer of list j
@@ -277,27 +224,16 @@ static unsigned pq_flat_grid(uint64_t C) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, 4096));
 }
 
-// The whole chain. d_offsets (N + 1) and *total_out are always produced; entries only when *total_out <= cap.
-hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
-                               uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s) {
+// Steps 2 to 5 (aix_posquery.hpp) for N lists already resolved.
+hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_ub, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions,
+                          uint64_t* d_rid, uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s, DevArr* own_pos) {
     *total_out = 0;
     if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);
-    const IndexDev ix = h->dev();
-    DevArr lo(s), ub(s), fo(s), nj(s), t0(s), t1(s), t2(s), t3(s), ne(s), nfo(s), nlo(s), nraw(s), bits(s), cnt(s), wr(s), kept(s);
-    hipError_t e = lo.alloc(8 * N);
-    if (e == hipSuccess) e = ub.alloc(8 * (N + 1));
-    if (e == hipSuccess) e = fo.alloc(8 * (N + 1));
+    DevArr fo(s), nj(s), t0(s), t1(s), t2(s), t3(s), ne(s), nfo(s), nlo(s), nraw(s), bits(s), cnt(s), wr(s), kept(s);
+    hipError_t e = fo.alloc(8 * (N + 1));
     if (e == hipSuccess) e = nj.alloc(8 * (N + 1));
     if (e != hipSuccess) return e;
-    uint64_t* d_ub = (uint64_t*)ub.p;
-    e = hipMemsetAsync(d_ub + N, 0, 8, s);
-    if (e != hipSuccess) return e;
-    if (h->k == 13) hipLaunchKernelGGL(k_pq_resolve13, dim3(pq_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 2) hipLaunchKernelGGL(k_pq_resolve23<2>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 4) hipLaunchKernelGGL(k_pq_resolve23<4>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else hipLaunchKernelGGL(k_pq_resolve23<8>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = pq_scan(d_ub, (uint64_t*)fo.p, N + 1, t0, s);
+    e = pq_scan(d_ub, (uint64_t*)fo.p, N + 1, t0, s);
     if (e == hipSuccess) e = pq_scan(rocprim::make_transform_iterator(d_ub, PqNonEmpty()), (uint64_t*)nj.p, N + 1, t1, s);
     uint64_t T = 0, J = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&T, (const uint64_t*)fo.p + N, 8, hipMemcpyDeviceToHost, s);
@@ -315,7 +251,7 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     if (e == hipSuccess) e = wr.alloc(8 * (C + 1));
     if (e == hipSuccess) e = kept.alloc(8 * (N + 1));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pq_compact, dim3(pq_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, (const uint64_t*)lo.p, J, T,
+    hipLaunchKernelGGL(k_pq_compact, dim3(pq_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, d_lo, J, T,
                        (uint64_t*)ne.p, (uint64_t*)nfo.p, (uint64_t*)nlo.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemsetAsync((uint64_t*)bits.p + C, 0, 8, s);
@@ -339,6 +275,11 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
     *total_out = total;
+    if (own_pos && total) {
+        if ((e = own_pos->alloc(8 * total)) != hipSuccess) return e;
+        d_positions = (uint64_t*)own_pos->p;
+        cap = total;
+    }
     if (total == 0 || total > cap || !d_positions) return hipSuccess;
     P.out = d_positions;
     if (d_rid) {
@@ -349,6 +290,28 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);         // the scratch blocks go back to the pool idle
     return e;
+}
+
+// The whole chain. d_offsets (N + 1) and *total_out are always produced; entries only when *total_out <= cap.
+hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_offsets, uint64_t* d_positions, uint64_t* d_rid,
+                               uint64_t* d_local, uint64_t cap, uint64_t* total_out, hipStream_t s) {
+    *total_out = 0;
+    if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);
+    const IndexDev ix = h->dev();
+    DevArr lo(s), ub(s);
+    hipError_t e = lo.alloc(8 * N);
+    if (e == hipSuccess) e = ub.alloc(8 * (N + 1));
+    if (e != hipSuccess) return e;
+    uint64_t* d_ub = (uint64_t*)ub.p;
+    e = hipMemsetAsync(d_ub + N, 0, 8, s);
+    if (e != hipSuccess) return e;
+    if (h->k == 13) hipLaunchKernelGGL(k_pq_resolve13, dim3(pq_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 2) hipLaunchKernelGGL(k_pq_resolve23<2>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 4) hipLaunchKernelGGL(k_pq_resolve23<4>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else hipLaunchKernelGGL(k_pq_resolve23<8>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return posquery_lists(h, (const uint64_t*)lo.p, d_ub, N, m, d_offsets, d_positions, d_rid, d_local, cap, total_out, s);
 }
 
 }  // namespace aix

@@ -544,6 +544,78 @@ class Index:
                                                    vp(by.data_ptr()) if nb else None, nb, C.byref(tot), st), "aix_reads_by_kmers_dev")
         return koff, rid, roff, by
 
+    # ---- sequences against the indexed reads (aix_seqhits.hip) ---------------------------------
+    @staticmethod
+    def _take_as(p, n: int, dtype) -> np.ndarray:
+        dt = np.dtype(dtype)
+        try:
+            return np.frombuffer(C.string_at(p, dt.itemsize * n), dtype=dt).copy() if n else np.zeros(0, dt)
+        finally:
+            lib().aix_free(p)
+
+    def seq_hits(self, seqs: Sequence, max_per_kmer: int = 0):
+        """Seed hits of every 23-window of every sequence against the attached positions index, intervals and reads:
+        (seq_offsets u64[M + 1], qoff u32, pos u64, rid u64, local i64, flag u8). The hits of sequence i are
+        [seq_offsets[i], seq_offsets[i + 1]), by window, then slot; flag = strand (0 as stored, 1 reverse complement, 2 neither) | 4 when
+        an interval was found."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(6)]
+        check(lib().aix_seq_hits(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, max_per_kmer, *[C.byref(p) for p in ps]), "aix_seq_hits")
+        so = self._take_as(ps[0], m + 1, np.uint64)
+        t = int(so[m])
+        return (so, self._take_as(ps[1], t, np.uint32), self._take_as(ps[2], t, np.uint64), self._take_as(ps[3], t, np.uint64),
+                self._take_as(ps[4], t, np.int64), self._take_as(ps[5], t, np.uint8))
+
+    def seq_votes(self, seqs: Sequence, min_votes: int = 1, max_per_kmer: int = 0):
+        """Votes per (read, strand, diagonal) of every sequence: (vote_offsets u64[M + 1], rid u64, strand u8, diag i64, votes u32,
+        q_first u32, q_last u32); the records of sequence i ascend by (rid, strand, diag). diag = local - qoff (strand 0), local + qoff
+        (strand 1); only groups of at least min_votes hits are reported."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(7)]
+        check(lib().aix_seq_votes(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, max_per_kmer, min_votes, *[C.byref(p) for p in ps]),
+              "aix_seq_votes")
+        vo = self._take_as(ps[0], m + 1, np.uint64)
+        r = int(vo[m])
+        return (vo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint8), self._take_as(ps[3], r, np.int64),
+                self._take_as(ps[4], r, np.uint32), self._take_as(ps[5], r, np.uint32), self._take_as(ps[6], r, np.uint32))
+
+    def _seq_t(self, what: str, seqs_t, offs_t, dtypes, cap_hint: int, call):
+        """offsets + one tensor per dtype through a `_dev` twin: filled in one call when cap_hint entries suffice, else sized, then filled."""
+        import torch
+        self._chk_dev(seqs_t)
+        self._chk_dev(offs_t)
+        m = offs_t.numel() - 1
+        dev = seqs_t.device
+        offsets = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64()
+        with torch.cuda.device(dev):
+            cap = max(int(cap_hint), 0)
+            while True:
+                outs = [torch.empty(max(cap, 1), dtype=dt, device=dev) for dt in dtypes]
+                check(call(m, vp(offsets.data_ptr()), [vp(o.data_ptr()) if cap else None for o in outs], cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                cap = total.value
+        return (offsets, *[o[:total.value] for o in outs])
+
+    def seq_hits_t(self, seqs_t, offs_t, max_per_kmer: int = 0, cap_hint: int = 0):
+        """seq_hits on device tensors (uint8 bytes, int64 offsets[M + 1] into them), on torch's current stream:
+        (seq_offsets int64, qoff int32, pos int64, rid int64, local int64, flag uint8) — bit patterns of the unsigned fields."""
+        import torch
+        st = _stream_ptr(self.device)
+        return self._seq_t("aix_seq_hits_dev", seqs_t, offs_t, [torch.int32, torch.int64, torch.int64, torch.int64, torch.uint8], cap_hint,
+                           lambda m, off, o, cap, tot: lib().aix_seq_hits_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, max_per_kmer, off, *o, cap, tot, st))
+
+    def seq_votes_t(self, seqs_t, offs_t, min_votes: int = 1, max_per_kmer: int = 0, cap_hint: int = 0):
+        """seq_votes on device tensors: (vote_offsets int64, rid int64, strand uint8, diag int64, votes int32, q_first int32, q_last int32)."""
+        import torch
+        st = _stream_ptr(self.device)
+        return self._seq_t("aix_seq_votes_dev", seqs_t, offs_t, [torch.int64, torch.uint8, torch.int64, torch.int32, torch.int32, torch.int32], cap_hint,
+                           lambda m, off, o, cap, tot: lib().aix_seq_votes_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, max_per_kmer, min_votes, off,
+                                                                               *o, cap, tot, st))
+
     # ---- De Bruijn neighbours and walks (aix_debruijn.hip) -------------------------------------
     @staticmethod
     def _dir(direction, both_ok: bool) -> int:

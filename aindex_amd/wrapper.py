@@ -880,6 +880,36 @@ class AindexWrapper:
         koff, _, roff, data = ix.reads_by_kmers(flat, max_reads)
         return self._spread_lists(len(kmers), keep, koff, self._csr_strings(roff, data))
 
+    # ---- sequences against the indexed reads (one GPU call per batch of sequences) -------------------------------------------
+    def _attach_for_mapping(self) -> Index:
+        """The 23-mer handle with positions, intervals and reads attached; RuntimeError naming the piece that cannot be."""
+        if self._is_13mer_mode:
+            raise RuntimeError("sequence mapping needs a 23-mer index (13-mer mode is loaded)")
+        at = self._attach_for_batch(True) if self.aindex_loaded else None
+        if at is None:
+            raise RuntimeError("sequence mapping needs the positions index: call load_aindex first")
+        if not self._ridx_on_device():
+            raise RuntimeError("sequence mapping needs a sorted .ridx (read intervals sorted and disjoint): call load_reads_index first")
+        ix = self._attach_reads_for_batch(at[0])
+        if ix is None:
+            raise RuntimeError("sequence mapping needs the reads: call load_reads first")
+        return ix
+
+    def get_sequence_hits_array(self, seqs, max_per_kmer: int = 0):
+        """Seed hits of every 23-window of every sequence (str or bytes), in one GPU call: CSR arrays (seq_offsets uint64[M + 1], qoff
+        uint32, pos uint64, rid uint64, local int64, flag uint8). Window q of a sequence gives exactly get_positions(seq[q:q + 23]); per
+        hit rid = get_rid(pos), local = pos - get_start(pos), flag bits 0-1 = strand (0: the reads hold the window at pos, 1: its reverse
+        complement, 2: neither), bit 2 = an interval was found."""
+        return self._attach_for_mapping().seq_hits(list(seqs), max_per_kmer)
+
+    def map_sequences(self, seqs, min_votes: int = 2, max_per_kmer: int = 0) -> List[List[tuple]]:
+        """Per sequence the list of (rid, strand, diag, votes, q_first, q_last): the reads it shares at least min_votes co-linear 23-mers
+        with, ascending by (rid, strand, diag). diag = offset_in_read - offset_in_sequence (strand 0) or their sum (strand 1)."""
+        vo, rid, strand, diag, votes, qf, ql = self._attach_for_mapping().seq_votes(list(seqs), min_votes, max_per_kmer)
+        recs = list(zip(rid.tolist(), strand.tolist(), diag.tolist(), votes.tolist(), qf.tolist(), ql.tolist()))
+        off = vo.tolist()
+        return [recs[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
     # ---- De Bruijn neighbours and extensions (one GPU call per batch) ---------------------------------------------------
     @staticmethod
     def _place_conts(n_items: int, keep: np.ndarray, recs: np.ndarray) -> list:

@@ -525,6 +525,45 @@ int aix_walk_dev(aix_index_t* h, const uint64_t* d_codes /* or NULL */, const ch
                  uint64_t max_steps, uint32_t cutoff, int mode, uint8_t* d_bases, uint32_t* d_len, uint8_t* d_stop,
                  uint32_t* d_tf /* nullable */, uint64_t* d_last /* nullable */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sequences against the indexed reads: seed hits with strand, and votes per (read, strand, diagonal).
+ * replaces, M sequences at a time, the loop a caller of the reference writes over the 23-windows of a sequence:
+ *          AindexWrapper::get_positions per window (python_wrapper.cpp:800-831), get_rid / get_start per occurrence (:757-789) and
+ *          get_read of 23 bytes per occurrence (:677-698) to tell the orientation — a bucket of the positions index holds both
+ *          orientations of its k-mer without a strand bit (hash.hpp:150-170).
+ * 23-mer handles only (AIX_ERR_MODE otherwise). The positions index (aix_aindex_attach*), the read intervals (aix_ridx_attach) and the
+ * reads (aix_reads_attach*) must be attached: AIX_ERR_ARG otherwise. Sequences come as aix_coverage_batch takes them: sequence i is the
+ * bytes seqs[offs[i] .. offs[i + 1]), offs ascending; a sequence of 2^32 bytes or more is AIX_ERR_ARG (query offsets are u32). seqs may
+ * be NULL when no sequence is 23 bytes long (M empty sequences give all-zero offsets).
+ * A sequence of length L has max(0, L - 22) windows, window q the 23 raw bytes at offset q. The _dev twins follow the sizing convention
+ * of aix_positions_query_dev: offsets and *total_out always, entries only when the total fits `cap`, never at or beyond it, AIX_OK either
+ * way; they return after the work on `stream` has completed. Host outputs are malloc'd (aix_free); M = 0 gives offsets = {0}.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_HIT_STRAND_MASK 3u   /* aix_seq_hits flag bits 0-1: 0 the reads hold the window's bytes at pos, 1 they hold the reverse
+                                    complement of its sanitised code (kmers.cpp:12-40), 2 neither, or pos + 23 lies beyond the reads */
+#define AIX_HIT_LOCATED     4u   /* bit 2: an interval was found for pos (python_wrapper.cpp:66-74)                                */
+/* Seed hits (python_wrapper.cpp:800-831 per window): the hits of window q are exactly aix_positions_query of its 23 bytes — get_pfid on
+ * the raw bytes, slot order, zeros skipped, the first max_per_kmer entries (0: all). CSR over sequences: hits of sequence i =
+ * [seq_offsets[i], seq_offsets[i + 1]), ordered by window, then slot. Per hit: qoff (window offset), pos (0-based position in the reads),
+ * rid / local (get_rid(pos), pos - get_start(pos), :757-789; 0 and pos without an interval) and flag (above). The reads are never read
+ * at or beyond their attached length, whatever the positions array holds. */
+int aix_seq_hits(aix_index_t* h, const char* seqs, const uint64_t* offs, uint64_t M, uint64_t max_per_kmer, uint64_t** seq_offsets_out,
+                 uint32_t** qoff_out, uint64_t** pos_out, uint64_t** rid_out, int64_t** local_out, uint8_t** flag_out);
+int aix_seq_hits_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t max_per_kmer, uint64_t* d_seq_offsets,
+                     uint32_t* d_qoff, uint64_t* d_pos, uint64_t* d_rid, int64_t* d_local, uint8_t* d_flag, uint64_t cap, uint64_t* total_out,
+                     void* stream);   /* python_wrapper.cpp:800-831, 757-789, 677-698; d_seq_offsets: M + 1 */
+/* Diagonal votes (the grouping a caller does over the hits above; python_wrapper.cpp:800-831, 757-789): of the hits of a sequence, those
+ * with strand 0 or 1 and an interval, grouped by (rid, strand, diag), diag = local - qoff (strand 0) or local + qoff (strand 1) —
+ * constant along a co-linear match in either orientation. One record per group of at least min_votes hits: rid, strand, diag, votes
+ * (hits in the group), q_first / q_last (its smallest / largest qoff). CSR over sequences, records ascending by (rid, strand, diag).
+ * Deterministic: independent of launch geometry and of every probe switch. */
+int aix_seq_votes(aix_index_t* h, const char* seqs, const uint64_t* offs, uint64_t M, uint64_t max_per_kmer, uint64_t min_votes,
+                  uint64_t** vote_offsets_out, uint64_t** rid_out, uint8_t** strand_out, int64_t** diag_out, uint32_t** votes_out,
+                  uint32_t** qfirst_out, uint32_t** qlast_out);
+int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t max_per_kmer, uint64_t min_votes,
+                      uint64_t* d_vote_offsets, uint64_t* d_rid, uint8_t* d_strand, int64_t* d_diag, uint32_t* d_votes, uint32_t* d_qfirst,
+                      uint32_t* d_qlast, uint64_t cap, uint64_t* total_out, void* stream);   /* python_wrapper.cpp:800-831, 757-789 */
+
 /* The same normalisation for a buffer already in HBM (byte-identical output; the readers are finite-state transducers,
  * resolved with a parallel scan of per-chunk transition functions). format must be PLAIN, FASTA or FASTQ; d_out holds
  * len+1 bytes; *out_len is a HOST pointer; the call synchronises the stream. */
