@@ -97,6 +97,15 @@ struct aix_index {
     hipStream_t hist_stream = nullptr;         // count23, AIX_COUNT23_HIST_CUS only: the partition + histogram kernels on their own CUs (CU-masked stream)
     hipStream_t probe_stream = nullptr;        // count23: the slot probe of piece i + 1 runs here while piece i is partitioned and added on the caller's stream
     hipEvent_t probe_ev[2] = {nullptr, nullptr}, hist_ev[2] = {nullptr, nullptr}, start_ev = nullptr;
+    // binned lookups (aix_lookup_binned.hip): records, survivor list, cursors and header of one piece. Grow-only, freed at close; not part
+    // of the index, so not in device_bytes. lb_done is recorded behind every call: a call on another stream waits for it first.
+    void* lb_ws = nullptr;
+    uint64_t lb_ws_bytes = 0;
+    uint64_t* lb_stats = nullptr;              // device: pieces binned, pieces direct, records that overflowed, survivors
+    hipEvent_t lb_done = nullptr;
+    hipStream_t lb_stream = nullptr;           // the stream of the last call
+    bool lb_used = false;
+    std::mutex lb_mutex;
     uint64_t device_bytes = 0;
     bool perm13_bijective = false;             // 13-mer: code -> mphf slot is a bijection of [0, 4^13) (true for the all-13-mers .pf)
     bool canonical_only = false;
@@ -179,6 +188,14 @@ void readsquery_release(aix_index* h);
 // through this one function, so that only aix_lookup.hip knows its layout
 __attribute__((visibility("hidden"))) int check_device(int device);
 __attribute__((visibility("hidden"))) void free_host_pipe(struct HostPipe* p);
+
+// The binned tf lookup of large absent-heavy batches (aix_lookup_binned.hip). AIX_LB_TAKEN: everything is enqueued on `s`;
+// AIX_LB_NOT_TAKEN: not a candidate (mode, index, switches, batch size) or no workspace, the caller runs the direct path; < 0: error.
+#define AIX_LB_NOT_TAKEN 0
+#define AIX_LB_TAKEN 1
+static constexpr uint64_t AIX_LB_DEFAULT_MIN = 1ull << 25;      // AIX_LOOKUP_BINNED_MIN (profiles/lookup_binned/README.md)
+int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t N, uint32_t* out, hipStream_t s);
+void lookup_binned_release(aix_index* h);       // the caller has switched to the handle's device
 
 // K13 in steps (aix_count.hip); the caller holds h->count_mutex from begin to end
 int count13_begin_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s);

@@ -112,6 +112,7 @@ static void destroy(aix_index* h) {
     if (h->perm13) (void)hipFree(h->perm13);
     if (h->scratch13) (void)hipFree(h->scratch13);
     if (h->count_ws) (void)hipFree(h->count_ws);
+    lookup_binned_release(h);
     posquery_release(h);
     readsquery_release(h);
     if (h->pipe) { free_host_pipe(h->pipe); h->pipe = nullptr; }

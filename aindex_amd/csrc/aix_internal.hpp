@@ -65,7 +65,11 @@ void pool_free(void* p);
 void pool_trim();
 
 // launchers (aix_kernels.hip). All asynchronous on `stream`; return hipGetLastError().
-hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s);
+// gate (nullable): a device word read at the start of the kernel; non-zero = the binned path answers this batch and the kernel returns at once
+hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s, const uint32_t* gate = nullptr);
+// canonical index: out[list[j]] = tf of query list[j] for j < *count (<= max_count, which sizes the grid), when *gate is non-zero; *survivors_stat += *count
+hipError_t launch_lookup23_list(const IndexDev& ix, const uint8_t* q, const uint32_t* list, const uint32_t* count, uint64_t max_count, const uint32_t* gate,
+                                uint32_t* out, unsigned long long* survivors_stat, hipStream_t s);
 hipError_t launch_lookup23_codes(const IndexDev& ix, const uint64_t* codes, uint64_t N, uint32_t* out, hipStream_t s);
 hipError_t launch_selftest_lower_bound(const uint16_t* a, uint32_t n, const uint32_t* keys, uint32_t nkeys, uint32_t* out, hipStream_t s);
 hipError_t launch_lookup23_ragged(const IndexDev& ix, const uint8_t* bytes, const uint64_t* offs, uint64_t N, uint32_t* out, hipStream_t s);

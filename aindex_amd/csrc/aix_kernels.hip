@@ -136,7 +136,9 @@ __device__ __forceinline__ void both23(const IndexDev& ix, bool active, uint64_t
          i##_base += (uint64_t)gridDim.x * kBlock, i += (uint64_t)gridDim.x * kBlock)
 
 template <int MODE, bool CANON, int LPP>
-__global__ void __launch_bounds__(kBlock) k_lookup23_ascii(const IndexDev ix_, const uint8_t* __restrict__ q, uint64_t N, LookupOut out) {
+__global__ void __launch_bounds__(kBlock) k_lookup23_ascii(const IndexDev ix_, const uint8_t* __restrict__ q, uint64_t N, LookupOut out,
+                                                          const uint32_t* __restrict__ gate /* nullable: non-zero = the binned path answers this batch */) {
+    if (gate && *gate) return;
     const IndexDev& ix = ix_;
     FilterGauge fg;
     AIX_WAVE_LOOP(i, N) {
@@ -174,6 +176,28 @@ __global__ void __launch_bounds__(kBlock) k_lookup23_ascii(const IndexDev ix_, c
                 }
             }
         }
+    }
+}
+
+// pass C of the binned lookup (aix_lookup_binned.hip): the queries list[0 .. *count) of a canonical index through the same probe
+// as above. The grid is sized for the worst case; *count and the gate word are read on the device.
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) k_lookup23_list(const IndexDev ix_, const uint8_t* __restrict__ q, const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ count, const uint32_t* __restrict__ gate, uint32_t* __restrict__ out,
+                                                         unsigned long long* __restrict__ survivors_stat) {
+    if (!*gate) return;
+    const IndexDev& ix = ix_;
+    const uint64_t n = *count;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(survivors_stat, (unsigned long long)n);
+    FilterGauge fg;
+    AIX_WAVE_LOOP(j, n) {
+        const bool in = j < n;
+        const uint64_t i = in ? list[j] : 0;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (in) load23(q + 23 * i, w0, w1, w2);
+        auto again = [&](uint64_t& a, uint64_t& b, uint64_t& c) { load23(q + 23 * i, a, b, c); };
+        const uint32_t v = query23<true, LPP>(ix, in, w0, w1, w2, fg, again).tf;
+        if (in) out[i] = v;
     }
 }
 
@@ -873,28 +897,39 @@ __global__ void __launch_bounds__(kBlock) k_gather(const uint8_t* __restrict__ t
         default: return CALL(8);            \
     }
 template <bool CANON, int LPP>
-static hipError_t lookup23_tf(const IndexDev& ix, const uint8_t* q, uint64_t N, LookupOut out, hipStream_t s) {
-    AIX_LAUNCH((k_lookup23_ascii<MODE_TF, CANON, LPP>), N, s, ix, q, N, out);
+static hipError_t lookup23_tf(const IndexDev& ix, const uint8_t* q, uint64_t N, LookupOut out, const uint32_t* gate, hipStream_t s) {
+    AIX_LAUNCH((k_lookup23_ascii<MODE_TF, CANON, LPP>), N, s, ix, q, N, out, gate);
 }
 template <bool CANON>
-static hipError_t lookup23_ascii_mode(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s) {
+static hipError_t lookup23_ascii_mode(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, const uint32_t* gate, hipStream_t s) {
     switch (mode) {
         case MODE_TF: {
-#define AIX_CALL(L) lookup23_tf<CANON, L>(ix, q, N, out, s)
+#define AIX_CALL(L) lookup23_tf<CANON, L>(ix, q, N, out, gate, s)
             AIX_LPP_SWITCH(ix.bk_lpp, AIX_CALL)
 #undef AIX_CALL
         }
-        case MODE_LINES: AIX_LAUNCH((k_lookup23_ascii<MODE_LINES, CANON, 8>), N, s, ix, q, N, out);
-        case MODE_HASH: AIX_LAUNCH((k_lookup23_ascii<MODE_HASH, CANON, 8>), N, s, ix, q, N, out);
-        case MODE_KIDSTRAND: AIX_LAUNCH((k_lookup23_ascii<MODE_KIDSTRAND, CANON, 8>), N, s, ix, q, N, out);
-        case MODE_BOTH: AIX_LAUNCH((k_lookup23_ascii<MODE_BOTH, CANON, 8>), N, s, ix, q, N, out);
-        case MODE_TOTAL: AIX_LAUNCH((k_lookup23_ascii<MODE_TOTAL, CANON, 8>), N, s, ix, q, N, out);
+        case MODE_LINES: AIX_LAUNCH((k_lookup23_ascii<MODE_LINES, CANON, 8>), N, s, ix, q, N, out, gate);
+        case MODE_HASH: AIX_LAUNCH((k_lookup23_ascii<MODE_HASH, CANON, 8>), N, s, ix, q, N, out, gate);
+        case MODE_KIDSTRAND: AIX_LAUNCH((k_lookup23_ascii<MODE_KIDSTRAND, CANON, 8>), N, s, ix, q, N, out, gate);
+        case MODE_BOTH: AIX_LAUNCH((k_lookup23_ascii<MODE_BOTH, CANON, 8>), N, s, ix, q, N, out, gate);
+        case MODE_TOTAL: AIX_LAUNCH((k_lookup23_ascii<MODE_TOTAL, CANON, 8>), N, s, ix, q, N, out, gate);
     }
     return hipErrorInvalidValue;
 }
-hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s) {
+hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s, const uint32_t* gate) {
     if (N == 0) return hipSuccess;
-    return ix.canonical_only ? lookup23_ascii_mode<true>(ix, q, N, mode, out, s) : lookup23_ascii_mode<false>(ix, q, N, mode, out, s);
+    return ix.canonical_only ? lookup23_ascii_mode<true>(ix, q, N, mode, out, gate, s) : lookup23_ascii_mode<false>(ix, q, N, mode, out, gate, s);
+}
+template <int LPP>
+static hipError_t lookup23_list_lpp(const IndexDev& ix, const uint8_t* q, const uint32_t* list, const uint32_t* count, uint64_t max_count, const uint32_t* gate,
+                                    uint32_t* out, unsigned long long* survivors_stat, hipStream_t s) {
+    AIX_LAUNCH((k_lookup23_list<LPP>), max_count, s, ix, q, list, count, gate, out, survivors_stat);
+}
+hipError_t launch_lookup23_list(const IndexDev& ix, const uint8_t* q, const uint32_t* list, const uint32_t* count, uint64_t max_count, const uint32_t* gate,
+                                uint32_t* out, unsigned long long* survivors_stat, hipStream_t s) {
+#define AIX_CALL(L) lookup23_list_lpp<L>(ix, q, list, count, max_count, gate, out, survivors_stat, s)
+    AIX_LPP_SWITCH(ix.bk_lpp, AIX_CALL)
+#undef AIX_CALL
 }
 // self-test of wave_lower_bound_pair (aix_device.hpp): wave w of the grid looks up keys[w] and keys[w] + 1 in the sorted array
 __global__ void __launch_bounds__(64) k_selftest_lower_bound(const uint16_t* __restrict__ a, uint32_t n, const uint32_t* __restrict__ keys, uint32_t* __restrict__ out) {

@@ -22,6 +22,10 @@ static int lookup_ascii_dev(aix_index_t* h, const char* d_kmers, uint64_t N, int
     const IndexDev d = h->dev();
     if (h->k == 23) {
         if (h->n == 0) return AIX_ERR_UNSUPPORTED;             // empty index: the host twins answer 0 without a launch
+        if (mode == MODE_TF) {                                 // large absent-heavy batches on a canonical index: filter read from L2
+            const int st = lookup23_binned(h, d, (const uint8_t*)d_kmers, N, o.tf, (hipStream_t)stream);
+            if (st != AIX_LB_NOT_TAKEN) return st == AIX_LB_TAKEN ? AIX_OK : st;
+        }
         HIPCHK(launch_lookup23_ascii(d, (const uint8_t*)d_kmers, N, mode, o, (hipStream_t)stream));
     } else {
         if (mode == MODE_KIDSTRAND) return AIX_ERR_MODE;       // hash_map is null in 13-mer mode (kid / strand need the checker)

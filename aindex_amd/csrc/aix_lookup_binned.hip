@@ -1,0 +1,418 @@
+// aix_lookup_binned.hip — tf lookups of large, absent-heavy 23-mer batches on a canonical index with the absence filter read
+// from L2 instead of the fabric. The direct kernel sends one scattered 8-byte filter read per query past L2 (the
+// filter is ~100 MB) and runs at the chip's random-line request rate. Here a piece of the batch (<= 2^27 queries) goes through
+//   k_lb_gate     ~16 K evenly spaced queries against the filter: the piece is binned iff fewer than a quarter of them pass
+//                 (FilterGauge's rule). One flag in the workspace header; every kernel behind it reads the flag first and
+//                 the one not chosen returns at once, so there is no host synchronisation.
+//   k_lb_bin      pass A: load, encode, strand pick and hash as the direct kernel does; one 8-byte record per clean query,
+//                 counting-sorted by filter slice in LDS per 4096-query tile and flushed into 256-record chunks of a per-slice
+//                 region (chunks come from a per-slice cursor; a workgroup asks for all chunks of a tile and slice at once).
+//                 out[i] = 0 for every query. Queries with other bytes, and records whose slice region is full, go onto the
+//                 survivor list instead.
+//   k_lb_filter   pass B: chunks in slice order across the whole grid, so that the chip reads one or two slices (~1 MiB each)
+//                 at a time and every XCD holds them in its L2 (the chunks are handed out in order through ticket counters). A record that passes is appended to the survivor list.
+//   k_lookup23_list (aix_kernels.hip) pass C: the survivors through the ordinary probe.
+// A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the low 18 bits of Jenkins' c, i.e.
+// three of the four bit positions bloom_mask takes from it: 8 bytes. Pass B therefore lets a superset of the filter's positives
+// through (~1.5 % of absent queries instead of ~0.5 %); pass C consults the complete filter again, so answers do not depend on it.
+#include <algorithm>
+
+#include "aix_env.hpp"
+#include "aix_handle.hpp"
+
+namespace aix {
+
+static constexpr int LB_TB = 512;                      // threads of pass A
+static constexpr int LB_QPL = 8;                       // queries per lane and tile
+static constexpr int LB_TILE = LB_TB * LB_QPL;         // 4096 queries per tile: 32 KiB of records in LDS
+static constexpr int LB_CH = 256;                      // records per chunk (2 KiB)
+static constexpr int LB_MAXBINS = 256;
+static constexpr unsigned LB_GRID_A = 768;             // three workgroups of pass A per CU (41 KiB of LDS each)
+static constexpr int LB_FB = 256;                      // threads of pass B: a lane takes one record of each chunk of a trip
+static constexpr int LB_U = 2;                         // chunks per trip of a pass-B workgroup (independent loads)
+static constexpr int LB_TICKETS = 8;                   // pass B hands its chunks out in order through these counters (one per XCD under round-robin dispatch)
+static constexpr int LB_SURV = 4096;                   // survivors a pass-B workgroup collects in LDS before it appends them
+static constexpr unsigned LB_GRID_B = 2048;
+static constexpr uint32_t LB_SAMPLES = 16384;
+static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 18;
+static constexpr uint32_t LB_NONE = 0xFFFFFFFFu;
+static constexpr uint64_t LB_HDR_BYTES = 4096;         // header (4 words) + cursors (LB_MAXBINS words) + ticket counters (a 128-byte line each), zeroed per piece
+enum { LB_FLAG = 0, LB_PASSED = 1, LB_DONE = 2, LB_NSURV = 3, LB_CURSOR = 16, LB_TICKET = 512 };
+
+struct LbGeom {
+    uint32_t nbins;        // filter slices
+    uint32_t wps;          // filter words per slice (<= 2^18)
+    uint32_t inv;          // floor(2^32 / wps), for word / wps
+    uint32_t cap;          // chunks per slice region
+};
+struct LbWs {
+    uint32_t* hdr;                 // LB_FLAG .. LB_NSURV, cursors from LB_CURSOR
+    uint32_t* list;                // survivor list: query indices of the piece
+    uint32_t* cnt;                 // [nbins * cap] records in each chunk
+    uint64_t* rec;                 // [nbins * cap * LB_CH]
+    unsigned long long* stats;     // pieces binned, pieces direct, records that overflowed, survivors
+};
+
+// the query's strand pick and hash as query23 (aix_kernels.hip) does them; false = other bytes
+__device__ __forceinline__ bool lb_hash(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t seed, uint64_t& b, uint64_t& c) {
+    const Enc23 e = encode23_words(w0, w1, w2);
+    if (!e.valid) return false;
+    const uint64_t r = revcomp(e.code, 23);
+    if (!(e.code <= r)) ascii23_of_rc(e.code, w0, w1, w2);
+    uint64_t a;
+    jenkins23(w0, w1, w2, seed, a, b, c);
+    return true;
+}
+__device__ __forceinline__ uint64_t lb_mask3(uint32_t c) { return (1ull << (c & 63)) | (1ull << ((c >> 6) & 63)) | (1ull << ((c >> 12) & 63)); }
+
+__global__ void __launch_bounds__(256) k_lb_gate(uint64_t seed, const uint64_t* __restrict__ bloom, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n,
+                                                 uint32_t nsamp, int force, uint32_t* __restrict__ hdr, unsigned long long* __restrict__ stats) {
+    if (force) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { hdr[LB_FLAG] = 1u; atomicAdd(&stats[0], 1ull); }
+        return;
+    }
+    __shared__ uint32_t s_pass;
+    if (threadIdx.x == 0) s_pass = 0;
+    __syncthreads();
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    bool pass = false;
+    if (s < nsamp) {
+        const uint64_t i = (uint64_t)s * n / nsamp;
+        uint64_t w0, w1, w2, b, c;
+        load23(q + 23 * i, w0, w1, w2);
+        pass = true;                                            // other bytes: the direct probe's business
+        if (lb_hash(w0, w1, w2, seed, b, c)) {
+            const uint64_t m = bloom_mask(c);
+            pass = (bloom[bloom_word(b, nbloom)] & m) == m;
+        }
+    }
+    const uint32_t wave = (uint32_t)__popcll(__ballot(pass));
+    if ((threadIdx.x & 63) == 0 && wave) atomicAdd(&s_pass, wave);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&hdr[LB_PASSED], s_pass);
+        __threadfence();
+        if (atomicAdd(&hdr[LB_DONE], 1u) == gridDim.x - 1) {    // the last workgroup decides
+            const uint32_t passed = atomicAdd(&hdr[LB_PASSED], 0u);
+            const bool binned = 4ull * passed < nsamp;
+            hdr[LB_FLAG] = binned ? 1u : 0u;
+            atomicAdd(&stats[binned ? 0 : 1], 1ull);
+        }
+    }
+}
+
+// exclusive scan of one value per lane over the workgroup (T threads); `all` = the total. Two barriers.
+template <int T>
+__device__ __forceinline__ uint32_t lb_scan_excl(uint32_t mine, uint32_t* wsum, uint32_t& all) {
+    const int t = threadIdx.x;
+    uint32_t s = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(s, d);
+        if ((t & 63) >= d) s += y;
+    }
+    if ((t & 63) == 63) wsum[t >> 6] = s;
+    __syncthreads();
+    uint32_t off = 0;
+    all = 0;
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) {
+        const uint32_t x = wsum[w];
+        if (w < (t >> 6)) off += x;
+        all += x;
+    }
+    __syncthreads();
+    return off + s - mine;
+}
+
+// where entry number `r` of slice `bin` in this tile goes: the chunk the workgroup was filling (fill f), then the fresh chunks from nb
+__device__ __forceinline__ void lb_place(uint32_t f, uint32_t cur, uint32_t nb, uint32_t r, uint32_t& chunk, uint32_t& o) {
+    const uint32_t pos = f + r;
+    if (pos < (uint32_t)LB_CH) { chunk = cur; o = pos; }
+    else { chunk = nb + (pos - LB_CH) / LB_CH; o = (pos - LB_CH) % LB_CH; }
+}
+
+__global__ void __launch_bounds__(LB_TB) k_lb_bin(uint64_t seed, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
+    if (!w.hdr[LB_FLAG]) return;
+    __shared__ uint64_t sorted[LB_TILE];
+    __shared__ uint16_t sbin[LB_TILE];
+    // per slice (entry nbins = the queries that go straight onto the survivor list): tile count, its exclusive scan, the chunk being filled
+    // and its fill, the first fresh chunk of this tile
+    __shared__ uint32_t hist[LB_MAXBINS + 1], loc_off[LB_MAXBINS + 1], cur_chunk[LB_MAXBINS + 1], cur_fill[LB_MAXBINS + 1], fresh[LB_MAXBINS + 1];
+    __shared__ uint32_t wsum[LB_TB / 64];
+    __shared__ uint32_t s_ov, s_ov_real, s_ov_rank, s_ov_base;
+    const uint32_t t = threadIdx.x, NB = g.nbins;
+    uint32_t* const cursor = w.hdr + LB_CURSOR;
+    if (t <= NB) { hist[t] = 0; cur_chunk[t] = LB_NONE; cur_fill[t] = LB_CH; fresh[t] = 0; }
+    __syncthreads();
+    const uint32_t ntiles = (n + LB_TILE - 1) / LB_TILE;
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint32_t base = tile * LB_TILE, in_tile = min((uint32_t)LB_TILE, n - base);
+        uint64_t rec[LB_QPL];
+        uint32_t meta[LB_QPL];                                   // slice | rank inside the tile's slice << 16
+#pragma unroll
+        for (int j = 0; j < LB_QPL; ++j) {
+            const uint32_t i = base + j * LB_TB + t;
+            meta[j] = LB_NONE;
+            rec[j] = 0;
+            if (i < n) {
+                uint64_t w0, w1, w2, b, c;
+                load23(q + 23ull * i, w0, w1, w2);
+                uint32_t bin = NB;
+                uint64_t r = i;
+                if (lb_hash(w0, w1, w2, seed, b, c)) {
+                    const uint32_t word = bloom_word(b, nbloom);
+                    bin = __umulhi(word, g.inv);                 // word / wps, at most one too small
+                    uint32_t wi = word - bin * g.wps;
+                    if (wi >= g.wps) { wi -= g.wps; ++bin; }
+                    r |= ((uint64_t)wi << LB_IDX_BITS) | ((uint64_t)((uint32_t)c & ((1u << LB_MASK_BITS) - 1)) << (LB_IDX_BITS + LB_WORD_BITS));
+                }
+                meta[j] = bin | (atomicAdd(&hist[bin], 1u) << 16);
+                rec[j] = r;
+                out[i] = 0;
+            }
+        }
+        __syncthreads();
+        const uint32_t a = t <= NB ? hist[t] : 0u;
+        uint32_t all;
+        const uint32_t excl = lb_scan_excl<LB_TB>(a, wsum, all);
+        if (t <= NB) loc_off[t] = excl;
+        if (t < NB && cur_fill[t] + a > (uint32_t)LB_CH) fresh[t] = atomicAdd(&cursor[t], (cur_fill[t] + a - 1) / LB_CH);
+        if (t == 0) { s_ov = 0; s_ov_real = 0; s_ov_rank = 0; }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < LB_QPL; ++j) {
+            if (meta[j] != LB_NONE) {
+                const uint32_t bin = meta[j] & 0xFFFFu, p = loc_off[bin] + (meta[j] >> 16);
+                sorted[p] = rec[j];
+                sbin[p] = (uint16_t)bin;
+            }
+        }
+        __syncthreads();
+        // flush: runs of one slice are contiguous in `sorted` and land contiguously in the slice's chunks
+        for (uint32_t i0 = t & ~63u; i0 < in_tile; i0 += LB_TB) {
+            const uint32_t i = i0 + (t & 63u);
+            bool ov = false, real = false;
+            if (i < in_tile) {
+                const uint32_t bin = sbin[i];
+                ov = true;
+                if (bin < NB) {
+                    uint32_t chunk, o;
+                    lb_place(cur_fill[bin], cur_chunk[bin], fresh[bin], i - loc_off[bin], chunk, o);
+                    if (chunk < g.cap) { w.rec[((uint64_t)bin * g.cap + chunk) * LB_CH + o] = sorted[i]; ov = false; }
+                    real = ov;
+                }
+            }
+            const uint32_t n_ov = (uint32_t)__popcll(__ballot(ov)), n_real = (uint32_t)__popcll(__ballot(real));
+            if ((t & 63u) == 0 && n_ov) { atomicAdd(&s_ov, n_ov); if (n_real) atomicAdd(&s_ov_real, n_real); }
+        }
+        __syncthreads();
+        if (s_ov) {                                              // rare: other bytes, or a slice region that is full -> survivor list
+            if (t == 0) {
+                s_ov_base = atomicAdd(&w.hdr[LB_NSURV], s_ov);
+                if (s_ov_real) atomicAdd(&w.stats[2], (unsigned long long)s_ov_real);
+            }
+            __syncthreads();
+            for (uint32_t i0 = t & ~63u; i0 < in_tile; i0 += LB_TB) {
+                const uint32_t i = i0 + (t & 63u);
+                bool ov = false;
+                if (i < in_tile) {
+                    const uint32_t bin = sbin[i];
+                    ov = true;
+                    if (bin < NB) {
+                        uint32_t chunk, o;
+                        lb_place(cur_fill[bin], cur_chunk[bin], fresh[bin], i - loc_off[bin], chunk, o);
+                        ov = chunk >= g.cap;
+                    }
+                }
+                const uint64_t m = __ballot(ov);
+                if (m) {
+                    uint32_t r0 = 0;
+                    if ((t & 63u) == 0) r0 = atomicAdd(&s_ov_rank, (uint32_t)__popcll(m));
+                    r0 = __shfl(r0, 0);
+                    if (ov) w.list[s_ov_base + r0 + (uint32_t)__popcll(m & ((1ull << (t & 63u)) - 1))] = (uint32_t)sorted[i] & ((1u << LB_IDX_BITS) - 1);
+                }
+            }
+        }
+        __syncthreads();
+        if (t < NB && a) {                                       // advance this slice's chunk; a chunk's count is written when the workgroup leaves it
+            const uint32_t tot = cur_fill[t] + a;
+            if (tot > (uint32_t)LB_CH) {
+                const uint32_t k = (tot - 1) / LB_CH, nb = fresh[t], old = cur_chunk[t];
+                uint32_t* const cnt = w.cnt + (uint64_t)t * g.cap;
+                if (old < g.cap) cnt[old] = LB_CH;
+                for (uint32_t u = 0; u + 1 < k; ++u) if (nb + u < g.cap) cnt[nb + u] = LB_CH;
+                cur_chunk[t] = nb + k - 1;
+                cur_fill[t] = tot - k * LB_CH;
+            } else {
+                cur_fill[t] = tot;
+            }
+        }
+        if (t <= NB) hist[t] = 0;
+        __syncthreads();
+    }
+    if (t < NB && cur_chunk[t] < g.cap) w.cnt[(uint64_t)t * g.cap + cur_chunk[t]] = cur_fill[t];
+}
+
+__global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict__ bloom, uint32_t nbloom, LbGeom g, LbWs w) {
+    if (!w.hdr[LB_FLAG]) return;
+    __shared__ uint32_t pre[LB_MAXBINS + 1];                    // chunks in the slices before this one
+    __shared__ uint32_t surv[LB_SURV];
+    __shared__ uint32_t wsum[LB_FB / 64];
+    __shared__ uint32_t s_n, s_base, s_ticket;
+    const uint32_t t = threadIdx.x, NB = g.nbins;
+    const uint32_t mine = t < NB ? min(w.hdr[LB_CURSOR + t], g.cap) : 0u;
+    uint32_t total;
+    const uint32_t excl = lb_scan_excl<LB_FB>(mine, wsum, total);
+    pre[t] = excl;
+    if (t == 0) { pre[LB_MAXBINS] = total; s_n = 0; }
+    __syncthreads();
+    auto flush = [&]() {                                         // every lane of the workgroup calls it
+        if (t == 0) s_base = atomicAdd(&w.hdr[LB_NSURV], s_n);
+        __syncthreads();
+        for (uint32_t i = t; i < s_n; i += LB_FB) w.list[s_base + i] = surv[i];
+        __syncthreads();
+        if (t == 0) s_n = 0;
+        __syncthreads();
+    };
+    // The chunks are handed out in slice order, LB_U at a time: what the grid has in flight is then one contiguous window of
+    // gridDim.x * LB_U chunks (~1 % of the records, so ~1 % of the filter: ~1 MB), however unevenly the workgroups advance. With a
+    // static grid stride the window drifted apart and 60 % of the filter reads missed L2 (profiles/lookup_binned/README.md).
+    const uint32_t lane_x = blockIdx.x % LB_TICKETS;
+    uint32_t* const ticket = w.hdr + LB_TICKET + 32 * lane_x;
+    uint32_t bin = 0;
+    for (;;) {
+        if (t == 0) s_ticket = atomicAdd(ticket, 1u);
+        __syncthreads();
+        const uint64_t it64 = ((uint64_t)s_ticket * LB_TICKETS + lane_x) * LB_U;
+        if (it64 >= total) break;
+        const uint32_t it = (uint32_t)it64;
+        uint64_t r[LB_U], wd[LB_U];
+        uint32_t cn[LB_U], wbase[LB_U];
+#pragma unroll
+        for (int u = 0; u < LB_U; ++u) {
+            const uint32_t item = it + u;
+            cn[u] = 0; r[u] = 0; wbase[u] = 0;
+            if (item < total) {
+                while (bin + 1 < NB && item >= pre[bin + 1]) ++bin;
+                const uint64_t ch = (uint64_t)bin * g.cap + (item - pre[bin]);
+                cn[u] = w.cnt[ch];
+                r[u] = __builtin_nontemporal_load(&w.rec[ch * LB_CH + t]);   // streamed once: keep the slice in L2
+                wbase[u] = bin * g.wps;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < LB_U; ++u) {
+            const uint32_t word = wbase[u] + ((uint32_t)(r[u] >> LB_IDX_BITS) & ((1u << LB_WORD_BITS) - 1));
+            wd[u] = (t < cn[u] && word < nbloom) ? bloom[word] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < LB_U; ++u) {
+            const uint64_t m3 = lb_mask3((uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));
+            const bool pass = t < cn[u] && (wd[u] & m3) == m3;
+            const uint64_t m = __ballot(pass);
+            if (m) {
+                uint32_t r0 = 0;
+                if ((t & 63u) == 0) r0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
+                r0 = __shfl(r0, 0);
+                if (pass) surv[r0 + (uint32_t)__popcll(m & ((1ull << (t & 63u)) - 1))] = (uint32_t)r[u] & ((1u << LB_IDX_BITS) - 1);
+            }
+        }
+        __syncthreads();
+        if (s_n > (uint32_t)(LB_SURV - LB_U * LB_FB)) flush();
+    }
+    if (s_n) flush();
+}
+
+}  // namespace aix
+
+// ---------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------
+static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+void lookup_binned_release(aix_index* h) {
+    if (h->lb_done) { (void)hipEventSynchronize(h->lb_done); (void)hipEventDestroy(h->lb_done); h->lb_done = nullptr; }
+    if (h->lb_ws) { (void)hipFree(h->lb_ws); h->lb_ws = nullptr; h->lb_ws_bytes = 0; }
+    if (h->lb_stats) { (void)hipFree(h->lb_stats); h->lb_stats = nullptr; }
+}
+
+// AIX_TAKEN: the batch is enqueued (binned kernels and, in auto mode, the gated direct kernel); AIX_NOT_TAKEN: the caller runs the
+// direct path; anything else is an error status
+int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t N, uint32_t* out, hipStream_t s) {
+    const long sw = env_int("AIX_LOOKUP_BINNED", 0, 2, 1);
+    if (sw == 0 || d.k != 23 || !d.canonical_only || !d.bk || !d.bloom || d.nbloom == 0) return AIX_LB_NOT_TAKEN;
+    if (sw == 1 && N < env_u64("AIX_LOOKUP_BINNED_MIN", 0, ~0ull, AIX_LB_DEFAULT_MIN)) return AIX_LB_NOT_TAKEN;
+    const uint64_t slice_bytes = env_u64("AIX_LOOKUP_SLICE_BYTES", 8, 2ull << 20, 1ull << 20);
+    LbGeom g;
+    g.wps = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(slice_bytes / 8, 1), d.nbloom);
+    g.nbins = (d.nbloom + g.wps - 1) / g.wps;
+    if (g.nbins > (uint32_t)LB_MAXBINS) return AIX_LB_NOT_TAKEN;   // a filter above ~500 MB: direct
+    g.inv = g.wps > 1 ? (uint32_t)((1ull << 32) / g.wps) : 0xFFFFFFFFu;
+    const uint64_t piece = std::min<uint64_t>(std::min<uint64_t>(N, 1ull << LB_IDX_BITS), env_u64("AIX_LOOKUP_PIECE", 1, 1ull << LB_IDX_BITS, 1ull << LB_IDX_BITS));
+    const unsigned grid_a = (unsigned)std::min<uint64_t>((piece + LB_TILE - 1) / LB_TILE, LB_GRID_A);
+    // a slice region: its share of a uniformly hashed piece plus a quarter, plus the chunk every pass-A workgroup leaves partly filled
+    const uint64_t test_cap = env_u64("AIX_LOOKUP_TEST_BIN_CAP", 0, ~0ull, ~0ull);
+    uint64_t cap = test_cap != ~0ull ? (test_cap + LB_CH - 1) / LB_CH : (piece + piece / 4) / g.nbins / LB_CH + 2 + grid_a;
+    cap = std::min<uint64_t>(cap, (piece + LB_CH - 1) / LB_CH + grid_a);
+    g.cap = (uint32_t)cap;
+    const uint64_t off_list = LB_HDR_BYTES, off_cnt = align_up(off_list + 4 * piece, 256), off_rec = align_up(off_cnt + 4ull * g.nbins * cap, 256);
+    const uint64_t need = off_rec + 8ull * g.nbins * cap * LB_CH;
+
+    std::lock_guard<std::mutex> lk(h->lb_mutex);               // orders the enqueueing; the event orders the streams
+    if (!h->lb_done && hipEventCreateWithFlags(&h->lb_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); h->lb_done = nullptr; return AIX_LB_NOT_TAKEN; }
+    if (!h->lb_stats) {
+        if (hipMalloc((void**)&h->lb_stats, 32) != hipSuccess) { (void)hipGetLastError(); h->lb_stats = nullptr; return AIX_LB_NOT_TAKEN; }
+        HIPCHK(hipMemset(h->lb_stats, 0, 32));
+    }
+    if (need > h->lb_ws_bytes) {                               // grow only; the kernels of earlier calls may still be using the old block
+        if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
+        if (h->lb_ws) { (void)hipFree(h->lb_ws); h->lb_ws = nullptr; h->lb_ws_bytes = 0; }
+        if (hipMalloc(&h->lb_ws, need) != hipSuccess) { (void)hipGetLastError(); h->lb_ws = nullptr; return AIX_LB_NOT_TAKEN; }
+        h->lb_ws_bytes = need;
+    }
+    if (h->lb_used && h->lb_stream != s) HIPCHK(hipStreamWaitEvent(s, h->lb_done, 0));
+    h->lb_used = true;
+    h->lb_stream = s;
+    struct RecordOnExit {                                       // also behind a failed launch: what was enqueued before it uses the workspace
+        hipEvent_t ev; hipStream_t s;
+        ~RecordOnExit() { (void)hipEventRecord(ev, s); }
+    } record_on_exit{h->lb_done, s};
+
+    uint8_t* const base = (uint8_t*)h->lb_ws;
+    LbWs w;
+    w.hdr = (uint32_t*)base;
+    w.list = (uint32_t*)(base + off_list);
+    w.cnt = (uint32_t*)(base + off_cnt);
+    w.rec = (uint64_t*)(base + off_rec);
+    w.stats = (unsigned long long*)h->lb_stats;
+    const unsigned grid_b = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)g.nbins * cap + LB_U - 1) / LB_U, 1), LB_GRID_B);
+    for (uint64_t lo = 0; lo < N; lo += piece) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, N - lo);
+        const uint8_t* qp = q + 23 * lo;
+        uint32_t* op = out + lo;
+        HIPCHK(hipMemsetAsync(w.hdr, 0, LB_HDR_BYTES, s));
+        const uint32_t nsamp = std::min<uint32_t>(m, LB_SAMPLES);
+        hipLaunchKernelGGL(k_lb_gate, dim3(sw == 2 ? 1 : (nsamp + 255) / 256), dim3(256), 0, s, d.m.seed, d.bloom, d.nbloom, qp, m, nsamp, sw == 2 ? 1 : 0, w.hdr,
+                           w.stats);
+        HIPCHK(hipGetLastError());
+        if (sw != 2) HIPCHK(launch_lookup23_ascii(d, qp, m, MODE_TF, LookupOut{op, nullptr, nullptr, nullptr}, s, w.hdr + LB_FLAG));
+        hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), 0, s, d.m.seed, d.nbloom, qp, m, g, w, op);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
+        HIPCHK(hipGetLastError());
+        HIPCHK(launch_lookup23_list(d, qp, w.list, w.hdr + LB_NSURV, m, w.hdr + LB_FLAG, op, w.stats + 3, s));
+    }
+    return AIX_LB_TAKEN;
+}
+
+extern "C" int aix_lookup_binned_stats(aix_index_t* h, uint64_t out[4]) {
+    if (!h || !out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    std::lock_guard<std::mutex> lk(h->lb_mutex);
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (!h->lb_stats) return AIX_OK;
+    if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
+    HIPCHK(hipMemcpy(out, h->lb_stats, 32, hipMemcpyDeviceToHost));
+    return AIX_OK;
+}

@@ -175,6 +175,10 @@ int aix_index_build_23_codes_dev(const void* pf_bytes, uint64_t pf_len, const ui
  * ------------------------------------------------------------------------------------------ */
 int aix_tf_batch_ascii(aix_index_t* h, const char* kmers, uint64_t N, uint32_t* out);
 int aix_tf_batch_ascii_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint32_t* d_out, void* stream);
+/* Tests and profiling: what aix_tf_batch_ascii_dev's binned path (large absent-heavy batches on a canonical index, AIX_LOOKUP_BINNED)
+ * has done on this handle so far. Synchronises. out = pieces binned, pieces answered directly, records that overflowed their bin,
+ * queries that reached the survivor probe. */
+int aix_lookup_binned_stats(aix_index_t* h, uint64_t out[4]);
 /* pre-encoded 2-bit codes (first base most significant; ACGT only), same answers as the ASCII call */
 int aix_tf_batch_codes(aix_index_t* h, const uint64_t* codes, uint64_t N, uint32_t* out);
 int aix_tf_batch_codes_dev(aix_index_t* h, const uint64_t* d_codes, uint64_t N, uint32_t* d_out, void* stream);
