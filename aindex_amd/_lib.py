@@ -31,6 +31,8 @@ DIR_NEXT, DIR_PREV, DIR_BOTH = 0, 1, 2
 WALK_GREEDY, WALK_UNITIG = 0, 1
 STOP_NAMES = ("max_steps", "dead_end", "branch", "join", "loop")   # AIX_STOP_*
 WALK_MAX_STEPS = 1 << 20
+SPECTRUM_STATS = 8                                                 # AIX_SPECTRUM_STATS
+STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", "max_wide", "sum_wide")
 
 
 class AixError(RuntimeError):
@@ -151,6 +153,16 @@ SIGNATURES = {
     "aix_seq_hits_dev": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_seq_votes": (i32, [vp, vp, vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "aix_seq_votes_dev": (i32, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_values_narrow_dev": (i32, [vp, u64, vp, vp]),
+    "aix_spectrum_dev": (i32, [vp, i32, u64, u64, vp, vp, vp]),
+    "aix_select_dev": (i32, [vp, u64, u32, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+    "aix_kmer_values_dev": (i32, [vp, vp, vp]),
+    "aix_tf_spectrum": (i32, [vp, u64, vp, vp]),
+    "aix_tf_spectrum_dev": (i32, [vp, u64, vp, vp, vp]),
+    "aix_top_kmers": (i32, [vp, u32, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
+    "aix_top_kmers_dev": (i32, [vp, u32, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+    "aix_kmers_by_kid": (i32, [vp, vp, u64, vp, vp, vp]),
+    "aix_kmers_by_kid_dev": (i32, [vp, vp, u64, vp, vp, vp, vp]),
     "aix_positions_start": (i32, [vp, u64, C.POINTER(u64)]),
     "aix_positions_start_k": (i32, [vp, u64, i32, C.POINTER(u64)]),
     "aix_index_scatter_shard_codes_dev": (i32, [vp, u64, vp, vp, u64, u64, i32, vp, vp, vp, vp]),

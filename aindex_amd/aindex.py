@@ -414,32 +414,34 @@ class AIndex:
             raise ValueError(f"Unsupported kmer_type: {kmer_type}. Use '13mer', '23mer', or 'auto'")
         return kmer_type
 
-    def _frequencies(self, kmer_type: str):
-        """(labels as a callable index -> str, tf array) exactly as the reference enumerates them: 13-mer mode walks the
-        tf array in FILE order (mphf order) and labels entry i with the base-4 spelling of i (aindex.py:633-649 — the label
-        is the 2-bit decoding of the mphf index, not the k-mer counted there; kept for drop-in parity); 23-mer mode walks
-        kid = 0..n-1 and asks get_tf_value(get_kmer_by_kid(kid)) — one batch lookup here."""
-        if kmer_type == "13mer":
-            tf = np.asarray(self._wrapper.get_13mer_tf_array_numpy()).astype(np.uint64) & np.uint64(0xFFFFFFFF)   # u32 view of the API
-            return self._index_to_13mer, tf
-        if self.n_kmers == 0:
+    _FREQ_CHUNK = 1 << 16                                          # entries decoded per fetch of iter_kmers_by_frequency
+
+    def _freq_index(self, kmer_type: str):
+        """The handle whose entries the reference enumerates: 13-mer mode walks the tf array in FILE order (mphf order) and labels entry i
+        with the base-4 spelling of i (aindex.py:633-649 — the label is the 2-bit decoding of the mphf index, not the k-mer counted there;
+        kept for drop-in parity); 23-mer mode walks kid = 0..n-1 and asks get_tf_value(get_kmer_by_kid(kid)). None: nothing to enumerate
+        ("13mer" without a 13-mer index: the reference's empty tf array)."""
+        if kmer_type == "23mer" and self.n_kmers == 0:
             raise RuntimeError("23-mer index not properly loaded")
-        from . import synth
-        codes = self._wrapper._checker() & np.uint64((1 << 46) - 1)                    # get_kmer_by_kid(kid) = decode of checker[kid]
-        kmers = synth.decode_kmers(codes, 23)                                          # (n, 23) uint8: no Python strings until one is yielded
-        tf = self.get_tf_values_array(kmers).astype(np.uint64)                         # get_tf_value(kmer) for every kid: ONE batch lookup
-        return (lambda i: bytes(kmers[i]).decode()), tf
+        return self._wrapper._freq_index(kmer_type)
 
     def iter_kmers_by_frequency(self, min_tf: int = 1, max_kmers: Optional[int] = None, kmer_type: str = "auto"):
         if not self._loaded:
             raise RuntimeError("Index not loaded")
-        label, tf = self._frequencies(self._kmer_type(kmer_type))
-        keep = np.nonzero(tf >= np.uint64(max(min_tf, 0)))[0]
-        order = keep[np.argsort(-tf[keep].astype(np.int64), kind="stable")]       # descending tf, ties in enumeration order
-        if max_kmers is not None:
-            order = order[:max_kmers]
-        for i in order:
-            yield label(int(i)), int(tf[i])
+        ix = self._freq_index(self._kmer_type(kmer_type))
+        if ix is None or max_kmers == 0:
+            return
+        # the selection runs on the device (threshold by radix select, stable cut, sort of the survivors): descending tf, ties in
+        # enumeration order. What comes back is 8 bytes per selected entry; the strings are decoded a chunk at a time.
+        want = max_kmers if (max_kmers is not None and max_kmers > 0) else 0
+        kid, tf, _, _ = ix.top_kmers(want, max(min_tf, 0), want_kmers=False)
+        if max_kmers is not None and max_kmers < 0:               # freq_list[:max_kmers] of the reference
+            kid, tf = kid[:max_kmers], tf[:max_kmers]
+        for lo in range(0, kid.shape[0], self._FREQ_CHUNK):
+            rows, _, _ = ix.kmers_by_kid(kid[lo:lo + self._FREQ_CHUNK])
+            labels = rows.view(f"S{ix.k}").reshape(-1).tolist()
+            for label, t in zip(labels, tf[lo:lo + self._FREQ_CHUNK].tolist()):
+                yield label.decode("ascii"), t
 
     def get_top_kmers(self, n: int = 100, min_tf: int = 1, kmer_type: str = "auto") -> List[Tuple[str, int]]:
         return list(self.iter_kmers_by_frequency(min_tf=min_tf, max_kmers=n, kmer_type=kmer_type))
@@ -448,14 +450,25 @@ class AIndex:
         if not self._loaded:
             raise RuntimeError("Index not loaded")
         kt = self._kmer_type(kmer_type)
-        _, tf = self._frequencies(kt)
-        nz = tf[tf > 0]
-        total = int(tf.shape[0])
-        return {"kmer_type": kt, "total_kmers": total, "non_zero_kmers": int(nz.shape[0]), "zero_kmers": total - int(nz.shape[0]),
-                "max_tf": int(nz.max()) if nz.shape[0] else 0, "min_tf": int(nz.min()) if nz.shape[0] else 0,
-                "avg_tf": (int(nz.sum(dtype=np.uint64)) / int(nz.shape[0])) if nz.shape[0] else 0,
-                "total_tf": int(tf.sum(dtype=np.uint64)) if nz.shape[0] else 0,
-                "coverage": (int(nz.shape[0]) / total) if total else 0}
+        ix = self._freq_index(kt)
+        st = ix.tf_stats() if ix is not None else {"n": 0, "non_zero": 0, "max": 0, "min_non_zero": 0, "sum": 0}
+        total, nz = st["n"], st["non_zero"]
+        return {"kmer_type": kt, "total_kmers": total, "non_zero_kmers": nz, "zero_kmers": total - nz,
+                "max_tf": st["max"] if nz else 0, "min_tf": st["min_non_zero"] if nz else 0,
+                "avg_tf": (st["sum"] / nz) if nz else 0, "total_tf": st["sum"] if nz else 0,
+                "coverage": (nz / total) if total else 0}
+
+    def get_tf_spectrum(self, max_tf: int = 255, kmer_type: str = "auto") -> List[int]:
+        """Frequency spectrum: entry j <= max_tf = k-mers with term frequency j, the last entry = k-mers with a higher one."""
+        if not self._loaded:
+            raise RuntimeError("Index not loaded")
+        return self._wrapper.get_tf_spectrum(max_tf, self._kmer_type(kmer_type))
+
+    def get_kmers_by_kid_batch(self, kids) -> List[str]:
+        return self._wrapper.get_kmers_by_kid_batch(kids)
+
+    def get_kmer_info_batch(self, kids):
+        return self._wrapper.get_kmer_info_batch(kids)
 
     # ---- 13-mer array access -----------------------------------------------------------------
     def get_13mer_tf_array(self) -> List[int]:

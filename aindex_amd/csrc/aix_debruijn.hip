@@ -29,27 +29,6 @@ struct DbFilter {
     __device__ __forceinline__ void seen(bool active, bool found) { if (policy == 0) fg.seen(active, found); }
 };
 
-// get_freq(uint64_t) (hash.hpp:123-140) for the lane's code; wave-cooperative: every lane calls it (want = false: nothing to probe).
-// The body of k_lookup23_codes.
-template <bool CANON>
-__device__ __forceinline__ uint32_t db_freq(const IndexDev& ix, bool want, uint64_t u, bool absence, bool& found) {
-    const uint64_t r = revcomp(u, 23);
-    uint64_t w0, w1, w2;
-    if (CANON) {
-        const uint64_t key = u <= r ? u : r;
-        ascii23_of_rc(u <= r ? r : u, w0, w1, w2);               // string of `key`
-        const Probe p = probe23_wave<8>(ix, want, w0, w1, w2, key, true, absence);
-        found = p.found;
-        return p.found ? p.tf : 0u;
-    }
-    ascii23_of_rc(r, w0, w1, w2);
-    const Probe f = probe23_wave<8>(ix, want, w0, w1, w2, u, true, absence);
-    ascii23_of_rc(u, w0, w1, w2);
-    const Probe g = probe23_wave<8>(ix, want && !f.found, w0, w1, w2, r, true, absence);
-    found = f.found || g.found;
-    return f.found ? f.tf : (g.found ? g.tf : 0u);
-}
-
 // debrujin.cpp:34-37 (dir 0) and :125-128 (dir 1)
 __device__ __forceinline__ uint64_t db_neigh(uint64_t u, int dir, uint32_t b) {
     return dir == 0 ? (((u << 2) | (uint64_t)b) & kMask46) : ((u >> 2) | ((uint64_t)b << 44));
@@ -105,7 +84,7 @@ __global__ void __launch_bounds__(kDB) k_db_neighbours(const IndexDev ix_, const
         const int d = dirs == AIX_DIR_BOTH ? (int)(rec & 1) : dirs;
         const uint64_t u = db_code(codes, ascii, i, in);
         bool found;
-        const uint32_t t = db_freq<CANON>(ix, in, db_neigh(u, d, b), fl.on(), found);
+        const uint32_t t = freq23_wave<CANON>(ix, in, db_neigh(u, d, b), fl.on(), found);
         fl.seen(in, found);
         const Cont c = db_cont(t, cutoff);
         if (in) {
@@ -134,7 +113,7 @@ __global__ void __launch_bounds__(kDB) k_db_walk(const IndexDev ix_, const uint6
         bool alive = in;
         for (uint32_t step = 0; step < L && __ballot(alive) != 0; ++step) {                                  // wave-uniform, bounded by max_steps
             bool found;
-            const uint32_t t = db_freq<CANON>(ix, alive, db_neigh(cur, dir, b), fl.on(), found);
+            const uint32_t t = freq23_wave<CANON>(ix, alive, db_neigh(cur, dir, b), fl.on(), found);
             fl.seen(alive, found);
             const Cont c = db_cont(t, cutoff);
             const uint64_t nxt = db_neigh(cur, dir, c.best);
@@ -143,7 +122,7 @@ __global__ void __launch_bounds__(kDB) k_db_walk(const IndexDev ix_, const uint6
             if (UNITIG) {
                 if (go && c.n > 1) { stop = AIX_STOP_BRANCH; go = false; }
                 bool found2;
-                const uint32_t t2 = db_freq<CANON>(ix, go, db_neigh(nxt, 1 - dir, b), fl.on(), found2);
+                const uint32_t t2 = freq23_wave<CANON>(ix, go, db_neigh(nxt, 1 - dir, b), fl.on(), found2);
                 fl.seen(go, found2);
                 const Cont c2 = db_cont(t2, cutoff);
                 if (go && c2.n > 1) { stop = AIX_STOP_JOIN; go = false; }

@@ -93,6 +93,27 @@ __device__ __forceinline__ Probe probe23_wave(const IndexDev& ix, bool want, uin
     return r;
 }
 
+// get_freq(uint64_t) (hash.hpp:123-140) = get_tf_value_23mer (python_wrapper.cpp:610-627) of the lane's code: the two-strand probe, forward
+// strand first. Wave-cooperative: every lane calls it (want = false: nothing to probe). The body of k_lookup23_codes at 8 lanes per probe.
+template <bool CANON>
+__device__ __forceinline__ uint32_t freq23_wave(const IndexDev& ix, bool want, uint64_t u, bool absence, bool& found) {
+    const uint64_t r = revcomp(u, 23);
+    uint64_t w0, w1, w2;
+    if (CANON) {
+        const uint64_t key = u <= r ? u : r;
+        ascii23_of_rc(u <= r ? r : u, w0, w1, w2);               // string of `key`
+        const Probe p = probe23_wave<8>(ix, want, w0, w1, w2, key, true, absence);
+        found = p.found;
+        return p.found ? p.tf : 0u;
+    }
+    ascii23_of_rc(r, w0, w1, w2);
+    const Probe f = probe23_wave<8>(ix, want, w0, w1, w2, u, true, absence);
+    ascii23_of_rc(u, w0, w1, w2);
+    const Probe g = probe23_wave<8>(ix, want && !f.found, w0, w1, w2, r, true, absence);
+    found = f.found || g.found;
+    return f.found ? f.tf : (g.found ? g.tf : 0u);
+}
+
 // The absence filter pays when most probes are absent keys (one cached 8-byte read instead of a 128-byte line from HBM) and
 // costs when most are present (one more read each). A wave decides trip by trip from what it has just seen: the filter is
 // consulted in the next trip iff fewer than a quarter of this trip's queries were found. The answers do not depend on it.

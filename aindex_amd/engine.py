@@ -716,6 +716,121 @@ class Index:
                                      _stream_ptr(self.device)), "aix_walk_dev")
         return bases_t, length, stop, tf_t, last
 
+    # ---- k-mers by frequency (aix_spectrum.hip) ------------------------------------------------
+    @staticmethod
+    def _stats_dict(stats: np.ndarray) -> dict:
+        return {f: int(v) for f, v in zip(_lib.STATS_FIELDS, stats.tolist())}
+
+    def tf_spectrum(self, nbins: int):
+        """(hist uint64[nbins], stats dict) of the per-kid values: hist[j] = entries with value j for j < nbins - 1, hist[nbins - 1] = entries
+        with value >= nbins - 1; stats: _lib.STATS_FIELDS. The value of entry i is get_tf_value(get_kmer_by_kid(i)) (23-mer handle) or the
+        u32 view of tf13[i] (13-mer handle)."""
+        if nbins < 2:
+            raise ValueError("nbins must be at least 2")
+        hist, stats = np.empty(nbins, np.uint64), np.empty(_lib.SPECTRUM_STATS, np.uint64)
+        check(lib().aix_tf_spectrum(self._h, nbins, _np_ptr(hist), _np_ptr(stats)), "aix_tf_spectrum")
+        return hist, self._stats_dict(stats)
+
+    def tf_stats(self) -> dict:
+        return self.tf_spectrum(2)[1]
+
+    @staticmethod
+    def _cut(n: int, size: int) -> int:
+        """max_items for the C ABI (a u64; 0 = all): any Python int, cut to the number of entries — ctypes would mask a larger one silently"""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        return min(n, size)
+
+    def top_kmers(self, n: int = 0, min_tf: int = 1, want_kmers: bool = True):
+        """(kid uint32[m], tf uint32[m], kmers uint8[m, k] | None, total): the first n (0 = all) entries with value >= min_tf in descending
+        value, ties in ascending kid; total = entries with value >= min_tf before the cut."""
+        min_tf = max(int(min_tf), 0)
+        if min_tf > 0xFFFFFFFF:                                     # no u32 value reaches it
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), (np.zeros((0, self.k), np.uint8) if want_kmers else None), 0
+        n = self._cut(n, self.n)
+        pk, pt, ps = vp(), vp(), vp()
+        m, total = C.c_uint64(), C.c_uint64()
+        check(lib().aix_top_kmers(self._h, min_tf, n, C.byref(pk), C.byref(pt), C.byref(ps) if want_kmers else None, C.byref(m), C.byref(total)),
+              "aix_top_kmers")
+        kid, tf = self._take_as(pk, m.value, np.uint32), self._take_as(pt, m.value, np.uint32)
+        kmers = self._take_as(ps, m.value * self.k, np.uint8).reshape(m.value, self.k) if want_kmers else None
+        return kid, tf, kmers, total.value
+
+    def kmers_by_kid(self, kids, want_rc: bool = False, want_tf: bool = False):
+        """(kmers uint8[N, k], rc uint8[N, k] | None, tf uint32[N] | None): get_kmer_by_kid / get_kmer_info for a batch of kids (uint64);
+        a kid >= n gives a row of NUL bytes and tf 0."""
+        kd = np.ascontiguousarray(kids, dtype=np.uint64).reshape(-1)
+        n = kd.shape[0]
+        out = np.zeros((n, self.k), np.uint8)
+        rc = np.zeros((n, self.k), np.uint8) if want_rc else None
+        tf = np.zeros(n, np.uint32) if want_tf else None
+        check(lib().aix_kmers_by_kid(self._h, _np_ptr(kd) if n else None, n, _np_ptr(out) if n else None, _np_ptr(rc) if n else None,
+                                     _np_ptr(tf) if n else None), "aix_kmers_by_kid")
+        return out, rc, tf
+
+    def kmer_values_t(self, out_t=None):
+        """int32[n] device tensor (u32 bit patterns): the value of every entry in kid order, asynchronous on torch's current stream."""
+        import torch
+        if out_t is None:
+            out_t = torch.empty(self.n, dtype=torch.int32, device=f"cuda:{self.device}")
+        elif out_t.dtype != torch.int32 or out_t.numel() != self.n:
+            raise ValueError("out_t must be an int32 tensor of n elements")
+        self._chk_dev(out_t)
+        with torch.cuda.device(self.device):
+            check(lib().aix_kmer_values_dev(self._h, vp(out_t.data_ptr()) if self.n else None, _stream_ptr(self.device)), "aix_kmer_values_dev")
+        return out_t
+
+    def tf_spectrum_t(self, nbins: int):
+        """(hist int64[nbins], stats int64[8]) device tensors on torch's current stream: complete on return for a 23-mer handle (the values
+        pass uses pool scratch), asynchronous for a 13-mer handle."""
+        import torch
+        if nbins < 2:
+            raise ValueError("nbins must be at least 2")
+        dev = f"cuda:{self.device}"
+        hist, stats = torch.empty(nbins, dtype=torch.int64, device=dev), torch.empty(_lib.SPECTRUM_STATS, dtype=torch.int64, device=dev)
+        with torch.cuda.device(self.device):
+            check(lib().aix_tf_spectrum_dev(self._h, nbins, vp(hist.data_ptr()), vp(stats.data_ptr()), _stream_ptr(self.device)), "aix_tf_spectrum_dev")
+        return hist, stats
+
+    def tf_stats_t(self):
+        return self.tf_spectrum_t(2)[1]
+
+    def top_kmers_t(self, n: int = 0, min_tf: int = 1, want_kmers: bool = True):
+        """(kid int32[m], tf int32[m], kmers uint8[m, k] | None, total) device tensors (u32 bit patterns); one call into buffers of
+        min(n, self.n) entries, returned cut to the m entries selected."""
+        import torch
+        dev = f"cuda:{self.device}"
+        min_tf = min(max(int(min_tf), 0), 1 << 32)
+        n = self._cut(n, self.n)
+        cap = 0 if min_tf >> 32 else (n if n else self.n)
+        kid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        tf = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        kmers = torch.empty((max(cap, 1), self.k), dtype=torch.uint8, device=dev) if want_kmers else None
+        m, total = C.c_uint64(), C.c_uint64()
+        with torch.cuda.device(self.device):
+            if not min_tf >> 32:                                    # else: no u32 value reaches it
+                check(lib().aix_top_kmers_dev(self._h, min_tf, n, vp(kid.data_ptr()), vp(tf.data_ptr()), vp(kmers.data_ptr()) if want_kmers else None, cap,
+                                              C.byref(m), C.byref(total), _stream_ptr(self.device)), "aix_top_kmers_dev")
+        assert m.value <= cap
+        return kid[: m.value], tf[: m.value], (kmers[: m.value] if want_kmers else None), total.value
+
+    def kmers_by_kid_t(self, kids_t, want_rc: bool = False, want_tf: bool = False):
+        """kmers_by_kid on an int64 device tensor of kids (u64 bit patterns): (kmers uint8[N, k], rc | None, tf int32[N] | None)."""
+        import torch
+        self._chk_dev(kids_t)
+        if kids_t.dtype != torch.int64:
+            raise ValueError("kids: an int64 tensor")
+        n, dev = kids_t.numel(), kids_t.device
+        out = torch.empty((n, self.k), dtype=torch.uint8, device=dev)
+        rc = torch.empty((n, self.k), dtype=torch.uint8, device=dev) if want_rc else None
+        tf = torch.empty(n, dtype=torch.int32, device=dev) if want_tf else None
+        with torch.cuda.device(dev):
+            check(lib().aix_kmers_by_kid_dev(self._h, vp(kids_t.data_ptr()) if n else None, n, vp(out.data_ptr()) if n else None,
+                                             vp(rc.data_ptr()) if (want_rc and n) else None, vp(tf.data_ptr()) if (want_tf and n) else None,
+                                             _stream_ptr(self.device)), "aix_kmers_by_kid_dev")
+        return out, rc, tf
+
     # ---- HBM-resident (torch) entry points: asynchronous on torch's current stream ------------
     def _chk_dev(self, t):
         if not t.is_cuda or t.device.index != self.device:
@@ -850,3 +965,60 @@ def synth_mix23_t(seed: int, genome_t, n: int, first: int = 0):
         check(lib().aix_synth_mix23_dev(seed, vp(genome_t.data_ptr()), genome_t.numel(), first, n, vp(t.data_ptr()), _stream_ptr()),
               "aix_synth_mix23_dev")
     return t
+
+
+# ---- frequency view of any value tensor in HBM (aix_spectrum.hip; e.g. what count23_fixed_t / count13_t leave there) ----
+def _values_arg(values_t):
+    import torch
+    if not values_t.is_cuda or not values_t.is_contiguous() or values_t.dtype not in (torch.int32, torch.int64):
+        raise ValueError("values: a contiguous int32 (u32) or int64 (u64) tensor on the GPU")
+    return 4 if values_t.dtype == torch.int32 else 8
+
+
+def spectrum_t(values_t, nbins: int):
+    """(hist int64[nbins], stats int64[8]) of a device tensor of u32 (int32) or u64 (int64, binned by their u32 view) values: hist[j] = entries
+    equal to j for j < nbins - 1, hist[nbins - 1] = entries >= nbins - 1; stats: _lib.STATS_FIELDS. Asynchronous on torch's current stream."""
+    import torch
+    eb = _values_arg(values_t)
+    if nbins < 2:
+        raise ValueError("nbins must be at least 2")
+    dev = values_t.device
+    hist, stats = torch.empty(nbins, dtype=torch.int64, device=dev), torch.empty(_lib.SPECTRUM_STATS, dtype=torch.int64, device=dev)
+    n = values_t.numel()
+    with torch.cuda.device(dev):
+        check(lib().aix_spectrum_dev(vp(values_t.data_ptr()) if n else None, eb, n, nbins, vp(hist.data_ptr()), vp(stats.data_ptr()), _stream_ptr(dev)),
+              "aix_spectrum_dev")
+    return hist, stats
+
+
+def top_values_t(values_t, n: int = 0, min_v: int = 1, idx_t=None, val_t=None):
+    """(idx int32[m], val int32[m], total) (u32 bit patterns): the first n (0 = all) entries with value >= min_v in descending value, ties in
+    ascending index; total = entries >= min_v before the cut. An int64 tensor is taken by its u32 view. idx_t / val_t: caller-owned int32
+    buffers; when the selection does not fit them they are left as they are and (None, None, total) is returned."""
+    import torch
+    eb = _values_arg(values_t)
+    dev, cnt = values_t.device, values_t.numel()
+    m, total = C.c_uint64(), C.c_uint64()
+    min_v = max(int(min_v), 0)
+    n = Index._cut(n, cnt)
+    if min_v > 0xFFFFFFFF:                                          # no u32 value reaches it
+        cnt, min_v = 0, 0
+    with torch.cuda.device(dev):
+        if eb == 8:
+            narrow = torch.empty(cnt, dtype=torch.int32, device=dev)
+            check(lib().aix_values_narrow_dev(vp(values_t.data_ptr()) if cnt else None, cnt, vp(narrow.data_ptr()) if cnt else None, _stream_ptr(dev)),
+                  "aix_values_narrow_dev")
+            values_t = narrow
+        if idx_t is None:
+            cap = min(n, cnt) if n else cnt
+            idx_t = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)[:cap]
+            val_t = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)[:cap]
+        cap = idx_t.numel()
+        if idx_t.dtype != torch.int32 or (val_t is not None and (val_t.dtype != torch.int32 or val_t.numel() < cap)):
+            raise ValueError("idx_t / val_t: int32 tensors of equal length")
+        check(lib().aix_select_dev(vp(values_t.data_ptr()) if cnt else None, cnt, min_v, n, vp(idx_t.data_ptr()) if cap else None,
+                                   vp(val_t.data_ptr()) if (val_t is not None and cap) else None, cap, C.byref(m), C.byref(total), _stream_ptr(dev)),
+              "aix_select_dev")
+    if m.value > cap:
+        return None, None, total.value
+    return idx_t[: m.value], (val_t[: m.value] if val_t is not None else None), total.value

@@ -536,6 +536,43 @@ class AindexWrapper:
         kmer = self._decode23(int(self._checker()[kid]))
         return (int(ix.tf_array()[kid]), kmer, self.get_reverse_complement_23mer(kmer))
 
+    # ---- k-mers by frequency and by kid, batched (engine.Index.top_kmers / tf_spectrum / kmers_by_kid) ----
+    def _freq_index(self, kmer_type: str) -> Optional[Index]:
+        """the handle whose entries iter_kmers_by_frequency enumerates for "13mer" / "23mer"; None = nothing to enumerate"""
+        if kmer_type == "13mer":
+            return self._ix13 if self._is_13mer_mode else None
+        return self._need23()
+
+    def get_tf_spectrum(self, max_tf: int = 255, kmer_type: str = "auto") -> List[int]:
+        """The frequency spectrum: entry j <= max_tf = the number of k-mers whose term frequency (the value iter_kmers_by_frequency
+        reports) is j; the last entry (index max_tf + 1) = the number with a higher one."""
+        if max_tf < 0:
+            raise ValueError("max_tf must not be negative")
+        if kmer_type == "auto":
+            kmer_type = "13mer" if self._is_13mer_mode else "23mer"
+        if kmer_type not in ("13mer", "23mer"):
+            raise ValueError(f"Unsupported kmer_type: {kmer_type}. Use '13mer', '23mer', or 'auto'")
+        ix = self._freq_index(kmer_type)
+        return ix.tf_spectrum(max_tf + 2)[0].tolist() if ix is not None else [0] * (max_tf + 2)
+
+    @staticmethod
+    def _kid_array(kids) -> np.ndarray:
+        if isinstance(kids, np.ndarray) and kids.dtype.kind == "u":
+            return kids.astype(np.uint64).reshape(-1)
+        return np.array([k if 0 <= k < (1 << 64) else (1 << 64) - 1 for k in kids], dtype=np.uint64)      # out of range = beyond every n
+
+    def get_kmers_by_kid_batch(self, kids) -> List[str]:
+        """[get_kmer_by_kid(kid) for kid in kids] (:718-724) in one call: "" for a kid beyond the index."""
+        rows, _, _ = self._need23().kmers_by_kid(self._kid_array(kids))
+        return [r.decode("ascii").rstrip("\0") for r in rows.view("S23").reshape(-1).tolist()] if rows.shape[0] else []
+
+    def get_kmer_info_batch(self, kids) -> List[Tuple[int, str, str]]:
+        """[get_kmer_info(kid) for kid in kids] (:744-755) in one call: (tf[kid], k-mer, reverse complement), (0, "", "") beyond the index."""
+        rows, rc, tf = self._need23().kmers_by_kid(self._kid_array(kids), want_rc=True, want_tf=True)
+        if not rows.shape[0]:
+            return []
+        return [(t, a.decode("ascii"), b.decode("ascii")) for t, a, b in zip(tf.tolist(), rows.view("S23").reshape(-1).tolist(), rc.view("S23").reshape(-1).tolist())]
+
     def get_reverse_complement_13mer(self, kmer: str) -> str:
         return _enc(kmer)[::-1].translate(_COMP).decode("latin-1")                      # :505-517
 
@@ -569,10 +606,8 @@ class AindexWrapper:
     def get_13mer_statistics(self) -> dict:
         if not self._is_13mer_mode:                                                     # :1038-1068
             return {}
-        tf = np.asarray(self._tf13_host)
-        nz = tf[tf != 0]
-        return {"total_kmers": TOTAL_13MERS, "non_zero_kmers": int(nz.shape[0]), "max_frequency": int(tf.max()),
-                "total_count": int(tf.sum(dtype=np.uint64))}
+        st = self._ix13.tf_stats()                                                      # one pass over the u64 table in HBM
+        return {"total_kmers": TOTAL_13MERS, "non_zero_kmers": st["non_zero_wide"], "max_frequency": st["max_wide"], "total_count": st["sum_wide"]}
 
     def get_23mer_statistics(self) -> str:
         if self._is_13mer_mode:                                                         # :1301-1315

@@ -568,6 +568,59 @@ int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs
                       uint64_t* d_vote_offsets, uint64_t* d_rid, uint8_t* d_strand, int64_t* d_diag, uint32_t* d_votes, uint32_t* d_qfirst,
                       uint32_t* d_qlast, uint64_t cap, uint64_t* total_out, void* stream);   /* python_wrapper.cpp:800-831, 757-789 */
 
+/* ------------------------------------------------------------------------------------------
+ * k-mers by frequency: per-kid values, frequency spectrum and statistics, stable top-N / threshold selection, batch kid -> k-mer.
+ * replaces AIndex.iter_kmers_by_frequency / get_top_kmers / get_kmer_frequency_stats (aindex/core/aindex.py:594-793: a Python loop over
+ *          every kid and a sort of all of them) and, N at a time, AindexWrapper::get_kmer_by_kid / get_kmer_info
+ *          (python_wrapper.cpp:718-755).
+ * Value of entry i. 23-mer handle, i < n: get_tf_value_23mer(get_kmer_by_kid(i)) (python_wrapper.cpp:610-627, 718-724) = the two-strand
+ * probe of checker[i] & (2^46 - 1), forward strand first; NOT tf[i] (they differ where a slot holds a key that is not in its own MPHF
+ * slot). 13-mer handle, i < 4^13: (uint32_t) tf13[i] in file order (get_13mer_tf_array, :983-991); the label of entry i is the base-4
+ * spelling of i (aindex.py:574-592). Order: descending value, ties in ascending i (Python's stable sort(key = tf, reverse = True),
+ * aindex.py:643, 671) = ascending by ((2^32 - 1 - v) << 32) | i. Selection(min_v, max_items): the first max_items (0 = all) entries
+ * with v >= min_v in that order; total = the number of entries with v >= min_v before the cut. Spectrum(nbins >= 2): hist[j] = #{i : v_i = j}
+ * for j < nbins - 1, hist[nbins - 1] = #{i : v_i >= nbins - 1}. The answers do not depend on any probe switch.
+ * Both handle kinds are accepted. AIX_ERR_ARG for nbins < 2 or a NULL output; AIX_ERR_NOMEM, before anything is allocated, for a size
+ * that cannot be held (nbins > 2^32, N >= 2^56). The _dev forms of the selection follow aix_positions_query_dev: *n_out / *total_out are
+ * always produced, entries only when *n_out <= cap, nothing is written at or beyond *n_out. Stream contract, per entry point:
+ * aix_select_dev and aix_top_kmers_dev read the size of the selection back, so they return after all their work on `stream` has completed
+ * (d_kmers included); aix_tf_spectrum_dev on a 23-mer handle also returns completed (its values live in pool scratch that goes back idle),
+ * on a 13-mer handle it is asynchronous; aix_values_narrow_dev, aix_spectrum_dev, aix_kmer_values_dev and aix_kmers_by_kid_dev are
+ * asynchronous on `stream`. Host arrays handed out are malloc'd (aix_free).
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_SPECTRUM_STATS 8   /* words of a statistics record: n, non-zero entries, max, smallest non-zero value (0 if none), sum — of the
+                                  u32 values — then non-zero entries, max and sum at full width (they differ from words 1, 2, 4 only for a
+                                  u64 source: get_13mer_statistics, python_wrapper.cpp:1038-1068, reads the u64 table) */
+/* Array level (no handle; device pointers of the current device). These also serve the tensors aix_count23_fixed_dev (u32) and
+ * aix_count13_dev (u64) leave in HBM. */
+/* the u32 view of n u64 entries (get_13mer_tf_array, python_wrapper.cpp:983-991) */
+int aix_values_narrow_dev(const uint64_t* d_in, uint64_t n, uint32_t* d_out, void* stream);
+/* spectrum (d_hist[nbins]) and statistics (d_stats[AIX_SPECTRUM_STATS]) of n entries of elem_bytes 4 (u32) or 8 (u64, binned by their
+ * u32 view); what get_kmer_frequency_stats computes (aindex.py:703-793). Asynchronous on `stream`. */
+int aix_spectrum_dev(const void* d_values, int elem_bytes, uint64_t n, uint64_t nbins, uint64_t* d_hist, uint64_t* d_stats, void* stream);
+/* Selection(min_v, max_items) over d_values[n], n < 2^32 (aindex.py:636-647): d_idx[j] / d_val[j] = index and value of the j-th entry.
+ * d_val may be NULL. */
+int aix_select_dev(const uint32_t* d_values, uint64_t n, uint32_t min_v, uint64_t max_items, uint32_t* d_idx, uint32_t* d_val, uint64_t cap,
+                   uint64_t* n_out, uint64_t* total_out, void* stream);
+/* Handle level. */
+/* d_out[i] = value of entry i for every i < n (aindex.py:661-664 for every kid); asynchronous on `stream` */
+int aix_kmer_values_dev(aix_index_t* h, uint32_t* d_out, void* stream);
+/* spectrum and statistics of the values (aindex.py:703-793); hist_out[nbins], stats_out[AIX_SPECTRUM_STATS] are the caller's */
+int aix_tf_spectrum(aix_index_t* h, uint64_t nbins, uint64_t* hist_out, uint64_t* stats_out);
+int aix_tf_spectrum_dev(aix_index_t* h, uint64_t nbins, uint64_t* d_hist, uint64_t* d_stats, void* stream);   /* aindex.py:703-793; 23-mer handle: completed on return */
+/* iter_kmers_by_frequency(min_tf, max_kmers) (aindex.py:594-681; max_kmers 0 = all): kid, value and — when kmers_out is not NULL — the
+ * k ASCII bytes of every selected entry (get_kmer_by_kid, python_wrapper.cpp:718-724; 13-mer: the spelling of the index). */
+int aix_top_kmers(aix_index_t* h, uint32_t min_tf, uint64_t max_kmers, uint32_t** kid_out, uint32_t** tf_out, char** kmers_out /* nullable */,
+                  uint64_t* n_out, uint64_t* total_out);
+int aix_top_kmers_dev(aix_index_t* h, uint32_t min_tf, uint64_t max_kmers, uint32_t* d_kid, uint32_t* d_tf /* nullable */,
+                      char* d_kmers /* nullable, cap * k bytes */, uint64_t cap, uint64_t* n_out, uint64_t* total_out, void* stream);   /* aindex.py:594-681 */
+/* get_kmer_by_kid / get_kmer_info (python_wrapper.cpp:718-755) for N kids: row i of kmers_out = the k ASCII bytes of checker[kid[i]] &
+ * (2^46 - 1), of rc_out (nullable) its reverse complement, tf_out[i] (nullable) = tf[kid[i]] read directly (:753, not the probe). For
+ * kid[i] >= n the rows are k NUL bytes and tf 0. 13-mer handle: the base-4 spelling of kid[i] and (uint32_t) tf13[kid[i]]. */
+int aix_kmers_by_kid(aix_index_t* h, const uint64_t* kid, uint64_t N, char* kmers_out, char* rc_out /* nullable */, uint32_t* tf_out /* nullable */);
+int aix_kmers_by_kid_dev(aix_index_t* h, const uint64_t* d_kid, uint64_t N, char* d_kmers, char* d_rc /* nullable */, uint32_t* d_tf /* nullable */,
+                         void* stream);   /* python_wrapper.cpp:718-755; asynchronous on `stream` */
+
 /* The same normalisation for a buffer already in HBM (byte-identical output; the readers are finite-state transducers,
  * resolved with a parallel scan of per-chunk transition functions). format must be PLAIN, FASTA or FASTQ; d_out holds
  * len+1 bytes; *out_len is a HOST pointer; the call synchronises the stream. */
