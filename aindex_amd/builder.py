@@ -50,7 +50,8 @@ def build_pf_codes(codes: np.ndarray, k: int) -> bytes:
 
 def build_pf_codes_t(keys_t, k: int) -> bytes:
     """GPU construction (parallel peeling) for keys already in HBM (int64/uint64 tensor of 2-bit codes). The result is a
-    valid emphf `.pf` for the reference, not byte-identical to `build_pf_codes` (see aix_builder_gpu.hip)."""
+    valid emphf `.pf` for the reference, not byte-identical to `build_pf_codes`, and a function of the key set alone: the same keys give the same
+    bytes whatever their order, the stream or the scheduling (see aix_builder_gpu.hip)."""
     import torch
     p, n = vp(), C.c_uint64()
     with torch.cuda.device(keys_t.device):

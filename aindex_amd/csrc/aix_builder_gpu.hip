@@ -7,8 +7,17 @@
 // reference loads and evaluates (mphf.hpp:79-113). Use aix_pf_build* (host) when byte-identity with the reference
 // matters; use this when the keys are already in HBM and build time matters.
 //
+// The output is a function of the key SET: the same keys give the same bytes whatever the scheduling, the stream or the
+// order of the keys. The rule: an edge is peeled in the first round at whose start one of its vertices has degree 1,
+// and its hinge is the LOWEST-numbered vertex of that edge with degree 1 at the start of that round. The edges of a
+// round follow from the degrees alone, a hinge's value depends only on later rounds and on non-hinge vertices (value
+// 0), so nothing else is left to chance; the order of the entries inside a round's slice of the peel list is
+// arbitrary and the bytes do not depend on it. tests/mwhc_ref.py restates the rule in numpy and
+// tests/test_gpu_builder.py holds this file against it byte for byte.
+//
 //   k_edges    : 2-bit code -> ASCII -> Jenkins -> (v0 < v1 < v2), degree and XOR-of-incident-edge-ids per vertex
-//   rounds     : k_claim   every frontier vertex of degree 1 claims its only edge (atomicExch) -> peel list
+//   rounds     : k_claim   every frontier vertex of degree 1 bids for its only edge: claimed[e] = min(claimed[e], v)
+//                k_collect the same frontier again: the vertex that won its edge appends (edge, hinge) to the peel list
 //                k_remove  claimed edges leave their three vertices (degree--, xor ^= e); vertices that drop to
 //                          degree 1 form the next frontier
 //   k_assign   : rounds in reverse: value(hinge) = (orientation - value(other1) - value(other2)) mod 3, 0 -> 3
@@ -67,15 +76,27 @@ __global__ void __launch_bounds__(GB) k_first_frontier(const uint32_t* __restric
         if (deg[v] == 1u) frontier[atomicAdd(fcount, 1u)] = (uint32_t)v;
 }
 
+// claimed[] starts as all-ones, which is no vertex: 3 D < 2^32 is checked at the entry point
 __global__ void __launch_bounds__(GB) k_claim(const uint32_t* __restrict__ frontier, uint32_t fcount, const uint32_t* __restrict__ deg, const uint32_t* __restrict__ xe,
-                                             uint32_t* __restrict__ claimed, uint32_t* __restrict__ peel_edge, uint32_t* __restrict__ peel_hinge,
-                                             uint32_t* __restrict__ pcount) {
+                                             uint32_t* __restrict__ claimed) {
     const uint64_t stride = (uint64_t)gridDim.x * GB;
     for (uint64_t i = (uint64_t)blockIdx.x * GB + threadIdx.x; i < fcount; i += stride) {
         const uint32_t v = frontier[i];
         if (deg[v] != 1u) continue;                      // stale: its last edge was removed through another vertex
+        atomicMin(&claimed[xe[v]], v);
+    }
+}
+
+// deg and xe are as k_claim saw them; a vertex is in a frontier at most once (its degree passes from 2 to 1 once)
+__global__ void __launch_bounds__(GB) k_collect(const uint32_t* __restrict__ frontier, uint32_t fcount, const uint32_t* __restrict__ deg, const uint32_t* __restrict__ xe,
+                                               const uint32_t* __restrict__ claimed, uint32_t* __restrict__ peel_edge, uint32_t* __restrict__ peel_hinge,
+                                               uint32_t* __restrict__ pcount) {
+    const uint64_t stride = (uint64_t)gridDim.x * GB;
+    for (uint64_t i = (uint64_t)blockIdx.x * GB + threadIdx.x; i < fcount; i += stride) {
+        const uint32_t v = frontier[i];
+        if (deg[v] != 1u) continue;
         const uint32_t e = xe[v];
-        if (atomicExch(&claimed[e], 1u) == 0u) {
+        if (claimed[e] == v) {                           // the lowest-numbered degree-1 vertex of e
             const uint32_t idx = atomicAdd(pcount, 1u);
             peel_edge[idx] = e;
             peel_hinge[idx] = v;
@@ -128,9 +149,9 @@ __global__ void __launch_bounds__(GB) k_pack(const uint8_t* __restrict__ bv, uin
 
 struct GpuBuf {
     void* p = nullptr;
-    hipError_t alloc(uint64_t bytes, bool zero, hipStream_t s) {
+    hipError_t alloc(uint64_t bytes, bool fill, hipStream_t s, int byte = 0) {
         hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e == hipSuccess && zero) e = hipMemsetAsync(p, 0, bytes ? bytes : 1, s);
+        if (e == hipSuccess && fill) e = hipMemsetAsync(p, byte, bytes ? bytes : 1, s);
         return e;
     }
     ~GpuBuf() { if (p) (void)hipFree(p); }
@@ -146,7 +167,7 @@ static hipError_t try_build(const uint64_t* d_codes, uint64_t n, int k, uint64_t
     if (e == hipSuccess) e = v2.alloc(4 * n, false, s);
     if (e == hipSuccess) e = deg.alloc(4 * m, true, s);
     if (e == hipSuccess) e = xe.alloc(4 * m, true, s);
-    if (e == hipSuccess) e = claimed.alloc(4 * n, true, s);
+    if (e == hipSuccess) e = claimed.alloc(4 * n, true, s, 0xFF);
     if (e == hipSuccess) e = pedge.alloc(4 * n, false, s);
     if (e == hipSuccess) e = phinge.alloc(4 * n, false, s);
     if (e == hipSuccess) e = f0.alloc(4 * m, false, s);
@@ -158,7 +179,8 @@ static hipError_t try_build(const uint64_t* d_codes, uint64_t n, int k, uint64_t
                        (uint32_t*)deg.p, (uint32_t*)xe.p);
     hipLaunchKernelGGL(k_first_frontier, dim3(ggrid(m)), dim3(GB), 0, s, (const uint32_t*)deg.p, m, (uint32_t*)f0.p, c + 1);
     uint32_t host[4] = {0, 0, 0, 0};
-    e = hipMemcpyAsync(host, c, 16, hipMemcpyDeviceToHost, s);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host, c, 16, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
     std::vector<uint32_t> round_start;
@@ -170,16 +192,19 @@ static hipError_t try_build(const uint64_t* d_codes, uint64_t n, int k, uint64_t
         const int nxt = cur == 1 ? 2 : 1;
         e = hipMemsetAsync(c + nxt, 0, 4, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_claim, dim3(ggrid(fcount)), dim3(GB), 0, s, fa, fcount, (const uint32_t*)deg.p, (const uint32_t*)xe.p, (uint32_t*)claimed.p,
+        hipLaunchKernelGGL(k_claim, dim3(ggrid(fcount)), dim3(GB), 0, s, fa, fcount, (const uint32_t*)deg.p, (const uint32_t*)xe.p, (uint32_t*)claimed.p);
+        hipLaunchKernelGGL(k_collect, dim3(ggrid(fcount)), dim3(GB), 0, s, fa, fcount, (const uint32_t*)deg.p, (const uint32_t*)xe.p, (const uint32_t*)claimed.p,
                            (uint32_t*)pedge.p, (uint32_t*)phinge.p, c);
-        e = hipMemcpyAsync(host, c, 4, hipMemcpyDeviceToHost, s);
+        e = hipGetLastError();                                          // a failed launch would otherwise only surface at the next copy
+        if (e == hipSuccess) e = hipMemcpyAsync(host, c, 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
         const uint32_t now = host[0];
         if (now == peeled) { round_start.pop_back(); break; }
         hipLaunchKernelGGL(k_remove, dim3(ggrid(now - peeled)), dim3(GB), 0, s, (const uint32_t*)pedge.p, peeled, now, (const uint32_t*)v0.p, (const uint32_t*)v1.p,
                            (const uint32_t*)v2.p, (uint32_t*)deg.p, (uint32_t*)xe.p, fb, c + nxt);
-        e = hipMemcpyAsync(host + nxt, c + nxt, 4, hipMemcpyDeviceToHost, s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(host + nxt, c + nxt, 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
         peeled = now;
@@ -210,6 +235,7 @@ static hipError_t try_build(const uint64_t* d_codes, uint64_t n, int k, uint64_t
 
 extern "C" int aix_pf_build_codes_dev(const uint64_t* d_codes, uint64_t n, int k, int device, void* stream, void** pf_out, uint64_t* pf_len) {
     using namespace aix;
+    // arguments and sizes are judged before d_codes is read or the device is touched (test_gpu_builder.py passes an n far beyond its tensor)
     if (!d_codes || !pf_out || !pf_len || n == 0 || k < 1 || k > 32) return AIX_ERR_ARG;
     const uint64_t D = ((uint64_t)std::ceil((double)n * 1.23) + 2) / 3;     // mphf.hpp:26
     if (D == 0) return AIX_ERR_ARG;
