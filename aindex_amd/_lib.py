@@ -33,6 +33,10 @@ STOP_NAMES = ("max_steps", "dead_end", "branch", "join", "loop")   # AIX_STOP_*
 WALK_MAX_STEPS = 1 << 20
 SPECTRUM_STATS = 8                                                 # AIX_SPECTRUM_STATS
 STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", "max_wide", "sum_wide")
+FIX_NAMES = ("clean", "fixed", "partial", "unfixed", "short", "too_long", "bad_range")   # AIX_FIX_*
+READFIX_MAX_LEN, READFIX_MAX_VERIFY, READFIX_MAX_FIXES = 4096, 16, 16
+# aix_readfix_t: one 32-byte record per read
+READFIX_FIELDS = [(f, "<u4") for f in ("status", "weak_before", "weak_after", "fixes", "n0", "nM", "trim_start", "trim_len")]
 
 
 class AixError(RuntimeError):
@@ -68,6 +72,12 @@ def cont_dtype():
     """numpy dtype of one aix_cont_t record"""
     import numpy as np
     return np.dtype(CONT_FIELDS)
+
+
+def readfix_dtype():
+    """numpy dtype of one aix_readfix_t record"""
+    import numpy as np
+    return np.dtype(READFIX_FIELDS)
 
 
 _LIB = None
@@ -149,6 +159,8 @@ SIGNATURES = {
     "aix_neighbours_dev": (i32, [vp, vp, vp, u64, i32, u32, vp, vp]),
     "aix_walk": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp]),
     "aix_walk_dev": (i32, [vp, vp, vp, u64, i32, u64, u32, i32, vp, vp, vp, vp, vp, vp]),
+    "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
+    "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "aix_seq_hits_dev": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_seq_votes": (i32, [vp, vp, vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

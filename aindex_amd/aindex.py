@@ -20,6 +20,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from . import _lib
 from .wrapper import AindexWrapper
 
 logger = logging.getLogger(__name__)
@@ -373,6 +374,60 @@ class AIndex:
     def extend_batch(self, kmers, max_steps: int = 1000, cutoff: int = 0, mode: str = "greedy", direction: str = "next") -> list:
         """[(extension, stop_name)] along the best continuation of every 23-mer, one GPU call per direction; see AindexWrapper.extend_batch."""
         return self._wrapper.extend_batch(kmers, max_steps, cutoff, mode, direction)
+
+    # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
+    def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):
+        """(corrected reads, records): every read's weak 23-windows (tf <= true_errors, read.hpp:296) are looked for, up to max_fixes
+        single-base substitutions are applied where exactly one base makes the next `verify` windows solid, one GPU call. records is a
+        structured array (_lib.readfix_dtype()) with status (index into _lib.FIX_NAMES), weak_before, weak_after, fixes, n0, nM and
+        the longest solid span trim_start, trim_len (what cut_start_to / cut_end_from would keep, read.hpp:324-343)."""
+        bs = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in reads]
+        if not bs:
+            return [], np.zeros(0, dtype=_lib.readfix_dtype())
+        lens = np.array([len(b) for b in bs], dtype=np.uint64)
+        end = np.cumsum(lens + np.uint64(1), dtype=np.uint64) - np.uint64(1)        # one separator byte behind every read
+        start = end - lens
+        buf = np.frombuffer(b"\n".join(bs) + b"\n", dtype=np.uint8)
+        out, rec, _, _ = self._wrapper._need23().fix_reads(buf, start, end, true_errors, verify, max_fixes)
+        raw = out.tobytes()
+        return [raw[a:b].decode("latin-1") for a, b in zip(start.tolist(), end.tolist())], rec
+
+    def classify_reads(self, reads: List[str], true_errors: int = 1):
+        """The records of correct_reads with max_fixes = 0: profile and trim span only, nothing is changed."""
+        return self.correct_reads(reads, true_errors, 1, 0)[1]
+
+    def correct_reads_file(self, reads_file: str, out_file: str, true_errors: int = 1, verify: int = 8, max_fixes: int = 4,
+                           chunk_bytes: int = 64 << 20) -> dict:
+        """correct_reads over a .reads file (one record per line, mates separated by '~'; every mate is a read of its own), in chunks
+        cut at line ends. out_file has the size of reads_file and differs from it in the fixed bytes only. Returns the number of
+        mates per status name (_lib.FIX_NAMES), "reads" (their sum) and simple_ok / simple_n0 / simple_nM, the counters of
+        CorrectionErrors (read.hpp:36-117): fixes applied, boundaries without a candidate base, boundaries with several."""
+        ix = self._wrapper._need23()
+        totals = {name: 0 for name in _lib.FIX_NAMES}
+        totals.update(reads=0, simple_ok=0, simple_n0=0, simple_nM=0)
+        with open(reads_file, "rb") as src, open(out_file, "wb") as dst:
+            while True:
+                chunk = src.read(chunk_bytes)
+                if not chunk:
+                    break
+                if not chunk.endswith(b"\n"):
+                    chunk += src.readline()                                           # up to the line end (or the end of the file)
+                a = np.frombuffer(chunk, dtype=np.uint8)
+                seps = np.flatnonzero((a == 10) | (a == 126)).astype(np.uint64)
+                start = np.concatenate([np.zeros(1, np.uint64), seps + np.uint64(1)])
+                end = np.concatenate([seps, np.array([a.shape[0]], np.uint64)])
+                if a[-1] == 10:                                                       # nothing follows the last line end
+                    start, end = start[:-1], end[:-1]
+                out, rec, _, _ = ix.fix_reads(a, start, end, true_errors, verify, max_fixes)
+                dst.write(out.tobytes())
+                counts = np.bincount(rec["status"], minlength=len(_lib.FIX_NAMES))
+                for name, n in zip(_lib.FIX_NAMES, counts.tolist()):
+                    totals[name] += n
+                totals["reads"] += int(rec.shape[0])
+                totals["simple_ok"] += int(rec["fixes"].sum(dtype=np.uint64))
+                totals["simple_n0"] += int(rec["n0"].sum(dtype=np.uint64))
+                totals["simple_nM"] += int(rec["nM"].sum(dtype=np.uint64))
+        return totals
 
     def get_reads_array(self, starts, ends, revcomp=False):
         """CSR arrays (offsets, bytes uint8); see AindexWrapper.get_reads_array."""

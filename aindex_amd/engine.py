@@ -716,6 +716,68 @@ class Index:
                                      _stream_ptr(self.device)), "aix_walk_dev")
         return bases_t, length, stop, tf_t, last
 
+    # ---- read cleaning (aix_readfix.hip) ---------------------------------------------------------
+    @staticmethod
+    def _fix_args(verify: int, max_fixes: int):
+        if not 1 <= verify <= _lib.READFIX_MAX_VERIFY:
+            raise ValueError(f"verify {verify}: 1 .. {_lib.READFIX_MAX_VERIFY}")
+        if not 0 <= max_fixes <= _lib.READFIX_MAX_FIXES:
+            raise ValueError(f"max_fixes {max_fixes}: 0 .. {_lib.READFIX_MAX_FIXES}")
+
+    def fix_reads(self, buf, start, end, true_errors: int = 1, verify: int = 8, max_fixes: int = 4, fix_pos=None, fix_old=None):
+        """Weak-window profile, trim span and single-base fixes of the reads buf[start[r] .. end[r]) (ascending, disjoint): (corrected copy
+        of buf uint8[], records readfix_dtype[M], fix_pos uint32[M, max_fixes], fix_old uint8[M, max_fixes]). fix_pos / fix_old: caller-owned
+        rows to write into (what lies at or beyond a row's `fixes` is left as it is); fresh rows are zeroed."""
+        self._fix_args(verify, max_fixes)
+        out = np.array(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf, dtype=np.uint8, copy=True).reshape(-1)
+        st, en = np.ascontiguousarray(start, dtype=np.uint64).reshape(-1), np.ascontiguousarray(end, dtype=np.uint64).reshape(-1)
+        m = st.shape[0]
+        if en.shape[0] != m:
+            raise ValueError("start and end must have the same length")
+        rec = np.zeros(m, dtype=_lib.readfix_dtype())
+        if fix_pos is None:
+            fix_pos = np.zeros((m, max_fixes), dtype=np.uint32)
+        if fix_old is None:
+            fix_old = np.zeros((m, max_fixes), dtype=np.uint8)
+        for a, dt in ((fix_pos, np.uint32), (fix_old, np.uint8)):
+            if a.dtype != dt or a.size != m * max_fixes or not a.flags.c_contiguous:
+                raise ValueError(f"fix_pos / fix_old must be contiguous uint32 / uint8 arrays of M * max_fixes = {m * max_fixes} elements")
+        logs = max_fixes > 0 and m > 0
+        check(lib().aix_reads_fix(self._h, _np_ptr(out) if m else None, out.shape[0], _np_ptr(st) if m else None, _np_ptr(en) if m else None, m, true_errors,
+                                  verify, max_fixes, _np_ptr(rec) if m else None, _np_ptr(fix_pos) if logs else None, _np_ptr(fix_old) if logs else None),
+              "aix_reads_fix")
+        return out, rec, fix_pos, fix_old
+
+    def fix_reads_t(self, buf_t, start_t, end_t, true_errors: int = 1, verify: int = 8, max_fixes: int = 4, fix_pos_t=None, fix_old_t=None):
+        """fix_reads on device tensors, asynchronous on torch's current stream: buf_t (uint8) is fixed IN PLACE; start_t / end_t are int64
+        tensors of M pairwise disjoint ranges. Returns (rec int32[M, 8] — the u32 words status, weak_before, weak_after, fixes, n0, nM,
+        trim_start, trim_len —, fix_pos int32[M, max_fixes], fix_old uint8[M, max_fixes]); fix_pos_t / fix_old_t: caller-owned rows."""
+        import torch
+        self._fix_args(verify, max_fixes)
+        if buf_t.dtype != torch.uint8 or start_t.dtype != torch.int64 or end_t.dtype != torch.int64 or start_t.numel() != end_t.numel():
+            raise ValueError("buf_t: a uint8 tensor; start_t / end_t: int64 tensors of equal length")
+        m, dev = start_t.numel(), buf_t.device
+        for t in (buf_t, start_t, end_t):
+            if t.numel():
+                self._chk_dev(t)
+        rec = torch.zeros((m, 8), dtype=torch.int32, device=dev)
+        if fix_pos_t is None:
+            fix_pos_t = torch.zeros((m, max_fixes), dtype=torch.int32, device=dev)
+        if fix_old_t is None:
+            fix_old_t = torch.zeros((m, max_fixes), dtype=torch.uint8, device=dev)
+        for t, dt in ((fix_pos_t, torch.int32), (fix_old_t, torch.uint8)):
+            if t.dtype != dt or t.numel() != m * max_fixes:
+                raise ValueError(f"fix_pos_t / fix_old_t must be int32 / uint8 tensors of M * max_fixes = {m * max_fixes} elements")
+            if t.numel():
+                self._chk_dev(t)
+        logs = max_fixes > 0 and m > 0
+        with torch.cuda.device(dev):
+            check(lib().aix_reads_fix_dev(self._h, vp(buf_t.data_ptr()) if m else None, buf_t.numel(), vp(start_t.data_ptr()) if m else None,
+                                          vp(end_t.data_ptr()) if m else None, m, true_errors, verify, max_fixes, vp(rec.data_ptr()) if m else None,
+                                          vp(fix_pos_t.data_ptr()) if logs else None, vp(fix_old_t.data_ptr()) if logs else None,
+                                          _stream_ptr(self.device)), "aix_reads_fix_dev")
+        return rec, fix_pos_t, fix_old_t
+
     # ---- k-mers by frequency (aix_spectrum.hip) ------------------------------------------------
     @staticmethod
     def _stats_dict(stats: np.ndarray) -> dict:

@@ -530,6 +530,67 @@ int aix_walk_dev(aix_index_t* h, const uint64_t* d_codes /* or NULL */, const ch
                  uint32_t* d_tf /* nullable */, uint64_t* d_last /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
+ * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
+ *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
+ *          settings.cpp:10, default 1), cut_end_from / cut_start_to (read.hpp:324-343) and the book-keeping of struct Correction /
+ *          struct CorrectionErrors (read.hpp:36-117: simple_ok, simple_n0, simple_nM). The reference holds no corrector; the rules
+ *          below are this library's. 23-mer handles only (AIX_ERR_MODE otherwise).
+ *
+ * Read r is the bytes s[0 .. L) = buf[start[r] .. end[r]) (the convention of get_read(start, end) and .ridx); reads are pairwise
+ * disjoint. t = true_errors, V = verify (1 .. AIX_READFIX_MAX_VERIFY), F = max_fixes (0 .. AIX_READFIX_MAX_FIXES; 0 = profile and
+ * trim only, nothing is written to the reads); V or F out of range is AIX_ERR_ARG.
+ *   start > end or end > total_bytes: AIX_FIX_BAD_RANGE; L < 23: AIX_FIX_SHORT; L > AIX_READFIX_MAX_LEN: AIX_FIX_TOO_LONG. Such a
+ *   read is left untouched and its other record words are 0. Nothing outside [0, total_bytes) is read whatever the arrays hold.
+ *   Otherwise W = L - 22 windows; valid(i): the 23 bytes of window i are upper-case A/C/G/T; fm(i) = valid(i) ? get_freq(code of
+ *   window i) : 0 (hash.hpp:123-140: forward strand, then the reverse complement; an invalid window is not probed);
+ *   solid(i) = fm(i) > t, weak = !solid (read.hpp:296). weak_before = weak windows of the read as given.
+ *   try(p, lo, hi), lo .. hi all containing p and hi - lo + 1 <= V: if s[p] is no ASCII letter there is no candidate (a separator is
+ *   never written); else base b of A, C, G, T is a candidate iff every window lo .. hi of the read with s[p] := b is solid. Exactly
+ *   one candidate: s[p] := b, log (p, old byte), fixes += 1 (simple_ok). None: n0 += 1 (simple_n0). Several: nM += 1 (simple_nM).
+ *   Phase R: c = 1; while fixes < F: i = the smallest i >= c, i < W with solid(i - 1) && weak(i), none = stop; p = i + 22;
+ *            try(p, i, min(i + V - 1, W - 1)); after a fix c stays, after a failure c = i + 1.
+ *   Phase L: c = W - 2; while fixes < F: i = the largest i <= c, i >= 0 with weak(i) && solid(i + 1), none = stop; p = i;
+ *            try(p, max(i - V + 1, 0), i); after a fix c stays, after a failure c = i - 1.
+ *   solid() is always that of the read as fixed so far. Then weak_after = weak windows of the final read, and the longest run of
+ *   solid windows [a, a + n), the earliest on ties, gives trim_start = a, trim_len = n + 22 in bases (what cut_start_to(a - 1) and
+ *   cut_end_from(a + n + 22) keep, read.hpp:324-343); both 0 without a solid window.
+ *   status: CLEAN weak_before == 0; FIXED weak_before > 0 && weak_after == 0; PARTIAL fixes > 0 && weak_after > 0; UNFIXED
+ *   fixes == 0 && weak_after > 0.
+ * Log rows of stride F: fix_pos[r * F + j], fix_old[r * F + j] (the byte that was there) for j < fixes in order of application;
+ * nothing is written at or beyond `fixes` in a row, and nothing is written to buf except the fixed bytes.
+ * Known limits: two errors closer than V + 22 can defeat both rules (n0); tf is not updated after a fix; indels, quality strings
+ * and the 13-mer mode are out of scope.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_READFIX_MAX_LEN    4096u  /* longest read: the solid bitmap is 64 lanes x 64 windows, the bytes sit in 4 KiB of LDS */
+#define AIX_READFIX_MAX_VERIFY 16u
+#define AIX_READFIX_MAX_FIXES  16u
+#define AIX_FIX_CLEAN     0
+#define AIX_FIX_FIXED     1
+#define AIX_FIX_PARTIAL   2
+#define AIX_FIX_UNFIXED   3
+#define AIX_FIX_SHORT     4
+#define AIX_FIX_TOO_LONG  5
+#define AIX_FIX_BAD_RANGE 6
+/* one 32-byte record per read: the profile of set_fm (read.hpp:286-307), the counters of CorrectionErrors (read.hpp:36-117),
+ * the span of cut_start_to / cut_end_from (read.hpp:324-343) */
+typedef struct {
+    uint32_t status, weak_before, weak_after, fixes, n0, nM, trim_start, trim_len;
+} aix_readfix_t;
+/* set_fm + cuts + Correction log (read.hpp:286-307, :324-343, :36-117) for M reads of a device buffer, fixed in place, asynchronous
+ * on `stream`. M = 0 is AIX_OK; an empty index is AIX_ERR_UNSUPPORTED; a NULL pointer where one is needed is AIX_ERR_ARG. The
+ * caller guarantees that the ranges are pairwise disjoint. */
+int aix_reads_fix_dev(aix_index_t* h, char* d_buf, uint64_t total_bytes, const uint64_t* d_start, const uint64_t* d_end, uint64_t M,
+                      uint32_t true_errors, uint32_t verify, uint32_t max_fixes, aix_readfix_t* d_rec,
+                      uint32_t* d_fix_pos /* NULL iff max_fixes == 0 */, uint8_t* d_fix_old /* NULL iff max_fixes == 0 */, void* stream);
+/* host twin (read.hpp:286-307, :324-343, :36-117): buf is fixed in place. Ranges that are not ascending and disjoint
+ * (end[i] <= start[i + 1]) are refused with AIX_ERR_ARG. The caller's log rows are uploaded before the kernel runs, so that what
+ * lies at or beyond `fixes` in a row comes back as it was. */
+int aix_reads_fix(aix_index_t* h, char* buf, uint64_t total_bytes, const uint64_t* start, const uint64_t* end, uint64_t M,
+                  uint32_t true_errors, uint32_t verify, uint32_t max_fixes, aix_readfix_t* rec, uint32_t* fix_pos /* NULL iff max_fixes == 0 */,
+                  uint8_t* fix_old /* NULL iff max_fixes == 0 */);
+
+/* ------------------------------------------------------------------------------------------
  * Sequences against the indexed reads: seed hits with strand, and votes per (read, strand, diagonal).
  * replaces, M sequences at a time, the loop a caller of the reference writes over the 23-windows of a sequence:
  *          AindexWrapper::get_positions per window (python_wrapper.cpp:800-831), get_rid / get_start per occurrence (:757-789) and
