@@ -35,6 +35,7 @@ SPECTRUM_STATS = 8                                                 # AIX_SPECTRU
 STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", "max_wide", "sum_wide")
 FIX_NAMES = ("clean", "fixed", "partial", "unfixed", "short", "too_long", "bad_range")   # AIX_FIX_*
 READFIX_MAX_LEN, READFIX_MAX_VERIFY, READFIX_MAX_FIXES = 4096, 16, 16
+SEQFIND_TRIP_BYTES = 64                                            # AIX_SEQFIND_TRIP_BYTES of csrc/aix_seqhits.hpp: pattern bytes per verification trip
 # aix_readfix_t: one 32-byte record per read
 READFIX_FIELDS = [(f, "<u4") for f in ("status", "weak_before", "weak_after", "fixes", "n0", "nM", "trim_start", "trim_len")]
 
@@ -165,6 +166,10 @@ SIGNATURES = {
     "aix_seq_hits_dev": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_seq_votes": (i32, [vp, vp, vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "aix_seq_votes_dev": (i32, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_seq_find": (i32, [vp, vp, vp, u64, u32, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "aix_seq_find_dev": (i32, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_kmer_strands": (i32, [vp, vp, u64, u64, vp, vp, vp]),
+    "aix_kmer_strands_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, vp]),
     "aix_values_narrow_dev": (i32, [vp, u64, vp, vp]),
     "aix_spectrum_dev": (i32, [vp, i32, u64, u64, vp, vp, vp]),
     "aix_select_dev": (i32, [vp, u64, u32, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]),

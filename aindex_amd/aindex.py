@@ -42,6 +42,41 @@ def get_revcomp(sequence: str) -> str:
     return "".join(c.get(x, x) for x in reversed(sequence))
 
 
+def iter_reads_by_kmer(kmer: str, aindex: "AIndex", k: int = 23):
+    """API_DOCUMENTATION.md:238-243 — yields (rid, pos, read, poses) per read that holds an indexed occurrence of the k-mer, rid ascending;
+    poses = the offsets of the k-mer inside the read, ascending, pos = poses[0]. get_rid2poses_batch + get_reads_by_rid_batch: two GPU calls."""
+    hits = aindex.get_rid2poses_batch([kmer[:k]])[0]
+    rids = sorted(hits)
+    for rid, read in zip(rids, aindex.get_reads_by_rid_batch(rids)):
+        poses = sorted(hits[rid])
+        yield rid, poses[0], read, poses
+
+
+def iter_reads_by_sequence(sequence: str, aindex: "AIndex", hd: Optional[int] = None, k: int = 23):
+    """API_DOCUMENTATION.md:245-246, 371-378 — yields per read that holds the sequence, rid ascending, (rid, pos, read, poses) when hd is
+    falsy (exact matches, N positions forgiven) and (rid, pos, read, poses, distance) otherwise (at most hd mismatches): poses = where
+    the sequence starts in the read, either strand, ascending and distinct; pos = poses[0]; distance = the smallest of the read's
+    alignments. k must be 23, the seed length of AIndex.find_sequences_array."""
+    if k != 23:
+        raise ValueError("iter_reads_by_sequence seeds with 23-mers: k must be 23")
+    _, _, rid, local, _, dist = aindex.find_sequences_array([sequence], hd or 0)
+    per = {}
+    for r, l, d in zip(rid.tolist(), local.tolist(), dist.tolist()):
+        e = per.setdefault(r, [set(), d])
+        e[0].add(l)
+        e[1] = min(e[1], d)
+    rids = sorted(per)
+    for r, read in zip(rids, aindex.get_reads_by_rid_batch(rids)):
+        poses = sorted(per[r][0])
+        yield (r, poses[0], read, poses, per[r][1]) if hd else (r, poses[0], read, poses)
+
+
+def get_srandness(kmer: str, aindex: "AIndex", k: int = 23) -> Tuple[int, int, int]:
+    """API_DOCUMENTATION.md:234-236, 379-381 — (plus, minus, total) of the k-mer's indexed occurrences: the reads hold it as given,
+    hold its reverse complement, all listed occurrences. (The reference's spelling of the name.)"""
+    return aindex.get_strandness_batch([kmer[:k]])[0]
+
+
 class AIndex:
     def __init__(self, device: int = 0):
         self._wrapper = AindexWrapper(device)
@@ -362,6 +397,26 @@ class AIndex:
     def map_sequences(self, seqs, min_votes: int = 2, max_per_kmer: int = 0) -> List[List[tuple]]:
         """Per sequence [(rid, strand, diag, votes, q_first, q_last)], one GPU call; see AindexWrapper.map_sequences."""
         return self._wrapper.map_sequences(seqs, min_votes, max_per_kmer)
+
+    def find_sequences_array(self, seqs, hd: int = 0, seed_step: int = 23, max_per_kmer: int = 0):
+        """CSR arrays (find_offsets, pos, rid, local, strand, dist) of the alignments of every sequence to the indexed reads with at most
+        hd mismatches, either strand, one GPU call; see AindexWrapper.find_sequences_array and include/aindex_hip.h for the rules."""
+        return self._wrapper.find_sequences_array(seqs, hd, seed_step, max_per_kmer)
+
+    def find_reads_by_sequence_batch(self, seqs, hd: int = 0) -> List[List[tuple]]:
+        """Per sequence [(rid, local, read, strand, dist)] ascending by (position in the reads file, strand): the reads that hold it with
+        at most hd mismatches (hamming_distance), local = where it starts in the read, strand 1 = the read holds its reverse complement.
+        Two GPU calls: the search, and the reads of every distinct rid."""
+        off, _, rid, local, strand, dist = self.find_sequences_array(seqs, hd)
+        uniq, inv = np.unique(rid, return_inverse=True)
+        reads = self.get_reads_by_rid_batch(uniq)
+        recs = [(r, l, reads[j], s, d) for r, l, j, s, d in zip(rid.tolist(), local.tolist(), inv.tolist(), strand.tolist(), dist.tolist())]
+        off = off.tolist()
+        return [recs[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def get_strandness_batch(self, kmers) -> List[tuple]:
+        """[(plus, minus, total)] per 23-mer, one GPU call; see AindexWrapper.get_strandness_batch."""
+        return self._wrapper.get_strandness_batch(kmers)
 
     def get_next_batch(self, kmers, cutoff: int = 0) -> List[dict]:
         """The four successors of every 23-mer with their tf (DEBRUJIN::print_next), one GPU call; see AindexWrapper.get_next_batch."""

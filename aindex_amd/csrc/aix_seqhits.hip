@@ -4,7 +4,8 @@
 //   AindexWrapper::get_read              python_wrapper.cpp:677-698   23 bytes per occurrence, to tell the strand (a bucket of the positions
 //                                                                     index holds both orientations of its k-mer without a strand bit)
 // The composition a user of the reference writes as a Python loop over the windows of a sequence, for M sequences at once. The chain:
-//   1 k_sh_windows   one lane per sequence: its windows max(0, L - 22); a scan gives woff[M + 1], the FLAT window space of W windows
+//   1 k_sh_windows   one lane per sequence: its windows max(0, L - 22) (every `step`-th of them when aix_seqfind.hip asks: offsets 0, step, ..);
+//                    a scan gives woff[M + 1], the FLAT window space of W windows
 //   2 k_sh_resolve*  one lane per window: the 23 raw bytes at their place in the sequence -> bucket -> (source start, upper bound) through
 //                    pq_resolve23_words, the body of k_pq_resolve23 (no N x 23 copy of the windows exists anywhere)
 //   3 posquery_lists steps 2 to 5 of aix_posquery.hip, unchanged: W lists -> koff[W + 1] and the positions, windows in sequence order,
@@ -19,28 +20,14 @@
 //            The sorts are stable and the hits of a sequence are in window order, so the first and last hit of a run carry q_first / q_last.
 // Every size, offset and flat index is 64 bits wide; byte counts are checked for overflow before anything is allocated. No atomics; all
 // stores are plain vector stores. Nothing depends on the launch geometry.
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-
-#include <rocprim/rocprim.hpp>
-
-#include "aix_posquery.hpp"
+#include "aix_seqhits.hpp"
 
 namespace aix {
-
-static constexpr int kSB = 256;
-static inline unsigned sh_grid(uint64_t work) {
-    uint64_t b = (work + kSB - 1) / kSB;
-    if (b > 8192) b = std::max<uint64_t>(8192, std::min<uint64_t>(b / 4, 65536));
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
 
 // ---------------------------------------------------------------------------------------------
 // 1 / 2. sequences -> windows -> lists
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kSB) k_sh_windows(const uint64_t* __restrict__ offs, uint64_t M, uint64_t* __restrict__ nwin, uint32_t* __restrict__ flag) {
+__global__ void __launch_bounds__(kSB) k_sh_windows(const uint64_t* __restrict__ offs, uint64_t M, uint64_t step, uint64_t* __restrict__ nwin, uint32_t* __restrict__ flag) {
     const uint64_t stride = (uint64_t)gridDim.x * kSB;
     bool bad = false;
     for (uint64_t i = (uint64_t)blockIdx.x * kSB + threadIdx.x; i <= M; i += stride) {
@@ -48,7 +35,7 @@ __global__ void __launch_bounds__(kSB) k_sh_windows(const uint64_t* __restrict__
         if (i < M) {
             const uint64_t a = offs[i], b = offs[i + 1];
             bad |= b < a || b - a >= (1ull << 32);                // query offsets are u32
-            if (b >= a && b - a >= 23) w = b - a - 22;
+            if (b >= a && b - a >= 23) w = (b - a - 23) / step + 1;                // windows at offsets 0, step, 2 step, .. <= L - 23
         }
         nwin[i] = w;                                              // nwin[M] = 0: the scan's last entry is the total
     }
@@ -73,7 +60,7 @@ __device__ __forceinline__ uint64_t sh_last_le(const uint64_t* __restrict__ a, u
 
 template <int LPP>
 __global__ void __launch_bounds__(kSB) k_sh_resolve(const IndexDev ix, const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ offs,
-                                                   const uint64_t* __restrict__ woff, uint64_t M, uint64_t W, const uint64_t* __restrict__ indices,
+                                                   const uint64_t* __restrict__ woff, uint64_t M, uint64_t W, uint64_t step, const uint64_t* __restrict__ indices,
                                                    uint64_t total, uint64_t* __restrict__ wseq, uint64_t* __restrict__ wsrc, uint64_t* __restrict__ lo_out,
                                                    uint64_t* __restrict__ ub_out) {
     const uint64_t stride = (uint64_t)gridDim.x * kSB;
@@ -84,7 +71,7 @@ __global__ void __launch_bounds__(kSB) k_sh_resolve(const IndexDev ix, const uin
         uint64_t w0 = 0, w1 = 0, w2 = 0, sq = 0, src = 0;
         if (in) {
             sq = sh_last_le(woff, M, s0, i);                                 // woff[M] == W > i; a sequence without windows is never the last one <= i
-            src = offs[sq] + (i - woff[sq]);
+            src = offs[sq] + (i - woff[sq]) * step;
             load23(seqs + src, w0, w1, w2);
         }
         uint64_t lo, ub;
@@ -105,7 +92,7 @@ struct ShHits {
     const uint8_t* seqs;
     const uint64_t *woff, *koff, *wseq, *wsrc;     // [M + 1], [W + 1], [W], [W]
     const uint64_t* pos;                           // [T]
-    uint64_t M, W, T;
+    uint64_t M, W, T, step;
     const uint8_t* reads;
     uint64_t reads_len;
     const uint64_t *rs, *re, *rr;                  // interval starts / ends / rids
@@ -133,6 +120,8 @@ __device__ __forceinline__ bool sh_read23(const uint8_t* __restrict__ rd, uint64
     return true;
 }
 
+// kLocate false (aix_seqfind.hip, which has an interval rule of its own): no interval search, rid / local not written, flag = the strand alone
+template <bool kLocate>
 __global__ void __launch_bounds__(kSB) k_sh_hits(const ShHits P) {
     const uint64_t stride = (uint64_t)gridDim.x * kSB;
     for (uint64_t base = (uint64_t)blockIdx.x * kSB + (threadIdx.x & ~63u); base < P.T; base += stride) {    // wave-uniform
@@ -140,7 +129,7 @@ __global__ void __launch_bounds__(kSB) k_sh_hits(const ShHits P) {
         const uint64_t wv = wave_count_le(P.koff, P.W + 1, base) - 1;        // koff[0] == 0
         if (e >= P.T) continue;
         const uint64_t w = sh_last_le(P.koff, P.W, wv, e);                   // koff[W] == T > e; a window without hits is never the last one <= e
-        const uint64_t sq = P.wseq[w], q = w - P.woff[sq], p = P.pos[e];
+        const uint64_t sq = P.wseq[w], q = (w - P.woff[sq]) * P.step, p = P.pos[e];
         uint64_t w0, w1, w2, r0, r1, r2, t0, t1, t2;
         load23(P.seqs + P.wsrc[w], w0, w1, w2);
         ascii23_of_rc(encode23_words(w0, w1, w2).code, r0, r1, r2);          // decode(reverseDNA(sanitised code))
@@ -149,10 +138,14 @@ __global__ void __launch_bounds__(kSB) k_sh_hits(const ShHits P) {
             if (t0 == w0 && t1 == w1 && t2 == w2) strand = 0;
             else if (t0 == r0 && t1 == r1 && t2 == r2) strand = 1;
         }
+        P.qoff[e] = (uint32_t)q;
+        if constexpr (!kLocate) {
+            P.flag[e] = (uint8_t)strand;
+            continue;
+        }
         uint64_t rd, sv;
         const bool found = pq_locate(P.rs, P.re, P.rr, P.rn, p, rd, sv);
         const int64_t local = (int64_t)(p - sv);
-        P.qoff[e] = (uint32_t)q;
         P.rid[e] = rd;
         P.local[e] = local;
         P.flag[e] = (uint8_t)(strand | (found ? 4u : 0u));
@@ -170,44 +163,11 @@ __global__ void __launch_bounds__(kSB) k_sh_seqoff(const uint64_t* __restrict__ 
     for (uint64_t i = (uint64_t)blockIdx.x * kSB + threadIdx.x; i <= M; i += stride) out[i] = koff[woff[i]];
 }
 
-// out[i] = in[0] + .. + in[i - 1] over n entries, u64 sums; `tmp` stays allocated until the caller has synchronised the stream
-template <class It>
-static hipError_t sh_scan(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    return e;
-}
-
-// n entries of `elem` bytes from the pool; hipErrorOutOfMemory when the byte count does not fit 64 bits
-static hipError_t sh_alloc(DevArr& a, uint64_t n, uint64_t elem) {
-    uint64_t bytes = 0;
-    if (__builtin_mul_overflow(n, elem, &bytes) || bytes >= (1ull << 62)) return hipErrorOutOfMemory;
-    return a.alloc(bytes);
-}
-
-// what the hits of a call live in: the user's buffers (aix_seq_hits_dev) or pool blocks (everything else)
-struct ShBufs {
-    DevArr woff, koff, pos, qoff, rid, local, flag, hseq, diag;
-    uint64_t W = 0, T = 0;
-    explicit ShBufs(hipStream_t s) : woff(s), koff(s), pos(s), qoff(s), rid(s), local(s), flag(s), hseq(s), diag(s) {}
-};
-
-struct ShUser {                    // aix_seq_hits_dev: where the entries go when they fit `cap`
-    uint32_t* qoff;
-    uint64_t* pos;
-    uint64_t* rid;
-    int64_t* local;
-    uint8_t* flag;
-    uint64_t cap;
-};
-
-// Steps 1 to 4. B.woff and (W != 0) B.koff are always produced and d_seq_offsets (M + 1, nullable) filled; the hits go to `user` when
-// they fit its cap, or — user == nullptr — to pool blocks of B; votes: hseq / diag as well. *bad: a sequence of 2^32 bytes or more,
+// Steps 1 to 4 (declared in aix_seqhits.hpp; aix_seqfind.hip runs them with a window stride). B.woff and (W != 0) B.koff are always produced and d_seq_offsets (M + 1, nullable) filled; the hits go to `user` when
+// they fit its cap, or — user == nullptr — to pool blocks of B; votes: hseq / diag as well; locate false (pool blocks, no votes): without rid / local and the located bit of the flag. *bad: a sequence of 2^32 bytes or more,
 // descending offsets, or windows without a byte buffer (nothing else is produced then). Synchronises `s`.
-static hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t m, uint64_t* d_seq_offsets, const ShUser* user, bool votes,
-                         ShBufs& B, bool* bad, hipStream_t s) {
+hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t m, uint64_t* d_seq_offsets, const ShUser* user, bool votes, ShBufs& B,
+                  bool* bad, hipStream_t s, uint64_t step, bool locate) {
     *bad = false;
     B.W = B.T = 0;
     DevArr nwin(s), fl(s), tmp(s), lo(s), ub(s), wseq(s), wsrc(s);
@@ -216,7 +176,7 @@ static hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     if (e == hipSuccess) e = fl.alloc(4);
     if (e == hipSuccess) e = hipMemsetAsync(fl.p, 0, 4, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sh_windows, dim3(sh_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, (uint64_t*)nwin.p, (uint32_t*)fl.p);
+    hipLaunchKernelGGL(k_sh_windows, dim3(sh_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, step, (uint64_t*)nwin.p, (uint32_t*)fl.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = sh_scan((const uint64_t*)nwin.p, (uint64_t*)B.woff.p, M + 1, tmp, s);
     uint64_t W = 0;
@@ -242,7 +202,7 @@ static hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     const IndexDev ix = h->dev();
     const uint64_t* woff = (const uint64_t*)B.woff.p;
 #define AIX_SH_RESOLVE(L)                                                                                                                                  \
-    hipLaunchKernelGGL(k_sh_resolve<L>, dim3(sh_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
+    hipLaunchKernelGGL(k_sh_resolve<L>, dim3(sh_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
                        (uint64_t*)wsrc.p, (uint64_t*)lo.p, (uint64_t*)ub.p)
     if (ix.bk_lpp == 2) AIX_SH_RESOLVE(2);
     else if (ix.bk_lpp == 4) AIX_SH_RESOLVE(4);
@@ -262,15 +222,15 @@ static hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     if (e == hipSuccess && T && (!user || (T <= user->cap && user->pos))) {
         ShHits P{};
         P.seqs = d_seqs; P.woff = woff; P.koff = (const uint64_t*)B.koff.p; P.wseq = (const uint64_t*)wseq.p; P.wsrc = (const uint64_t*)wsrc.p;
-        P.M = M; P.W = W; P.T = T;
+        P.M = M; P.W = W; P.T = T; P.step = step;
         P.reads = h->rd; P.reads_len = h->rd_len;
         P.rs = h->rx; P.re = h->rx + h->rx_n; P.rr = h->rx + 2 * h->rx_n; P.rn = h->rx_n;
         if (user) {
             P.pos = user->pos; P.qoff = user->qoff; P.rid = user->rid; P.local = user->local; P.flag = user->flag;
         } else {
             e = sh_alloc(B.qoff, T, 4);
-            if (e == hipSuccess) e = sh_alloc(B.rid, T, 8);
-            if (e == hipSuccess) e = sh_alloc(B.local, T, 8);
+            if (e == hipSuccess && locate) e = sh_alloc(B.rid, T, 8);
+            if (e == hipSuccess && locate) e = sh_alloc(B.local, T, 8);
             if (e == hipSuccess) e = sh_alloc(B.flag, T, 1);
             if (e == hipSuccess && votes) e = sh_alloc(B.hseq, T, 8);
             if (e == hipSuccess && votes) e = sh_alloc(B.diag, T, 8);
@@ -278,7 +238,8 @@ static hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
             P.pos = (const uint64_t*)B.pos.p; P.qoff = (uint32_t*)B.qoff.p; P.rid = (uint64_t*)B.rid.p; P.local = (int64_t*)B.local.p; P.flag = (uint8_t*)B.flag.p;
             P.hseq = (uint64_t*)B.hseq.p; P.diag = (int64_t*)B.diag.p;
         }
-        hipLaunchKernelGGL(k_sh_hits, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
+        if (locate) hipLaunchKernelGGL(k_sh_hits<true>, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
+        else hipLaunchKernelGGL(k_sh_hits<false>, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);          // the scratch blocks go back to the pool idle
@@ -312,14 +273,6 @@ struct SvDiagKey {                 // diagonal - smallest diagonal: ascending as
     __host__ __device__ uint64_t operator()(int64_t d) const { return (uint64_t)d - (uint64_t)dlo; }
 };
 struct SvStrandOf { __host__ __device__ uint8_t operator()(uint8_t f) const { return (uint8_t)(f & 3u); } };
-struct SvWiden8 { __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)v; } };
-
-template <class T, class Map>
-__global__ void __launch_bounds__(kSB) k_sv_gather(const T* __restrict__ in, const uint64_t* __restrict__ perm, uint64_t n, Map map, T* __restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kSB;
-    for (uint64_t i = (uint64_t)blockIdx.x * kSB + threadIdx.x; i < n; i += stride) out[i] = map(in[perm[i]]);
-}
-struct SvSame { template <class T> __host__ __device__ T operator()(T v) const { return v; } };
 
 // head[i] = sorted entry i is a kept hit and the first of its (sequence, read, strand, diagonal) run; head[T] = 0
 __global__ void __launch_bounds__(kSB) k_sv_heads(const uint64_t* __restrict__ perm, const uint64_t* __restrict__ sseq, const uint64_t* __restrict__ rid,
@@ -388,19 +341,6 @@ __global__ void __launch_bounds__(kSB) k_sv_write(const uint64_t* __restrict__ g
         O.qfirst[o] = qoff[a];                                 // stable sorts over hits in window order: the run is ascending in qoff
         O.qlast[o] = qoff[b];
     }
-}
-
-static unsigned sv_bits(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) ++b; return b; }
-
-// one stable pass of the permutation: keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary storage is as large as
-// the keys and values together: the four passes share ONE block (tmp.alloc waits for the pass before it, then takes the block back from the pool)
-template <class KeyIt, class Key, class ValIt>
-static hipError_t sv_sort(KeyIt keys, Key* keys_out, ValIt perm_in, uint64_t* perm_out, uint64_t T, unsigned bits, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
-    return e;
 }
 
 // d_vote_offsets (M + 1) and *total_out always; the records only when *total_out <= cap
@@ -501,23 +441,6 @@ static hipError_t sv_run(const ShBufs& B, uint64_t M, uint64_t min_votes, uint64
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define SHCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
-static int sh_check(const aix_index* h) {
-    if (h->k != 23) return AIX_ERR_MODE;
-    if (!h->ai_attached || !h->rx_attached || !h->rd_attached) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
-    if (h->n == 0) return AIX_ERR_UNSUPPORTED;
-    return AIX_OK;
-}
-
 extern "C" int aix_seq_hits_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t max_per_kmer, uint64_t* d_seq_offsets,
                                 uint32_t* d_qoff, uint64_t* d_pos, uint64_t* d_rid, int64_t* d_local, uint8_t* d_flag, uint64_t cap, uint64_t* total_out, void* stream) {
     if (!h || !d_seq_offsets || !total_out || (M && !d_offs) || M >= (1ull << 56)) return AIX_ERR_ARG;
@@ -553,29 +476,6 @@ extern "C" int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint6
     B.pos.drop(); B.local.drop();                              // the diagonal holds what the grouping needs of them: the sorts take these blocks
     const SvOut O{cap ? d_rid : nullptr, d_strand, d_diag, d_votes, d_qfirst, d_qlast};
     SHCHK(sv_run(B, M, min_votes, d_vote_offsets, O, cap, total_out, s));
-    return AIX_OK;
-}
-
-// device buffer -> malloc'd host copy (aix_free)
-static int sh_to_host(const void* d, uint64_t bytes, void** out) {
-    void* p = malloc(bytes ? bytes : 1);
-    if (!p) return AIX_ERR_NOMEM;
-    if (bytes) {
-        const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(p); SHCHK(e); }
-    }
-    *out = p;
-    return AIX_OK;
-}
-
-// the sequences of a host call in HBM: bytes (padded for load23) and offsets
-static int sh_upload(const char* seqs, const uint64_t* offs, uint64_t M, DevBuf& ds, DevBuf& dof) {
-    const uint64_t bytes = M ? offs[M] : 0;
-    if (bytes >= (1ull << 60)) return AIX_ERR_NOMEM;
-    SHCHK(ds.alloc(bytes + 16));
-    SHCHK(dof.alloc(8 * (M + 1)));
-    if (bytes) SHCHK(hipMemcpy(ds.p, seqs, bytes, hipMemcpyHostToDevice));
-    SHCHK(hipMemcpy(dof.p, offs, 8 * (M + 1), hipMemcpyHostToDevice));
     return AIX_OK;
 }
 

@@ -1,0 +1,128 @@
+// aix_seqhits.hpp — what more than one translation unit uses of the chain sequences -> windows -> seed hits (aix_seqhits.hip: hits and
+// diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts): the hit buffers, steps 1 to 4 with a window stride, the
+// stable rocPRIM passes over a permutation, and the host ends of the C ABI.
+#pragma once
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "aix_posquery.hpp"
+
+// bytes of a pattern that one trip of the verification loop of aix_seqfind.hip compares (16 lanes x one dword). Not part of the C ABI:
+// _lib.SEQFIND_TRIP_BYTES repeats it for the tests that place pattern lengths around its multiples.
+#define AIX_SEQFIND_TRIP_BYTES 64u
+
+namespace aix {
+
+static constexpr int kSB = 256;
+static inline unsigned sh_grid(uint64_t work) {
+    uint64_t b = (work + kSB - 1) / kSB;
+    if (b > 8192) b = std::max<uint64_t>(8192, std::min<uint64_t>(b / 4, 65536));
+    if (b == 0) b = 1;
+    return (unsigned)b;
+}
+
+// out[i] = in[0] + .. + in[i - 1] over n entries, u64 sums; `tmp` stays allocated until the caller has synchronised the stream
+template <class It>
+static hipError_t sh_scan(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+    return e;
+}
+
+// n entries of `elem` bytes from the pool; hipErrorOutOfMemory when the byte count does not fit 64 bits
+static hipError_t sh_alloc(DevArr& a, uint64_t n, uint64_t elem) {
+    uint64_t bytes = 0;
+    if (__builtin_mul_overflow(n, elem, &bytes) || bytes >= (1ull << 62)) return hipErrorOutOfMemory;
+    return a.alloc(bytes);
+}
+
+// what the hits of a call live in: the user's buffers (aix_seq_hits_dev) or pool blocks (everything else)
+struct ShBufs {
+    DevArr woff, koff, pos, qoff, rid, local, flag, hseq, diag;
+    uint64_t W = 0, T = 0;
+    explicit ShBufs(hipStream_t s) : woff(s), koff(s), pos(s), qoff(s), rid(s), local(s), flag(s), hseq(s), diag(s) {}
+};
+
+struct ShUser {                    // aix_seq_hits_dev: where the entries go when they fit `cap`
+    uint32_t* qoff;
+    uint64_t* pos;
+    uint64_t* rid;
+    int64_t* local;
+    uint8_t* flag;
+    uint64_t cap;
+};
+
+// Steps 1 to 4 of aix_seqhits.hip for M sequences: the windows at offsets 0, step, 2 step, .. <= L - 23 of every sequence (step 1: all of
+// them, what aix_seq_hits* and aix_seq_votes* ask for), their lists, and the hits with strand and interval; qoff is the window's offset.
+// locate false (user == nullptr, votes false): the interval search is left out, B.rid / B.local stay empty and the flag holds the strand alone.
+hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t m, uint64_t* d_seq_offsets, const ShUser* user, bool votes, ShBufs& B,
+                  bool* bad, hipStream_t s, uint64_t step = 1, bool locate = true);
+
+struct SvWiden8 { __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)v; } };
+
+template <class T, class Map>
+__global__ void __launch_bounds__(kSB) k_sv_gather(const T* __restrict__ in, const uint64_t* __restrict__ perm, uint64_t n, Map map, T* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kSB;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSB + threadIdx.x; i < n; i += stride) out[i] = map(in[perm[i]]);
+}
+struct SvSame { template <class T> __host__ __device__ T operator()(T v) const { return v; } };
+
+static unsigned sv_bits(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) ++b; return b; }
+
+// one stable pass of the permutation: keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary storage is as large as
+// the keys and values together: the four passes share ONE block (tmp.alloc waits for the pass before it, then takes the block back from the pool)
+template <class KeyIt, class Key, class ValIt>
+static hipError_t sv_sort(KeyIt keys, Key* keys_out, ValIt perm_in, uint64_t* perm_out, uint64_t T, unsigned bits, DevArr& tmp, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
+    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
+    return e;
+}
+
+}  // namespace aix
+
+#define SHCHK(expr)                                                                              \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
+        if (_e != hipSuccess) {                                                                  \
+            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
+            return AIX_ERR_HIP;                                                                  \
+        }                                                                                        \
+    } while (0)
+
+static int sh_check(const aix_index* h) {
+    if (h->k != 23) return AIX_ERR_MODE;
+    if (!h->ai_attached || !h->rx_attached || !h->rd_attached) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
+    if (h->n == 0) return AIX_ERR_UNSUPPORTED;
+    return AIX_OK;
+}
+
+// device buffer -> malloc'd host copy (aix_free)
+static int sh_to_host(const void* d, uint64_t bytes, void** out) {
+    void* p = malloc(bytes ? bytes : 1);
+    if (!p) return AIX_ERR_NOMEM;
+    if (bytes) {
+        const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(p); SHCHK(e); }
+    }
+    *out = p;
+    return AIX_OK;
+}
+
+// the sequences of a host call in HBM: bytes (padded for load23) and offsets
+static int sh_upload(const char* seqs, const uint64_t* offs, uint64_t M, DevBuf& ds, DevBuf& dof) {
+    const uint64_t bytes = M ? offs[M] : 0;
+    if (bytes >= (1ull << 60)) return AIX_ERR_NOMEM;
+    SHCHK(ds.alloc(bytes + 16));
+    SHCHK(dof.alloc(8 * (M + 1)));
+    if (bytes) SHCHK(hipMemcpy(ds.p, seqs, bytes, hipMemcpyHostToDevice));
+    SHCHK(hipMemcpy(dof.p, offs, 8 * (M + 1), hipMemcpyHostToDevice));
+    return AIX_OK;
+}

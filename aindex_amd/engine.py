@@ -616,6 +616,52 @@ class Index:
                            lambda m, off, o, cap, tot: lib().aix_seq_votes_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, max_per_kmer, min_votes, off,
                                                                                *o, cap, tot, st))
 
+    # ---- sequences with mismatches, strand counts (aix_seqfind.hip) ----------------------------
+    def seq_find(self, seqs: Sequence, hd: int = 0, seed_step: int = 23, max_per_kmer: int = 0):
+        """Alignments of every sequence to the indexed reads with at most hd mismatches (hamming_distance: positions with an N on either
+        side are ignored), found from the seed hits of its 23-windows at offsets 0, seed_step, ..: (find_offsets u64[M + 1], pos u64, rid u64,
+        local u64, strand u8, dist u32). The records of sequence i are [find_offsets[i], find_offsets[i + 1]), ascending by (pos, strand);
+        pos is where the alignment starts in the reads file, local = pos - start of the read that contains it whole. Complete when
+        hd < len // 23 and seed_step is 1 or 23 (include/aindex_hip.h)."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(6)]
+        check(lib().aix_seq_find(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, hd, seed_step, max_per_kmer, *[C.byref(p) for p in ps]),
+              "aix_seq_find")
+        fo = self._take_as(ps[0], m + 1, np.uint64)
+        r = int(fo[m])
+        return (fo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint64), self._take_as(ps[3], r, np.uint64),
+                self._take_as(ps[4], r, np.uint8), self._take_as(ps[5], r, np.uint32))
+
+    def seq_find_t(self, seqs_t, offs_t, hd: int = 0, seed_step: int = 23, max_per_kmer: int = 0, cap_hint: int = 0):
+        """seq_find on device tensors (uint8 bytes, int64 offsets[M + 1] into them), on torch's current stream:
+        (find_offsets int64, pos int64, rid int64, local int64, strand uint8, dist int32) — bit patterns of the unsigned fields."""
+        import torch
+        st = _stream_ptr(self.device)
+        return self._seq_t("aix_seq_find_dev", seqs_t, offs_t, [torch.int64, torch.int64, torch.int64, torch.uint8, torch.int32], cap_hint,
+                           lambda m, off, o, cap, tot: lib().aix_seq_find_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, hd, seed_step, max_per_kmer, off,
+                                                                              *o, cap, tot, st))
+
+    def kmer_strands(self, kmers, max_per_kmer: int = 0):
+        """(plus, minus, total) uint64[N]: of the listed hits of every 23-mer (`kmers`: what tf_ascii takes), those where the reads hold it
+        as given, those where they hold its reverse complement, and all of them."""
+        a = _as_u8(kmers, 23)
+        n = a.shape[0] // 23
+        out = [np.zeros(n, np.uint64) for _ in range(3)]
+        check(lib().aix_kmer_strands(self._h, _np_ptr(a) if n else None, n, max_per_kmer, *[_np_ptr(o) if n else None for o in out]), "aix_kmer_strands")
+        return tuple(out)
+
+    def kmer_strands_t(self, kmers_t, max_per_kmer: int = 0):
+        """kmer_strands on a uint8 device tensor of N * 23 bytes: three int64 device tensors, on torch's current stream."""
+        import torch
+        self._chk_dev(kmers_t)
+        n = kmers_t.numel() // 23
+        out = [torch.zeros(n, dtype=torch.int64, device=kmers_t.device) for _ in range(3)]
+        with torch.cuda.device(kmers_t.device):
+            check(lib().aix_kmer_strands_dev(self._h, vp(kmers_t.data_ptr()) if n else None, n, max_per_kmer, *[vp(o.data_ptr()) if n else None for o in out],
+                                             _stream_ptr(self.device)), "aix_kmer_strands_dev")
+        return tuple(out)
+
     # ---- De Bruijn neighbours and walks (aix_debruijn.hip) -------------------------------------
     @staticmethod
     def _dir(direction, both_ok: bool) -> int:

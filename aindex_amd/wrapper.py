@@ -945,6 +945,22 @@ class AindexWrapper:
         off = vo.tolist()
         return [recs[off[i]:off[i + 1]] for i in range(len(off) - 1)]
 
+    def find_sequences_array(self, seqs, hd: int = 0, seed_step: int = 23, max_per_kmer: int = 0):
+        """Where every sequence (str or bytes) lies in the indexed reads with at most hd mismatches, either strand, in one GPU call: CSR
+        arrays (find_offsets uint64[M + 1], pos uint64, rid uint64, local uint64, strand uint8, dist uint32); see Index.seq_find."""
+        return self._attach_for_mapping().seq_find(list(seqs), hd, seed_step, max_per_kmer)
+
+    def get_strandness_batch(self, kmers, max_per_kmer: int = 0) -> List[tuple]:
+        """[(plus, minus, total)] per 23-mer in one GPU call: its listed occurrences where the reads hold it as given, where they hold its
+        reverse complement, and all of them (Index.kmer_strands). Items of another length give (0, 0, 0) in place."""
+        flat, keep = self._split_fixed(kmers, 23)
+        out = [(0, 0, 0)] * len(kmers)
+        if keep.shape[0]:
+            plus, minus, total = self._attach_for_mapping().kmer_strands(flat, max_per_kmer)
+            for i, rec in zip(keep.tolist(), zip(plus.tolist(), minus.tolist(), total.tolist())):
+                out[i] = rec
+        return out
+
     # ---- De Bruijn neighbours and extensions (one GPU call per batch) ---------------------------------------------------
     @staticmethod
     def _place_conts(n_items: int, keep: np.ndarray, recs: np.ndarray) -> list:

@@ -630,6 +630,53 @@ int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs
                       uint32_t* d_qlast, uint64_t cap, uint64_t* total_out, void* stream);   /* python_wrapper.cpp:800-831, 757-789 */
 
 /* ------------------------------------------------------------------------------------------
+ * Sequences with mismatches against the indexed reads (Hamming seeds), and strand counts of k-mers.
+ * replaces, M sequences at a time, the documented "Analysis Functions" iter_reads_by_sequence(seq, aindex, hd) and get_srandness(kmer,
+ *          aindex) (API_DOCUMENTATION.md:232-255, 371-382; the reference holds no code for them, so this header is the contract) over
+ *          hamming_distance (aindex.py:44-46): the loop a caller writes over aix_seq_hits, aix_reads_fetch and one comparison per candidate.
+ * Restrictions and input form are those of aix_seq_hits: 23-mer handles only (AIX_ERR_MODE); positions index, read intervals and reads
+ * attached (AIX_ERR_ARG otherwise); M sequences as seqs + offs[M + 1], each shorter than 2^32 bytes (AIX_ERR_ARG otherwise).
+ *   hd            the largest distance reported
+ *   seed_step     >= 1; 0 means 23
+ *   max_per_kmer  as in aix_seq_hits
+ * Seeds: the seeds of a sequence of length L >= 23 are its 23-windows at offsets q = 0, seed_step, 2 seed_step, .. <= L - 23; a shorter
+ *   sequence has no seeds and no results.
+ * Hits: the hits of a seed are exactly the aix_seq_hits hits of that window, cap included; only hits with strand 0 or 1 count.
+ * Proposed alignments: a hit (q, pos, strand) proposes the alignment that starts at absolute reads offset a = pos - q (strand 0) or
+ *   a = pos - (L - 23 - q) (strand 1). It is dropped when a < 0, when a + L exceeds the attached reads, or when no interval
+ *   (rid, start, end) has start <= a and a + L <= end: plain containment in [start, end), not the off-by-one rule of get_rid
+ *   (python_wrapper.cpp:757-789).
+ * Distance: x_j = reads[a + j]; y_j = seq[j] (strand 0) or comp(seq[L - 1 - j]) (strand 1), comp: A <-> T, C <-> G, a <-> t, c <-> g, every
+ *   other byte as it is. d = #{ j : x_j != y_j and x_j != 'N' and y_j != 'N' } on raw bytes: hamming_distance (aindex.py:44-46).
+ * Output: an alignment is reported when d <= hd, each (a, strand) of a sequence once however many seeds proposed it. CSR over sequences:
+ *   the records of sequence i are [find_offsets[i], find_offsets[i + 1]), ascending by (a, strand). Columns: pos = a, rid,
+ *   local = a - start, strand, dist = d. The answer is independent of launch geometry and of every probe switch. The reads are never read
+ *   at or beyond their attached length, whatever the positions array holds.
+ * Completeness: the answer equals the full Hamming search over the indexed reads whenever the seed set holds hd + 1 pairwise disjoint
+ *   windows that the positions index lists in full (max_per_kmer = 0, every occurrence indexed): one of them is free of mismatches. That is
+ *   the case when hd < floor(L / 23) and seed_step is 1 or 23. An alignment with an 'N' inside every such window can be missed: the N rule
+ *   forgives what the seed lookup does not.
+ * The _dev twin follows the sizing convention of aix_seq_hits_dev: find_offsets and *total_out always, records only when the total fits
+ * `cap`, never at or beyond it, AIX_OK either way; it returns after the work on `stream` has completed. Host outputs are malloc'd
+ * (aix_free); M = 0 gives find_offsets = {0}.
+ * ------------------------------------------------------------------------------------------ */
+int aix_seq_find(aix_index_t* h, const char* seqs, const uint64_t* offs, uint64_t M, uint32_t hd, uint64_t seed_step, uint64_t max_per_kmer,
+                 uint64_t** find_offsets_out, uint64_t** pos_out, uint64_t** rid_out, uint64_t** local_out, uint8_t** strand_out,
+                 uint32_t** dist_out);   /* API_DOCUMENTATION.md:232-255, 371-382; aindex.py:44-46 */
+int aix_seq_find_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint32_t hd, uint64_t seed_step,
+                     uint64_t max_per_kmer, uint64_t* d_find_offsets, uint64_t* d_pos, uint64_t* d_rid, uint64_t* d_local, uint8_t* d_strand,
+                     uint32_t* d_dist, uint64_t cap, uint64_t* total_out, void* stream);   /* API_DOCUMENTATION.md:232-255; d_find_offsets: M + 1 */
+/* get_srandness (API_DOCUMENTATION.md:232-255, 371-382) for N 23-mers in the input form of aix_positions_query (N * 23 bytes): per k-mer
+ * total = its listed hits (aix_seq_hits of the 23 bytes, cut to max_per_kmer when that is > 0), plus = those whose strand flag is 0 (the
+ * reads hold the k-mer as given), minus = those whose strand flag is 1 (they hold its reverse complement); total - plus - minus hits are
+ * neither. Outputs hold N entries each (the caller's; device buffers for the _dev twin, which returns after the work on `stream` has
+ * completed). N = 0 is AIX_OK. Same restrictions as aix_seq_hits. */
+int aix_kmer_strands(aix_index_t* h, const char* kmers, uint64_t N, uint64_t max_per_kmer, uint64_t* plus_out, uint64_t* minus_out,
+                     uint64_t* total_out);
+int aix_kmer_strands_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint64_t max_per_kmer, uint64_t* d_plus, uint64_t* d_minus,
+                         uint64_t* d_total, void* stream);   /* API_DOCUMENTATION.md:232-255 */
+
+/* ------------------------------------------------------------------------------------------
  * k-mers by frequency: per-kid values, frequency spectrum and statistics, stable top-N / threshold selection, batch kid -> k-mer.
  * replaces AIndex.iter_kmers_by_frequency / get_top_kmers / get_kmer_frequency_stats (aindex/core/aindex.py:594-793: a Python loop over
  *          every kid and a sort of all of them) and, N at a time, AindexWrapper::get_kmer_by_kid / get_kmer_info
