@@ -36,6 +36,7 @@ STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", 
 FIX_NAMES = ("clean", "fixed", "partial", "unfixed", "short", "too_long", "bad_range")   # AIX_FIX_*
 READFIX_MAX_LEN, READFIX_MAX_VERIFY, READFIX_MAX_FIXES = 4096, 16, 16
 SEQFIND_TRIP_BYTES = 64                                            # AIX_SEQFIND_TRIP_BYTES of csrc/aix_seqhits.hpp: pattern bytes per verification trip
+SEQEDIT_MAX_ED = 7                                                 # AIX_SEQEDIT_MAX_ED of csrc/aix_seqhits.hpp: the largest ed of aix_seq_edit
 # aix_readfix_t: one 32-byte record per read
 READFIX_FIELDS = [(f, "<u4") for f in ("status", "weak_before", "weak_after", "fixes", "n0", "nM", "trim_start", "trim_len")]
 
@@ -168,6 +169,9 @@ SIGNATURES = {
     "aix_seq_votes_dev": (i32, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_seq_find": (i32, [vp, vp, vp, u64, u32, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "aix_seq_find_dev": (i32, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_seq_edit": (i32, [vp, vp, vp, u64, u32, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                           C.POINTER(vp)]),
+    "aix_seq_edit_dev": (i32, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
     "aix_kmer_strands": (i32, [vp, vp, u64, u64, vp, vp, vp]),
     "aix_kmer_strands_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, vp]),
     "aix_values_narrow_dev": (i32, [vp, u64, vp, vp]),

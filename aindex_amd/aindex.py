@@ -37,6 +37,18 @@ def hamming_distance(s1: str, s2: str) -> int:
     return sum(1 for a, b in zip(s1, s2) if a != b and a != "N" and b != "N")
 
 
+def edit_distance(s1: str, s2: str) -> int:
+    """aindex.py:22 re-exports editdistance.eval under this name: plain Levenshtein distance (unit costs, no N rule), on the host."""
+    if len(s1) < len(s2):
+        s1, s2 = s2, s1
+    row = list(range(len(s2) + 1))
+    for i, a in enumerate(s1, 1):
+        diag, row[0] = row[0], i
+        for j, b in enumerate(s2, 1):
+            diag, row[j] = row[j], min(diag + (a != b), row[j] + 1, row[j - 1] + 1)
+    return row[-1]
+
+
 def get_revcomp(sequence: str) -> str:
     c = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N", "a": "t", "c": "g", "g": "c", "t": "a", "n": "n", "~": "~", "[": "]", "]": "["}
     return "".join(c.get(x, x) for x in reversed(sequence))
@@ -413,6 +425,34 @@ class AIndex:
         recs = [(r, l, reads[j], s, d) for r, l, j, s, d in zip(rid.tolist(), local.tolist(), inv.tolist(), strand.tolist(), dist.tolist())]
         off = off.tolist()
         return [recs[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def find_sequences_edit_array(self, seqs, ed: int = 1, seed_step: int = 23, max_per_kmer: int = 0):
+        """CSR arrays (find_offsets, start, end, rid, local, strand, dist) of the alignments of every sequence to the indexed reads with
+        edit distance at most ed (substitutions, inserted and deleted bases), either strand, one GPU call; see
+        AindexWrapper.find_sequences_edit_array and include/aindex_hip.h for the rules."""
+        return self._wrapper.find_sequences_edit_array(seqs, ed, seed_step, max_per_kmer)
+
+    def find_reads_by_sequence_edit_batch(self, seqs, ed: int = 1) -> List[List[tuple]]:
+        """Per sequence, per read that holds it with edit distance at most ed, rid ascending: (rid, starts[0], read, starts, ends, smallest
+        dist); starts / ends = where its alignments begin / end in the read, either strand, each ascending and distinct. Seeds on either
+        side of an indel report near-duplicate records of one alignment in the arrays; this surface merges them per read.
+        Two GPU calls: the search, and the reads of every distinct rid."""
+        off, start, end, rid, local, _, dist = self.find_sequences_edit_array(seqs, ed)
+        uniq = np.unique(rid)
+        reads = dict(zip(uniq.tolist(), self.get_reads_by_rid_batch(uniq)))
+        off = off.tolist()
+        lend = (end - start + local).tolist()
+        rid, local, dist = rid.tolist(), local.tolist(), dist.tolist()
+        out = []
+        for i in range(len(off) - 1):
+            per = {}
+            for j in range(off[i], off[i + 1]):
+                e = per.setdefault(rid[j], [set(), set(), dist[j]])
+                e[0].add(local[j])
+                e[1].add(lend[j])
+                e[2] = min(e[2], dist[j])
+            out.append([(r, min(per[r][0]), reads[r], sorted(per[r][0]), sorted(per[r][1]), per[r][2]) for r in sorted(per)])
+        return out
 
     def get_strandness_batch(self, kmers) -> List[tuple]:
         """[(plus, minus, total)] per 23-mer, one GPU call; see AindexWrapper.get_strandness_batch."""

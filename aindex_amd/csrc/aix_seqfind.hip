@@ -50,35 +50,6 @@ struct SfVerify {
     uint32_t* dist;
 };
 
-// bytes [p, p + 4) of a buffer of `size` bytes, first byte least significant; a byte outside [0, size) reads as 0 and is never touched.
-// Inside, two aligned dwords (they reach up to 3 bytes before p and 4 behind p + 4); within 3 bytes of the start or 8 of the end, bytes.
-__device__ __forceinline__ uint32_t sf_load4(const uint8_t* __restrict__ buf, uint64_t size, int64_t p) {
-    if (p >= 3 && (uint64_t)p < size && size - (uint64_t)p >= 8) {
-        const uint8_t* at = buf + p;
-        const uint32_t o = (uint32_t)((uintptr_t)at & 3);
-        const uint32_t* q = (const uint32_t*)(at - o);         // pointer arithmetic, as load23: the loads stay global_load
-        return __funnelshift_r(q[0], q[1], o * 8);
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int64_t at = p + b;
-        if (at >= 0 && (uint64_t)at < size) v |= (uint32_t)buf[at] << (8 * b);
-    }
-    return v;
-}
-
-// A <-> T, C <-> G, a <-> t, c <-> g, every other byte as it is
-__device__ __forceinline__ uint32_t sf_comp(uint32_t c) {
-    const uint32_t u = c & 0xDFu, lower = c & 0x20u;
-    const uint32_t r = u == 'A' ? 'T' : u == 'T' ? 'A' : u == 'C' ? 'G' : u == 'G' ? 'C' : 0u;
-    return r ? (r | lower) : c;
-}
-
-__device__ __forceinline__ uint64_t sf_shfl64(uint64_t v, uint32_t src) {
-    return (uint64_t)bperm(src, (uint32_t)v) | ((uint64_t)bperm(src, (uint32_t)(v >> 32)) << 32);
-}
-
 __global__ void __launch_bounds__(kSB) k_sf_verify(const SfVerify P) {
     const uint32_t lane = threadIdx.x & 63u, sub = lane & (kSfLanes - 1u), grp = lane / kSfLanes;
     const uint64_t stride = (uint64_t)gridDim.x * kSB;

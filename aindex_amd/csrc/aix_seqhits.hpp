@@ -1,5 +1,5 @@
 // aix_seqhits.hpp — what more than one translation unit uses of the chain sequences -> windows -> seed hits (aix_seqhits.hip: hits and
-// diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts): the hit buffers, steps 1 to 4 with a window stride, the
+// diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts; aix_seqedit.hip: edit-distance alignments): the hit buffers, steps 1 to 4 with a window stride, the
 // stable rocPRIM passes over a permutation, and the host ends of the C ABI.
 #pragma once
 #include <algorithm>
@@ -13,6 +13,9 @@
 // bytes of a pattern that one trip of the verification loop of aix_seqfind.hip compares (16 lanes x one dword). Not part of the C ABI:
 // _lib.SEQFIND_TRIP_BYTES repeats it for the tests that place pattern lengths around its multiples.
 #define AIX_SEQFIND_TRIP_BYTES 64u
+// the largest edit distance aix_seq_edit accepts: a band of 2 * 7 + 1 = 15 diagonals fits the 16 lanes that share one proposal
+// (aix_seqedit.hip). Not part of the C ABI's types; include/aindex_hip.h states the bound and _lib.SEQEDIT_MAX_ED repeats it.
+#define AIX_SEQEDIT_MAX_ED 7u
 
 namespace aix {
 
@@ -83,6 +86,36 @@ static hipError_t sv_sort(KeyIt keys, Key* keys_out, ValIt perm_in, uint64_t* pe
     if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
     return e;
+}
+
+// ---- device helpers of the verification kernels (aix_seqfind.hip: Hamming; aix_seqedit.hip: banded edit distance) ----
+// bytes [p, p + 4) of a buffer of `size` bytes, first byte least significant; a byte outside [0, size) reads as 0 and is never touched.
+// Inside, two aligned dwords (they reach up to 3 bytes before p and 4 behind p + 4); within 3 bytes of the start or 8 of the end, bytes.
+__device__ __forceinline__ uint32_t sf_load4(const uint8_t* __restrict__ buf, uint64_t size, int64_t p) {
+    if (p >= 3 && (uint64_t)p < size && size - (uint64_t)p >= 8) {
+        const uint8_t* at = buf + p;
+        const uint32_t o = (uint32_t)((uintptr_t)at & 3);
+        const uint32_t* q = (const uint32_t*)(at - o);         // pointer arithmetic, as load23: the loads stay global_load
+        return __funnelshift_r(q[0], q[1], o * 8);
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int64_t at = p + b;
+        if (at >= 0 && (uint64_t)at < size) v |= (uint32_t)buf[at] << (8 * b);
+    }
+    return v;
+}
+
+// A <-> T, C <-> G, a <-> t, c <-> g, every other byte as it is
+__device__ __forceinline__ uint32_t sf_comp(uint32_t c) {
+    const uint32_t u = c & 0xDFu, lower = c & 0x20u;
+    const uint32_t r = u == 'A' ? 'T' : u == 'T' ? 'A' : u == 'C' ? 'G' : u == 'G' ? 'C' : 0u;
+    return r ? (r | lower) : c;
+}
+
+__device__ __forceinline__ uint64_t sf_shfl64(uint64_t v, uint32_t src) {
+    return (uint64_t)bperm(src, (uint32_t)v) | ((uint64_t)bperm(src, (uint32_t)(v >> 32)) << 32);
 }
 
 }  // namespace aix

@@ -642,6 +642,32 @@ class Index:
                            lambda m, off, o, cap, tot: lib().aix_seq_find_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, hd, seed_step, max_per_kmer, off,
                                                                               *o, cap, tot, st))
 
+    # ---- sequences with substitutions, insertions and deletions (aix_seqedit.hip) -----------------
+    def seq_edit(self, seqs: Sequence, ed: int = 1, seed_step: int = 23, max_per_kmer: int = 0):
+        """Alignments of every sequence to the indexed reads with edit distance at most ed (0 .. _lib.SEQEDIT_MAX_ED; substitutions,
+        inserted and deleted bases, the N rule of hamming_distance), found by a banded dynamic programme around the diagonal of every seed
+        hit: (find_offsets u64[M + 1], start u64, end u64, rid u64, local u64, strand u8, dist u32). The records of sequence i are
+        [find_offsets[i], find_offsets[i + 1]), ascending by (start, strand); the alignment is reads[start:end], local = start - start of
+        the read that holds the seed. Complete when ed < len // 23 and seed_step is 1 or 23 (include/aindex_hip.h)."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(7)]
+        check(lib().aix_seq_edit(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, ed, seed_step, max_per_kmer, *[C.byref(p) for p in ps]),
+              "aix_seq_edit")
+        fo = self._take_as(ps[0], m + 1, np.uint64)
+        r = int(fo[m])
+        return (fo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint64), self._take_as(ps[3], r, np.uint64),
+                self._take_as(ps[4], r, np.uint64), self._take_as(ps[5], r, np.uint8), self._take_as(ps[6], r, np.uint32))
+
+    def seq_edit_t(self, seqs_t, offs_t, ed: int = 1, seed_step: int = 23, max_per_kmer: int = 0, cap_hint: int = 0):
+        """seq_edit on device tensors (uint8 bytes, int64 offsets[M + 1] into them), on torch's current stream:
+        (find_offsets int64, start int64, end int64, rid int64, local int64, strand uint8, dist int32) — bit patterns of the unsigned fields."""
+        import torch
+        st = _stream_ptr(self.device)
+        return self._seq_t("aix_seq_edit_dev", seqs_t, offs_t, [torch.int64, torch.int64, torch.int64, torch.int64, torch.uint8, torch.int32], cap_hint,
+                           lambda m, off, o, cap, tot: lib().aix_seq_edit_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, ed, seed_step, max_per_kmer, off,
+                                                                              *o, cap, tot, st))
+
     def kmer_strands(self, kmers, max_per_kmer: int = 0):
         """(plus, minus, total) uint64[N]: of the listed hits of every 23-mer (`kmers`: what tf_ascii takes), those where the reads hold it
         as given, those where they hold its reverse complement, and all of them."""

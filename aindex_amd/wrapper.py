@@ -950,6 +950,12 @@ class AindexWrapper:
         arrays (find_offsets uint64[M + 1], pos uint64, rid uint64, local uint64, strand uint8, dist uint32); see Index.seq_find."""
         return self._attach_for_mapping().seq_find(list(seqs), hd, seed_step, max_per_kmer)
 
+    def find_sequences_edit_array(self, seqs, ed: int = 1, seed_step: int = 23, max_per_kmer: int = 0):
+        """Where every sequence (str or bytes) lies in the indexed reads with edit distance at most ed, either strand, in one GPU call: CSR
+        arrays (find_offsets uint64[M + 1], start uint64, end uint64, rid uint64, local uint64, strand uint8, dist uint32); see
+        Index.seq_edit."""
+        return self._attach_for_mapping().seq_edit(list(seqs), ed, seed_step, max_per_kmer)
+
     def get_strandness_batch(self, kmers, max_per_kmer: int = 0) -> List[tuple]:
         """[(plus, minus, total)] per 23-mer in one GPU call: its listed occurrences where the reads hold it as given, where they hold its
         reverse complement, and all of them (Index.kmer_strands). Items of another length give (0, 0, 0) in place."""

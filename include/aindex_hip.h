@@ -666,6 +666,52 @@ int aix_seq_find(aix_index_t* h, const char* seqs, const uint64_t* offs, uint64_
 int aix_seq_find_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint32_t hd, uint64_t seed_step,
                      uint64_t max_per_kmer, uint64_t* d_find_offsets, uint64_t* d_pos, uint64_t* d_rid, uint64_t* d_local, uint8_t* d_strand,
                      uint32_t* d_dist, uint64_t cap, uint64_t* total_out, void* stream);   /* API_DOCUMENTATION.md:232-255; d_find_offsets: M + 1 */
+/* ------------------------------------------------------------------------------------------
+ * Sequences against the indexed reads with substitutions, insertions and deletions (edit distance): indel-tolerant seed verification.
+ * replaces the loop a caller writes over aix_seq_hits, aix_reads_fetch and a dynamic programme per candidate on the host; the reference's
+ *          public module imports edit_distance beside hamming_distance (aindex/core/aindex.py:22-23) and holds no search over either, so
+ *          this header is the contract. tests/seqedit_ref.py restates it.
+ * Restrictions, input form, seeds and hits are those of aix_seq_find: 23-mer handles only (AIX_ERR_MODE); positions index, read intervals
+ * and reads attached (AIX_ERR_ARG otherwise); M sequences as seqs + offs[M + 1], each shorter than 2^32 bytes; seed_step 0 means 23;
+ * max_per_kmer as in aix_seq_hits; only hits with strand 0 or 1 count.
+ *   ed            the largest distance reported, 0 <= ed <= 7 (AIX_SEQEDIT_MAX_ED of csrc/aix_seqhits.hpp); AIX_ERR_ARG otherwise
+ * Oriented pattern: y_i (0 <= i < L) exactly as in aix_seq_find: seq[i] (strand 0) or comp(seq[L - 1 - i]) (strand 1), the same comp.
+ * Proposal: a hit (q, pos, strand) anchors the diagonal a = pos - q (strand 0) or a = pos - (L - 23 - q) (strand 1); a is signed and may
+ *   be negative. The hit belongs to the interval (rid, start, end) with start <= pos and pos + 23 <= end: plain containment of the SEED,
+ *   found by bisection; without one the proposal is dropped. Text columns: lo = max(start, a - ed), hi = min(end, a + L + ed, attached
+ *   length). Bytes of the reads outside [lo, hi) never reach a cell that exists, and nothing is read outside the attached reads,
+ *   whatever the positions array holds.
+ * Banded programme: cells (i, j) exist for 0 <= i <= L, lo <= j <= hi and |j - i - a| <= ed. Row 0: D[0][j] = 0 with start j (the start
+ *   of the text is free). Three moves into (i, j), each from an existing cell: from (i - 1, j - 1) at cost 0 when x_{j-1} == y_{i-1} or
+ *   either byte is 'N' (raw bytes: the N rule of hamming_distance), else 1, x_j = reads[j]; from (i - 1, j) at cost 1; from (i, j - 1) at
+ *   cost 1. Every cell carries the pair (cost, start); its value is the lexicographic minimum over its incoming moves. The pattern is
+ *   consumed whole, the end of the text is free: the proposal's result is the lexicographic minimum (dist, start, end = j) over the
+ *   existing cells of row L, and the proposal survives when dist <= ed.
+ * Output: one record per (start, strand) of a sequence: the lexicographically smallest (dist, end) among its surviving proposals that share
+ *   that (start, strand). CSR over sequences, the records of sequence i = [find_offsets[i], find_offsets[i + 1]), ascending by
+ *   (start, strand). Columns: start u64, end u64 (the alignment is reads[start, end)), rid u64, local u64 = start - interval start,
+ *   strand u8, dist u32. The answer is independent of launch geometry and of every probe switch.
+ * ed = 0: the band is one diagonal, so the records equal those of aix_seq_find(hd = 0) with start = a and end = a + L.
+ * Near-duplicates: two seeds on different diagonals (on either side of an indel) can report overlapping records with different start for
+ *   one underlying alignment: their bands differ, so their tie-breaks can differ. An alignment with at most ed edits lies inside the
+ *   band of each of its untouched seeds, so this needs a second alignment within ed at another start that one band holds and the other
+ *   does not: self-similar text (tandem repeats, homopolymers). This array surface keeps both; the list surface
+ *   (AIndex.find_reads_by_sequence_edit_batch) merges per read.
+ * Completeness: if an alignment of the whole pattern to a substring of one read has at most ed edits, one of ed + 1 pairwise disjoint seed
+ *   windows is untouched by them; when it is listed in full its band holds the whole alignment (an alignment with at most ed edits drifts
+ *   at most ed diagonals from an untouched seed). So for ed < floor(L / 23), seed_step 1 or 23, max_per_kmer = 0, every occurrence indexed
+ *   and no 'N' in the seeds, the smallest distance per (rid, strand) equals that of an unbanded semi-global Levenshtein search (same N rule)
+ *   over every read.
+ * The _dev twin follows the sizing convention of aix_seq_find_dev: d_find_offsets[M + 1] and *total_out always, records only when the
+ * total fits `cap`, never at or beyond it, AIX_OK either way; it returns after the work on `stream` has completed. Host outputs are
+ * malloc'd (aix_free); M = 0 gives find_offsets = {0}.
+ * ------------------------------------------------------------------------------------------ */
+int aix_seq_edit(aix_index_t* h, const char* seqs, const uint64_t* offs, uint64_t M, uint32_t ed, uint64_t seed_step, uint64_t max_per_kmer,
+                 uint64_t** find_offsets_out, uint64_t** start_out, uint64_t** end_out, uint64_t** rid_out, uint64_t** local_out,
+                 uint8_t** strand_out, uint32_t** dist_out);   /* aindex/core/aindex.py:22-23 */
+int aix_seq_edit_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint32_t ed, uint64_t seed_step,
+                     uint64_t max_per_kmer, uint64_t* d_find_offsets, uint64_t* d_start, uint64_t* d_end, uint64_t* d_rid, uint64_t* d_local,
+                     uint8_t* d_strand, uint32_t* d_dist, uint64_t cap, uint64_t* total_out, void* stream);   /* d_find_offsets: M + 1 */
 /* get_srandness (API_DOCUMENTATION.md:232-255, 371-382) for N 23-mers in the input form of aix_positions_query (N * 23 bytes): per k-mer
  * total = its listed hits (aix_seq_hits of the 23 bytes, cut to max_per_kmer when that is > 0), plus = those whose strand flag is 0 (the
  * reads hold the k-mer as given), minus = those whose strand flag is 1 (they hold its reverse complement); total - plus - minus hits are
