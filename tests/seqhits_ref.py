@@ -37,7 +37,7 @@ def revcomp(s: bytes) -> bytes:
 
 class Ref:
     def __init__(self, prefix: str, indices=None, positions=None, reads: bytes = None, ridx=None):
-        z = np.load(os.path.join(os.path.dirname(prefix), "aindex.npz"))
+        z = np.load(os.path.join(os.path.dirname(prefix), "aindex.npz")) if indices is None or positions is None else None
         self.orc = O.OracleIndex23.from_prefix(prefix)
         self.checker = self.orc.checker().tolist()
         self.n = len(self.checker)
