@@ -228,6 +228,7 @@ SIGNATURES = {
     "aix_selftest_lower_bound_dev": (i32, [vp, C.c_uint32, vp, C.c_uint32, vp, vp]),
     "aix_debug_rehome": (i32, [vp, C.c_uint32]),
     "aix_debug_pointers": (i32, [vp, C.POINTER(u64)]),
+    "aix_debug_filter_words": (i32, [vp, vp, u64]),
     "aix_selftest_mod": (u64, [u64, u64]),
     "aix_selftest_revcomp": (u64, [u64, i32]),
 }

@@ -118,6 +118,15 @@ extern "C" int aix_debug_rehome(aix_index_t* h, uint32_t mask) {
     return st;
 }
 
+// host copy of the absence filter (nwords must be the handle's absence_filter_words): for the suite, which rebuilds the filter from the keys
+extern "C" int aix_debug_filter_words(aix_index_t* h, uint64_t* out, uint64_t nwords) {
+    if (!h || !out || !h->bloom || h->nbloom == 0 || nwords != h->nbloom) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->bloom, 8ull * h->nbloom, hipMemcpyDeviceToHost));
+    return AIX_OK;
+}
+
 // GPU self-test hook of the suite: lower bounds of keys[i] and keys[i] + 1 in a sorted u16 array, by the wave-wide search the partition kernels
 // use to find a partition's chunks (out[2 i], out[2 i + 1]); all pointers are device pointers
 extern "C" int aix_selftest_lower_bound_dev(const uint16_t* d_sorted, uint32_t n, const uint32_t* d_keys, uint32_t nkeys, uint32_t* d_out, void* stream) {

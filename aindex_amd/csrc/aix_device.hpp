@@ -68,11 +68,30 @@ struct __attribute__((aligned(16))) BkEntry {
 // Absence filter in front of the verification table (lookups and coverage, where most probes may be absent keys): a blocked
 // Bloom filter, one 64-bit word per probe, four bits per key, filled from the same keys as the table. It is small enough to
 // live in the Infinity Cache (16 bits per key by default), so an absent key is usually answered by ONE 8-byte cached read and
-// never reaches HBM; a filed key passes it by construction. Word and bits come from hash words the bucket choice does not use.
-__device__ __forceinline__ uint64_t bloom_mask(uint64_t c) {
-    return (1ull << (c & 63)) | (1ull << ((c >> 6) & 63)) | (1ull << ((c >> 12) & 63)) | (1ull << ((c >> 18) & 63));
+// never reaches HBM; a filed key passes it by construction.
+// The filter is keyed by the stored 46-bit CODE, not by the Jenkins hash of its ASCII: it is built when the index is opened, is never
+// written to a file, and is consulted only by probes whose hashed bytes are exactly the ASCII of their code, so the code determines
+// the key and an absent query is answered without the ASCII of its canonical strand and without Jenkins. filter_key is a 32-bit mix
+// (the final() of Bob Jenkins' lookup3, public domain) of the two halves of the code: hw picks the word, hb the bits. The mask has
+// one bit in each 16-bit quarter of the word: 16 bits of hb.
+AIX_HD uint32_t rot32(uint32_t x, uint32_t k) { return (x << k) | (x >> (32u - k)); }
+AIX_HD void filter_key(uint64_t code, uint32_t& hw, uint32_t& hb) {
+    uint32_t a = (uint32_t)code + 0x9E3779B9u, b = (uint32_t)(code >> 32) + 0x85EBCA6Bu, c = 0xC2B2AE35u;
+    c ^= b; c -= rot32(b, 14);
+    a ^= c; a -= rot32(c, 11);
+    b ^= a; b -= rot32(a, 25);
+    c ^= b; c -= rot32(b, 16);
+    a ^= c; a -= rot32(c, 4);
+    b ^= a; b -= rot32(a, 14);
+    c ^= b; c -= rot32(b, 24);
+    hw = b;
+    hb = c;
 }
-__device__ __forceinline__ uint32_t bloom_word(uint64_t b, uint32_t nwords) { return (uint32_t)__umul64hi(b, (uint64_t)nwords); }
+AIX_HD uint64_t bloom_mask(uint32_t hb) {
+    const uint32_t lo = (1u << (hb & 15)) | (0x10000u << ((hb >> 4) & 15)), hi = (1u << ((hb >> 8) & 15)) | (0x10000u << ((hb >> 12) & 15));
+    return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+AIX_HD uint32_t bloom_word(uint32_t hw, uint32_t nwords) { return (uint32_t)(((uint64_t)hw * nwords) >> 32); }
 
 // ---------------------------------------------------------------------------------------------
 // exact h % d for a launch-invariant d (Moeller-Granlund 2-by-1 division, 32-bit limbs).

@@ -514,7 +514,11 @@ __global__ void __launch_bounds__(kBlock) k_bk_fill(const MphfDev m, const KeyRe
         ascii23_of_rc(revcomp(kr.code, 23), w0, w1, w2);
         jenkins23(w0, w1, w2, m.seed, a, b, c);
         if (mphf_from_hash(m, a, b, c) != i) continue;         // not where the MPHF puts it: the reference cannot find it, neither can a probe
-        if (bloom) atomicOr((unsigned long long*)&bloom[bloom_word(b, nbloom)], (unsigned long long)bloom_mask(c));
+        if (bloom) {                                           // keyed by the code itself (aix_device.hpp: filter_key)
+            uint32_t hw, hb;
+            filter_key(kr.code, hw, hb);
+            atomicOr((unsigned long long*)&bloom[bloom_word(hw, nbloom)], (unsigned long long)bloom_mask(hb));
+        }
         const uint32_t bi = bucket_of(a, nb);
         const uint32_t pos = atomicAdd(&fill[bi], 1u);
         BkEntry e;

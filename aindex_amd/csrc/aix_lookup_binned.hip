@@ -4,7 +4,8 @@
 //   k_lb_gate     ~16 K evenly spaced queries against the filter: the piece is binned iff fewer than a quarter of them pass
 //                 (FilterGauge's rule). One flag in the workspace header; every kernel behind it reads the flag first and
 //                 the one not chosen returns at once, so there is no host synchronisation.
-//   k_lb_bin      pass A: load, encode, strand pick and hash as the direct kernel does; one 8-byte record per clean query,
+//   k_lb_bin      pass A: load, encode, strand pick and the filter key of the canonical code (no ASCII of the other strand and no
+//                 Jenkins hash: the filter is keyed by the code, aix_device.hpp); one 8-byte record per clean query,
 //                 counting-sorted by filter slice in LDS per 4096-query tile and flushed into 256-record chunks of a per-slice
 //                 region (chunks come from a per-slice cursor; a workgroup asks for all chunks of a tile and slice at once).
 //                 out[i] = 0 for every query. Queries with other bytes, and records whose slice region is full, go onto the
@@ -12,9 +13,9 @@
 //   k_lb_filter   pass B: chunks in slice order across the whole grid, so that the chip reads one or two slices (~1 MiB each)
 //                 at a time and every XCD holds them in its L2 (the chunks are handed out in order through ticket counters). A record that passes is appended to the survivor list.
 //   k_lookup23_list (aix_kernels.hip) pass C: the survivors through the ordinary probe.
-// A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the low 18 bits of Jenkins' c, i.e.
-// three of the four bit positions bloom_mask takes from it: 8 bytes. Pass B therefore lets a superset of the filter's positives
-// through (~1.5 % of absent queries instead of ~0.5 %); pass C consults the complete filter again, so answers do not depend on it.
+// A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the 16 bits of the filter key from which
+// bloom_mask takes all four bit positions: 8 bytes, three bits spare. Pass B therefore lets exactly the filter's positives through
+// (~0.5 % of absent queries); pass C goes through the ordinary probe, which consults the filter again, so answers do not depend on it.
 #include <algorithm>
 
 #include "aix_env.hpp"
@@ -34,7 +35,8 @@ static constexpr int LB_TICKETS = 8;                   // pass B hands its chunk
 static constexpr int LB_SURV = 4096;                   // survivors a pass-B workgroup collects in LDS before it appends them
 static constexpr unsigned LB_GRID_B = 2048;
 static constexpr uint32_t LB_SAMPLES = 16384;
-static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 18;
+static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 16;
+static_assert(LB_MASK_BITS == 16 && LB_IDX_BITS + LB_WORD_BITS + LB_MASK_BITS <= 64, "the record holds the 16 bits bloom_mask reads");
 static constexpr uint32_t LB_NONE = 0xFFFFFFFFu;
 static constexpr uint64_t LB_HDR_BYTES = 4096;         // header (4 words) + cursors (LB_MAXBINS words) + ticket counters (a 128-byte line each), zeroed per piece
 enum { LB_FLAG = 0, LB_PASSED = 1, LB_DONE = 2, LB_NSURV = 3, LB_CURSOR = 16, LB_TICKET = 512 };
@@ -53,19 +55,16 @@ struct LbWs {
     unsigned long long* stats;     // pieces binned, pieces direct, records that overflowed, survivors
 };
 
-// the query's strand pick and hash as query23 (aix_kernels.hip) does them; false = other bytes
-__device__ __forceinline__ bool lb_hash(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t seed, uint64_t& b, uint64_t& c) {
+// the filter key of the code query23 (aix_kernels.hip) probes: that of the canonical strand; false = other bytes
+__device__ __forceinline__ bool lb_hash(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t& hw, uint32_t& hb) {
     const Enc23 e = encode23_words(w0, w1, w2);
     if (!e.valid) return false;
     const uint64_t r = revcomp(e.code, 23);
-    if (!(e.code <= r)) ascii23_of_rc(e.code, w0, w1, w2);
-    uint64_t a;
-    jenkins23(w0, w1, w2, seed, a, b, c);
+    filter_key(e.code <= r ? e.code : r, hw, hb);
     return true;
 }
-__device__ __forceinline__ uint64_t lb_mask3(uint32_t c) { return (1ull << (c & 63)) | (1ull << ((c >> 6) & 63)) | (1ull << ((c >> 12) & 63)); }
 
-__global__ void __launch_bounds__(256) k_lb_gate(uint64_t seed, const uint64_t* __restrict__ bloom, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n,
+__global__ void __launch_bounds__(256) k_lb_gate(const uint64_t* __restrict__ bloom, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n,
                                                  uint32_t nsamp, int force, uint32_t* __restrict__ hdr, unsigned long long* __restrict__ stats) {
     if (force) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { hdr[LB_FLAG] = 1u; atomicAdd(&stats[0], 1ull); }
@@ -78,12 +77,13 @@ __global__ void __launch_bounds__(256) k_lb_gate(uint64_t seed, const uint64_t* 
     bool pass = false;
     if (s < nsamp) {
         const uint64_t i = (uint64_t)s * n / nsamp;
-        uint64_t w0, w1, w2, b, c;
+        uint64_t w0, w1, w2;
+        uint32_t hw, hb;
         load23(q + 23 * i, w0, w1, w2);
         pass = true;                                            // other bytes: the direct probe's business
-        if (lb_hash(w0, w1, w2, seed, b, c)) {
-            const uint64_t m = bloom_mask(c);
-            pass = (bloom[bloom_word(b, nbloom)] & m) == m;
+        if (lb_hash(w0, w1, w2, hw, hb)) {
+            const uint64_t m = bloom_mask(hb);
+            pass = (bloom[bloom_word(hw, nbloom)] & m) == m;
         }
     }
     const uint32_t wave = (uint32_t)__popcll(__ballot(pass));
@@ -132,7 +132,7 @@ __device__ __forceinline__ void lb_place(uint32_t f, uint32_t cur, uint32_t nb, 
     else { chunk = nb + (pos - LB_CH) / LB_CH; o = (pos - LB_CH) % LB_CH; }
 }
 
-__global__ void __launch_bounds__(LB_TB) k_lb_bin(uint64_t seed, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
+__global__ void __launch_bounds__(LB_TB) k_lb_bin(uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
     if (!w.hdr[LB_FLAG]) return;
     __shared__ uint64_t sorted[LB_TILE];
     __shared__ uint16_t sbin[LB_TILE];
@@ -156,16 +156,17 @@ __global__ void __launch_bounds__(LB_TB) k_lb_bin(uint64_t seed, uint32_t nbloom
             meta[j] = LB_NONE;
             rec[j] = 0;
             if (i < n) {
-                uint64_t w0, w1, w2, b, c;
+                uint64_t w0, w1, w2;
+                uint32_t hw, hb;
                 load23(q + 23ull * i, w0, w1, w2);
                 uint32_t bin = NB;
                 uint64_t r = i;
-                if (lb_hash(w0, w1, w2, seed, b, c)) {
-                    const uint32_t word = bloom_word(b, nbloom);
+                if (lb_hash(w0, w1, w2, hw, hb)) {
+                    const uint32_t word = bloom_word(hw, nbloom);
                     bin = __umulhi(word, g.inv);                 // word / wps, at most one too small
                     uint32_t wi = word - bin * g.wps;
                     if (wi >= g.wps) { wi -= g.wps; ++bin; }
-                    r |= ((uint64_t)wi << LB_IDX_BITS) | ((uint64_t)((uint32_t)c & ((1u << LB_MASK_BITS) - 1)) << (LB_IDX_BITS + LB_WORD_BITS));
+                    r |= ((uint64_t)wi << LB_IDX_BITS) | ((uint64_t)(hb & ((1u << LB_MASK_BITS) - 1)) << (LB_IDX_BITS + LB_WORD_BITS));
                 }
                 meta[j] = bin | (atomicAdd(&hist[bin], 1u) << 16);
                 rec[j] = r;
@@ -308,8 +309,8 @@ __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict_
         }
 #pragma unroll
         for (int u = 0; u < LB_U; ++u) {
-            const uint64_t m3 = lb_mask3((uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));
-            const bool pass = t < cn[u] && (wd[u] & m3) == m3;
+            const uint64_t mk = bloom_mask((uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));   // all four positions: the low LB_MASK_BITS bits
+            const bool pass = t < cn[u] && (wd[u] & mk) == mk;
             const uint64_t m = __ballot(pass);
             if (m) {
                 uint32_t r0 = 0;
@@ -393,11 +394,11 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
         uint32_t* op = out + lo;
         HIPCHK(hipMemsetAsync(w.hdr, 0, LB_HDR_BYTES, s));
         const uint32_t nsamp = std::min<uint32_t>(m, LB_SAMPLES);
-        hipLaunchKernelGGL(k_lb_gate, dim3(sw == 2 ? 1 : (nsamp + 255) / 256), dim3(256), 0, s, d.m.seed, d.bloom, d.nbloom, qp, m, nsamp, sw == 2 ? 1 : 0, w.hdr,
+        hipLaunchKernelGGL(k_lb_gate, dim3(sw == 2 ? 1 : (nsamp + 255) / 256), dim3(256), 0, s, d.bloom, d.nbloom, qp, m, nsamp, sw == 2 ? 1 : 0, w.hdr,
                            w.stats);
         HIPCHK(hipGetLastError());
         if (sw != 2) HIPCHK(launch_lookup23_ascii(d, qp, m, MODE_TF, LookupOut{op, nullptr, nullptr, nullptr}, s, w.hdr + LB_FLAG));
-        hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), 0, s, d.m.seed, d.nbloom, qp, m, g, w, op);
+        hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), 0, s, d.nbloom, qp, m, g, w, op);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
         HIPCHK(hipGetLastError());

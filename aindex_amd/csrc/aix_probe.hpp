@@ -68,17 +68,17 @@ __device__ __forceinline__ Probe probe23_wave(const IndexDev& ix, bool want, uin
                                               bool absence = true) {
     Probe r;
     r.found = false; r.tf = 0; r.slot = 0; r.lines = 0;
-    const bool rest = want;
+    bool use = want && filters && ix.bk, mphf = want;
+    if (ix.bk && ix.bloom && absence && use) {                  // absent from the filter = not a filed key; an unfiled key (overflow) is in it too
+        r.lines += 4096;
+        uint32_t hw, hb;
+        filter_key(code, hw, hb);                               // filters: the hashed bytes are the ASCII of `code`, so the code is the key
+        const uint64_t m = bloom_mask(hb);
+        if ((ix.bloom[bloom_word(hw, ix.nbloom)] & m) != m) { use = false; mphf = false; }
+    }
     uint64_t a = 0, b = 0, c = 0;
-    if (rest) jenkins23(w0, w1, w2, ix.m.seed, a, b, c);
-    bool mphf = rest;
+    if (use || mphf) jenkins23(w0, w1, w2, ix.m.seed, a, b, c); // only the lanes that go on to the bucket or the MPHF path
     if (ix.bk) {
-        bool use = rest && filters;
-        if (ix.bloom && absence && use) {                       // absent from the filter = not a filed key; an unfiled key (overflow) is in it too
-            r.lines += 4096;
-            const uint64_t m = bloom_mask(c);
-            if ((ix.bloom[bloom_word(b, ix.nbloom)] & m) != m) { use = false; mphf = false; }
-        }
         const BkRes k = bucket_probe_wave<LPP>(ix.bk, ix.nb, use, a, code);
         if (use) {
             r.lines += 65536;

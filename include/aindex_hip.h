@@ -821,6 +821,9 @@ int aix_debug_relocate_table(aix_index_t* h, void* d_dst);
 int aix_debug_relocate_bloom(aix_index_t* h, uint64_t pad_bytes);
 int aix_debug_pointers(const aix_index_t* h, uint64_t out[5]);   /* device addresses: MPHF records, side index, unfiled keys, table, absence filter */
 int aix_debug_rehome(aix_index_t* h, uint32_t mask);   /* 1 MPHF records, 2 side index, 4 unfiled keys, 8 table, 16 absence filter -> fresh blocks */
+/* Host copy of the absence filter of a 23-mer handle (nwords = its absence_filter_words; AIX_ERR_ARG on any other size or without a filter).
+ * The filter is built when the index is opened and has no file format; only the test-suite reads it. */
+int aix_debug_filter_words(aix_index_t* h, uint64_t* out, uint64_t nwords);
 
 /* self-test hook of the GPU suite: lower bounds of keys[i] and keys[i] + 1 in a sorted u16 array of n entries, computed by the wave-wide search with
  * which the partition kernels find a partition's chunks; out[2 i], out[2 i + 1]. Device pointers. */
