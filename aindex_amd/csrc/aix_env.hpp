@@ -29,10 +29,11 @@
 //     AIX_COUNT23_HIST_CUS         AB  n[,style], n 8 .. 224         -      CU-masked streams for histogram and probe
 //   per call, the binned tf lookup (aix_lookup_binned.hip)
 //     AIX_LOOKUP_BINNED            AB  0, 1, 2                       1      0 never, 1 auto (candidate batches, the device gate decides per piece), 2 always (no gate, no minimum)
-//     AIX_LOOKUP_BINNED_MIN        T   queries                       2^25   smallest batch that is a candidate
+//     AIX_LOOKUP_BINNED_MIN        T   queries                       2^24   smallest batch that is a candidate
 //     AIX_LOOKUP_SLICE_BYTES       T/H 8 .. 2 MiB                    1 MiB  filter slice = one bin (small values: many bins on a tiny index)
 //     AIX_LOOKUP_PIECE             H   1 .. 2^27                     2^27   queries per piece
 //     AIX_LOOKUP_TEST_BIN_CAP      H   records                       -      capacity of a bin's region (forces the overflow route)
+//     AIX_LOOKUP_TEST_GRID_B       H   1 .. 1024                     1024   workgroups of pass B at most (many tickets per workgroup on a small batch)
 //   per call, elsewhere
 //     AIX_DISTINCT_PIECE           H   1 .. 2^31                     2^30   windows per K1 piece (aix_merge.hip entry points, aix_count.hip, aix_ingest.hip)
 //     AIX_POSITIONS_PIECE          H   1 .. 2^31                     2^30   windows per piece of the positions fill (aix_positions.hip)

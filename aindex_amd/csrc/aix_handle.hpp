@@ -193,7 +193,7 @@ __attribute__((visibility("hidden"))) void free_host_pipe(struct HostPipe* p);
 // AIX_LB_NOT_TAKEN: not a candidate (mode, index, switches, batch size) or no workspace, the caller runs the direct path; < 0: error.
 #define AIX_LB_NOT_TAKEN 0
 #define AIX_LB_TAKEN 1
-static constexpr uint64_t AIX_LB_DEFAULT_MIN = 1ull << 25;      // AIX_LOOKUP_BINNED_MIN (profiles/lookup_binned/README.md)
+static constexpr uint64_t AIX_LB_DEFAULT_MIN = 1ull << 24;      // AIX_LOOKUP_BINNED_MIN (profiles/lookup_binned/README.md)
 int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t N, uint32_t* out, hipStream_t s);
 void lookup_binned_release(aix_index* h);       // the caller has switched to the handle's device
 

@@ -11,7 +11,9 @@
 //                 out[i] = 0 for every query. Queries with other bytes, and records whose slice region is full, go onto the
 //                 survivor list instead.
 //   k_lb_filter   pass B: chunks in slice order across the whole grid, so that the chip reads one or two slices (~1 MiB each)
-//                 at a time and every XCD holds them in its L2 (the chunks are handed out in order through ticket counters). A record that passes is appended to the survivor list.
+//                 at a time and every XCD holds them in its L2. The chunks are handed out in order through eight ticket counters,
+//                 four chunks (1024 records) per ticket to a workgroup of 512 threads: ~107 000 returning atomics per 10^8
+//                 queries, 128 workgroups on a counter. A record that passes is appended to the survivor list.
 //   k_lookup23_list (aix_kernels.hip) pass C: the survivors through the ordinary probe.
 // A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the 16 bits of the filter key from which
 // bloom_mask takes all four bit positions: 8 bytes, three bits spare. Pass B therefore lets exactly the filter's positives through
@@ -29,11 +31,16 @@ static constexpr int LB_TILE = LB_TB * LB_QPL;         // 4096 queries per tile:
 static constexpr int LB_CH = 256;                      // records per chunk (2 KiB)
 static constexpr int LB_MAXBINS = 256;
 static constexpr unsigned LB_GRID_A = 768;             // three workgroups of pass A per CU (41 KiB of LDS each)
-static constexpr int LB_FB = 256;                      // threads of pass B: a lane takes one record of each chunk of a trip
-static constexpr int LB_U = 2;                         // chunks per trip of a pass-B workgroup (independent loads)
-static constexpr int LB_TICKETS = 8;                   // pass B hands its chunks out in order through these counters (one per XCD under round-robin dispatch)
-static constexpr int LB_SURV = 4096;                   // survivors a pass-B workgroup collects in LDS before it appends them
-static constexpr unsigned LB_GRID_B = 2048;
+static constexpr int LB_FB = 512;                      // threads of pass B: a lane takes one record of each chunk group of a trip
+static constexpr int LB_CPG = LB_FB / LB_CH;           // chunks per chunk group: one record per lane
+static constexpr int LB_U = 2;                         // chunk groups per trip of a pass-B workgroup (independent loads)
+static constexpr int LB_CPT = LB_U * LB_CPG;           // chunks per ticket = per trip: 1024 records
+static constexpr int LB_TICKETS = 8;                   // pass B hands its tickets out in order through these counters (one per XCD under round-robin dispatch)
+static constexpr int LB_SURV = 4096;                   // survivors a pass-B workgroup can hold in LDS
+static constexpr int LB_FLUSH_AT = LB_SURV - LB_U * LB_FB;   // it appends them once it holds more than this, so that a trip's records always fit
+static constexpr unsigned LB_GRID_B = 1024;            // four workgroups per CU: 1024 * 1024 ~ 10^6 records in flight, one slice's worth
+static_assert(LB_FB % LB_CH == 0 && LB_FB >= LB_MAXBINS && LB_FB % 64 == 0, "pass B scans the slices' chunk counts with one lane per slice");
+static_assert(LB_FLUSH_AT > 0, "LB_SURV holds the flush threshold plus one trip's records");
 static constexpr uint32_t LB_SAMPLES = 16384;
 static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 16;
 static_assert(LB_MASK_BITS == 16 && LB_IDX_BITS + LB_WORD_BITS + LB_MASK_BITS <= 64, "the record holds the 16 bits bloom_mask reads");
@@ -265,7 +272,7 @@ __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict_
     const uint32_t mine = t < NB ? min(w.hdr[LB_CURSOR + t], g.cap) : 0u;
     uint32_t total;
     const uint32_t excl = lb_scan_excl<LB_FB>(mine, wsum, total);
-    pre[t] = excl;
+    if (t < (uint32_t)LB_MAXBINS) pre[t] = excl;
     if (t == 0) { pre[LB_MAXBINS] = total; s_n = 0; }
     __syncthreads();
     auto flush = [&]() {                                         // every lane of the workgroup calls it
@@ -276,41 +283,45 @@ __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict_
         if (t == 0) s_n = 0;
         __syncthreads();
     };
-    // The chunks are handed out in slice order, LB_U at a time: what the grid has in flight is then one contiguous window of
-    // gridDim.x * LB_U chunks (~1 % of the records, so ~1 % of the filter: ~1 MB), however unevenly the workgroups advance. With a
-    // static grid stride the window drifted apart and 60 % of the filter reads missed L2 (profiles/lookup_binned/README.md).
-    const uint32_t lane_x = blockIdx.x % LB_TICKETS;
+    // The chunks are handed out in slice order, a ticket of LB_CPT at a time: what the grid has in flight is then one contiguous
+    // window of gridDim.x * LB_CPT chunks (~1 % of the records, so ~1 % of the filter: ~1 MB), however unevenly the workgroups
+    // advance. With a static grid stride the window drifted apart and 60 % of the filter reads missed L2; a workgroup that holds a
+    // second ticket ahead of the one it filters widens the window too, and lost more than the overlap gained
+    // (profiles/lookup_binned/README.md). Ticket k of counter x = chunks (k * nt + x) * LB_CPT onwards; lane t takes record t % LB_CH
+    // of chunk u * LB_CPG + t / LB_CH of the ticket, u < LB_U. A lane's chunk numbers only ever increase, and so does `bin`.
+    const uint32_t nt = min(gridDim.x, (uint32_t)LB_TICKETS);   // counters in use: each of them has a workgroup that pulls on it
+    const uint32_t lane_x = blockIdx.x % nt;
     uint32_t* const ticket = w.hdr + LB_TICKET + 32 * lane_x;
     uint32_t bin = 0;
     for (;;) {
         if (t == 0) s_ticket = atomicAdd(ticket, 1u);
         __syncthreads();
-        const uint64_t it64 = ((uint64_t)s_ticket * LB_TICKETS + lane_x) * LB_U;
+        const uint64_t it64 = ((uint64_t)s_ticket * nt + lane_x) * LB_CPT;
         if (it64 >= total) break;
         const uint32_t it = (uint32_t)it64;
         uint64_t r[LB_U], wd[LB_U];
         uint32_t cn[LB_U], wbase[LB_U];
 #pragma unroll
         for (int u = 0; u < LB_U; ++u) {
-            const uint32_t item = it + u;
+            const uint32_t item = it + u * LB_CPG + t / LB_CH;
             cn[u] = 0; r[u] = 0; wbase[u] = 0;
             if (item < total) {
                 while (bin + 1 < NB && item >= pre[bin + 1]) ++bin;
                 const uint64_t ch = (uint64_t)bin * g.cap + (item - pre[bin]);
                 cn[u] = w.cnt[ch];
-                r[u] = __builtin_nontemporal_load(&w.rec[ch * LB_CH + t]);   // streamed once: keep the slice in L2
+                r[u] = __builtin_nontemporal_load(&w.rec[ch * LB_CH + t % LB_CH]);   // streamed once: keep the slice in L2
                 wbase[u] = bin * g.wps;
             }
         }
 #pragma unroll
         for (int u = 0; u < LB_U; ++u) {
             const uint32_t word = wbase[u] + ((uint32_t)(r[u] >> LB_IDX_BITS) & ((1u << LB_WORD_BITS) - 1));
-            wd[u] = (t < cn[u] && word < nbloom) ? bloom[word] : 0ull;
+            wd[u] = (t % LB_CH < cn[u] && word < nbloom) ? bloom[word] : 0ull;
         }
 #pragma unroll
         for (int u = 0; u < LB_U; ++u) {
             const uint64_t mk = bloom_mask((uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));   // all four positions: the low LB_MASK_BITS bits
-            const bool pass = t < cn[u] && (wd[u] & mk) == mk;
+            const bool pass = t % LB_CH < cn[u] && (wd[u] & mk) == mk;
             const uint64_t m = __ballot(pass);
             if (m) {
                 uint32_t r0 = 0;
@@ -320,7 +331,7 @@ __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict_
             }
         }
         __syncthreads();
-        if (s_n > (uint32_t)(LB_SURV - LB_U * LB_FB)) flush();
+        if (s_n > (uint32_t)LB_FLUSH_AT) flush();
     }
     if (s_n) flush();
 }
@@ -387,7 +398,8 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     w.cnt = (uint32_t*)(base + off_cnt);
     w.rec = (uint64_t*)(base + off_rec);
     w.stats = (unsigned long long*)h->lb_stats;
-    const unsigned grid_b = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)g.nbins * cap + LB_U - 1) / LB_U, 1), LB_GRID_B);
+    const uint64_t test_grid_b = env_u64("AIX_LOOKUP_TEST_GRID_B", 1, LB_GRID_B, LB_GRID_B);   // fewer workgroups: many tickets each on a small batch
+    const unsigned grid_b = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)g.nbins * cap + LB_CPT - 1) / LB_CPT, 1), test_grid_b);
     for (uint64_t lo = 0; lo < N; lo += piece) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(piece, N - lo);
         const uint8_t* qp = q + 23 * lo;
