@@ -470,6 +470,49 @@ class AIndex:
         """[(extension, stop_name)] along the best continuation of every 23-mer, one GPU call per direction; see AindexWrapper.extend_batch."""
         return self._wrapper.extend_batch(kmers, max_steps, cutoff, mode, direction)
 
+    # ---- De Bruijn compaction (Index.unitigs; aix_unitigs.hip) -----------------------------------------
+    def get_unitigs(self, cutoff: int = 0, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
+        """[(sequence, tf_sum, circular)] of every maximal unitig with at least min_kmers k-mers, in unitig order (ascending first k-mer)."""
+        self._req()
+        u = self._wrapper._need23().unitigs(cutoff)
+        off, text = u["offsets"].tolist(), u["bases"].tobytes().decode("ascii")
+        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(u["tf_sum"].tolist(), u["circular"].tolist()))
+                if off[i + 1] - off[i] - 22 >= min_kmers]
+
+    def get_unitig_of_kmers(self, kmers, cutoff: int = 0) -> List[Optional[Tuple[int, int, int]]]:
+        """[(unitig, pos, strand)] per 23-mer through the kid lookup: the k-mer occupies bases [pos, pos + 23) of that unitig, as given
+        (strand 0) or as its reverse complement (strand 1). None for an item that is not 23 characters, absent from the index, or dead."""
+        self._req()
+        import torch
+        ix = self._wrapper._need23()
+        flat, keep = self._wrapper._split_fixed(kmers, 23)
+        out: List[Optional[Tuple[int, int, int]]] = [None] * len(kmers)
+        if keep.shape[0] == 0:
+            return out
+        kid, strand = ix.kid_strand_ascii(flat)
+        ku, kp, kf = ix.unitigs_layout_t(cutoff)[:3]
+        at = torch.from_numpy(np.where(strand != 0, kid, 0).astype(np.int64)).to(ku.device)
+        ku, kp, kf = (t[at].cpu().numpy() for t in (ku, kp, kf))
+        for j, i in enumerate(keep.tolist()):
+            if strand[j] != 0 and ku[j] != -1:
+                out[i] = (int(ku[j]), int(kp[j]), int(kf[j] & 1) ^ int(strand[j] == 2))
+        return out
+
+    def write_unitigs(self, path: str, cutoff: int = 0, min_kmers: int = 1) -> int:
+        """FASTA of get_unitigs: >u{id} LN:i:{len} KC:i:{tf_sum} km:f:{tf_sum/m:.1f}[ circular]; returns the number of records written."""
+        self._req()
+        u = self._wrapper._need23().unitigs(cutoff)
+        off, text = u["offsets"].tolist(), u["bases"].tobytes().decode("ascii")
+        written = 0
+        with open(path, "w") as f:
+            for i, (s, c) in enumerate(zip(u["tf_sum"].tolist(), u["circular"].tolist())):
+                ln = off[i + 1] - off[i]
+                if ln - 22 < min_kmers:
+                    continue
+                f.write(f">u{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
+                written += 1
+        return written
+
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):
         """(corrected reads, records): every read's weak 23-windows (tf <= true_errors, read.hpp:296) are looked for, up to max_fixes

@@ -1,5 +1,5 @@
 // aix_probe.hpp — private: the probe of the batch kernels (verification table, side index, unfiled keys, MPHF fallback) and the
-// absence-filter gauge, shared by the translation units whose kernels look 23-mers up (aix_kernels.hip, aix_debruijn.hip).
+// absence-filter gauge, shared by the translation units whose kernels look 23-mers up (aix_kernels.hip, aix_debruijn.hip, aix_unitigs.hip).
 #pragma once
 #include "aix_internal.hpp"
 
@@ -112,6 +112,16 @@ __device__ __forceinline__ uint32_t freq23_wave(const IndexDev& ix, bool want, u
     const Probe g = probe23_wave<8>(ix, want && !f.found, w0, w1, w2, r, true, absence);
     found = f.found || g.found;
     return f.found ? f.tf : (g.found ? g.tf : 0u);
+}
+
+// The sibling of freq23_wave<true> that also says WHERE the key is stored: the probe of min(u, revcomp u), whose `slot` is the kid of a
+// found key (key_at(ix, slot).code is that canonical code). Wave-cooperative like freq23_wave; the compaction (aix_unitigs.hip) links
+// k-mers to their neighbours through it.
+__device__ __forceinline__ Probe slot23_wave(const IndexDev& ix, bool want, uint64_t u, bool absence) {
+    const uint64_t r = revcomp(u, 23);
+    uint64_t w0, w1, w2;
+    ascii23_of_rc(u <= r ? r : u, w0, w1, w2);                   // string of min(u, r)
+    return probe23_wave<8>(ix, want, w0, w1, w2, u <= r ? u : r, true, absence);
 }
 
 // The absence filter pays when most probes are absent keys (one cached 8-byte read instead of a 128-byte line from HBM) and

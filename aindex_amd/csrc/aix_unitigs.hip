@@ -1,0 +1,609 @@
+// aix_unitigs.hip — De Bruijn compaction: every maximal non-branching path (unitig) of a canonical 23-mer index resident in HBM, once,
+// with its abundance, and the map from every stored k-mer to its unitig, offset and strand. The contract is stated above the
+// declarations in include/aindex_hip.h; DESIGN 5i has the derivations and the resources.
+//
+// A node (stored key) has two ports: 2 kid + 0 = R (leaving in stored orientation), 2 kid + 1 = L (leaving as the reverse complement).
+// The chain (one plain launch per step and per round; every host loop is bounded by a count computed on the host):
+//   ports    k_ug_ports: one quad per port, the four lanes probe next(x, b) through the wave-cooperative probe with slots
+//            (slot23_wave, aix_probe.hpp); one u32 word per port = the entered port of the only live successor, or a code for
+//            "out-degree 0 / 2 / 3 / 4" or "dead node"
+//   links    k_ug_links: port p is linked to t = word[p] iff word[t] == p (so both out-degrees are 1, and links are symmetric by
+//            construction) and t is a port of another node (self-loops and hairpins are cut). Ranking state: succ(p) = t ^ 1, d = 1;
+//            a port without a link is a terminal: d = 0 and an explicit flag (bit 63). A fixed point of succ is NOT the test.
+//   rank     k_ug_jump: synchronous pointer jumping, double-buffered: an unflagged port takes over end, flag and distance of the port
+//            it points at. After round r every port within 2^(r - 1) hops of its end is flagged; the host reads the number of unflagged
+//            ports after every round and stops when it is 0 or did not change (what is left then lies on cycles).
+//   cycles   only when ports are left: k_ug_cyc_init / k_ug_cyc_jump carry the minimum of (stored code, port bit) over a window of 2^r
+//            successors and the distance to its first occurrence. Of the two directed port cycles of a circle the one through the R port
+//            of the smallest node is kept; the position of a node is the distance its OTHER port has to that node in the opposite cycle.
+//   place    k_ug_place: per live node the spelling (smaller first oriented k-mer), position and strand; the nodes at position 0 are the
+//            starts. rocPRIM sorts the starts by first code = the unitig ids; k_ug_ids / k_ug_assign hand every node its id.
+//   emit     k_ug_check validates the layout against the index; rocPRIM sorts the live nodes by (unitig, position), which IS unitig
+//            order: k_ug_emit writes offsets, bases, the circular flag and tf along every unitig; tf_sum / min / max come from one
+//            reduce-by-key over that array (no atomic on a per-unitig word).
+// Integer only, no LDS, no grid-wide barrier, no spin-wait. Every index derived from 2 n, from an offset or from the total is 64 bits wide.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include <rocprim/rocprim.hpp>
+
+#include "aix_env.hpp"
+#include "aix_handle.hpp"
+#include "aix_probe.hpp"
+
+namespace aix {
+
+static constexpr int kUB = 256;                                   // four waves = 64 quads per workgroup
+static constexpr uint64_t kMask46 = (1ULL << 46) - 1;
+static constexpr uint32_t kWNone = 0xFFFFFFF8u;                   // port words from here on: no single live successor; + the out-degree (0, 2, 3, 4)
+static constexpr uint32_t kWDead = kWNone + 7u;                   // the node itself is dead
+static constexpr uint64_t kFlag = 1ULL << 63;                     // ranking state: nx | (d | terminal flag << 31) << 32
+static constexpr uint64_t kCycMark = 1ULL << 63;                  // kid_unitig between k_ug_place and k_ug_assign: this bit + the first code of the circle
+
+struct UgCounters {                                               // one zeroed record per call
+    unsigned long long n_live, n_circular, n_starts, bad, max_pos;
+    unsigned long long unflagged[66];                             // [0] after k_ug_links, [r] after round r
+};
+
+static inline unsigned ug_grid(uint64_t work, uint64_t per_block) {
+    uint64_t b = (work + per_block - 1) / per_block;
+    if (b > 4096) b = 4096;                                        // grid-stride: a few atomics per workgroup, not per wave of work
+    if (b == 0) b = 1;
+    return (unsigned)b;
+}
+
+template <int J>
+__device__ __forceinline__ uint32_t ug_quad_bcast(uint32_t v) {   // lane J of the quad to its four lanes (DPP quad_perm [J, J, J, J]); all lanes active
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xf, 0xf, false);
+}
+
+__device__ __forceinline__ unsigned long long ug_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+__device__ __forceinline__ unsigned long long ug_wave_max(unsigned long long v) {
+#pragma unroll
+    for (int s = 32; s; s >>= 1) { const unsigned long long o = __shfl_xor(v, s); v = o > v ? o : v; }
+    return v;
+}
+
+// the oriented k-mer that leaves node `code` through `port`
+__device__ __forceinline__ uint64_t ug_orient(uint64_t code, uint32_t port) { return (port & 1u) ? revcomp(code, 23) : code; }
+
+// ---------------------------------------------------------------------------------------------
+// 1. ports
+// ---------------------------------------------------------------------------------------------
+// One quad per (kid, port), 16 per wave, as k_db_neighbours lays its records out. policy: 0 = FilterGauge, 1 = filter always, 2 = never.
+__global__ void __launch_bounds__(kUB) k_ug_ports(const IndexDev ix_, uint32_t cutoff, int policy, uint32_t* __restrict__ word) {
+    const IndexDev& ix = ix_;
+    const uint64_t NP = 2 * ix.n;
+    const uint32_t lane = threadIdx.x & 63u, b = lane & 3u;
+    FilterGauge fg;
+    const uint64_t stride = (uint64_t)gridDim.x * 64;
+    for (uint64_t base = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 6) * 16; base < NP; base += stride) {    // wave-uniform
+        const uint64_t p = base + (lane >> 2);
+        const bool in = p < NP;
+        KeyRec k;
+        k.code = 0; k.tf = 0;
+        if (in) k = key_at(ix, p >> 1);
+        const bool live = in && k.tf > cutoff;
+        const uint64_t x = ug_orient(k.code & kMask46, (uint32_t)p);
+        const uint64_t y = ((x << 2) | (uint64_t)b) & kMask46;     // next(x, b)
+        const bool absence = policy == 1 ? true : (policy == 2 ? false : fg.on);
+        const Probe q = slot23_wave(ix, live, y, absence);
+        if (policy == 0) fg.seen(live, q.found);
+        const bool ylive = live && q.found && q.tf > cutoff && q.slot < ix.n;
+        // stored orientation: the successor is entered through its L port and left through R
+        const uint32_t ent = 2u * (uint32_t)q.slot + (y <= revcomp(y, 23) ? 1u : 0u);
+        const uint32_t l0 = ug_quad_bcast<0>(ylive), l1 = ug_quad_bcast<1>(ylive), l2 = ug_quad_bcast<2>(ylive), l3 = ug_quad_bcast<3>(ylive);
+        const uint32_t e0 = ug_quad_bcast<0>(ent), e1 = ug_quad_bcast<1>(ent), e2 = ug_quad_bcast<2>(ent), e3 = ug_quad_bcast<3>(ent);
+        const uint32_t deg = l0 + l1 + l2 + l3;
+        const uint32_t e = l0 ? e0 : (l1 ? e1 : (l2 ? e2 : e3));
+        if (in && b == 0) word[p] = !live ? kWDead : (deg == 1 ? e : kWNone + deg);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 2. links and 3. ranking
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ug_count(unsigned long long mine, unsigned long long* dst) {
+    const unsigned long long s = ug_wave_sum(mine);
+    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
+}
+
+__global__ void __launch_bounds__(kUB) k_ug_links(const uint32_t* __restrict__ word, uint64_t NP, uint64_t* __restrict__ st, unsigned long long* __restrict__ unflagged) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    unsigned long long open = 0;
+    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+        const uint32_t t = word[p];
+        bool linked = false;
+        if (t < kWNone && (uint64_t)t < NP) linked = (uint64_t)word[t] == p && (t >> 1) != (uint32_t)(p >> 1);
+        st[p] = linked ? ((uint64_t)(t ^ 1u) | (1ULL << 32)) : (p | kFlag);
+        open += linked;
+    }
+    ug_count(open, unflagged);
+}
+
+__global__ void __launch_bounds__(kUB) k_ug_jump(const uint64_t* __restrict__ in, uint64_t NP, uint64_t* __restrict__ out, unsigned long long* __restrict__ unflagged) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    unsigned long long open = 0;
+    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+        uint64_t s = in[p];
+        if (!(s & kFlag)) {
+            const uint64_t q = in[(uint32_t)s];
+            // on a cycle d doubles every round and means nothing: it is kept below the flag bit
+            const uint64_t d = (((s >> 32) & 0x7FFFFFFFu) + ((q >> 32) & 0x7FFFFFFFu)) & 0x7FFFFFFFu;
+            s = (q & (kFlag | 0xFFFFFFFFull)) | (d << 32);
+            open += !(s & kFlag);
+        }
+        out[p] = s;
+    }
+    ug_count(open, unflagged);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 4. cycles: state a = nx | md << 32 and key = stored code << 1 | port bit, for the unflagged ports only
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kUB) k_ug_cyc_init(const IndexDev ix_, const uint64_t* __restrict__ rank, const uint32_t* __restrict__ word, uint64_t NP,
+                                                    uint64_t* __restrict__ a, uint64_t* __restrict__ key) {
+    const IndexDev& ix = ix_;
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+        if (rank[p] & kFlag) continue;
+        a[p] = (uint64_t)(word[p] ^ 1u);                           // an unflagged port is linked: its word is its link
+        key[p] = ((key_at(ix, p >> 1).code & kMask46) << 1) | (p & 1);
+    }
+}
+
+__global__ void __launch_bounds__(kUB) k_ug_cyc_jump(const uint64_t* __restrict__ rank, uint64_t NP, uint64_t span, const uint64_t* __restrict__ a_in,
+                                                    const uint64_t* __restrict__ k_in, uint64_t* __restrict__ a_out, uint64_t* __restrict__ k_out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+        if (rank[p] & kFlag) continue;
+        const uint64_t a = a_in[p];
+        uint64_t k = k_in[p], md = a >> 32;
+        const uint32_t q = (uint32_t)a;
+        const uint64_t aq = a_in[q], kq = k_in[q];
+        if (kq < k) { k = kq; md = span + (aq >> 32); }            // strictly smaller: the first occurrence stays. md < the cycle's length
+        a_out[p] = (aq & 0xFFFFFFFFull) | (md << 32);
+        k_out[p] = k;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 5. layout
+// ---------------------------------------------------------------------------------------------
+// Per kid. Path node: both ports are flagged; spelling A starts at the end reached through L (this node: position dL, stored orientation),
+// spelling B at the end reached through R (position dR, reversed); the first oriented k-mer of a spelling leaves its end node through the
+// port opposite the unlinked one. Circle node: neither port is flagged. kid_unitig holds, until k_ug_assign, the start's kid (path) or
+// kCycMark | first code (circle); a start appends (first code, kid).
+__global__ void __launch_bounds__(kUB) k_ug_place(const IndexDev ix_, uint32_t cutoff, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ cyc_a,
+                                                 const uint64_t* __restrict__ cyc_k, uint64_t* __restrict__ kid_unitig, uint32_t* __restrict__ kid_pos,
+                                                 uint8_t* __restrict__ kid_flag, uint64_t* __restrict__ start_code, uint32_t* __restrict__ start_kid,
+                                                 UgCounters* __restrict__ ctr) {
+    const IndexDev& ix = ix_;
+    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kUB;
+    unsigned long long live = 0, circ = 0;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+        const KeyRec me = key_at(ix, kid);
+        if (!(me.tf > cutoff)) {
+            kid_unitig[kid] = AIX_UNITIG_NONE; kid_pos[kid] = 0; kid_flag[kid] = 0;
+            continue;
+        }
+        ++live;
+        const uint64_t sR = rank[2 * kid], sL = rank[2 * kid + 1];
+        uint32_t pos, flag;
+        uint64_t first, tmp;
+        if ((sR & kFlag) || (sL & kFlag) || !cyc_a) {
+            const uint32_t eR = (uint32_t)sR, eL = (uint32_t)sL;
+            const uint32_t dR = (uint32_t)(sR >> 32) & 0x7FFFFFFFu, dL = (uint32_t)(sL >> 32) & 0x7FFFFFFFu;
+            const uint64_t fa = ug_orient(key_at(ix, eL >> 1).code & kMask46, eL ^ 1u);
+            const uint64_t fb = ug_orient(key_at(ix, eR >> 1).code & kMask46, eR ^ 1u);
+            const bool A = fa < fb;                                // one node: stored code against its reverse complement
+            pos = A ? dL : dR;
+            flag = A ? 0u : 1u;
+            first = A ? fa : fb;
+            tmp = (uint64_t)((A ? eL : eR) >> 1);
+        } else {
+            const uint64_t kR = cyc_k[2 * kid];
+            const bool keepR = (kR & 1) == 0;                      // this node's R port lies on the kept directed cycle
+            pos = (uint32_t)(cyc_a[2 * kid + (keepR ? 1 : 0)] >> 32);
+            flag = (keepR ? 0u : 1u) | 2u;
+            first = kR >> 1;
+            tmp = kCycMark | first;
+            if (pos == 0) ++circ;
+        }
+        kid_pos[kid] = pos;
+        kid_flag[kid] = (uint8_t)flag;
+        if (pos == 0) {
+            const unsigned long long j = atomicAdd(&ctr->n_starts, 1ull);
+            if (j < n) { start_code[j] = first; start_kid[j] = (uint32_t)kid; }
+        } else {
+            kid_unitig[kid] = tmp;
+        }
+    }
+    ug_count(live, &ctr->n_live);
+    ug_count(circ, &ctr->n_circular);
+}
+
+__global__ void __launch_bounds__(kUB) k_ug_ids(const uint32_t* __restrict__ sorted_kid, uint64_t U, uint64_t n, uint64_t* __restrict__ kid_unitig) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kUB + threadIdx.x; j < U; j += stride) {
+        const uint32_t kid = sorted_kid[j];
+        if (kid < n) kid_unitig[kid] = j;
+    }
+}
+
+// every live node that is not a start reads its id at its start (starts are not written here)
+__global__ void __launch_bounds__(kUB) k_ug_assign(const uint64_t* __restrict__ sorted_code, uint64_t U, uint64_t n, const uint32_t* __restrict__ kid_pos,
+                                                  uint64_t* __restrict__ kid_unitig) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+        if (kid_pos[kid] == 0) continue;                           // dead, or a start
+        const uint64_t t = kid_unitig[kid];
+        uint64_t id;
+        if (t & kCycMark) {                                        // a circle knows its first code, not its start's kid: lower bound in the sorted codes
+            const uint64_t code = t & kMask46;
+            uint64_t lo = 0, hi = U;
+            while (lo < hi) {                                      // at most 64 trips
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (sorted_code[mid] < code) lo = mid + 1; else hi = mid;
+            }
+            id = lo;
+        } else {
+            id = t < n ? kid_unitig[t] : AIX_UNITIG_NONE;
+        }
+        kid_unitig[kid] = id;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 6. emit
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kUB) k_ug_check(const IndexDev ix_, uint32_t cutoff, uint64_t U, const uint64_t* __restrict__ kid_unitig,
+                                                 const uint32_t* __restrict__ kid_pos, UgCounters* __restrict__ ctr) {
+    const IndexDev& ix = ix_;
+    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kUB;
+    unsigned long long live = 0, starts = 0, bad = 0, mx = 0;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+        const uint64_t u = kid_unitig[kid];
+        if (u == AIX_UNITIG_NONE) continue;
+        const uint32_t pos = kid_pos[kid];
+        ++live;
+        starts += pos == 0;
+        bad += u >= U || !(key_at(ix, kid).tf > cutoff);
+        mx = pos > mx ? pos : mx;
+    }
+    ug_count(live, &ctr->n_live);
+    ug_count(starts, &ctr->n_starts);
+    ug_count(bad, &ctr->bad);
+    mx = ug_wave_max(mx);
+    if ((threadIdx.x & 63u) == 0 && mx) atomicMax(&ctr->max_pos, mx);
+}
+
+// sort key of a node: unitig << pos_bits | position; dead nodes behind everything
+__global__ void __launch_bounds__(kUB) k_ug_keys(uint64_t n, uint64_t U, int pos_bits, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
+                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ kids) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+        const uint64_t u = kid_unitig[kid];
+        keys[kid] = u == AIX_UNITIG_NONE ? U << pos_bits : ((u << pos_bits) | kid_pos[kid]);
+        kids[kid] = (uint32_t)kid;
+    }
+}
+
+// Entry j of the sorted nodes is k-mer j in unitig order: its unitig's k-mers start at j - pos, its bases at j - pos + 22 u.
+__global__ void __launch_bounds__(kUB) k_ug_emit(const IndexDev ix_, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ kids, uint64_t n_live, uint64_t U,
+                                                int pos_bits, const uint8_t* __restrict__ kid_flag, uint64_t total, uint64_t* __restrict__ offsets,
+                                                uint8_t* __restrict__ bases, uint8_t* __restrict__ circular, uint32_t* __restrict__ tf_out) {
+    const IndexDev& ix = ix_;
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kUB + threadIdx.x; j < n_live; j += stride) {
+        const uint64_t key = keys[j], u = key >> pos_bits, pos = key & ((1ULL << pos_bits) - 1);
+        const uint32_t kid = kids[j];
+        if (u >= U || pos > j || kid >= ix.n) continue;            // (a layout that k_ug_check accepted never gets here)
+        const KeyRec rec = key_at(ix, kid);
+        const uint32_t flag = kid_flag[kid];
+        tf_out[j] = rec.tf;
+        const uint64_t x = ug_orient(rec.code & kMask46, flag);
+        const uint64_t at = j + 22 * u;                            // the k-mer occupies bases [at, at + 23)
+        if (pos == 0) {
+            offsets[u] = at;
+            circular[u] = (uint8_t)((flag >> 1) & 1u);
+            uint64_t w[3];
+            ascii23_of_rc(revcomp(x, 23), w[0], w[1], w[2]);
+            for (uint32_t c = 0; c < 23; ++c)
+                if (at + c < total) bases[at + c] = (uint8_t)(w[c >> 3] >> (8 * (c & 7)));
+        } else if (at + 22 < total) {
+            bases[at + 22] = (uint8_t)(AIX_LUT_ACGT >> (8 * (uint32_t)(x & 3)));
+        }
+        if (j == 0) offsets[U] = total;
+    }
+}
+
+struct UgAgg {
+    unsigned long long sum;
+    uint32_t mn, mx;
+};
+struct UgAggOp {
+    __host__ __device__ UgAgg operator()(const UgAgg& a, const UgAgg& b) const { return UgAgg{a.sum + b.sum, a.mn < b.mn ? a.mn : b.mn, a.mx > b.mx ? a.mx : b.mx}; }
+};
+struct UgToAgg {
+    __host__ __device__ UgAgg operator()(uint32_t t) const { return UgAgg{t, t, t}; }
+};
+struct UgUnitigOf {
+    int pos_bits;
+    __host__ __device__ uint64_t operator()(uint64_t key) const { return key >> pos_bits; }
+};
+
+__global__ void __launch_bounds__(kUB) k_ug_stats(const uint64_t* __restrict__ uniq, const UgAgg* __restrict__ agg, const uint64_t* __restrict__ count, uint64_t U,
+                                                 uint64_t* __restrict__ tf_sum, uint32_t* __restrict__ tf_min, uint32_t* __restrict__ tf_max) {
+    const uint64_t m = *count < U ? *count : U, stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t i = (uint64_t)blockIdx.x * kUB + threadIdx.x; i < m; i += stride) {
+        const uint64_t u = uniq[i];
+        if (u >= U) continue;
+        const UgAgg a = agg[i];
+        tf_sum[u] = a.sum; tf_min[u] = a.mn; tf_max[u] = a.mx;
+    }
+}
+
+// AIX_DBJ_FILTER (A/B switch): the policy of the walks (aix_debruijn.hip), whose probes these are: found keys nearly always
+static inline int ug_policy() { return (int)env_int("AIX_DBJ_FILTER", 0, 2, 2); }
+
+static inline int ug_ceil_log2(uint64_t v) {                      // smallest r with 2^r >= v
+    int r = 0;
+    while (r < 64 && (1ULL << r) < v) ++r;
+    return r;
+}
+static inline int ug_bit_length(uint64_t v) {
+    int r = 0;
+    while (v) { ++r; v >>= 1; }
+    return r;
+}
+
+#define UG(expr)                                 \
+    do {                                         \
+        const hipError_t e_ = (expr);            \
+        if (e_ != hipSuccess) return e_;         \
+    } while (0)
+#define UGL(...)                                 \
+    do {                                         \
+        hipLaunchKernelGGL(__VA_ARGS__);         \
+        UG(hipGetLastError());                   \
+    } while (0)
+
+static hipError_t ug_read(UgCounters* host, const UgCounters* dev, hipStream_t s) {
+    UG(hipMemcpyAsync(host, dev, sizeof(UgCounters), hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
+}
+
+// Outputs of the layout call. Synchronises `s`.
+static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_unitig, uint32_t* kid_pos, uint8_t* kid_flag, uint64_t out[4], hipStream_t s) {
+    const IndexDev ix = h->dev();
+    const uint64_t n = ix.n, NP = 2 * n;
+    const dim3 blk(kUB);
+    DevArr ctr_a(s), word(s), r0(s), r1(s), ca0(s), ck0(s), ca1(s), ck1(s), sc(s), sk(s), sc2(s), sk2(s), tmp(s);
+    UG(ctr_a.alloc(sizeof(UgCounters)));
+    UG(word.alloc(4 * NP));
+    UG(r0.alloc(8 * NP));
+    UG(r1.alloc(8 * NP));
+    UgCounters* ctr = (UgCounters*)ctr_a.p;
+    UgCounters hc;
+    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    UGL(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, 65536)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
+    UGL(k_ug_links, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
+    UG(ug_read(&hc, ctr, s));
+    uint64_t *cur = (uint64_t*)r0.p, *oth = (uint64_t*)r1.p;
+    uint64_t open = hc.unflagged[0];
+    const int max_rounds = std::min(64, ug_ceil_log2(n) + 1);
+    for (int r = 1; r <= max_rounds && open; ++r) {
+        UGL(k_ug_jump, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
+        UG(ug_read(&hc, ctr, s));
+        std::swap(cur, oth);
+        const bool same = hc.unflagged[r] == open;
+        open = hc.unflagged[r];
+        if (same) break;                                           // only cycle ports are left
+    }
+    (oth == (uint64_t*)r0.p ? r0 : r1).drop();
+    const uint64_t *cyc_a = nullptr, *cyc_k = nullptr;
+    if (open) {
+        UG(ca0.alloc(8 * NP));
+        UG(ck0.alloc(8 * NP));
+        UG(ca1.alloc(8 * NP));
+        UG(ck1.alloc(8 * NP));
+        uint64_t *a = (uint64_t*)ca0.p, *k = (uint64_t*)ck0.p, *a2 = (uint64_t*)ca1.p, *k2 = (uint64_t*)ck1.p;
+        UGL(k_ug_cyc_init, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, ix, (const uint64_t*)cur, (const uint32_t*)word.p, NP, a, k);
+        const int rounds = std::min(64, ug_ceil_log2(open) + 1);
+        for (int r = 1; r <= rounds; ++r) {
+            UGL(k_ug_cyc_jump, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint64_t*)cur, NP, r <= 63 ? 1ULL << (r - 1) : 0ULL, (const uint64_t*)a,
+                (const uint64_t*)k, a2, k2);
+            std::swap(a, a2);
+            std::swap(k, k2);
+        }
+        cyc_a = a; cyc_k = k;
+        UG(hipStreamSynchronize(s));
+        (a2 == (uint64_t*)ca0.p ? ca0 : ca1).drop();
+        (k2 == (uint64_t*)ck0.p ? ck0 : ck1).drop();
+    }
+    word.drop();
+    UG(sc.alloc(8 * n));
+    UG(sk.alloc(4 * n));
+    UGL(k_ug_place, dim3(ug_grid(n, 2 * kUB)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
+        (uint32_t*)sk.p, ctr);
+    UG(ug_read(&hc, ctr, s));
+    const uint64_t U = std::min<uint64_t>(hc.n_starts, n);
+    if (U) {
+        UG(sc2.alloc(8 * U));
+        UG(sk2.alloc(4 * U));
+        size_t tb = 0;
+        UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
+        UG(tmp.alloc(tb ? tb : 1));
+        UG(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
+        UGL(k_ug_ids, dim3(ug_grid(U, 4 * kUB)), blk, 0, s, (const uint32_t*)sk2.p, U, n, kid_unitig);
+        UGL(k_ug_assign, dim3(ug_grid(n, 4 * kUB)), blk, 0, s, (const uint64_t*)sc2.p, U, n, (const uint32_t*)kid_pos, kid_unitig);
+    }
+    out[0] = U;
+    out[1] = hc.n_live + 22 * U;
+    out[2] = hc.n_live;
+    out[3] = hc.n_circular;
+    return hipStreamSynchronize(s);
+}
+
+// *bad: the layout does not belong to (index, cutoff, U); nothing was written then. Synchronises `s`.
+static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* kid_unitig, const uint32_t* kid_pos, const uint8_t* kid_flag, uint64_t U,
+                          uint64_t* offsets, uint8_t* bases, uint8_t* circular, uint64_t* tf_sum, uint32_t* tf_min, uint32_t* tf_max, uint32_t* kmer_tf, bool* bad,
+                          hipStream_t s) {
+    const IndexDev ix = h->dev();
+    const uint64_t n = ix.n;
+    const dim3 blk(kUB);
+    *bad = false;
+    DevArr ctr_a(s), keys(s), kids(s), keys2(s), kids2(s), tmp(s), tfs(s), uniq(s), agg(s), cnt(s), tmp2(s);
+    UG(ctr_a.alloc(sizeof(UgCounters)));
+    UgCounters* ctr = (UgCounters*)ctr_a.p;
+    UgCounters hc;
+    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
+    UG(ug_read(&hc, ctr, s));
+    if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
+    const uint64_t n_live = hc.n_live, total = n_live + 22 * U;
+    if (U == 0) {
+        UG(hipMemsetAsync(offsets, 0, 8, s));
+        return hipStreamSynchronize(s);
+    }
+    const int pos_bits = ug_bit_length(hc.max_pos), end_bit = pos_bits + ug_bit_length(U);
+    UG(keys.alloc(8 * n));
+    UG(kids.alloc(4 * n));
+    UG(keys2.alloc(8 * n));
+    UG(kids2.alloc(4 * n));
+    UGL(k_ug_keys, dim3(ug_grid(n, 4 * kUB)), blk, 0, s, n, U, pos_bits, kid_unitig, kid_pos, (uint64_t*)keys.p, (uint32_t*)kids.p);
+    size_t tb = 0;
+    UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, (size_t)n, 0u,
+                                 (unsigned)end_bit, s));
+    UG(tmp.alloc(tb ? tb : 1));
+    UG(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, (size_t)n, 0u,
+                                 (unsigned)end_bit, s));
+    UG(hipStreamSynchronize(s));
+    keys.drop();
+    kids.drop();
+    uint32_t* tf_seq = kmer_tf;
+    if (!tf_seq) {
+        UG(tfs.alloc(4 * n_live));
+        tf_seq = (uint32_t*)tfs.p;
+    }
+    UGL(k_ug_emit, dim3(ug_grid(n_live, 2 * kUB)), blk, 0, s, ix, (const uint64_t*)keys2.p, (const uint32_t*)kids2.p, n_live, U, pos_bits, kid_flag, total, offsets,
+        bases, circular, tf_seq);
+    UG(uniq.alloc(8 * U));
+    UG(agg.alloc(sizeof(UgAgg) * U));
+    UG(cnt.alloc(8));
+    auto kin = rocprim::make_transform_iterator((const uint64_t*)keys2.p, UgUnitigOf{pos_bits});
+    auto vin = rocprim::make_transform_iterator((const uint32_t*)tf_seq, UgToAgg());
+    tb = 0;
+    UG(rocprim::reduce_by_key(nullptr, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
+    UG(tmp2.alloc(tb ? tb : 1));
+    UG(rocprim::reduce_by_key(tmp2.p, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
+    UGL(k_ug_stats, dim3(ug_grid(U, 4 * kUB)), blk, 0, s, (const uint64_t*)uniq.p, (const UgAgg*)agg.p, (const uint64_t*)cnt.p, U, tf_sum, tf_min, tf_max);
+    return hipStreamSynchronize(s);
+}
+
+}  // namespace aix
+
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+#define UGCHK(expr)                                                                              \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
+        if (_e != hipSuccess) {                                                                  \
+            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
+            return AIX_ERR_HIP;                                                                  \
+        }                                                                                        \
+    } while (0)
+
+// the refusals every entry point shares, decided before anything is allocated or launched
+static int ug_check_handle(const aix_index_t* h) {
+    if (!h) return AIX_ERR_ARG;
+    if (h->k != 23) return AIX_ERR_MODE;
+    if (!h->canonical_only) return AIX_ERR_UNSUPPORTED;          // freq(x) != freq(rc x): the graph is not strand-symmetric
+    if (h->n == 0) return AIX_ERR_UNSUPPORTED;
+    if (2 * h->n > (uint64_t)kWNone) return AIX_ERR_UNSUPPORTED;  // a port (2 kid + port) must fit its u32 word below the codes
+    return AIX_OK;
+}
+
+extern "C" int aix_unitigs_layout_dev(aix_index_t* h, uint32_t cutoff, uint64_t* d_kid_unitig, uint32_t* d_kid_pos, uint8_t* d_kid_flag, uint64_t* n_unitigs_out,
+                                      uint64_t* total_bases_out, uint64_t* n_live_out, uint64_t* n_circular_out, void* stream) {
+    const int st = ug_check_handle(h);
+    if (st) return st;
+    if (!d_kid_unitig || !d_kid_pos || !d_kid_flag || !n_unitigs_out || !total_bases_out || !n_live_out || !n_circular_out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    uint64_t out[4] = {0, 0, 0, 0};
+    UGCHK(ug_layout(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, out, (hipStream_t)stream));
+    *n_unitigs_out = out[0]; *total_bases_out = out[1]; *n_live_out = out[2]; *n_circular_out = out[3];
+    return AIX_OK;
+}
+
+extern "C" int aix_unitigs_emit_dev(aix_index_t* h, uint32_t cutoff, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag, uint64_t U,
+                                    uint64_t* d_offsets, uint8_t* d_bases, uint8_t* d_circular, uint64_t* d_tf_sum, uint32_t* d_tf_min, uint32_t* d_tf_max,
+                                    uint32_t* d_kmer_tf, void* stream) {
+    const int st = ug_check_handle(h);
+    if (st) return st;
+    if (!d_kid_unitig || !d_kid_pos || !d_kid_flag || !d_offsets) return AIX_ERR_ARG;
+    if (U && (!d_bases || !d_circular || !d_tf_sum || !d_tf_min || !d_tf_max)) return AIX_ERR_ARG;
+    if (U > h->n) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    bool bad = false;
+    UGCHK(ug_emit(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_bases, d_circular, d_tf_sum, d_tf_min, d_tf_max, d_kmer_tf, &bad,
+                  (hipStream_t)stream));
+    return bad ? AIX_ERR_ARG : AIX_OK;
+}
+
+extern "C" int aix_unitigs(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, uint64_t** offsets_out, uint8_t** bases_out, uint8_t** circular_out,
+                           uint64_t** tf_sum_out, uint32_t** tf_min_out, uint32_t** tf_max_out, uint32_t** kmer_tf_out, uint64_t** kid_unitig_out,
+                           uint32_t** kid_pos_out, uint8_t** kid_flag_out) {
+    const int st = ug_check_handle(h);
+    if (st) return st;
+    if (!n_unitigs_out || !offsets_out || !bases_out || !circular_out || !tf_sum_out || !tf_min_out || !tf_max_out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    const uint64_t n = h->n;
+    DevArr ku, kp, kf, off, bs, ci, ts, tn, tx, kt;
+    UGCHK(ku.alloc(8 * n));
+    UGCHK(kp.alloc(4 * n));
+    UGCHK(kf.alloc(n));
+    uint64_t U = 0, total = 0, n_live = 0, n_circ = 0;
+    int r = aix_unitigs_layout_dev(h, cutoff, (uint64_t*)ku.p, (uint32_t*)kp.p, (uint8_t*)kf.p, &U, &total, &n_live, &n_circ, nullptr);
+    if (r) return r;
+    UGCHK(off.alloc(8 * (U + 1)));
+    UGCHK(bs.alloc(total));
+    UGCHK(ci.alloc(U));
+    UGCHK(ts.alloc(8 * U));
+    UGCHK(tn.alloc(4 * U));
+    UGCHK(tx.alloc(4 * U));
+    if (kmer_tf_out) UGCHK(kt.alloc(4 * n_live));
+    r = aix_unitigs_emit_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (uint64_t*)off.p, (uint8_t*)bs.p, (uint8_t*)ci.p,
+                             (uint64_t*)ts.p, (uint32_t*)tn.p, (uint32_t*)tx.p, kmer_tf_out ? (uint32_t*)kt.p : nullptr, nullptr);
+    if (r) return r;
+    // host copies: {destination, device block, bytes}; a NULL destination is an output the caller did not ask for
+    struct Out { void** dst; const void* src; uint64_t bytes; } outs[] = {
+        {(void**)offsets_out, off.p, 8 * (U + 1)}, {(void**)bases_out, bs.p, total}, {(void**)circular_out, ci.p, U}, {(void**)tf_sum_out, ts.p, 8 * U},
+        {(void**)tf_min_out, tn.p, 4 * U}, {(void**)tf_max_out, tx.p, 4 * U}, {(void**)kmer_tf_out, kt.p, 4 * n_live}, {(void**)kid_unitig_out, ku.p, 8 * n},
+        {(void**)kid_pos_out, kp.p, 4 * n}, {(void**)kid_flag_out, kf.p, n}};
+    void* host[10] = {nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 10 && e == hipSuccess; ++i) {
+        if (!outs[i].dst) continue;
+        host[i] = malloc(outs[i].bytes ? outs[i].bytes : 1);
+        if (!host[i]) e = hipErrorOutOfMemory;
+        else if (outs[i].bytes) e = hipMemcpy(host[i], outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) {
+        for (void* p : host) free(p);
+        UGCHK(e);
+    }
+    for (int i = 0; i < 10; ++i)
+        if (outs[i].dst) *outs[i].dst = host[i];
+    *n_unitigs_out = U;
+    return AIX_OK;
+}

@@ -788,6 +788,64 @@ class Index:
                                      _stream_ptr(self.device)), "aix_walk_dev")
         return bases_t, length, stop, tf_t, last
 
+    # ---- De Bruijn compaction (aix_unitigs.hip) ---------------------------------------------------
+    UNITIG_KEYS = ("offsets", "bases", "circular", "tf_sum", "tf_min", "tf_max", "kmer_tf", "kid_unitig", "kid_pos", "kid_flag")
+
+    def unitigs_layout_t(self, cutoff: int = 0):
+        """The graph analysed once: (kid_unitig int64[n], kid_pos int32[n], kid_flag uint8[n], U, total_bases, n_live, n_circular) — device
+        tensors (u64 / u32 bit patterns; a dead kid holds -1 = AIX_UNITIG_NONE, 0, 0) and ints. Complete on return."""
+        import torch
+        dev = f"cuda:{self.device}"
+        ku = torch.empty(self.n, dtype=torch.int64, device=dev)
+        kp = torch.empty(self.n, dtype=torch.int32, device=dev)
+        kf = torch.empty(self.n, dtype=torch.uint8, device=dev)
+        u, total, live, circ = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        with torch.cuda.device(self.device):
+            check(lib().aix_unitigs_layout_dev(self._h, cutoff, vp(ku.data_ptr()), vp(kp.data_ptr()), vp(kf.data_ptr()), C.byref(u), C.byref(total),
+                                               C.byref(live), C.byref(circ), _stream_ptr(self.device)), "aix_unitigs_layout_dev")
+        return ku, kp, kf, u.value, total.value, live.value, circ.value
+
+    def unitigs_t(self, cutoff: int = 0, want_kmer_tf: bool = False, layout=None) -> dict:
+        """All maximal unitigs at `cutoff` as a dict of device tensors (u64 / u32 bit patterns): offsets int64[U + 1], bases uint8[offsets[U]],
+        circular uint8[U], tf_sum int64[U], tf_min / tf_max int32[U], kmer_tf int32[n_live] | None (k-mer j of unitig u at
+        offsets[u] - 22 u + j), the three per-kid arrays, and the ints U, n_live, n_circular. layout: what unitigs_layout_t(cutoff) returned."""
+        import torch
+        ku, kp, kf, u, total, live, circ = layout if layout is not None else self.unitigs_layout_t(cutoff)
+        for t in (ku, kp, kf):
+            self._chk_dev(t)
+        dev = ku.device
+        out = {"offsets": torch.empty(u + 1, dtype=torch.int64, device=dev), "bases": torch.empty(total, dtype=torch.uint8, device=dev),
+               "circular": torch.empty(u, dtype=torch.uint8, device=dev), "tf_sum": torch.empty(u, dtype=torch.int64, device=dev),
+               "tf_min": torch.empty(u, dtype=torch.int32, device=dev), "tf_max": torch.empty(u, dtype=torch.int32, device=dev),
+               "kmer_tf": torch.empty(live, dtype=torch.int32, device=dev) if want_kmer_tf else None}
+        p = lambda t: vp(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            check(lib().aix_unitigs_emit_dev(self._h, cutoff, p(ku), p(kp), p(kf), u, p(out["offsets"]), p(out["bases"]), p(out["circular"]), p(out["tf_sum"]),
+                                             p(out["tf_min"]), p(out["tf_max"]), p(out["kmer_tf"]), _stream_ptr(self.device)), "aix_unitigs_emit_dev")
+        out.update(kid_unitig=ku, kid_pos=kp, kid_flag=kf, U=u, n_live=live, n_circular=circ)
+        return out
+
+    def unitigs(self, cutoff: int = 0, want_kmer_tf: bool = False) -> dict:
+        """unitigs_t through host memory: the same dict with numpy arrays (offsets / tf_sum / kid_unitig uint64, tf_min / tf_max / kmer_tf /
+        kid_pos uint32)."""
+        ps = [vp() for _ in range(10)]
+        u = C.c_uint64()
+        refs = [C.byref(q) for q in ps]
+        if not want_kmer_tf:
+            refs[6] = None
+        check(lib().aix_unitigs(self._h, cutoff, C.byref(u), *refs), "aix_unitigs")
+        U = u.value
+        off = self._take_as(ps[0], U + 1, np.uint64)
+        total = int(off[U])
+        live = total - 22 * U
+        sizes = (None, total, U, U, U, U, live, self.n, self.n, self.n)
+        types = (None, np.uint8, np.uint8, np.uint64, np.uint32, np.uint32, np.uint32, np.uint64, np.uint32, np.uint8)
+        out = {"offsets": off}
+        for i in range(1, 10):
+            out[self.UNITIG_KEYS[i]] = self._take_as(ps[i], sizes[i], types[i]) if refs[i] is not None else None
+        out.update(U=U, n_live=live, n_circular=int(out["circular"].sum()))
+        return out
+
     # ---- read cleaning (aix_readfix.hip) ---------------------------------------------------------
     @staticmethod
     def _fix_args(verify: int, max_fixes: int):

@@ -530,6 +530,52 @@ int aix_walk_dev(aix_index_t* h, const uint64_t* d_codes /* or NULL */, const ch
                  uint32_t* d_tf /* nullable */, uint64_t* d_last /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * De Bruijn compaction: all maximal unitigs of an index, once each, with their abundance, and the map k-mer -> (unitig, offset, strand).
+ * (The reference has no counterpart; the notation is that of the layer above: next / prev, rc, canon(x) = min(x, rc x).)
+ *
+ * Handles. 23-mer handles whose every stored code is canonical (aix_info_t::canonical_only == 1). Any other 23-mer handle is
+ * AIX_ERR_UNSUPPORTED (freq(x) and freq(rc x) differ there, the graph is not strand-symmetric), a 13-mer handle AIX_ERR_MODE, an empty
+ * index AIX_ERR_UNSUPPORTED, as is one whose ports (2 kid + port) do not fit a 32-bit word (n > 2^31 - 4). A NULL pointer where one is
+ * needed is AIX_ERR_ARG; AIX_ERR_NOMEM keeps nothing. All of these are decided before anything is allocated or launched.
+ *
+ * Nodes. The oriented 23-mer x is live iff canon(x) is a stored key with tf > cutoff (for every cutoff >= 0 exactly "non-zero after the
+ * CONT cutoff rule"; a stored tf of 0 is dead). out(x) = the live members of {next(x, b)}, in(x) = the live members of {prev(x, b)}
+ * = rc(out(rc x)).
+ * Edges. x -> y is a unitig edge iff y in out(x), |out(x)| == 1, |in(y)| == 1 and canon(y) != canon(x); the last condition cuts
+ * self-loops (a homopolymer is a linear unitig of one node) and hairpins (y == rc x). With x -> y, rc y -> rc x is an edge too. A node has
+ * two ports — 0 = R, leaving in stored orientation; 1 = L, leaving as the reverse complement — with at most one link each, so the
+ * components are simple paths and simple cycles, and they partition the live keys.
+ * Spelling. A unitig of m k-mers is its first oriented k-mer plus the last base of each following one: m + 22 ASCII bases. Path: of its
+ * two spellings the one whose first oriented k-mer has the smaller 46-bit code (m == 1: the stored key; m > 1: the two belong to
+ * different nodes and never tie). Cycle: it starts at the node with the smallest stored code, in stored orientation, leaves through its R
+ * port and spells m k-mers (the first k-mer is not repeated); circular = 1.
+ * Order. Unitig ids 0 .. U - 1 ascend by the code of the first oriented k-mer of the spelling. These codes are distinct: the output is a
+ * pure function of (key set, tf, cutoff) — not of the MPHF, the launch geometry or any probe switch.
+ *
+ * Outputs per stored kid (n each): kid_unitig (AIX_UNITIG_NONE if dead), kid_pos (the k-mer occupies bases [offsets[u] + pos,
+ * offsets[u] + pos + 23)), kid_flag (bit 0: the stored key appears reverse-complemented in the spelling; bit 1: the unitig is circular);
+ * dead kids get pos = 0 and flag = 0. Per unitig: offsets[U + 1], bases[offsets[U]], circular[U], and tf_sum / tf_min / tf_max over the
+ * member tf. Optional: kmer_tf[n_live] in unitig order — k-mer j of unitig u sits at offsets[u] - 22 u + j: the coverage profile along
+ * every unitig. A cutoff at which nothing is live gives U = 0 and offsets = {0}.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_UNITIG_NONE 0xFFFFFFFFFFFFFFFFull
+/* The graph is analysed once, here: the three per-kid arrays, and the sizes the second call needs (*total_bases_out = offsets[U],
+ * *n_live_out = the length of kmer_tf). Returns after its work on `stream` has completed. Scratch: see DESIGN 5i. */
+int aix_unitigs_layout_dev(aix_index_t* h, uint32_t cutoff, uint64_t* d_kid_unitig, uint32_t* d_kid_pos, uint8_t* d_kid_flag,
+                           uint64_t* n_unitigs_out, uint64_t* total_bases_out, uint64_t* n_live_out, uint64_t* n_circular_out, void* stream);
+/* Spells the unitigs of a layout: d_offsets[U + 1], d_bases[total], d_circular / d_tf_sum / d_tf_min / d_tf_max [U], d_kmer_tf[n_live]
+ * (nullable); nothing is written at or beyond these sizes. Member tf are read from the index; `cutoff` is only checked against the
+ * layout: a live kid whose tf is <= cutoff — or any other disagreement between the arrays, U and the index — is AIX_ERR_ARG, with
+ * nothing written. Returns after its work on `stream` has completed. */
+int aix_unitigs_emit_dev(aix_index_t* h, uint32_t cutoff, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag,
+                         uint64_t U, uint64_t* d_offsets, uint8_t* d_bases, uint8_t* d_circular, uint64_t* d_tf_sum, uint32_t* d_tf_min,
+                         uint32_t* d_tf_max, uint32_t* d_kmer_tf /* nullable */, void* stream);
+/* Both calls for host memory: every array is malloc'd (aix_free). */
+int aix_unitigs(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, uint64_t** offsets_out, uint8_t** bases_out, uint8_t** circular_out,
+                uint64_t** tf_sum_out, uint32_t** tf_min_out, uint32_t** tf_max_out, uint32_t** kmer_tf_out /* nullable */,
+                uint64_t** kid_unitig_out /* nullable */, uint32_t** kid_pos_out /* nullable */, uint8_t** kid_flag_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
