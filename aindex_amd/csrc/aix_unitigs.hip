@@ -47,9 +47,13 @@ struct UgCounters {                                               // one zeroed 
     unsigned long long unflagged[66];                             // [0] after k_ug_links, [r] after round r
 };
 
-static inline unsigned ug_grid(uint64_t work, uint64_t per_block) {
+// AIX_UG_TEST_GRID (test hook, read per call): workgroups of every launch at most, so that small indexes make many trips
+static inline uint64_t ug_test_grid() { return env_u64("AIX_UG_TEST_GRID", 1, 65536, 65536); }
+
+static inline unsigned ug_grid(uint64_t work, uint64_t per_block, uint64_t cap) {
     uint64_t b = (work + per_block - 1) / per_block;
     if (b > 4096) b = 4096;                                        // grid-stride: a few atomics per workgroup, not per wave of work
+    if (b > cap) b = cap;
     if (b == 0) b = 1;
     return (unsigned)b;
 }
@@ -383,7 +387,7 @@ static hipError_t ug_read(UgCounters* host, const UgCounters* dev, hipStream_t s
 // Outputs of the layout call. Synchronises `s`.
 static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_unitig, uint32_t* kid_pos, uint8_t* kid_flag, uint64_t out[4], hipStream_t s) {
     const IndexDev ix = h->dev();
-    const uint64_t n = ix.n, NP = 2 * n;
+    const uint64_t n = ix.n, NP = 2 * n, cap = ug_test_grid();
     const dim3 blk(kUB);
     DevArr ctr_a(s), word(s), r0(s), r1(s), ca0(s), ck0(s), ca1(s), ck1(s), sc(s), sk(s), sc2(s), sk2(s), tmp(s);
     UG(ctr_a.alloc(sizeof(UgCounters)));
@@ -393,14 +397,14 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
     UgCounters* ctr = (UgCounters*)ctr_a.p;
     UgCounters hc;
     UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    UGL(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, 65536)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
-    UGL(k_ug_links, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
+    UGL(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
+    UGL(k_ug_links, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
     UG(ug_read(&hc, ctr, s));
     uint64_t *cur = (uint64_t*)r0.p, *oth = (uint64_t*)r1.p;
     uint64_t open = hc.unflagged[0];
     const int max_rounds = std::min(64, ug_ceil_log2(n) + 1);
     for (int r = 1; r <= max_rounds && open; ++r) {
-        UGL(k_ug_jump, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
+        UGL(k_ug_jump, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
         UG(ug_read(&hc, ctr, s));
         std::swap(cur, oth);
         const bool same = hc.unflagged[r] == open;
@@ -415,10 +419,10 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
         UG(ca1.alloc(8 * NP));
         UG(ck1.alloc(8 * NP));
         uint64_t *a = (uint64_t*)ca0.p, *k = (uint64_t*)ck0.p, *a2 = (uint64_t*)ca1.p, *k2 = (uint64_t*)ck1.p;
-        UGL(k_ug_cyc_init, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, ix, (const uint64_t*)cur, (const uint32_t*)word.p, NP, a, k);
+        UGL(k_ug_cyc_init, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, ix, (const uint64_t*)cur, (const uint32_t*)word.p, NP, a, k);
         const int rounds = std::min(64, ug_ceil_log2(open) + 1);
         for (int r = 1; r <= rounds; ++r) {
-            UGL(k_ug_cyc_jump, dim3(ug_grid(NP, 4 * kUB)), blk, 0, s, (const uint64_t*)cur, NP, r <= 63 ? 1ULL << (r - 1) : 0ULL, (const uint64_t*)a,
+            UGL(k_ug_cyc_jump, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)cur, NP, r <= 63 ? 1ULL << (r - 1) : 0ULL, (const uint64_t*)a,
                 (const uint64_t*)k, a2, k2);
             std::swap(a, a2);
             std::swap(k, k2);
@@ -431,7 +435,7 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
     word.drop();
     UG(sc.alloc(8 * n));
     UG(sk.alloc(4 * n));
-    UGL(k_ug_place, dim3(ug_grid(n, 2 * kUB)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
+    UGL(k_ug_place, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
         (uint32_t*)sk.p, ctr);
     UG(ug_read(&hc, ctr, s));
     const uint64_t U = std::min<uint64_t>(hc.n_starts, n);
@@ -442,8 +446,8 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
         UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
         UG(tmp.alloc(tb ? tb : 1));
         UG(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
-        UGL(k_ug_ids, dim3(ug_grid(U, 4 * kUB)), blk, 0, s, (const uint32_t*)sk2.p, U, n, kid_unitig);
-        UGL(k_ug_assign, dim3(ug_grid(n, 4 * kUB)), blk, 0, s, (const uint64_t*)sc2.p, U, n, (const uint32_t*)kid_pos, kid_unitig);
+        UGL(k_ug_ids, dim3(ug_grid(U, 4 * kUB, cap)), blk, 0, s, (const uint32_t*)sk2.p, U, n, kid_unitig);
+        UGL(k_ug_assign, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)sc2.p, U, n, (const uint32_t*)kid_pos, kid_unitig);
     }
     out[0] = U;
     out[1] = hc.n_live + 22 * U;
@@ -457,7 +461,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
                           uint64_t* offsets, uint8_t* bases, uint8_t* circular, uint64_t* tf_sum, uint32_t* tf_min, uint32_t* tf_max, uint32_t* kmer_tf, bool* bad,
                           hipStream_t s) {
     const IndexDev ix = h->dev();
-    const uint64_t n = ix.n;
+    const uint64_t n = ix.n, cap = ug_test_grid();
     const dim3 blk(kUB);
     *bad = false;
     DevArr ctr_a(s), keys(s), kids(s), keys2(s), kids2(s), tmp(s), tfs(s), uniq(s), agg(s), cnt(s), tmp2(s);
@@ -465,7 +469,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
     UgCounters* ctr = (UgCounters*)ctr_a.p;
     UgCounters hc;
     UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
+    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
     UG(ug_read(&hc, ctr, s));
     if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
     const uint64_t n_live = hc.n_live, total = n_live + 22 * U;
@@ -478,7 +482,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
     UG(kids.alloc(4 * n));
     UG(keys2.alloc(8 * n));
     UG(kids2.alloc(4 * n));
-    UGL(k_ug_keys, dim3(ug_grid(n, 4 * kUB)), blk, 0, s, n, U, pos_bits, kid_unitig, kid_pos, (uint64_t*)keys.p, (uint32_t*)kids.p);
+    UGL(k_ug_keys, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, n, U, pos_bits, kid_unitig, kid_pos, (uint64_t*)keys.p, (uint32_t*)kids.p);
     size_t tb = 0;
     UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, (size_t)n, 0u,
                                  (unsigned)end_bit, s));
@@ -493,7 +497,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
         UG(tfs.alloc(4 * n_live));
         tf_seq = (uint32_t*)tfs.p;
     }
-    UGL(k_ug_emit, dim3(ug_grid(n_live, 2 * kUB)), blk, 0, s, ix, (const uint64_t*)keys2.p, (const uint32_t*)kids2.p, n_live, U, pos_bits, kid_flag, total, offsets,
+    UGL(k_ug_emit, dim3(ug_grid(n_live, 2 * kUB, cap)), blk, 0, s, ix, (const uint64_t*)keys2.p, (const uint32_t*)kids2.p, n_live, U, pos_bits, kid_flag, total, offsets,
         bases, circular, tf_seq);
     UG(uniq.alloc(8 * U));
     UG(agg.alloc(sizeof(UgAgg) * U));
@@ -504,7 +508,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
     UG(rocprim::reduce_by_key(nullptr, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
     UG(tmp2.alloc(tb ? tb : 1));
     UG(rocprim::reduce_by_key(tmp2.p, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
-    UGL(k_ug_stats, dim3(ug_grid(U, 4 * kUB)), blk, 0, s, (const uint64_t*)uniq.p, (const UgAgg*)agg.p, (const uint64_t*)cnt.p, U, tf_sum, tf_min, tf_max);
+    UGL(k_ug_stats, dim3(ug_grid(U, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)uniq.p, (const UgAgg*)agg.p, (const uint64_t*)cnt.p, U, tf_sum, tf_min, tf_max);
     return hipStreamSynchronize(s);
 }
 

@@ -15,6 +15,7 @@ import debruijn_ref as D
 import graph_cases as G
 import oracle_lib as O
 import unitigs_cases as UC
+import unitigs_check as KC
 import unitigs_ref as R
 from aindex_amd import _lib, builder
 from aindex_amd.engine import Index
@@ -174,13 +175,13 @@ import hashlib, sys
 import numpy as np
 sys.path.insert(0, sys.argv[1])
 from aindex_amd.engine import Index
-p = sys.argv[2]
 h = hashlib.sha256()
-with Index.open_23(p + ".pf", p + ".tf.bin", p + ".kmers.bin") as ix:
-    for cutoff in (0, 3):
-        u = ix.unitigs(cutoff, want_kmer_tf=True)
-        for k in %r:
-            h.update(np.ascontiguousarray(u[k]).tobytes())
+for p in sys.argv[2:]:
+    with Index.open_23(p + ".pf", p + ".tf.bin", p + ".kmers.bin") as ix:
+        for cutoff in (0, 3):
+            u = ix.unitigs(cutoff, want_kmer_tf=True)
+            for k in %r:
+                h.update(np.ascontiguousarray(u[k]).tobytes())
 print("digest", h.hexdigest())
 """ % (ARRAYS + ("kmer_tf",),)
 
@@ -324,3 +325,220 @@ def test_list_surface(cases, small23_prefix, tmp_path):
         assert ai.get_unitig_of_kmers([]) == [] and ai.get_unitig_of_kmers(["ACGT"]) == [None]
     finally:
         ai._wrapper.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# planted topologies, many trips of every grid-stride loop, the natural second trip, streams
+# ---------------------------------------------------------------------------------------------
+def _numpy(u):
+    """a device-form answer as the numpy dict that _digest and unitigs_check.check take"""
+    return {k: (_host(v) if hasattr(v, "cpu") else v) for k, v in u.items()}
+
+
+@pytest.fixture(scope="module")
+def topo(tmp_path_factory):
+    """name -> {"prefix", "case", "want": cutoff -> the restatement's answer in the index's kid order}: the planted topologies as index files,
+    each built and answered once, when a test first asks for it"""
+    d = str(tmp_path_factory.mktemp("ugt"))
+    planted, made = UC.topology_cases(), {}
+
+    def get(name):
+        if name not in made:
+            case = planted[name]
+            prefix = os.path.join(d, name)
+            open(prefix + ".pf", "wb").write(builder.build_pf_codes(case.codes, 23))
+            rc, checker, tf = O.index_scatter(O.OracleMphf(prefix + ".pf"), np.ascontiguousarray(D.decode(case.codes)).reshape(-1), case.tfs)
+            assert rc == 0
+            checker.tofile(prefix + ".kmers.bin")
+            tf.tofile(prefix + ".tf.bin")
+            codes = checker & np.uint64(R.MASK)
+            made[name] = {"prefix": prefix, "case": case, "codes": codes, "tfs": tf,
+                          "want": {c: R.unitigs(codes, tf, c) for c in UC.topology_cutoffs(name)}}
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", sorted(UC.topology_cases()))
+def test_planted_topologies_host_and_device_forms(topo, name):
+    """8. Hairpin ends, self-loops with neighbours, lollipops, a bubble and a tip at the cutoff, circles that a cutoff opens, hundreds of
+    small circles beside a long path, isolated keys, one key, tf at 2^32 - 1: the restatement's arrays in both forms at cutoffs 0 and 3
+    (`heavy`: 0xFFFFFFFE too), and unitigs_check.check accepts them. test_unitigs_cpu.py asserts that each case holds its structure."""
+    t = topo(name)
+    with _open(t["prefix"]) as ix:
+        assert ix.canonical_only and ix.n == t["case"].codes.shape[0]
+        for cutoff in UC.topology_cutoffs(name):
+            want = t["want"][cutoff]
+            _same(ix.unitigs(cutoff, want_kmer_tf=True), want, True, (name, cutoff, "host"))
+            layout = ix.unitigs_layout_t(cutoff)
+            assert layout[3:] == (want["U"], int(want["offsets"][-1]), want["n_live"], want["n_circular"])
+            got = ix.unitigs_t(cutoff, want_kmer_tf=True, layout=layout)
+            _same(got, want, True, (name, cutoff, "device"))
+            KC.check(t["codes"], t["tfs"], cutoff, _numpy(got))
+        if name == "isolated_one":
+            u = ix.unitigs(0)
+            assert u["U"] == 1 and u["offsets"].tolist() == [0, 23] and u["bases"].tobytes().decode() == R.spell([int(t["codes"][0])])
+        if name == "heavy":
+            assert int(ix.unitigs(0)["tf_sum"].max()) == 6 * 0xFFFFFFFF and ix.unitigs(0xFFFFFFFF)["U"] == 0
+
+
+def test_many_trips_of_every_loop_on_small_cases(cases, depth, topo, monkeypatch):
+    """9. AIX_UG_TEST_GRID = 1, 2, 3 workgroups for k_ug_ports and every grid-stride launch: hundreds of trips per workgroup, the tail of
+    the last trip inside a live wave (18 484 ports are no multiple of 16), the filter gauge carried from trip to trip. The restatement's
+    digest at cutoffs 0 and 3 in this process; with 2 workgroups, AIX_DBJ_FILTER 0, 1, 2 each in a fresh child."""
+    many = topo("many_circles")
+    assert (2 * many["codes"].shape[0]) % 16 != 0
+    opened = []
+    try:
+        sets = [(depth["ix"], {0: _digest(depth["want"]), 3: _digest(R.unitigs(depth["ix"].checker_array() & np.uint64(R.MASK), depth["ix"].tf_array(), 3))})]
+        for prefix, want in ((cases[3], None), (many["prefix"], many["want"])):
+            ix = _open(prefix)
+            opened.append(ix)
+            sets.append((ix, {c: _digest(want[c] if want else _ref(ix, c)) for c in (0, 3)}))
+        assert len({d[0] for _, d in sets}) == 3
+        for grid in ("1", "2", "3"):
+            monkeypatch.setenv("AIX_UG_TEST_GRID", grid)
+            for i, (ix, want) in enumerate(sets):
+                for c in (0, 3):
+                    assert _digest(ix.unitigs(c, want_kmer_tf=True)) == want[c], (grid, i, c, "host")
+                    assert _digest(_numpy(ix.unitigs_t(c, want_kmer_tf=True))) == want[c], (grid, i, c, "device")
+        monkeypatch.delenv("AIX_UG_TEST_GRID")
+        h = hashlib.sha256()
+        for ix, want in sets[1:]:
+            for c in (0, 3):
+                u = ix.unitigs(c, want_kmer_tf=True)
+                assert _digest(u) == want[c]
+                for k in ARRAYS + ("kmer_tf",):
+                    h.update(np.ascontiguousarray(u[k]).tobytes())
+    finally:
+        for ix in opened:
+            ix.close()
+    kids = []
+    for policy in ("0", "1", "2"):
+        env = dict(os.environ, AIX_DBJ_FILTER=policy, AIX_UG_TEST_GRID="2", AIX_NO_TORCH="1")
+        kids.append(subprocess.Popen([sys.executable, "-c", _CHILD, ROOT, cases[3], many["prefix"]], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
+    for policy, k in zip("012", kids):
+        out, err = k.communicate(timeout=300)
+        assert k.returncode == 0, (policy, err.decode()[-2000:])
+        assert out.decode().split()[-2:] == ["digest", h.hexdigest()], policy
+
+
+def _midsize_text(rng):
+    """plain text (records end with a newline): a 1.3 Mbp genome; 150-bp reads of either strand at 6 x over a further 150 kbp with 0.5 %
+    substitutions; circular sequences of 3 .. 99 991 bases, each with its first 22 bases appended and written twice; the reads of
+    test_gpu_debruijn._seeded_reads (tandem arrays, a planted repeat)."""
+    from test_gpu_debruijn import _seeded_reads
+    nl = np.array([10], np.uint8)
+    parts = [D.LETTERS[rng.integers(0, 4, 1_300_000)], nl]
+    g = rng.integers(0, 4, 150_000).astype(np.uint8)
+    n_reads = 6 * len(g) // 150
+    reads = g[rng.integers(0, len(g) - 150, n_reads)[:, None] + np.arange(150)[None, :]]
+    reads = np.where(rng.random(reads.shape) < 0.005, (reads + rng.integers(1, 4, reads.shape)) % 4, reads).astype(np.uint8)
+    flip = rng.random(n_reads) < 0.5
+    reads[flip] = (3 - reads[flip])[:, ::-1]
+    parts.append(np.concatenate([D.LETTERS[reads], np.full((n_reads, 1), 10, np.uint8)], axis=1).reshape(-1))
+    circles = (3, 4097, 65_536, 65_537, 99_991)
+    for m in circles:
+        unit = np.array([0, 1, 2], np.uint8) if m == 3 else rng.integers(0, 4, m).astype(np.uint8)
+        ring = D.LETTERS[np.tile(unit, 22 // m + 2)[: m + 22]]
+        parts += [ring, nl, ring, nl]
+    parts.append(_seeded_reads(rng)[1])
+    return np.concatenate(parts), circles
+
+
+def test_natural_second_trip_and_grids_at_their_caps(monkeypatch):
+    """10. An index of 2.2 .. 3 million keys built on the device: k_ug_ports makes a second trip over at least 2^17 ports, every
+    grid-stride launch over ports runs at its cap of 4096 workgroups, the ranking takes 21 or 22 rounds, circles of 3 .. 99 991 k-mers
+    are ranked beside them. unitigs_check.check (link table through torch on the device) accepts the device form at cutoffs 0 and 1;
+    cutoff 0 with AIX_UG_TEST_GRID=512, and with AIX_DBJ_FILTER 0 and 1 (read per call), is byte-identical. The restatement does not run
+    at this size in the suite; run once on a CPU (6.5 minutes) it gave the figures below, and check() accepted its answer.
+    On an MI355X: n = 2 273 469, U = 38 886 (1076 at cutoff 1, where the genome, written once, is dead), n_circular = 5 (3, 4097, 65 536,
+    65 537 and 99 991 k-mers), longest unitig 1 299 978 k-mers; the whole test takes 0.9 s of wall time."""
+    import time
+    import torch
+    from aindex_amd import counting
+    t0 = time.time()
+    plain, circles = _midsize_text(np.random.default_rng(20251))
+    keys, counts = counting.count_distinct_t(torch.from_numpy(plain).cuda(), 23, _lib.CANON_TRUE_RC)
+    pf = builder.build_pf_codes_t(keys, 23)
+    ix = Index.build_23_codes_t(pf, keys, counts.to(torch.int32))
+    torch.cuda.synchronize()
+    try:
+        n = ix.n
+        assert 2 ** 21 + 2 ** 16 <= n <= 3_000_000 and ix.canonical_only
+        codes, tfs = ix.checker_array() & np.uint64(R.MASK), ix.tf_array()
+        t1 = time.time()
+        got = {}
+        for cutoff in (0, 1):
+            got[cutoff] = _numpy(ix.unitigs_t(cutoff, want_kmer_tf=True))
+            KC.check(codes, tfs, cutoff, got[cutoff], device="cuda")
+        u = got[0]
+        m = np.diff(u["offsets"].astype(np.int64)) - 22
+        print("n", n, "U", u["U"], "n_circular", u["n_circular"], "longest", int(m.max()), "U at cutoff 1", got[1]["U"],
+              "circles", sorted(m[u["circular"] == 1].tolist())[-6:], "build %.1f s, two cutoffs with check %.1f s" % (t1 - t0, time.time() - t1))
+        assert u["n_circular"] >= 5 and u["U"] >= 10 ** 4 and int(m.max()) >= 2 ** 19
+        assert set(circles) <= set(m[u["circular"] == 1].tolist())
+        assert got[1]["U"] < u["U"]
+        monkeypatch.setenv("AIX_UG_TEST_GRID", "512")
+        assert _digest(_numpy(ix.unitigs_t(0, want_kmer_tf=True))) == _digest(u)
+        monkeypatch.delenv("AIX_UG_TEST_GRID")
+        for policy in ("0", "1"):                                    # the gauge carried into the natural second trip; the filter always on
+            monkeypatch.setenv("AIX_DBJ_FILTER", policy)
+            assert _digest(_numpy(ix.unitigs_t(0, want_kmer_tf=True))) == _digest(u), policy
+        print("whole test %.1f s" % (time.time() - t0))
+    finally:
+        ix.close()
+
+
+def test_links_in_numpy_and_in_torch_on_the_device(cases, topo):
+    """11. unitigs_check.links through torch on the device equals its numpy form on the graph cases and on two planted ones (plumbing of
+    the checker, not a kernel)."""
+    import torch
+    sets = [G.make_graph_case(seed)[:2] for seed in SEEDS] + [(topo(name)["codes"], topo(name)["tfs"]) for name in ("hairpin_ends", "many_circles")]
+    for i, (codes, tfs) in enumerate(sets):
+        for cutoff in (0, 3):
+            want = KC.links(codes, tfs, cutoff)
+            got = KC._links_on(codes, tfs, cutoff, "cuda")
+            assert (want >= 0).sum() > 100 and got.dtype == want.dtype and np.array_equal(got, want), (i, cutoff)
+
+
+def test_side_streams_and_two_threads(cases):
+    """12. (a) unitigs_t under a side stream; (b) the layout made under stream A (the call synchronises its stream) and emitted under
+    stream B; (c) two host threads, each under a stream of its own, four calls each at cutoffs 0 and 3 on ONE handle — queries are
+    thread-safe per handle (include/aindex_hip.h), as test_concurrent_host_calls_one_handle relies on: per-call scratch, one counter
+    record per call, nothing on the handle is written. The restatement's arrays / digest every time."""
+    import threading
+    import torch
+    with _open(cases[6]) as ix:
+        want = {c: _ref(ix, c) for c in (0, 3)}
+        digest = {c: _digest(want[c]) for c in (0, 3)}
+        assert digest[0] != digest[3]
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        for c in (0, 3):
+            with torch.cuda.stream(a):
+                got = ix.unitigs_t(c, want_kmer_tf=True)
+            a.synchronize()
+            _same(got, want[c], True, (c, "side stream"))
+            with torch.cuda.stream(a):
+                layout = ix.unitigs_layout_t(c)
+            with torch.cuda.stream(b):
+                got = ix.unitigs_t(c, want_kmer_tf=True, layout=layout)
+            b.synchronize()
+            _same(got, want[c], True, (c, "layout on one stream, emit on another"))
+        errors = []
+
+        def worker(stream, first):
+            try:
+                with torch.cuda.stream(stream):
+                    for it in range(4):
+                        for c in ((0, 3) if first else (3, 0)):
+                            got = _numpy(ix.unitigs_t(c, want_kmer_tf=True))
+                            if _digest(got) != digest[c]:
+                                errors.append((first, it, c))
+            except Exception as e:                                   # noqa: BLE001
+                errors.append(repr(e))
+        threads = [threading.Thread(target=worker, args=(s, i == 0)) for i, s in enumerate((a, b))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert not errors, errors
