@@ -293,6 +293,35 @@ AIX_HD Enc23 encode23_words(uint64_t w0, uint64_t w1, uint64_t w2) {
     e.valid = ((b0 | b1 | b2 | b3 | b4 | (b5 & 0x00010101u)) == 0);
     return e;
 }
+// sum of a.byte[i] * b.byte[i] over the four bytes, plus c
+AIX_HD uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(a, b, c, false);                 // v_dot4_u32_u8
+#else
+    for (int i = 0; i < 4; ++i) c += ((a >> (8 * i)) & 0xffu) * ((b >> (8 * i)) & 0xffu);
+    return c;
+#endif
+}
+#define AIX_DOT_PACK4 0x01041040u   // 4 pairs, one per byte, first byte most significant -> 8 bits
+#define AIX_DOT_PACK3 0x00010410u   // the same for the first 3 bytes -> 6 bits
+// encode23_words for callers that drop a query with other bytes: the same `valid`, and the same code whenever it holds (then no
+// byte is sanitised, so the pairs are packed as they are); when it does not hold the code is unspecified. One test of the
+// "lut4(pair) ^ byte" words instead of a mask per byte, and a byte-wise dot product instead of a multiply per dword.
+AIX_HD bool encode23_clean(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t& code) {
+    const uint32_t x0 = (uint32_t)w0, x1 = (uint32_t)(w0 >> 32), x2 = (uint32_t)w1, x3 = (uint32_t)(w1 >> 32), x4 = (uint32_t)w2, x5 = (uint32_t)(w2 >> 32);
+    const uint32_t c0 = ((x0 >> 1) ^ (x0 >> 2)) & 0x03030303u, c1 = ((x1 >> 1) ^ (x1 >> 2)) & 0x03030303u, c2 = ((x2 >> 1) ^ (x2 >> 2)) & 0x03030303u;
+    const uint32_t c3 = ((x3 >> 1) ^ (x3 >> 2)) & 0x03030303u, c4 = ((x4 >> 1) ^ (x4 >> 2)) & 0x03030303u, c5 = ((x5 >> 1) ^ (x5 >> 2)) & 0x03030303u;
+    const uint32_t y = (lut4(c0, AIX_LUT_ACGT) ^ x0) | (lut4(c1, AIX_LUT_ACGT) ^ x1) | (lut4(c2, AIX_LUT_ACGT) ^ x2) | (lut4(c3, AIX_LUT_ACGT) ^ x3) |
+                       (lut4(c4, AIX_LUT_ACGT) ^ x4) | ((lut4(c5, AIX_LUT_ACGT) ^ x5) & 0x00FFFFFFu);   // zero byte <=> valid base; the 24th byte is not the query's
+    if (y) return false;
+    uint32_t hi = dot4(c0, AIX_DOT_PACK4, 0u);                                                        // bases 0..15
+    hi = dot4(c1, AIX_DOT_PACK4, hi << 8);
+    hi = dot4(c2, AIX_DOT_PACK4, hi << 8);
+    hi = dot4(c3, AIX_DOT_PACK4, hi << 8);
+    const uint32_t lo = dot4(c5, AIX_DOT_PACK3, dot4(c4, AIX_DOT_PACK4, 0u) << 6);                    // bases 16..22
+    code = ((uint64_t)hi << 14) | lo;
+    return true;
+}
 struct Enc13 {
     uint32_t code;
     bool valid;

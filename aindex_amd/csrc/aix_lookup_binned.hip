@@ -9,7 +9,9 @@
 //                 counting-sorted by filter slice in LDS per 4096-query tile and flushed into 256-record chunks of a per-slice
 //                 region (chunks come from a per-slice cursor; a workgroup asks for all chunks of a tile and slice at once).
 //                 out[i] = 0 for every query. Queries with other bytes, and records whose slice region is full, go onto the
-//                 survivor list instead.
+//                 survivor list instead. A lane fetches a query's dwords one query before it encodes them (lb_fetch), encodes with
+//                 encode23_clean, finds the slice with a shift where the slice width is a power of two (the shipped 2^17 words is),
+//                 and the tile's zeros are written with 16-byte stores behind the query loop: 80 VGPRs, three workgroups per CU.
 //   k_lb_filter   pass B: chunks in slice order across the whole grid, so that the chip reads one or two slices (~1 MiB each)
 //                 at a time and every XCD holds them in its L2. The chunks are handed out in order through eight ticket counters,
 //                 four chunks (1024 records) per ticket to a workgroup of 512 threads: ~107 000 returning atomics per 10^8
@@ -45,13 +47,17 @@ static constexpr uint32_t LB_SAMPLES = 16384;
 static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 16;
 static_assert(LB_MASK_BITS == 16 && LB_IDX_BITS + LB_WORD_BITS + LB_MASK_BITS <= 64, "the record holds the 16 bits bloom_mask reads");
 static constexpr uint32_t LB_NONE = 0xFFFFFFFFu;
+static constexpr uint32_t LB_LO_BITS = 32 - LB_IDX_BITS, LB_META_LO = 9;   // pass A's per-query word: slice (9 bits) | the word-field bits of a record's low dword | rank << 16
+static_assert(LB_IDX_BITS < 32 && LB_MAXBINS < (1 << LB_META_LO) && LB_META_LO + LB_LO_BITS <= 16 && LB_TILE <= (1 << 13), "that word never equals LB_NONE");
 static constexpr uint64_t LB_HDR_BYTES = 4096;         // header (4 words) + cursors (LB_MAXBINS words) + ticket counters (a 128-byte line each), zeroed per piece
 enum { LB_FLAG = 0, LB_PASSED = 1, LB_DONE = 2, LB_NSURV = 3, LB_CURSOR = 16, LB_TICKET = 512 };
 
+static constexpr uint32_t LB_NO_SHIFT = 32;
 struct LbGeom {
     uint32_t nbins;        // filter slices
     uint32_t wps;          // filter words per slice (<= 2^18)
     uint32_t inv;          // floor(2^32 / wps), for word / wps
+    uint32_t shift;        // log2(wps) where wps is a power of two (the shipped 2^17 is): word / wps is a shift; otherwise LB_NO_SHIFT
     uint32_t cap;          // chunks per slice region
 };
 struct LbWs {
@@ -64,11 +70,23 @@ struct LbWs {
 
 // the filter key of the code query23 (aix_kernels.hip) probes: that of the canonical strand; false = other bytes
 __device__ __forceinline__ bool lb_hash(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t& hw, uint32_t& hb) {
-    const Enc23 e = encode23_words(w0, w1, w2);
-    if (!e.valid) return false;
-    const uint64_t r = revcomp(e.code, 23);
-    filter_key(e.code <= r ? e.code : r, hw, hb);
+    uint64_t code;
+    if (!encode23_clean(w0, w1, w2, code)) return false;
+    const uint64_t r = revcomp(code, 23);
+    filter_key(code <= r ? code : r, hw, hb);
     return true;
+}
+
+// filter word -> its slice and the word inside the slice; the branch is the same for every query of a launch
+__device__ __forceinline__ void lb_slice(uint32_t word, const LbGeom& g, uint32_t& bin, uint32_t& wi) {
+    if (g.shift != LB_NO_SHIFT) {
+        bin = word >> g.shift;
+        wi = word & (g.wps - 1);
+    } else {
+        bin = __umulhi(word, g.inv);                             // word / wps, at most one too small
+        wi = word - bin * g.wps;
+        if (wi >= g.wps) { wi -= g.wps; ++bin; }
+    }
 }
 
 __global__ void __launch_bounds__(256) k_lb_gate(const uint64_t* __restrict__ bloom, uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n,
@@ -139,7 +157,41 @@ __device__ __forceinline__ void lb_place(uint32_t f, uint32_t cur, uint32_t nb, 
     else { chunk = nb + (pos - LB_CH) / LB_CH; o = (pos - LB_CH) % LB_CH; }
 }
 
-__global__ void __launch_bounds__(LB_TB) k_lb_bin(uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
+// Pass A fetches a query's dwords LB_AHEAD queries before it encodes them, so that a wave has loads in flight while it computes.
+// The queries are addressed from q rounded down to a dword (qa = q - q mod 4) with a 32-bit byte offset (23 * (2^27 + a grid's
+// tiles) + 3 < 2^32): one register per address. Tiles and a lane's stride inside a tile (LB_TB queries) are multiples of four
+// queries, so every query of a lane starts at the same offset `o` inside its dword, whatever the tile.
+// The fetch has no branch in it (a load under `if (i < n)`, or a conditional seventh load as in load23, makes hipcc wait for the
+// loads right behind them) and reads no address that load23 does not read for a query of this batch: the offset is clamped to that
+// of the batch's last query (n >= 1), which is 23 * 4 k bytes away and so has the lane's `o` too; dwords 0..5 of the window are
+// load23's, and the seventh load is dword 6 only where load23 reads it (o >= 2); elsewhere it is dword 5 again, whose value
+// lb_words never lets through: for o < 2 the funnel shift puts at most its low byte into the word's 24th byte, which is masked off.
+static constexpr int LB_AHEAD = 1;
+static_assert(LB_AHEAD >= 1 && LB_QPL % LB_AHEAD == 0, "a query's slot in the ring of fetched queries is the same in every tile");
+static_assert(LB_TB % 4 == 0, "one offset inside the dword per lane");
+struct LbRaw { uint32_t d[7]; };
+// b = the query's first byte counted from qa (clamped by the caller), o = b % 4
+__device__ __forceinline__ LbRaw lb_fetch(const uint8_t* __restrict__ qa, uint32_t b, uint32_t o) {
+    const uint8_t* const a = qa + (b - o);
+    LbRaw r;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r.d[k] = *(const uint32_t*)(a + 4 * k);
+    r.d[6] = *(const uint32_t*)(qa + (b - o + (o >= 2 ? 24u : 20u)));
+    return r;
+}
+// load23's words from the fetched dwords
+__device__ __forceinline__ void lb_words(const LbRaw& r, uint32_t o, uint64_t& w0, uint64_t& w1, uint64_t& w2) {
+    uint32_t sh = o * 8;
+    asm("" : "+v"(sh));                                          // one register for the six shifts (hipcc otherwise keeps a copy of it per shift, for all of the kernel)
+    const uint32_t e0 = __funnelshift_r(r.d[0], r.d[1], sh), e1 = __funnelshift_r(r.d[1], r.d[2], sh);
+    const uint32_t e2 = __funnelshift_r(r.d[2], r.d[3], sh), e3 = __funnelshift_r(r.d[3], r.d[4], sh);
+    const uint32_t e4 = __funnelshift_r(r.d[4], r.d[5], sh), e5 = __funnelshift_r(r.d[5], r.d[6], sh) & 0x00FFFFFFu;
+    w0 = e0 | ((uint64_t)e1 << 32);
+    w1 = e2 | ((uint64_t)e3 << 32);
+    w2 = e4 | ((uint64_t)e5 << 32);
+}
+
+__global__ void __launch_bounds__(LB_TB, 3 * LB_TB / 256) k_lb_bin(uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
     if (!w.hdr[LB_FLAG]) return;
     __shared__ uint64_t sorted[LB_TILE];
     __shared__ uint16_t sbin[LB_TILE];
@@ -153,32 +205,61 @@ __global__ void __launch_bounds__(LB_TB) k_lb_bin(uint32_t nbloom, const uint8_t
     if (t <= NB) { hist[t] = 0; cur_chunk[t] = LB_NONE; cur_fill[t] = LB_CH; fresh[t] = 0; }
     __syncthreads();
     const uint32_t ntiles = (n + LB_TILE - 1) / LB_TILE;
+    const uint32_t qo = (uint32_t)((uintptr_t)q & 3);
+    const uint8_t* const qa = q - qo;
+    // what a fetch beyond the batch is clamped to: the last query that is one of this lane's modulo 4 (it starts at the lane's offset
+    // inside its dword, and every query of the lane beyond it is beyond the batch); a lane that has no query at all (t >= n) fetches the
+    // batch's last query every time, and takes its offset
+    const uint32_t i_last = t < n ? n - 1 - ((n - 1 - t) & 3u) : n - 1;
+    const uint32_t b_last = qo + 23u * i_last, o = b_last & 3u;
+    LbRaw ahead[LB_AHEAD];                                       // the lane's next LB_AHEAD queries
+#pragma unroll
+    for (int j = 0; j < LB_AHEAD; ++j) ahead[j] = lb_fetch(qa, min(qo + 23u * (blockIdx.x * LB_TILE + j * LB_TB + t), b_last), o);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint32_t base = tile * LB_TILE, in_tile = min((uint32_t)LB_TILE, n - base);
-        uint64_t rec[LB_QPL];
-        uint32_t meta[LB_QPL];                                   // slice | rank inside the tile's slice << 16
+        // a record's high dword; its low dword is the query index, which the lane knows, and LB_LO_BITS bits of the word field, kept in meta
+        // (eight registers fewer than whole records: with the fetched queries beside them the kernel would not fit 80 VGPRs without scratch)
+        uint32_t rec_hi[LB_QPL];
+        uint32_t meta[LB_QPL];                                   // slice | low bits of the word << LB_META_LO | rank inside the tile's slice << 16
 #pragma unroll
         for (int j = 0; j < LB_QPL; ++j) {
             const uint32_t i = base + j * LB_TB + t;
+            // this query's dwords were fetched LB_AHEAD queries ago; fetch those of the lane's query LB_AHEAD further on (in this tile, or
+            // at the start of the workgroup's next one) before this one is encoded
+            const LbRaw cur = ahead[j % LB_AHEAD];
+            const uint32_t i_next = j + LB_AHEAD < LB_QPL ? i + LB_AHEAD * LB_TB : i + LB_AHEAD * LB_TB + (gridDim.x - 1) * LB_TILE;
+            ahead[j % LB_AHEAD] = lb_fetch(qa, min(qo + 23u * i_next, b_last), o);
             meta[j] = LB_NONE;
-            rec[j] = 0;
+            rec_hi[j] = 0;
             if (i < n) {
                 uint64_t w0, w1, w2;
                 uint32_t hw, hb;
-                load23(q + 23ull * i, w0, w1, w2);
+                lb_words(cur, o, w0, w1, w2);
                 uint32_t bin = NB;
                 uint64_t r = i;
                 if (lb_hash(w0, w1, w2, hw, hb)) {
                     const uint32_t word = bloom_word(hw, nbloom);
-                    bin = __umulhi(word, g.inv);                 // word / wps, at most one too small
-                    uint32_t wi = word - bin * g.wps;
-                    if (wi >= g.wps) { wi -= g.wps; ++bin; }
+                    uint32_t wi;
+                    lb_slice(word, g, bin, wi);
                     r |= ((uint64_t)wi << LB_IDX_BITS) | ((uint64_t)(hb & ((1u << LB_MASK_BITS) - 1)) << (LB_IDX_BITS + LB_WORD_BITS));
                 }
-                meta[j] = bin | (atomicAdd(&hist[bin], 1u) << 16);
-                rec[j] = r;
-                out[i] = 0;
+                meta[j] = bin | (((uint32_t)r >> LB_IDX_BITS) << LB_META_LO) | (atomicAdd(&hist[bin], 1u) << 16);
+                rec_hi[j] = (uint32_t)(r >> 32);
             }
+        }
+        // out[i] = 0 for the tile's queries, behind the query loop: a store counts in vmcnt like a load, so one store per query would
+        // stand in the chain the next query's loads are waited for through. out + base is 4-byte aligned only: up to three single
+        // dwords in front of and behind the 16-byte stores.
+        {
+            uint32_t* const o0 = out + base;
+            const uint32_t head = min(in_tile, (0u - (uint32_t)((uintptr_t)o0 >> 2)) & 3u);
+            const uint32_t nvec = (in_tile - head) / 4, tail = in_tile - head - 4 * nvec;
+            uint4* const ov = (uint4*)(o0 + head);
+#pragma unroll
+            for (int k = 0; k < LB_TILE / 4 / LB_TB; ++k)
+                if (k * LB_TB + t < nvec) ov[k * LB_TB + t] = make_uint4(0u, 0u, 0u, 0u);
+            if (t < head) o0[t] = 0;
+            if (t < tail) o0[head + 4 * nvec + t] = 0;
         }
         __syncthreads();
         const uint32_t a = t <= NB ? hist[t] : 0u;
@@ -191,8 +272,9 @@ __global__ void __launch_bounds__(LB_TB) k_lb_bin(uint32_t nbloom, const uint8_t
 #pragma unroll
         for (int j = 0; j < LB_QPL; ++j) {
             if (meta[j] != LB_NONE) {
-                const uint32_t bin = meta[j] & 0xFFFFu, p = loc_off[bin] + (meta[j] >> 16);
-                sorted[p] = rec[j];
+                const uint32_t bin = meta[j] & ((1u << LB_META_LO) - 1), p = loc_off[bin] + (meta[j] >> 16);
+                const uint32_t lo = (base + j * LB_TB + t) | (((meta[j] >> LB_META_LO) & ((1u << LB_LO_BITS) - 1)) << LB_IDX_BITS);
+                sorted[p] = lo | ((uint64_t)rec_hi[j] << 32);
                 sbin[p] = (uint16_t)bin;
             }
         }
@@ -238,7 +320,7 @@ __global__ void __launch_bounds__(LB_TB) k_lb_bin(uint32_t nbloom, const uint8_t
                     uint32_t r0 = 0;
                     if ((t & 63u) == 0) r0 = atomicAdd(&s_ov_rank, (uint32_t)__popcll(m));
                     r0 = __shfl(r0, 0);
-                    if (ov) w.list[s_ov_base + r0 + (uint32_t)__popcll(m & ((1ull << (t & 63u)) - 1))] = (uint32_t)sorted[i] & ((1u << LB_IDX_BITS) - 1);
+                    if (ov) w.list[s_ov_base + r0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint32_t)sorted[i] & ((1u << LB_IDX_BITS) - 1);
                 }
             }
         }
@@ -361,6 +443,7 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     g.nbins = (d.nbloom + g.wps - 1) / g.wps;
     if (g.nbins > (uint32_t)LB_MAXBINS) return AIX_LB_NOT_TAKEN;   // a filter above ~500 MB: direct
     g.inv = g.wps > 1 ? (uint32_t)((1ull << 32) / g.wps) : 0xFFFFFFFFu;
+    g.shift = (g.wps & (g.wps - 1)) == 0 ? (uint32_t)__builtin_ctz(g.wps) : LB_NO_SHIFT;
     const uint64_t piece = std::min<uint64_t>(std::min<uint64_t>(N, 1ull << LB_IDX_BITS), env_u64("AIX_LOOKUP_PIECE", 1, 1ull << LB_IDX_BITS, 1ull << LB_IDX_BITS));
     const unsigned grid_a = (unsigned)std::min<uint64_t>((piece + LB_TILE - 1) / LB_TILE, LB_GRID_A);
     // a slice region: its share of a uniformly hashed piece plus a quarter, plus the chunk every pass-A workgroup leaves partly filled
