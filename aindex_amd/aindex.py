@@ -16,7 +16,7 @@ from __future__ import annotations
 import logging
 import os
 from enum import IntEnum
-from typing import List, Optional, Tuple
+from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 
@@ -52,6 +52,33 @@ def edit_distance(s1: str, s2: str) -> int:
 def get_revcomp(sequence: str) -> str:
     c = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N", "a": "t", "c": "g", "g": "c", "t": "a", "n": "n", "~": "~", "[": "]", "]": "["}
     return "".join(c.get(x, x) for x in reversed(sequence))
+
+
+def unitig_link_pairs(links: dict) -> List[Tuple[int, str, int, str]]:
+    """[(a, '+' | '-', b, '+' | '-')] of Index.unitig_links: one tuple per dual pair of links — (e, t) is written iff (e, t) <= (t ^ 1, e ^ 1)
+    as tuples, so a self-dual link appears once —, ascending by (e, position among the links of e)."""
+    off = np.asarray(links["link_off"]).astype(np.int64)
+    to = np.asarray(links["link_to"]).astype(np.int64)
+    e = np.repeat(np.arange(off.shape[0] - 1, dtype=np.int64), np.diff(off))
+    keep = e <= (to ^ 1)                                            # e == t ^ 1 makes t == e ^ 1: the second components tie
+    return [(a >> 1, "+-"[a & 1], b >> 1, "+-"[b & 1]) for a, b in zip(e[keep].tolist(), to[keep].tolist())]
+
+
+def format_gfa(unitigs: dict, links: dict) -> Iterator[str]:
+    """The lines (no line ends) of a GFA 1 file of the unitig graph: the header, one S line per unitig of Index.unitigs (named u{id}, with
+    LN = bases, KC = tf_sum, km = tf_sum / k-mers), one L line with overlap 22M per tuple of unitig_link_pairs, and the closing link
+    u{c} + -> u{c} + of every circular unitig. Host only."""
+    yield "H\tVN:Z:1.0"
+    off, text = np.asarray(unitigs["offsets"]).astype(np.int64).tolist(), np.asarray(unitigs["bases"]).tobytes().decode("ascii")
+    circular = np.asarray(unitigs["circular"]).tolist()
+    for i, s in enumerate(np.asarray(unitigs["tf_sum"]).tolist()):
+        ln = off[i + 1] - off[i]
+        yield f"S\tu{i}\t{text[off[i]:off[i + 1]]}\tLN:i:{ln}\tKC:i:{s}\tkm:f:{s / (ln - 22):.1f}"
+    for a, sa, b, sb in unitig_link_pairs(links):
+        yield f"L\tu{a}\t{sa}\tu{b}\t{sb}\t22M"
+    for i, c in enumerate(circular):
+        if c:
+            yield f"L\tu{i}\t+\tu{i}\t+\t22M"
 
 
 def iter_reads_by_kmer(kmer: str, aindex: "AIndex", k: int = 23):
@@ -512,6 +539,32 @@ class AIndex:
                 f.write(f">u{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
                 written += 1
         return written
+
+    # ---- the unitig graph (Index.unitig_links; aix_unitigs.hip) ------------------------------------------
+    def get_unitig_links(self, cutoff: int = 0) -> List[Tuple[int, str, int, str]]:
+        """[(a, '+' | '-', b, '+' | '-')]: unitig a, traversed forwards (+) or backwards (-), is followed by unitig b with an overlap of 22
+        bases; one tuple per pair of dual links (unitig_link_pairs). The closing link of a circular unitig is not among them."""
+        self._req()
+        return unitig_link_pairs(self._wrapper._need23().unitig_links(cutoff))
+
+    def get_bubbles(self, cutoff: int = 0) -> List[Tuple[int, int]]:
+        """[(u, w)] with u < w: the two arms of every simple bubble (same source end, same sink end, attached nowhere else)."""
+        self._req()
+        mate = self._wrapper._need23().unitig_links(cutoff)["bubble_mate"]
+        u = np.nonzero(mate != np.uint32(_lib.BUBBLE_NONE))[0]
+        return [(a, b) for a, b in zip(u.tolist(), mate[u].tolist()) if a < b]
+
+    def write_gfa(self, path: str, cutoff: int = 0) -> Tuple[int, int]:
+        """GFA 1 of the unitig graph (format_gfa); returns (segments, links) written."""
+        self._req()
+        ix = self._wrapper._need23()
+        segments = links = 0
+        with open(path, "w") as f:
+            for line in format_gfa(ix.unitigs(cutoff), ix.unitig_links(cutoff)):
+                segments += line[0] == "S"
+                links += line[0] == "L"
+                f.write(line + "\n")
+        return segments, links
 
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):

@@ -21,6 +21,7 @@
 //   emit     k_ug_check validates the layout against the index; rocPRIM sorts the live nodes by (unitig, position), which IS unitig
 //            order: k_ug_emit writes offsets, bases, the circular flag and tf along every unitig; tf_sum / min / max come from one
 //            reduce-by-key over that array (no atomic on a per-unitig word).
+//   graph    section 7 below: the links between unitig ends and the simple bubbles, from a layout and the offsets of its emit.
 // Integer only, no LDS, no grid-wide barrier, no spin-wait. Every index derived from 2 n, from an offset or from the total is 64 bits wide.
 #include <algorithm>
 #include <cstdlib>
@@ -512,6 +513,210 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
     return hipStreamSynchronize(s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// 7. the unitig graph: links between unitig ends, simple bubbles (the contract is the block below the compaction's in aindex_hip.h)
+// ---------------------------------------------------------------------------------------------
+// End 2 u + 0 leaves the spelling of linear unitig u through its last oriented k-mer, end 2 u + 1 through rc of its first. The chain:
+//   ends     k_ul_ends: one lane per kid; the member at position 0 / m - 1 of a linear unitig is the kid of end 2 u + 1 / 2 u + 0
+//   probe    k_ul_probe: one quad per end, laid out as k_ug_ports; a live successor y at slot s gives the word 2 kid_unitig[s] + r, and must sit
+//            at position 0 (r = 0) or m - 1 (r = 1) of a linear unitig; the quad's words are compacted in base order: cand[4 e ..], deg[e]
+//   scan     rocPRIM exclusive scan of deg[2 U + 1] (the last is 0) = link_off; link_off[2 U] = E
+//   fill     k_ul_fill: one lane per end copies its words to link_to + link_off[e]
+//   bubbles  k_ul_bubbles: one lane per unitig, the chain of gathers of the bubble rule over link_off / link_to; no handle
+static constexpr uint32_t kLNone = 0xFFFFFFFFu;                   // end_kid: no such end (circular unitig); cand: no word; bubble_mate: none
+
+struct UlCounters {                                               // one zeroed record per call
+    unsigned long long bad, n_ends, n_circular, n_none;
+};
+
+__global__ void __launch_bounds__(kUB) k_ul_ends(uint64_t n, uint64_t U, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
+                                                const uint8_t* __restrict__ kid_flag, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ end_kid,
+                                                UlCounters* __restrict__ ctr) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    unsigned long long bad = 0, ends = 0, circ = 0;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+        const uint64_t u = kid_unitig[kid];
+        if (u == AIX_UNITIG_NONE) continue;
+        if (u >= U) { ++bad; continue; }
+        const uint64_t lo = offsets[u], hi = offsets[u + 1];
+        const uint64_t pos = kid_pos[kid];
+        if (hi < lo + 23 || pos >= hi - lo - 22) { ++bad; continue; }
+        const uint64_t m = hi - lo - 22;
+        if (kid_flag[kid] & 2u) { circ += pos == 0; continue; }
+        if (pos == 0) { end_kid[2 * u + 1] = (uint32_t)kid; ++ends; }
+        if (pos == m - 1) { end_kid[2 * u] = (uint32_t)kid; ++ends; }
+    }
+    ug_count(bad, &ctr->bad);
+    ug_count(ends, &ctr->n_ends);
+    ug_count(circ, &ctr->n_circular);
+}
+
+// One quad per end, 16 per wave. policy as k_ug_ports. cand[4 e + j] = the j-th link word of end e in base order (kLNone behind the degree).
+__global__ void __launch_bounds__(kUB) k_ul_probe(const IndexDev ix_, uint32_t cutoff, int policy, uint64_t U, const uint64_t* __restrict__ kid_unitig,
+                                                 const uint32_t* __restrict__ kid_pos, const uint8_t* __restrict__ kid_flag, const uint64_t* __restrict__ offsets,
+                                                 const uint32_t* __restrict__ end_kid, uint32_t* __restrict__ cand, uint32_t* __restrict__ deg,
+                                                 UlCounters* __restrict__ ctr) {
+    const IndexDev& ix = ix_;
+    const uint64_t NE = 2 * U;
+    const uint32_t lane = threadIdx.x & 63u, b = lane & 3u;
+    FilterGauge fg;
+    unsigned long long bad = 0, none = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * 64;
+    for (uint64_t base = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 6) * 16; base < NE; base += stride) {    // wave-uniform
+        const uint64_t e = base + (lane >> 2);
+        const bool in = e < NE;
+        const uint32_t kid = in ? end_kid[e] : kLNone;
+        const bool has = in && (uint64_t)kid < ix.n;
+        none += in && b == 0 && kid == kLNone;
+        bad += in && b == 0 && kid != kLNone && !has;
+        KeyRec k;
+        k.code = 0; k.tf = 0;
+        uint32_t f = 0;
+        if (has) { k = key_at(ix, kid); f = kid_flag[kid]; }
+        const bool live = has && k.tf > cutoff;
+        const uint64_t x = ug_orient(k.code & kMask46, (f ^ (uint32_t)e) & 1u);
+        const uint64_t y = ((x << 2) | (uint64_t)b) & kMask46;     // next(x, b)
+        const bool absence = policy == 1 ? true : (policy == 2 ? false : fg.on);
+        const Probe q = slot23_wave(ix, live, y, absence);
+        if (policy == 0) fg.seen(live, q.found);
+        bool ylive = live && q.found && q.tf > cutoff && q.slot < ix.n;
+        uint32_t w = kLNone;
+        if (ylive) {
+            const uint64_t v = kid_unitig[q.slot];
+            if (v < U) {
+                const uint32_t fv = kid_flag[q.slot];
+                const uint64_t pos = kid_pos[q.slot], lo = offsets[v], hi = offsets[v + 1];
+                const uint32_t r = (y <= revcomp(y, 23) ? 0u : 1u) ^ (fv & 1u);
+                // a successor of an end is the first k-mer of a linear unitig in the entering orientation
+                const bool ok = !(fv & 2u) && hi >= lo + 23 && (r ? pos + 1 == hi - lo - 22 : pos == 0);
+                w = 2u * (uint32_t)v + r;
+                bad += !ok;
+            } else {
+                ++bad;
+                ylive = false;
+            }
+        }
+        const uint32_t l0 = ug_quad_bcast<0>(ylive), l1 = ug_quad_bcast<1>(ylive), l2 = ug_quad_bcast<2>(ylive), l3 = ug_quad_bcast<3>(ylive);
+        const uint32_t w0 = ug_quad_bcast<0>(w), w1 = ug_quad_bcast<1>(w), w2 = ug_quad_bcast<2>(w), w3 = ug_quad_bcast<3>(w);
+        const uint32_t p1 = l0, p2 = l0 + l1, p3 = p2 + l2, d = p3 + l3;
+        uint32_t c[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            c[j] = (l0 && j == 0) ? w0 : ((l1 && p1 == j) ? w1 : ((l2 && p2 == j) ? w2 : ((l3 && p3 == j) ? w3 : kLNone)));
+        if (in && b == 0) {
+            *reinterpret_cast<uint4*>(cand + 4 * e) = make_uint4(c[0], c[1], c[2], c[3]);
+            deg[e] = d;
+        }
+    }
+    ug_count(bad, &ctr->bad);
+    ug_count(none, &ctr->n_none);
+}
+
+struct UlWiden {
+    __host__ __device__ uint64_t operator()(uint32_t d) const { return d; }
+};
+
+__global__ void __launch_bounds__(kUB) k_ul_fill(uint64_t NE, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ cand, uint64_t E,
+                                                uint32_t* __restrict__ link_to) {
+    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t e = (uint64_t)blockIdx.x * kUB + threadIdx.x; e < NE; e += stride) {
+        const uint64_t o = link_off[e], o1 = link_off[e + 1];
+        const uint4 c4 = *reinterpret_cast<const uint4*>(cand + 4 * e);
+        const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            if (o + j < o1 && o + j < E) link_to[o + j] = c[j];
+    }
+}
+
+// degree and first target of end e; e < NE is the caller's business, every other index is checked here. A degree above 4 reads as 5.
+__device__ __forceinline__ uint32_t ul_deg(const uint64_t* __restrict__ link_off, uint64_t E, uint64_t e, uint64_t& at) {
+    at = link_off[e];
+    const uint64_t hi = link_off[e + 1];
+    if (hi < at || hi > E) return 5u;
+    return hi - at > 4 ? 5u : (uint32_t)(hi - at);
+}
+
+__global__ void __launch_bounds__(kUB) k_ul_bubbles(uint64_t U, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, uint64_t E,
+                                                   uint32_t* __restrict__ mate) {
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kUB;
+    for (uint64_t u = (uint64_t)blockIdx.x * kUB + threadIdx.x; u < U; u += stride) {
+        uint32_t res = kLNone;
+        uint64_t aR, aL, aF, aS, aX, aY;
+        do {
+            if (ul_deg(link_off, E, 2 * u, aR) != 1 || ul_deg(link_off, E, 2 * u + 1, aL) != 1) break;
+            const uint64_t tR = link_to[aR], tL = link_to[aL];
+            if (tR >= NE || tL >= NE) break;
+            if (ul_deg(link_off, E, tL ^ 1, aF) != 2) break;       // the source end
+            const uint64_t t0 = link_to[aF], t1 = link_to[aF + 1];
+            if (t0 != 2 * u && t1 != 2 * u) break;
+            const uint64_t x = t0 == 2 * u ? t1 : t0;
+            if (x >= NE || (x >> 1) == u) break;
+            if (ul_deg(link_off, E, tR ^ 1, aS) != 2) break;       // the sink: in-degree 2
+            if (ul_deg(link_off, E, x, aX) != 1 || link_to[aX] != tR) break;
+            if (ul_deg(link_off, E, x ^ 1, aY) != 1 || link_to[aY] != tL) break;
+            res = (uint32_t)(x >> 1);
+        } while (false);
+        mate[u] = res;
+    }
+}
+
+// *bad: the layout or the offsets do not belong to (index, cutoff, U), nothing was written then; *E is set once link_off is written: if it is
+// above link_cap, link_to is untouched. Synchronises `s`.
+static hipError_t ul_links(const aix_index* h, uint32_t cutoff, const uint64_t* kid_unitig, const uint32_t* kid_pos, const uint8_t* kid_flag, uint64_t U,
+                           const uint64_t* offsets, uint64_t* link_off, uint32_t* link_to, uint64_t link_cap, uint64_t* E_out, bool* bad, hipStream_t s) {
+    const IndexDev ix = h->dev();
+    const uint64_t n = ix.n, NE = 2 * U, cap = ug_test_grid();
+    const dim3 blk(kUB);
+    *bad = false;
+    DevArr ctr_a(s), lc_a(s), ek(s), cand(s), deg(s), tmp(s);
+    UG(ctr_a.alloc(sizeof(UgCounters)));
+    UG(lc_a.alloc(sizeof(UlCounters)));
+    UgCounters* ctr = (UgCounters*)ctr_a.p;
+    UlCounters* lc = (UlCounters*)lc_a.p;
+    UgCounters hc;
+    UlCounters hl;
+    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    UG(hipMemsetAsync(lc, 0, sizeof(UlCounters), s));
+    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
+    UG(ug_read(&hc, ctr, s));
+    if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
+    if (U == 0) {
+        UG(hipMemsetAsync(link_off, 0, 8, s));
+        *E_out = 0;
+        return hipStreamSynchronize(s);
+    }
+    UG(ek.alloc(4 * NE));
+    UG(hipMemsetAsync(ek.p, 0xFF, 4 * NE, s));
+    UGL(k_ul_ends, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, n, U, kid_unitig, kid_pos, kid_flag, offsets, (uint32_t*)ek.p, lc);
+    UG(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
+    UG(hipStreamSynchronize(s));
+    if (hl.bad || hl.n_circular > U || hl.n_ends != 2 * (U - hl.n_circular)) { *bad = true; return hipSuccess; }
+    const uint64_t n_circular = hl.n_circular;
+    UG(cand.alloc(16 * NE));
+    UG(deg.alloc(4 * (NE + 1)));
+    UG(hipMemsetAsync((uint32_t*)deg.p + NE, 0, 4, s));
+    UGL(k_ul_probe, dim3(ug_grid(NE, 2 * 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), U, kid_unitig, kid_pos, kid_flag, offsets, (const uint32_t*)ek.p,
+        (uint32_t*)cand.p, (uint32_t*)deg.p, lc);
+    UG(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
+    UG(hipStreamSynchronize(s));
+    // every written end was written once: 2 (U - circular) writes, and exactly the two ends of every circular unitig are empty
+    if (hl.bad || hl.n_none != 2 * n_circular) { *bad = true; return hipSuccess; }
+    ek.drop();
+    auto din = rocprim::make_transform_iterator((const uint32_t*)deg.p, UlWiden());
+    size_t tb = 0;
+    UG(rocprim::exclusive_scan(nullptr, tb, din, link_off, (uint64_t)0, (size_t)(NE + 1), rocprim::plus<uint64_t>(), s));
+    UG(tmp.alloc(tb ? tb : 1));
+    UG(rocprim::exclusive_scan(tmp.p, tb, din, link_off, (uint64_t)0, (size_t)(NE + 1), rocprim::plus<uint64_t>(), s));
+    uint64_t E = 0;
+    UG(hipMemcpyAsync(&E, link_off + NE, 8, hipMemcpyDeviceToHost, s));
+    UG(hipStreamSynchronize(s));
+    *E_out = E;
+    if (E > link_cap || E == 0) return hipSuccess;
+    UGL(k_ul_fill, dim3(ug_grid(NE, 4 * kUB, cap)), blk, 0, s, NE, (const uint64_t*)link_off, (const uint32_t*)cand.p, E, link_to);
+    return hipStreamSynchronize(s);
+}
+
 }  // namespace aix
 
 // ---------------------------------------------------------------------------------------------
@@ -609,5 +814,89 @@ extern "C" int aix_unitigs(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_
     for (int i = 0; i < 10; ++i)
         if (outs[i].dst) *outs[i].dst = host[i];
     *n_unitigs_out = U;
+    return AIX_OK;
+}
+
+extern "C" int aix_unitig_links_dev(aix_index_t* h, uint32_t cutoff, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag, uint64_t U,
+                                    const uint64_t* d_offsets, uint64_t* d_link_off, uint32_t* d_link_to, uint64_t link_cap, uint64_t* n_links_out, void* stream) {
+    const int st = ug_check_handle(h);
+    if (st) return st;
+    if (!d_kid_unitig || !d_kid_pos || !d_kid_flag || !d_offsets || !d_link_off || !n_links_out) return AIX_ERR_ARG;
+    if (link_cap && !d_link_to) return AIX_ERR_ARG;
+    if (U > h->n) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    bool bad = false;
+    uint64_t E = 0;
+    UGCHK(ul_links(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_link_off, d_link_to, link_cap, &E, &bad, (hipStream_t)stream));
+    if (bad) return AIX_ERR_ARG;
+    *n_links_out = E;
+    return E > link_cap ? AIX_ERR_ARG : AIX_OK;
+}
+
+extern "C" int aix_unitig_bubbles_dev(uint64_t U, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E, uint32_t* d_bubble_mate, void* stream) {
+    if (!d_link_off) return AIX_ERR_ARG;
+    if (U && !d_bubble_mate) return AIX_ERR_ARG;
+    if (E && !d_link_to) return AIX_ERR_ARG;
+    if (U > (uint64_t)kWNone / 2 || E > 8 * U) return AIX_ERR_ARG;
+    if (U == 0) return AIX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ul_bubbles, dim3(ug_grid(U, 4 * kUB, ug_test_grid())), dim3(kUB), 0, s, U, d_link_off, d_link_to, E, d_bubble_mate);
+    UGCHK(hipGetLastError());
+    UGCHK(hipStreamSynchronize(s));
+    return AIX_OK;
+}
+
+extern "C" int aix_unitig_links(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, uint64_t* n_links_out, uint64_t** link_off_out, uint32_t** link_to_out,
+                                uint32_t** bubble_mate_out) {
+    const int st = ug_check_handle(h);
+    if (st) return st;
+    if (!n_unitigs_out || !n_links_out || !link_off_out || !link_to_out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    const uint64_t n = h->n;
+    DevArr ku, kp, kf, off, bs, ci, ts, tn, tx, lo, lt, bm;
+    UGCHK(ku.alloc(8 * n));
+    UGCHK(kp.alloc(4 * n));
+    UGCHK(kf.alloc(n));
+    uint64_t U = 0, total = 0, n_live = 0, n_circ = 0, E = 0;
+    int r = aix_unitigs_layout_dev(h, cutoff, (uint64_t*)ku.p, (uint32_t*)kp.p, (uint8_t*)kf.p, &U, &total, &n_live, &n_circ, nullptr);
+    if (r) return r;
+    UGCHK(off.alloc(8 * (U + 1)));
+    UGCHK(bs.alloc(total));
+    UGCHK(ci.alloc(U));
+    UGCHK(ts.alloc(8 * U));
+    UGCHK(tn.alloc(4 * U));
+    UGCHK(tx.alloc(4 * U));
+    r = aix_unitigs_emit_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (uint64_t*)off.p, (uint8_t*)bs.p, (uint8_t*)ci.p,
+                             (uint64_t*)ts.p, (uint32_t*)tn.p, (uint32_t*)tx.p, nullptr, nullptr);
+    if (r) return r;
+    bs.drop(); ci.drop(); ts.drop(); tn.drop(); tx.drop();
+    UGCHK(lo.alloc(8 * (2 * U + 1)));
+    UGCHK(lt.alloc(4 * 8 * U));
+    r = aix_unitig_links_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (const uint64_t*)off.p, (uint64_t*)lo.p,
+                             (uint32_t*)lt.p, 8 * U, &E, nullptr);
+    if (r) return r;
+    if (bubble_mate_out) {
+        UGCHK(bm.alloc(4 * U));
+        r = aix_unitig_bubbles_dev(U, (const uint64_t*)lo.p, (const uint32_t*)lt.p, E, (uint32_t*)bm.p, nullptr);
+        if (r) return r;
+    }
+    struct Out { void** dst; const void* src; uint64_t bytes; } outs[] = {
+        {(void**)link_off_out, lo.p, 8 * (2 * U + 1)}, {(void**)link_to_out, lt.p, 4 * E}, {(void**)bubble_mate_out, bm.p, 4 * U}};
+    void* host[3] = {nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) {
+        if (!outs[i].dst) continue;
+        host[i] = malloc(outs[i].bytes ? outs[i].bytes : 1);
+        if (!host[i]) e = hipErrorOutOfMemory;
+        else if (outs[i].bytes) e = hipMemcpy(host[i], outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) {
+        for (void* p : host) free(p);
+        UGCHK(e);
+    }
+    for (int i = 0; i < 3; ++i)
+        if (outs[i].dst) *outs[i].dst = host[i];
+    *n_unitigs_out = U;
+    *n_links_out = E;
     return AIX_OK;
 }

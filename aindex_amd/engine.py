@@ -846,6 +846,38 @@ class Index:
         out.update(U=U, n_live=live, n_circular=int(out["circular"].sum()))
         return out
 
+    def unitig_links_t(self, cutoff: int = 0, unitigs=None) -> dict:
+        """The unitig graph at `cutoff` as a dict of device tensors (u64 / u32 bit patterns): link_off int64[2 U + 1], link_to int32[E] — the
+        links of end 2 u + side (side 0 leaves unitig u at the right end of its spelling, side 1 at the left) are the words 2 v + r at
+        link_to[link_off[e] : link_off[e + 1]] —, bubble_mate int32[U] (-1 = none), and the ints U, E. unitigs: what unitigs_t(cutoff) returned."""
+        import torch
+        un = unitigs if unitigs is not None else self.unitigs_t(cutoff)
+        ku, kp, kf, off, u = un["kid_unitig"], un["kid_pos"], un["kid_flag"], un["offsets"], int(un["U"])
+        for t in (ku, kp, kf, off):
+            self._chk_dev(t)
+        if off.numel() != u + 1:
+            raise ValueError("offsets must hold U + 1 entries")
+        dev = ku.device
+        link_off = torch.empty(2 * u + 1, dtype=torch.int64, device=dev)
+        link_to = torch.empty(8 * u, dtype=torch.int32, device=dev)
+        mate = torch.empty(u, dtype=torch.int32, device=dev)
+        e = C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_unitig_links_dev(self._h, cutoff, p(ku), p(kp), p(kf), u, p(off), p(link_off), p(link_to), 8 * u, C.byref(e),
+                                             _stream_ptr(self.device)), "aix_unitig_links_dev")
+            link_to = link_to[:e.value].clone()
+            check(lib().aix_unitig_bubbles_dev(u, p(link_off), p(link_to), e.value, p(mate), _stream_ptr(self.device)), "aix_unitig_bubbles_dev")
+        return {"link_off": link_off, "link_to": link_to, "bubble_mate": mate, "U": u, "E": e.value}
+
+    def unitig_links(self, cutoff: int = 0) -> dict:
+        """unitig_links_t through host memory: link_off uint64[2 U + 1], link_to uint32[E], bubble_mate uint32[U] (0xFFFFFFFF = none), U, E."""
+        ps = [vp() for _ in range(3)]
+        u, e = C.c_uint64(), C.c_uint64()
+        check(lib().aix_unitig_links(self._h, cutoff, C.byref(u), C.byref(e), *[C.byref(q) for q in ps]), "aix_unitig_links")
+        return {"link_off": self._take_as(ps[0], 2 * u.value + 1, np.uint64), "link_to": self._take_as(ps[1], e.value, np.uint32),
+                "bubble_mate": self._take_as(ps[2], u.value, np.uint32), "U": u.value, "E": e.value}
+
     # ---- read cleaning (aix_readfix.hip) ---------------------------------------------------------
     @staticmethod
     def _fix_args(verify: int, max_fixes: int):

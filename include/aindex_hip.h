@@ -576,6 +576,57 @@ int aix_unitigs(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, uint64
                 uint64_t** kid_unitig_out /* nullable */, uint32_t** kid_pos_out /* nullable */, uint8_t** kid_flag_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * The unitig graph: which unitig follows which (links between unitig ends), and simple two-armed bubbles.
+ * (The reference has no counterpart; the notation is that of the compaction above.)
+ *
+ * Handles. Exactly those of aix_unitigs_layout_dev: a 23-mer handle with canonical_only == 1, else AIX_ERR_UNSUPPORTED; a 13-mer handle
+ * AIX_ERR_MODE; an empty index AIX_ERR_UNSUPPORTED; NULL where a pointer is needed AIX_ERR_ARG. All of these are decided before anything
+ * is allocated or launched. The call takes a layout (kid_unitig, kid_pos, kid_flag, U) and the offsets[U + 1] of the emit and validates
+ * them first against the index and the cutoff, as the emit does, and against each other: every linear unitig has exactly one member at
+ * position 0 and one at position m - 1, every member's position is below m. Any disagreement is AIX_ERR_ARG with no output array
+ * written. No address outside the given sizes is read or written, whatever the arrays hold.
+ *
+ * Ends. A linear unitig u of m = offsets[u + 1] - offsets[u] - 22 k-mers has two ends: end 2 u + 0 ("u+") leaves the spelling at its
+ * right end, through the last oriented k-mer x of the spelling; end 2 u + 1 ("u-") leaves it at its left end, through rc of the first
+ * oriented k-mer. A circular unitig has no ends: its two entries have degree 0.
+ * Links. The links of end e are the live members of {next(x, b), b = A, C, G, T}, in base order (live as in the layout: canon(y) stored
+ * with tf > cutoff). Each link is one u32 word 2 v + r: v is the unitig of y; r = 0 if y appears in v's spelling as given — v is entered
+ * at its position 0 and traversed forwards ("v+") — and r = 1 if y appears reverse-complemented — v is entered at position m_v - 1 and
+ * traversed backwards ("v-"). Every link overlaps by exactly 22 bases.
+ * A live successor y of a path end x is always the first k-mer of its unitig in the entering orientation, and that unitig is never
+ * circular: a unitig edge z -> y needs |in(y)| == 1, so z == x, and x -> y would itself be a unitig edge. The call checks this for every
+ * link; a violation is an inconsistent layout (AIX_ERR_ARG).
+ * Duality. (e -> t) is a link iff (t ^ 1 -> e ^ 1) is one. Self-dual links exist: a hairpin end gives u+ -> u-; a homopolymer gives
+ * u+ -> u+ and its dual u- -> u-.
+ *
+ * Outputs. link_off u64[2 U + 1], the exclusive prefix of the end degrees (0 .. 4 each); link_to u32[E], E = link_off[2 U] <= 8 U.
+ * U = 0 gives link_off = {0} and E = 0. A pure function of (key set, tf, cutoff) — not of the MPHF, the launch geometry or any probe
+ * switch.
+ *
+ * Simple bubbles. bubble_mate u32[U], AIX_BUBBLE_NONE for none. Linear unitig u is an arm with mate w iff
+ *   deg(2 u) == deg(2 u + 1) == 1, with tR and tL those two link words;
+ *   the source end f = tL ^ 1 has degree exactly 2, and its targets are {2 u + 0, x} with w = x >> 1 != u;
+ *   the sink has in-degree exactly 2: deg(tR ^ 1) == 2;
+ *   the other arm, traversed as x, is attached the same way and nowhere else: deg(x) == 1 and its link is tR, deg(x ^ 1) == 1 and its
+ *   link is tL.
+ * The relation is symmetric (mate[mate[u]] == u); a circular unitig never qualifies. Length and abundance thresholds ("a tip of at most
+ * 2 k bases", "the weaker arm") are the caller's: one line over offsets, tf_sum and the degrees.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_BUBBLE_NONE 0xFFFFFFFFu
+/* d_link_off[2 U + 1] and d_link_to[link_cap] (NULL allowed when link_cap == 0). If E > link_cap: AIX_ERR_ARG with *n_links_out = E,
+ * d_link_off written and d_link_to untouched — a caller may size and repeat; 8 U always suffices. Returns after its work on `stream`
+ * has completed. Scratch: see DESIGN 5j. */
+int aix_unitig_links_dev(aix_index_t* h, uint32_t cutoff, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag,
+                         uint64_t U, const uint64_t* d_offsets, uint64_t* d_link_off, uint32_t* d_link_to, uint64_t link_cap,
+                         uint64_t* n_links_out, void* stream);
+/* d_bubble_mate[U] from d_link_off[2 U + 1] and d_link_to[E]; needs no handle (the current device). Every index read from the arrays is
+ * checked against 2 U and E before it is used; E > 8 U or a NULL array is AIX_ERR_ARG. Returns after its work on `stream` has completed. */
+int aix_unitig_bubbles_dev(uint64_t U, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E, uint32_t* d_bubble_mate, void* stream);
+/* Layout, offsets, links and bubbles for host memory: every array is malloc'd (aix_free). */
+int aix_unitig_links(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, uint64_t* n_links_out, uint64_t** link_off_out,
+                     uint32_t** link_to_out, uint32_t** bubble_mate_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
