@@ -566,6 +566,50 @@ class AIndex:
                 f.write(line + "\n")
         return segments, links
 
+    # ---- contigs (Index.graph_clean_t; aix_graphclean.hip) -----------------------------------------------
+    def _contig_graph(self, cutoff: int, tip_max_kmers: int, bubble_max_kmers: int, rounds: int) -> dict:
+        """the cleaned graph as numpy arrays (u64 / u32): unitigs and links at `cutoff` on the device, up to `rounds` rounds of cleaning"""
+        self._req()
+        ix = self._wrapper._need23()
+        un = ix.unitigs_t(cutoff)
+        g, _ = ix.graph_clean_t(un, ix.unitig_links_t(cutoff, unitigs=un), tip_max_kmers, bubble_max_kmers, rounds)
+        return ix._graph_to_host({k: g[k] for k in ix.GRAPH_KEYS})
+
+    def get_contigs(self, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
+                    min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
+        """[(sequence, tf_sum, circular)] of every contig with at least min_kmers k-mers, in contig order: the unitigs at `cutoff` after up to
+        `rounds` rounds of tip clipping (tips of at most tip_max_kmers k-mers), bubble popping and recompaction."""
+        g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
+        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
+                if off[i + 1] - off[i] - 22 >= min_kmers]
+
+    def write_contigs(self, path: str, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, min_kmers: int = 1) -> int:
+        """FASTA of get_contigs: >c{id} LN:i:{len} KC:i:{tf_sum} km:f:{tf_sum/m:.1f}[ circular]; returns the number of records written."""
+        g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
+        written = 0
+        with open(path, "w") as f:
+            for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
+                ln = off[i + 1] - off[i]
+                if ln - 22 < min_kmers:
+                    continue
+                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
+                written += 1
+        return written
+
+    def write_contigs_gfa(self, path: str, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3) -> Tuple[int, int]:
+        """GFA 1 of the cleaned graph through format_gfa (segments are named u{contig id}, as format_gfa names them); returns (segments,
+        links) written."""
+        g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        segments = links = 0
+        with open(path, "w") as f:
+            for line in format_gfa(g, g):
+                segments += line[0] == "S"
+                links += line[0] == "L"
+                f.write(line + "\n")
+        return segments, links
+
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):
         """(corrected reads, records): every read's weak 23-windows (tf <= true_errors, read.hpp:296) are looked for, up to max_fixes

@@ -44,7 +44,7 @@
 //     AIX_K1_ROCPRIM               AB  set / not set                 -      K1 through the radix sort (aix_k1.hip)
 //     AIX_K1_TEST_REGION           H   >= 1                          -      chunk ids per workgroup of K1
 //     AIX_DBJ_FILTER               AB  0, 1, 2                       1/2/0  (neighbours / walks / read fixes) absence filter of those kernels: 0 per-trip gauge, 1 always, 2 never (aix_debruijn.hip, aix_readfix.hip; aix_unitigs.hip takes the walks' default)
-//     AIX_UG_TEST_GRID             H   1 .. 65536                    -      workgroups at most of k_ug_ports and of every grid-stride launch of the compaction (many trips on a small index; aix_unitigs.hip)
+//     AIX_UG_TEST_GRID             H   1 .. 65536                    -      workgroups at most of k_ug_ports and of every grid-stride launch of the compaction (many trips on a small index; aix_unitigs.hip, aix_graphclean.hip)
 //     AIX_INGEST_PART_MB           T   1 .. 2047                     256    part size of the streaming ingestion (aix_ingest.hip)
 //     AIX_INGEST_TEST_PART         H   >= 1 bytes                    -      part size in bytes (cuts everywhere)
 //   once per process

@@ -878,6 +878,164 @@ class Index:
         return {"link_off": self._take_as(ps[0], 2 * u.value + 1, np.uint64), "link_to": self._take_as(ps[1], e.value, np.uint32),
                 "bubble_mate": self._take_as(ps[2], u.value, np.uint32), "U": u.value, "E": e.value}
 
+    # ---- graph cleaning (aix_graphclean.hip) ------------------------------------------------------
+    GRAPH_KEYS = ("offsets", "bases", "circular", "tf_sum", "tf_min", "tf_max", "link_off", "link_to")
+    GRAPH_DTYPES = (np.uint64, np.uint8, np.uint8, np.uint64, np.uint32, np.uint32, np.uint64, np.uint32)
+
+    @classmethod
+    def _graph_of(cls, unitigs: dict, links) -> dict:
+        """the eight arrays of a unitig set from unitigs_t / unitig_links_t dicts, or from one merged dict (links None)"""
+        return {k: (unitigs[k] if k in unitigs else links[k]) for k in cls.GRAPH_KEYS}
+
+    def _graph_ptrs(self, g: dict):
+        for k in self.GRAPH_KEYS:
+            self._chk_dev(g[k])
+        u, e = g["offsets"].numel() - 1, g["link_to"].numel()
+        if u < 0 or g["link_off"].numel() != 2 * u + 1 or any(g[k].numel() != u for k in ("circular", "tf_sum", "tf_min", "tf_max")):
+            raise ValueError("the arrays of a unitig set must hold U + 1 offsets, U values each and 2 U + 1 link offsets")
+        return u, e, {k: vp(g[k].data_ptr()) for k in self.GRAPH_KEYS}
+
+    def graph_mark_t(self, unitigs: dict, links: dict = None, tip_max_kmers: int = 46, bubble_max_kmers: int = 46):
+        """Tips and weaker bubble arms of a unitig set in HBM: (remove uint8[U] — 0 keep, 1 tip, 2 arm —, n_tips, n_arms). links None:
+        `unitigs` holds the link arrays too. A bubble_mate in either dict is used, else it is computed."""
+        import torch
+        g = self._graph_of(unitigs, links)
+        u, e, q = self._graph_ptrs(g)
+        mate = (links or {}).get("bubble_mate", unitigs.get("bubble_mate"))
+        if mate is not None:
+            self._chk_dev(mate)
+        remove = torch.empty(u, dtype=torch.uint8, device=g["offsets"].device)
+        tips, arms = C.c_uint64(), C.c_uint64()
+        with torch.cuda.device(self.device):
+            check(lib().aix_graph_mark_dev(u, q["offsets"], q["circular"], q["tf_sum"], q["link_off"], q["link_to"], e,
+                                           vp(mate.data_ptr()) if mate is not None else None, tip_max_kmers, bubble_max_kmers, vp(remove.data_ptr()),
+                                           C.byref(tips), C.byref(arms), _stream_ptr(self.device)), "aix_graph_mark_dev")
+        return remove, tips.value, arms.value
+
+    def graph_compact_t(self, unitigs: dict, links: dict, remove) -> dict:
+        """The survivors of `remove` (uint8[U], non-zero = removed) compacted into contigs: a unitig set in the format of unitigs_t /
+        unitig_links_t merged (offsets, bases, circular, tf_sum, tf_min, tf_max, link_off, link_to, bubble_mate, U, E, n_circular), plus the
+        map unitig_contig int32[U] (-1 = removed), unitig_pos int64[U], unitig_flag uint8[U]. links None: `unitigs` is a merged dict."""
+        import torch
+        g = self._graph_of(unitigs, links)
+        u, e, q = self._graph_ptrs(g)
+        self._chk_dev(remove)
+        if remove.numel() != u:
+            raise ValueError("remove must hold U entries")
+        dev = g["offsets"].device
+        uc = torch.empty(u, dtype=torch.int32, device=dev)
+        up = torch.empty(u, dtype=torch.int64, device=dev)
+        uf = torch.empty(u, dtype=torch.uint8, device=dev)
+        c, total, e2, circ = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_graph_compact_layout_dev(u, q["offsets"], q["bases"], q["circular"], q["link_off"], q["link_to"], e, p(remove), p(uc), p(up), p(uf),
+                                                     C.byref(c), C.byref(total), C.byref(e2), C.byref(circ), _stream_ptr(self.device)),
+                  "aix_graph_compact_layout_dev")
+            n = c.value
+            out = {"offsets": torch.empty(n + 1, dtype=torch.int64, device=dev), "bases": torch.empty(total.value, dtype=torch.uint8, device=dev),
+                   "circular": torch.empty(n, dtype=torch.uint8, device=dev), "tf_sum": torch.empty(n, dtype=torch.int64, device=dev),
+                   "tf_min": torch.empty(n, dtype=torch.int32, device=dev), "tf_max": torch.empty(n, dtype=torch.int32, device=dev),
+                   "link_off": torch.empty(2 * n + 1, dtype=torch.int64, device=dev), "link_to": torch.empty(e2.value, dtype=torch.int32, device=dev)}
+            check(lib().aix_graph_compact_emit_dev(u, *[q[k] for k in self.GRAPH_KEYS[:6]], q["link_off"], q["link_to"], e, p(remove), p(uc), p(up), p(uf), n,
+                                                   total.value, e2.value, *[p(out[k]) for k in self.GRAPH_KEYS], _stream_ptr(self.device)),
+                  "aix_graph_compact_emit_dev")
+            mate = torch.empty(n, dtype=torch.int32, device=dev)
+            check(lib().aix_unitig_bubbles_dev(n, p(out["link_off"]), p(out["link_to"]), e2.value, p(mate), _stream_ptr(self.device)), "aix_unitig_bubbles_dev")
+        out.update(bubble_mate=mate, U=n, E=e2.value, n_circular=circ.value, unitig_contig=uc, unitig_pos=up, unitig_flag=uf)
+        return out
+
+    def graph_clean_t(self, unitigs: dict, links: dict = None, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 1):
+        """Mark then compact, repeated until nothing is removed or `rounds` is reached: (graph, rounds done). The graph is a merged dict as
+        graph_compact_t returns it; its map arrays are those of the last round (absent when no round removed anything)."""
+        g = dict(self._graph_of(unitigs, links))
+        g.update(U=g["offsets"].numel() - 1, E=g["link_to"].numel())
+        mate = (links or {}).get("bubble_mate", unitigs.get("bubble_mate"))
+        if mate is not None:
+            g["bubble_mate"] = mate
+        done = 0
+        while done < rounds:
+            remove, tips, arms = self.graph_mark_t(g, None, tip_max_kmers, bubble_max_kmers)
+            if tips + arms == 0:
+                break
+            g = self.graph_compact_t(g, None, remove)
+            done += 1
+        return g, done
+
+    def graph_clean_round(self, graph: dict, tip_max_kmers: int = 46, bubble_max_kmers: int = 46) -> dict:
+        """One round through host memory (aix_graph_clean): numpy arrays in (the eight arrays of a unitig set), numpy arrays out — G', remove
+        uint8[U], the map, and the ints U, E, n_tips, n_arms."""
+        a = [np.ascontiguousarray(graph[k], dtype=dt) for k, dt in zip(self.GRAPH_KEYS, self.GRAPH_DTYPES)]
+        u, e = a[0].shape[0] - 1, a[7].shape[0]
+        if u < 0 or a[6].shape[0] != 2 * u + 1 or any(a[i].shape[0] != u for i in (2, 3, 4, 5)) or (u and a[1].shape[0] != int(a[0][u])):
+            raise ValueError("the arrays of a unitig set must hold U + 1 offsets, offsets[U] bases, U values each and 2 U + 1 link offsets")
+        ps = [vp() for _ in range(12)]
+        n = [C.c_uint64() for _ in range(4)]
+        with self._device_ctx():
+            check(lib().aix_graph_clean(u, *[x.ctypes.data_as(vp) for x in a], e, tip_max_kmers, bubble_max_kmers, *[C.byref(x) for x in n],
+                                        *[C.byref(x) for x in ps]), "aix_graph_clean")
+        c, e2 = n[0].value, n[1].value
+        off = self._take_as(ps[0], c + 1, np.uint64)
+        sizes = (None, int(off[c]), c, c, c, c, 2 * c + 1, e2, u, u, u, u)
+        names = self.GRAPH_KEYS + ("remove", "unitig_contig", "unitig_pos", "unitig_flag")
+        types = self.GRAPH_DTYPES + (np.uint8, np.uint32, np.uint64, np.uint8)
+        out = {"offsets": off}
+        for i in range(1, 12):
+            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+        out.update(U=c, E=e2, n_tips=n[2].value, n_arms=n[3].value)
+        return out
+
+    def graph_mark(self, unitigs: dict, links: dict = None, tip_max_kmers: int = 46, bubble_max_kmers: int = 46) -> np.ndarray:
+        """graph_mark_t through host memory: numpy arrays in, remove uint8[U] out."""
+        return self.graph_mark_t(self._graph_to_device(unitigs, links), None, tip_max_kmers, bubble_max_kmers)[0].cpu().numpy()
+
+    def graph_compact(self, unitigs: dict, links: dict, remove) -> dict:
+        """graph_compact_t through host memory: numpy arrays in and out (u64 / u32 as in Index.unitigs and Index.unitig_links)."""
+        import torch
+        r = torch.from_numpy(np.ascontiguousarray(remove, dtype=np.uint8)).to(f"cuda:{self.device}")
+        return self._graph_to_host(self.graph_compact_t(self._graph_to_device(unitigs, links), None, r))
+
+    def graph_clean(self, unitigs: dict, links: dict = None, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 1):
+        """graph_clean_t through host memory: (graph of numpy arrays, rounds done); each round is one aix_graph_clean call."""
+        g = {k: np.ascontiguousarray(self._graph_of(unitigs, links)[k], dtype=dt) for k, dt in zip(self.GRAPH_KEYS, self.GRAPH_DTYPES)}
+        g.update(U=g["offsets"].shape[0] - 1, E=g["link_to"].shape[0])
+        done = 0
+        while done < rounds:
+            nxt = self.graph_clean_round(g, tip_max_kmers, bubble_max_kmers)
+            if nxt["n_tips"] + nxt["n_arms"] == 0:
+                break
+            g = nxt
+            done += 1
+        return g, done
+
+    def _device_ctx(self):
+        """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
+        import contextlib
+        import sys
+        torch = sys.modules.get("torch")
+        return torch.cuda.device(self.device) if torch is not None and torch.cuda.is_available() else contextlib.nullcontext()
+
+    def _graph_to_device(self, unitigs: dict, links) -> dict:
+        import torch
+        g = self._graph_of(unitigs, links)
+        signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}
+        out = {}
+        for k, dt in zip(self.GRAPH_KEYS, self.GRAPH_DTYPES):
+            a = np.ascontiguousarray(g[k], dtype=dt)
+            out[k] = torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).to(f"cuda:{self.device}")
+        return out
+
+    @staticmethod
+    def _graph_to_host(g: dict) -> dict:
+        unsigned = {np.dtype(np.int64): np.uint64, np.dtype(np.int32): np.uint32}
+        out = {}
+        for k, v in g.items():
+            if hasattr(v, "cpu"):
+                a = v.cpu().numpy()
+                v = a.view(unsigned.get(a.dtype, a.dtype))
+            out[k] = v
+        return out
+
     # ---- read cleaning (aix_readfix.hip) ---------------------------------------------------------
     @staticmethod
     def _fix_args(verify: int, max_fixes: int):

@@ -627,6 +627,99 @@ int aix_unitig_links(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_out, u
                      uint32_t** link_to_out, uint32_t** bubble_mate_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph cleaning: clip tips, pop bubbles, and compact the surviving unitigs again into contigs.
+ * (The reference has no counterpart; the notation is that of the two blocks above. tests/graph_clean_ref.py restates this block.)
+ *
+ * A unitig set G is (U, offsets u64[U + 1], bases u8[offsets[U]], circular u8[U], tf_sum u64[U], tf_min / tf_max u32[U],
+ * link_off u64[2 U + 1], link_to u32[E]): what aix_unitigs_emit_dev and aix_unitig_links_dev write, and what the compaction below writes,
+ * so the step can be applied to its own output. m_u = offsets[u + 1] - offsets[u] - 22; ends, link words 2 v + r and duality as above.
+ * No call takes an index handle: they work on device arrays of the current device. All are asynchronous on `stream` and return after
+ * their work on it has completed. Scratch comes from the pool and goes back on every path; AIX_ERR_NOMEM keeps nothing.
+ *
+ * Validation (every call, before anything is written; a violation is AIX_ERR_ARG with no output touched): offsets ascend by at least 23
+ * per unitig; link_off starts at 0, ascends, ends at E, and no end has more than 4 links (so E <= 8 U); every link word is below 2 U; a
+ * circular unitig has no link and is no link's target; every surviving link e -> t has its dual t ^ 1 -> e ^ 1 (mark: every link).
+ * Every index read from an input array is checked against U, 2 U, E and offsets[U] before it is used. U > 2^31 - 4 is
+ * AIX_ERR_UNSUPPORTED (an end must fit a 32-bit word). A NULL pointer where one is needed is AIX_ERR_ARG. The bases are taken to be
+ * upper-case A, C, G, T (what the emit writes); this is not checked: a byte c counts as base ((c >> 1) ^ (c >> 2)) & 3 and is
+ * complemented as c ^ (c & 2 ? 0x04 : 0x15).
+ *
+ * 1. Mark. remove u8[U]: 0 keep, 1 tip, 2 bubble arm. All decisions are taken from the input graph alone, in one round; the result does
+ *    not depend on launch geometry.
+ *    Outranks. w outranks u iff tf_sum_w m_u > tf_sum_u m_w (mean(w) > mean(u), compared exactly in 128-bit products), or the two
+ *      products are equal and w < u. A strict total order.
+ *    Tip candidate. A linear unitig with m_u <= tip_max_kmers, one end of degree 0 and the other end a of degree exactly 1.
+ *    Tip removal. t = the single link of a, f = t ^ 1 (the end that faces u). u is removed iff f has another link x with x >> 1 != u
+ *      whose unitig w = x >> 1 is no tip candidate, or is a candidate that outranks u. Where every sibling at a fork is a candidate,
+ *      exactly one survives; a candidate whose fork has no other link survives.
+ *    Bubble arm. u has the mate w = bubble_mate[u], m_u <= bubble_max_kmers, m_w <= bubble_max_kmers and w outranks u: exactly one arm
+ *      of a qualifying bubble is removed. An arm has two ends of degree 1, so it is never a tip candidate. bubble_mate may be NULL (it is
+ *      computed inside, aix_unitig_bubbles_dev); a given one must be symmetric with entries below U (AIX_ERR_ARG otherwise).
+ *    A threshold of 0 switches its rule off; a threshold above 32767 is AIX_ERR_ARG.
+ *
+ * 2. Compact. Takes G and any remove u8[U] (non-zero = removed), so callers may OR in masks of their own.
+ *    Surviving links. A link survives iff neither of its unitigs is removed; deg'(e) counts the surviving links of end e.
+ *    Merge edges. e -> t is a merge edge iff deg'(e) == 1, deg'(t ^ 1) == 1 and t >> 1 != e >> 1 — which cuts hairpins (u+ -> u-) and the
+ *      self-loop of a homopolymer — with one exception: the link u+ -> u+ (t == e) of a unitig of m_u >= 2 k-mers is a merge edge and
+ *      closes u on itself. (Its last and first k-mer are different nodes, so the k-mer rule of the compaction above links them too;
+ *      without the exception property (b) below would fail on a ring whose stem was clipped.) With e -> t, t ^ 1 -> e ^ 1 is a merge edge
+ *      too: components are simple paths and simple cycles of surviving unitigs. An input-circular unitig is a contig of its own and is
+ *      passed through unchanged.
+ *    Spelling. The first member is oriented and copied whole; every following oriented member contributes its bases from offset 22 on; a
+ *      backwards member is reverse-complemented. A contig of members m_1 .. m_j has the sum of their k-mers; tf_sum is the sum, tf_min the
+ *      minimum, tf_max the maximum of its members' values (there are no junction k-mers).
+ *    Path. Of its two spellings the one whose first oriented 23-mer has the smaller 46-bit code (the rule of the compaction above); on a
+ *      tie — possible only on input that is no compaction — the one whose first member has the smaller id, then the one that spells the
+ *      members as given.
+ *    Merged cycle. It starts at its member with the smallest unitig id, traversed forwards, and has circular = 1. This is NOT the
+ *      smallest-stored-code rotation of the compaction above: finding that rotation would split a member. A caller who needs that form
+ *      rotates on the host (tests/graph_clean_ref.py: canonical_form).
+ *    Order. Contig ids 0 .. C - 1 ascend by the code of the first 23-mer of the spelling; ties (same remark) by the id of the first member.
+ *    Map. unitig_contig u32[U] (AIX_BUBBLE_NONE if removed); unitig_pos u64[U]: the oriented spelling of the member occupies bases
+ *      [offsets'[c] + pos, offsets'[c] + pos + m_u + 22) of its contig, so pos is the number of k-mers in front of it and its first
+ *      contributed base is pos (first member) or pos + 22; unitig_flag u8[U]: bit 0 the member is reversed, bit 1 the contig is a merged
+ *      cycle (an input-circular unitig keeps flag 0). Removed unitigs get pos 0 and flag 0.
+ *    Links of G'. A circular contig has no ends. End 2 c + 0 / 2 c + 1 of a linear contig is the outward end of its last / first
+ *      member; its links are the surviving links of that unitig end (none of them is a merge edge), in their original order, each word
+ *      2 v + r rewritten to 2 contig(v) + (r ^ flag(v) & 1). That v is the member at that end of its contig is checked (AIX_ERR_ARG).
+ *      Duality holds in G'.
+ *    Properties. (a) With remove all zero on a G that aix_unitigs_emit_dev + aix_unitig_links_dev wrote, G' == G in every array and the
+ *      map is the identity. (b) G' equals — up to the rotation and strand of merged circular contigs and the id order that follows from
+ *      them — what those two calls return for an index that holds only the k-mers of the surviving unitigs.
+ *    U == 0, or everything removed, gives C = 0, offsets' = {0}, link_off' = {0}.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_GRAPH_MAX_THRESHOLD 32767u
+/* d_remove[U] and the two counts. d_bubble_mate[U] nullable. */
+int aix_graph_mark_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_circular, const uint64_t* d_tf_sum, const uint64_t* d_link_off,
+                       const uint32_t* d_link_to, uint64_t E, const uint32_t* d_bubble_mate /* nullable: computed inside when NULL */,
+                       uint32_t tip_max_kmers, uint32_t bubble_max_kmers, uint8_t* d_remove, uint64_t* n_tips_out, uint64_t* n_arms_out, void* stream);
+/* The graph is analysed once, here: the three map arrays [U], and the sizes the second call needs: C, offsets'[C], E' and the number of
+ * circular contigs. Scratch: see DESIGN 5k. */
+int aix_graph_compact_layout_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, const uint8_t* d_circular, const uint64_t* d_link_off,
+                                 const uint32_t* d_link_to, uint64_t E, const uint8_t* d_remove, uint32_t* d_unitig_contig, uint64_t* d_unitig_pos,
+                                 uint8_t* d_unitig_flag, uint64_t* n_contigs_out, uint64_t* total_bases_out, uint64_t* n_links_out,
+                                 uint64_t* n_circular_out, void* stream);
+/* Writes G': d_out_offsets[C + 1], d_out_bases[total_bases], d_out_circular / tf_sum / tf_min / tf_max [C], d_out_link_off[2 C + 1],
+ * d_out_link_to[n_links]; nothing is written at or beyond these sizes. The map is validated against (G, remove) and the three sizes
+ * first: members of a contig follow each other without a gap, every merge edge joins neighbours in matching orientation, every other
+ * end is a contig end; any disagreement is AIX_ERR_ARG with nothing written. d_bases must be aligned to 8 and d_out_bases to 16 bytes
+ * (AIX_ERR_ARG): the emission loads and stores whole words. Input and output arrays must not overlap. */
+int aix_graph_compact_emit_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, const uint8_t* d_circular, const uint64_t* d_tf_sum,
+                               const uint32_t* d_tf_min, const uint32_t* d_tf_max, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E,
+                               const uint8_t* d_remove, const uint32_t* d_unitig_contig, const uint64_t* d_unitig_pos, const uint8_t* d_unitig_flag,
+                               uint64_t C, uint64_t total_bases, uint64_t n_links, uint64_t* d_out_offsets, uint8_t* d_out_bases,
+                               uint8_t* d_out_circular, uint64_t* d_out_tf_sum, uint32_t* d_out_tf_min, uint32_t* d_out_tf_max,
+                               uint64_t* d_out_link_off, uint32_t* d_out_link_to, void* stream);
+/* One round — mark, layout, emit — for host memory: G in host arrays, G', remove[U] and the map in malloc'd arrays (aix_free); the last
+ * four outputs are nullable. */
+int aix_graph_clean(uint64_t U, const uint64_t* offsets, const uint8_t* bases, const uint8_t* circular, const uint64_t* tf_sum, const uint32_t* tf_min,
+                    const uint32_t* tf_max, const uint64_t* link_off, const uint32_t* link_to, uint64_t E, uint32_t tip_max_kmers,
+                    uint32_t bubble_max_kmers, uint64_t* n_contigs_out, uint64_t* n_links_out, uint64_t* n_tips_out, uint64_t* n_arms_out,
+                    uint64_t** offsets_out, uint8_t** bases_out, uint8_t** circular_out, uint64_t** tf_sum_out, uint32_t** tf_min_out,
+                    uint32_t** tf_max_out, uint64_t** link_off_out, uint32_t** link_to_out, uint8_t** remove_out /* nullable */,
+                    uint32_t** unitig_contig_out /* nullable */, uint64_t** unitig_pos_out /* nullable */, uint8_t** unitig_flag_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
