@@ -13,7 +13,7 @@
 #include <string>
 
 #include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 #include "aix_probe.hpp"
 
 namespace aix {
@@ -188,13 +188,6 @@ hipError_t launch_db_walk(const IndexDev& ix, const uint64_t* codes, const uint8
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define DBALLOC(buf, bytes)                                                                   \
-    do {                                                                                      \
-        const hipError_t e_ = (buf).alloc(bytes);                                             \
-        if (e_ == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }     \
-        HIPCHK(e_);                                                                           \
-    } while (0)
-
 static int db_check_input(const aix_index_t* h, const void* codes, const void* ascii, uint64_t n) {
     if (!h) return AIX_ERR_ARG;
     if (h->k != 23) return AIX_ERR_MODE;
@@ -226,8 +219,8 @@ extern "C" int aix_neighbours(aix_index_t* h, const uint64_t* codes, const char*
     DevGuard g(h->device);
     const uint64_t in_bytes = codes ? 8 * N : 23 * N, out_bytes = 32 * N * (dirs == AIX_DIR_BOTH ? 2 : 1);
     DevBuf din, dout;
-    DBALLOC(din, in_bytes + 16);
-    DBALLOC(dout, out_bytes);
+    AIXCHK(din.alloc(in_bytes + 16));
+    AIXCHK(dout.alloc(out_bytes));
     HIPCHK(hipMemcpy(din.p, codes ? (const void*)codes : (const void*)ascii, in_bytes, hipMemcpyHostToDevice));
     const int r = aix_neighbours_dev(h, codes ? (const uint64_t*)din.p : nullptr, codes ? nullptr : (const char*)din.p, N, dirs, cutoff, (aix_cont_t*)dout.p, nullptr);
     if (r) return r;
@@ -270,12 +263,12 @@ extern "C" int aix_walk(aix_index_t* h, const uint64_t* codes, const char* ascii
     DevGuard g(h->device);
     const uint64_t in_bytes = codes ? 8 * S : 23 * S;
     DevBuf din, db, dl, ds, dt, dc;
-    DBALLOC(din, in_bytes + 16);
-    DBALLOC(db, cells);
-    DBALLOC(dl, 4 * S);
-    DBALLOC(ds, S);
-    if (out_tf) DBALLOC(dt, 4 * cells);
-    if (out_last) DBALLOC(dc, 8 * S);
+    AIXCHK(din.alloc(in_bytes + 16));
+    AIXCHK(db.alloc(cells));
+    AIXCHK(dl.alloc(4 * S));
+    AIXCHK(ds.alloc(S));
+    if (out_tf) AIXCHK(dt.alloc(4 * cells));
+    if (out_last) AIXCHK(dc.alloc(8 * S));
     HIPCHK(hipMemcpy(din.p, codes ? (const void*)codes : (const void*)ascii, in_bytes, hipMemcpyHostToDevice));
     // a row is written up to its length only: the caller's rows go up first, so that what lies beyond comes back as it was
     HIPCHK(hipMemcpy(db.p, out_bases, cells, hipMemcpyHostToDevice));

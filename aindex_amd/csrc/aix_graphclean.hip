@@ -4,8 +4,9 @@
 // and the resources. No index handle: the arrays and the current device, like aix_unitig_bubbles_dev.
 //
 // The compaction is that of aix_unitigs.hip one level up: a node is a unitig, its two ports are its ends 2 u + 0 / 2 u + 1, at most one
-// link survives per merged port. The chain (one plain launch per step and per round; every host loop is bounded by a count computed on
-// the host; integer only, no LDS, no grid-wide barrier, no spin-wait):
+// link survives per merged port. What the two levels share is in aix_chains.hpp, and why their kernels are not. The chain (one plain
+// launch per step and per round; every host loop is bounded by a count computed on the host; integer only, no LDS, no grid-wide barrier,
+// no spin-wait):
 //   validate k_gc_validate: one lane per end; offsets, degrees, link words, duality of the surviving links, the mates
 //   mark     k_gc_mark: one lane per unitig, the tip and the arm rule over the input graph alone
 //   words    k_gc_words: per end the surviving degree and, when it is 1, the end that FACES it (link ^ 1)
@@ -26,14 +27,10 @@
 #include <cstring>
 #include <string>
 
-#include <rocprim/rocprim.hpp>
-
-#include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_chains.hpp"
 
 namespace aix {
 
-static constexpr int kGB = 256;
 static constexpr uint32_t kGNone = 0xFFFFFFFFu;                   // word: no single surviving link; contig: removed; mate: none
 static constexpr uint64_t kGFlag = 1ULL << 63;                    // ranking state: terminal reached
 static constexpr uint64_t kGDead = ~0ULL;                         // sort key of a removed unitig / of a unitig that starts no contig
@@ -44,30 +41,7 @@ struct GcCounters {                                               // one zeroed 
     unsigned long long unflagged[66];                             // [0] after k_gc_links, [r] after round r
 };
 
-// AIX_UG_TEST_GRID (test hook of the compaction, read per call): workgroups of every launch at most
-static inline uint64_t gc_test_grid() { return env_u64("AIX_UG_TEST_GRID", 1, 65536, 65536); }
-
-static inline unsigned gc_grid(uint64_t work, uint64_t per_block, uint64_t cap) {
-    uint64_t b = (work + per_block - 1) / per_block;
-    if (b > 4096) b = 4096;
-    if (b > cap) b = cap;
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
-
-__device__ __forceinline__ void gc_count(unsigned long long mine, unsigned long long* dst) {
-    unsigned long long v = mine;
-#pragma unroll
-    for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
-    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(dst, v);
-}
-__device__ __forceinline__ void gc_max(unsigned long long mine, unsigned long long* dst) {
-    unsigned long long v = mine;
-#pragma unroll
-    for (int s = 32; s; s >>= 1) { const unsigned long long o = __shfl_xor(v, s); v = o > v ? o : v; }
-    if ((threadIdx.x & 63u) == 0 && v) atomicMax(dst, v);
-}
-
+// (block size kCB, grid sizer, the AIX_UG_TEST_GRID hook of the compaction, wave-reduced counters: aix_chains.hpp)
 __device__ __forceinline__ uint64_t gc_m(const uint64_t* __restrict__ offsets, uint64_t u) { return offsets[u + 1] - offsets[u] - 22; }
 __device__ __forceinline__ uint32_t gc_base(uint32_t c) { return ((c >> 1) ^ (c >> 2)) & 3u; }               // A 0, C 1, G 2, T 3
 
@@ -89,12 +63,12 @@ __device__ __forceinline__ bool gc_alive(const uint8_t* __restrict__ remove, uin
 // ---------------------------------------------------------------------------------------------
 // 1. validation of a unitig set (every later kernel relies on it: indices are used unchecked behind it)
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGB) k_gc_validate(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
+__global__ void __launch_bounds__(kCB) k_gc_validate(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
                                                     const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, uint64_t E,
                                                     const uint8_t* __restrict__ remove, const uint32_t* __restrict__ mate, GcCounters* __restrict__ ctr) {
-    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
-    for (uint64_t e = (uint64_t)blockIdx.x * kGB + threadIdx.x; e < NE; e += stride) {
+    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         const uint64_t u = e >> 1;
         if (!(e & 1)) {
             const uint64_t a = offsets[u], b = offsets[u + 1];
@@ -121,7 +95,7 @@ __global__ void __launch_bounds__(kGB) k_gc_validate(uint64_t U, const uint64_t*
             bad += !dual;
         }
     }
-    gc_count(bad, &ctr->bad);
+    count_add(bad, &ctr->bad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -143,13 +117,13 @@ __device__ __forceinline__ uint32_t gc_attached(const uint64_t* __restrict__ off
     return kGNone;
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_mark(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
+__global__ void __launch_bounds__(kCB) k_gc_mark(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
                                                 const uint64_t* __restrict__ tf_sum, const uint64_t* __restrict__ link_off,
                                                 const uint32_t* __restrict__ link_to, const uint32_t* __restrict__ mate, uint32_t tip_max, uint32_t bub_max,
                                                 uint8_t* __restrict__ remove, GcCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long tips = 0, arms = 0;
-    for (uint64_t u = (uint64_t)blockIdx.x * kGB + threadIdx.x; u < U; u += stride) {
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         uint32_t res = 0;
         const uint32_t a = tip_max ? gc_attached(offsets, circular, link_off, u, tip_max) : kGNone;
         if (a != kGNone) {
@@ -166,17 +140,17 @@ __global__ void __launch_bounds__(kGB) k_gc_mark(uint64_t U, const uint64_t* __r
         tips += res == 1;
         arms += res == 2;
     }
-    gc_count(tips, &ctr->n_tips);
-    gc_count(arms, &ctr->n_arms);
+    count_add(tips, &ctr->n_tips);
+    count_add(arms, &ctr->n_arms);
 }
 
 // ---------------------------------------------------------------------------------------------
 // 3. surviving degrees, merge links, ranking
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGB) k_gc_words(uint64_t U, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to,
+__global__ void __launch_bounds__(kCB) k_gc_words(uint64_t U, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to,
                                                  const uint8_t* __restrict__ remove, uint32_t* __restrict__ word, uint8_t* __restrict__ degp) {
-    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t e = (uint64_t)blockIdx.x * kGB + threadIdx.x; e < NE; e += stride) {
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         uint32_t d = 0, t1 = kGNone;
         if (gc_alive(remove, e >> 1))
             for (uint64_t i = link_off[e]; i < link_off[e + 1]; ++i) {
@@ -188,12 +162,12 @@ __global__ void __launch_bounds__(kGB) k_gc_words(uint64_t U, const uint64_t* __
     }
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_links(const uint32_t* __restrict__ word, const uint8_t* __restrict__ degp, const uint64_t* __restrict__ offsets,
+__global__ void __launch_bounds__(kCB) k_gc_links(const uint32_t* __restrict__ word, const uint8_t* __restrict__ degp, const uint64_t* __restrict__ offsets,
                                                  uint64_t NE, uint64_t* __restrict__ nx, uint64_t* __restrict__ dist, uint8_t* __restrict__ merged,
                                                  GcCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long open = 0, links = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         const uint32_t f = word[p];
         bool linked = false;
         if ((uint64_t)f < NE && (uint64_t)word[f] == p)
@@ -204,15 +178,15 @@ __global__ void __launch_bounds__(kGB) k_gc_links(const uint32_t* __restrict__ w
         open += linked;
         links += linked ? 0u : degp[p];
     }
-    gc_count(open, &ctr->unflagged[0]);
-    gc_count(links, &ctr->links);
+    count_add(open, &ctr->unflagged[0]);
+    count_add(links, &ctr->links);
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_jump(const uint64_t* __restrict__ nx_in, const uint64_t* __restrict__ d_in, uint64_t NE, uint64_t* __restrict__ nx_out,
+__global__ void __launch_bounds__(kCB) k_gc_jump(const uint64_t* __restrict__ nx_in, const uint64_t* __restrict__ d_in, uint64_t NE, uint64_t* __restrict__ nx_out,
                                                 uint64_t* __restrict__ d_out, unsigned long long* __restrict__ unflagged) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long open = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         uint64_t s = nx_in[p], d = d_in[p];
         if (!(s & kGFlag)) {
             const uint64_t q = s & 0xFFFFFFFFull;
@@ -223,14 +197,14 @@ __global__ void __launch_bounds__(kGB) k_gc_jump(const uint64_t* __restrict__ nx
         nx_out[p] = s;
         d_out[p] = d;
     }
-    gc_count(open, unflagged);
+    count_add(open, unflagged);
 }
 
 // cycles: a = succ | minimum end id << 32, md = k-mers to its first occurrence, w = k-mers of the window; unflagged ends only
-__global__ void __launch_bounds__(kGB) k_gc_cyc_init(const uint64_t* __restrict__ rank, const uint32_t* __restrict__ word, const uint64_t* __restrict__ offsets,
+__global__ void __launch_bounds__(kCB) k_gc_cyc_init(const uint64_t* __restrict__ rank, const uint32_t* __restrict__ word, const uint64_t* __restrict__ offsets,
                                                     uint64_t NE, uint64_t* __restrict__ a, uint64_t* __restrict__ md, uint64_t* __restrict__ w) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         if (rank[p] & kGFlag) continue;
         const uint32_t succ = word[p] ^ 1u;                        // an unflagged end is merged: its word is its link
         a[p] = (uint64_t)succ | (p << 32);
@@ -239,11 +213,11 @@ __global__ void __launch_bounds__(kGB) k_gc_cyc_init(const uint64_t* __restrict_
     }
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_cyc_jump(const uint64_t* __restrict__ rank, uint64_t NE, const uint64_t* __restrict__ a_in,
+__global__ void __launch_bounds__(kCB) k_gc_cyc_jump(const uint64_t* __restrict__ rank, uint64_t NE, const uint64_t* __restrict__ a_in,
                                                     const uint64_t* __restrict__ md_in, const uint64_t* __restrict__ w_in, uint64_t* __restrict__ a_out,
                                                     uint64_t* __restrict__ md_out, uint64_t* __restrict__ w_out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         if (rank[p] & kGFlag) continue;
         const uint64_t a = a_in[p], q = a & 0xFFFFFFFFull;
         if (q >= NE || (rank[q] & kGFlag)) { a_out[p] = a; md_out[p] = md_in[p]; w_out[p] = w_in[p]; continue; }   // (never: a successor on a cycle is on it)
@@ -261,14 +235,14 @@ __global__ void __launch_bounds__(kGB) k_gc_cyc_jump(const uint64_t* __restrict_
 // ---------------------------------------------------------------------------------------------
 // Per unitig. Path member: both ends are flagged; spelling A starts at the member reached through the left end (this member: position dL,
 // as given), spelling B at the one reached through the right end (position dR, reversed). Cycle member: neither end is flagged.
-__global__ void __launch_bounds__(kGB) k_gc_place(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ bases,
+__global__ void __launch_bounds__(kCB) k_gc_place(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ bases,
                                                  const uint8_t* __restrict__ circular, const uint8_t* __restrict__ remove, const uint64_t* __restrict__ rank,
                                                  const uint64_t* __restrict__ dist, const uint64_t* __restrict__ cyc_a, const uint64_t* __restrict__ cyc_md,
                                                  uint32_t* __restrict__ start_of, uint64_t* __restrict__ pos_out, uint8_t* __restrict__ flag_out,
                                                  uint64_t* __restrict__ start_code, uint32_t* __restrict__ start_id, GcCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long alive = 0, starts = 0, circ = 0, total = 0;
-    for (uint64_t u = (uint64_t)blockIdx.x * kGB + threadIdx.x; u < U; u += stride) {
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         start_id[u] = (uint32_t)u;
         if (remove[u]) {
             start_of[u] = kGNone; pos_out[u] = 0; flag_out[u] = 0; start_code[u] = kGDead;
@@ -309,24 +283,24 @@ __global__ void __launch_bounds__(kGB) k_gc_place(uint64_t U, const uint64_t* __
         starts += pos == 0;
         circ += pos == 0 && closed;
     }
-    gc_count(alive, &ctr->n_alive);
-    gc_count(starts, &ctr->n_starts);
-    gc_count(circ, &ctr->n_circular);
-    gc_count(total, &ctr->total_k);
+    count_add(alive, &ctr->n_alive);
+    count_add(starts, &ctr->n_starts);
+    count_add(circ, &ctr->n_circular);
+    count_add(total, &ctr->total_k);
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_ids(const uint32_t* __restrict__ sorted_id, uint64_t C, uint64_t U, uint32_t* __restrict__ start_cid) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t j = (uint64_t)blockIdx.x * kGB + threadIdx.x; j < C; j += stride) {
+__global__ void __launch_bounds__(kCB) k_gc_ids(const uint32_t* __restrict__ sorted_id, uint64_t C, uint64_t U, uint32_t* __restrict__ start_cid) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < C; j += stride) {
         const uint32_t u = sorted_id[j];
         if (u < U) start_cid[u] = (uint32_t)j;
     }
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_assign(const uint32_t* __restrict__ start_of, const uint32_t* __restrict__ start_cid, uint64_t U,
+__global__ void __launch_bounds__(kCB) k_gc_assign(const uint32_t* __restrict__ start_of, const uint32_t* __restrict__ start_cid, uint64_t U,
                                                   uint32_t* __restrict__ contig) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t u = (uint64_t)blockIdx.x * kGB + threadIdx.x; u < U; u += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         const uint32_t st = start_of[u];
         contig[u] = (uint64_t)st < U ? start_cid[st] : kGNone;
     }
@@ -335,11 +309,11 @@ __global__ void __launch_bounds__(kGB) k_gc_assign(const uint32_t* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // 5. emit: validation of the map
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGB) k_gc_mapcheck(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ remove,
+__global__ void __launch_bounds__(kCB) k_gc_mapcheck(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ remove,
                                                     const uint32_t* __restrict__ contig, const uint64_t* __restrict__ pos, uint64_t C, GcCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long alive = 0, starts = 0, bad = 0, total = 0, mx = 0;
-    for (uint64_t u = (uint64_t)blockIdx.x * kGB + threadIdx.x; u < U; u += stride) {
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         const uint32_t c = contig[u];
         if (remove[u]) { bad += c != kGNone; continue; }
         ++alive;
@@ -348,26 +322,26 @@ __global__ void __launch_bounds__(kGB) k_gc_mapcheck(uint64_t U, const uint64_t*
         total += gc_m(offsets, u);
         mx = pos[u] > mx ? pos[u] : mx;
     }
-    gc_count(alive, &ctr->n_alive);
-    gc_count(starts, &ctr->n_starts);
-    gc_count(bad, &ctr->bad);
-    gc_count(total, &ctr->total_k);
-    gc_max(mx, &ctr->max_pos);
+    count_add(alive, &ctr->n_alive);
+    count_add(starts, &ctr->n_starts);
+    count_add(bad, &ctr->bad);
+    count_add(total, &ctr->total_k);
+    count_max(mx, &ctr->max_pos);
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_keys(uint64_t U, int pos_bits, const uint8_t* __restrict__ remove, const uint32_t* __restrict__ contig,
+__global__ void __launch_bounds__(kCB) k_gc_keys(uint64_t U, int pos_bits, const uint8_t* __restrict__ remove, const uint32_t* __restrict__ contig,
                                                 const uint64_t* __restrict__ pos, uint64_t* __restrict__ keys, uint32_t* __restrict__ ids) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t u = (uint64_t)blockIdx.x * kGB + threadIdx.x; u < U; u += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         keys[u] = remove[u] ? kGDead : (((uint64_t)contig[u] << pos_bits) | pos[u]);
         ids[u] = (uint32_t)u;
     }
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_mlen(uint64_t S, const uint32_t* __restrict__ ms, uint64_t U, const uint64_t* __restrict__ offsets,
+__global__ void __launch_bounds__(kCB) k_gc_mlen(uint64_t S, const uint32_t* __restrict__ ms, uint64_t U, const uint64_t* __restrict__ offsets,
                                                 uint64_t* __restrict__ mlen) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t j = (uint64_t)blockIdx.x * kGB + threadIdx.x; j <= S; j += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j <= S; j += stride) {
         const uint32_t u = j < S ? ms[j] : kGNone;
         mlen[j] = (uint64_t)u < U ? gc_m(offsets, u) : 0;
     }
@@ -376,11 +350,11 @@ __global__ void __launch_bounds__(kGB) k_gc_mlen(uint64_t S, const uint32_t* __r
 // Member j of the sorted members (contig, position): kpre[j] k-mers lie in front of it. Checks that the members of every contig 0 .. C - 1
 // follow each other without a gap, and writes begin[j] (the first output byte the member contributes; begin[S] = total) and the new
 // offsets (scratch).
-__global__ void __launch_bounds__(kGB) k_gc_begin(uint64_t S, uint64_t C, int pos_bits, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ kpre,
+__global__ void __launch_bounds__(kCB) k_gc_begin(uint64_t S, uint64_t C, int pos_bits, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ kpre,
                                                  uint64_t total, uint64_t* __restrict__ begin, uint64_t* __restrict__ new_off, GcCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB, mask = (1ULL << pos_bits) - 1;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB, mask = (1ULL << pos_bits) - 1;
     unsigned long long bad = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * kGB + threadIdx.x; j < S; j += stride) {
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < S; j += stride) {
         const uint64_t key = keys[j], c = key >> pos_bits, p = key & mask;
         if (j == 0) {
             bad += c != 0 || p != 0;
@@ -396,19 +370,19 @@ __global__ void __launch_bounds__(kGB) k_gc_begin(uint64_t S, uint64_t C, int po
         begin[j] = kpre[j] + 22 * c + (p ? 22 : 0);
         if (p == 0) new_off[c] = kpre[j] + 22 * c;
     }
-    gc_count(bad, &ctr->bad);
+    count_add(bad, &ctr->bad);
 }
 
 // Per end of every surviving unitig: a merged end has its neighbour next to it in the same contig, in the matching orientation; any
 // other end is an end of its contig, and every unitig it links to sits at the end of its own contig. Writes the degrees of the contig ends.
-__global__ void __launch_bounds__(kGB) k_gc_ends(uint64_t U, uint64_t C, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
+__global__ void __launch_bounds__(kCB) k_gc_ends(uint64_t U, uint64_t C, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
                                                 const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, const uint8_t* __restrict__ remove,
                                                 const uint32_t* __restrict__ word, const uint8_t* __restrict__ degp, const uint8_t* __restrict__ merged,
                                                 const uint32_t* __restrict__ contig, const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flag,
                                                 const uint64_t* __restrict__ new_off, uint32_t* __restrict__ ndeg, GcCounters* __restrict__ ctr) {
-    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kGB;
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         const uint64_t u = p >> 1;
         if (remove[u]) continue;
         const uint64_t c = contig[u], mc = new_off[c + 1] - new_off[c] - 22, mu = gc_m(offsets, u), pu = pos[u];
@@ -442,19 +416,15 @@ __global__ void __launch_bounds__(kGB) k_gc_ends(uint64_t U, uint64_t C, const u
             }
         }
     }
-    gc_count(bad, &ctr->bad);
+    count_add(bad, &ctr->bad);
 }
 
-struct GcWiden {
-    __host__ __device__ uint64_t operator()(uint32_t d) const { return d; }
-};
-
-__global__ void __launch_bounds__(kGB) k_gc_fill(uint64_t U, const uint8_t* __restrict__ circular, const uint64_t* __restrict__ link_off,
+__global__ void __launch_bounds__(kCB) k_gc_fill(uint64_t U, const uint8_t* __restrict__ circular, const uint64_t* __restrict__ link_off,
                                                 const uint32_t* __restrict__ link_to, const uint8_t* __restrict__ remove, const uint8_t* __restrict__ merged,
                                                 const uint32_t* __restrict__ contig, const uint8_t* __restrict__ flag, const uint64_t* __restrict__ new_lo, uint64_t E2,
                                                 uint32_t* __restrict__ out_to) {
-    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t p = (uint64_t)blockIdx.x * kGB + threadIdx.x; p < NE; p += stride) {
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         const uint64_t u = p >> 1;
         if (remove[u] || merged[p] || circular[u]) continue;
         uint64_t at = new_lo[2 * (uint64_t)contig[u] + (((uint32_t)p ^ flag[u]) & 1u)];
@@ -493,11 +463,11 @@ __device__ __forceinline__ uint64_t gc_comp8(uint64_t w) {
     return w ^ ((cg & 0x0404040404040404ull) | (~cg & 0x1515151515151515ull));
 }
 
-__global__ void __launch_bounds__(kGB) k_gc_emit(uint64_t S, const uint64_t* __restrict__ begin, const uint32_t* __restrict__ ms, const uint64_t* __restrict__ keys,
+__global__ void __launch_bounds__(kCB) k_gc_emit(uint64_t S, const uint64_t* __restrict__ begin, const uint32_t* __restrict__ ms, const uint64_t* __restrict__ keys,
                                                 int pos_bits, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ flag,
                                                 const uint64_t* __restrict__ words_in, uint64_t total_in, uint8_t* __restrict__ out, uint64_t total) {
-    const uint64_t chunks = (total + 15) >> 4, stride = (uint64_t)gridDim.x * kGB, mask = (1ULL << pos_bits) - 1;
-    for (uint64_t ch = (uint64_t)blockIdx.x * kGB + threadIdx.x; ch < chunks; ch += stride) {
+    const uint64_t chunks = (total + 15) >> 4, stride = (uint64_t)gridDim.x * kCB, mask = (1ULL << pos_bits) - 1;
+    for (uint64_t ch = (uint64_t)blockIdx.x * kCB + threadIdx.x; ch < chunks; ch += stride) {
         const uint64_t o = ch << 4, end = o + 16 < total ? o + 16 : total;
         uint64_t lo = 0, hi = S;                                   // the last member with begin <= o (begin[0] == 0)
         while (hi - lo > 1) {                                      // at most 64 trips
@@ -539,67 +509,18 @@ __global__ void __launch_bounds__(kGB) k_gc_emit(uint64_t S, const uint64_t* __r
 // ---------------------------------------------------------------------------------------------
 // 7. emit: per-contig values
 // ---------------------------------------------------------------------------------------------
-struct GcAgg {
-    unsigned long long sum;
-    uint32_t mn, mx;
-};
-struct GcAggOp {
-    __host__ __device__ GcAgg operator()(const GcAgg& a, const GcAgg& b) const { return GcAgg{a.sum + b.sum, a.mn < b.mn ? a.mn : b.mn, a.mx > b.mx ? a.mx : b.mx}; }
-};
-struct GcContigOf {
-    int pos_bits;
-    __host__ __device__ uint64_t operator()(uint64_t key) const { return key >> pos_bits; }
-};
-
-__global__ void __launch_bounds__(kGB) k_gc_gather(uint64_t S, const uint32_t* __restrict__ ms, const uint64_t* __restrict__ keys, int pos_bits, uint64_t C,
+// (the {sum, min, max} aggregate, its reduction by contig and the kernel that scatters the result: aix_chains.hpp)
+__global__ void __launch_bounds__(kCB) k_gc_gather(uint64_t S, const uint32_t* __restrict__ ms, const uint64_t* __restrict__ keys, int pos_bits, uint64_t C,
                                                   const uint8_t* __restrict__ circular, const uint8_t* __restrict__ flag, const uint64_t* __restrict__ tf_sum,
-                                                  const uint32_t* __restrict__ tf_min, const uint32_t* __restrict__ tf_max, GcAgg* __restrict__ agg,
+                                                  const uint32_t* __restrict__ tf_min, const uint32_t* __restrict__ tf_max, ChainAgg* __restrict__ agg,
                                                   uint8_t* __restrict__ out_circular) {
-    const uint64_t stride = (uint64_t)gridDim.x * kGB, mask = (1ULL << pos_bits) - 1;
-    for (uint64_t j = (uint64_t)blockIdx.x * kGB + threadIdx.x; j < S; j += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB, mask = (1ULL << pos_bits) - 1;
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < S; j += stride) {
         const uint32_t u = ms[j];
-        agg[j] = GcAgg{tf_sum[u], tf_min[u], tf_max[u]};
+        agg[j] = ChainAgg{tf_sum[u], tf_min[u], tf_max[u]};
         const uint64_t c = keys[j] >> pos_bits;
         if ((keys[j] & mask) == 0 && c < C) out_circular[c] = (uint8_t)((circular[u] != 0) | ((flag[u] >> 1) & 1u));
     }
-}
-
-__global__ void __launch_bounds__(kGB) k_gc_stats(const uint64_t* __restrict__ uniq, const GcAgg* __restrict__ agg, const uint64_t* __restrict__ count, uint64_t C,
-                                                 uint64_t* __restrict__ tf_sum, uint32_t* __restrict__ tf_min, uint32_t* __restrict__ tf_max) {
-    const uint64_t m = *count < C ? *count : C, stride = (uint64_t)gridDim.x * kGB;
-    for (uint64_t i = (uint64_t)blockIdx.x * kGB + threadIdx.x; i < m; i += stride) {
-        const uint64_t c = uniq[i];
-        if (c >= C) continue;
-        const GcAgg a = agg[i];
-        tf_sum[c] = a.sum; tf_min[c] = a.mn; tf_max[c] = a.mx;
-    }
-}
-
-static inline int gc_ceil_log2(uint64_t v) {
-    int r = 0;
-    while (r < 64 && (1ULL << r) < v) ++r;
-    return r;
-}
-static inline int gc_bit_length(uint64_t v) {
-    int r = 0;
-    while (v) { ++r; v >>= 1; }
-    return r;
-}
-
-#define GC(expr)                                 \
-    do {                                         \
-        const hipError_t e_ = (expr);            \
-        if (e_ != hipSuccess) return e_;         \
-    } while (0)
-#define GCL(...)                                 \
-    do {                                         \
-        hipLaunchKernelGGL(__VA_ARGS__);         \
-        GC(hipGetLastError());                   \
-    } while (0)
-
-static hipError_t gc_read(GcCounters* host, const GcCounters* dev, hipStream_t s) {
-    GC(hipMemcpyAsync(host, dev, sizeof(GcCounters), hipMemcpyDeviceToHost, s));
-    return hipStreamSynchronize(s);
 }
 
 struct GcGraph {                                                  // a unitig set in HBM
@@ -616,24 +537,24 @@ struct GcGraph {                                                  // a unitig se
 // *bad: the arrays are no unitig set (with `remove`: one of its surviving links has no dual). Synchronises `s`.
 static hipError_t gc_validate(const GcGraph& g, const uint8_t* remove, const uint32_t* mate, GcCounters* ctr, bool* bad, hipStream_t s) {
     GcCounters hc;
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GCL(k_gc_validate, dim3(gc_grid(2 * g.U, 2 * kGB, gc_test_grid())), dim3(kGB), 0, s, g.U, g.offsets, g.circular, g.link_off, g.link_to, g.E, remove, mate, ctr);
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY_LAUNCH(k_gc_validate, dim3(chain_grid(2 * g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.link_off, g.link_to, g.E, remove, mate, ctr);
+    AIX_TRY(chain_read(&hc, ctr, s));
     *bad = hc.bad != 0;
     return hipSuccess;
 }
 
 static hipError_t gc_mark(const GcGraph& g, const uint32_t* mate, uint32_t tip_max, uint32_t bub_max, uint8_t* remove, uint64_t out[2], bool* bad, hipStream_t s) {
     DevArr ctr_a(s);
-    GC(ctr_a.alloc(sizeof(GcCounters)));
+    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
     GcCounters* ctr = (GcCounters*)ctr_a.p;
-    GC(gc_validate(g, nullptr, mate, ctr, bad, s));
+    AIX_TRY(gc_validate(g, nullptr, mate, ctr, bad, s));
     if (*bad) return hipSuccess;
     GcCounters hc;
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GCL(k_gc_mark, dim3(gc_grid(g.U, 2 * kGB, gc_test_grid())), dim3(kGB), 0, s, g.U, g.offsets, g.circular, g.tf_sum, g.link_off, g.link_to, mate, tip_max, bub_max,
-        remove, ctr);
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY_LAUNCH(k_gc_mark, dim3(chain_grid(g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.tf_sum, g.link_off, g.link_to, mate, tip_max,
+        bub_max, remove, ctr);
+    AIX_TRY(chain_read(&hc, ctr, s));
     out[0] = hc.n_tips;
     out[1] = hc.n_arms;
     return hipSuccess;
@@ -643,83 +564,77 @@ static hipError_t gc_mark(const GcGraph& g, const uint32_t* mate, uint32_t tip_m
 // unflagged[0] and links. No synchronisation.
 static hipError_t gc_merge_links(const GcGraph& g, const uint8_t* remove, uint32_t* word, uint8_t* degp, uint8_t* merged, uint64_t* nx, uint64_t* dist,
                                  GcCounters* ctr, hipStream_t s) {
-    const uint64_t NE = 2 * g.U, cap = gc_test_grid();
-    GCL(k_gc_words, dim3(gc_grid(NE, 4 * kGB, cap)), dim3(kGB), 0, s, g.U, g.link_off, g.link_to, remove, word, degp);
-    GCL(k_gc_links, dim3(gc_grid(NE, 4 * kGB, cap)), dim3(kGB), 0, s, (const uint32_t*)word, (const uint8_t*)degp, g.offsets, NE, nx, dist, merged, ctr);
+    const uint64_t NE = 2 * g.U, cap = chain_test_grid();
+    AIX_TRY_LAUNCH(k_gc_words, dim3(chain_grid(NE, 4 * kCB, cap)), dim3(kCB), 0, s, g.U, g.link_off, g.link_to, remove, word, degp);
+    AIX_TRY_LAUNCH(k_gc_links, dim3(chain_grid(NE, 4 * kCB, cap)), dim3(kCB), 0, s, (const uint32_t*)word, (const uint8_t*)degp, g.offsets, NE, nx, dist, merged, ctr);
     return hipSuccess;
 }
 
 // out: C, total bases, links of the contig ends, circular contigs. Synchronises `s`.
 static hipError_t gc_layout(const GcGraph& g, const uint8_t* remove, uint32_t* contig, uint64_t* pos, uint8_t* flag, uint64_t out[4], bool* bad, hipStream_t s) {
-    const uint64_t U = g.U, NE = 2 * U, cap = gc_test_grid();
-    const dim3 blk(kGB);
+    const uint64_t U = g.U, NE = 2 * U, cap = chain_test_grid();
+    const dim3 blk(kCB);
     DevArr ctr_a(s), word(s), degp(s), mg(s), n0(s), d0(s), n1(s), d1(s), ca0(s), cm0(s), cw0(s), ca1(s), cm1(s), cw1(s), so(s), sc(s), si(s), sc2(s), si2(s), cid(s), tmp(s);
-    GC(ctr_a.alloc(sizeof(GcCounters)));
+    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
     GcCounters* ctr = (GcCounters*)ctr_a.p;
     GcCounters hc;
-    GC(gc_validate(g, remove, nullptr, ctr, bad, s));
+    AIX_TRY(gc_validate(g, remove, nullptr, ctr, bad, s));
     if (*bad) return hipSuccess;
     if (U == 0) return hipSuccess;
-    GC(word.alloc(4 * NE));
-    GC(degp.alloc(NE));
-    GC(mg.alloc(NE));
-    GC(n0.alloc(8 * NE));
-    GC(d0.alloc(8 * NE));
-    GC(n1.alloc(8 * NE));
-    GC(d1.alloc(8 * NE));
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GC(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(word.alloc(4 * NE));
+    AIX_TRY(degp.alloc(NE));
+    AIX_TRY(mg.alloc(NE));
+    AIX_TRY(n0.alloc(8 * NE));
+    AIX_TRY(d0.alloc(8 * NE));
+    AIX_TRY(n1.alloc(8 * NE));
+    AIX_TRY(d1.alloc(8 * NE));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
+    AIX_TRY(chain_read(&hc, ctr, s));
     const uint64_t links = hc.links;
     uint64_t *cn = (uint64_t*)n0.p, *cd = (uint64_t*)d0.p, *on = (uint64_t*)n1.p, *od = (uint64_t*)d1.p;
     uint64_t open = hc.unflagged[0];
-    const int max_rounds = std::min(64, gc_ceil_log2(U) + 1);
-    for (int r = 1; r <= max_rounds && open; ++r) {
-        GCL(k_gc_jump, dim3(gc_grid(NE, 4 * kGB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint64_t*)cd, NE, on, od, &ctr->unflagged[r]);
-        GC(gc_read(&hc, ctr, s));
+    AIX_TRY(chain_rank(U, ctr->unflagged, &open, s, [&](int r) {
+        AIX_TRY_LAUNCH(k_gc_jump, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint64_t*)cd, NE, on, od, &ctr->unflagged[r]);
         std::swap(cn, on);
         std::swap(cd, od);
-        const bool same = hc.unflagged[r] == open;
-        open = hc.unflagged[r];
-        if (same) break;                                           // only ends on cycles are left
-    }
+        return hipSuccess;
+    }));                                                           // open: only ends on cycles are left
     const uint64_t *cyc_a = nullptr, *cyc_md = nullptr;
     if (open) {
-        GC(ca0.alloc(8 * NE));
-        GC(cm0.alloc(8 * NE));
-        GC(cw0.alloc(8 * NE));
-        GC(ca1.alloc(8 * NE));
-        GC(cm1.alloc(8 * NE));
-        GC(cw1.alloc(8 * NE));
+        AIX_TRY(ca0.alloc(8 * NE));
+        AIX_TRY(cm0.alloc(8 * NE));
+        AIX_TRY(cw0.alloc(8 * NE));
+        AIX_TRY(ca1.alloc(8 * NE));
+        AIX_TRY(cm1.alloc(8 * NE));
+        AIX_TRY(cw1.alloc(8 * NE));
         uint64_t *a = (uint64_t*)ca0.p, *m = (uint64_t*)cm0.p, *w = (uint64_t*)cw0.p, *a2 = (uint64_t*)ca1.p, *m2 = (uint64_t*)cm1.p, *w2 = (uint64_t*)cw1.p;
-        GCL(k_gc_cyc_init, dim3(gc_grid(NE, 4 * kGB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint32_t*)word.p, g.offsets, NE, a, m, w);
-        const int rounds = std::min(64, gc_ceil_log2(open) + 1);
+        AIX_TRY_LAUNCH(k_gc_cyc_init, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint32_t*)word.p, g.offsets, NE, a, m, w);
+        const int rounds = std::min(64, ceil_log2(open) + 1);
         for (int r = 1; r <= rounds; ++r) {
-            GCL(k_gc_cyc_jump, dim3(gc_grid(NE, 4 * kGB, cap)), blk, 0, s, (const uint64_t*)cn, NE, (const uint64_t*)a, (const uint64_t*)m, (const uint64_t*)w, a2, m2, w2);
+            AIX_TRY_LAUNCH(k_gc_cyc_jump, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cn, NE, (const uint64_t*)a, (const uint64_t*)m, (const uint64_t*)w, a2,
+                m2, w2);
             std::swap(a, a2);
             std::swap(m, m2);
             std::swap(w, w2);
         }
         cyc_a = a; cyc_md = m;
     }
-    GC(so.alloc(4 * U));
-    GC(sc.alloc(8 * U));
-    GC(si.alloc(4 * U));
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GCL(k_gc_place, dim3(gc_grid(U, 2 * kGB, cap)), blk, 0, s, U, g.offsets, g.bases, g.circular, remove, (const uint64_t*)cn, (const uint64_t*)cd, cyc_a, cyc_md,
+    AIX_TRY(so.alloc(4 * U));
+    AIX_TRY(sc.alloc(8 * U));
+    AIX_TRY(si.alloc(4 * U));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY_LAUNCH(k_gc_place, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, g.bases, g.circular, remove, (const uint64_t*)cn, (const uint64_t*)cd, cyc_a, cyc_md,
         (uint32_t*)so.p, pos, flag, (uint64_t*)sc.p, (uint32_t*)si.p, ctr);
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(chain_read(&hc, ctr, s));
     const uint64_t C = std::min<uint64_t>(hc.n_starts, U);
-    GC(sc2.alloc(8 * U));
-    GC(si2.alloc(4 * U));
-    GC(cid.alloc(4 * U));
-    size_t tb = 0;
-    GC(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)si.p, (uint32_t*)si2.p, (size_t)U, 0u, 64u, s));
-    GC(tmp.alloc(tb ? tb : 1));
-    GC(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)si.p, (uint32_t*)si2.p, (size_t)U, 0u, 64u, s));
-    GC(hipMemsetAsync(cid.p, 0xFF, 4 * U, s));
-    GCL(k_gc_ids, dim3(gc_grid(C, 4 * kGB, cap)), blk, 0, s, (const uint32_t*)si2.p, C, U, (uint32_t*)cid.p);
-    GCL(k_gc_assign, dim3(gc_grid(U, 4 * kGB, cap)), blk, 0, s, (const uint32_t*)so.p, (const uint32_t*)cid.p, U, contig);
+    AIX_TRY(sc2.alloc(8 * U));
+    AIX_TRY(si2.alloc(4 * U));
+    AIX_TRY(cid.alloc(4 * U));
+    AIX_TRY(sort_pairs((const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)si.p, (uint32_t*)si2.p, U, 64u, tmp, s));
+    AIX_TRY(hipMemsetAsync(cid.p, 0xFF, 4 * U, s));
+    AIX_TRY_LAUNCH(k_gc_ids, dim3(chain_grid(C, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)si2.p, C, U, (uint32_t*)cid.p);
+    AIX_TRY_LAUNCH(k_gc_assign, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)so.p, (const uint32_t*)cid.p, U, contig);
     out[0] = C;
     out[1] = hc.total_k + 22 * C;
     out[2] = links;
@@ -741,102 +656,91 @@ struct GcOut {                                                    // G' in HBM, 
 // does not fit 63 bits. Synchronises `s`.
 static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_t* contig, const uint64_t* pos, const uint8_t* flag, uint64_t C, uint64_t total,
                           uint64_t E2, const GcOut& o, int* status, hipStream_t s) {
-    const uint64_t U = g.U, NE = 2 * U, cap = gc_test_grid();
-    const dim3 blk(kGB);
+    const uint64_t U = g.U, NE = 2 * U, cap = chain_test_grid();
+    const dim3 blk(kCB);
     *status = AIX_ERR_ARG;
     DevArr ctr_a(s), word(s), degp(s), mg(s), n0(s), d0(s), keys(s), ids(s), keys2(s), ms(s), tmp(s), mlen(s), kpre(s), begin(s), noff(s), ndeg(s), nlo(s), agg(s), uniq(s),
         ragg(s), cnt(s);
-    GC(ctr_a.alloc(sizeof(GcCounters)));
+    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
     GcCounters* ctr = (GcCounters*)ctr_a.p;
     GcCounters hc;
     bool bad = false;
-    GC(gc_validate(g, remove, nullptr, ctr, &bad, s));
+    AIX_TRY(gc_validate(g, remove, nullptr, ctr, &bad, s));
     if (bad) return hipSuccess;
     uint64_t total_in = 0;
-    GC(hipMemcpyAsync(&total_in, g.offsets + U, 8, hipMemcpyDeviceToHost, s));
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GCL(k_gc_mapcheck, dim3(gc_grid(U, 2 * kGB, cap)), blk, 0, s, U, g.offsets, remove, contig, pos, C, ctr);
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(hipMemcpyAsync(&total_in, g.offsets + U, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY_LAUNCH(k_gc_mapcheck, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, remove, contig, pos, C, ctr);
+    AIX_TRY(chain_read(&hc, ctr, s));
     const uint64_t S = hc.n_alive;
     if (hc.bad || hc.n_starts != C || S < C || (C == 0 && S) || hc.total_k + 22 * C != total || (S && hc.max_pos >= hc.total_k)) return hipSuccess;
     if (C == 0) {
         if (E2) return hipSuccess;
-        GC(hipMemsetAsync(o.offsets, 0, 8, s));
-        GC(hipMemsetAsync(o.link_off, 0, 8, s));
+        AIX_TRY(hipMemsetAsync(o.offsets, 0, 8, s));
+        AIX_TRY(hipMemsetAsync(o.link_off, 0, 8, s));
         *status = AIX_OK;
         return hipStreamSynchronize(s);
     }
-    const int pos_bits = gc_bit_length(hc.max_pos);
-    if (pos_bits + gc_bit_length(C) > 63) { *status = AIX_ERR_UNSUPPORTED; return hipSuccess; }
-    GC(word.alloc(4 * NE));
-    GC(degp.alloc(NE));
-    GC(mg.alloc(NE));
-    GC(n0.alloc(8 * NE));
-    GC(d0.alloc(8 * NE));
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GC(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
-    GC(keys.alloc(8 * U));
-    GC(ids.alloc(4 * U));
-    GC(keys2.alloc(8 * U));
-    GC(ms.alloc(4 * U));
-    GCL(k_gc_keys, dim3(gc_grid(U, 4 * kGB, cap)), blk, 0, s, U, pos_bits, remove, contig, pos, (uint64_t*)keys.p, (uint32_t*)ids.p);
-    size_t tb = 0;
-    GC(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)ids.p, (uint32_t*)ms.p, (size_t)U, 0u, 64u, s));
-    GC(tmp.alloc(tb ? tb : 1));
-    GC(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)ids.p, (uint32_t*)ms.p, (size_t)U, 0u, 64u, s));
-    GC(hipStreamSynchronize(s));
+    const int pos_bits = bit_length(hc.max_pos);
+    if (pos_bits + bit_length(C) > 63) { *status = AIX_ERR_UNSUPPORTED; return hipSuccess; }
+    AIX_TRY(word.alloc(4 * NE));
+    AIX_TRY(degp.alloc(NE));
+    AIX_TRY(mg.alloc(NE));
+    AIX_TRY(n0.alloc(8 * NE));
+    AIX_TRY(d0.alloc(8 * NE));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
+    AIX_TRY(keys.alloc(8 * U));
+    AIX_TRY(ids.alloc(4 * U));
+    AIX_TRY(keys2.alloc(8 * U));
+    AIX_TRY(ms.alloc(4 * U));
+    AIX_TRY_LAUNCH(k_gc_keys, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, U, pos_bits, remove, contig, pos, (uint64_t*)keys.p, (uint32_t*)ids.p);
+    AIX_TRY(sort_pairs((const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)ids.p, (uint32_t*)ms.p, U, 64u, tmp, s));
+    AIX_TRY(hipStreamSynchronize(s));
     n0.drop(); d0.drop(); keys.drop(); ids.drop();
-    GC(mlen.alloc(8 * (S + 1)));
-    GC(kpre.alloc(8 * (S + 1)));
-    GC(begin.alloc(8 * (S + 1)));
-    GC(noff.alloc(8 * (C + 1)));
-    GCL(k_gc_mlen, dim3(gc_grid(S + 1, 4 * kGB, cap)), blk, 0, s, S, (const uint32_t*)ms.p, U, g.offsets, (uint64_t*)mlen.p);
-    tb = 0;
-    GC(rocprim::exclusive_scan(nullptr, tb, (const uint64_t*)mlen.p, (uint64_t*)kpre.p, (uint64_t)0, (size_t)(S + 1), rocprim::plus<uint64_t>(), s));
-    GC(tmp.alloc(tb ? tb : 1));
-    GC(rocprim::exclusive_scan(tmp.p, tb, (const uint64_t*)mlen.p, (uint64_t*)kpre.p, (uint64_t)0, (size_t)(S + 1), rocprim::plus<uint64_t>(), s));
-    GC(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    GC(hipMemsetAsync(noff.p, 0, 8 * (C + 1), s));
-    GCL(k_gc_begin, dim3(gc_grid(S, 4 * kGB, cap)), blk, 0, s, S, C, pos_bits, (const uint64_t*)keys2.p, (const uint64_t*)kpre.p, total, (uint64_t*)begin.p,
+    AIX_TRY(mlen.alloc(8 * (S + 1)));
+    AIX_TRY(kpre.alloc(8 * (S + 1)));
+    AIX_TRY(begin.alloc(8 * (S + 1)));
+    AIX_TRY(noff.alloc(8 * (C + 1)));
+    AIX_TRY_LAUNCH(k_gc_mlen, dim3(chain_grid(S + 1, 4 * kCB, cap)), blk, 0, s, S, (const uint32_t*)ms.p, U, g.offsets, (uint64_t*)mlen.p);
+    AIX_TRY(scan_u64((const uint64_t*)mlen.p, (uint64_t*)kpre.p, S + 1, tmp, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
+    AIX_TRY(hipMemsetAsync(noff.p, 0, 8 * (C + 1), s));
+    AIX_TRY_LAUNCH(k_gc_begin, dim3(chain_grid(S, 4 * kCB, cap)), blk, 0, s, S, C, pos_bits, (const uint64_t*)keys2.p, (const uint64_t*)kpre.p, total, (uint64_t*)begin.p,
         (uint64_t*)noff.p, ctr);
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(chain_read(&hc, ctr, s));
     if (hc.bad) return hipSuccess;
-    GC(ndeg.alloc(4 * (2 * C + 1)));
-    GC(nlo.alloc(8 * (2 * C + 1)));
-    GC(hipMemsetAsync(ndeg.p, 0, 4 * (2 * C + 1), s));
-    GCL(k_gc_ends, dim3(gc_grid(NE, 2 * kGB, cap)), blk, 0, s, U, C, g.offsets, g.circular, g.link_off, g.link_to, remove, (const uint32_t*)word.p, (const uint8_t*)degp.p,
-        (const uint8_t*)mg.p, contig, pos, flag, (const uint64_t*)noff.p, (uint32_t*)ndeg.p, ctr);
-    auto din = rocprim::make_transform_iterator((const uint32_t*)ndeg.p, GcWiden());
-    tb = 0;
-    GC(rocprim::exclusive_scan(nullptr, tb, din, (uint64_t*)nlo.p, (uint64_t)0, (size_t)(2 * C + 1), rocprim::plus<uint64_t>(), s));
-    GC(tmp.alloc(tb ? tb : 1));
-    GC(rocprim::exclusive_scan(tmp.p, tb, din, (uint64_t*)nlo.p, (uint64_t)0, (size_t)(2 * C + 1), rocprim::plus<uint64_t>(), s));
+    AIX_TRY(ndeg.alloc(4 * (2 * C + 1)));
+    AIX_TRY(nlo.alloc(8 * (2 * C + 1)));
+    AIX_TRY(hipMemsetAsync(ndeg.p, 0, 4 * (2 * C + 1), s));
+    AIX_TRY_LAUNCH(k_gc_ends, dim3(chain_grid(NE, 2 * kCB, cap)), blk, 0, s, U, C, g.offsets, g.circular, g.link_off, g.link_to, remove, (const uint32_t*)word.p,
+        (const uint8_t*)degp.p, (const uint8_t*)mg.p, contig, pos, flag, (const uint64_t*)noff.p, (uint32_t*)ndeg.p, ctr);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint32_t*)ndeg.p, Widen<uint32_t>()), (uint64_t*)nlo.p, 2 * C + 1, tmp, s));
     uint64_t E_new = 0;
-    GC(hipMemcpyAsync(&E_new, (const uint64_t*)nlo.p + 2 * C, 8, hipMemcpyDeviceToHost, s));
-    GC(gc_read(&hc, ctr, s));
+    AIX_TRY(hipMemcpyAsync(&E_new, (const uint64_t*)nlo.p + 2 * C, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(chain_read(&hc, ctr, s));
     if (hc.bad || E_new != E2) return hipSuccess;
     // everything is validated: from here on the outputs are written
-    GC(hipMemcpyAsync(o.offsets, noff.p, 8 * (C + 1), hipMemcpyDeviceToDevice, s));
-    GC(hipMemcpyAsync(o.link_off, nlo.p, 8 * (2 * C + 1), hipMemcpyDeviceToDevice, s));
+    AIX_TRY(hipMemcpyAsync(o.offsets, noff.p, 8 * (C + 1), hipMemcpyDeviceToDevice, s));
+    AIX_TRY(hipMemcpyAsync(o.link_off, nlo.p, 8 * (2 * C + 1), hipMemcpyDeviceToDevice, s));
     if (E2)
-        GCL(k_gc_fill, dim3(gc_grid(NE, 4 * kGB, cap)), blk, 0, s, U, g.circular, g.link_off, g.link_to, remove, (const uint8_t*)mg.p, contig, flag, (const uint64_t*)nlo.p,
-            E2, o.link_to);
-    GCL(k_gc_emit, dim3(gc_grid((total + 15) >> 4, kGB, cap)), blk, 0, s, S, (const uint64_t*)begin.p, (const uint32_t*)ms.p, (const uint64_t*)keys2.p, pos_bits, g.offsets,
-        flag, reinterpret_cast<const uint64_t*>(g.bases), total_in, o.bases, total);
-    GC(agg.alloc(sizeof(GcAgg) * S));
-    GC(uniq.alloc(8 * C));
-    GC(ragg.alloc(sizeof(GcAgg) * C));
-    GC(cnt.alloc(8));
-    GCL(k_gc_gather, dim3(gc_grid(S, 4 * kGB, cap)), blk, 0, s, S, (const uint32_t*)ms.p, (const uint64_t*)keys2.p, pos_bits, C, g.circular, flag, g.tf_sum, g.tf_min,
-        g.tf_max, (GcAgg*)agg.p, o.circular);
-    auto kin = rocprim::make_transform_iterator((const uint64_t*)keys2.p, GcContigOf{pos_bits});
-    tb = 0;
-    GC(rocprim::reduce_by_key(nullptr, tb, kin, (const GcAgg*)agg.p, (size_t)S, (uint64_t*)uniq.p, (GcAgg*)ragg.p, (uint64_t*)cnt.p, GcAggOp(),
-                              rocprim::equal_to<uint64_t>(), s));
-    GC(tmp.alloc(tb ? tb : 1));
-    GC(rocprim::reduce_by_key(tmp.p, tb, kin, (const GcAgg*)agg.p, (size_t)S, (uint64_t*)uniq.p, (GcAgg*)ragg.p, (uint64_t*)cnt.p, GcAggOp(),
-                              rocprim::equal_to<uint64_t>(), s));
-    GCL(k_gc_stats, dim3(gc_grid(C, 4 * kGB, cap)), blk, 0, s, (const uint64_t*)uniq.p, (const GcAgg*)ragg.p, (const uint64_t*)cnt.p, C, o.tf_sum, o.tf_min, o.tf_max);
+        AIX_TRY_LAUNCH(k_gc_fill, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, U, g.circular, g.link_off, g.link_to, remove, (const uint8_t*)mg.p, contig, flag,
+            (const uint64_t*)nlo.p, E2, o.link_to);
+    AIX_TRY_LAUNCH(k_gc_emit, dim3(chain_grid((total + 15) >> 4, kCB, cap)), blk, 0, s, S, (const uint64_t*)begin.p, (const uint32_t*)ms.p, (const uint64_t*)keys2.p, pos_bits,
+        g.offsets, flag, reinterpret_cast<const uint64_t*>(g.bases), total_in, o.bases, total);
+    AIX_TRY(agg.alloc(sizeof(ChainAgg) * S));
+    AIX_TRY(uniq.alloc(8 * C));
+    AIX_TRY(ragg.alloc(sizeof(ChainAgg) * C));
+    AIX_TRY(cnt.alloc(8));
+    AIX_TRY_LAUNCH(k_gc_gather, dim3(chain_grid(S, 4 * kCB, cap)), blk, 0, s, S, (const uint32_t*)ms.p, (const uint64_t*)keys2.p, pos_bits, C, g.circular, flag, g.tf_sum, g.tf_min,
+        g.tf_max, (ChainAgg*)agg.p, o.circular);
+    auto kin = rocprim::make_transform_iterator((const uint64_t*)keys2.p, ChainUnitOf{pos_bits});
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) {
+        return rocprim::reduce_by_key(t, tb, kin, (const ChainAgg*)agg.p, (size_t)S, (uint64_t*)uniq.p, (ChainAgg*)ragg.p, (uint64_t*)cnt.p, ChainAggOp(),
+                                      rocprim::equal_to<uint64_t>(), s);
+    }));
+    AIX_TRY_LAUNCH(k_chain_stats<ChainAgg>, dim3(chain_grid(C, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)uniq.p, (const ChainAgg*)ragg.p, (const uint64_t*)cnt.p, C, o.tf_sum,
+                   o.tf_min, o.tf_max);
     *status = AIX_OK;
     return hipStreamSynchronize(s);
 }
@@ -846,16 +750,6 @@ static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define GCCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 // the refusals every entry point shares, decided before anything is allocated or launched
 static int gc_check_sizes(uint64_t U, const void* offsets, const void* circular, const void* link_off, const void* link_to, uint64_t E) {
     if (U > 0x7FFFFFFFull - 4) return AIX_ERR_UNSUPPORTED;       // an end (2 u + side) must fit its u32 word below the codes
@@ -879,14 +773,14 @@ extern "C" int aix_graph_mark_dev(uint64_t U, const uint64_t* d_offsets, const u
         DevArr bm(s);
         const uint32_t* mate = d_bubble_mate;
         if (!mate) {
-            GCCHK(bm.alloc(4 * U));
+            AIXCHK(bm.alloc(4 * U));
             const int r = aix_unitig_bubbles_dev(U, d_link_off, d_link_to, E, (uint32_t*)bm.p, stream);
             if (r) return r;
             mate = (const uint32_t*)bm.p;
         }
         const GcGraph g{U, E, d_offsets, nullptr, d_circular, d_tf_sum, nullptr, nullptr, d_link_off, d_link_to};
         bool bad = false;
-        GCCHK(gc_mark(g, mate, tip_max_kmers, bubble_max_kmers, d_remove, out, &bad, s));
+        AIXCHK(gc_mark(g, mate, tip_max_kmers, bubble_max_kmers, d_remove, out, &bad, s));
         if (bad) return AIX_ERR_ARG;
     }
     *n_tips_out = out[0];
@@ -905,7 +799,7 @@ extern "C" int aix_graph_compact_layout_dev(uint64_t U, const uint64_t* d_offset
     const GcGraph g{U, E, d_offsets, d_bases, d_circular, nullptr, nullptr, nullptr, d_link_off, d_link_to};
     uint64_t out[4] = {0, 0, 0, 0};
     bool bad = false;
-    GCCHK(gc_layout(g, d_remove, d_unitig_contig, d_unitig_pos, d_unitig_flag, out, &bad, (hipStream_t)stream));
+    AIXCHK(gc_layout(g, d_remove, d_unitig_contig, d_unitig_pos, d_unitig_flag, out, &bad, (hipStream_t)stream));
     if (bad) return AIX_ERR_ARG;
     *n_contigs_out = out[0]; *total_bases_out = out[1]; *n_links_out = out[2]; *n_circular_out = out[3];
     return AIX_OK;
@@ -927,7 +821,7 @@ extern "C" int aix_graph_compact_emit_dev(uint64_t U, const uint64_t* d_offsets,
     const GcGraph g{U, E, d_offsets, d_bases, d_circular, d_tf_sum, d_tf_min, d_tf_max, d_link_off, d_link_to};
     const GcOut o{d_out_offsets, d_out_bases, d_out_circular, d_out_tf_sum, d_out_tf_min, d_out_tf_max, d_out_link_off, d_out_link_to};
     int status = AIX_ERR_ARG;
-    GCCHK(gc_emit(g, d_remove, d_unitig_contig, d_unitig_pos, d_unitig_flag, C, total_bases, n_links, o, &status, (hipStream_t)stream));
+    AIXCHK(gc_emit(g, d_remove, d_unitig_contig, d_unitig_pos, d_unitig_flag, C, total_bases, n_links, o, &status, (hipStream_t)stream));
     return status;
 }
 
@@ -952,13 +846,13 @@ extern "C" int aix_graph_clean(uint64_t U, const uint64_t* offsets, const uint8_
     const void* src[9] = {offsets, bases, circular, tf_sum, tf_min, tf_max, link_off, link_to, nullptr};
     const uint64_t bytes[9] = {8 * (U + 1), total_in, U, 8 * U, 4 * U, 4 * U, 8 * (2 * U + 1), 4 * E, 0};
     for (int i = 0; i < 8; ++i) {
-        GCCHK(in[i].alloc(bytes[i]));
-        if (bytes[i]) GCCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
+        AIXCHK(in[i].alloc(bytes[i]));
+        if (bytes[i]) AIXCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
     }
-    GCCHK(rm.alloc(U));
-    GCCHK(uc.alloc(4 * U));
-    GCCHK(up.alloc(8 * U));
-    GCCHK(uf.alloc(U));
+    AIXCHK(rm.alloc(U));
+    AIXCHK(uc.alloc(4 * U));
+    AIXCHK(up.alloc(8 * U));
+    AIXCHK(uf.alloc(U));
     uint64_t tips = 0, arms = 0, C = 0, total = 0, E2 = 0, n_circ = 0;
     int r = aix_graph_mark_dev(U, (const uint64_t*)in[0].p, (const uint8_t*)in[2].p, (const uint64_t*)in[3].p, (const uint64_t*)in[6].p, (const uint32_t*)in[7].p, E,
                                nullptr, tip_max_kmers, bubble_max_kmers, (uint8_t*)rm.p, &tips, &arms, nullptr);
@@ -966,38 +860,25 @@ extern "C" int aix_graph_clean(uint64_t U, const uint64_t* offsets, const uint8_
     r = aix_graph_compact_layout_dev(U, (const uint64_t*)in[0].p, (const uint8_t*)in[1].p, (const uint8_t*)in[2].p, (const uint64_t*)in[6].p, (const uint32_t*)in[7].p,
                                      E, (const uint8_t*)rm.p, (uint32_t*)uc.p, (uint64_t*)up.p, (uint8_t*)uf.p, &C, &total, &E2, &n_circ, nullptr);
     if (r) return r;
-    GCCHK(oo.alloc(8 * (C + 1)));
-    GCCHK(ob.alloc(total));
-    GCCHK(oc.alloc(C));
-    GCCHK(os.alloc(8 * C));
-    GCCHK(on.alloc(4 * C));
-    GCCHK(ox.alloc(4 * C));
-    GCCHK(ol.alloc(8 * (2 * C + 1)));
-    GCCHK(ot.alloc(4 * E2));
+    AIXCHK(oo.alloc(8 * (C + 1)));
+    AIXCHK(ob.alloc(total));
+    AIXCHK(oc.alloc(C));
+    AIXCHK(os.alloc(8 * C));
+    AIXCHK(on.alloc(4 * C));
+    AIXCHK(ox.alloc(4 * C));
+    AIXCHK(ol.alloc(8 * (2 * C + 1)));
+    AIXCHK(ot.alloc(4 * E2));
     r = aix_graph_compact_emit_dev(U, (const uint64_t*)in[0].p, (const uint8_t*)in[1].p, (const uint8_t*)in[2].p, (const uint64_t*)in[3].p, (const uint32_t*)in[4].p,
                                    (const uint32_t*)in[5].p, (const uint64_t*)in[6].p, (const uint32_t*)in[7].p, E, (const uint8_t*)rm.p, (const uint32_t*)uc.p,
                                    (const uint64_t*)up.p, (const uint8_t*)uf.p, C, total, E2, (uint64_t*)oo.p, (uint8_t*)ob.p, (uint8_t*)oc.p, (uint64_t*)os.p,
                                    (uint32_t*)on.p, (uint32_t*)ox.p, (uint64_t*)ol.p, (uint32_t*)ot.p, nullptr);
     if (r) return r;
     // host copies: {destination, device block, bytes}; a NULL destination is an output the caller did not ask for
-    struct Out { void** dst; const void* src; uint64_t bytes; } outs[] = {
+    const HostOut outs[] = {
         {(void**)offsets_out, oo.p, 8 * (C + 1)}, {(void**)bases_out, ob.p, total}, {(void**)circular_out, oc.p, C}, {(void**)tf_sum_out, os.p, 8 * C},
         {(void**)tf_min_out, on.p, 4 * C}, {(void**)tf_max_out, ox.p, 4 * C}, {(void**)link_off_out, ol.p, 8 * (2 * C + 1)}, {(void**)link_to_out, ot.p, 4 * E2},
         {(void**)remove_out, rm.p, U}, {(void**)unitig_contig_out, uc.p, 4 * U}, {(void**)unitig_pos_out, up.p, 8 * U}, {(void**)unitig_flag_out, uf.p, U}};
-    void* host[12] = {nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 12 && e == hipSuccess; ++i) {
-        if (!outs[i].dst) continue;
-        host[i] = malloc(outs[i].bytes ? outs[i].bytes : 1);
-        if (!host[i]) e = hipErrorOutOfMemory;
-        else if (outs[i].bytes) e = hipMemcpy(host[i], outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) {
-        for (void* p : host) free(p);
-        GCCHK(e);
-    }
-    for (int i = 0; i < 12; ++i)
-        if (outs[i].dst) *outs[i].dst = host[i];
+    AIXCHK(copy_out_host(outs, 12));
     *n_contigs_out = C; *n_links_out = E2; *n_tips_out = tips; *n_arms_out = arms;
     return AIX_OK;
 }

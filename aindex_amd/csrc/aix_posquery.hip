@@ -27,19 +27,11 @@
 #include <new>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "aix_posquery.hpp"
 
 namespace aix {
 
-static constexpr int kB = 256;
-static inline unsigned pq_grid(uint64_t work) {
-    uint64_t b = (work + kB - 1) / kB;
-    if (b > 8192) b = std::max<uint64_t>(8192, std::min<uint64_t>(b / 4, 65536));
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
+static constexpr int kB = kFlatBlock;                             // the grid of the flat kernels: flat_grid (aix_hostkit.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // attach: indices[0] == 0, indices[i] <= indices[i + 1], indices[n] <= total
@@ -207,17 +199,6 @@ __global__ void __launch_bounds__(kB) k_pq_locate(const uint64_t* __restrict__ p
 }
 
 struct PqNonEmpty { __host__ __device__ uint64_t operator()(uint64_t v) const { return v ? 1ull : 0ull; } };
-struct PqWiden { __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; } };
-
-// out[i] = in[0] + .. + in[i - 1] over n entries, u64 sums; `tmp` stays allocated until the caller has synchronised the stream
-template <class It>
-static hipError_t pq_scan(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    return e;
-}
 
 static unsigned pq_flat_grid(uint64_t C) {
     const uint64_t want = (C + 4 * 8 - 1) / (4 * 8);           // at least eight chunks per wave, four waves per workgroup
@@ -233,8 +214,8 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     hipError_t e = fo.alloc(8 * (N + 1));
     if (e == hipSuccess) e = nj.alloc(8 * (N + 1));
     if (e != hipSuccess) return e;
-    e = pq_scan(d_ub, (uint64_t*)fo.p, N + 1, t0, s);
-    if (e == hipSuccess) e = pq_scan(rocprim::make_transform_iterator(d_ub, PqNonEmpty()), (uint64_t*)nj.p, N + 1, t1, s);
+    e = scan_u64(d_ub, (uint64_t*)fo.p, N + 1, t0, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator(d_ub, PqNonEmpty()), (uint64_t*)nj.p, N + 1, t1, s);
     uint64_t T = 0, J = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&T, (const uint64_t*)fo.p + N, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&J, (const uint64_t*)nj.p + N, 8, hipMemcpyDeviceToHost, s);
@@ -251,7 +232,7 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     if (e == hipSuccess) e = wr.alloc(8 * (C + 1));
     if (e == hipSuccess) e = kept.alloc(8 * (N + 1));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pq_compact, dim3(pq_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, d_lo, J, T,
+    hipLaunchKernelGGL(k_pq_compact, dim3(flat_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, d_lo, J, T,
                        (uint64_t*)ne.p, (uint64_t*)nfo.p, (uint64_t*)nlo.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemsetAsync((uint64_t*)bits.p + C, 0, 8, s);
@@ -264,12 +245,12 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     P.offsets = d_offsets; P.m = m;
     hipLaunchKernelGGL(k_pq_flat<false>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
     e = hipGetLastError();
-    if (e == hipSuccess) e = pq_scan(rocprim::make_transform_iterator((const uint32_t*)cnt.p, PqWiden()), (uint64_t*)wr.p, C + 1, t2, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint32_t*)cnt.p, Widen<uint32_t>()), (uint64_t*)wr.p, C + 1, t2, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pq_segrank, dim3(pq_grid(J)), dim3(kB), 0, s, (const uint64_t*)bits.p, (const uint64_t*)wr.p, (const uint64_t*)nfo.p, (const uint64_t*)ne.p, J, m,
+    hipLaunchKernelGGL(k_pq_segrank, dim3(flat_grid(J)), dim3(kB), 0, s, (const uint64_t*)bits.p, (const uint64_t*)wr.p, (const uint64_t*)nfo.p, (const uint64_t*)ne.p, J, m,
                        (uint64_t*)nraw.p, (uint64_t*)kept.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = pq_scan((const uint64_t*)kept.p, d_offsets, N + 1, t3, s);
+    if (e == hipSuccess) e = scan_u64((const uint64_t*)kept.p, d_offsets, N + 1, t3, s);
     uint64_t total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d_offsets + N, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -305,10 +286,10 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     uint64_t* d_ub = (uint64_t*)ub.p;
     e = hipMemsetAsync(d_ub + N, 0, 8, s);
     if (e != hipSuccess) return e;
-    if (h->k == 13) hipLaunchKernelGGL(k_pq_resolve13, dim3(pq_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 2) hipLaunchKernelGGL(k_pq_resolve23<2>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 4) hipLaunchKernelGGL(k_pq_resolve23<4>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else hipLaunchKernelGGL(k_pq_resolve23<8>, dim3(pq_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    if (h->k == 13) hipLaunchKernelGGL(k_pq_resolve13, dim3(flat_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 2) hipLaunchKernelGGL(k_pq_resolve23<2>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 4) hipLaunchKernelGGL(k_pq_resolve23<4>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else hipLaunchKernelGGL(k_pq_resolve23<8>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return posquery_lists(h, (const uint64_t*)lo.p, d_ub, N, m, d_offsets, d_positions, d_rid, d_local, cap, total_out, s);
@@ -319,16 +300,6 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define PQCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 static void pq_detach_aindex(aix_index* h) {
     if (h->ai_owned) {
         if (h->ai_indices) (void)hipFree(h->ai_indices);
@@ -351,12 +322,12 @@ void posquery_release(aix_index* h) {
 static int pq_validate(aix_index* h, const uint64_t* d_indices, uint64_t total, hipStream_t s) {
     DevBuf flag(s);
     uint32_t bad = 0;
-    PQCHK(flag.alloc(4));
-    PQCHK(hipMemsetAsync(flag.p, 0, 4, s));
-    hipLaunchKernelGGL(k_pq_validate, dim3(pq_grid(h->n + 1)), dim3(kB), 0, s, d_indices, h->n, total, (uint32_t*)flag.p);
-    PQCHK(hipGetLastError());
-    PQCHK(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, s));
-    PQCHK(hipStreamSynchronize(s));
+    AIXCHK(flag.alloc(4));
+    AIXCHK(hipMemsetAsync(flag.p, 0, 4, s));
+    hipLaunchKernelGGL(k_pq_validate, dim3(flat_grid(h->n + 1)), dim3(kB), 0, s, d_indices, h->n, total, (uint32_t*)flag.p);
+    AIXCHK(hipGetLastError());
+    AIXCHK(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, s));
+    AIXCHK(hipStreamSynchronize(s));
     return bad ? AIX_ERR_FORMAT : AIX_OK;
 }
 
@@ -428,11 +399,11 @@ extern "C" int aix_ridx_attach(aix_index_t* h, const uint64_t* triples, uint64_t
         soa[2 * n_reads + i] = triples[3 * i];
     }
     uint64_t* d = nullptr;
-    PQCHK(hipMalloc((void**)&d, n_reads ? 24 * n_reads : 8));
+    AIXCHK(hipMalloc((void**)&d, n_reads ? 24 * n_reads : 8));
     if (n_reads) {
         const hipError_t e = hipMemcpy(d, soa.data(), 24 * n_reads, hipMemcpyHostToDevice);
         if (e != hipSuccess) (void)hipFree(d);
-        PQCHK(e);
+        AIXCHK(e);
     }
     if (h->rx) { (void)hipDeviceSynchronize(); (void)hipFree(h->rx); h->device_bytes -= 24 * h->rx_n; }
     h->rx = d; h->rx_n = n_reads; h->rx_attached = true;
@@ -446,7 +417,7 @@ extern "C" int aix_positions_query_dev(aix_index_t* h, const char* d_kmers, uint
     if (!h->ai_attached || (d_rid && !h->rx_attached)) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
     if (h->k == 23 && h->n == 0) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
-    PQCHK(posquery_run(h, (const uint8_t*)d_kmers, N, max_per_kmer, d_offsets, cap ? d_positions : nullptr, d_rid, d_local, cap, total_out, (hipStream_t)stream));
+    AIXCHK(posquery_run(h, (const uint8_t*)d_kmers, N, max_per_kmer, d_offsets, cap ? d_positions : nullptr, d_rid, d_local, cap, total_out, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -460,16 +431,16 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
     DevGuard g(h->device);
     const uint64_t qb = N * h->k;
     DevBuf dq, doff, dpos, drid, dloc;
-    PQCHK(dq.alloc(qb + 16));
-    PQCHK(doff.alloc(8 * (N + 1)));
-    if (qb) PQCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
+    AIXCHK(dq.alloc(qb + 16));
+    AIXCHK(doff.alloc(8 * (N + 1)));
+    if (qb) AIXCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
     uint64_t total = 0;
-    PQCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, nullptr, nullptr, nullptr, 0, &total, 0));
+    AIXCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, nullptr, nullptr, nullptr, 0, &total, 0));
     if (total) {
-        PQCHK(dpos.alloc(8 * total));
-        if (rid_out) { PQCHK(drid.alloc(8 * total)); PQCHK(dloc.alloc(8 * total)); }
+        AIXCHK(dpos.alloc(8 * total));
+        if (rid_out) { AIXCHK(drid.alloc(8 * total)); AIXCHK(dloc.alloc(8 * total)); }
         uint64_t again = 0;
-        PQCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, (uint64_t*)dpos.p, (uint64_t*)drid.p, (uint64_t*)dloc.p, total, &again, 0));
+        AIXCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, (uint64_t*)dpos.p, (uint64_t*)drid.p, (uint64_t*)dloc.p, total, &again, 0));
         if (again != total) { set_last_error("aix_positions_query: the index changed between the sizing and the filling pass"); return AIX_ERR_HIP; }
     }
     uint64_t* ho = (uint64_t*)malloc(8 * (N + 1));
@@ -481,7 +452,7 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
     if (e == hipSuccess && total) e = hipMemcpy(hp, dpos.p, 8 * total, hipMemcpyDeviceToHost);
     if (e == hipSuccess && total && rid_out) e = hipMemcpy(hr, drid.p, 8 * total, hipMemcpyDeviceToHost);
     if (e == hipSuccess && total && rid_out) e = hipMemcpy(hl, dloc.p, 8 * total, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(ho); free(hp); free(hr); free(hl); PQCHK(e); }
+    if (e != hipSuccess) { free(ho); free(hp); free(hr); free(hl); AIXCHK(e); }
     *offsets_out = ho; *positions_out = hp;
     if (rid_out) { *rid_out = hr; *local_out = hl; }
     return AIX_OK;
@@ -492,8 +463,8 @@ extern "C" int aix_positions_locate_dev(aix_index_t* h, const uint64_t* d_pos, u
     if (!h->rx_attached) return AIX_ERR_ARG;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    hipLaunchKernelGGL(k_pq_locate, dim3(pq_grid(N)), dim3(kB), 0, (hipStream_t)stream, d_pos, N, h->rx, h->rx + h->rx_n, h->rx + 2 * h->rx_n, h->rx_n, d_rid, d_start);
-    PQCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pq_locate, dim3(flat_grid(N)), dim3(kB), 0, (hipStream_t)stream, d_pos, N, h->rx, h->rx + h->rx_n, h->rx + 2 * h->rx_n, h->rx_n, d_rid, d_start);
+    AIXCHK(hipGetLastError());
     return AIX_OK;
 }
 
@@ -503,13 +474,13 @@ extern "C" int aix_positions_locate(aix_index_t* h, const uint64_t* pos, uint64_
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
     DevBuf dp, dr, ds;
-    PQCHK(dp.alloc(8 * N));
-    PQCHK(dr.alloc(8 * N));
-    PQCHK(ds.alloc(8 * N));
-    PQCHK(hipMemcpy(dp.p, pos, 8 * N, hipMemcpyHostToDevice));
+    AIXCHK(dp.alloc(8 * N));
+    AIXCHK(dr.alloc(8 * N));
+    AIXCHK(ds.alloc(8 * N));
+    AIXCHK(hipMemcpy(dp.p, pos, 8 * N, hipMemcpyHostToDevice));
     const int st = aix_positions_locate_dev(h, (const uint64_t*)dp.p, N, (uint64_t*)dr.p, (uint64_t*)ds.p, nullptr);
     if (st) return st;
-    PQCHK(hipMemcpy(rid_out, dr.p, 8 * N, hipMemcpyDeviceToHost));
-    PQCHK(hipMemcpy(start_out, ds.p, 8 * N, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(rid_out, dr.p, 8 * N, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(start_out, ds.p, 8 * N, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

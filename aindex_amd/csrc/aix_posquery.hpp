@@ -1,7 +1,7 @@
 // aix_posquery.hpp — the device functions of the position queries that more than one translation unit uses (aix_posquery.hip: packed
 // k-mer batches; aix_seqhits.hip: the windows of sequences), and the part of the chain behind the resolve step.
 #pragma once
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 
 namespace aix {
 

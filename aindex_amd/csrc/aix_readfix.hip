@@ -19,7 +19,7 @@
 // Both phase loops strictly advance (a fix raises `fixes`, a failure moves c by at least one window), so they are bounded by
 // W + max_fixes trips each; there is no run-until-done form. Offsets into the buffer and the log rows are 64 bits wide. Integer only.
 #include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 #include "aix_probe.hpp"
 
 namespace aix {
@@ -250,13 +250,6 @@ hipError_t launch_reads_fix(const IndexDev& ix, uint8_t* buf, uint64_t total, co
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define RFALLOC(buf, bytes)                                                                   \
-    do {                                                                                      \
-        const hipError_t e_ = (buf).alloc(bytes);                                             \
-        if (e_ == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }     \
-        HIPCHK(e_);                                                                           \
-    } while (0)
-
 static_assert(sizeof(aix_readfix_t) == 32, "aix_readfix_t is eight u32 words");
 
 // the checks both forms share
@@ -302,16 +295,16 @@ extern "C" int aix_reads_fix(aix_index_t* h, char* buf, uint64_t total_bytes, co
     if (__builtin_mul_overflow(M, (uint64_t)max_fixes, &cells) || cells >= (1ULL << 48)) return AIX_ERR_NOMEM;
     DevGuard g(h->device);
     DevBuf db, ds, de, dr, dp, dold;
-    RFALLOC(db, total_bytes);
-    RFALLOC(ds, 8 * M);
-    RFALLOC(de, 8 * M);
-    RFALLOC(dr, sizeof(aix_readfix_t) * M);
+    AIXCHK(db.alloc(total_bytes));
+    AIXCHK(ds.alloc(8 * M));
+    AIXCHK(de.alloc(8 * M));
+    AIXCHK(dr.alloc(sizeof(aix_readfix_t) * M));
     HIPCHK(hipMemcpy(db.p, buf, total_bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ds.p, start, 8 * M, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(de.p, end, 8 * M, hipMemcpyHostToDevice));
     if (max_fixes) {
-        RFALLOC(dp, 4 * cells);
-        RFALLOC(dold, cells);
+        AIXCHK(dp.alloc(4 * cells));
+        AIXCHK(dold.alloc(cells));
         // a row is written up to `fixes` only: the caller's rows go up first, so that what lies beyond comes back as it was
         HIPCHK(hipMemcpy(dp.p, fix_pos, 4 * cells, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dold.p, fix_old, cells, hipMemcpyHostToDevice));

@@ -24,19 +24,11 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 
 namespace aix {
 
-static constexpr int kRB = 256;
-static inline unsigned rq_grid(uint64_t work) {
-    uint64_t b = (work + kRB - 1) / kRB;
-    if (b > 8192) b = std::max<uint64_t>(8192, std::min<uint64_t>(b / 4, 65536));
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
+static constexpr int kRB = kFlatBlock;                            // the grid of the flat kernels: flat_grid (aix_hostkit.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // 1. spans
@@ -183,24 +175,12 @@ static unsigned rq_gather_grid(uint64_t total) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, 4096));
 }
 
-struct RqWiden8 { __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)v; } };
-
-// out[i] = in[0] + .. + in[i - 1] over n entries, u64 sums; `tmp` stays allocated until the caller has synchronised the stream
-template <class It>
-static hipError_t rq_scan(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    return e;
-}
-
 // passes 2 and 3: d_len (R + 1, last entry 0) -> d_offsets (R + 1) and *total_out, always; the bytes only when *total_out <= cap
 static hipError_t rq_gather_run(aix_index* h, const uint64_t* d_src, const uint64_t* d_len, const uint8_t* d_rc, uint64_t R, uint64_t* d_offsets, uint8_t* d_bytes,
                                 uint64_t cap, uint64_t* total_out, hipStream_t s) {
     *total_out = 0;
     DevArr tmp(s);
-    hipError_t e = rq_scan(d_len, d_offsets, R + 1, tmp, s);
+    hipError_t e = scan_u64(d_len, d_offsets, R + 1, tmp, s);
     uint64_t total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d_offsets + R, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -355,8 +335,8 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     const uint64_t rn = h->rx_n;
     const uint64_t *rs = h->rx, *re = h->rx + rn, *rr = h->rx + 2 * rn;
     const uint64_t *d_off = (const uint64_t*)off.p, *d_lst = (const uint64_t*)lst.p, *d_key = (const uint64_t*)key.p;
-    hipLaunchKernelGGL(k_rk_locate, dim3(rq_grid(T)), dim3(kRB), 0, s, d_off, N, (const uint64_t*)pos.p, T, rs, re, rn, (uint64_t*)lst.p, (uint64_t*)key.p);
-    hipLaunchKernelGGL(k_rk_ascending, dim3(rq_grid(T)), dim3(kRB), 0, s, d_lst, d_key, T, (uint32_t*)flag.p);
+    hipLaunchKernelGGL(k_rk_locate, dim3(flat_grid(T)), dim3(kRB), 0, s, d_off, N, (const uint64_t*)pos.p, T, rs, re, rn, (uint64_t*)lst.p, (uint64_t*)key.p);
+    hipLaunchKernelGGL(k_rk_ascending, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, d_key, T, (uint32_t*)flag.p);
     e = hipGetLastError();
     uint32_t unsorted = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&unsorted, flag.p, 4, hipMemcpyDeviceToHost, s);
@@ -379,20 +359,20 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
         if (e == hipSuccess) e = tmp.alloc(std::max<size_t>(std::max(tb, tb2), 1));
         if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, d_key, (uint64_t*)k2.p, iota, (uint64_t*)perm.p, (size_t)T, 0u, kb, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rk_gather_lst, dim3(rq_grid(T)), dim3(kRB), 0, s, d_lst, (const uint64_t*)perm.p, T, (uint64_t*)k3.p);
+        hipLaunchKernelGGL(k_rk_gather_lst, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, (const uint64_t*)perm.p, T, (uint64_t*)k3.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s);
         if (e != hipSuccess) return e;
         d_perm = (const uint64_t*)p2.p;
     }
-    hipLaunchKernelGGL(k_rk_first, dim3(rq_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->rd_len, (uint8_t*)flags.p);
+    hipLaunchKernelGGL(k_rk_first, dim3(flat_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->rd_len, (uint8_t*)flags.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)flags.p + T, 0, 1, s);
-    if (e == hipSuccess) e = rq_scan(rocprim::make_transform_iterator((const uint8_t*)flags.p, RkFlagBit{(uint8_t)(m ? 1 : 0)}), (uint64_t*)rank.p, T + 1, t1, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)flags.p, RkFlagBit{(uint8_t)(m ? 1 : 0)}), (uint64_t*)rank.p, T + 1, t1, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rk_keep, dim3(rq_grid(T + 1)), dim3(kRB), 0, s, (const uint8_t*)flags.p, (const uint64_t*)rank.p, d_lst, d_off, T, m, (uint8_t*)keep.p);
+    hipLaunchKernelGGL(k_rk_keep, dim3(flat_grid(T + 1)), dim3(kRB), 0, s, (const uint8_t*)flags.p, (const uint64_t*)rank.p, d_lst, d_off, T, m, (uint8_t*)keep.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = rq_scan(rocprim::make_transform_iterator((const uint8_t*)keep.p, RqWiden8()), (uint64_t*)orank.p, T + 1, t2, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)orank.p, T + 1, t2, s);
     uint64_t R = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&R, (const uint64_t*)orank.p + T, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -400,7 +380,7 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     if (e == hipSuccess) e = src.alloc(8 * std::max<uint64_t>(R, 1));
     if (e == hipSuccess) e = len.alloc(8 * (R + 1));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rk_emit, dim3(rq_grid(std::max(T, N + 1))), dim3(kRB), 0, s, (const uint8_t*)keep.p, (const uint64_t*)orank.p, d_key, d_off, N, T, rs, re, rr, rn,
+    hipLaunchKernelGGL(k_rk_emit, dim3(flat_grid(std::max(T, N + 1))), dim3(kRB), 0, s, (const uint8_t*)keep.p, (const uint64_t*)orank.p, d_key, d_off, N, T, rs, re, rr, rn,
                        h->rd_len, R, d_koff, (uint64_t*)rid.p, (uint64_t*)src.p, (uint64_t*)len.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -413,16 +393,6 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define RQCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 void readsquery_release(aix_index* h) {
     if (h->rd_owned) {
         if (h->rd) (void)hipFree(h->rd);
@@ -448,7 +418,7 @@ extern "C" int aix_reads_attach(aix_index_t* h, const char* reads, uint64_t len)
     if (len) {
         e = hipMemcpy(d, reads, len, hipMemcpyHostToDevice);
         if (e != hipSuccess) (void)hipFree(d);
-        RQCHK(e);
+        AIXCHK(e);
     }
     (void)hipDeviceSynchronize();
     readsquery_release(h);
@@ -461,7 +431,7 @@ extern "C" int aix_reads_attach(aix_index_t* h, const char* reads, uint64_t len)
 extern "C" int aix_reads_attach_dev(aix_index_t* h, const char* d_reads, uint64_t len, void* stream) {
     if (!h || (len && !d_reads)) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    RQCHK(hipStreamSynchronize((hipStream_t)stream));          // what filled the buffer on `stream` has completed before any query reads it
+    AIXCHK(hipStreamSynchronize((hipStream_t)stream));          // what filled the buffer on `stream` has completed before any query reads it
     (void)hipDeviceSynchronize();
     readsquery_release(h);
     h->rd = reinterpret_cast<uint8_t*>(const_cast<char*>(d_reads)); h->rd_len = len;
@@ -491,11 +461,11 @@ extern "C" int aix_reads_fetch_dev(aix_index_t* h, const uint64_t* d_start, cons
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     DevArr src(s), len(s);
-    RQCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
-    RQCHK(len.alloc(8 * (N + 1)));
-    hipLaunchKernelGGL(k_rq_spans_fetch, dim3(rq_grid(N + 1)), dim3(kRB), 0, s, d_start, d_end, N, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
-    RQCHK(hipGetLastError());
-    RQCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, d_revcomp, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
+    AIXCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
+    AIXCHK(len.alloc(8 * (N + 1)));
+    hipLaunchKernelGGL(k_rq_spans_fetch, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_start, d_end, N, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
+    AIXCHK(hipGetLastError());
+    AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, d_revcomp, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
     return AIX_OK;
 }
 
@@ -506,11 +476,11 @@ extern "C" int aix_reads_fetch_rid_dev(aix_index_t* h, const uint64_t* d_rid, ui
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     DevArr src(s), len(s);
-    RQCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
-    RQCHK(len.alloc(8 * (N + 1)));
-    hipLaunchKernelGGL(k_rq_spans_rid, dim3(rq_grid(N + 1)), dim3(kRB), 0, s, d_rid, N, h->rx, h->rx + h->rx_n, h->rx_n, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
-    RQCHK(hipGetLastError());
-    RQCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
+    AIXCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
+    AIXCHK(len.alloc(8 * (N + 1)));
+    hipLaunchKernelGGL(k_rq_spans_rid, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_rid, N, h->rx, h->rx + h->rx_n, h->rx_n, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
+    AIXCHK(hipGetLastError());
+    AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
     return AIX_OK;
 }
 
@@ -529,20 +499,20 @@ extern "C" int aix_reads_by_kmers_dev(aix_index_t* h, const char* d_kmers, uint6
     totals_out[0] = totals_out[1] = 0;
     DevArr rid(s), src(s), len(s), roff(s);
     uint64_t R = 0, total = 0;
-    RQCHK(rk_run(h, (const uint8_t*)d_kmers, N, max_reads, d_kmer_offsets, rid, src, len, &R, s));
+    AIXCHK(rk_run(h, (const uint8_t*)d_kmers, N, max_reads, d_kmer_offsets, rid, src, len, &R, s));
     if (R) {
-        RQCHK(roff.alloc(8 * (R + 1)));
+        AIXCHK(roff.alloc(8 * (R + 1)));
         const bool fits = R <= cap_reads && d_rid && d_read_offsets;
-        RQCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, fits && cap_bytes ? (uint8_t*)d_bytes : nullptr, cap_bytes,
+        AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, fits && cap_bytes ? (uint8_t*)d_bytes : nullptr, cap_bytes,
                             &total, s));
         if (fits) {
-            RQCHK(hipMemcpyAsync(d_rid, rid.p, 8 * R, hipMemcpyDeviceToDevice, s));
-            RQCHK(hipMemcpyAsync(d_read_offsets, roff.p, 8 * (R + 1), hipMemcpyDeviceToDevice, s));
-            RQCHK(hipStreamSynchronize(s));
+            AIXCHK(hipMemcpyAsync(d_rid, rid.p, 8 * R, hipMemcpyDeviceToDevice, s));
+            AIXCHK(hipMemcpyAsync(d_read_offsets, roff.p, 8 * (R + 1), hipMemcpyDeviceToDevice, s));
+            AIXCHK(hipStreamSynchronize(s));
         }
     } else if (d_read_offsets) {
-        RQCHK(hipMemsetAsync(d_read_offsets, 0, 8, s));        // read_offsets = {0}
-        RQCHK(hipStreamSynchronize(s));
+        AIXCHK(hipMemsetAsync(d_read_offsets, 0, 8, s));        // read_offsets = {0}
+        AIXCHK(hipStreamSynchronize(s));
     }
     totals_out[0] = R; totals_out[1] = total;
     return AIX_OK;
@@ -554,7 +524,7 @@ static int rq_to_host(const void* d, uint64_t bytes, void** out) {
     if (!p) return AIX_ERR_NOMEM;
     if (bytes) {
         const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(p); RQCHK(e); }
+        if (e != hipSuccess) { free(p); AIXCHK(e); }
     }
     *out = p;
     return AIX_OK;
@@ -564,11 +534,11 @@ template <class Sizer>
 static int rq_host_fetch(uint64_t N, uint64_t** offsets_out, char** bytes_out, Sizer run) {
     *offsets_out = nullptr; *bytes_out = nullptr;
     DevBuf doff, dby;
-    RQCHK(doff.alloc(8 * (N + 1)));
+    AIXCHK(doff.alloc(8 * (N + 1)));
     uint64_t total = 0, again = 0;
     if (const int st = run((uint64_t*)doff.p, nullptr, 0, &total)) return st;
     if (total) {
-        RQCHK(dby.alloc(total));
+        AIXCHK(dby.alloc(total));
         if (const int st = run((uint64_t*)doff.p, (char*)dby.p, total, &again)) return st;
         if (again != total) { set_last_error("aix_reads_fetch: the attachment changed between the sizing and the filling pass"); return AIX_ERR_HIP; }
     }
@@ -586,11 +556,11 @@ extern "C" int aix_reads_fetch(aix_index_t* h, const uint64_t* start, const uint
     if (!h->rd_attached) return AIX_ERR_ARG;
     DevGuard g(h->device);
     DevBuf ds, de, dr;
-    RQCHK(ds.alloc(8 * N));
-    RQCHK(de.alloc(8 * N));
-    if (N) RQCHK(hipMemcpy(ds.p, start, 8 * N, hipMemcpyHostToDevice));
-    if (N) RQCHK(hipMemcpy(de.p, end, 8 * N, hipMemcpyHostToDevice));
-    if (revcomp && N) { RQCHK(dr.alloc(N)); RQCHK(hipMemcpy(dr.p, revcomp, N, hipMemcpyHostToDevice)); }
+    AIXCHK(ds.alloc(8 * N));
+    AIXCHK(de.alloc(8 * N));
+    if (N) AIXCHK(hipMemcpy(ds.p, start, 8 * N, hipMemcpyHostToDevice));
+    if (N) AIXCHK(hipMemcpy(de.p, end, 8 * N, hipMemcpyHostToDevice));
+    if (revcomp && N) { AIXCHK(dr.alloc(N)); AIXCHK(hipMemcpy(dr.p, revcomp, N, hipMemcpyHostToDevice)); }
     return rq_host_fetch(N, offsets_out, bytes_out, [&](uint64_t* off, char* by, uint64_t cap, uint64_t* tot) {
         return aix_reads_fetch_dev(h, (const uint64_t*)ds.p, (const uint64_t*)de.p, (const uint8_t*)dr.p, N, off, by, cap, tot, nullptr);
     });
@@ -602,8 +572,8 @@ extern "C" int aix_reads_fetch_rid(aix_index_t* h, const uint64_t* rid, uint64_t
     if (!h->rd_attached || !h->rx_attached) return AIX_ERR_ARG;
     DevGuard g(h->device);
     DevBuf dr;
-    RQCHK(dr.alloc(8 * N));
-    if (N) RQCHK(hipMemcpy(dr.p, rid, 8 * N, hipMemcpyHostToDevice));
+    AIXCHK(dr.alloc(8 * N));
+    if (N) AIXCHK(hipMemcpy(dr.p, rid, 8 * N, hipMemcpyHostToDevice));
     return rq_host_fetch(N, offsets_out, bytes_out, [&](uint64_t* off, char* by, uint64_t cap, uint64_t* tot) {
         return aix_reads_fetch_rid_dev(h, (const uint64_t*)dr.p, N, off, by, cap, tot, nullptr);
     });
@@ -619,18 +589,18 @@ extern "C" int aix_reads_by_kmers(aix_index_t* h, const char* kmers, uint64_t N,
     const uint64_t qb = N * h->k;
     DevBuf dq, dko, dby;
     DevArr rid, src, len, roff;
-    RQCHK(dq.alloc(qb + 16));
-    RQCHK(dko.alloc(8 * (N + 1)));
-    if (qb) RQCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
+    AIXCHK(dq.alloc(qb + 16));
+    AIXCHK(dko.alloc(8 * (N + 1)));
+    if (qb) AIXCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
     uint64_t R = 0, total = 0, again = 0;
-    RQCHK(rk_run(h, (const uint8_t*)dq.p, N, max_reads, (uint64_t*)dko.p, rid, src, len, &R, nullptr));
-    RQCHK(roff.alloc(8 * (R + 1)));
+    AIXCHK(rk_run(h, (const uint8_t*)dq.p, N, max_reads, (uint64_t*)dko.p, rid, src, len, &R, nullptr));
+    AIXCHK(roff.alloc(8 * (R + 1)));
     if (R) {
-        RQCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, nullptr, 0, &total, nullptr));
-        RQCHK(dby.alloc(total));
-        RQCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, (uint8_t*)dby.p, total, &again, nullptr));
+        AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, nullptr, 0, &total, nullptr));
+        AIXCHK(dby.alloc(total));
+        AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, R, (uint64_t*)roff.p, (uint8_t*)dby.p, total, &again, nullptr));
     } else {
-        RQCHK(hipMemset(roff.p, 0, 8));
+        AIXCHK(hipMemset(roff.p, 0, 8));
     }
     void *hk = nullptr, *hr = nullptr, *ho = nullptr, *hb = nullptr;
     int st = rq_to_host(dko.p, 8 * (N + 1), &hk);

@@ -283,9 +283,9 @@ static hipError_t se_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     P.ed = ed;
     P.keep = (uint8_t*)keep.p; P.key = (uint64_t*)F.key.p; P.hseq = (uint64_t*)hseq.p; P.end = (uint64_t*)F.end.p; P.rid = (uint64_t*)F.rid.p;
     P.local = (uint64_t*)F.local.p;
-    hipLaunchKernelGGL(k_se_verify, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
+    hipLaunchKernelGGL(k_se_verify, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)keep.p, SvWiden8()), (uint64_t*)srank.p, T + 1, ts, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)srank.p, T + 1, ts, s);
     uint64_t S = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&S, (const uint64_t*)srank.p + T, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -302,24 +302,24 @@ static hipError_t se_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     if (e == hipSuccess) e = sh_alloc(F.head, S + 1, 1);
     if (e == hipSuccess) e = sh_alloc(F.orank, S + 1, 8);
     if (e != hipSuccess) return e;
-    const dim3 blk(kSB), gS(sh_grid(S));
-    hipLaunchKernelGGL(k_se_compact, dim3(sh_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
+    const dim3 blk(kSB), gS(flat_grid(S));
+    hipLaunchKernelGGL(k_se_compact, dim3(flat_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
                        (uint64_t*)csrc.p);
     e = hipGetLastError();
     // least significant key first: (start, strand, dist, end), then the sequence; start < reads_len, so the key needs the bits of reads_len << 9
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sv_bits((h->rd_len << (kSeLowBits + 1)) | 0x1FFull), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sv_bits((h->rd_len << (kSeLowBits + 1)) | 0x1FFull), tmp, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gS, blk, 0, s, (const uint64_t*)hseq.p, (const uint64_t*)pa.p, S, SvSame(), (uint64_t*)kin.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sv_bits(M), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sv_bits(M), tmp, s);
     if (e != hipSuccess) return e;
     const uint64_t* sseq = (const uint64_t*)kout.p;
-    hipLaunchKernelGGL(k_se_heads, dim3(sh_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
+    hipLaunchKernelGGL(k_se_heads, dim3(flat_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)F.head.p, SvWiden8()), (uint64_t*)F.orank.p, S + 1, ts2, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)F.head.p, Widen<uint8_t>()), (uint64_t*)F.orank.p, S + 1, ts2, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&F.R, (const uint64_t*)F.orank.p + S, 8, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_se_seqoff, dim3(sh_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
+    hipLaunchKernelGGL(k_se_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
@@ -328,7 +328,7 @@ static hipError_t se_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
 // the F.R records into buffers that hold them. Synchronises `s`.
 static hipError_t se_write(const SeState& F, const SeOut& O, hipStream_t s) {
     if (F.R == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_se_write, dim3(sh_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
+    hipLaunchKernelGGL(k_se_write, dim3(flat_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
                        (const uint64_t*)F.key.p, (const uint64_t*)F.end.p, (const uint64_t*)F.rid.p, (const uint64_t*)F.local.p, O);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -352,13 +352,13 @@ extern "C" int aix_seq_edit_dev(aix_index_t* h, const char* d_seqs, const uint64
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { SHCHK(hipMemsetAsync(d_find_offsets, 0, 8, s)); SHCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(hipMemsetAsync(d_find_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
     SeState F(s);
     bool bad = false;
-    SHCHK(se_run(h, (const uint8_t*)d_seqs, d_offs, M, ed, seed_step ? seed_step : 23, max_per_kmer, d_find_offsets, F, &bad, s));
+    AIXCHK(se_run(h, (const uint8_t*)d_seqs, d_offs, M, ed, seed_step ? seed_step : 23, max_per_kmer, d_find_offsets, F, &bad, s));
     if (bad) return AIX_ERR_ARG;
     *total_out = F.R;
-    if (F.R && F.R <= cap) SHCHK(se_write(F, SeOut{d_start, d_end, d_rid, d_local, d_strand, d_dist}, s));
+    if (F.R && F.R <= cap) AIXCHK(se_write(F, SeOut{d_start, d_end, d_rid, d_local, d_strand, d_dist}, s));
     return AIX_OK;
 }
 
@@ -377,16 +377,16 @@ extern "C" int aix_seq_edit(aix_index_t* h, const char* seqs, const uint64_t* of
     DevGuard g(h->device);
     DevBuf ds, dof, dfo, dp, de, dr, dl, dst, dd;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
-    SHCHK(dfo.alloc(8 * (M + 1)));
-    SHCHK(hipMemset(dfo.p, 0, 8 * (M + 1)));
+    AIXCHK(dfo.alloc(8 * (M + 1)));
+    AIXCHK(hipMemset(dfo.p, 0, 8 * (M + 1)));
     SeState F(nullptr);
     bool bad = false;
-    if (M) SHCHK(se_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, ed, seed_step ? seed_step : 23, max_per_kmer, (uint64_t*)dfo.p, F, &bad, nullptr));
+    if (M) AIXCHK(se_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, ed, seed_step ? seed_step : 23, max_per_kmer, (uint64_t*)dfo.p, F, &bad, nullptr));
     if (bad) return AIX_ERR_ARG;
     const uint64_t R = F.R;                                    // <= the survivors, whose blocks were allocated: 8 R cannot overflow
     if (R) {
-        SHCHK(dp.alloc(8 * R)); SHCHK(de.alloc(8 * R)); SHCHK(dr.alloc(8 * R)); SHCHK(dl.alloc(8 * R)); SHCHK(dst.alloc(R)); SHCHK(dd.alloc(4 * R));
-        SHCHK(se_write(F, SeOut{(uint64_t*)dp.p, (uint64_t*)de.p, (uint64_t*)dr.p, (uint64_t*)dl.p, (uint8_t*)dst.p, (uint32_t*)dd.p}, nullptr));
+        AIXCHK(dp.alloc(8 * R)); AIXCHK(de.alloc(8 * R)); AIXCHK(dr.alloc(8 * R)); AIXCHK(dl.alloc(8 * R)); AIXCHK(dst.alloc(R)); AIXCHK(dd.alloc(4 * R));
+        AIXCHK(se_write(F, SeOut{(uint64_t*)dp.p, (uint64_t*)de.p, (uint64_t*)dr.p, (uint64_t*)dl.p, (uint8_t*)dst.p, (uint32_t*)dd.p}, nullptr));
     }
     void *ho = nullptr, *hp = nullptr, *he = nullptr, *hr = nullptr, *hl = nullptr, *hs = nullptr, *hdd = nullptr;
     int st = sh_to_host(dfo.p, 8 * (M + 1), &ho);

@@ -239,9 +239,9 @@ static hipError_t sf_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     P.hd = hd;
     P.keep = (uint8_t*)keep.p; P.key = (uint64_t*)F.key.p; P.hseq = (uint64_t*)hseq.p; P.rid = (uint64_t*)F.rid.p; P.local = (uint64_t*)F.local.p;
     P.dist = (uint32_t*)F.dist.p;
-    hipLaunchKernelGGL(k_sf_verify, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
+    hipLaunchKernelGGL(k_sf_verify, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)keep.p, SvWiden8()), (uint64_t*)srank.p, T + 1, ts, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)srank.p, T + 1, ts, s);
     uint64_t S = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&S, (const uint64_t*)srank.p + T, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -258,24 +258,24 @@ static hipError_t sf_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     if (e == hipSuccess) e = sh_alloc(F.head, S + 1, 1);
     if (e == hipSuccess) e = sh_alloc(F.orank, S + 1, 8);
     if (e != hipSuccess) return e;
-    const dim3 blk(kSB), gS(sh_grid(S));
-    hipLaunchKernelGGL(k_sf_compact, dim3(sh_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
+    const dim3 blk(kSB), gS(flat_grid(S));
+    hipLaunchKernelGGL(k_sf_compact, dim3(flat_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
                        (uint64_t*)csrc.p);
     e = hipGetLastError();
     // least significant key first: (a, strand), then the sequence; a <= reads_len, so the key needs the bits of 2 reads_len + 1
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sv_bits((h->rd_len << 1) | 1ull), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sv_bits((h->rd_len << 1) | 1ull), tmp, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gS, blk, 0, s, (const uint64_t*)hseq.p, (const uint64_t*)pa.p, S, SvSame(), (uint64_t*)kin.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sv_bits(M), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sv_bits(M), tmp, s);
     if (e != hipSuccess) return e;
     const uint64_t* sseq = (const uint64_t*)kout.p;
-    hipLaunchKernelGGL(k_sf_heads, dim3(sh_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
+    hipLaunchKernelGGL(k_sf_heads, dim3(flat_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)F.head.p, SvWiden8()), (uint64_t*)F.orank.p, S + 1, ts2, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)F.head.p, Widen<uint8_t>()), (uint64_t*)F.orank.p, S + 1, ts2, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&F.R, (const uint64_t*)F.orank.p + S, 8, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sf_seqoff, dim3(sh_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
+    hipLaunchKernelGGL(k_sf_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
@@ -284,7 +284,7 @@ static hipError_t sf_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
 // the F.R records into buffers that hold them. Synchronises `s`.
 static hipError_t sf_write(const SfState& F, const SfOut& O, hipStream_t s) {
     if (F.R == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sf_write, dim3(sh_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
+    hipLaunchKernelGGL(k_sf_write, dim3(flat_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
                        (const uint64_t*)F.key.p, (const uint64_t*)F.rid.p, (const uint64_t*)F.local.p, (const uint32_t*)F.dist.p, O);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -330,7 +330,7 @@ static hipError_t ks_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     hipError_t e = sh_alloc(offs, N + 1, 8);
     if (e == hipSuccess) e = sh_alloc(soff, N + 1, 8);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ks_offs, dim3(sh_grid(N + 1)), dim3(kSB), 0, s, N, (uint64_t*)offs.p);
+    hipLaunchKernelGGL(k_ks_offs, dim3(flat_grid(N + 1)), dim3(kSB), 0, s, N, (uint64_t*)offs.p);
     e = hipGetLastError();
     bool bad = false;
     if (e == hipSuccess) e = sh_run(h, d_kmers, (const uint64_t*)offs.p, N, m, (uint64_t*)soff.p, nullptr, false, B, &bad, s, 1, false);
@@ -341,11 +341,11 @@ static hipError_t ks_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
         B.pos.drop(); B.qoff.drop();
         e = sh_alloc(sp, T, 8);
         if (e == hipSuccess) e = sh_alloc(sm, T, 8);
-        if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{0}), (uint64_t*)sp.p, T, t0, s);
-        if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{1}), (uint64_t*)sm.p, T, t1, s);
+        if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{0}), (uint64_t*)sp.p, T, t0, s);
+        if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{1}), (uint64_t*)sm.p, T, t1, s);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_ks_counts, dim3(sh_grid(N)), dim3(kSB), 0, s, (const uint64_t*)soff.p, (const uint64_t*)sp.p, (const uint64_t*)sm.p,
+    hipLaunchKernelGGL(k_ks_counts, dim3(flat_grid(N)), dim3(kSB), 0, s, (const uint64_t*)soff.p, (const uint64_t*)sp.p, (const uint64_t*)sm.p,
                        (const uint8_t*)B.flag.p, T, N, d_plus, d_minus, d_total);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -369,13 +369,13 @@ extern "C" int aix_seq_find_dev(aix_index_t* h, const char* d_seqs, const uint64
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { SHCHK(hipMemsetAsync(d_find_offsets, 0, 8, s)); SHCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(hipMemsetAsync(d_find_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
     SfState F(s);
     bool bad = false;
-    SHCHK(sf_run(h, (const uint8_t*)d_seqs, d_offs, M, hd, seed_step ? seed_step : 23, max_per_kmer, d_find_offsets, F, &bad, s));
+    AIXCHK(sf_run(h, (const uint8_t*)d_seqs, d_offs, M, hd, seed_step ? seed_step : 23, max_per_kmer, d_find_offsets, F, &bad, s));
     if (bad) return AIX_ERR_ARG;
     *total_out = F.R;
-    if (F.R && F.R <= cap) SHCHK(sf_write(F, SfOut{d_pos, d_rid, d_local, d_strand, d_dist}, s));
+    if (F.R && F.R <= cap) AIXCHK(sf_write(F, SfOut{d_pos, d_rid, d_local, d_strand, d_dist}, s));
     return AIX_OK;
 }
 
@@ -389,16 +389,16 @@ extern "C" int aix_seq_find(aix_index_t* h, const char* seqs, const uint64_t* of
     DevGuard g(h->device);
     DevBuf ds, dof, dfo, dp, dr, dl, dst, dd;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
-    SHCHK(dfo.alloc(8 * (M + 1)));
-    SHCHK(hipMemset(dfo.p, 0, 8 * (M + 1)));
+    AIXCHK(dfo.alloc(8 * (M + 1)));
+    AIXCHK(hipMemset(dfo.p, 0, 8 * (M + 1)));
     SfState F(nullptr);
     bool bad = false;
-    if (M) SHCHK(sf_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, hd, seed_step ? seed_step : 23, max_per_kmer, (uint64_t*)dfo.p, F, &bad, nullptr));
+    if (M) AIXCHK(sf_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, hd, seed_step ? seed_step : 23, max_per_kmer, (uint64_t*)dfo.p, F, &bad, nullptr));
     if (bad) return AIX_ERR_ARG;
     const uint64_t R = F.R;                                    // <= the survivors, whose blocks were allocated: 8 R cannot overflow
     if (R) {
-        SHCHK(dp.alloc(8 * R)); SHCHK(dr.alloc(8 * R)); SHCHK(dl.alloc(8 * R)); SHCHK(dst.alloc(R)); SHCHK(dd.alloc(4 * R));
-        SHCHK(sf_write(F, SfOut{(uint64_t*)dp.p, (uint64_t*)dr.p, (uint64_t*)dl.p, (uint8_t*)dst.p, (uint32_t*)dd.p}, nullptr));
+        AIXCHK(dp.alloc(8 * R)); AIXCHK(dr.alloc(8 * R)); AIXCHK(dl.alloc(8 * R)); AIXCHK(dst.alloc(R)); AIXCHK(dd.alloc(4 * R));
+        AIXCHK(sf_write(F, SfOut{(uint64_t*)dp.p, (uint64_t*)dr.p, (uint64_t*)dl.p, (uint8_t*)dst.p, (uint32_t*)dd.p}, nullptr));
     }
     void *ho = nullptr, *hp = nullptr, *hr = nullptr, *hl = nullptr, *hs = nullptr, *hdd = nullptr;
     int st = sh_to_host(dfo.p, 8 * (M + 1), &ho);
@@ -419,7 +419,7 @@ extern "C" int aix_kmer_strands_dev(aix_index_t* h, const char* d_kmers, uint64_
     if (const int st = sh_check(h)) return st;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    SHCHK(ks_run(h, (const uint8_t*)d_kmers, N, max_per_kmer, d_plus, d_minus, d_total, (hipStream_t)stream));
+    AIXCHK(ks_run(h, (const uint8_t*)d_kmers, N, max_per_kmer, d_plus, d_minus, d_total, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -429,13 +429,13 @@ extern "C" int aix_kmer_strands(aix_index_t* h, const char* kmers, uint64_t N, u
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
     DevBuf dq, dc;
-    SHCHK(dq.alloc(23 * N + 16));                              // padded for load23
-    SHCHK(dc.alloc(24 * N));
-    SHCHK(hipMemcpy(dq.p, kmers, 23 * N, hipMemcpyHostToDevice));
+    AIXCHK(dq.alloc(23 * N + 16));                              // padded for load23
+    AIXCHK(dc.alloc(24 * N));
+    AIXCHK(hipMemcpy(dq.p, kmers, 23 * N, hipMemcpyHostToDevice));
     uint64_t* c = (uint64_t*)dc.p;
-    SHCHK(ks_run(h, (const uint8_t*)dq.p, N, max_per_kmer, c, c + N, c + 2 * N, nullptr));
-    SHCHK(hipMemcpy(plus_out, c, 8 * N, hipMemcpyDeviceToHost));
-    SHCHK(hipMemcpy(minus_out, c + N, 8 * N, hipMemcpyDeviceToHost));
-    SHCHK(hipMemcpy(total_out, c + 2 * N, 8 * N, hipMemcpyDeviceToHost));
+    AIXCHK(ks_run(h, (const uint8_t*)dq.p, N, max_per_kmer, c, c + N, c + 2 * N, nullptr));
+    AIXCHK(hipMemcpy(plus_out, c, 8 * N, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(minus_out, c + N, 8 * N, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(total_out, c + 2 * N, 8 * N, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

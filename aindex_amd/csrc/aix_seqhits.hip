@@ -176,9 +176,9 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
     if (e == hipSuccess) e = fl.alloc(4);
     if (e == hipSuccess) e = hipMemsetAsync(fl.p, 0, 4, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sh_windows, dim3(sh_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, step, (uint64_t*)nwin.p, (uint32_t*)fl.p);
+    hipLaunchKernelGGL(k_sh_windows, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, step, (uint64_t*)nwin.p, (uint32_t*)fl.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan((const uint64_t*)nwin.p, (uint64_t*)B.woff.p, M + 1, tmp, s);
+    if (e == hipSuccess) e = scan_u64((const uint64_t*)nwin.p, (uint64_t*)B.woff.p, M + 1, tmp, s);
     uint64_t W = 0;
     uint32_t flag = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&W, (const uint64_t*)B.woff.p + M, 8, hipMemcpyDeviceToHost, s);
@@ -202,7 +202,7 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
     const IndexDev ix = h->dev();
     const uint64_t* woff = (const uint64_t*)B.woff.p;
 #define AIX_SH_RESOLVE(L)                                                                                                                                  \
-    hipLaunchKernelGGL(k_sh_resolve<L>, dim3(sh_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
+    hipLaunchKernelGGL(k_sh_resolve<L>, dim3(flat_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
                        (uint64_t*)wsrc.p, (uint64_t*)lo.p, (uint64_t*)ub.p)
     if (ix.bk_lpp == 2) AIX_SH_RESOLVE(2);
     else if (ix.bk_lpp == 4) AIX_SH_RESOLVE(4);
@@ -216,7 +216,7 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
     if (e != hipSuccess) return e;
     B.T = T;
     if (d_seq_offsets) {
-        hipLaunchKernelGGL(k_sh_seqoff, dim3(sh_grid(M + 1)), dim3(kSB), 0, s, woff, (const uint64_t*)B.koff.p, M, d_seq_offsets);
+        hipLaunchKernelGGL(k_sh_seqoff, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, woff, (const uint64_t*)B.koff.p, M, d_seq_offsets);
         e = hipGetLastError();
     }
     if (e == hipSuccess && T && (!user || (T <= user->cap && user->pos))) {
@@ -238,8 +238,8 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
             P.pos = (const uint64_t*)B.pos.p; P.qoff = (uint32_t*)B.qoff.p; P.rid = (uint64_t*)B.rid.p; P.local = (int64_t*)B.local.p; P.flag = (uint8_t*)B.flag.p;
             P.hseq = (uint64_t*)B.hseq.p; P.diag = (int64_t*)B.diag.p;
         }
-        if (locate) hipLaunchKernelGGL(k_sh_hits<true>, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
-        else hipLaunchKernelGGL(k_sh_hits<false>, dim3(sh_grid(T)), dim3(kSB), 0, s, P);
+        if (locate) hipLaunchKernelGGL(k_sh_hits<true>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
+        else hipLaunchKernelGGL(k_sh_hits<false>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);          // the scratch blocks go back to the pool idle
@@ -369,10 +369,7 @@ static hipError_t sv_run(const ShBufs& B, uint64_t M, uint64_t min_votes, uint64
     SvRange r = none;
     {
         auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), SvRangeOf{hseq, diag, rid, M});
-        size_t tb = 0;
-        e = rocprim::reduce(nullptr, tb, in, (SvRange*)rng.p, none, (size_t)T, SvRangeJoin(), s);
-        if (e == hipSuccess) e = rt.alloc(tb ? tb : 1);
-        if (e == hipSuccess) e = rocprim::reduce(rt.p, tb, in, (SvRange*)rng.p, none, (size_t)T, SvRangeJoin(), s);
+        e = with_temp(rt, [&](void* t, size_t& tb) { return rocprim::reduce(t, tb, in, (SvRange*)rng.p, none, (size_t)T, SvRangeJoin(), s); });
         if (e == hipSuccess) e = hipMemcpyAsync(&r, rng.p, sizeof(SvRange), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
@@ -383,32 +380,32 @@ static hipError_t sv_run(const ShBufs& B, uint64_t M, uint64_t min_votes, uint64
         return e;
     }
     uint64_t *d_pa = (uint64_t*)pa.p, *d_pb = (uint64_t*)pb.p, *d_kin = (uint64_t*)kin.p, *d_kout = (uint64_t*)kout.p;
-    const dim3 gT(sh_grid(T)), blk(kSB);
+    const dim3 gT(flat_grid(T)), blk(kSB);
     // least significant key first: diagonal, strand, read id, sequence
-    e = sv_sort(rocprim::make_transform_iterator(diag, SvDiagKey{r.dlo}), d_kout, rocprim::counting_iterator<uint64_t>(0), d_pa, T,
+    e = sort_pairs(rocprim::make_transform_iterator(diag, SvDiagKey{r.dlo}), d_kout, rocprim::counting_iterator<uint64_t>(0), d_pa, T,
                 sv_bits((uint64_t)r.dhi - (uint64_t)r.dlo), tmp, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_sv_gather<uint8_t, SvStrandOf>), gT, blk, 0, s, flag, (const uint64_t*)d_pa, T, SvStrandOf(), (uint8_t*)k8in.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sv_sort((const uint8_t*)k8in.p, (uint8_t*)k8out.p, (const uint64_t*)d_pa, d_pb, T, 2u, tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint8_t*)k8in.p, (uint8_t*)k8out.p, (const uint64_t*)d_pa, d_pb, T, 2u, tmp, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, rid, (const uint64_t*)d_pb, T, SvSame(), d_kin);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pb, d_pa, T, sv_bits(r.rmax), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pb, d_pa, T, sv_bits(r.rmax), tmp, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, hseq, (const uint64_t*)d_pa, T, SvSame(), d_kin);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sv_sort((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pa, d_pb, T, sv_bits(M), tmp, s);
+    if (e == hipSuccess) e = sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pa, d_pb, T, sv_bits(M), tmp, s);
     if (e != hipSuccess) return e;
     const uint64_t *perm = d_pb, *sseq = d_kout;               // the hits by (sequence, read, strand, diagonal, hit number); dropped hits last
     pa.drop(); kin.drop(); k8in.drop(); k8out.drop(); tmp.drop();          // (waits for the sorts) their blocks serve the passes below
     e = sh_alloc(head, T + 1, 1);
     if (e == hipSuccess) e = sh_alloc(gid, T + 1, 8);
     if (e != hipSuccess) return e;
-    const dim3 gT1(sh_grid(T + 1));
+    const dim3 gT1(flat_grid(T + 1));
     hipLaunchKernelGGL(k_sv_heads, gT1, blk, 0, s, perm, sseq, rid, flag, diag, T, M, (uint8_t*)head.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)head.p, SvWiden8()), (uint64_t*)gid.p, T + 1, ts, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)head.p, Widen<uint8_t>()), (uint64_t*)gid.p, T + 1, ts, s);
     uint64_t G = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&G, (const uint64_t*)gid.p + T, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -417,19 +414,19 @@ static hipError_t sv_run(const ShBufs& B, uint64_t M, uint64_t min_votes, uint64
     if (e == hipSuccess) e = sh_alloc(orank, G + 1, 8);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_sv_starts, gT1, blk, 0, s, (const uint8_t*)head.p, (const uint64_t*)gid.p, sseq, T, M, G, (uint64_t*)gstart.p);
-    hipLaunchKernelGGL(k_sv_emit, dim3(sh_grid(G + 1)), blk, 0, s, (const uint64_t*)gstart.p, G, min_votes, (uint8_t*)emit.p);
+    hipLaunchKernelGGL(k_sv_emit, dim3(flat_grid(G + 1)), blk, 0, s, (const uint64_t*)gstart.p, G, min_votes, (uint8_t*)emit.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = sh_scan(rocprim::make_transform_iterator((const uint8_t*)emit.p, SvWiden8()), (uint64_t*)orank.p, G + 1, ts2, s);
+    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)emit.p, Widen<uint8_t>()), (uint64_t*)orank.p, G + 1, ts2, s);
     uint64_t R = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&R, (const uint64_t*)orank.p + G, 8, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sv_seqoff, dim3(sh_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)gid.p, (const uint64_t*)orank.p, T, M, d_vote_offsets);
+    hipLaunchKernelGGL(k_sv_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)gid.p, (const uint64_t*)orank.p, T, M, d_vote_offsets);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
     *total_out = R;
     if (R == 0 || R > cap || !O.rid) return hipSuccess;
-    hipLaunchKernelGGL(k_sv_write, dim3(sh_grid(G)), blk, 0, s, (const uint64_t*)gstart.p, (const uint8_t*)emit.p, (const uint64_t*)orank.p, G, perm, rid, flag, diag,
+    hipLaunchKernelGGL(k_sv_write, dim3(flat_grid(G)), blk, 0, s, (const uint64_t*)gstart.p, (const uint8_t*)emit.p, (const uint64_t*)orank.p, G, perm, rid, flag, diag,
                        (const uint32_t*)B.qoff.p, O);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -449,11 +446,11 @@ extern "C" int aix_seq_hits_dev(aix_index_t* h, const char* d_seqs, const uint64
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { SHCHK(hipMemsetAsync(d_seq_offsets, 0, 8, s)); SHCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(hipMemsetAsync(d_seq_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
     const ShUser u{d_qoff, cap ? d_pos : nullptr, d_rid, d_local, d_flag, cap};
     ShBufs B(s);
     bool bad = false;
-    SHCHK(sh_run(h, (const uint8_t*)d_seqs, d_offs, M, max_per_kmer, d_seq_offsets, &u, false, B, &bad, s));
+    AIXCHK(sh_run(h, (const uint8_t*)d_seqs, d_offs, M, max_per_kmer, d_seq_offsets, &u, false, B, &bad, s));
     if (bad) return AIX_ERR_ARG;
     *total_out = B.T;
     return AIX_OK;
@@ -468,14 +465,14 @@ extern "C" int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint6
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { SHCHK(hipMemsetAsync(d_vote_offsets, 0, 8, s)); SHCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(hipMemsetAsync(d_vote_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
     ShBufs B(s);
     bool bad = false;
-    SHCHK(sh_run(h, (const uint8_t*)d_seqs, d_offs, M, max_per_kmer, nullptr, nullptr, true, B, &bad, s));
+    AIXCHK(sh_run(h, (const uint8_t*)d_seqs, d_offs, M, max_per_kmer, nullptr, nullptr, true, B, &bad, s));
     if (bad) return AIX_ERR_ARG;
     B.pos.drop(); B.local.drop();                              // the diagonal holds what the grouping needs of them: the sorts take these blocks
     const SvOut O{cap ? d_rid : nullptr, d_strand, d_diag, d_votes, d_qfirst, d_qlast};
-    SHCHK(sv_run(B, M, min_votes, d_vote_offsets, O, cap, total_out, s));
+    AIXCHK(sv_run(B, M, min_votes, d_vote_offsets, O, cap, total_out, s));
     return AIX_OK;
 }
 
@@ -488,11 +485,11 @@ extern "C" int aix_seq_hits(aix_index_t* h, const char* seqs, const uint64_t* of
     DevGuard g(h->device);
     DevBuf ds, dof, dso;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
-    SHCHK(dso.alloc(8 * (M + 1)));
-    SHCHK(hipMemset(dso.p, 0, 8 * (M + 1)));
+    AIXCHK(dso.alloc(8 * (M + 1)));
+    AIXCHK(hipMemset(dso.p, 0, 8 * (M + 1)));
     ShBufs B(nullptr);
     bool bad = false;
-    if (M) SHCHK(sh_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, max_per_kmer, (uint64_t*)dso.p, nullptr, false, B, &bad, nullptr));
+    if (M) AIXCHK(sh_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, max_per_kmer, (uint64_t*)dso.p, nullptr, false, B, &bad, nullptr));
     if (bad) return AIX_ERR_ARG;
     const uint64_t T = B.T;
     void *ho = nullptr, *hq = nullptr, *hp = nullptr, *hr = nullptr, *hl = nullptr, *hf = nullptr;
@@ -517,21 +514,21 @@ extern "C" int aix_seq_votes(aix_index_t* h, const char* seqs, const uint64_t* o
     DevGuard g(h->device);
     DevBuf ds, dof, dvo, dr, dst, dd, dv, dqf, dql;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
-    SHCHK(dvo.alloc(8 * (M + 1)));
-    SHCHK(hipMemset(dvo.p, 0, 8 * (M + 1)));
+    AIXCHK(dvo.alloc(8 * (M + 1)));
+    AIXCHK(hipMemset(dvo.p, 0, 8 * (M + 1)));
     uint64_t R = 0;
     if (M) {
         ShBufs B(nullptr);
         bool bad = false;
-        SHCHK(sh_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, max_per_kmer, nullptr, nullptr, true, B, &bad, nullptr));
+        AIXCHK(sh_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, max_per_kmer, nullptr, nullptr, true, B, &bad, nullptr));
         if (bad) return AIX_ERR_ARG;
         B.pos.drop(); B.local.drop();
         // a record needs at least one hit: B.T bounds the records, so one grouping pass fills buffers of that size
         uint64_t cap = B.T;
         if (min_votes > 1) cap = B.T / min_votes;
-        SHCHK(dr.alloc(8 * cap)); SHCHK(dst.alloc(cap)); SHCHK(dd.alloc(8 * cap)); SHCHK(dv.alloc(4 * cap)); SHCHK(dqf.alloc(4 * cap)); SHCHK(dql.alloc(4 * cap));
+        AIXCHK(dr.alloc(8 * cap)); AIXCHK(dst.alloc(cap)); AIXCHK(dd.alloc(8 * cap)); AIXCHK(dv.alloc(4 * cap)); AIXCHK(dqf.alloc(4 * cap)); AIXCHK(dql.alloc(4 * cap));
         const SvOut O{(uint64_t*)dr.p, (uint8_t*)dst.p, (int64_t*)dd.p, (uint32_t*)dv.p, (uint32_t*)dqf.p, (uint32_t*)dql.p};
-        SHCHK(sv_run(B, M, min_votes, (uint64_t*)dvo.p, O, cap, &R, nullptr));
+        AIXCHK(sv_run(B, M, min_votes, (uint64_t*)dvo.p, O, cap, &R, nullptr));
     }
     void *ho = nullptr, *hr = nullptr, *hs = nullptr, *hd = nullptr, *hv = nullptr, *hf = nullptr, *hl = nullptr;
     int st = sh_to_host(dvo.p, 8 * (M + 1), &ho);

@@ -1,12 +1,11 @@
 // aix_seqhits.hpp — what more than one translation unit uses of the chain sequences -> windows -> seed hits (aix_seqhits.hip: hits and
-// diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts; aix_seqedit.hip: edit-distance alignments): the hit buffers, steps 1 to 4 with a window stride, the
-// stable rocPRIM passes over a permutation, and the host ends of the C ABI.
+// diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts; aix_seqedit.hip: edit-distance alignments): the hit
+// buffers, steps 1 to 4 with a window stride, the gather of a permutation, the device helpers of the verification kernels and the host
+// ends of the C ABI. (Scans, the stable sort passes and the error mapping are those of aix_hostkit.hpp.)
 #pragma once
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "aix_posquery.hpp"
 
@@ -19,23 +18,7 @@
 
 namespace aix {
 
-static constexpr int kSB = 256;
-static inline unsigned sh_grid(uint64_t work) {
-    uint64_t b = (work + kSB - 1) / kSB;
-    if (b > 8192) b = std::max<uint64_t>(8192, std::min<uint64_t>(b / 4, 65536));
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
-
-// out[i] = in[0] + .. + in[i - 1] over n entries, u64 sums; `tmp` stays allocated until the caller has synchronised the stream
-template <class It>
-static hipError_t sh_scan(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-    return e;
-}
+static constexpr int kSB = kFlatBlock;                            // the grid of the flat kernels: flat_grid (aix_hostkit.hpp)
 
 // n entries of `elem` bytes from the pool; hipErrorOutOfMemory when the byte count does not fit 64 bits
 static hipError_t sh_alloc(DevArr& a, uint64_t n, uint64_t elem) {
@@ -66,8 +49,6 @@ struct ShUser {                    // aix_seq_hits_dev: where the entries go whe
 hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, uint64_t M, uint64_t m, uint64_t* d_seq_offsets, const ShUser* user, bool votes, ShBufs& B,
                   bool* bad, hipStream_t s, uint64_t step = 1, bool locate = true);
 
-struct SvWiden8 { __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)v; } };
-
 template <class T, class Map>
 __global__ void __launch_bounds__(kSB) k_sv_gather(const T* __restrict__ in, const uint64_t* __restrict__ perm, uint64_t n, Map map, T* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * kSB;
@@ -77,16 +58,9 @@ struct SvSame { template <class T> __host__ __device__ T operator()(T v) const {
 
 static unsigned sv_bits(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) ++b; return b; }
 
-// one stable pass of the permutation: keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary storage is as large as
-// the keys and values together: the four passes share ONE block (tmp.alloc waits for the pass before it, then takes the block back from the pool)
-template <class KeyIt, class Key, class ValIt>
-static hipError_t sv_sort(KeyIt keys, Key* keys_out, ValIt perm_in, uint64_t* perm_out, uint64_t T, unsigned bits, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, keys, keys_out, perm_in, perm_out, (size_t)T, 0u, bits, s);
-    return e;
-}
+// A stable pass of a permutation is sort_pairs (aix_hostkit.hpp): keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary
+// storage is as large as the keys and values together: the passes of a chain share ONE block (tmp.alloc waits for the pass before it, then
+// takes the block back from the pool)
 
 // ---- device helpers of the verification kernels (aix_seqfind.hip: Hamming; aix_seqedit.hip: banded edit distance) ----
 // bytes [p, p + 4) of a buffer of `size` bytes, first byte least significant; a byte outside [0, size) reads as 0 and is never touched.
@@ -120,16 +94,6 @@ __device__ __forceinline__ uint64_t sf_shfl64(uint64_t v, uint32_t src) {
 
 }  // namespace aix
 
-#define SHCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 static int sh_check(const aix_index* h) {
     if (h->k != 23) return AIX_ERR_MODE;
     if (!h->ai_attached || !h->rx_attached || !h->rd_attached) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
@@ -143,7 +107,7 @@ static int sh_to_host(const void* d, uint64_t bytes, void** out) {
     if (!p) return AIX_ERR_NOMEM;
     if (bytes) {
         const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(p); SHCHK(e); }
+        if (e != hipSuccess) { free(p); AIXCHK(e); }
     }
     *out = p;
     return AIX_OK;
@@ -153,9 +117,9 @@ static int sh_to_host(const void* d, uint64_t bytes, void** out) {
 static int sh_upload(const char* seqs, const uint64_t* offs, uint64_t M, DevBuf& ds, DevBuf& dof) {
     const uint64_t bytes = M ? offs[M] : 0;
     if (bytes >= (1ull << 60)) return AIX_ERR_NOMEM;
-    SHCHK(ds.alloc(bytes + 16));
-    SHCHK(dof.alloc(8 * (M + 1)));
-    if (bytes) SHCHK(hipMemcpy(ds.p, seqs, bytes, hipMemcpyHostToDevice));
-    SHCHK(hipMemcpy(dof.p, offs, 8 * (M + 1), hipMemcpyHostToDevice));
+    AIXCHK(ds.alloc(bytes + 16));
+    AIXCHK(dof.alloc(8 * (M + 1)));
+    if (bytes) AIXCHK(hipMemcpy(ds.p, seqs, bytes, hipMemcpyHostToDevice));
+    AIXCHK(hipMemcpy(dof.p, offs, 8 * (M + 1), hipMemcpyHostToDevice));
     return AIX_OK;
 }

@@ -31,10 +31,8 @@
 #include <cstring>
 #include <string>
 
-#include <rocprim/rocprim.hpp>
-
 #include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 #include "aix_probe.hpp"
 
 namespace aix {
@@ -362,11 +360,7 @@ static hipError_t sp_spectrum(const T* d_vals, uint64_t n, uint64_t nbins, uint6
 }
 
 static hipError_t sp_scan(const uint32_t* in, uint32_t* out, uint64_t n, DevArr& tmp, hipStream_t s) {
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
-    return e;
+    return with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s); });
 }
 
 // Selection over d_vals[n], n < 2^32. *m_out / *total_out are always produced; the entries only when they fit `cap` (d_idx / d_val), or
@@ -415,10 +409,9 @@ static hipError_t sp_select(const uint32_t* d_vals, uint64_t n, uint32_t min_v, 
     hipLaunchKernelGGL(k_sp_emit, dim3(nblk), dim3(kSB), 0, s, d_vals, n, (const SelState*)d_st, nblk, (const uint32_t*)ogt, (const uint32_t*)oeq, m,
                        (unsigned long long*)keys.p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t tb = 0;
-    e = rocprim::radix_sort_keys(nullptr, tb, (const unsigned long long*)keys.p, (unsigned long long*)sorted.p, (size_t)m, 0u, 64u, s);
-    if (e == hipSuccess) e = t2.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::radix_sort_keys(t2.p, tb, (const unsigned long long*)keys.p, (unsigned long long*)sorted.p, (size_t)m, 0u, 64u, s);
+    e = with_temp(t2, [&](void* t, size_t& tb) {
+        return rocprim::radix_sort_keys(t, tb, (const unsigned long long*)keys.p, (unsigned long long*)sorted.p, (size_t)m, 0u, 64u, s);
+    });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_sp_unpack, dim3(sp_grid(m, 4 * kSB)), dim3(kSB), 0, s, (const unsigned long long*)sorted.p, m, d_idx, d_val);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -436,16 +429,6 @@ static hipError_t sp_decode(const aix_index* h, const uint64_t* kid64, const uin
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define SPCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 static constexpr uint64_t kMaxBins = 1ull << 32;                  // a u32 value has no bin beyond 2^32 - 1; more cannot be held by any caller we serve
 
 // ---- array level ----------------------------------------------------------------------------------
@@ -453,15 +436,15 @@ extern "C" int aix_values_narrow_dev(const uint64_t* d_in, uint64_t n, uint32_t*
     if (n && (!d_in || !d_out)) return AIX_ERR_ARG;
     if (n == 0) return AIX_OK;
     hipLaunchKernelGGL(k_sp_narrow, dim3(sp_grid(n, 4 * kSB)), dim3(kSB), 0, (hipStream_t)stream, d_in, n, d_out);
-    SPCHK(hipGetLastError());
+    AIXCHK(hipGetLastError());
     return AIX_OK;
 }
 
 extern "C" int aix_spectrum_dev(const void* d_values, int elem_bytes, uint64_t n, uint64_t nbins, uint64_t* d_hist, uint64_t* d_stats, void* stream) {
     if (nbins < 2 || !d_hist || !d_stats || (n && !d_values) || (elem_bytes != 4 && elem_bytes != 8)) return AIX_ERR_ARG;
     if (nbins > kMaxBins || n >= (1ull << 60)) return AIX_ERR_NOMEM;
-    if (elem_bytes == 8) SPCHK(sp_spectrum((const uint64_t*)d_values, n, nbins, d_hist, d_stats, (hipStream_t)stream));
-    else SPCHK(sp_spectrum((const uint32_t*)d_values, n, nbins, d_hist, d_stats, (hipStream_t)stream));
+    if (elem_bytes == 8) AIXCHK(sp_spectrum((const uint64_t*)d_values, n, nbins, d_hist, d_stats, (hipStream_t)stream));
+    else AIXCHK(sp_spectrum((const uint32_t*)d_values, n, nbins, d_hist, d_stats, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -469,7 +452,7 @@ extern "C" int aix_select_dev(const uint32_t* d_values, uint64_t n, uint32_t min
                               uint64_t* n_out, uint64_t* total_out, void* stream) {
     if (!n_out || !total_out || (n && !d_values)) return AIX_ERR_ARG;
     if (n >= (1ull << 32)) return AIX_ERR_ARG;                    // an index is 32 bits wide
-    SPCHK(sp_select(d_values, n, min_v, max_items, cap ? d_idx : nullptr, d_val, cap, nullptr, nullptr, n_out, total_out, (hipStream_t)stream));
+    AIXCHK(sp_select(d_values, n, min_v, max_items, cap ? d_idx : nullptr, d_val, cap, nullptr, nullptr, n_out, total_out, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -478,7 +461,7 @@ extern "C" int aix_kmer_values_dev(aix_index_t* h, uint32_t* d_out, void* stream
     if (!h || (h->n && !d_out)) return AIX_ERR_ARG;
     if (h->n >= (1ull << 32)) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
-    SPCHK(sp_values(h, d_out, (hipStream_t)stream));
+    AIXCHK(sp_values(h, d_out, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -489,13 +472,13 @@ extern "C" int aix_tf_spectrum_dev(aix_index_t* h, uint64_t nbins, uint64_t* d_h
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     if (h->k == 13) {                                             // the table itself: the u32 view and the full-width statistics in one pass
-        SPCHK(sp_spectrum((const uint64_t*)h->tf13_mphf, h->n, nbins, d_hist, d_stats, s));
+        AIXCHK(sp_spectrum((const uint64_t*)h->tf13_mphf, h->n, nbins, d_hist, d_stats, s));
         return AIX_OK;
     }
     DevArr vals(s);
-    SPCHK(vals.alloc(4 * h->n));
-    SPCHK(sp_values(h, (uint32_t*)vals.p, s));
-    SPCHK(sp_spectrum((const uint32_t*)vals.p, h->n, nbins, d_hist, d_stats, s));
+    AIXCHK(vals.alloc(4 * h->n));
+    AIXCHK(sp_values(h, (uint32_t*)vals.p, s));
+    AIXCHK(sp_spectrum((const uint32_t*)vals.p, h->n, nbins, d_hist, d_stats, s));
     return AIX_OK;
 }
 
@@ -504,12 +487,12 @@ extern "C" int aix_tf_spectrum(aix_index_t* h, uint64_t nbins, uint64_t* hist_ou
     if (nbins > kMaxBins) return AIX_ERR_NOMEM;
     DevGuard g(h->device);
     DevBuf dh, ds;
-    SPCHK(dh.alloc(8 * nbins));
-    SPCHK(ds.alloc(8 * AIX_SPECTRUM_STATS));
+    AIXCHK(dh.alloc(8 * nbins));
+    AIXCHK(ds.alloc(8 * AIX_SPECTRUM_STATS));
     const int st = aix_tf_spectrum_dev(h, nbins, (uint64_t*)dh.p, (uint64_t*)ds.p, nullptr);
     if (st) return st;
-    SPCHK(hipMemcpy(hist_out, dh.p, 8 * nbins, hipMemcpyDeviceToHost));
-    SPCHK(hipMemcpy(stats_out, ds.p, 8 * AIX_SPECTRUM_STATS, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(hist_out, dh.p, 8 * nbins, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(stats_out, ds.p, 8 * AIX_SPECTRUM_STATS, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
 
@@ -520,12 +503,12 @@ extern "C" int aix_top_kmers_dev(aix_index_t* h, uint32_t min_tf, uint64_t max_k
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     DevArr vals(s);
-    SPCHK(vals.alloc(4 * h->n));
-    SPCHK(sp_values(h, (uint32_t*)vals.p, s));
-    SPCHK(sp_select((const uint32_t*)vals.p, h->n, min_tf, max_kmers, cap ? d_kid : nullptr, d_tf, cap, nullptr, nullptr, n_out, total_out, s));
+    AIXCHK(vals.alloc(4 * h->n));
+    AIXCHK(sp_values(h, (uint32_t*)vals.p, s));
+    AIXCHK(sp_select((const uint32_t*)vals.p, h->n, min_tf, max_kmers, cap ? d_kid : nullptr, d_tf, cap, nullptr, nullptr, n_out, total_out, s));
     if (*n_out && *n_out <= cap && d_kid && d_kmers) {
-        SPCHK(sp_decode(h, nullptr, d_kid, *n_out, d_kmers, nullptr, nullptr, s));
-        SPCHK(hipStreamSynchronize(s));                           // as the selection: every output is complete on return
+        AIXCHK(sp_decode(h, nullptr, d_kid, *n_out, d_kmers, nullptr, nullptr, s));
+        AIXCHK(hipStreamSynchronize(s));                           // as the selection: every output is complete on return
     }
     return AIX_OK;
 }
@@ -539,13 +522,13 @@ extern "C" int aix_top_kmers(aix_index_t* h, uint32_t min_tf, uint64_t max_kmers
     if (h->n >= (1ull << 32)) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
     DevArr vals, idx, val, km;
-    SPCHK(vals.alloc(4 * h->n));
-    SPCHK(sp_values(h, (uint32_t*)vals.p, nullptr));
+    AIXCHK(vals.alloc(4 * h->n));
+    AIXCHK(sp_values(h, (uint32_t*)vals.p, nullptr));
     uint64_t m = 0, total = 0;
-    SPCHK(sp_select((const uint32_t*)vals.p, h->n, min_tf, max_kmers, nullptr, nullptr, 0, &idx, &val, &m, &total, nullptr));
+    AIXCHK(sp_select((const uint32_t*)vals.p, h->n, min_tf, max_kmers, nullptr, nullptr, 0, &idx, &val, &m, &total, nullptr));
     if (m && kmers_out) {
-        SPCHK(km.alloc(m * h->k));
-        SPCHK(sp_decode(h, nullptr, (const uint32_t*)idx.p, m, (char*)km.p, nullptr, nullptr, nullptr));
+        AIXCHK(km.alloc(m * h->k));
+        AIXCHK(sp_decode(h, nullptr, (const uint32_t*)idx.p, m, (char*)km.p, nullptr, nullptr, nullptr));
     }
     uint32_t* hk = (uint32_t*)malloc(m ? 4 * m : 4);
     uint32_t* ht = (uint32_t*)malloc(m ? 4 * m : 4);
@@ -554,7 +537,7 @@ extern "C" int aix_top_kmers(aix_index_t* h, uint32_t min_tf, uint64_t max_kmers
     if (e == hipSuccess && m) e = hipMemcpy(hk, idx.p, 4 * m, hipMemcpyDeviceToHost);
     if (e == hipSuccess && m) e = hipMemcpy(ht, val.p, 4 * m, hipMemcpyDeviceToHost);
     if (e == hipSuccess && m && kmers_out) e = hipMemcpy(hs, km.p, m * h->k, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(hk); free(ht); free(hs); SPCHK(e); }
+    if (e != hipSuccess) { free(hk); free(ht); free(hs); AIXCHK(e); }
     *kid_out = hk; *tf_out = ht;
     if (kmers_out) *kmers_out = hs;
     *n_out = m; *total_out = total;
@@ -566,7 +549,7 @@ extern "C" int aix_kmers_by_kid_dev(aix_index_t* h, const uint64_t* d_kid, uint6
     if (N >= (1ull << 56)) return AIX_ERR_NOMEM;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    SPCHK(sp_decode(h, d_kid, nullptr, N, d_kmers, d_rc, d_tf, (hipStream_t)stream));
+    AIXCHK(sp_decode(h, d_kid, nullptr, N, d_kmers, d_rc, d_tf, (hipStream_t)stream));
     return AIX_OK;
 }
 
@@ -577,15 +560,15 @@ extern "C" int aix_kmers_by_kid(aix_index_t* h, const uint64_t* kid, uint64_t N,
     DevGuard g(h->device);
     const uint64_t bytes = N * h->k;
     DevBuf dk, dm, dr, dt;
-    SPCHK(dk.alloc(8 * N));
-    SPCHK(dm.alloc(bytes));
-    if (rc_out) SPCHK(dr.alloc(bytes));
-    if (tf_out) SPCHK(dt.alloc(4 * N));
-    SPCHK(hipMemcpy(dk.p, kid, 8 * N, hipMemcpyHostToDevice));
+    AIXCHK(dk.alloc(8 * N));
+    AIXCHK(dm.alloc(bytes));
+    if (rc_out) AIXCHK(dr.alloc(bytes));
+    if (tf_out) AIXCHK(dt.alloc(4 * N));
+    AIXCHK(hipMemcpy(dk.p, kid, 8 * N, hipMemcpyHostToDevice));
     const int st = aix_kmers_by_kid_dev(h, (const uint64_t*)dk.p, N, (char*)dm.p, (char*)dr.p, (uint32_t*)dt.p, nullptr);
     if (st) return st;
-    SPCHK(hipMemcpy(kmers_out, dm.p, bytes, hipMemcpyDeviceToHost));
-    if (rc_out) SPCHK(hipMemcpy(rc_out, dr.p, bytes, hipMemcpyDeviceToHost));
-    if (tf_out) SPCHK(hipMemcpy(tf_out, dt.p, 4 * N, hipMemcpyDeviceToHost));
+    AIXCHK(hipMemcpy(kmers_out, dm.p, bytes, hipMemcpyDeviceToHost));
+    if (rc_out) AIXCHK(hipMemcpy(rc_out, dr.p, bytes, hipMemcpyDeviceToHost));
+    if (tf_out) AIXCHK(hipMemcpy(tf_out, dt.p, 4 * N, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

@@ -28,15 +28,11 @@
 #include <cstring>
 #include <string>
 
-#include <rocprim/rocprim.hpp>
-
-#include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_chains.hpp"
 #include "aix_probe.hpp"
 
 namespace aix {
 
-static constexpr int kUB = 256;                                   // four waves = 64 quads per workgroup
 static constexpr uint64_t kMask46 = (1ULL << 46) - 1;
 static constexpr uint32_t kWNone = 0xFFFFFFF8u;                   // port words from here on: no single live successor; + the out-degree (0, 2, 3, 4)
 static constexpr uint32_t kWDead = kWNone + 7u;                   // the node itself is dead
@@ -48,31 +44,10 @@ struct UgCounters {                                               // one zeroed 
     unsigned long long unflagged[66];                             // [0] after k_ug_links, [r] after round r
 };
 
-// AIX_UG_TEST_GRID (test hook, read per call): workgroups of every launch at most, so that small indexes make many trips
-static inline uint64_t ug_test_grid() { return env_u64("AIX_UG_TEST_GRID", 1, 65536, 65536); }
-
-static inline unsigned ug_grid(uint64_t work, uint64_t per_block, uint64_t cap) {
-    uint64_t b = (work + per_block - 1) / per_block;
-    if (b > 4096) b = 4096;                                        // grid-stride: a few atomics per workgroup, not per wave of work
-    if (b > cap) b = cap;
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
-
+// (block size kCB = four waves = 64 quads per workgroup, grid sizer, AIX_UG_TEST_GRID, wave-reduced counters: aix_chains.hpp)
 template <int J>
 __device__ __forceinline__ uint32_t ug_quad_bcast(uint32_t v) {   // lane J of the quad to its four lanes (DPP quad_perm [J, J, J, J]); all lanes active
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ unsigned long long ug_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-__device__ __forceinline__ unsigned long long ug_wave_max(unsigned long long v) {
-#pragma unroll
-    for (int s = 32; s; s >>= 1) { const unsigned long long o = __shfl_xor(v, s); v = o > v ? o : v; }
-    return v;
 }
 
 // the oriented k-mer that leaves node `code` through `port`
@@ -82,7 +57,7 @@ __device__ __forceinline__ uint64_t ug_orient(uint64_t code, uint32_t port) { re
 // 1. ports
 // ---------------------------------------------------------------------------------------------
 // One quad per (kid, port), 16 per wave, as k_db_neighbours lays its records out. policy: 0 = FilterGauge, 1 = filter always, 2 = never.
-__global__ void __launch_bounds__(kUB) k_ug_ports(const IndexDev ix_, uint32_t cutoff, int policy, uint32_t* __restrict__ word) {
+__global__ void __launch_bounds__(kCB) k_ug_ports(const IndexDev ix_, uint32_t cutoff, int policy, uint32_t* __restrict__ word) {
     const IndexDev& ix = ix_;
     const uint64_t NP = 2 * ix.n;
     const uint32_t lane = threadIdx.x & 63u, b = lane & 3u;
@@ -114,28 +89,23 @@ __global__ void __launch_bounds__(kUB) k_ug_ports(const IndexDev ix_, uint32_t c
 // ---------------------------------------------------------------------------------------------
 // 2. links and 3. ranking
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ug_count(unsigned long long mine, unsigned long long* dst) {
-    const unsigned long long s = ug_wave_sum(mine);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(dst, s);
-}
-
-__global__ void __launch_bounds__(kUB) k_ug_links(const uint32_t* __restrict__ word, uint64_t NP, uint64_t* __restrict__ st, unsigned long long* __restrict__ unflagged) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+__global__ void __launch_bounds__(kCB) k_ug_links(const uint32_t* __restrict__ word, uint64_t NP, uint64_t* __restrict__ st, unsigned long long* __restrict__ unflagged) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long open = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NP; p += stride) {
         const uint32_t t = word[p];
         bool linked = false;
         if (t < kWNone && (uint64_t)t < NP) linked = (uint64_t)word[t] == p && (t >> 1) != (uint32_t)(p >> 1);
         st[p] = linked ? ((uint64_t)(t ^ 1u) | (1ULL << 32)) : (p | kFlag);
         open += linked;
     }
-    ug_count(open, unflagged);
+    count_add(open, unflagged);
 }
 
-__global__ void __launch_bounds__(kUB) k_ug_jump(const uint64_t* __restrict__ in, uint64_t NP, uint64_t* __restrict__ out, unsigned long long* __restrict__ unflagged) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+__global__ void __launch_bounds__(kCB) k_ug_jump(const uint64_t* __restrict__ in, uint64_t NP, uint64_t* __restrict__ out, unsigned long long* __restrict__ unflagged) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long open = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NP; p += stride) {
         uint64_t s = in[p];
         if (!(s & kFlag)) {
             const uint64_t q = in[(uint32_t)s];
@@ -146,27 +116,27 @@ __global__ void __launch_bounds__(kUB) k_ug_jump(const uint64_t* __restrict__ in
         }
         out[p] = s;
     }
-    ug_count(open, unflagged);
+    count_add(open, unflagged);
 }
 
 // ---------------------------------------------------------------------------------------------
 // 4. cycles: state a = nx | md << 32 and key = stored code << 1 | port bit, for the unflagged ports only
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kUB) k_ug_cyc_init(const IndexDev ix_, const uint64_t* __restrict__ rank, const uint32_t* __restrict__ word, uint64_t NP,
+__global__ void __launch_bounds__(kCB) k_ug_cyc_init(const IndexDev ix_, const uint64_t* __restrict__ rank, const uint32_t* __restrict__ word, uint64_t NP,
                                                     uint64_t* __restrict__ a, uint64_t* __restrict__ key) {
     const IndexDev& ix = ix_;
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NP; p += stride) {
         if (rank[p] & kFlag) continue;
         a[p] = (uint64_t)(word[p] ^ 1u);                           // an unflagged port is linked: its word is its link
         key[p] = ((key_at(ix, p >> 1).code & kMask46) << 1) | (p & 1);
     }
 }
 
-__global__ void __launch_bounds__(kUB) k_ug_cyc_jump(const uint64_t* __restrict__ rank, uint64_t NP, uint64_t span, const uint64_t* __restrict__ a_in,
+__global__ void __launch_bounds__(kCB) k_ug_cyc_jump(const uint64_t* __restrict__ rank, uint64_t NP, uint64_t span, const uint64_t* __restrict__ a_in,
                                                     const uint64_t* __restrict__ k_in, uint64_t* __restrict__ a_out, uint64_t* __restrict__ k_out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t p = (uint64_t)blockIdx.x * kUB + threadIdx.x; p < NP; p += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NP; p += stride) {
         if (rank[p] & kFlag) continue;
         const uint64_t a = a_in[p];
         uint64_t k = k_in[p], md = a >> 32;
@@ -185,14 +155,14 @@ __global__ void __launch_bounds__(kUB) k_ug_cyc_jump(const uint64_t* __restrict_
 // spelling B at the end reached through R (position dR, reversed); the first oriented k-mer of a spelling leaves its end node through the
 // port opposite the unlinked one. Circle node: neither port is flagged. kid_unitig holds, until k_ug_assign, the start's kid (path) or
 // kCycMark | first code (circle); a start appends (first code, kid).
-__global__ void __launch_bounds__(kUB) k_ug_place(const IndexDev ix_, uint32_t cutoff, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ cyc_a,
+__global__ void __launch_bounds__(kCB) k_ug_place(const IndexDev ix_, uint32_t cutoff, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ cyc_a,
                                                  const uint64_t* __restrict__ cyc_k, uint64_t* __restrict__ kid_unitig, uint32_t* __restrict__ kid_pos,
                                                  uint8_t* __restrict__ kid_flag, uint64_t* __restrict__ start_code, uint32_t* __restrict__ start_kid,
                                                  UgCounters* __restrict__ ctr) {
     const IndexDev& ix = ix_;
-    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kUB;
+    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long live = 0, circ = 0;
-    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+    for (uint64_t kid = (uint64_t)blockIdx.x * kCB + threadIdx.x; kid < n; kid += stride) {
         const KeyRec me = key_at(ix, kid);
         if (!(me.tf > cutoff)) {
             kid_unitig[kid] = AIX_UNITIG_NONE; kid_pos[kid] = 0; kid_flag[kid] = 0;
@@ -230,23 +200,23 @@ __global__ void __launch_bounds__(kUB) k_ug_place(const IndexDev ix_, uint32_t c
             kid_unitig[kid] = tmp;
         }
     }
-    ug_count(live, &ctr->n_live);
-    ug_count(circ, &ctr->n_circular);
+    count_add(live, &ctr->n_live);
+    count_add(circ, &ctr->n_circular);
 }
 
-__global__ void __launch_bounds__(kUB) k_ug_ids(const uint32_t* __restrict__ sorted_kid, uint64_t U, uint64_t n, uint64_t* __restrict__ kid_unitig) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t j = (uint64_t)blockIdx.x * kUB + threadIdx.x; j < U; j += stride) {
+__global__ void __launch_bounds__(kCB) k_ug_ids(const uint32_t* __restrict__ sorted_kid, uint64_t U, uint64_t n, uint64_t* __restrict__ kid_unitig) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < U; j += stride) {
         const uint32_t kid = sorted_kid[j];
         if (kid < n) kid_unitig[kid] = j;
     }
 }
 
 // every live node that is not a start reads its id at its start (starts are not written here)
-__global__ void __launch_bounds__(kUB) k_ug_assign(const uint64_t* __restrict__ sorted_code, uint64_t U, uint64_t n, const uint32_t* __restrict__ kid_pos,
+__global__ void __launch_bounds__(kCB) k_ug_assign(const uint64_t* __restrict__ sorted_code, uint64_t U, uint64_t n, const uint32_t* __restrict__ kid_pos,
                                                   uint64_t* __restrict__ kid_unitig) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kCB + threadIdx.x; kid < n; kid += stride) {
         if (kid_pos[kid] == 0) continue;                           // dead, or a start
         const uint64_t t = kid_unitig[kid];
         uint64_t id;
@@ -268,12 +238,12 @@ __global__ void __launch_bounds__(kUB) k_ug_assign(const uint64_t* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // 6. emit
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kUB) k_ug_check(const IndexDev ix_, uint32_t cutoff, uint64_t U, const uint64_t* __restrict__ kid_unitig,
+__global__ void __launch_bounds__(kCB) k_ug_check(const IndexDev ix_, uint32_t cutoff, uint64_t U, const uint64_t* __restrict__ kid_unitig,
                                                  const uint32_t* __restrict__ kid_pos, UgCounters* __restrict__ ctr) {
     const IndexDev& ix = ix_;
-    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kUB;
+    const uint64_t n = ix.n, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long live = 0, starts = 0, bad = 0, mx = 0;
-    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+    for (uint64_t kid = (uint64_t)blockIdx.x * kCB + threadIdx.x; kid < n; kid += stride) {
         const uint64_t u = kid_unitig[kid];
         if (u == AIX_UNITIG_NONE) continue;
         const uint32_t pos = kid_pos[kid];
@@ -282,18 +252,17 @@ __global__ void __launch_bounds__(kUB) k_ug_check(const IndexDev ix_, uint32_t c
         bad += u >= U || !(key_at(ix, kid).tf > cutoff);
         mx = pos > mx ? pos : mx;
     }
-    ug_count(live, &ctr->n_live);
-    ug_count(starts, &ctr->n_starts);
-    ug_count(bad, &ctr->bad);
-    mx = ug_wave_max(mx);
-    if ((threadIdx.x & 63u) == 0 && mx) atomicMax(&ctr->max_pos, mx);
+    count_add(live, &ctr->n_live);
+    count_add(starts, &ctr->n_starts);
+    count_add(bad, &ctr->bad);
+    count_max(mx, &ctr->max_pos);
 }
 
 // sort key of a node: unitig << pos_bits | position; dead nodes behind everything
-__global__ void __launch_bounds__(kUB) k_ug_keys(uint64_t n, uint64_t U, int pos_bits, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
+__global__ void __launch_bounds__(kCB) k_ug_keys(uint64_t n, uint64_t U, int pos_bits, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
                                                 uint64_t* __restrict__ keys, uint32_t* __restrict__ kids) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t kid = (uint64_t)blockIdx.x * kCB + threadIdx.x; kid < n; kid += stride) {
         const uint64_t u = kid_unitig[kid];
         keys[kid] = u == AIX_UNITIG_NONE ? U << pos_bits : ((u << pos_bits) | kid_pos[kid]);
         kids[kid] = (uint32_t)kid;
@@ -301,12 +270,12 @@ __global__ void __launch_bounds__(kUB) k_ug_keys(uint64_t n, uint64_t U, int pos
 }
 
 // Entry j of the sorted nodes is k-mer j in unitig order: its unitig's k-mers start at j - pos, its bases at j - pos + 22 u.
-__global__ void __launch_bounds__(kUB) k_ug_emit(const IndexDev ix_, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ kids, uint64_t n_live, uint64_t U,
+__global__ void __launch_bounds__(kCB) k_ug_emit(const IndexDev ix_, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ kids, uint64_t n_live, uint64_t U,
                                                 int pos_bits, const uint8_t* __restrict__ kid_flag, uint64_t total, uint64_t* __restrict__ offsets,
                                                 uint8_t* __restrict__ bases, uint8_t* __restrict__ circular, uint32_t* __restrict__ tf_out) {
     const IndexDev& ix = ix_;
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t j = (uint64_t)blockIdx.x * kUB + threadIdx.x; j < n_live; j += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < n_live; j += stride) {
         const uint64_t key = keys[j], u = key >> pos_bits, pos = key & ((1ULL << pos_bits) - 1);
         const uint32_t kid = kids[j];
         if (u >= U || pos > j || kid >= ix.n) continue;            // (a layout that k_ug_check accepted never gets here)
@@ -329,126 +298,70 @@ __global__ void __launch_bounds__(kUB) k_ug_emit(const IndexDev ix_, const uint6
     }
 }
 
-struct UgAgg {
-    unsigned long long sum;
-    uint32_t mn, mx;
+struct UgToAgg {                                                  // (the aggregate, its reduction and k_chain_stats: aix_chains.hpp)
+    __host__ __device__ ChainAgg operator()(uint32_t t) const { return ChainAgg{t, t, t}; }
 };
-struct UgAggOp {
-    __host__ __device__ UgAgg operator()(const UgAgg& a, const UgAgg& b) const { return UgAgg{a.sum + b.sum, a.mn < b.mn ? a.mn : b.mn, a.mx > b.mx ? a.mx : b.mx}; }
-};
-struct UgToAgg {
-    __host__ __device__ UgAgg operator()(uint32_t t) const { return UgAgg{t, t, t}; }
-};
-struct UgUnitigOf {
-    int pos_bits;
-    __host__ __device__ uint64_t operator()(uint64_t key) const { return key >> pos_bits; }
-};
-
-__global__ void __launch_bounds__(kUB) k_ug_stats(const uint64_t* __restrict__ uniq, const UgAgg* __restrict__ agg, const uint64_t* __restrict__ count, uint64_t U,
-                                                 uint64_t* __restrict__ tf_sum, uint32_t* __restrict__ tf_min, uint32_t* __restrict__ tf_max) {
-    const uint64_t m = *count < U ? *count : U, stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t i = (uint64_t)blockIdx.x * kUB + threadIdx.x; i < m; i += stride) {
-        const uint64_t u = uniq[i];
-        if (u >= U) continue;
-        const UgAgg a = agg[i];
-        tf_sum[u] = a.sum; tf_min[u] = a.mn; tf_max[u] = a.mx;
-    }
-}
 
 // AIX_DBJ_FILTER (A/B switch): the policy of the walks (aix_debruijn.hip), whose probes these are: found keys nearly always
 static inline int ug_policy() { return (int)env_int("AIX_DBJ_FILTER", 0, 2, 2); }
 
-static inline int ug_ceil_log2(uint64_t v) {                      // smallest r with 2^r >= v
-    int r = 0;
-    while (r < 64 && (1ULL << r) < v) ++r;
-    return r;
-}
-static inline int ug_bit_length(uint64_t v) {
-    int r = 0;
-    while (v) { ++r; v >>= 1; }
-    return r;
-}
-
-#define UG(expr)                                 \
-    do {                                         \
-        const hipError_t e_ = (expr);            \
-        if (e_ != hipSuccess) return e_;         \
-    } while (0)
-#define UGL(...)                                 \
-    do {                                         \
-        hipLaunchKernelGGL(__VA_ARGS__);         \
-        UG(hipGetLastError());                   \
-    } while (0)
-
-static hipError_t ug_read(UgCounters* host, const UgCounters* dev, hipStream_t s) {
-    UG(hipMemcpyAsync(host, dev, sizeof(UgCounters), hipMemcpyDeviceToHost, s));
-    return hipStreamSynchronize(s);
-}
-
 // Outputs of the layout call. Synchronises `s`.
 static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_unitig, uint32_t* kid_pos, uint8_t* kid_flag, uint64_t out[4], hipStream_t s) {
     const IndexDev ix = h->dev();
-    const uint64_t n = ix.n, NP = 2 * n, cap = ug_test_grid();
-    const dim3 blk(kUB);
+    const uint64_t n = ix.n, NP = 2 * n, cap = chain_test_grid();
+    const dim3 blk(kCB);
     DevArr ctr_a(s), word(s), r0(s), r1(s), ca0(s), ck0(s), ca1(s), ck1(s), sc(s), sk(s), sc2(s), sk2(s), tmp(s);
-    UG(ctr_a.alloc(sizeof(UgCounters)));
-    UG(word.alloc(4 * NP));
-    UG(r0.alloc(8 * NP));
-    UG(r1.alloc(8 * NP));
+    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
+    AIX_TRY(word.alloc(4 * NP));
+    AIX_TRY(r0.alloc(8 * NP));
+    AIX_TRY(r1.alloc(8 * NP));
     UgCounters* ctr = (UgCounters*)ctr_a.p;
     UgCounters hc;
-    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    UGL(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
-    UGL(k_ug_links, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
-    UG(ug_read(&hc, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    AIX_TRY_LAUNCH(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
+    AIX_TRY_LAUNCH(k_ug_links, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
+    AIX_TRY(chain_read(&hc, ctr, s));
     uint64_t *cur = (uint64_t*)r0.p, *oth = (uint64_t*)r1.p;
     uint64_t open = hc.unflagged[0];
-    const int max_rounds = std::min(64, ug_ceil_log2(n) + 1);
-    for (int r = 1; r <= max_rounds && open; ++r) {
-        UGL(k_ug_jump, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
-        UG(ug_read(&hc, ctr, s));
+    AIX_TRY(chain_rank(n, ctr->unflagged, &open, s, [&](int r) {
+        AIX_TRY_LAUNCH(k_ug_jump, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
         std::swap(cur, oth);
-        const bool same = hc.unflagged[r] == open;
-        open = hc.unflagged[r];
-        if (same) break;                                           // only cycle ports are left
-    }
+        return hipSuccess;
+    }));                                                           // open: only cycle ports are left
     (oth == (uint64_t*)r0.p ? r0 : r1).drop();
     const uint64_t *cyc_a = nullptr, *cyc_k = nullptr;
     if (open) {
-        UG(ca0.alloc(8 * NP));
-        UG(ck0.alloc(8 * NP));
-        UG(ca1.alloc(8 * NP));
-        UG(ck1.alloc(8 * NP));
+        AIX_TRY(ca0.alloc(8 * NP));
+        AIX_TRY(ck0.alloc(8 * NP));
+        AIX_TRY(ca1.alloc(8 * NP));
+        AIX_TRY(ck1.alloc(8 * NP));
         uint64_t *a = (uint64_t*)ca0.p, *k = (uint64_t*)ck0.p, *a2 = (uint64_t*)ca1.p, *k2 = (uint64_t*)ck1.p;
-        UGL(k_ug_cyc_init, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, ix, (const uint64_t*)cur, (const uint32_t*)word.p, NP, a, k);
-        const int rounds = std::min(64, ug_ceil_log2(open) + 1);
+        AIX_TRY_LAUNCH(k_ug_cyc_init, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, ix, (const uint64_t*)cur, (const uint32_t*)word.p, NP, a, k);
+        const int rounds = std::min(64, ceil_log2(open) + 1);
         for (int r = 1; r <= rounds; ++r) {
-            UGL(k_ug_cyc_jump, dim3(ug_grid(NP, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)cur, NP, r <= 63 ? 1ULL << (r - 1) : 0ULL, (const uint64_t*)a,
+            AIX_TRY_LAUNCH(k_ug_cyc_jump, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cur, NP, r <= 63 ? 1ULL << (r - 1) : 0ULL, (const uint64_t*)a,
                 (const uint64_t*)k, a2, k2);
             std::swap(a, a2);
             std::swap(k, k2);
         }
         cyc_a = a; cyc_k = k;
-        UG(hipStreamSynchronize(s));
+        AIX_TRY(hipStreamSynchronize(s));
         (a2 == (uint64_t*)ca0.p ? ca0 : ca1).drop();
         (k2 == (uint64_t*)ck0.p ? ck0 : ck1).drop();
     }
     word.drop();
-    UG(sc.alloc(8 * n));
-    UG(sk.alloc(4 * n));
-    UGL(k_ug_place, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
+    AIX_TRY(sc.alloc(8 * n));
+    AIX_TRY(sk.alloc(4 * n));
+    AIX_TRY_LAUNCH(k_ug_place, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
         (uint32_t*)sk.p, ctr);
-    UG(ug_read(&hc, ctr, s));
+    AIX_TRY(chain_read(&hc, ctr, s));
     const uint64_t U = std::min<uint64_t>(hc.n_starts, n);
     if (U) {
-        UG(sc2.alloc(8 * U));
-        UG(sk2.alloc(4 * U));
-        size_t tb = 0;
-        UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
-        UG(tmp.alloc(tb ? tb : 1));
-        UG(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, (size_t)U, 0u, 46u, s));
-        UGL(k_ug_ids, dim3(ug_grid(U, 4 * kUB, cap)), blk, 0, s, (const uint32_t*)sk2.p, U, n, kid_unitig);
-        UGL(k_ug_assign, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)sc2.p, U, n, (const uint32_t*)kid_pos, kid_unitig);
+        AIX_TRY(sc2.alloc(8 * U));
+        AIX_TRY(sk2.alloc(4 * U));
+        AIX_TRY(sort_pairs((const uint64_t*)sc.p, (uint64_t*)sc2.p, (const uint32_t*)sk.p, (uint32_t*)sk2.p, U, 46u, tmp, s));
+        AIX_TRY_LAUNCH(k_ug_ids, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)sk2.p, U, n, kid_unitig);
+        AIX_TRY_LAUNCH(k_ug_assign, dim3(chain_grid(n, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)sc2.p, U, n, (const uint32_t*)kid_pos, kid_unitig);
     }
     out[0] = U;
     out[1] = hc.n_live + 22 * U;
@@ -462,54 +375,49 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
                           uint64_t* offsets, uint8_t* bases, uint8_t* circular, uint64_t* tf_sum, uint32_t* tf_min, uint32_t* tf_max, uint32_t* kmer_tf, bool* bad,
                           hipStream_t s) {
     const IndexDev ix = h->dev();
-    const uint64_t n = ix.n, cap = ug_test_grid();
-    const dim3 blk(kUB);
+    const uint64_t n = ix.n, cap = chain_test_grid();
+    const dim3 blk(kCB);
     *bad = false;
     DevArr ctr_a(s), keys(s), kids(s), keys2(s), kids2(s), tmp(s), tfs(s), uniq(s), agg(s), cnt(s), tmp2(s);
-    UG(ctr_a.alloc(sizeof(UgCounters)));
+    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
     UgCounters* ctr = (UgCounters*)ctr_a.p;
     UgCounters hc;
-    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
-    UG(ug_read(&hc, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
+    AIX_TRY(chain_read(&hc, ctr, s));
     if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
     const uint64_t n_live = hc.n_live, total = n_live + 22 * U;
     if (U == 0) {
-        UG(hipMemsetAsync(offsets, 0, 8, s));
+        AIX_TRY(hipMemsetAsync(offsets, 0, 8, s));
         return hipStreamSynchronize(s);
     }
-    const int pos_bits = ug_bit_length(hc.max_pos), end_bit = pos_bits + ug_bit_length(U);
-    UG(keys.alloc(8 * n));
-    UG(kids.alloc(4 * n));
-    UG(keys2.alloc(8 * n));
-    UG(kids2.alloc(4 * n));
-    UGL(k_ug_keys, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, n, U, pos_bits, kid_unitig, kid_pos, (uint64_t*)keys.p, (uint32_t*)kids.p);
-    size_t tb = 0;
-    UG(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, (size_t)n, 0u,
-                                 (unsigned)end_bit, s));
-    UG(tmp.alloc(tb ? tb : 1));
-    UG(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, (size_t)n, 0u,
-                                 (unsigned)end_bit, s));
-    UG(hipStreamSynchronize(s));
+    const int pos_bits = bit_length(hc.max_pos), end_bit = pos_bits + bit_length(U);
+    AIX_TRY(keys.alloc(8 * n));
+    AIX_TRY(kids.alloc(4 * n));
+    AIX_TRY(keys2.alloc(8 * n));
+    AIX_TRY(kids2.alloc(4 * n));
+    AIX_TRY_LAUNCH(k_ug_keys, dim3(chain_grid(n, 4 * kCB, cap)), blk, 0, s, n, U, pos_bits, kid_unitig, kid_pos, (uint64_t*)keys.p, (uint32_t*)kids.p);
+    AIX_TRY(sort_pairs((const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)kids.p, (uint32_t*)kids2.p, n, (unsigned)end_bit, tmp, s));
+    AIX_TRY(hipStreamSynchronize(s));
     keys.drop();
     kids.drop();
     uint32_t* tf_seq = kmer_tf;
     if (!tf_seq) {
-        UG(tfs.alloc(4 * n_live));
+        AIX_TRY(tfs.alloc(4 * n_live));
         tf_seq = (uint32_t*)tfs.p;
     }
-    UGL(k_ug_emit, dim3(ug_grid(n_live, 2 * kUB, cap)), blk, 0, s, ix, (const uint64_t*)keys2.p, (const uint32_t*)kids2.p, n_live, U, pos_bits, kid_flag, total, offsets,
-        bases, circular, tf_seq);
-    UG(uniq.alloc(8 * U));
-    UG(agg.alloc(sizeof(UgAgg) * U));
-    UG(cnt.alloc(8));
-    auto kin = rocprim::make_transform_iterator((const uint64_t*)keys2.p, UgUnitigOf{pos_bits});
+    AIX_TRY_LAUNCH(k_ug_emit, dim3(chain_grid(n_live, 2 * kCB, cap)), blk, 0, s, ix, (const uint64_t*)keys2.p, (const uint32_t*)kids2.p, n_live, U, pos_bits, kid_flag, total,
+        offsets, bases, circular, tf_seq);
+    AIX_TRY(uniq.alloc(8 * U));
+    AIX_TRY(agg.alloc(sizeof(ChainAgg) * U));
+    AIX_TRY(cnt.alloc(8));
+    auto kin = rocprim::make_transform_iterator((const uint64_t*)keys2.p, ChainUnitOf{pos_bits});
     auto vin = rocprim::make_transform_iterator((const uint32_t*)tf_seq, UgToAgg());
-    tb = 0;
-    UG(rocprim::reduce_by_key(nullptr, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
-    UG(tmp2.alloc(tb ? tb : 1));
-    UG(rocprim::reduce_by_key(tmp2.p, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (UgAgg*)agg.p, (uint64_t*)cnt.p, UgAggOp(), rocprim::equal_to<uint64_t>(), s));
-    UGL(k_ug_stats, dim3(ug_grid(U, 4 * kUB, cap)), blk, 0, s, (const uint64_t*)uniq.p, (const UgAgg*)agg.p, (const uint64_t*)cnt.p, U, tf_sum, tf_min, tf_max);
+    AIX_TRY(with_temp(tmp2, [&](void* t, size_t& tb) {
+        return rocprim::reduce_by_key(t, tb, kin, vin, (size_t)n_live, (uint64_t*)uniq.p, (ChainAgg*)agg.p, (uint64_t*)cnt.p, ChainAggOp(), rocprim::equal_to<uint64_t>(), s);
+    }));
+    AIX_TRY_LAUNCH(k_chain_stats<ChainAgg>, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)uniq.p, (const ChainAgg*)agg.p, (const uint64_t*)cnt.p, U, tf_sum,
+                   tf_min, tf_max);
     return hipStreamSynchronize(s);
 }
 
@@ -529,12 +437,12 @@ struct UlCounters {                                               // one zeroed 
     unsigned long long bad, n_ends, n_circular, n_none;
 };
 
-__global__ void __launch_bounds__(kUB) k_ul_ends(uint64_t n, uint64_t U, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
+__global__ void __launch_bounds__(kCB) k_ul_ends(uint64_t n, uint64_t U, const uint64_t* __restrict__ kid_unitig, const uint32_t* __restrict__ kid_pos,
                                                 const uint8_t* __restrict__ kid_flag, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ end_kid,
                                                 UlCounters* __restrict__ ctr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0, ends = 0, circ = 0;
-    for (uint64_t kid = (uint64_t)blockIdx.x * kUB + threadIdx.x; kid < n; kid += stride) {
+    for (uint64_t kid = (uint64_t)blockIdx.x * kCB + threadIdx.x; kid < n; kid += stride) {
         const uint64_t u = kid_unitig[kid];
         if (u == AIX_UNITIG_NONE) continue;
         if (u >= U) { ++bad; continue; }
@@ -546,13 +454,13 @@ __global__ void __launch_bounds__(kUB) k_ul_ends(uint64_t n, uint64_t U, const u
         if (pos == 0) { end_kid[2 * u + 1] = (uint32_t)kid; ++ends; }
         if (pos == m - 1) { end_kid[2 * u] = (uint32_t)kid; ++ends; }
     }
-    ug_count(bad, &ctr->bad);
-    ug_count(ends, &ctr->n_ends);
-    ug_count(circ, &ctr->n_circular);
+    count_add(bad, &ctr->bad);
+    count_add(ends, &ctr->n_ends);
+    count_add(circ, &ctr->n_circular);
 }
 
 // One quad per end, 16 per wave. policy as k_ug_ports. cand[4 e + j] = the j-th link word of end e in base order (kLNone behind the degree).
-__global__ void __launch_bounds__(kUB) k_ul_probe(const IndexDev ix_, uint32_t cutoff, int policy, uint64_t U, const uint64_t* __restrict__ kid_unitig,
+__global__ void __launch_bounds__(kCB) k_ul_probe(const IndexDev ix_, uint32_t cutoff, int policy, uint64_t U, const uint64_t* __restrict__ kid_unitig,
                                                  const uint32_t* __restrict__ kid_pos, const uint8_t* __restrict__ kid_flag, const uint64_t* __restrict__ offsets,
                                                  const uint32_t* __restrict__ end_kid, uint32_t* __restrict__ cand, uint32_t* __restrict__ deg,
                                                  UlCounters* __restrict__ ctr) {
@@ -608,18 +516,14 @@ __global__ void __launch_bounds__(kUB) k_ul_probe(const IndexDev ix_, uint32_t c
             deg[e] = d;
         }
     }
-    ug_count(bad, &ctr->bad);
-    ug_count(none, &ctr->n_none);
+    count_add(bad, &ctr->bad);
+    count_add(none, &ctr->n_none);
 }
 
-struct UlWiden {
-    __host__ __device__ uint64_t operator()(uint32_t d) const { return d; }
-};
-
-__global__ void __launch_bounds__(kUB) k_ul_fill(uint64_t NE, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ cand, uint64_t E,
+__global__ void __launch_bounds__(kCB) k_ul_fill(uint64_t NE, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ cand, uint64_t E,
                                                 uint32_t* __restrict__ link_to) {
-    const uint64_t stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t e = (uint64_t)blockIdx.x * kUB + threadIdx.x; e < NE; e += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         const uint64_t o = link_off[e], o1 = link_off[e + 1];
         const uint4 c4 = *reinterpret_cast<const uint4*>(cand + 4 * e);
         const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
@@ -637,10 +541,10 @@ __device__ __forceinline__ uint32_t ul_deg(const uint64_t* __restrict__ link_off
     return hi - at > 4 ? 5u : (uint32_t)(hi - at);
 }
 
-__global__ void __launch_bounds__(kUB) k_ul_bubbles(uint64_t U, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, uint64_t E,
+__global__ void __launch_bounds__(kCB) k_ul_bubbles(uint64_t U, const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, uint64_t E,
                                                    uint32_t* __restrict__ mate) {
-    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kUB;
-    for (uint64_t u = (uint64_t)blockIdx.x * kUB + threadIdx.x; u < U; u += stride) {
+    const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         uint32_t res = kLNone;
         uint64_t aR, aL, aF, aS, aX, aY;
         do {
@@ -666,54 +570,50 @@ __global__ void __launch_bounds__(kUB) k_ul_bubbles(uint64_t U, const uint64_t* 
 static hipError_t ul_links(const aix_index* h, uint32_t cutoff, const uint64_t* kid_unitig, const uint32_t* kid_pos, const uint8_t* kid_flag, uint64_t U,
                            const uint64_t* offsets, uint64_t* link_off, uint32_t* link_to, uint64_t link_cap, uint64_t* E_out, bool* bad, hipStream_t s) {
     const IndexDev ix = h->dev();
-    const uint64_t n = ix.n, NE = 2 * U, cap = ug_test_grid();
-    const dim3 blk(kUB);
+    const uint64_t n = ix.n, NE = 2 * U, cap = chain_test_grid();
+    const dim3 blk(kCB);
     *bad = false;
     DevArr ctr_a(s), lc_a(s), ek(s), cand(s), deg(s), tmp(s);
-    UG(ctr_a.alloc(sizeof(UgCounters)));
-    UG(lc_a.alloc(sizeof(UlCounters)));
+    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
+    AIX_TRY(lc_a.alloc(sizeof(UlCounters)));
     UgCounters* ctr = (UgCounters*)ctr_a.p;
     UlCounters* lc = (UlCounters*)lc_a.p;
     UgCounters hc;
     UlCounters hl;
-    UG(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    UG(hipMemsetAsync(lc, 0, sizeof(UlCounters), s));
-    UGL(k_ug_check, dim3(ug_grid(n, 2 * kUB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
-    UG(ug_read(&hc, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
+    AIX_TRY(hipMemsetAsync(lc, 0, sizeof(UlCounters), s));
+    AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
+    AIX_TRY(chain_read(&hc, ctr, s));
     if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
     if (U == 0) {
-        UG(hipMemsetAsync(link_off, 0, 8, s));
+        AIX_TRY(hipMemsetAsync(link_off, 0, 8, s));
         *E_out = 0;
         return hipStreamSynchronize(s);
     }
-    UG(ek.alloc(4 * NE));
-    UG(hipMemsetAsync(ek.p, 0xFF, 4 * NE, s));
-    UGL(k_ul_ends, dim3(ug_grid(n, 4 * kUB, cap)), blk, 0, s, n, U, kid_unitig, kid_pos, kid_flag, offsets, (uint32_t*)ek.p, lc);
-    UG(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
-    UG(hipStreamSynchronize(s));
+    AIX_TRY(ek.alloc(4 * NE));
+    AIX_TRY(hipMemsetAsync(ek.p, 0xFF, 4 * NE, s));
+    AIX_TRY_LAUNCH(k_ul_ends, dim3(chain_grid(n, 4 * kCB, cap)), blk, 0, s, n, U, kid_unitig, kid_pos, kid_flag, offsets, (uint32_t*)ek.p, lc);
+    AIX_TRY(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     if (hl.bad || hl.n_circular > U || hl.n_ends != 2 * (U - hl.n_circular)) { *bad = true; return hipSuccess; }
     const uint64_t n_circular = hl.n_circular;
-    UG(cand.alloc(16 * NE));
-    UG(deg.alloc(4 * (NE + 1)));
-    UG(hipMemsetAsync((uint32_t*)deg.p + NE, 0, 4, s));
-    UGL(k_ul_probe, dim3(ug_grid(NE, 2 * 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), U, kid_unitig, kid_pos, kid_flag, offsets, (const uint32_t*)ek.p,
+    AIX_TRY(cand.alloc(16 * NE));
+    AIX_TRY(deg.alloc(4 * (NE + 1)));
+    AIX_TRY(hipMemsetAsync((uint32_t*)deg.p + NE, 0, 4, s));
+    AIX_TRY_LAUNCH(k_ul_probe, dim3(chain_grid(NE, 2 * 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), U, kid_unitig, kid_pos, kid_flag, offsets, (const uint32_t*)ek.p,
         (uint32_t*)cand.p, (uint32_t*)deg.p, lc);
-    UG(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
-    UG(hipStreamSynchronize(s));
+    AIX_TRY(hipMemcpyAsync(&hl, lc, sizeof(UlCounters), hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     // every written end was written once: 2 (U - circular) writes, and exactly the two ends of every circular unitig are empty
     if (hl.bad || hl.n_none != 2 * n_circular) { *bad = true; return hipSuccess; }
     ek.drop();
-    auto din = rocprim::make_transform_iterator((const uint32_t*)deg.p, UlWiden());
-    size_t tb = 0;
-    UG(rocprim::exclusive_scan(nullptr, tb, din, link_off, (uint64_t)0, (size_t)(NE + 1), rocprim::plus<uint64_t>(), s));
-    UG(tmp.alloc(tb ? tb : 1));
-    UG(rocprim::exclusive_scan(tmp.p, tb, din, link_off, (uint64_t)0, (size_t)(NE + 1), rocprim::plus<uint64_t>(), s));
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint32_t*)deg.p, Widen<uint32_t>()), link_off, NE + 1, tmp, s));
     uint64_t E = 0;
-    UG(hipMemcpyAsync(&E, link_off + NE, 8, hipMemcpyDeviceToHost, s));
-    UG(hipStreamSynchronize(s));
+    AIX_TRY(hipMemcpyAsync(&E, link_off + NE, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     *E_out = E;
     if (E > link_cap || E == 0) return hipSuccess;
-    UGL(k_ul_fill, dim3(ug_grid(NE, 4 * kUB, cap)), blk, 0, s, NE, (const uint64_t*)link_off, (const uint32_t*)cand.p, E, link_to);
+    AIX_TRY_LAUNCH(k_ul_fill, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, NE, (const uint64_t*)link_off, (const uint32_t*)cand.p, E, link_to);
     return hipStreamSynchronize(s);
 }
 
@@ -722,16 +622,6 @@ static hipError_t ul_links(const aix_index* h, uint32_t cutoff, const uint64_t* 
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-#define UGCHK(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e == hipErrorOutOfMemory) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }        \
-        if (_e != hipSuccess) {                                                                  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-            return AIX_ERR_HIP;                                                                  \
-        }                                                                                        \
-    } while (0)
-
 // the refusals every entry point shares, decided before anything is allocated or launched
 static int ug_check_handle(const aix_index_t* h) {
     if (!h) return AIX_ERR_ARG;
@@ -749,7 +639,7 @@ extern "C" int aix_unitigs_layout_dev(aix_index_t* h, uint32_t cutoff, uint64_t*
     if (!d_kid_unitig || !d_kid_pos || !d_kid_flag || !n_unitigs_out || !total_bases_out || !n_live_out || !n_circular_out) return AIX_ERR_ARG;
     DevGuard g(h->device);
     uint64_t out[4] = {0, 0, 0, 0};
-    UGCHK(ug_layout(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, out, (hipStream_t)stream));
+    AIXCHK(ug_layout(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, out, (hipStream_t)stream));
     *n_unitigs_out = out[0]; *total_bases_out = out[1]; *n_live_out = out[2]; *n_circular_out = out[3];
     return AIX_OK;
 }
@@ -764,7 +654,7 @@ extern "C" int aix_unitigs_emit_dev(aix_index_t* h, uint32_t cutoff, const uint6
     if (U > h->n) return AIX_ERR_ARG;
     DevGuard g(h->device);
     bool bad = false;
-    UGCHK(ug_emit(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_bases, d_circular, d_tf_sum, d_tf_min, d_tf_max, d_kmer_tf, &bad,
+    AIXCHK(ug_emit(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_bases, d_circular, d_tf_sum, d_tf_min, d_tf_max, d_kmer_tf, &bad,
                   (hipStream_t)stream));
     return bad ? AIX_ERR_ARG : AIX_OK;
 }
@@ -778,41 +668,28 @@ extern "C" int aix_unitigs(aix_index_t* h, uint32_t cutoff, uint64_t* n_unitigs_
     DevGuard g(h->device);
     const uint64_t n = h->n;
     DevArr ku, kp, kf, off, bs, ci, ts, tn, tx, kt;
-    UGCHK(ku.alloc(8 * n));
-    UGCHK(kp.alloc(4 * n));
-    UGCHK(kf.alloc(n));
+    AIXCHK(ku.alloc(8 * n));
+    AIXCHK(kp.alloc(4 * n));
+    AIXCHK(kf.alloc(n));
     uint64_t U = 0, total = 0, n_live = 0, n_circ = 0;
     int r = aix_unitigs_layout_dev(h, cutoff, (uint64_t*)ku.p, (uint32_t*)kp.p, (uint8_t*)kf.p, &U, &total, &n_live, &n_circ, nullptr);
     if (r) return r;
-    UGCHK(off.alloc(8 * (U + 1)));
-    UGCHK(bs.alloc(total));
-    UGCHK(ci.alloc(U));
-    UGCHK(ts.alloc(8 * U));
-    UGCHK(tn.alloc(4 * U));
-    UGCHK(tx.alloc(4 * U));
-    if (kmer_tf_out) UGCHK(kt.alloc(4 * n_live));
+    AIXCHK(off.alloc(8 * (U + 1)));
+    AIXCHK(bs.alloc(total));
+    AIXCHK(ci.alloc(U));
+    AIXCHK(ts.alloc(8 * U));
+    AIXCHK(tn.alloc(4 * U));
+    AIXCHK(tx.alloc(4 * U));
+    if (kmer_tf_out) AIXCHK(kt.alloc(4 * n_live));
     r = aix_unitigs_emit_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (uint64_t*)off.p, (uint8_t*)bs.p, (uint8_t*)ci.p,
                              (uint64_t*)ts.p, (uint32_t*)tn.p, (uint32_t*)tx.p, kmer_tf_out ? (uint32_t*)kt.p : nullptr, nullptr);
     if (r) return r;
     // host copies: {destination, device block, bytes}; a NULL destination is an output the caller did not ask for
-    struct Out { void** dst; const void* src; uint64_t bytes; } outs[] = {
+    const HostOut outs[] = {
         {(void**)offsets_out, off.p, 8 * (U + 1)}, {(void**)bases_out, bs.p, total}, {(void**)circular_out, ci.p, U}, {(void**)tf_sum_out, ts.p, 8 * U},
         {(void**)tf_min_out, tn.p, 4 * U}, {(void**)tf_max_out, tx.p, 4 * U}, {(void**)kmer_tf_out, kt.p, 4 * n_live}, {(void**)kid_unitig_out, ku.p, 8 * n},
         {(void**)kid_pos_out, kp.p, 4 * n}, {(void**)kid_flag_out, kf.p, n}};
-    void* host[10] = {nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 10 && e == hipSuccess; ++i) {
-        if (!outs[i].dst) continue;
-        host[i] = malloc(outs[i].bytes ? outs[i].bytes : 1);
-        if (!host[i]) e = hipErrorOutOfMemory;
-        else if (outs[i].bytes) e = hipMemcpy(host[i], outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) {
-        for (void* p : host) free(p);
-        UGCHK(e);
-    }
-    for (int i = 0; i < 10; ++i)
-        if (outs[i].dst) *outs[i].dst = host[i];
+    AIXCHK(copy_out_host(outs, 10));
     *n_unitigs_out = U;
     return AIX_OK;
 }
@@ -827,7 +704,7 @@ extern "C" int aix_unitig_links_dev(aix_index_t* h, uint32_t cutoff, const uint6
     DevGuard g(h->device);
     bool bad = false;
     uint64_t E = 0;
-    UGCHK(ul_links(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_link_off, d_link_to, link_cap, &E, &bad, (hipStream_t)stream));
+    AIXCHK(ul_links(h, cutoff, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_link_off, d_link_to, link_cap, &E, &bad, (hipStream_t)stream));
     if (bad) return AIX_ERR_ARG;
     *n_links_out = E;
     return E > link_cap ? AIX_ERR_ARG : AIX_OK;
@@ -840,9 +717,9 @@ extern "C" int aix_unitig_bubbles_dev(uint64_t U, const uint64_t* d_link_off, co
     if (U > (uint64_t)kWNone / 2 || E > 8 * U) return AIX_ERR_ARG;
     if (U == 0) return AIX_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ul_bubbles, dim3(ug_grid(U, 4 * kUB, ug_test_grid())), dim3(kUB), 0, s, U, d_link_off, d_link_to, E, d_bubble_mate);
-    UGCHK(hipGetLastError());
-    UGCHK(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(k_ul_bubbles, dim3(chain_grid(U, 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, U, d_link_off, d_link_to, E, d_bubble_mate);
+    AIXCHK(hipGetLastError());
+    AIXCHK(hipStreamSynchronize(s));
     return AIX_OK;
 }
 
@@ -854,48 +731,34 @@ extern "C" int aix_unitig_links(aix_index_t* h, uint32_t cutoff, uint64_t* n_uni
     DevGuard g(h->device);
     const uint64_t n = h->n;
     DevArr ku, kp, kf, off, bs, ci, ts, tn, tx, lo, lt, bm;
-    UGCHK(ku.alloc(8 * n));
-    UGCHK(kp.alloc(4 * n));
-    UGCHK(kf.alloc(n));
+    AIXCHK(ku.alloc(8 * n));
+    AIXCHK(kp.alloc(4 * n));
+    AIXCHK(kf.alloc(n));
     uint64_t U = 0, total = 0, n_live = 0, n_circ = 0, E = 0;
     int r = aix_unitigs_layout_dev(h, cutoff, (uint64_t*)ku.p, (uint32_t*)kp.p, (uint8_t*)kf.p, &U, &total, &n_live, &n_circ, nullptr);
     if (r) return r;
-    UGCHK(off.alloc(8 * (U + 1)));
-    UGCHK(bs.alloc(total));
-    UGCHK(ci.alloc(U));
-    UGCHK(ts.alloc(8 * U));
-    UGCHK(tn.alloc(4 * U));
-    UGCHK(tx.alloc(4 * U));
+    AIXCHK(off.alloc(8 * (U + 1)));
+    AIXCHK(bs.alloc(total));
+    AIXCHK(ci.alloc(U));
+    AIXCHK(ts.alloc(8 * U));
+    AIXCHK(tn.alloc(4 * U));
+    AIXCHK(tx.alloc(4 * U));
     r = aix_unitigs_emit_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (uint64_t*)off.p, (uint8_t*)bs.p, (uint8_t*)ci.p,
                              (uint64_t*)ts.p, (uint32_t*)tn.p, (uint32_t*)tx.p, nullptr, nullptr);
     if (r) return r;
     bs.drop(); ci.drop(); ts.drop(); tn.drop(); tx.drop();
-    UGCHK(lo.alloc(8 * (2 * U + 1)));
-    UGCHK(lt.alloc(4 * 8 * U));
+    AIXCHK(lo.alloc(8 * (2 * U + 1)));
+    AIXCHK(lt.alloc(4 * 8 * U));
     r = aix_unitig_links_dev(h, cutoff, (const uint64_t*)ku.p, (const uint32_t*)kp.p, (const uint8_t*)kf.p, U, (const uint64_t*)off.p, (uint64_t*)lo.p,
                              (uint32_t*)lt.p, 8 * U, &E, nullptr);
     if (r) return r;
     if (bubble_mate_out) {
-        UGCHK(bm.alloc(4 * U));
+        AIXCHK(bm.alloc(4 * U));
         r = aix_unitig_bubbles_dev(U, (const uint64_t*)lo.p, (const uint32_t*)lt.p, E, (uint32_t*)bm.p, nullptr);
         if (r) return r;
     }
-    struct Out { void** dst; const void* src; uint64_t bytes; } outs[] = {
-        {(void**)link_off_out, lo.p, 8 * (2 * U + 1)}, {(void**)link_to_out, lt.p, 4 * E}, {(void**)bubble_mate_out, bm.p, 4 * U}};
-    void* host[3] = {nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) {
-        if (!outs[i].dst) continue;
-        host[i] = malloc(outs[i].bytes ? outs[i].bytes : 1);
-        if (!host[i]) e = hipErrorOutOfMemory;
-        else if (outs[i].bytes) e = hipMemcpy(host[i], outs[i].src, outs[i].bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) {
-        for (void* p : host) free(p);
-        UGCHK(e);
-    }
-    for (int i = 0; i < 3; ++i)
-        if (outs[i].dst) *outs[i].dst = host[i];
+    const HostOut outs[] = {{(void**)link_off_out, lo.p, 8 * (2 * U + 1)}, {(void**)link_to_out, lt.p, 4 * E}, {(void**)bubble_mate_out, bm.p, 4 * U}};
+    AIXCHK(copy_out_host(outs, 3));
     *n_unitigs_out = U;
     *n_links_out = E;
     return AIX_OK;
