@@ -34,6 +34,8 @@ WALK_MAX_STEPS = 1 << 20
 UNITIG_NONE = (1 << 64) - 1                                        # AIX_UNITIG_NONE
 BUBBLE_NONE = 0xFFFFFFFF                                           # AIX_BUBBLE_NONE
 GRAPH_MAX_THRESHOLD = 32767                                        # AIX_GRAPH_MAX_THRESHOLD
+THREAD_NO_LINK = (1 << 64) - 1                                     # AIX_THREAD_NO_LINK
+THREAD_BROKEN = (1 << 64) - 2                                      # AIX_THREAD_BROKEN
 SPECTRUM_STATS = 8                                                 # AIX_SPECTRUM_STATS
 STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", "max_wide", "sum_wide")
 FIX_NAMES = ("clean", "fixed", "partial", "unfixed", "short", "too_long", "bad_range")   # AIX_FIX_*
@@ -174,6 +176,10 @@ SIGNATURES = {
     "aix_graph_compact_layout_dev": (i32, [u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp] + [C.POINTER(u64)] * 4 + [vp]),
     "aix_graph_compact_emit_dev": (i32, [u64] + [vp] * 8 + [u64] + [vp] * 4 + [u64] * 3 + [vp] * 9),
     "aix_graph_clean": (i32, [u64] + [vp] * 8 + [u64, u32, u32] + [C.POINTER(u64)] * 4 + [C.POINTER(vp)] * 12),
+    "aix_graph_kidmap_dev": (i32, [u64, vp, vp, vp, u64] + [vp] * 8),
+    "aix_thread_nodes_dev": (i32, [u64, vp, vp, vp, u64, vp, vp, vp]),
+    "aix_seq_thread_dev": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64] + [vp] * 8 + [u64, C.POINTER(u64), vp]),
+    "aix_seq_thread": (i32, [vp, u32, vp, vp, u64] + [C.POINTER(vp)] * 8 + [C.POINTER(u64)] * 2),
     "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
     "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

@@ -81,6 +81,43 @@ def format_gfa(unitigs: dict, links: dict) -> Iterator[str]:
             yield f"L\tu{i}\t+\tu{i}\t+\t22M"
 
 
+def format_gfa_paths(unitigs: dict, links: dict, support, thread: dict, names: List[str]) -> Iterator[str]:
+    """format_gfa with the read evidence of Index.seq_thread: every L line carries RC:i:{support of the link} (the closing link of a
+    circular unitig: the number of times a step wound round it), and one P line per maximal stretch of linked steps of every sequence —
+    named names[i], then names[i].2, .. —, its segments as u{id}+ / u{id}-, with * for the overlaps. A step of one unitig alone is a
+    stretch too. unitigs / links / support / thread: numpy arrays (u64 / u32) of one graph. Host only."""
+    off = np.asarray(unitigs["offsets"]).astype(np.int64)
+    lo = np.asarray(links["link_off"]).astype(np.int64)
+    to = np.asarray(links["link_to"]).astype(np.int64)
+    e = np.repeat(np.arange(lo.shape[0] - 1, dtype=np.int64), np.diff(lo))
+    kept = np.asarray(support)[e <= (to ^ 1)].tolist()              # the links unitig_link_pairs writes, in its order
+    su, sp, sf = (np.asarray(thread[k]).astype(np.int64) for k in ("step_unitig", "step_pos", "step_flag"))
+    span = np.asarray(thread["q_last"]).astype(np.int64) - np.asarray(thread["q_first"]).astype(np.int64) + 1
+    m = (np.diff(off) - 22)[su] if su.shape[0] else su
+    ahead = np.where(sf & 1, m - 1 - sp, sp)                        # k-mers between the start of the traversal and the first window
+    wraps = np.bincount(su, weights=(ahead + span - 1) // np.maximum(m, 1), minlength=off.shape[0] - 1).astype(np.int64).tolist() if su.shape[0] else []
+    n_link = 0
+    for line in format_gfa(unitigs, links):
+        if line[0] == "L":
+            if n_link < len(kept):
+                line += f"\tRC:i:{kept[n_link]}"
+            else:
+                line += f"\tRC:i:{wraps[int(line.split(chr(9))[1][1:])] if wraps else 0}"
+            n_link += 1
+        yield line
+    sso = np.asarray(thread["seq_step_off"]).astype(np.int64).tolist()
+    linked = (np.asarray(thread["step_link"]) < np.uint64(_lib.THREAD_BROKEN)).tolist()
+    seg = [f"u{u}{'-' if f & 1 else '+'}" for u, f in zip(su.tolist(), sf.tolist())]
+    for i, name in enumerate(names):
+        part, start = 1, sso[i]
+        for j in range(sso[i] + 1, sso[i + 1] + 1):
+            if j == sso[i + 1] or not linked[j]:
+                if j > start:
+                    yield f"P\t{name if part == 1 else f'{name}.{part}'}\t{','.join(seg[start:j])}\t*"
+                    part += 1
+                start = j
+
+
 def iter_reads_by_kmer(kmer: str, aindex: "AIndex", k: int = 23):
     """API_DOCUMENTATION.md:238-243 — yields (rid, pos, read, poses) per read that holds an indexed occurrence of the k-mer, rid ascending;
     poses = the offsets of the k-mer inside the read, ascending, pos = poses[0]. get_rid2poses_batch + get_reads_by_rid_batch: two GPU calls."""
@@ -609,6 +646,56 @@ class AIndex:
                 links += line[0] == "L"
                 f.write(line + "\n")
         return segments, links
+
+    # ---- threading (Index.seq_thread_t; aix_seqthread.hip) ------------------------------------------------
+    def _thread(self, seqs, graph, cutoff: int, want_support: bool):
+        """(graph, the arrays of Index.seq_thread_t as numpy u64 / u32 in a dict, link_support | None)"""
+        self._req()
+        import torch
+        from .engine import _ragged
+        ix = self._wrapper._need23()
+        if graph is None:
+            graph = ix.thread_graph_t(cutoff)
+        data, offs = _ragged(seqs)
+        dev = graph["node"].device
+        st = torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev)
+        so = torch.from_numpy(offs.astype(np.int64)).to(dev)
+        sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev) if want_support else None
+        got = ix.seq_thread_t(graph, st, so, link_support=sup)
+        thread = ix._graph_to_host(dict(zip(ix.THREAD_KEYS, got)))
+        return graph, thread, (ix._graph_to_host({"s": sup})["s"] if want_support else None)
+
+    def thread_sequences(self, seqs, graph=None, cutoff: int = 0) -> List[List[tuple]]:
+        """Per sequence its path through the graph: [(unitig, '+' | '-', pos, q_first, q_last, linked)] — windows q_first .. q_last follow
+        each other on `unitig` from position pos on, forwards (+) or backwards (-); linked: the step is joined to the one before it by a
+        link of the graph. graph: what Index.thread_graph_t returned (unitigs, or contigs after cleaning), so that a caller builds it
+        once; None: the unitig graph at `cutoff`."""
+        _, t, _ = self._thread(seqs, graph, cutoff, False)
+        sso = t["seq_step_off"].tolist()
+        linked = (t["step_link"] < np.uint64(_lib.THREAD_BROKEN)).tolist()
+        rows = list(zip(t["step_unitig"].tolist(), ["+-"[f & 1] for f in t["step_flag"].tolist()], t["step_pos"].tolist(), t["q_first"].tolist(),
+                        t["q_last"].tolist(), linked))
+        return [rows[sso[i]:sso[i + 1]] for i in range(len(seqs))]
+
+    def get_link_support(self, seqs, graph=None, cutoff: int = 0) -> np.ndarray:
+        """uint64[E]: how many times the sequences traverse every link of the graph (a link and its dual count together)."""
+        return self._thread(seqs, graph, cutoff, True)[2]
+
+    def write_gfa_paths(self, path: str, seqs, names=None, graph=None, cutoff: int = 0) -> int:
+        """GFA 1 of the graph with the sequences threaded through it (format_gfa_paths): segments, links with RC:i: support, and one P line
+        per linked stretch of steps; names default to seq{i}. Returns the number of P lines written."""
+        graph, t, sup = self._thread(seqs, graph, cutoff, True)
+        ix = self._wrapper._need23()
+        g = ix._graph_to_host({k: graph[k] for k in ix.GRAPH_KEYS})
+        names = list(names) if names is not None else [f"seq{i}" for i in range(len(seqs))]
+        if len(names) != len(seqs):
+            raise ValueError("one name per sequence")
+        written = 0
+        with open(path, "w") as f:
+            for line in format_gfa_paths(g, g, sup, t, names):
+                written += line[0] == "P"
+                f.write(line + "\n")
+        return written
 
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):

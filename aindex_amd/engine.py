@@ -1008,6 +1008,102 @@ class Index:
             done += 1
         return g, done
 
+    # ---- threading (aix_seqthread.hip) -------------------------------------------------------------
+    THREAD_KEYS = ("seq_step_off", "step_unitig", "step_pos", "step_flag", "q_first", "q_last", "step_link")
+    THREAD_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint8, np.uint32, np.uint32, np.uint64)
+
+    def graph_kidmap_t(self, kid_map, offsets_t, compacted: dict, out=None):
+        """A k-mer map (kid_unitig int64[n], kid_pos int32[n], kid_flag uint8[n]) of a graph with `offsets_t` carried through one
+        compaction round: `compacted` is what graph_compact_t returned for that graph. -> the three arrays on the contigs (new tensors,
+        or `out`, which may be kid_map itself)."""
+        import torch
+        ku, kp, kf = kid_map
+        uc, up, uf = compacted["unitig_contig"], compacted["unitig_pos"], compacted["unitig_flag"]
+        for t in (ku, kp, kf, offsets_t, uc, up, uf):
+            self._chk_dev(t)
+        n, u = ku.numel(), offsets_t.numel() - 1
+        if kp.numel() != n or kf.numel() != n or u < 0 or any(t.numel() != u for t in (uc, up, uf)):
+            raise ValueError("a k-mer map holds n entries per array, the compaction map U")
+        o = out if out is not None else (torch.empty_like(ku), torch.empty_like(kp), torch.empty_like(kf))
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_graph_kidmap_dev(n, p(ku), p(kp), p(kf), u, p(offsets_t), p(uc), p(up), p(uf), p(o[0]), p(o[1]), p(o[2]),
+                                             _stream_ptr(self.device)), "aix_graph_kidmap_dev")
+        return o
+
+    def thread_nodes_t(self, kid_map, offsets_t):
+        """One word per kid from a k-mer map and the offsets of its graph: node int64[n] = unitig << 33 | pos << 2 | flag, -1 for a dead kid."""
+        import torch
+        ku, kp, kf = kid_map
+        for t in (ku, kp, kf, offsets_t):
+            self._chk_dev(t)
+        n, u = ku.numel(), offsets_t.numel() - 1
+        if kp.numel() != n or kf.numel() != n or u < 0:
+            raise ValueError("a k-mer map holds n entries per array")
+        node = torch.empty(n, dtype=torch.int64, device=ku.device)
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_thread_nodes_dev(n, p(ku), p(kp), p(kf), u, p(offsets_t), p(node), _stream_ptr(self.device)), "aix_thread_nodes_dev")
+        return node
+
+    def thread_graph_t(self, cutoff: int = 0, tip_max_kmers: int = 0, bubble_max_kmers: int = 0, rounds: int = 0) -> dict:
+        """The graph sequences are threaded through, built once: unitigs and links at `cutoff`, then up to `rounds` cleaning rounds (mark,
+        compact, the k-mer map composed after every round). -> the eight arrays of the graph, the k-mer map (kid_unitig, kid_pos,
+        kid_flag), node int64[n], and the ints U, E, rounds (done)."""
+        un = self.unitigs_t(cutoff)
+        g = dict(self._graph_of(un, self.unitig_links_t(cutoff, unitigs=un)))
+        kid_map = (un["kid_unitig"], un["kid_pos"], un["kid_flag"])
+        done = 0
+        while done < rounds:
+            remove, tips, arms = self.graph_mark_t(g, None, tip_max_kmers, bubble_max_kmers)
+            if tips + arms == 0:
+                break
+            nxt = self.graph_compact_t(g, None, remove)
+            kid_map = self.graph_kidmap_t(kid_map, g["offsets"], nxt)
+            g = {k: nxt[k] for k in self.GRAPH_KEYS}
+            done += 1
+        g.update(kid_unitig=kid_map[0], kid_pos=kid_map[1], kid_flag=kid_map[2], node=self.thread_nodes_t(kid_map, g["offsets"]),
+                 U=g["offsets"].numel() - 1, E=g["link_to"].numel(), rounds=done)
+        return g
+
+    def seq_thread_t(self, graph: dict, seqs_t, offs_t, link_support=None, cap_hint: int = 0):
+        """The paths of M sequences (uint8 bytes, int64 offsets[M + 1]) through `graph` (what thread_graph_t returned), on torch's current
+        stream: (seq_step_off int64[M + 1], step_unitig int32, step_pos int32, step_flag uint8, q_first int32, q_last int32, step_link
+        int64) — bit patterns of the unsigned fields; step_link -1 = no link, -2 = broken. link_support: int64[E], one is added per
+        traversed link and its dual (accumulated across calls)."""
+        import torch
+        u, e, q = self._graph_ptrs({k: graph[k] for k in self.GRAPH_KEYS})
+        node = graph["node"]
+        self._chk_dev(node)
+        if node.numel() != self.n:
+            raise ValueError("node must hold one word per stored k-mer")
+        if link_support is not None:
+            self._chk_dev(link_support)
+            if link_support.numel() != e or link_support.dtype != torch.int64:
+                raise ValueError("link_support must be int64[E]")
+        sup = vp(link_support.data_ptr()) if link_support is not None else None
+        st = _stream_ptr(self.device)
+        return self._seq_t("aix_seq_thread_dev", seqs_t, offs_t, [torch.int32, torch.int32, torch.uint8, torch.int32, torch.int32, torch.int64], cap_hint,
+                           lambda m, off, o, cap, tot: lib().aix_seq_thread_dev(self._h, vp(seqs_t.data_ptr()), vp(offs_t.data_ptr()), m, vp(node.data_ptr()), u,
+                                                                                q["offsets"], q["circular"], q["link_off"], q["link_to"], e, sup, off, *o, cap, tot, st))
+
+    def seq_thread(self, seqs: Sequence, cutoff: int = 0) -> dict:
+        """seq_thread_t through host memory, on the unitig graph at `cutoff` (built inside): numpy arrays seq_step_off uint64[M + 1],
+        step_unitig / step_pos / q_first / q_last uint32, step_flag uint8, step_link uint64, link_support uint64[E] (counted from zero),
+        and the ints U, E."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(8)]
+        u, e = C.c_uint64(), C.c_uint64()
+        check(lib().aix_seq_thread(self._h, cutoff, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, *[C.byref(p) for p in ps], C.byref(u), C.byref(e)),
+              "aix_seq_thread")
+        out = {"seq_step_off": self._take_as(ps[0], m + 1, np.uint64)}
+        t = int(out["seq_step_off"][m])
+        for i in range(1, 7):
+            out[self.THREAD_KEYS[i]] = self._take_as(ps[i], t, self.THREAD_DTYPES[i])
+        out.update(link_support=self._take_as(ps[7], e.value, np.uint64), U=u.value, E=e.value)
+        return out
+
     def _device_ctx(self):
         """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
         import contextlib

@@ -720,6 +720,88 @@ int aix_graph_clean(uint64_t U, const uint64_t* offsets, const uint8_t* bases, c
                     uint32_t** unitig_contig_out /* nullable */, uint64_t** unitig_pos_out /* nullable */, uint8_t** unitig_flag_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Threading: the path of every sequence through a unitig or contig graph, and the number of sequences that traverse every link.
+ * (The reference has no counterpart; the notation is that of the three blocks above. tests/seqthread_ref.py restates this block.)
+ *
+ * A k-mer map of a unitig set G is the three per-kid arrays of aix_unitigs_layout_dev read against G's offsets: kid_unitig u64[n]
+ * (AIX_UNITIG_NONE: the kid has no place in G), kid_pos u32[n] (the k-mer occupies bases [offsets[u] + pos, offsets[u] + pos + 23)),
+ * kid_flag u8[n] (bit 0: the stored key appears reverse-complemented in the spelling; bit 1: circular). m_u = offsets[u + 1] - offsets[u] - 22.
+ *
+ * 1. aix_graph_kidmap_dev carries a k-mer map of G through one compaction round to G': inputs the map on G, U and offsets[U + 1] of G,
+ *    and unitig_contig / unitig_pos / unitig_flag [U] as aix_graph_compact_layout_dev wrote them; outputs the map on G'. The outputs may
+ *    be the input arrays (every lane reads its own entry before it writes it). For a kid with (u, p, f):
+ *      u == AIX_UNITIG_NONE or unitig_contig[u] == AIX_BUBBLE_NONE: dead — AIX_UNITIG_NONE, pos 0, flag 0;
+ *      else unitig' = unitig_contig[u]; pos' = unitig_pos[u] + (unitig_flag[u] & 1 ? m_u - 1 - p : p);
+ *           flag' bit 0 = (f ^ unitig_flag[u]) & 1; flag' bit 1 = ((f | unitig_flag[u]) >> 1) & 1.
+ *    Validation, before anything is written (a violation is AIX_ERR_ARG with the outputs untouched): u < U; offsets[u + 1] >=
+ *    offsets[u] + 23 and p < m_u; unitig_contig[u] is AIX_BUBBLE_NONE or below 2^31 - 4 (the limit of U'); pos' fits 32 bits. A NULL
+ *    pointer where one is needed (offsets always; the kid arrays when n > 0; the unitig arrays when U > 0) is AIX_ERR_ARG, decided
+ *    before anything is allocated or launched. No handle: the current device. n == 0 is AIX_OK.
+ *
+ * 2. aix_thread_nodes_dev packs a k-mer map into one word per kid, node u64[n]:
+ *      node = unitig << 33 | pos << 2 | (flag & 3)      bits 63 .. 33 the unitig, bits 32 .. 2 the position, bits 1 .. 0 the flag
+ *      node = 0xFFFFFFFFFFFFFFFF                          a dead kid (no unitig id reaches 2^31 - 1)
+ *    Every entry is checked in the same pass: u < U, offsets[u + 1] >= offsets[u] + 23 and pos < m_u, else AIX_ERR_ARG with nothing
+ *    written. U > 2^31 - 4, or a position of 2^31 or more, is AIX_ERR_UNSUPPORTED with nothing written. NULL pointers as in 1.
+ *
+ * 3. aix_seq_thread_dev. Handle: exactly those of aix_unitigs_layout_dev (23-mer, canonical_only == 1, not empty, n <= 2^31 - 4), with the
+ *    same statuses. Sequences as aix_seq_hits_dev takes them: sequence i is the bytes d_seqs[d_offs[i] .. d_offs[i + 1]), offsets
+ *    ascending, a sequence of 2^32 bytes or more is AIX_ERR_ARG; d_seqs may be NULL when no sequence is 23 bytes long. Graph: d_node[n]
+ *    (n of the handle), U, d_offsets[U + 1], d_circular[U], d_link_off[2 U + 1], d_link_to[E] — a unitig set, or what the cleaning wrote,
+ *    with the node words of its k-mer map.
+ *    Validation, before anything is written (AIX_ERR_ARG with every output and link_support untouched): every node word is dead or
+ *    names a unitig below U and a position below its m_u; offsets ascend by at least 23 per unitig; link_off starts at 0, ascends, ends
+ *    at E, and no end has more than 4 links; E <= 8 U. U > 2^31 - 4 is AIX_ERR_UNSUPPORTED. Link words are not validated: they are only
+ *    compared. Every index read from node, offsets, link_off and link_to is checked against n, U, 2 U and E before it is used; whatever
+ *    the arrays hold, no address outside the given sizes is read or written.
+ *    Windows. Sequence i of length L has max(0, L - 22) windows, window q the 23 bytes at offset q. A window has a node iff all 23 bytes
+ *    are upper-case A, C, G, T, its canonical code is a stored key (whatever its tf), and node[kid] is not dead. Its node is (u, p, s)
+ *    with u and p from the word and s = flag bit 0 xor (the window's code is not the canonical one): s = 0 the window reads the
+ *    unitig's spelling forwards, s = 1 backwards. (k is odd: no window equals its own reverse complement.)
+ *    Steps. A step is a maximal run of consecutive windows of one sequence that all have nodes and where each follows its predecessor:
+ *    same u, same s, and p' = p + 1 (s = 0) or p' = p - 1 (s = 1); on a unitig with circular[u] != 0 the step is taken mod m_u, so a
+ *    step may wind round it more than once. A linear unitig of one k-mer never continues. One record per step: step_unitig u32,
+ *    step_pos u32 (the position of the first window), step_flag u8 (bit 0: traversed backwards; bit 1: circular[u] != 0), q_first and
+ *    q_last u32 (its first and last window), step_link u64. CSR over sequences: the steps of sequence i are
+ *    [seq_step_off[i], seq_step_off[i + 1]), ordered by q_first.
+ *    step_link. AIX_THREAD_NO_LINK when the step is the first of its sequence or a window without a node lies between it and the step
+ *    before. Else the two steps are adjacent (q_first == q_last of the previous step + 1) and the value is the index j into link_to of
+ *    the link e -> t traversed: e = 2 u + s of the previous step's last window, which must sit at its exit (p == m_u - 1 for s = 0,
+ *    p == 0 for s = 1); t = 2 v + s_v of this step's first window, which must sit at its entry (p == 0 for s_v = 0, p == m_v - 1 for
+ *    s_v = 1); j is the first index in [link_off[e], link_off[e + 1]) with link_to[j] == t. Adjacent steps without such a link get
+ *    AIX_THREAD_BROKEN: a value, not an error — it cannot occur when node map and links describe the same graph.
+ *    Link support (d_link_support u64[E], nullable). For every step with a link index j, support[j] += 1, and support[j'] += 1 for
+ *    its dual j' (the link t ^ 1 -> e ^ 1, found the same way) when it exists and j' != j; a hairpin u+ -> u- is its own dual and
+ *    counts once. The array is accumulated, never zeroed: a caller adds batch after batch. The adds happen only in the call that writes
+ *    the entries, so sizing first does not count twice. Starting from zero on a graph with duality, support[j] == support[dual j], and
+ *    a batch and its reverse complement give the same array. Integer adds commute: the result does not depend on the launch geometry.
+ *    Sizing, as aix_seq_hits_dev: d_seq_step_off[M + 1] and *total_out are always written; the entries, and the support, only when
+ *    *total_out <= cap (entries each of the six step arrays hold; they may be NULL when cap == 0), never at or beyond cap; AIX_OK
+ *    either way. M = 0 gives seq_step_off = {0}. The result is a pure function of (sequences, key set, node map, graph) — not of the
+ *    MPHF, the launch geometry or any probe switch. Returns after its work on `stream` has completed. Scratch: see DESIGN 5l.
+ *
+ * The host form builds layout, emit, links and nodes of the unitig graph at `cutoff` inside (as aix_unitig_links does), threads host
+ * sequences through it and returns malloc'd arrays (aix_free): seq_step_off[M + 1] and the six step arrays, optionally
+ * link_support[E] counted from zero, U and E. Threading through contigs is a device-form feature.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_THREAD_NO_LINK 0xFFFFFFFFFFFFFFFFull
+#define AIX_THREAD_BROKEN  0xFFFFFFFFFFFFFFFEull
+int aix_graph_kidmap_dev(uint64_t n, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag, uint64_t U,
+                         const uint64_t* d_offsets, const uint32_t* d_unitig_contig, const uint64_t* d_unitig_pos, const uint8_t* d_unitig_flag,
+                         uint64_t* d_out_unitig, uint32_t* d_out_pos, uint8_t* d_out_flag, void* stream);
+int aix_thread_nodes_dev(uint64_t n, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag, uint64_t U,
+                         const uint64_t* d_offsets, uint64_t* d_node, void* stream);
+int aix_seq_thread_dev(aix_index_t* h, const char* d_seqs, const uint64_t* d_offs, uint64_t M, const uint64_t* d_node, uint64_t U,
+                       const uint64_t* d_offsets, const uint8_t* d_circular, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E,
+                       uint64_t* d_link_support /* nullable */, uint64_t* d_seq_step_off, uint32_t* d_step_unitig, uint32_t* d_step_pos,
+                       uint8_t* d_step_flag, uint32_t* d_q_first, uint32_t* d_q_last, uint64_t* d_step_link, uint64_t cap, uint64_t* total_out,
+                       void* stream);
+int aix_seq_thread(aix_index_t* h, uint32_t cutoff, const char* seqs, const uint64_t* offs, uint64_t M, uint64_t** seq_step_off_out,
+                   uint32_t** step_unitig_out, uint32_t** step_pos_out, uint8_t** step_flag_out, uint32_t** q_first_out, uint32_t** q_last_out,
+                   uint64_t** step_link_out, uint64_t** link_support_out /* nullable */, uint64_t* n_unitigs_out /* nullable */,
+                   uint64_t* n_links_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
