@@ -180,6 +180,11 @@ SIGNATURES = {
     "aix_thread_nodes_dev": (i32, [u64, vp, vp, vp, u64, vp, vp, vp]),
     "aix_seq_thread_dev": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64] + [vp] * 8 + [u64, C.POINTER(u64), vp]),
     "aix_seq_thread": (i32, [vp, u32, vp, vp, u64] + [C.POINTER(vp)] * 8 + [C.POINTER(u64)] * 2),
+    "aix_thread_pairs_dev": (i32, [u64, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), vp]),
+    "aix_graph_resolve_mark_dev": (i32, [u64, vp, vp, vp, vp, u64, vp, vp, u64, u64, u64, vp, vp] + [C.POINTER(u64)] * 3 + [vp]),
+    "aix_graph_resolve_layout_dev": (i32, [u64, vp, u64, vp, vp, vp] + [C.POINTER(u64)] * 3 + [vp]),
+    "aix_graph_resolve_emit_dev": (i32, [u64] + [vp] * 8 + [u64] + [vp] * 4 + [u64] * 4 + [vp] * 10),
+    "aix_graph_resolve": (i32, [u64] + [vp] * 8 + [u64, vp, vp, u64, u64, u64] + [C.POINTER(u64)] * 4 + [C.POINTER(vp)] * 11),
     "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
     "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

@@ -697,6 +697,61 @@ class AIndex:
                 f.write(line + "\n")
         return written
 
+    # ---- repeat resolution (Index.graph_resolve_t; aix_graphresolve.hip) ---------------------------------
+    RESOLVE_BATCH_BYTES = 64 << 20                                 # reads threaded per call
+
+    def _resolved_graph(self, reads, cutoff: int, tip_max_kmers: int, bubble_max_kmers: int, rounds: int, min_link_support: int, min_pair_support: int,
+                        max_pair_noise: int) -> dict:
+        """the resolved and recompacted graph as numpy arrays: the cleaned graph built once, `reads` threaded through it in batches with
+        link support and transitions accumulated, weak links removed and repeats split, then one compaction under a zero mask"""
+        self._req()
+        import torch
+        from .engine import _ragged
+        ix = self._wrapper._need23()
+        graph = ix.thread_graph_t(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        dev = graph["node"].device
+        sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev)
+        pair = torch.zeros(16 * int(graph["U"]), dtype=torch.int64, device=dev)
+        batch, size = [], 0
+        reads = list(reads)
+        for i, r in enumerate(reads):
+            batch.append(r)
+            size += len(r)
+            if size >= self.RESOLVE_BATCH_BYTES or i + 1 == len(reads):
+                data, offs = _ragged(batch)
+                st = torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev)
+                steps = ix.seq_thread_t(graph, st, torch.from_numpy(offs.astype(np.int64)).to(dev), link_support=sup)
+                ix.thread_pairs_t(graph, steps, pair)
+                batch, size = [], 0
+        g = ix.graph_resolve_t(graph, sup, pair, min_link_support, min_pair_support, max_pair_noise, compact=True)
+        return ix._graph_to_host({k: g[k] for k in ix.GRAPH_KEYS})
+
+    def get_resolved_contigs(self, reads, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, min_link_support: int = 2,
+                             min_pair_support: int = 2, max_pair_noise: int = 0, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
+        """get_contigs with repeats resolved by `reads`: [(sequence, tf_sum, circular)]. The reads are threaded through the cleaned graph; a
+        link that fewer than min_link_support reads traverse is removed where its fork has a better one, and a repeat unitig whose entry
+        and exit links pair up one to one (every pair seen min_pair_support times or more, every other combination at most
+        max_pair_noise times) is split into one copy per pair, which the final compaction merges into its two neighbours."""
+        g = self._resolved_graph(reads, cutoff, tip_max_kmers, bubble_max_kmers, rounds, min_link_support, min_pair_support, max_pair_noise)
+        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
+        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
+                if off[i + 1] - off[i] - 22 >= min_kmers]
+
+    def write_resolved_contigs(self, path: str, reads, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
+                               min_link_support: int = 2, min_pair_support: int = 2, max_pair_noise: int = 0, min_kmers: int = 1) -> int:
+        """FASTA of get_resolved_contigs in the form of write_contigs; returns the number of records written."""
+        g = self._resolved_graph(reads, cutoff, tip_max_kmers, bubble_max_kmers, rounds, min_link_support, min_pair_support, max_pair_noise)
+        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
+        written = 0
+        with open(path, "w") as f:
+            for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
+                ln = off[i + 1] - off[i]
+                if ln - 22 < min_kmers:
+                    continue
+                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
+                written += 1
+        return written
+
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):
         """(corrected reads, records): every read's weak 23-windows (tf <= true_errors, read.hpp:296) are looked for, up to max_fixes

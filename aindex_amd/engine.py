@@ -1104,6 +1104,122 @@ class Index:
         out.update(link_support=self._take_as(ps[7], e.value, np.uint64), U=u.value, E=e.value)
         return out
 
+    # ---- repeat resolution (aix_graphresolve.hip) -------------------------------------------------
+    def thread_pairs_t(self, graph: dict, steps, pair_support=None):
+        """The transitions of threaded sequences through every unitig: `steps` is what seq_thread_t returned for `graph` (only step_unitig,
+        step_flag and step_link are read). pair_support int64[16 U]: cell 16 u + 4 x + y counts the sequences that pass unitig u between
+        link x of end 2 u and link y of end 2 u + 1 (local indices); accumulated across calls, a zeroed one is made when None.
+        -> (pair_support, n_pairs)."""
+        import torch
+        lo, to = graph["link_off"], graph["link_to"]
+        su, sf, sl = steps[1], steps[3], steps[6]
+        for t in (lo, to, su, sf, sl):
+            self._chk_dev(t)
+        u, e, n = (lo.numel() - 1) // 2, to.numel(), su.numel()
+        if lo.numel() != 2 * u + 1 or sf.numel() != n or sl.numel() != n:
+            raise ValueError("link_off must hold 2 U + 1 entries, the step arrays T each")
+        if pair_support is None:
+            pair_support = torch.zeros(16 * u, dtype=torch.int64, device=lo.device)
+        self._chk_dev(pair_support)
+        if pair_support.numel() != 16 * u or pair_support.dtype != torch.int64:
+            raise ValueError("pair_support must be int64[16 U]")
+        got = C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_thread_pairs_dev(u, p(lo), p(to), e, n, p(su), p(sf), p(sl), p(pair_support), C.byref(got), _stream_ptr(self.device)),
+                  "aix_thread_pairs_dev")
+        return pair_support, got.value
+
+    def _support_ptrs(self, u: int, e: int, link_support, pair_support):
+        import torch
+        for t, n, what in ((link_support, e, "link_support must be int64[E]"), (pair_support, 16 * u, "pair_support must be int64[16 U]")):
+            if t is not None:
+                self._chk_dev(t)
+                if t.numel() != n or t.dtype != torch.int64:
+                    raise ValueError(what)
+        return [vp(t.data_ptr()) if t is not None else None for t in (link_support, pair_support)]
+
+    def graph_resolve_mark_t(self, graph: dict, link_support=None, pair_support=None, min_link_support: int = 2, min_pair_support: int = 2,
+                             max_pair_noise: int = 0):
+        """Weak links and repeat splits of a unitig set in HBM, decided from link_support int64[E] and pair_support int64[16 U] (either may
+        be None: its rule is off): (link_remove uint8[E], copies uint8[U], n_links_removed, n_split, n_copies_added)."""
+        import torch
+        u, e, q = self._graph_ptrs({k: graph[k] for k in self.GRAPH_KEYS})
+        sup, pair = self._support_ptrs(u, e, link_support, pair_support)
+        dev = graph["offsets"].device
+        remove = torch.empty(e, dtype=torch.uint8, device=dev)
+        copies = torch.empty(u, dtype=torch.uint8, device=dev)
+        n = [C.c_uint64() for _ in range(3)]
+        with torch.cuda.device(self.device):
+            check(lib().aix_graph_resolve_mark_dev(u, q["offsets"], q["circular"], q["link_off"], q["link_to"], e, sup, pair, min_link_support, min_pair_support,
+                                                   max_pair_noise, vp(remove.data_ptr()), vp(copies.data_ptr()), *[C.byref(x) for x in n],
+                                                   _stream_ptr(self.device)), "aix_graph_resolve_mark_dev")
+        return remove, copies, n[0].value, n[1].value, n[2].value
+
+    def graph_resolve_t(self, graph: dict, link_support=None, pair_support=None, min_link_support: int = 2, min_pair_support: int = 2,
+                        max_pair_noise: int = 0, compact: bool = True) -> dict:
+        """Mark, layout and emit of the repeat resolution: the resolved unitig set G_r as a merged dict in the format of graph_compact_t
+        (the eight arrays, U, E) plus link_remove uint8[E], copies uint8[U], copy_base int32[U] (-1 = unsplit), unitig_origin int32[U']
+        and the ints n_links_removed, n_split, n_copies_added. compact: G_r is then compacted under an all-zero mask (graph_compact_t) and
+        that merged dict is returned, with "resolved" = the dict described above; unitig_origin still refers to G_r's ids."""
+        import torch
+        g = {k: graph[k] for k in self.GRAPH_KEYS}
+        u, e, q = self._graph_ptrs(g)
+        remove, copies, removed, n_split, added = self.graph_resolve_mark_t(graph, link_support, pair_support, min_link_support, min_pair_support, max_pair_noise)
+        _, pair = self._support_ptrs(u, e, None, pair_support)
+        dev = g["offsets"].device
+        base = torch.empty(u, dtype=torch.int32, device=dev)
+        u2, total, e2 = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_graph_resolve_layout_dev(u, q["offsets"], e, p(remove), p(copies), p(base), C.byref(u2), C.byref(total), C.byref(e2),
+                                                     _stream_ptr(self.device)), "aix_graph_resolve_layout_dev")
+            n = u2.value
+            out = {"offsets": torch.empty(n + 1, dtype=torch.int64, device=dev), "bases": torch.empty(total.value, dtype=torch.uint8, device=dev),
+                   "circular": torch.empty(n, dtype=torch.uint8, device=dev), "tf_sum": torch.empty(n, dtype=torch.int64, device=dev),
+                   "tf_min": torch.empty(n, dtype=torch.int32, device=dev), "tf_max": torch.empty(n, dtype=torch.int32, device=dev),
+                   "link_off": torch.empty(2 * n + 1, dtype=torch.int64, device=dev), "link_to": torch.empty(e2.value, dtype=torch.int32, device=dev)}
+            origin = torch.empty(n, dtype=torch.int32, device=dev)
+            check(lib().aix_graph_resolve_emit_dev(u, *[q[k] for k in self.GRAPH_KEYS], e, p(remove), p(copies), p(base), pair, min_pair_support, n, total.value,
+                                                   e2.value, *[p(out[k]) for k in self.GRAPH_KEYS], p(origin), _stream_ptr(self.device)),
+                  "aix_graph_resolve_emit_dev")
+        out.update(U=n, E=e2.value, link_remove=remove, copies=copies, copy_base=base, unitig_origin=origin, n_links_removed=removed, n_split=n_split,
+                   n_copies_added=added)
+        if not compact:
+            return out
+        merged = self.graph_compact_t(out, None, torch.zeros(n, dtype=torch.uint8, device=dev))
+        merged.update(resolved=out, unitig_origin=origin)
+        return merged
+
+    def graph_resolve(self, graph: dict, link_support=None, pair_support=None, min_link_support: int = 2, min_pair_support: int = 2,
+                      max_pair_noise: int = 0) -> dict:
+        """The resolution through host memory (aix_graph_resolve): numpy arrays in (the eight arrays of a unitig set, link_support uint64[E]
+        and pair_support uint64[16 U], either may be None), numpy arrays out — G_r, link_remove uint8[E], copies uint8[U], unitig_origin
+        uint32[U'] and the ints U, E, n_links_removed, n_split."""
+        a = [np.ascontiguousarray(graph[k], dtype=dt) for k, dt in zip(self.GRAPH_KEYS, self.GRAPH_DTYPES)]
+        u, e = a[0].shape[0] - 1, a[7].shape[0]
+        if u < 0 or a[6].shape[0] != 2 * u + 1 or any(a[i].shape[0] != u for i in (2, 3, 4, 5)) or (u and a[1].shape[0] != int(a[0][u])):
+            raise ValueError("the arrays of a unitig set must hold U + 1 offsets, offsets[U] bases, U values each and 2 U + 1 link offsets")
+        sup = None if link_support is None else np.ascontiguousarray(link_support, dtype=np.uint64)
+        pair = None if pair_support is None else np.ascontiguousarray(pair_support, dtype=np.uint64)
+        if (sup is not None and sup.shape[0] != e) or (pair is not None and pair.shape[0] != 16 * u):
+            raise ValueError("link_support must hold E entries, pair_support 16 U")
+        ps = [vp() for _ in range(11)]
+        n = [C.c_uint64() for _ in range(4)]
+        with self._device_ctx():
+            check(lib().aix_graph_resolve(u, *[x.ctypes.data_as(vp) for x in a], e, _np_ptr(sup), _np_ptr(pair), min_link_support, min_pair_support, max_pair_noise,
+                                          *[C.byref(x) for x in n], *[C.byref(x) for x in ps]), "aix_graph_resolve")
+        u2, e2 = n[0].value, n[1].value
+        off = self._take_as(ps[0], u2 + 1, np.uint64)
+        sizes = (None, int(off[u2]), u2, u2, u2, u2, 2 * u2 + 1, e2, e, u, u2)
+        names = self.GRAPH_KEYS + ("link_remove", "copies", "unitig_origin")
+        types = self.GRAPH_DTYPES + (np.uint8, np.uint8, np.uint32)
+        out = {"offsets": off}
+        for i in range(1, 11):
+            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+        out.update(U=u2, E=e2, n_links_removed=n[2].value, n_split=n[3].value)
+        return out
+
     def _device_ctx(self):
         """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
         import contextlib

@@ -802,6 +802,101 @@ int aix_seq_thread(aix_index_t* h, uint32_t cutoff, const char* seqs, const uint
                    uint64_t* n_links_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Repeat resolution: the transitions of threaded sequences through every unitig, weak-link removal, and repeat splitting.
+ * (The reference has no counterpart; the notation is that of the four blocks above. tests/graph_resolve_ref.py restates this block.)
+ *
+ * Ends, link words and duality as above: end 2 u + 0 is the exit of unitig u traversed forwards, end 2 u + 1 its exit backwards; the
+ * links of end e are link_to[link_off[e] .. link_off[e + 1]), and the LOCAL INDEX of link j at e is j - link_off[e], 0 .. 3; the dual of
+ * e -> t is t ^ 1 -> e ^ 1, found as the first index in the list of t ^ 1 whose word is e ^ 1. No call takes an index handle: they work on
+ * device arrays of the current device, are asynchronous on `stream` and return after their work on it has completed. Every call
+ * validates first and writes second: a violation is AIX_ERR_ARG with no output (and no in/out array) touched. Every index read from an
+ * input array is checked against U, 2 U, E and T before it is used. U > 2^31 - 4 is AIX_ERR_UNSUPPORTED, E > 8 U and a NULL pointer where
+ * one is needed AIX_ERR_ARG, decided before anything is allocated or launched. Scratch comes from the pool and goes back on every path.
+ *
+ * 1. aix_thread_pairs_dev. Inputs U, link_off[2 U + 1], link_to[E] and the step arrays step_unitig u32[T], step_flag u8[T], step_link
+ *    u64[T] as aix_seq_thread_dev wrote them (all sequences of a batch, concatenated). In/out pair_support u64[16 U]: accumulated, never
+ *    zeroed, like link_support. Step i (1 <= i < T - 1) is a TRANSITION iff a = step_link[i] and b = step_link[i + 1] are both below E: by
+ *    the threading contract step i - 1 is then the adjacent step of the same sequence, and the step enters u = step_unitig[i] at its
+ *    entry and leaves it at its exit. With s = step_flag[i] & 1, e_prev = 2 step_unitig[i - 1] + (step_flag[i - 1] & 1) and d the dual of
+ *    a (it lies in the list of (2 u + s) ^ 1): s == 0 gives x = the local index of b at end 2 u and y = that of d at end 2 u + 1; s == 1
+ *    gives y = the local index of b at end 2 u + 1 and x = that of d at end 2 u. Then pair_support[16 u + 4 x + y] += 1: x names the
+ *    link at end 2 u, y the link at end 2 u + 1, whichever way the sequence went. A sequence and its reverse complement hit the same
+ *    cell; a sequence that crosses u twice counts twice. *n_pairs_out = the number of transitions. Counted from zero over the same
+ *    batches as link_support, the cells of a link sum to at most its support — except at a hairpin u+ -> u-, its own dual, which the
+ *    support counts once per traversal while the sequence passes u twice there (into the hairpin and out of it): at most twice.
+ *    Validation: link_off starts at 0, ascends, ends at E, at most 4 links per end; step_unitig < U; every step_link is below E or one of
+ *    AIX_THREAD_NO_LINK / AIX_THREAD_BROKEN; step_link[0] is no link; for a transition a lies in the list of e_prev and link_to[a] ==
+ *    2 u + s, b lies in the list of 2 u + s, and d exists. T == 0 or U == 0 is AIX_OK with nothing done. Integer adds commute: the
+ *    result does not depend on the launch geometry.
+ *
+ * 2. aix_graph_resolve_mark_dev decides, from the input arrays alone, in one round. Inputs U, offsets, circular, link_off, link_to, E,
+ *    link_support u64[E] (nullable), pair_support u64[16 U] (nullable) and three thresholds; outputs link_remove u8[E] (1 = removed),
+ *    copies u8[U] (1 .. 4) and three counts. Validation: that of the cleaning block with the duality of EVERY link; link_support[j] ==
+ *    link_support[dual j] when the array is given; max_pair_noise < min_pair_support when splitting is on.
+ *    Weak links (off when link_support is NULL or min_link_support == 0). Link j: e -> t is weak iff support[j] < min_link_support. It is
+ *      removed iff it is weak and end e or end t ^ 1 has a link that is not weak: a fork decides, a lone weak link in a thin region
+ *      stays. The rule is symmetric under duality, so the surviving links keep duality; a hairpin is its own dual.
+ *    Splits (off when pair_support is NULL or min_pair_support == 0). A, B = the surviving links of ends 2 u, 2 u + 1. u is split iff it
+ *      is linear; |A| == |B| == d >= 2; no surviving link of u names u itself (no hairpin, no tandem self-link); every cell (x, y) of
+ *      A x B is strong (>= min_pair_support) or noise (<= max_pair_noise); every x has exactly one strong y and every y exactly one
+ *      strong x. Then copies[u] = d, else 1. Cells of removed links are ignored.
+ *
+ * 3. aix_graph_resolve_layout_dev / aix_graph_resolve_emit_dev write G_r, a unitig set in exactly the format of the input.
+ *    Layout. U' = U + sum(copies - 1); copy_base u32[U] = the id of copy 1 of u (U + the exclusive scan of copies - 1), AIX_BUBBLE_NONE
+ *      for an unsplit u; the sizes U', offsets'[U'] and E' = E - removed. copies outside 1 .. 4 is AIX_ERR_ARG, U' > 2^31 - 4
+ *      AIX_ERR_UNSUPPORTED.
+ *    Emit. The eight arrays of G_r and unitig_origin u32[U']. It validates the unitig set, that link_remove is set on a link and its
+ *      dual alike, that copy_base is the layout's, that every copies[u] > 1 is a split the arrays support (linear, no surviving self
+ *      link, the strong cells of the surviving links a perfect matching of copies[u] pairs; noise is mark's affair and is not looked at
+ *      again) and the three sizes, before anything is written. Ids below U keep offsets, bases, circular, tf_min and tf_max. Copy c of u
+ *      is numbered by the rank c of its end-0 link among A, in list order: copy 0 keeps the id u, copy c >= 1 is copy_base[u] + c - 1;
+ *      the copies are appended to the bases in id order with the same spelling, circular, tf_min and tf_max. tf_sum: with S the sum of
+ *      u's strong cells and p_c the strong cell of copy c, copy c >= 1 gets floor(tf_sum p_c / S), exact in 128 bits, and copy 0 the
+ *      rest, so the sum is conserved.
+ *      Links. Every surviving link j: e -> t exists exactly once in G_r. Its source is end e & 1 of the copy of e >> 1 that OWNS j: an
+ *      unsplit unitig is its own copy 0; at end 0 of a split unitig the rank of j in A; at end 1 the rank of the x matched to j's y. Its
+ *      word is 2 id(the copy of t >> 1 that owns dual j) + (t & 1). The links of an end keep their order; every end of a copy has
+ *      exactly one link; duality holds in G_r.
+ *      Input and output arrays must not overlap. d_out_bases must be aligned to 8 bytes (AIX_ERR_ARG), what the compaction asks of its
+ *      input.
+ *    Properties. (a) With nothing removed and nothing split, G_r == G in every array and unitig_origin is the identity. (b)
+ *      aix_graph_mark_dev and aix_graph_compact_* accept G_r; under an all-zero mask the compaction merges every copy with its two
+ *      neighbours. (c) E' = E - removed, sum tf_sum' = sum tf_sum, sum(copies - 1) = U' - U.
+ *    K-mer map. Unsplit unitigs keep id and positions, so a k-mer map of G stays valid for them. The k-mers of a split unitig keep
+ *      pointing at copy 0: threading through G_r reports AIX_THREAD_BROKEN at the other copies. A second resolution round therefore
+ *      needs a map that names several copies, which this block does not provide.
+ *    U == 0 gives U' = 0, offsets' = {0}, link_off' = {0}.
+ *
+ * The host form takes G, link_support and pair_support (both nullable) in host arrays, runs mark, layout and emit, and returns G_r,
+ * link_remove[E], copies[U] and unitig_origin[U'] in malloc'd arrays (aix_free); the last three are nullable.
+ * ------------------------------------------------------------------------------------------ */
+int aix_thread_pairs_dev(uint64_t U, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E, uint64_t T, const uint32_t* d_step_unitig,
+                         const uint8_t* d_step_flag, const uint64_t* d_step_link, uint64_t* d_pair_support, uint64_t* n_pairs_out, void* stream);
+int aix_graph_resolve_mark_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_circular, const uint64_t* d_link_off, const uint32_t* d_link_to,
+                               uint64_t E, const uint64_t* d_link_support /* nullable */, const uint64_t* d_pair_support /* nullable */,
+                               uint64_t min_link_support, uint64_t min_pair_support, uint64_t max_pair_noise, uint8_t* d_link_remove, uint8_t* d_copies,
+                               uint64_t* n_links_removed_out, uint64_t* n_split_out, uint64_t* n_copies_added_out, void* stream);
+int aix_graph_resolve_layout_dev(uint64_t U, const uint64_t* d_offsets, uint64_t E, const uint8_t* d_link_remove, const uint8_t* d_copies,
+                                 uint32_t* d_copy_base, uint64_t* n_unitigs_out, uint64_t* total_bases_out, uint64_t* n_links_out, void* stream);
+/* Writes G_r: d_out_offsets[U' + 1], d_out_bases[total_bases], d_out_circular / tf_sum / tf_min / tf_max [U'], d_out_link_off[2 U' + 1],
+ * d_out_link_to[n_links], d_unitig_origin[U']; nothing is written at or beyond these sizes. d_pair_support may be NULL when nothing is
+ * split. Scratch: see DESIGN 5m. */
+int aix_graph_resolve_emit_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, const uint8_t* d_circular, const uint64_t* d_tf_sum,
+                               const uint32_t* d_tf_min, const uint32_t* d_tf_max, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E,
+                               const uint8_t* d_link_remove, const uint8_t* d_copies, const uint32_t* d_copy_base,
+                               const uint64_t* d_pair_support /* nullable */, uint64_t min_pair_support, uint64_t n_unitigs, uint64_t total_bases,
+                               uint64_t n_links, uint64_t* d_out_offsets, uint8_t* d_out_bases, uint8_t* d_out_circular, uint64_t* d_out_tf_sum,
+                               uint32_t* d_out_tf_min, uint32_t* d_out_tf_max, uint64_t* d_out_link_off, uint32_t* d_out_link_to,
+                               uint32_t* d_unitig_origin, void* stream);
+int aix_graph_resolve(uint64_t U, const uint64_t* offsets, const uint8_t* bases, const uint8_t* circular, const uint64_t* tf_sum, const uint32_t* tf_min,
+                      const uint32_t* tf_max, const uint64_t* link_off, const uint32_t* link_to, uint64_t E, const uint64_t* link_support /* nullable */,
+                      const uint64_t* pair_support /* nullable */, uint64_t min_link_support, uint64_t min_pair_support, uint64_t max_pair_noise,
+                      uint64_t* n_unitigs_out, uint64_t* n_links_out, uint64_t* n_links_removed_out, uint64_t* n_split_out, uint64_t** offsets_out,
+                      uint8_t** bases_out, uint8_t** circular_out, uint64_t** tf_sum_out, uint32_t** tf_min_out, uint32_t** tf_max_out,
+                      uint64_t** link_off_out, uint32_t** link_to_out, uint8_t** link_remove_out /* nullable */, uint8_t** copies_out /* nullable */,
+                      uint32_t** unitig_origin_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
