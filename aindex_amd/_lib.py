@@ -185,6 +185,12 @@ SIGNATURES = {
     "aix_graph_resolve_layout_dev": (i32, [u64, vp, u64, vp, vp, vp] + [C.POINTER(u64)] * 3 + [vp]),
     "aix_graph_resolve_emit_dev": (i32, [u64] + [vp] * 8 + [u64] + [vp] * 4 + [u64] * 4 + [vp] * 10),
     "aix_graph_resolve": (i32, [u64] + [vp] * 8 + [u64, vp, vp, u64, u64, u64] + [C.POINTER(u64)] * 4 + [C.POINTER(vp)] * 11),
+    "aix_mate_links_dev": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "aix_mate_bundle_dev": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]),
+    "aix_scaffold_mark_dev": (i32, [u64] + [vp] * 6 + [u64, u32, u64, u64, u64, vp, vp, vp, C.POINTER(u64), vp]),
+    "aix_scaffold_layout_dev": (i32, [u64, vp, vp, vp, vp, u32, vp, vp, vp, vp] + [C.POINTER(u64)] * 3 + [vp]),
+    "aix_scaffold_emit_dev": (i32, [u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "aix_scaffold": (i32, [u64, vp, vp, vp, u64, vp, vp, u32, u64, u64, u64, u32] + [C.POINTER(u64)] * 4 + [C.POINTER(vp)] * 12),
     "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
     "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

@@ -752,6 +752,130 @@ class AIndex:
                 written += 1
         return written
 
+    # ---- scaffolding (Index.mate_links_t .. scaffold_t; aix_scaffold.hip) --------------------------------
+    def _pairs(self, pairs) -> list:
+        """[(left, right)] as bytes, both mates in fragment orientation: tuples, lines holding '~', or None for the loaded reads file"""
+        if pairs is None:
+            pairs = [r for _, r in self.iter_reads()]
+        out = []
+        for p in pairs:
+            if isinstance(p, (str, bytes)):
+                b = p.encode("latin-1") if isinstance(p, str) else bytes(p)
+                if b.count(b"~") != 1:
+                    continue                                       # a single-end line carries no pair
+                p = b.split(b"~")
+            a, b = p
+            out.append((a.encode("latin-1") if isinstance(a, str) else bytes(a), b.encode("latin-1") if isinstance(b, str) else bytes(b)))
+        return out
+
+    def _batches(self, seqs, dev):
+        """device (bytes, offsets) of `seqs` in batches of RESOLVE_BATCH_BYTES, each an even number of sequences"""
+        import torch
+        from .engine import _ragged
+        batch, size = [], 0
+        for i, r in enumerate(seqs):
+            batch.append(r)
+            size += len(r)
+            if (size >= self.RESOLVE_BATCH_BYTES and len(batch) % 2 == 0) or i + 1 == len(seqs):
+                data, offs = _ragged(batch)
+                yield torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev), torch.from_numpy(offs.astype(np.int64)).to(dev)
+                batch, size = [], 0
+
+    def scaffold_graph(self, pairs, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, resolve: bool = False):
+        """The graph the mates are threaded through (what Index.thread_graph_t returns): the cleaned graph, or with resolve=True the
+        resolved and recompacted one, the k-mers of split unitigs set dead in the map so that mates anchor in unique sequence. pairs
+        (read only with resolve=True): as get_scaffolds takes them."""
+        self._req()
+        import torch
+        ix = self._wrapper._need23()
+        graph = ix.thread_graph_t(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        if not resolve:
+            return graph
+        dev = graph["node"].device
+        sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev)
+        pair = torch.zeros(16 * int(graph["U"]), dtype=torch.int64, device=dev)
+        for st, so in self._batches([m for p in self._pairs(pairs) for m in p], dev):
+            ix.thread_pairs_t(graph, ix.seq_thread_t(graph, st, so, link_support=sup), pair)
+        merged = ix.graph_resolve_t(graph, sup, pair, compact=True)
+        ku = graph["kid_unitig"].clone()
+        ku[(ku >= 0) & (merged["resolved"]["copies"][ku.clamp(min=0)] > 1)] = -1          # AIX_UNITIG_NONE: a split unitig has no single place
+        kid_map = ix.graph_kidmap_t((ku, graph["kid_pos"], graph["kid_flag"]), merged["resolved"]["offsets"], merged)
+        g = {k: merged[k] for k in ix.GRAPH_KEYS}
+        g.update(kid_unitig=kid_map[0], kid_pos=kid_map[1], kid_flag=kid_map[2], node=ix.thread_nodes_t(kid_map, g["offsets"]), U=g["offsets"].numel() - 1,
+                 E=g["link_to"].numel(), rounds=graph["rounds"])
+        return g
+
+    def _scaffolds(self, pairs, insert_size, max_insert, min_anchor_windows, min_pairs, dominance, min_contig_bases, min_gap, cutoff, tip_max_kmers,
+                   bubble_max_kmers, rounds, resolve) -> dict:
+        """numpy arrays: the scaffolds (Index.scaffold_t), the joins, and the contigs' offsets"""
+        import torch
+        ix = self._wrapper._need23()
+        pairs = self._pairs(pairs)
+        graph = self.scaffold_graph(pairs, cutoff, tip_max_kmers, bubble_max_kmers, rounds, resolve)
+        dev = graph["node"].device
+        hist, keys, ds = None, [], []
+        for st, so in self._batches([m for p in pairs for m in p], dev):
+            key, d, _, hist = ix.mate_links_t(graph, ix.seq_thread_t(graph, st, so), so, min_anchor_windows, max_insert, hist)
+            keys.append(key)
+            ds.append(d)
+        if insert_size is None:
+            if hist is None:
+                raise ValueError("no pairs: pass insert_size")
+            insert_size = ix.insert_size_t(hist)                   # ValueError when no pair lies within one contig
+        key = torch.cat(keys) if keys else torch.zeros(0, dtype=torch.int64, device=dev)
+        d = torch.cat(ds) if ds else torch.zeros(0, dtype=torch.int32, device=dev)
+        slinks = ix.mate_bundle_t(key, d, int(graph["U"]), cap_hint=2 * key.numel())      # S <= 2 N: one pass, no sizing pass
+        joins = ix.scaffold_mark_t(graph, slinks, insert_size, min_pairs, dominance, min_contig_bases)
+        sc = ix.scaffold_t(graph, joins, min_gap)
+        out = ix._graph_to_host({k: v for k, v in {**joins, **sc, "offsets": graph["offsets"]}.items() if hasattr(v, "cpu")})
+        out.update(insert_size=insert_size, n_scaffolds=sc["n_scaffolds"], n_joins=joins["n_joins"], n_cut=sc["n_cut"])
+        return out
+
+    def get_scaffolds(self, pairs=None, insert_size: Optional[int] = None, max_insert: int = 1000, min_anchor_windows: int = 1, min_pairs: int = 2,
+                      dominance: int = 2, min_contig_bases: int = 0, min_gap: int = 1, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46,
+                      rounds: int = 3, resolve: bool = False) -> List[Tuple[str, List[tuple]]]:
+        """Contigs joined by read pairs: [(sequence, [(contig, '+' | '-', gap)])], the gap in front of the member (0 for the first) as
+        estimated, 'N' runs of max(gap, min_gap) in the sequence. pairs: [(left, right)] or lines `left~right`, both mates on the
+        fragment's strand as a reads file holds them; None: the loaded reads file. insert_size None: the median of the pairs that lie
+        within one contig."""
+        s = self._scaffolds(pairs, insert_size, max_insert, min_anchor_windows, min_pairs, dominance, min_contig_bases, min_gap, cutoff, tip_max_kmers,
+                            bubble_max_kmers, rounds, resolve)
+        text, so, mo = s["scaffold_bases"].tobytes().decode("ascii"), s["scaffold_offsets"].tolist(), s["member_off"].tolist()
+        mem, gap = s["member"].tolist(), s["member_gap"].view(np.int64).tolist()
+        return [(text[so[i]:so[i + 1]], [(w >> 1, "+-"[w & 1], g) for w, g in zip(mem[mo[i]:mo[i + 1]], gap[mo[i]:mo[i + 1]])]) for i in range(len(so) - 1)]
+
+    def write_scaffolds(self, path: str, pairs=None, **kw) -> int:
+        """FASTA of get_scaffolds (records s0, s1, ..); returns the number of records written."""
+        got = self.get_scaffolds(pairs, **kw)
+        with open(path, "w") as f:
+            for i, (seq, members) in enumerate(got):
+                f.write(f">s{i} LN:i:{len(seq)} members:i:{len(members)}\n{seq}\n")
+        return len(got)
+
+    def write_scaffolds_agp(self, path: str, pairs=None, **kw) -> int:
+        """AGP 2.0 of the scaffolds: a W line per member (component c<contig>, whole, with its orientation) and an N line per gap
+        (scaffold, linkage yes, paired-ends); returns the number of lines written. The arguments and defaults are get_scaffolds's."""
+        import inspect
+        args = inspect.signature(self.get_scaffolds).bind(pairs, **kw)     # a TypeError for a name get_scaffolds does not take
+        args.apply_defaults()
+        s, min_gap = self._scaffolds(**args.arguments), args.arguments["min_gap"]
+        off, mo, mem, gap = s["offsets"].tolist(), s["member_off"].tolist(), s["member"].tolist(), s["member_gap"].view(np.int64).tolist()
+        lines = 0
+        with open(path, "w") as f:
+            f.write("##agp-version 2.0\n")
+            for i in range(len(mo) - 1):
+                at, part = 1, 1
+                for j in range(mo[i], mo[i + 1]):
+                    if j > mo[i]:
+                        n = max(gap[j], min_gap)
+                        f.write(f"s{i}\t{at}\t{at + n - 1}\t{part}\tN\t{n}\tscaffold\tyes\tpaired-ends\n")
+                        at, part, lines = at + n, part + 1, lines + 1
+                    u = mem[j] >> 1
+                    ln = off[u + 1] - off[u]
+                    f.write(f"s{i}\t{at}\t{at + ln - 1}\t{part}\tW\tc{u}\t1\t{ln}\t{'+-'[mem[j] & 1]}\n")
+                    at, part, lines = at + ln, part + 1, lines + 1
+        return lines
+
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):
         """(corrected reads, records): every read's weak 23-windows (tf <= true_errors, read.hpp:296) are looked for, up to max_fixes

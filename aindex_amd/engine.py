@@ -1220,6 +1220,151 @@ class Index:
         out.update(U=u2, E=e2, n_links_removed=n[2].value, n_split=n[3].value)
         return out
 
+    # ---- scaffolding (aix_scaffold.hip) -------------------------------------------------------------
+    SLINK_KEYS = ("slink_off", "slink_to", "slink_count", "slink_dsum")
+
+    def mate_links_t(self, graph: dict, steps, offs_t, min_anchor_windows: int = 1, max_insert: int = 1000, insert_hist=None):
+        """One observation per pair of a threaded batch: `steps` is what seq_thread_t returned for `graph` and the sequences of `offs_t`
+        (int64[2 P + 1]; sequence 2 i the left mate, 2 i + 1 the right mate, both in fragment orientation). insert_hist int64[max_insert + 1]
+        is accumulated across calls, a zeroed one is made when None. -> (obs_key int64[P], obs_d int32[P], counts int64[4] = same contig,
+        link, discordant, unanchored, insert_hist) — bit patterns of the unsigned fields; obs_key -1 = no observation."""
+        import torch
+        off, circ = graph["offsets"], graph["circular"]
+        sso, su, sp, sf, qf, ql = steps[:6]
+        for t in (off, circ, offs_t, sso, su, sp, sf, qf, ql):
+            self._chk_dev(t)
+        m, n, u = offs_t.numel() - 1, su.numel(), off.numel() - 1
+        if m < 0 or m % 2 or sso.numel() != m + 1 or any(t.numel() != n for t in (sp, sf, qf, ql)) or circ.numel() != u:
+            raise ValueError("a batch of pairs holds 2 P + 1 offsets and step offsets, the step arrays T entries each")
+        dev = off.device
+        if insert_hist is None:
+            insert_hist = torch.zeros(max_insert + 1, dtype=torch.int64, device=dev)
+        self._chk_dev(insert_hist)
+        if insert_hist.numel() != max_insert + 1 or insert_hist.dtype != torch.int64:
+            raise ValueError("insert_hist must be int64[max_insert + 1]")
+        pairs = m // 2
+        key = torch.empty(pairs, dtype=torch.int64, device=dev)
+        d = torch.empty(pairs, dtype=torch.int32, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_mate_links_dev(pairs, p(offs_t), p(sso), n, p(su), p(sp), p(sf), p(qf), p(ql), u, p(off), p(circ), min_anchor_windows, max_insert,
+                                           p(insert_hist), p(key), p(d), p(counts), _stream_ptr(self.device)), "aix_mate_links_dev")
+        return key, d, counts, insert_hist
+
+    def mate_bundle_t(self, obs_key, obs_d, n_contigs: int, cap_hint: int = 0) -> dict:
+        """The observations of any number of batches (concatenated by the caller) as the scaffold graph over the 2 U contig ends:
+        slink_off int64[2 U + 1], slink_to int32[S], slink_count int64[S], slink_dsum int64[S] and the int S. cap_hint: the entries to
+        make room for at once; below S the call runs twice, a sizing pass and the fill. 2 N is always enough."""
+        import torch
+        self._chk_dev(obs_key)
+        self._chk_dev(obs_d)
+        n = obs_key.numel()
+        if obs_d.numel() != n or obs_key.dtype != torch.int64 or obs_d.dtype != torch.int32:
+            raise ValueError("obs_key must be int64[N], obs_d int32[N]")
+        dev = obs_key.device
+        off = torch.empty(2 * n_contigs + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            cap = max(int(cap_hint), 0)
+            while True:
+                outs = [torch.empty(max(cap, 1), dtype=dt, device=dev) for dt in (torch.int32, torch.int64, torch.int64)]
+                check(lib().aix_mate_bundle_dev(n, p(obs_key), p(obs_d), n_contigs, p(off), *[p(o) if cap else None for o in outs], cap, C.byref(total),
+                                                _stream_ptr(self.device)), "aix_mate_bundle_dev")
+                if total.value <= cap:
+                    break
+                cap = total.value
+        s = total.value
+        return {"slink_off": off, "slink_to": outs[0][:s], "slink_count": outs[1][:s], "slink_dsum": outs[2][:s], "S": s}
+
+    def scaffold_mark_t(self, graph: dict, slinks: dict, insert_size: int, min_pairs: int = 2, dominance: int = 2, min_contig_bases: int = 0) -> dict:
+        """Which contig ends are joined: join int32[2 U] (-1 = none), join_count int64[2 U], join_gap int64[2 U] and the int n_joins."""
+        import torch
+        off, circ = graph["offsets"], graph["circular"]
+        sl = [slinks[k] for k in self.SLINK_KEYS]
+        for t in [off, circ] + sl:
+            self._chk_dev(t)
+        u, s = off.numel() - 1, sl[1].numel()
+        if u < 0 or circ.numel() != u or sl[0].numel() != 2 * u + 1 or sl[2].numel() != s or sl[3].numel() != s:
+            raise ValueError("a scaffold graph holds 2 U + 1 link offsets and S entries per link array")
+        dev = off.device
+        join = torch.empty(2 * u, dtype=torch.int32, device=dev)
+        count = torch.empty(2 * u, dtype=torch.int64, device=dev)
+        gap = torch.empty(2 * u, dtype=torch.int64, device=dev)
+        n = C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_scaffold_mark_dev(u, p(off), p(circ), *[p(t) for t in sl], s, insert_size, min_pairs, dominance, min_contig_bases, p(join), p(count), p(gap),
+                                              C.byref(n), _stream_ptr(self.device)), "aix_scaffold_mark_dev")
+        return {"join": join, "join_count": count, "join_gap": gap, "n_joins": n.value}
+
+    def scaffold_t(self, graph: dict, joins: dict, min_gap: int = 1) -> dict:
+        """Layout and emit of the scaffolds of `graph` (offsets, bases) under `joins` (what scaffold_mark_t returned): contig_scaffold and
+        contig_rank int32[U], contig_pos int64[U], contig_flag uint8[U], scaffold_offsets int64[Sc + 1], scaffold_bases uint8, member_off
+        int64[Sc + 1], member int32[U] (2 u + flag), member_gap int64[U] and the ints n_scaffolds, total_bases, n_cut."""
+        import torch
+        off, bases = graph["offsets"], graph["bases"]
+        jn, jc, jg = joins["join"], joins["join_count"], joins["join_gap"]
+        for t in (off, bases, jn, jc, jg):
+            self._chk_dev(t)
+        u = off.numel() - 1
+        if u < 0 or any(t.numel() != 2 * u for t in (jn, jc, jg)):
+            raise ValueError("join, join_count and join_gap hold 2 U entries")
+        dev = off.device
+        cs, cr = torch.empty(u, dtype=torch.int32, device=dev), torch.empty(u, dtype=torch.int32, device=dev)
+        cp, cf = torch.empty(u, dtype=torch.int64, device=dev), torch.empty(u, dtype=torch.uint8, device=dev)
+        n = [C.c_uint64() for _ in range(3)]
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_scaffold_layout_dev(u, p(off), p(jn), p(jc), p(jg), min_gap, p(cs), p(cr), p(cp), p(cf), *[C.byref(x) for x in n],
+                                                _stream_ptr(self.device)), "aix_scaffold_layout_dev")
+            sc, total = n[0].value, n[1].value
+            so, mo = torch.empty(sc + 1, dtype=torch.int64, device=dev), torch.empty(sc + 1, dtype=torch.int64, device=dev)
+            sb = torch.empty(total, dtype=torch.uint8, device=dev)
+            mm, mg = torch.empty(u, dtype=torch.int32, device=dev), torch.empty(u, dtype=torch.int64, device=dev)
+            check(lib().aix_scaffold_emit_dev(u, p(off), p(bases), p(jn), p(jg), min_gap, p(cs), p(cr), p(cp), p(cf), sc, total, p(so), p(sb), p(mo), p(mm), p(mg),
+                                              _stream_ptr(self.device)), "aix_scaffold_emit_dev")
+        return {"contig_scaffold": cs, "contig_rank": cr, "contig_pos": cp, "contig_flag": cf, "scaffold_offsets": so, "scaffold_bases": sb, "member_off": mo,
+                "member": mm, "member_gap": mg, "n_scaffolds": sc, "total_bases": total, "n_cut": n[2].value}
+
+    @staticmethod
+    def insert_size_t(hist) -> int:
+        """The lower median of an insert histogram (what mate_links_t accumulated). ValueError when it is empty: the caller then passes
+        insert_size itself."""
+        import torch
+        acc = torch.cumsum(hist, 0)
+        n = int(acc[-1]) if acc.numel() else 0
+        if n == 0:
+            raise ValueError("the insert histogram is empty")
+        return int(torch.searchsorted(acc, torch.tensor([(n + 1) // 2], dtype=acc.dtype, device=acc.device))[0])
+
+    def scaffold(self, offsets, bases, circular, obs_key, obs_d, insert_size: int, min_pairs: int = 2, dominance: int = 2, min_contig_bases: int = 0,
+                 min_gap: int = 1) -> dict:
+        """Bundle, mark, layout and emit through host memory (aix_scaffold): numpy arrays in (the contigs and N observations), numpy arrays
+        out — the five scaffold arrays, join / join_count / join_gap [2 U], the map, and the ints n_scaffolds, n_joins, n_cut, S."""
+        a = [np.ascontiguousarray(x, dtype=dt) for x, dt in zip((offsets, bases, circular, obs_key, obs_d), (np.uint64, np.uint8, np.uint8, np.uint64, np.uint32))]
+        u, nobs = a[0].shape[0] - 1, a[3].shape[0]
+        if u < 0 or a[2].shape[0] != u or a[4].shape[0] != nobs or (u and a[1].shape[0] != int(a[0][u])):
+            raise ValueError("contigs hold U + 1 offsets, offsets[U] bases and U flags; observations N keys and N distances")
+        ps = [vp() for _ in range(12)]
+        n = [C.c_uint64() for _ in range(4)]
+        with self._device_ctx():
+            check(lib().aix_scaffold(u, _np_ptr(a[0]), _np_ptr(a[1]) if u else None, _np_ptr(a[2]) if u else None, nobs, _np_ptr(a[3]) if nobs else None,
+                                     _np_ptr(a[4]) if nobs else None, insert_size, min_pairs, dominance, min_contig_bases, min_gap, *[C.byref(x) for x in n],
+                                     *[C.byref(x) for x in ps]), "aix_scaffold")
+        sc = n[0].value
+        so = self._take_as(ps[0], sc + 1, np.uint64)
+        names = ("scaffold_offsets", "scaffold_bases", "member_off", "member", "member_gap", "join", "join_count", "join_gap", "contig_scaffold", "contig_rank",
+                 "contig_pos", "contig_flag")
+        sizes = (None, int(so[sc]), sc + 1, u, u, 2 * u, 2 * u, 2 * u, u, u, u, u)
+        types = (np.uint64, np.uint8, np.uint64, np.uint32, np.int64, np.uint32, np.uint64, np.int64, np.uint32, np.uint32, np.uint64, np.uint8)
+        out = {"scaffold_offsets": so}
+        for i in range(1, 12):
+            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+        out.update(n_scaffolds=sc, n_joins=n[1].value, n_cut=n[2].value, S=n[3].value, total_bases=int(so[sc]))
+        return out
+
     def _device_ctx(self):
         """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
         import contextlib

@@ -897,6 +897,103 @@ int aix_graph_resolve(uint64_t U, const uint64_t* offsets, const uint8_t* bases,
                       uint32_t** unitig_origin_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Scaffolding: read pairs threaded through a contig graph become counted, gap-estimated links between contig ends; the joins are
+ * decided per end; chains of joined contigs are written as gapped scaffolds.
+ * (The reference has no counterpart; the notation is that of the graph blocks above. tests/scaffold_ref.py restates this block.)
+ *
+ * L_u = offsets[u + 1] - offsets[u], m_u = L_u - 22. End 2 u + 0 is the exit of contig u traversed forwards, 2 u + 1 its exit backwards; a
+ * word 2 v + r names v entered in orientation r; the dual of e -> t is t ^ 1 -> e ^ 1. No call takes an index handle: they work on device
+ * arrays of the current device, are asynchronous on `stream` and return after their work on it has completed. Every call validates
+ * first and writes second: a violation is AIX_ERR_ARG with no output (and no in/out array) touched. Every index read from an input
+ * array is checked against its bound before it is used. U > 2^31 - 4 is AIX_ERR_UNSUPPORTED, a NULL pointer where one is needed
+ * AIX_ERR_ARG, decided before anything is allocated or launched. Scratch comes from the pool and goes back on every path. Integer adds
+ * and deterministic tie rules only: no result depends on the launch geometry.
+ *
+ * 1. aix_mate_links_dev: one observation per pair. Inputs P; d_offs[2 P + 1], the sequence offsets of a threaded batch in which sequence
+ *    2 i is the left mate A and 2 i + 1 the right mate B of pair i, both in fragment orientation (the line R1~revcomp(R2) of a reads
+ *    file); seq_step_off[2 P + 1] and the step arrays step_unitig, step_pos, step_flag, q_first, q_last [T] of aix_seq_thread_dev; U,
+ *    offsets[U + 1], circular[U]; min_anchor_windows >= 1 and max_insert in 1 .. 2^20.
+ *    Anchor of a mate: its step with the most windows (q_last - q_first + 1), the earliest on a tie; it is an anchor only with at least
+ *      min_anchor_windows windows and on a unitig that is not circular. With (u, pos, s = flag & 1) of that step, the start of the mate in
+ *      the coordinates of its contig oriented as the step traverses it is, in signed 64 bits, x0 = pos - q_first (s = 0) or
+ *      (m_u - 1 - pos) - q_first (s = 1).
+ *    Cases, with anchors (u, sA, x0A), (v, sB, x0B) and mate lengths LA, LB. A mate without an anchor: unanchored. u == v, sA == sB:
+ *      F = x0B + LB - x0A; 1 <= F <= max_insert gives insert_hist[F] += 1 (u64[max_insert + 1], accumulated, never zeroed), otherwise
+ *      discordant. u == v, sA != sB: discordant. u != v: d = (L_u - x0A) + (x0B + LB), the bases of the fragment that lie on the two
+ *      contigs if they were abutted; d > max_insert is discordant, and so is d < 1 (only hand-set steps reach it: a q_first beyond the
+ *      mate puts its end in front of the contig); otherwise the pair observes the link e -> t, e = 2 u + sA, t = 2 v + sB. Of (e, t) and its dual (t ^ 1, e ^ 1) the one with the smaller first word is stored (the canonical form).
+ *    Outputs obs_key u64[P] = e << 32 | t of the canonical form, all ones for a pair that is no observation; obs_d u32[P] (0 there);
+ *      counts u64[4] = {same contig, link, discordant, unanchored}, written, not accumulated. A pair and its reverse complement
+ *      (rc(B), rc(A)) give the same key and the same d whenever neither mate has two steps tied for the most windows.
+ *    Validation: seq_step_off starts at 0, ascends and ends at T; step_unitig < U; step_pos < m_u; q_first <= q_last; offsets ascend by at
+ *      least 23; d_offs ascends and every mate is shorter than 2^32 bytes. P == 0 is AIX_OK (counts all zero).
+ *
+ * 2. aix_mate_bundle_dev: N observations (a caller concatenates its batches) into the scaffold graph, a CSR over the 2 U ends:
+ *    slink_off u64[2 U + 1], slink_to u32[S], slink_count u64[S], slink_dsum u64[S]. One bundle per distinct key carries count and the
+ *    sum of d; every bundle is written twice, as e -> t in the list of e and as its dual in the list of t ^ 1, with equal count and dsum,
+ *    so S is twice the number of bundles. The list of an end ascends by target word and may be of any length. Sizing, as
+ *    aix_seq_hits_dev: slink_off and *total_out = S are always written, the entries only when S <= cap, never at or beyond cap (they
+ *    may be NULL when cap == 0); AIX_OK either way. Validation: every key is all ones (skipped) or canonical with both words below
+ *    2 U, on different contigs, and d >= 1. N == 0 gives slink_off all zero. N >= 2^32 is AIX_ERR_UNSUPPORTED (a bundle is named by
+ *    32 bits), in the host form too.
+ *
+ * 3. aix_scaffold_mark_dev: which ends are joined, one round, from the arrays alone. A link is a CANDIDATE iff count >= min_pairs (>= 1),
+ *    both its contigs are linear and both are at least min_contig_bases long. The BEST link of an end is its candidate with the largest
+ *    count, the smaller target word on a tie. An end is DECIDED iff it has a best link and every other candidate c at it has
+ *    count_c * dominance <= count_best (dominance >= 1; the product in 128 bits). e -> t is a JOIN iff it is the best link of a decided e
+ *    and its dual is the best link of a decided t ^ 1. Outputs join u32[2 U] (join[e] = t and join[t ^ 1] = e ^ 1, AIX_BUBBLE_NONE
+ *    elsewhere), join_count u64[2 U], join_gap i64[2 U] = insert_size - floor(dsum / count) (equal at both ends of a join, 0 elsewhere)
+ *    and the number of joins. Every end takes part in at most one join: the components are simple paths and simple cycles of contigs.
+ *    Validation: offsets ascend by at least 23; slink_off starts at 0, ascends and ends at S; words below 2 U; no link within one contig;
+ *    lists ascend strictly; count >= 1; floor(dsum / count) fits 32 bits; every link has its dual with equal count and dsum.
+ *
+ * 4. aix_scaffold_layout_dev ranks the ends by pointer jumping over `join`. What the ranking leaves open lies on cycles; a cycle is cut
+ *    at its join with the smallest min(count, 2^32 - 1) << 32 | min(e, t ^ 1) and then ranked as a path. The written gap of a join is
+ *    max(join_gap, min_gap), min_gap >= 1. Of a path's two terminal contigs the one with the smaller id comes first, oriented so that the
+ *    path leaves it; a single contig is forwards. Scaffold ids ascend by the id of the first member. Every contig belongs to exactly one
+ *    scaffold. Outputs contig_scaffold u32[U], contig_rank u32[U] (its index among the members), contig_pos u64[U] (the offset of its
+ *    first base in the scaffold), contig_flag u8[U] (bit 0: reversed), the number of scaffolds, their total bases, and the joins cut.
+ *    Validation: offsets; a join names an end of another contig below 2 U whose entry names it back, with equal count and gap.
+ *
+ *    aix_scaffold_emit_dev validates the map against join and the two sizes before anything is written: (scaffold, rank) are dense; a
+ *    member follows its predecessor through a join in matching orientation, at the distance of the predecessor's length and written
+ *    gap; the two outer ends of a scaffold are unjoined, or joined to each other (the cut of a cycle; that it was the weakest join is
+ *    the layout's affair and is not looked at again); first members obey the order rules above; the lengths sum to total_bases. It
+ *    writes scaffold_offsets u64[Sc + 1] and scaffold_bases (every member's oriented bases whole, a reversed member reverse-complemented
+ *    by the byte rule of the cleaning block, 'N' over the gaps), the member CSR member_off u64[Sc + 1] and member u32[U] (word
+ *    2 u + flag) and member_gap i64[U], the raw join_gap in front of the member, 0 for a first member. With no joins the scaffolds are
+ *    the contigs: the same bases, the same offsets, the identity map. U == 0 gives {0} for both offset arrays.
+ *
+ * The host form takes the contigs and N observations in host arrays, runs bundle, mark, layout and emit, and returns malloc'd arrays
+ * (aix_free); the last seven are nullable.
+ * ------------------------------------------------------------------------------------------ */
+int aix_mate_links_dev(uint64_t P, const uint64_t* d_offs, const uint64_t* d_seq_step_off, uint64_t T, const uint32_t* d_step_unitig,
+                       const uint32_t* d_step_pos, const uint8_t* d_step_flag, const uint32_t* d_q_first, const uint32_t* d_q_last, uint64_t U,
+                       const uint64_t* d_offsets, const uint8_t* d_circular, uint32_t min_anchor_windows, uint32_t max_insert,
+                       uint64_t* d_insert_hist, uint64_t* d_obs_key, uint32_t* d_obs_d, uint64_t* d_counts, void* stream);
+int aix_mate_bundle_dev(uint64_t N, const uint64_t* d_obs_key, const uint32_t* d_obs_d, uint64_t U, uint64_t* d_slink_off, uint32_t* d_slink_to,
+                        uint64_t* d_slink_count, uint64_t* d_slink_dsum, uint64_t cap, uint64_t* total_out, void* stream);
+int aix_scaffold_mark_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_circular, const uint64_t* d_slink_off, const uint32_t* d_slink_to,
+                          const uint64_t* d_slink_count, const uint64_t* d_slink_dsum, uint64_t S, uint32_t insert_size, uint64_t min_pairs,
+                          uint64_t dominance, uint64_t min_contig_bases, uint32_t* d_join, uint64_t* d_join_count, int64_t* d_join_gap,
+                          uint64_t* n_joins_out, void* stream);
+int aix_scaffold_layout_dev(uint64_t U, const uint64_t* d_offsets, const uint32_t* d_join, const uint64_t* d_join_count, const int64_t* d_join_gap,
+                            uint32_t min_gap, uint32_t* d_contig_scaffold, uint32_t* d_contig_rank, uint64_t* d_contig_pos, uint8_t* d_contig_flag,
+                            uint64_t* n_scaffolds_out, uint64_t* total_bases_out, uint64_t* n_cut_out, void* stream);
+/* Nothing is written at or beyond the sizes given. Input and output arrays must not overlap. Scratch: see DESIGN 5n. */
+int aix_scaffold_emit_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, const uint32_t* d_join, const int64_t* d_join_gap,
+                          uint32_t min_gap, const uint32_t* d_contig_scaffold, const uint32_t* d_contig_rank, const uint64_t* d_contig_pos,
+                          const uint8_t* d_contig_flag, uint64_t n_scaffolds, uint64_t total_bases, uint64_t* d_scaffold_offsets,
+                          uint8_t* d_scaffold_bases, uint64_t* d_member_off, uint32_t* d_member, int64_t* d_member_gap, void* stream);
+int aix_scaffold(uint64_t U, const uint64_t* offsets, const uint8_t* bases, const uint8_t* circular, uint64_t N, const uint64_t* obs_key,
+                 const uint32_t* obs_d, uint32_t insert_size, uint64_t min_pairs, uint64_t dominance, uint64_t min_contig_bases, uint32_t min_gap,
+                 uint64_t* n_scaffolds_out, uint64_t* n_joins_out, uint64_t* n_cut_out, uint64_t* n_slinks_out, uint64_t** scaffold_offsets_out,
+                 uint8_t** scaffold_bases_out, uint64_t** member_off_out, uint32_t** member_out, int64_t** member_gap_out,
+                 uint32_t** join_out /* nullable */, uint64_t** join_count_out /* nullable */, int64_t** join_gap_out /* nullable */,
+                 uint32_t** contig_scaffold_out /* nullable */, uint32_t** contig_rank_out /* nullable */, uint64_t** contig_pos_out /* nullable */,
+                 uint8_t** contig_flag_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
