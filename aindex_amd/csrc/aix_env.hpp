@@ -33,6 +33,7 @@
 //     AIX_LOOKUP_SLICE_BYTES       T/H 8 .. 2 MiB                    1 MiB  filter slice = one bin (small values: many bins on a tiny index)
 //     AIX_LOOKUP_PIECE             H   1 .. 2^27                     2^27   queries per piece
 //     AIX_LOOKUP_TEST_BIN_CAP      H   records                       -      capacity of a bin's region (forces the overflow route)
+//     AIX_LOOKUP_TEST_GRID_A       H   1 .. 768                      768    workgroups of pass A at most (many tiles per workgroup on a small batch)
 //     AIX_LOOKUP_TEST_GRID_B       H   1 .. 1024                     1024   workgroups of pass B at most (many tickets per workgroup on a small batch)
 //   per call, elsewhere
 //     AIX_DISTINCT_PIECE           H   1 .. 2^31                     2^30   windows per K1 piece (aix_merge.hip entry points, aix_count.hip, aix_ingest.hip)

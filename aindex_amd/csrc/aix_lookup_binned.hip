@@ -8,8 +8,15 @@
 //                 Jenkins hash: the filter is keyed by the code, aix_device.hpp); one 8-byte record per clean query,
 //                 counting-sorted by filter slice in LDS per 4096-query tile and flushed into 256-record chunks of a per-slice
 //                 region (chunks come from a per-slice cursor; a workgroup asks for all chunks of a tile and slice at once).
+//                 The flush writes whole 128-byte lines (LB_LINE = 16 records): what a slice's run leaves over stays in an LDS carry
+//                 (fewer than LB_LINE records per slice, 128 bytes of dynamic shared memory each) and goes in front of the slice's
+//                 run of the workgroup's next tile; the last tile writes everything. Chunks are 2 KiB and regions 256-byte
+//                 aligned, so a line never straddles chunks. One wave flushes a slice and advances its chunk, fill and counts;
+//                 nobody else touches them until the next tile's first barrier, so a tile has five barriers and none at its end.
+//                 LDS: 32 KiB of sorted records + 6 KiB of per-slice tables + the carry = 50 KiB at 96 slices (three workgroups
+//                 per CU), 70 KiB at 256 (two).
 //                 out[i] = 0 for every query. Queries with other bytes, and records whose slice region is full, go onto the
-//                 survivor list instead. A lane fetches a query's dwords one query before it encodes them (lb_fetch), encodes with
+//                 survivor list instead, appended by the wave that flushes them. A lane fetches a query's dwords one query before it encodes them (lb_fetch), encodes with
 //                 encode23_clean, finds the slice with a shift where the slice width is a power of two (the shipped 2^17 words is),
 //                 and the tile's zeros are written with 16-byte stores behind the query loop: 80 VGPRs, three workgroups per CU.
 //   k_lb_filter   pass B: chunks in slice order across the whole grid, so that the chip reads one or two slices (~1 MiB each)
@@ -31,8 +38,10 @@ static constexpr int LB_TB = 512;                      // threads of pass A
 static constexpr int LB_QPL = 8;                       // queries per lane and tile
 static constexpr int LB_TILE = LB_TB * LB_QPL;         // 4096 queries per tile: 32 KiB of records in LDS
 static constexpr int LB_CH = 256;                      // records per chunk (2 KiB)
+static constexpr int LB_LINE = 16;                     // records per 128-byte line: pass A writes whole lines and carries the rest of a slice's run
 static constexpr int LB_MAXBINS = 256;
-static constexpr unsigned LB_GRID_A = 768;             // three workgroups of pass A per CU (41 KiB of LDS each)
+static_assert(LB_CH % LB_LINE == 0 && LB_LINE <= 64, "lines do not straddle chunks; one wave instruction moves a carry");
+static constexpr unsigned LB_GRID_A = 768;             // three workgroups of pass A per CU (38 KiB of LDS each + 128 bytes per slice: 50 KiB at 96 slices)
 static constexpr int LB_FB = 512;                      // threads of pass B: a lane takes one record of each chunk group of a trip
 static constexpr int LB_CPG = LB_FB / LB_CH;           // chunks per chunk group: one record per lane
 static constexpr int LB_U = 2;                         // chunk groups per trip of a pass-B workgroup (independent loads)
@@ -194,15 +203,16 @@ __device__ __forceinline__ void lb_words(const LbRaw& r, uint32_t o, uint64_t& w
 __global__ void __launch_bounds__(LB_TB, 3 * LB_TB / 256) k_lb_bin(uint32_t nbloom, const uint8_t* __restrict__ q, uint32_t n, LbGeom g, LbWs w, uint32_t* __restrict__ out) {
     if (!w.hdr[LB_FLAG]) return;
     __shared__ uint64_t sorted[LB_TILE];
-    __shared__ uint16_t sbin[LB_TILE];
-    // per slice (entry nbins = the queries that go straight onto the survivor list): tile count, its exclusive scan, the chunk being filled
-    // and its fill, the first fresh chunk of this tile
-    __shared__ uint32_t hist[LB_MAXBINS + 1], loc_off[LB_MAXBINS + 1], cur_chunk[LB_MAXBINS + 1], cur_fill[LB_MAXBINS + 1], fresh[LB_MAXBINS + 1];
+    extern __shared__ __attribute__((aligned(16))) uint64_t carry[];   // [nbins][LB_LINE]: the records of a slice that do not fill a line yet
+    // per slice (entry nbins = the queries that go straight onto the survivor list): tile count, its exclusive scan (entry nbins + 1 =
+    // the tile's queries), the chunk being filled and its fill (a multiple of LB_LINE before the last tile), the first fresh chunk of
+    // this tile, the records carried
+    __shared__ uint32_t hist[LB_MAXBINS + 1], loc_off[LB_MAXBINS + 2], cur_chunk[LB_MAXBINS], cur_fill[LB_MAXBINS], fresh[LB_MAXBINS], carry_n[LB_MAXBINS];
     __shared__ uint32_t wsum[LB_TB / 64];
-    __shared__ uint32_t s_ov, s_ov_real, s_ov_rank, s_ov_base;
     const uint32_t t = threadIdx.x, NB = g.nbins;
     uint32_t* const cursor = w.hdr + LB_CURSOR;
-    if (t <= NB) { hist[t] = 0; cur_chunk[t] = LB_NONE; cur_fill[t] = LB_CH; fresh[t] = 0; }
+    if (t <= NB) hist[t] = 0;
+    if (t < NB) { cur_chunk[t] = LB_NONE; cur_fill[t] = LB_CH; fresh[t] = 0; carry_n[t] = 0; }
     __syncthreads();
     const uint32_t ntiles = (n + LB_TILE - 1) / LB_TILE;
     const uint32_t qo = (uint32_t)((uintptr_t)q & 3);
@@ -262,12 +272,18 @@ __global__ void __launch_bounds__(LB_TB, 3 * LB_TB / 256) k_lb_bin(uint32_t nblo
             if (t < tail) o0[head + 4 * nvec + t] = 0;
         }
         __syncthreads();
+        // the workgroup's last tile writes everything; before it only whole lines leave, and the rest of a slice's run stays in `carry`
+        const bool last = tile + gridDim.x >= ntiles;
         const uint32_t a = t <= NB ? hist[t] : 0u;
+        if (t <= NB) hist[t] = 0;                                // the next tile's counting starts behind four more barriers
         uint32_t all;
         const uint32_t excl = lb_scan_excl<LB_TB>(a, wsum, all);
         if (t <= NB) loc_off[t] = excl;
-        if (t < NB && cur_fill[t] + a > (uint32_t)LB_CH) fresh[t] = atomicAdd(&cursor[t], (cur_fill[t] + a - 1) / LB_CH);
-        if (t == 0) { s_ov = 0; s_ov_real = 0; s_ov_rank = 0; }
+        if (t == 0) loc_off[NB + 1] = all;
+        if (t < NB) {
+            const uint32_t tot = carry_n[t] + a, full = last ? tot : tot & ~(uint32_t)(LB_LINE - 1);
+            if (cur_fill[t] + full > (uint32_t)LB_CH) fresh[t] = atomicAdd(&cursor[t], (cur_fill[t] + full - 1) / LB_CH);
+        }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < LB_QPL; ++j) {
@@ -275,73 +291,74 @@ __global__ void __launch_bounds__(LB_TB, 3 * LB_TB / 256) k_lb_bin(uint32_t nblo
                 const uint32_t bin = meta[j] & ((1u << LB_META_LO) - 1), p = loc_off[bin] + (meta[j] >> 16);
                 const uint32_t lo = (base + j * LB_TB + t) | (((meta[j] >> LB_META_LO) & ((1u << LB_LO_BITS) - 1)) << LB_IDX_BITS);
                 sorted[p] = lo | ((uint64_t)rec_hi[j] << 32);
-                sbin[p] = (uint16_t)bin;
             }
         }
         __syncthreads();
-        // flush: runs of one slice are contiguous in `sorted` and land contiguously in the slice's chunks
-        for (uint32_t i0 = t & ~63u; i0 < in_tile; i0 += LB_TB) {
-            const uint32_t i = i0 + (t & 63u);
-            bool ov = false, real = false;
-            if (i < in_tile) {
-                const uint32_t bin = sbin[i];
-                ov = true;
-                if (bin < NB) {
-                    uint32_t chunk, o;
-                    lb_place(cur_fill[bin], cur_chunk[bin], fresh[bin], i - loc_off[bin], chunk, o);
-                    if (chunk < g.cap) { w.rec[((uint64_t)bin * g.cap + chunk) * LB_CH + o] = sorted[i]; ov = false; }
-                    real = ov;
+        // flush: wave v takes slices v, v + LB_TB / 64, ... A slice's run is its carry followed by its records of this tile (contiguous
+        // in `sorted`); it lands contiguously behind the slice's fill, which is a multiple of LB_LINE, so every store instruction
+        // writes whole 128-byte lines (a chunk is 2 KiB, a region 256-byte aligned). Only this wave touches the slice's carry, chunk and
+        // fill here, and thread `bin` reads them again behind the next tile's first barrier: no barrier at the end of a tile.
+        const uint32_t lane = t & 63u;
+        for (uint32_t b = __builtin_amdgcn_readfirstlane(t >> 6); b <= NB; b += LB_TB / 64) {
+            const uint32_t off = loc_off[b], cnt_b = loc_off[b + 1] - off;
+            if (b == NB) {                                       // other bytes (rare): straight onto the survivor list
+                if (cnt_b) {
+                    uint32_t s0 = 0;
+                    if (lane == 0) s0 = atomicAdd(&w.hdr[LB_NSURV], cnt_b);
+                    s0 = __shfl(s0, 0);
+                    for (uint32_t p = lane; p < cnt_b; p += 64) w.list[s0 + p] = (uint32_t)sorted[off + p] & ((1u << LB_IDX_BITS) - 1);
                 }
+                break;
             }
-            const uint32_t n_ov = (uint32_t)__popcll(__ballot(ov)), n_real = (uint32_t)__popcll(__ballot(real));
-            if ((t & 63u) == 0 && n_ov) { atomicAdd(&s_ov, n_ov); if (n_real) atomicAdd(&s_ov_real, n_real); }
-        }
-        __syncthreads();
-        if (s_ov) {                                              // rare: other bytes, or a slice region that is full -> survivor list
-            if (t == 0) {
-                s_ov_base = atomicAdd(&w.hdr[LB_NSURV], s_ov);
-                if (s_ov_real) atomicAdd(&w.stats[2], (unsigned long long)s_ov_real);
-            }
-            __syncthreads();
-            for (uint32_t i0 = t & ~63u; i0 < in_tile; i0 += LB_TB) {
-                const uint32_t i = i0 + (t & 63u);
+            const uint32_t c = carry_n[b], tot = c + cnt_b, full = last ? tot : tot & ~(uint32_t)(LB_LINE - 1);
+            const uint32_t f = cur_fill[b], cur = cur_chunk[b], nb = fresh[b];
+            uint64_t* const cy = carry + b * LB_LINE;
+            for (uint32_t p0 = 0; p0 < full; p0 += 64) {
+                const uint32_t p = p0 + lane;
                 bool ov = false;
-                if (i < in_tile) {
-                    const uint32_t bin = sbin[i];
-                    ov = true;
-                    if (bin < NB) {
-                        uint32_t chunk, o;
-                        lb_place(cur_fill[bin], cur_chunk[bin], fresh[bin], i - loc_off[bin], chunk, o);
-                        ov = chunk >= g.cap;
-                    }
+                uint64_t r = 0;
+                if (p < full) {
+                    r = p < c ? cy[p] : sorted[off + (p - c)];
+                    uint32_t chunk, o;
+                    lb_place(f, cur, nb, p, chunk, o);
+                    if (chunk < g.cap) w.rec[((uint64_t)b * g.cap + chunk) * LB_CH + o] = r;
+                    else ov = true;
                 }
                 const uint64_t m = __ballot(ov);
-                if (m) {
-                    uint32_t r0 = 0;
-                    if ((t & 63u) == 0) r0 = atomicAdd(&s_ov_rank, (uint32_t)__popcll(m));
-                    r0 = __shfl(r0, 0);
-                    if (ov) w.list[s_ov_base + r0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint32_t)sorted[i] & ((1u << LB_IDX_BITS) - 1);
+                if (m) {                                         // rare: the slice's region is full -> survivor list
+                    uint32_t s0 = 0;
+                    if (lane == 0) {
+                        s0 = atomicAdd(&w.hdr[LB_NSURV], (uint32_t)__popcll(m));
+                        atomicAdd(&w.stats[2], (unsigned long long)__popcll(m));
+                    }
+                    s0 = __shfl(s0, 0);
+                    if (ov) w.list[s0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint32_t)r & ((1u << LB_IDX_BITS) - 1);
                 }
             }
-        }
-        __syncthreads();
-        if (t < NB && a) {                                       // advance this slice's chunk; a chunk's count is written when the workgroup leaves it
-            const uint32_t tot = cur_fill[t] + a;
-            if (tot > (uint32_t)LB_CH) {
-                const uint32_t k = (tot - 1) / LB_CH, nb = fresh[t], old = cur_chunk[t];
-                uint32_t* const cnt = w.cnt + (uint64_t)t * g.cap;
-                if (old < g.cap) cnt[old] = LB_CH;
-                for (uint32_t u = 0; u + 1 < k; ++u) if (nb + u < g.cap) cnt[nb + u] = LB_CH;
-                cur_chunk[t] = nb + k - 1;
-                cur_fill[t] = tot - k * LB_CH;
-            } else {
-                cur_fill[t] = tot;
+            // what is left becomes the carry. full == 0: the old carry stays and the tile's records follow it; otherwise all of it comes
+            // from `sorted` (p >= full >= LB_LINE > c), and the wave has read the old carry above
+            if (lane < tot - full) {
+                const uint32_t p = full + lane;
+                if (p >= c) cy[p - full] = sorted[off + (p - c)];
+            }
+            // advance the slice's chunk; a chunk's count is written when the workgroup leaves it
+            uint32_t n_chunk = cur, n_fill = f + full;
+            uint32_t* const cnt = w.cnt + (uint64_t)b * g.cap;
+            if (n_fill > (uint32_t)LB_CH) {
+                const uint32_t k = (n_fill - 1) / LB_CH;
+                if (lane == 0 && cur < g.cap) cnt[cur] = LB_CH;
+                for (uint32_t u = lane; u + 1 < k; u += 64) if (nb + u < g.cap) cnt[nb + u] = LB_CH;
+                n_chunk = nb + k - 1;
+                n_fill -= k * LB_CH;
+            }
+            if (lane == 0) {
+                carry_n[b] = tot - full;
+                cur_chunk[b] = n_chunk;
+                cur_fill[b] = n_fill;
+                if (last && n_chunk < g.cap) cnt[n_chunk] = n_fill;
             }
         }
-        if (t <= NB) hist[t] = 0;
-        __syncthreads();
     }
-    if (t < NB && cur_chunk[t] < g.cap) w.cnt[(uint64_t)t * g.cap + cur_chunk[t]] = cur_fill[t];
 }
 
 __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict__ bloom, uint32_t nbloom, LbGeom g, LbWs w) {
@@ -445,7 +462,9 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     g.inv = g.wps > 1 ? (uint32_t)((1ull << 32) / g.wps) : 0xFFFFFFFFu;
     g.shift = (g.wps & (g.wps - 1)) == 0 ? (uint32_t)__builtin_ctz(g.wps) : LB_NO_SHIFT;
     const uint64_t piece = std::min<uint64_t>(std::min<uint64_t>(N, 1ull << LB_IDX_BITS), env_u64("AIX_LOOKUP_PIECE", 1, 1ull << LB_IDX_BITS, 1ull << LB_IDX_BITS));
-    const unsigned grid_a = (unsigned)std::min<uint64_t>((piece + LB_TILE - 1) / LB_TILE, LB_GRID_A);
+    const uint64_t test_grid_a = env_u64("AIX_LOOKUP_TEST_GRID_A", 1, LB_GRID_A, LB_GRID_A);   // fewer workgroups: many tiles each on a small batch
+    const unsigned grid_a = (unsigned)std::min<uint64_t>((piece + LB_TILE - 1) / LB_TILE, test_grid_a);
+    const uint32_t carry_bytes = g.nbins * LB_LINE * 8;
     // a slice region: its share of a uniformly hashed piece plus a quarter, plus the chunk every pass-A workgroup leaves partly filled
     const uint64_t test_cap = env_u64("AIX_LOOKUP_TEST_BIN_CAP", 0, ~0ull, ~0ull);
     uint64_t cap = test_cap != ~0ull ? (test_cap + LB_CH - 1) / LB_CH : (piece + piece / 4) / g.nbins / LB_CH + 2 + grid_a;
@@ -474,6 +493,8 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
         ~RecordOnExit() { (void)hipEventRecord(ev, s); }
     } record_on_exit{h->lb_done, s};
 
+    // pass A's static LDS is 38 KiB: with the carry of more than 128 slices it may pass 64 KiB (two workgroups per CU then)
+    if (carry_bytes > (16u << 10)) HIPCHK(hipFuncSetAttribute((const void*)k_lb_bin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)carry_bytes));
     uint8_t* const base = (uint8_t*)h->lb_ws;
     LbWs w;
     w.hdr = (uint32_t*)base;
@@ -493,7 +514,7 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
                            w.stats);
         HIPCHK(hipGetLastError());
         if (sw != 2) HIPCHK(launch_lookup23_ascii(d, qp, m, MODE_TF, LookupOut{op, nullptr, nullptr, nullptr}, s, w.hdr + LB_FLAG));
-        hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), 0, s, d.nbloom, qp, m, g, w, op);
+        hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), carry_bytes, s, d.nbloom, qp, m, g, w, op);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
         HIPCHK(hipGetLastError());
