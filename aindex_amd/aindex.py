@@ -806,8 +806,9 @@ class AIndex:
         return g
 
     def _scaffolds(self, pairs, insert_size, max_insert, min_anchor_windows, min_pairs, dominance, min_contig_bases, min_gap, cutoff, tip_max_kmers,
-                   bubble_max_kmers, rounds, resolve) -> dict:
-        """numpy arrays: the scaffolds (Index.scaffold_t), the joins, and the contigs' offsets"""
+                   bubble_max_kmers, rounds, resolve, close_gaps=False, gap_tolerance=50, max_fill=16, max_fill_states=1024, drop_absorbed=True) -> dict:
+        """numpy arrays: the scaffolds (Index.scaffold_t), the joins, and the contigs' offsets; with close_gaps the closure
+        (Index.gap_close_t) and the filled scaffolds (Index.scaffold_fill_t) too"""
         import torch
         ix = self._wrapper._need23()
         pairs = self._pairs(pairs)
@@ -827,19 +828,41 @@ class AIndex:
         slinks = ix.mate_bundle_t(key, d, int(graph["U"]), cap_hint=2 * key.numel())      # S <= 2 N: one pass, no sizing pass
         joins = ix.scaffold_mark_t(graph, slinks, insert_size, min_pairs, dominance, min_contig_bases)
         sc = ix.scaffold_t(graph, joins, min_gap)
-        out = ix._graph_to_host({k: v for k, v in {**joins, **sc, "offsets": graph["offsets"]}.items() if hasattr(v, "cpu")})
+        more = {}
+        if close_gaps:
+            closure = ix.gap_close_t(graph, joins, gap_tolerance, max_fill, max_fill_states, cap_hint=int(graph["U"]))   # room for a fill per contig: mostly one pass
+            more = {**closure, **ix.scaffold_fill_t(graph, joins, sc, closure, min_gap)}
+        out = ix._graph_to_host({k: v for k, v in {**joins, **sc, **more, "offsets": graph["offsets"]}.items() if hasattr(v, "cpu")})
         out.update(insert_size=insert_size, n_scaffolds=sc["n_scaffolds"], n_joins=joins["n_joins"], n_cut=sc["n_cut"])
+        if close_gaps:
+            out["close_counts"] = more["counts"]
         return out
+
+    @staticmethod
+    def _kept(s, drop_absorbed: bool) -> list:
+        """the filled scaffolds that are written: with drop_absorbed, not a single contig that fills a closed gap elsewhere"""
+        fo, fm, uses = s["fmember_off"].tolist(), s["fmember"], s["fill_uses"]
+        return [i for i in range(len(fo) - 1) if not (drop_absorbed and fo[i + 1] - fo[i] == 1 and uses[int(fm[fo[i]]) >> 1] >= 1)]
 
     def get_scaffolds(self, pairs=None, insert_size: Optional[int] = None, max_insert: int = 1000, min_anchor_windows: int = 1, min_pairs: int = 2,
                       dominance: int = 2, min_contig_bases: int = 0, min_gap: int = 1, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46,
-                      rounds: int = 3, resolve: bool = False) -> List[Tuple[str, List[tuple]]]:
+                      rounds: int = 3, resolve: bool = False, close_gaps: bool = False, gap_tolerance: int = 50, max_fill: int = 16,
+                      max_fill_states: int = 1024, drop_absorbed: bool = True) -> List[Tuple[str, List[tuple]]]:
         """Contigs joined by read pairs: [(sequence, [(contig, '+' | '-', gap)])], the gap in front of the member (0 for the first) as
         estimated, 'N' runs of max(gap, min_gap) in the sequence. pairs: [(left, right)] or lines `left~right`, both mates on the
         fragment's strand as a reads file holds them; None: the loaded reads file. insert_size None: the median of the pairs that lie
-        within one contig."""
+        within one contig.
+        close_gaps: every join with exactly one path of the estimated length (within gap_tolerance) through at most max_fill unjoined
+        contigs of the graph, found within max_fill_states search states, is written with the bases of that path in place of its 'N'
+        run. The members are then (contig, strand, gap, kind) with kind "member" or "fill", the gap -22 for a member that overlaps its
+        predecessor by 22 bases; with drop_absorbed a single-contig scaffold whose contig fills a gap is left out."""
         s = self._scaffolds(pairs, insert_size, max_insert, min_anchor_windows, min_pairs, dominance, min_contig_bases, min_gap, cutoff, tip_max_kmers,
-                            bubble_max_kmers, rounds, resolve)
+                            bubble_max_kmers, rounds, resolve, close_gaps, gap_tolerance, max_fill, max_fill_states, drop_absorbed)
+        if close_gaps:
+            text, so, fo = s["fscaffold_bases"].tobytes().decode("ascii"), s["fscaffold_offsets"].tolist(), s["fmember_off"].tolist()
+            mem, flag, gap = s["fmember"].tolist(), s["fmember_flag"].tolist(), s["fmember_gap"].view(np.int64).tolist()
+            return [(text[so[i]:so[i + 1]], [(mem[j] >> 1, "+-"[mem[j] & 1], -22 if flag[j] & 1 else gap[j], "fill" if flag[j] & 2 else "member")
+                                             for j in range(fo[i], fo[i + 1])]) for i in self._kept(s, drop_absorbed)]
         text, so, mo = s["scaffold_bases"].tobytes().decode("ascii"), s["scaffold_offsets"].tolist(), s["member_off"].tolist()
         mem, gap = s["member"].tolist(), s["member_gap"].view(np.int64).tolist()
         return [(text[so[i]:so[i + 1]], [(w >> 1, "+-"[w & 1], g) for w, g in zip(mem[mo[i]:mo[i + 1]], gap[mo[i]:mo[i + 1]])]) for i in range(len(so) - 1)]
@@ -854,11 +877,30 @@ class AIndex:
 
     def write_scaffolds_agp(self, path: str, pairs=None, **kw) -> int:
         """AGP 2.0 of the scaffolds: a W line per member (component c<contig>, whole, with its orientation) and an N line per gap
-        (scaffold, linkage yes, paired-ends); returns the number of lines written. The arguments and defaults are get_scaffolds's."""
+        (scaffold, linkage yes, paired-ends); returns the number of lines written. The arguments and defaults are get_scaffolds's.
+        With close_gaps a member that overlaps its predecessor is a W line over its component bases 23 .. L, with no N line."""
         import inspect
         args = inspect.signature(self.get_scaffolds).bind(pairs, **kw)     # a TypeError for a name get_scaffolds does not take
         args.apply_defaults()
         s, min_gap = self._scaffolds(**args.arguments), args.arguments["min_gap"]
+        if args.arguments["close_gaps"]:
+            off, fo, mem = s["offsets"].tolist(), s["fmember_off"].tolist(), s["fmember"].tolist()
+            flag, gap = s["fmember_flag"].tolist(), s["fmember_gap"].view(np.int64).tolist()
+            lines = 0
+            with open(path, "w") as f:
+                f.write("##agp-version 2.0\n")
+                for i, sc in enumerate(self._kept(s, args.arguments["drop_absorbed"])):
+                    at, part = 1, 1
+                    for j in range(fo[sc], fo[sc + 1]):
+                        if j > fo[sc] and not flag[j] & 1:
+                            n = max(gap[j], min_gap)
+                            f.write(f"s{i}\t{at}\t{at + n - 1}\t{part}\tN\t{n}\tscaffold\tyes\tpaired-ends\n")
+                            at, part, lines = at + n, part + 1, lines + 1
+                        u = mem[j] >> 1
+                        ln, skip = off[u + 1] - off[u], 22 * (flag[j] & 1)
+                        f.write(f"s{i}\t{at}\t{at + ln - skip - 1}\t{part}\tW\tc{u}\t{skip + 1}\t{ln}\t{'+-'[mem[j] & 1]}\n")
+                        at, part, lines = at + ln - skip, part + 1, lines + 1
+            return lines
         off, mo, mem, gap = s["offsets"].tolist(), s["member_off"].tolist(), s["member"].tolist(), s["member_gap"].view(np.int64).tolist()
         lines = 0
         with open(path, "w") as f:
@@ -875,6 +917,19 @@ class AIndex:
                     f.write(f"s{i}\t{at}\t{at + ln - 1}\t{part}\tW\tc{u}\t1\t{ln}\t{'+-'[mem[j] & 1]}\n")
                     at, part, lines = at + ln, part + 1, lines + 1
         return lines
+
+    def get_gap_closures(self, pairs=None, **kw) -> List[tuple]:
+        """One record (e, t, gap, status, dist, [path words], states) per join of the scaffolds, e its owner end (e < t ^ 1): the
+        estimated gap, "closed" | "no_path" | "ambiguous" | "exhausted", the length of the path (0 unless closed), the intermediates in
+        order from e to t, and the search states stored. The arguments and defaults are get_scaffolds's (close_gaps is implied)."""
+        import inspect
+        from .engine import Index
+        args = inspect.signature(self.get_scaffolds).bind(pairs, **kw)
+        args.apply_defaults()
+        s = self._scaffolds(**dict(args.arguments, close_gaps=True))
+        jn, jg, st = s["join"].tolist(), s["join_gap"].view(np.int64).tolist(), s["close_status"].tolist()
+        dist, ns, po, path = s["close_dist"].view(np.int64).tolist(), s["close_states"].tolist(), s["path_off"].tolist(), s["path"].tolist()
+        return [(e, t, jg[e], Index.CLOSE_STATUS[st[e]], dist[e], path[po[e]:po[e + 1]], ns[e]) for e, t in enumerate(jn) if t != 0xFFFFFFFF and e < t ^ 1]
 
     # ---- read cleaning (Index.fix_reads; the scaffolding of read.hpp:36-117, :286-343) -----------------
     def correct_reads(self, reads: List[str], true_errors: int = 1, verify: int = 8, max_fixes: int = 4):

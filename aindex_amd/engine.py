@@ -1365,6 +1365,103 @@ class Index:
         out.update(n_scaffolds=sc, n_joins=n[1].value, n_cut=n[2].value, S=n[3].value, total_bases=int(so[sc]))
         return out
 
+    # ---- gap closing (aix_gapclose.hip) --------------------------------------------------------------
+    CLOSE_STATUS = ("none", "closed", "no_path", "ambiguous", "exhausted")
+
+    def _gap_graph(self, graph: dict, joins: dict):
+        off, lo, lt, jn, jg = graph["offsets"], graph["link_off"], graph["link_to"], joins["join"], joins["join_gap"]
+        for t in (off, lo, lt, jn, jg):
+            self._chk_dev(t)
+        u = off.numel() - 1
+        if u < 0 or lo.numel() != 2 * u + 1 or jn.numel() != 2 * u or jg.numel() != 2 * u:
+            raise ValueError("a graph holds U + 1 offsets and 2 U + 1 link offsets, the joins 2 U entries per array")
+        return off, lo, lt, jn, jg, u
+
+    def gap_close_t(self, graph: dict, joins: dict, tolerance: int = 50, max_fill: int = 16, max_states: int = 1024, cap_hint: int = 0) -> dict:
+        """One bounded path search per join of `joins` (what scaffold_mark_t returned) through `graph` (offsets, link_off, link_to):
+        close_status uint8[2 U] (see CLOSE_STATUS), close_dist int64[2 U], close_states int32[2 U], path_off int64[2 U + 1], path
+        int32[total] (the intermediates of every closed join, at its owner end), fill_uses int32[U], counts (ints: joins of status 1 .. 4
+        and the joins) and the int total. cap_hint: the path entries to make room for at once; below the total the call runs twice."""
+        import torch
+        off, lo, lt, jn, jg, u = self._gap_graph(graph, joins)
+        dev = off.device
+        st = torch.empty(2 * u, dtype=torch.uint8, device=dev)
+        dist = torch.empty(2 * u, dtype=torch.int64, device=dev)
+        ns = torch.empty(2 * u, dtype=torch.int32, device=dev)
+        po = torch.empty(2 * u + 1, dtype=torch.int64, device=dev)
+        uses = torch.empty(u, dtype=torch.int32, device=dev)
+        counts = torch.empty(5, dtype=torch.int64, device=dev)
+        total = C.c_uint64()
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            cap = max(int(cap_hint), 0)
+            while True:
+                path = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+                check(lib().aix_gap_close_dev(u, p(off), p(lo), p(lt), lt.numel(), p(jn), p(jg), tolerance, max_fill, max_states, p(st), p(dist), p(ns), p(po),
+                                              p(path) if cap else None, cap, C.byref(total), p(uses), p(counts), _stream_ptr(self.device)), "aix_gap_close_dev")
+                if total.value <= cap:
+                    break
+                cap = total.value
+        return {"close_status": st, "close_dist": dist, "close_states": ns, "path_off": po, "path": path[:total.value], "fill_uses": uses,
+                "counts": [int(x) for x in counts.tolist()], "total": total.value}
+
+    def scaffold_fill_t(self, graph: dict, joins: dict, scaffolds: dict, closure: dict, min_gap: int = 1) -> dict:
+        """The filled scaffolds of `scaffolds` (what scaffold_t returned for `graph` and `joins`) under `closure` (what gap_close_t
+        returned): fmember_off int64[Sc + 1], fmember int32[Mf], fmember_flag uint8[Mf] (bit 0: overlaps its predecessor by 22 bases, bit 1:
+        a fill contig), fmember_gap and fmember_pos int64[Mf], fscaffold_offsets int64[Sc + 1], fscaffold_bases uint8 and the ints
+        n_fmembers, total_bases."""
+        import torch
+        off, lo, lt, jn, jg, u = self._gap_graph(graph, joins)
+        bases, mo, mm = graph["bases"], scaffolds["member_off"], scaffolds["member"]
+        cs, cd, po, pa = closure["close_status"], closure["close_dist"], closure["path_off"], closure["path"]
+        for t in (bases, mo, mm, cs, cd, po, pa):
+            self._chk_dev(t)
+        sc, pt = mo.numel() - 1, pa.numel()
+        if sc < 0 or mm.numel() != u or cs.numel() != 2 * u or cd.numel() != 2 * u or po.numel() != 2 * u + 1:
+            raise ValueError("the member CSR holds Sc + 1 offsets and U members, the closure 2 U entries per array and 2 U + 1 path offsets")
+        dev = off.device
+        fo, so = torch.empty(sc + 1, dtype=torch.int64, device=dev), torch.empty(sc + 1, dtype=torch.int64, device=dev)
+        fm = torch.empty(u + pt, dtype=torch.int32, device=dev)
+        ff = torch.empty(u + pt, dtype=torch.uint8, device=dev)
+        fg, fp = torch.empty(u + pt, dtype=torch.int64, device=dev), torch.empty(u + pt, dtype=torch.int64, device=dev)
+        n = [C.c_uint64(), C.c_uint64()]
+        p = lambda t: vp(t.data_ptr())
+        with torch.cuda.device(self.device):
+            check(lib().aix_scaffold_fill_layout_dev(u, p(off), p(lo), p(lt), lt.numel(), p(jn), p(jg), min_gap, sc, p(mo), p(mm), p(cs), p(cd), p(po),
+                                                     p(pa) if pt else None, pt, p(fo), p(fm), p(ff), p(fg), p(fp), p(so), C.byref(n[0]), C.byref(n[1]),
+                                                     _stream_ptr(self.device)), "aix_scaffold_fill_layout_dev")
+            mf, total = n[0].value, n[1].value
+            sb = torch.empty(total, dtype=torch.uint8, device=dev)
+            check(lib().aix_scaffold_fill_emit_dev(u, p(off), p(bases), min_gap, sc, p(fo), mf, p(fm), p(ff), p(fg), p(fp), p(so), total, p(sb),
+                                                   _stream_ptr(self.device)), "aix_scaffold_fill_emit_dev")
+        return {"fmember_off": fo, "fmember": fm[:mf], "fmember_flag": ff[:mf], "fmember_gap": fg[:mf], "fmember_pos": fp[:mf], "fscaffold_offsets": so,
+                "fscaffold_bases": sb, "n_fmembers": mf, "total_bases": total}
+
+    def scaffold_fill(self, offsets, bases, link_off, link_to, join, join_gap, member_off, member, tolerance: int = 50, max_fill: int = 16,
+                      max_states: int = 1024, min_gap: int = 1) -> dict:
+        """Search, layout and emit through host memory (aix_scaffold_fill): numpy arrays in (the contigs, their links, the joins and the
+        member CSR), numpy arrays out — the closure of gap_close_t and the filled arrays of scaffold_fill_t, with the ints n_fmembers,
+        total_bases, total (path entries) and counts (a list)."""
+        types = (np.uint64, np.uint8, np.uint64, np.uint32, np.uint32, np.int64, np.uint64, np.uint32)
+        a = [np.ascontiguousarray(x, dtype=dt) for x, dt in zip((offsets, bases, link_off, link_to, join, join_gap, member_off, member), types)]
+        u, e, sc = a[0].shape[0] - 1, a[3].shape[0], a[6].shape[0] - 1
+        if u < 0 or sc < 0 or a[2].shape[0] != 2 * u + 1 or a[4].shape[0] != 2 * u or a[5].shape[0] != 2 * u or a[7].shape[0] != u or (u and a[1].shape[0] != int(a[0][u])):
+            raise ValueError("contigs hold U + 1 offsets and offsets[U] bases, the links 2 U + 1 offsets, the joins 2 U entries, the members Sc + 1 offsets and U words")
+        ps = [vp() for _ in range(14)]
+        n = [C.c_uint64() for _ in range(3)]
+        ptr = lambda x: _np_ptr(x) if x.shape[0] else None
+        with self._device_ctx():
+            check(lib().aix_scaffold_fill(u, _np_ptr(a[0]), ptr(a[1]), _np_ptr(a[2]), ptr(a[3]), e, ptr(a[4]), ptr(a[5]), sc, _np_ptr(a[6]), ptr(a[7]), tolerance,
+                                          max_fill, max_states, min_gap, *[C.byref(x) for x in n], *[C.byref(x) for x in ps]), "aix_scaffold_fill")
+        mf, total, pt = (x.value for x in n)
+        names = ("fscaffold_offsets", "fscaffold_bases", "fmember_off", "fmember", "fmember_flag", "fmember_gap", "fmember_pos", "close_status", "close_dist",
+                 "close_states", "path_off", "path", "fill_uses", "counts")
+        sizes = (sc + 1, total, sc + 1, mf, mf, mf, mf, 2 * u, 2 * u, 2 * u, 2 * u + 1, pt, u, 5)
+        types = (np.uint64, np.uint8, np.uint64, np.uint32, np.uint8, np.int64, np.uint64, np.uint8, np.int64, np.uint32, np.uint64, np.uint32, np.uint32, np.uint64)
+        out = {k: self._take_as(q, s, t) for k, q, s, t in zip(names, ps, sizes, types)}
+        out.update(n_fmembers=mf, total_bases=total, total=pt, counts=[int(x) for x in out["counts"]])
+        return out
+
     def _device_ctx(self):
         """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
         import contextlib

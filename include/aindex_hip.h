@@ -994,6 +994,91 @@ int aix_scaffold(uint64_t U, const uint64_t* offsets, const uint8_t* bases, cons
                  uint8_t** contig_flag_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Gap closing: the 'N' run of a join is replaced by the bases of a path through the contig graph, where exactly one path of the
+ * estimated length exists.
+ * (The reference has no counterpart; the notation is that of the scaffolding block. tests/gap_close_ref.py restates this block.)
+ *
+ * L_w is the length of the contig of word w; the exit end of a contig entered as word w is w itself; the dual of e -> t is
+ * t ^ 1 -> e ^ 1. No call takes an index handle: they work on device arrays of the current device, are asynchronous on `stream` and
+ * return after their work on it has completed. Every call validates first and writes second: a violation is AIX_ERR_ARG with no
+ * output touched. Every index read from an input array is checked against its bound before it is used. U > 2^31 - 4 is
+ * AIX_ERR_UNSUPPORTED, a NULL pointer where one is needed AIX_ERR_ARG, decided before anything is allocated or launched. Scratch comes
+ * from the pool and goes back on every path. Integer only; no result depends on the launch geometry.
+ *
+ * 1. aix_gap_close_dev: the search. Inputs U, offsets[U + 1], link_off[2 U + 1], link_to[E] (the graph the pairs were threaded through;
+ *    a list may be of any length, and the graph need not be dual-closed), join u32[2 U] and join_gap i64[2 U] of
+ *    aix_scaffold_mark_dev, tolerance (0 .. 2^20), max_fill (0 .. 64), max_states (1 .. 4096), and cap for the path array.
+ *    The OWNER of a join e -> t is its end e with e < (t ^ 1); the search runs once per join, from the owner, with g = join_gap[e].
+ *    Rule. A candidate is (w, d, k): w a word, d (signed) the bases between the last base of e's contig and the first base of w, k the
+ *      number of intermediates before w. The first candidates are (x, -22, 0) for every link x of end e. A candidate with w == t becomes
+ *      a stored state, a HIT, iff |d - g| <= tolerance; it is never expanded. A candidate with w != t becomes a stored state, an
+ *      INTERMEDIATE, iff k < max_fill, both join entries of w's contig are none (a fill goes only through contigs the scaffolder left
+ *      single) and d + L_w - 22 <= g + tolerance. The children of an intermediate are (y, d + L_w - 22, k + 1) for every link y of end
+ *      w. A contig may recur on a path, so a tandem repeat is counted out by length. The set of states, and therefore every output, is
+ *      independent of the order in which candidates are examined.
+ *    Status per join, equal at both its ends, 0 on unjoined ends: 4 exhausted (the complete search would store more than max_states
+ *      states, whatever hits it saw), else 2 no hit, 3 ambiguous (two or more hits), 1 closed (exactly one hit).
+ *    Outputs close_status u8[2 U]; close_dist i64[2 U], the hit's d at both ends when closed, else 0; close_states u32[2 U], the states
+ *      stored, max_states when exhausted, at both ends; path_off u64[2 U + 1] and path u32[cap], a CSR keyed by end that is non-empty
+ *      only at the owner of a closed join and holds the intermediates in order from e to t; fill_uses u32[U], the closed joins that pass
+ *      through each contig, once per occurrence; counts u64[5] = joins of status 1 .. 4 and the number of joins, written, not
+ *      accumulated. Sizing, as aix_mate_bundle_dev: path_off and *total_out are always written, the entries only when the total <= cap,
+ *      never at or beyond cap (path may be NULL when cap == 0); AIX_OK either way. U == 0 and "no joins" are AIX_OK.
+ *    Validation: offsets ascend by at least 23; link_off starts at 0, ascends and ends at E; link words below 2 U; join is symmetric as
+ *      the layout requires (the named end is below 2 U, lies on another contig and names the caller back with an equal gap);
+ *      |join_gap| <= 2^30 on joined ends.
+ *
+ * 2. aix_scaffold_fill_layout_dev: the filled member lists, from the graph, the joins, min_gap >= 1, the member CSR of
+ *    aix_scaffold_emit_dev (n_scaffolds, member_off, member) and the closure (close_status, close_dist, path_off, path, the path total).
+ *    A join between ADJACENT members that is closed contributes its path, then the member; the path is reversed with every word ^ 1 when
+ *    the scaffold traverses the join from the non-owner side. A join that is not closed, and the cut join of a cycle, stay as they are.
+ *    Outputs fmember_off u64[Sc + 1]; fmember u32[Mf]; fmember_flag u8[Mf] (bit 0: the member overlaps its predecessor by 22 bases,
+ *      bit 1: it is a fill contig); fmember_gap i64[Mf], the raw join_gap in front of an unclosed member, close_dist in front of the
+ *      member that ends a closed join, 0 elsewhere; fmember_pos u64[Mf], the offset in the filled scaffold of the first byte the member
+ *      writes; fscaffold_offsets u64[Sc + 1]; *n_fmembers_out = Mf and *total_bases_out. The caller allocates U + path total entries for
+ *      the fmember arrays, which is always enough.
+ *    Validation: that of the search for the graph and the joins; the member CSR is dense (member_off starts at 0, ascends strictly, ends
+ *      at U) and names every contig once; a member follows its predecessor through join; statuses are 0 .. 4, 0 on an unjoined end and
+ *      equal at both ends of a join; path_off starts at 0, ascends and ends at the path total; only owners of closed joins have paths;
+ *      every step of a path (e -> p0, p0 -> p1, .., p_last -> t) is a link of the graph; every intermediate has no join; close_dist
+ *      equals the path's length, sum (L_p - 22) - 22, at both ends.
+ *
+ *    aix_scaffold_fill_emit_dev revalidates the fmember arrays against offsets and flags (fmember_off starts at 0, ascends strictly and
+ *    ends at n_fmembers; words below 2 U; flags 0, 1 or 3; a first member has flag 0 and position 0; every other member starts where
+ *    its predecessor's bytes and its own 'N' run end; a scaffold ends with its last member; fscaffold_offsets starts at 0 and ends at
+ *    total_bases), then writes fscaffold_bases: a first or unclosed member whole, an unclosed member preceded by max(gap, min_gap)
+ *    bytes of 'N', a member with bit 0 without its first 22 oriented bases; reverse complement by the byte rule of the cleaning block.
+ *    The 22 overlapping bases are not compared: a graph the library wrote has them equal. With no closed join the filled scaffolds
+ *    equal the scaffolds byte for byte and fmember equals member.
+ *
+ * aix_scaffold_fill is the host form of search, layout and emit: contigs, links, joins and the member CSR in host arrays, malloc'd
+ * arrays out (aix_free); the last seven (the closure) are nullable.
+ * ------------------------------------------------------------------------------------------ */
+int aix_gap_close_dev(uint64_t U, const uint64_t* d_offsets, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E, const uint32_t* d_join,
+                      const int64_t* d_join_gap, uint32_t tolerance, uint32_t max_fill, uint32_t max_states, uint8_t* d_close_status,
+                      int64_t* d_close_dist, uint32_t* d_close_states, uint64_t* d_path_off, uint32_t* d_path, uint64_t cap, uint64_t* total_out,
+                      uint32_t* d_fill_uses, uint64_t* d_counts, void* stream);
+int aix_scaffold_fill_layout_dev(uint64_t U, const uint64_t* d_offsets, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E,
+                                 const uint32_t* d_join, const int64_t* d_join_gap, uint32_t min_gap, uint64_t n_scaffolds,
+                                 const uint64_t* d_member_off, const uint32_t* d_member, const uint8_t* d_close_status, const int64_t* d_close_dist,
+                                 const uint64_t* d_path_off, const uint32_t* d_path, uint64_t path_total, uint64_t* d_fmember_off, uint32_t* d_fmember,
+                                 uint8_t* d_fmember_flag, int64_t* d_fmember_gap, uint64_t* d_fmember_pos, uint64_t* d_fscaffold_offsets,
+                                 uint64_t* n_fmembers_out, uint64_t* total_bases_out, void* stream);
+/* Nothing is written at or beyond the sizes given. Input and output arrays must not overlap. Scratch: see DESIGN 5o. */
+int aix_scaffold_fill_emit_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, uint32_t min_gap, uint64_t n_scaffolds,
+                               const uint64_t* d_fmember_off, uint64_t n_fmembers, const uint32_t* d_fmember, const uint8_t* d_fmember_flag,
+                               const int64_t* d_fmember_gap, const uint64_t* d_fmember_pos, const uint64_t* d_fscaffold_offsets, uint64_t total_bases,
+                               uint8_t* d_fscaffold_bases, void* stream);
+int aix_scaffold_fill(uint64_t U, const uint64_t* offsets, const uint8_t* bases, const uint64_t* link_off, const uint32_t* link_to, uint64_t E,
+                      const uint32_t* join, const int64_t* join_gap, uint64_t n_scaffolds, const uint64_t* member_off, const uint32_t* member,
+                      uint32_t tolerance, uint32_t max_fill, uint32_t max_states, uint32_t min_gap, uint64_t* n_fmembers_out, uint64_t* total_bases_out,
+                      uint64_t* path_total_out, uint64_t** fscaffold_offsets_out, uint8_t** fscaffold_bases_out, uint64_t** fmember_off_out,
+                      uint32_t** fmember_out, uint8_t** fmember_flag_out, int64_t** fmember_gap_out, uint64_t** fmember_pos_out,
+                      uint8_t** close_status_out /* nullable */, int64_t** close_dist_out /* nullable */, uint32_t** close_states_out /* nullable */,
+                      uint64_t** path_off_out /* nullable */, uint32_t** path_out /* nullable */, uint32_t** fill_uses_out /* nullable */,
+                      uint64_t** counts_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
