@@ -10,18 +10,19 @@
 //            stored), a scan of the path lengths into path_off, k_gp_gather
 //   layout   k_gp_validate, k_gf_members and k_gf_ends (one lane per member / end; a path is walked by the lane of its owner), k_gf_count,
 //            two scans (filled members and bytes per member group), k_gf_write
-//   emit     k_gf_em_validate (one lane per filled member), k_gf_em_bases (one lane per output byte, a bisection over the first bytes)
+//   emit     k_gf_em_validate (one lane per filled member), k_graph_em_bases<true> (one lane per output byte, a bisection over the first bytes)
+// What the graph files share (the counters holder, the predicates of the validate kernels, the unit length, the link search, the
+// bisection, the written gap, that emit kernel) is in aix_graph.hpp.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 
 namespace aix {
 
-static constexpr uint32_t kPNone = 0xFFFFFFFFu;                   // join: none (AIX_BUBBLE_NONE)
-static constexpr uint64_t kPMaxU = 0x7FFFFFFFull - 4;             // the limit of the graph calls: an end must fit a 32-bit word
+// (kNoEnd is the join of an unjoined end; the constants, the counters holder, the predicates of the validation, the helpers and k_graph_em_bases: aix_graph.hpp)
 static constexpr long long kPMaxGap = 1ll << 30;
 static constexpr uint32_t kPMaxTol = 1u << 20, kPMaxFill = 64, kPMaxStates = 4096;
 static constexpr int kPW = 64;                                    // the search: one wave per workgroup
@@ -40,16 +41,6 @@ struct GpGraph {                                                  // contigs, th
     const long long* join_gap;
 };
 
-// zeroes `ctr`, runs `launch`, reads it back. Synchronises `s`.
-template <class Launch>
-static hipError_t gp_counted(GpCounters* ctr, GpCounters* host, hipStream_t s, Launch&& launch) {
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GpCounters), s));
-    AIX_TRY(launch());
-    return chain_read(host, ctr, s);
-}
-
-__device__ __forceinline__ uint64_t gp_len(const GpGraph& g, uint64_t w) { return g.offsets[(w >> 1) + 1] - g.offsets[w >> 1]; }
-
 // ---------------------------------------------------------------------------------------------
 // 1. the search
 // ---------------------------------------------------------------------------------------------
@@ -63,21 +54,15 @@ __global__ void __launch_bounds__(kCB) k_gp_validate(const GpGraph g, uint64_t* 
         if (i == NE && own) own[NE] = 0;
         if (i >= NE) continue;
         const uint64_t e = i;
-        if (!(e & 1)) {
-            const uint64_t a = g.offsets[e >> 1], b = g.offsets[(e >> 1) + 1];
-            bad += b < a || b - a < 23;
-        }
-        const uint64_t lo = g.link_off[e], hi = g.link_off[e + 1];
-        bad += e == 0 && lo != 0;
-        bad += e == NE - 1 && hi != g.E;
-        bad += hi < lo || hi > g.E;
+        if (!(e & 1)) bad += span_bad(g.offsets[e >> 1], g.offsets[(e >> 1) + 1]);
+        bad += csr_bad(e, NE, g.link_off[e], g.link_off[e + 1], g.E, kAnyDegree);
         const uint64_t t = g.join[e];
         uint64_t mine = 0;
-        if (t != kPNone) {
-            if (t >= NE || (t >> 1) == (e >> 1) || (uint64_t)g.join[t ^ 1] != (e ^ 1)) ++bad;
+        if (t != kNoEnd) {
+            if (!join_dual_ok(g.join, g.join_gap, NE, e, t)) ++bad;
             else {
                 const long long gap = g.join_gap[e];
-                bad += g.join_gap[t ^ 1] != gap || gap > kPMaxGap || gap < -kPMaxGap;
+                bad += gap > kPMaxGap || gap < -kPMaxGap;
                 mine = e < (t ^ 1);
             }
         }
@@ -107,9 +92,9 @@ __device__ __forceinline__ int gp_keep(const GpGraph& g, const GpRule& r, uint64
         const long long x = d - r.gap;
         return (x <= r.tol && x >= -r.tol) ? 2 : 0;
     }
-    if (k >= r.max_fill || g.join[y & ~1ull] != kPNone || g.join[y | 1ull] != kPNone) return 0;
+    if (k >= r.max_fill || g.join[y & ~1ull] != kNoEnd || g.join[y | 1ull] != kNoEnd) return 0;
     const long long room = r.lim + 22 - d;                        // d + L_y - 22 <= lim, L_y taken as unsigned
-    return (room > 0 && gp_len(g, y) <= (uint64_t)room) ? 1 : 0;
+    return (room > 0 && unit_len(g.offsets, y) <= (uint64_t)room) ? 1 : 0;
 }
 
 // One wave per workgroup, a join at a time. LDS: word, d and packed (parent, k, hit) of the stored states, max_states of each. A round
@@ -151,7 +136,7 @@ __global__ void __launch_bounds__(kPW) k_gp_search(const GpGraph g, uint64_t J, 
                     if (!(p & kPHit)) {
                         have = true;
                         src = sw[i];
-                        cd = (long long)sd[i] + (long long)gp_len(g, src) - 22;          // <= lim: the state was stored
+                        cd = (long long)sd[i] + (long long)unit_len(g.offsets, src) - 22;  // <= lim: the state was stored
                         ck = ((p >> 16) & 0x7Fu) + 1;
                         par = i;
                     }
@@ -241,18 +226,8 @@ struct GfIn {                                                     // the member 
     uint32_t min_gap;
 };
 
-// the scaffold of member i: the last s in [0, n) with off[s] <= i (off[0] == 0). Ends whatever the array holds.
-__device__ __forceinline__ uint64_t gf_scaffold(const uint64_t* __restrict__ off, uint64_t n, uint64_t i) {
-    uint64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // member_off starts at 0, ascends strictly and ends at U; a member word is below 2 U and follows its predecessor through `join`;
-// seen[u] = the members that name contig u
+// seen[u] = the members that name contig u. (The scaffold of member i is last_le(member_off, 0, Sc, i): member_off[0] == 0.)
 __global__ void __launch_bounds__(kCB) k_gf_members(const GpGraph g, const GfIn f, uint32_t* __restrict__ seen, GpCounters* __restrict__ ctr) {
     const uint64_t NE = 2 * g.U, work = (g.U > f.Sc + 1 ? g.U : f.Sc + 1), stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
@@ -267,7 +242,7 @@ __global__ void __launch_bounds__(kCB) k_gf_members(const GpGraph g, const GfIn 
             const uint64_t w = f.member[i];
             if (w >= NE) { ++bad; continue; }
             atomicAdd(seen + (w >> 1), 1u);
-            if (i == 0 || f.member_off[gf_scaffold(f.member_off, f.Sc, i)] == i) continue;
+            if (i == 0 || f.member_off[last_le(f.member_off, 0, f.Sc, i)] == i) continue;
             const uint64_t p = f.member[i - 1];
             bad += p >= NE || (uint64_t)g.join[p < NE ? p : 0] != w;
         }
@@ -275,11 +250,7 @@ __global__ void __launch_bounds__(kCB) k_gf_members(const GpGraph g, const GfIn 
     count_add(bad, &ctr->bad);
 }
 
-__device__ __forceinline__ bool gf_linked(const GpGraph& g, uint64_t a, uint64_t b) {
-    for (uint64_t q = g.link_off[a], hi = g.link_off[a + 1]; q < hi; ++q)
-        if ((uint64_t)g.link_to[q] == b) return true;
-    return false;
-}
+__device__ __forceinline__ bool gf_linked(const GpGraph& g, uint64_t a, uint64_t b) { return link_find(g.link_to, g.link_off[a], g.link_off[a + 1], b) != kNoLink; }
 
 // every contig is named once; statuses are 0 .. 4, 0 on an unjoined end, equal at both ends of a join; path_off starts at 0, ascends and
 // ends at the total; only the owner of a closed join has a path; every step of it is a link, every intermediate unjoined, and
@@ -290,29 +261,26 @@ __global__ void __launch_bounds__(kCB) k_gf_ends(const GpGraph g, const GfIn f, 
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         if (!(e & 1)) bad += seen[e >> 1] != 1;
         const uint64_t a = f.path_off[e], b = f.path_off[e + 1];
-        bad += e == 0 && a != 0;
-        bad += e == NE - 1 && b != f.ptotal;
-        if (b < a || b > f.ptotal) { ++bad; continue; }
+        bad += csr_bad(e, NE, a, b, f.ptotal, kAnyDegree);
+        if (!csr_in_range(a, b, f.ptotal, kAnyDegree)) continue;
         const uint32_t st = f.status[e];
         const uint64_t t = g.join[e];
         bad += st > 4;
-        if (t == kPNone) { bad += st != 0 || b != a; continue; }
+        if (t == kNoEnd) { bad += st != 0 || b != a; continue; }
         bad += f.status[t ^ 1] != st;
         if (st != 1 || e > (t ^ 1)) { bad += b != a; continue; }
         uint64_t at = e, d = (uint64_t)-22ll;
         bool ok = true;
         for (uint64_t q = a; q < b && ok; ++q) {
             const uint64_t w = f.path[q];
-            ok = w < NE && gf_linked(g, at, w) && g.join[w & ~1ull] == kPNone && g.join[w | 1ull] == kPNone;
-            if (ok) { d += gp_len(g, w) - 22; at = w; }
+            ok = w < NE && gf_linked(g, at, w) && g.join[w & ~1ull] == kNoEnd && g.join[w | 1ull] == kNoEnd;
+            if (ok) { d += unit_len(g.offsets, w) - 22; at = w; }
         }
         ok = ok && gf_linked(g, at, t);
         bad += !ok || (uint64_t)f.dist[e] != d || (uint64_t)f.dist[t ^ 1] != d;
     }
     count_add(bad, &ctr->bad);
 }
-
-__device__ __forceinline__ uint64_t gf_wgap(long long gap, uint32_t min_gap) { return (uint64_t)(gap > (long long)min_gap ? gap : (long long)min_gap); }
 
 // per member i (behind the validation): cnt[i] = the filled members it brings (its path and itself), len[i] = the bytes they write,
 // the 'N' run of an unclosed join included: a closed join writes close_dist + L bytes, as close_dist = sum (L_p - 22) - 22
@@ -321,14 +289,14 @@ __global__ void __launch_bounds__(kCB) k_gf_count(const GpGraph g, const GfIn f,
     for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i <= g.U; i += stride) {
         if (i == g.U) { cnt[i] = 0; len[i] = 0; continue; }
         const uint64_t w = f.member[i];
-        uint64_t c = 1, n = gp_len(g, w);
-        if (i && f.member_off[gf_scaffold(f.member_off, f.Sc, i)] != i) {
+        uint64_t c = 1, n = unit_len(g.offsets, w);
+        if (i && f.member_off[last_le(f.member_off, 0, f.Sc, i)] != i) {
             const uint64_t e = f.member[i - 1];
             if (f.status[e] == 1) {
                 const uint64_t o = e < (w ^ 1) ? e : (w ^ 1);
                 c += f.path_off[o + 1] - f.path_off[o];
                 n += (uint64_t)f.dist[e];
-            } else n += gf_wgap(g.join_gap[e], f.min_gap);
+            } else n += written_gap(g.join_gap[e], f.min_gap);
         }
         cnt[i] = c;
         len[i] = n;
@@ -350,7 +318,7 @@ __global__ void __launch_bounds__(kCB) k_gf_write(const GpGraph g, const GfIn f,
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i <= g.U; i += stride) {
         if (i == g.U) { o.fmember_off[f.Sc] = fo[i]; o.fscaffold_offsets[f.Sc] = gs[i]; continue; }
-        const uint64_t s = gf_scaffold(f.member_off, f.Sc, i), i0 = f.member_off[s], base = gs[i0], w = f.member[i];
+        const uint64_t s = last_le(f.member_off, 0, f.Sc, i), i0 = f.member_off[s], base = gs[i0], w = f.member[i];
         uint64_t j = fo[i], x = gs[i] - base;
         uint8_t flag = 0;
         long long gap = 0;
@@ -368,13 +336,13 @@ __global__ void __launch_bounds__(kCB) k_gf_write(const GpGraph g, const GfIn f,
                     o.flag[j] = 3;
                     o.gap[j] = 0;
                     o.pos[j] = x;
-                    x += gp_len(g, p) - 22;
+                    x += unit_len(g.offsets, p) - 22;
                 }
                 flag = 1;
                 gap = f.dist[e];
             } else {
                 gap = g.join_gap[e];
-                x += gf_wgap(gap, f.min_gap);
+                x += written_gap(gap, f.min_gap);
             }
         }
         if (j >= o.cap) continue;                                 // (never: cap >= U + the path total)
@@ -407,10 +375,7 @@ __global__ void __launch_bounds__(kCB) k_gf_em_validate(const GfMap m, uint64_t*
     const uint64_t NE = 2 * m.U, ms = m.Mf > m.Sc + 1 ? m.Mf : m.Sc + 1, work = ms > m.U ? ms : m.U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
     for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j < work; j += stride) {
-        if (j < m.U) {
-            const uint64_t a = m.offsets[j], b = m.offsets[j + 1];
-            bad += b < a || b - a < 23;
-        }
+        if (j < m.U) bad += span_bad(m.offsets[j], m.offsets[j + 1]);
         if (j <= m.Sc) {
             const uint64_t a = m.fmember_off[j], x = m.fso[j];
             bad += j == 0 && (a != 0 || x != 0);
@@ -420,14 +385,14 @@ __global__ void __launch_bounds__(kCB) k_gf_em_validate(const GfMap m, uint64_t*
         if (j >= m.Mf) continue;
         const uint64_t w = m.fmember[j], fl = m.flag[j];
         if (w >= NE || !(fl == 0 || fl == 1 || fl == 3)) { ++bad; continue; }
-        const uint64_t s = gf_scaffold(m.fmember_off, m.Sc, j), j0 = m.fmember_off[s], j1 = m.fmember_off[s + 1], x = m.pos[j];
-        const uint64_t L = m.offsets[(w >> 1) + 1] - m.offsets[w >> 1];
+        const uint64_t s = last_le(m.fmember_off, 0, m.Sc, j), j0 = m.fmember_off[s], j1 = m.fmember_off[s + 1], x = m.pos[j];
+        const uint64_t L = unit_len(m.offsets, w);
         if (j == j0) bad += fl != 0 || x != 0;
         else {
             const uint64_t pw = m.fmember[j - 1], pf = m.flag[j - 1];
             if (pw >= NE) { ++bad; continue; }
-            const uint64_t pl = m.offsets[(pw >> 1) + 1] - m.offsets[pw >> 1];
-            bad += x != m.pos[j - 1] + pl - 22 * (pf & 1) + (fl == 0 ? gf_wgap(m.gap[j], m.min_gap) : 0);
+            const uint64_t pl = unit_len(m.offsets, pw);
+            bad += x != m.pos[j - 1] + pl - 22 * (pf & 1) + (fl == 0 ? written_gap(m.gap[j], m.min_gap) : 0);
         }
         if (j + 1 == j1) bad += m.fso[s + 1] - m.fso[s] != x + L - 22 * (fl & 1);
         mstart[j] = m.fso[s] + x;
@@ -435,24 +400,11 @@ __global__ void __launch_bounds__(kCB) k_gf_em_validate(const GfMap m, uint64_t*
     count_add(bad, &ctr->bad);
 }
 
-// output byte i belongs to the last member whose first byte is at or before it: a base of that member, or the 'N' run behind it
-__global__ void __launch_bounds__(kCB) k_gf_em_bases(const GfMap m, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ mstart, uint8_t* __restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kCB;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i < m.total; i += stride) {
-        const uint64_t j = gf_scaffold(mstart, m.Mf, i);          // mstart[0] == 0 <= i
-        const uint64_t w = m.fmember[j], u = w >> 1, a = m.offsets[u], len = m.offsets[u + 1] - a, x = i - mstart[j] + 22 * (m.flag[j] & 1u);
-        uint8_t c = 'N';
-        if (x < len) {
-            c = bases[w & 1 ? a + len - 1 - x : a + x];
-            if (w & 1) c ^= (c & 2) ? 0x04 : 0x15;
-        }
-        out[i] = c;
-    }
-}
+// (the bases of the filled scaffolds: k_graph_em_bases<true>, aix_graph.hpp)
 
 // the refusals the calls share, decided before anything is allocated or launched
 static int gp_check_graph(uint64_t U, const void* offsets, const void* link_off, const void* link_to, uint64_t E, const void* join, const void* join_gap) {
-    if (U > kPMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!offsets || !link_off || E >= (1ull << 60) || (E && (!link_to || !U)) || (U && (!join || !join_gap))) return AIX_ERR_ARG;
     return AIX_OK;
 }
@@ -484,13 +436,13 @@ extern "C" int aix_gap_close_dev(uint64_t U, const uint64_t* d_offsets, const ui
     const uint64_t NE = 2 * U, grid_cap = chain_test_grid();
     const dim3 blk(kCB);
     const GpGraph g{U, E, d_offsets, d_link_off, d_link_to, d_join, (const long long*)d_join_gap};
-    DevArr ctr_a(s), own(s), at(s), list(s), slot(s), plen(s), tmp(s), tmp2(s);
-    AIXCHK(ctr_a.alloc(sizeof(GpCounters)));
+    Counted<GpCounters> ctr(s);
+    DevArr own(s), at(s), list(s), slot(s), plen(s), tmp(s), tmp2(s);
+    AIXCHK(ctr.init());
     AIXCHK(own.alloc(8 * (NE + 1)));
-    GpCounters* ctr = (GpCounters*)ctr_a.p;
-    GpCounters hc;
-    AIXCHK(gp_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gp_validate, dim3(chain_grid(std::max(NE + 1, E), 2 * kCB, grid_cap)), blk, 0, s, g, (uint64_t*)own.p, ctr);
+    const GpCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gp_validate, dim3(chain_grid(std::max(NE + 1, E), 2 * kCB, grid_cap)), blk, 0, s, g, (uint64_t*)own.p, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
@@ -513,9 +465,9 @@ extern "C" int aix_gap_close_dev(uint64_t U, const uint64_t* d_offsets, const ui
         hipLaunchKernelGGL(k_gp_list, dim3(chain_grid(NE, 4 * kCB, grid_cap)), blk, 0, s, NE, J, (const uint64_t*)own.p, (const uint64_t*)at.p, (uint32_t*)list.p);
         AIXCHK(hipGetLastError());
         AIXCHK(hipMemsetAsync(plen.p, 0, 8 * (NE + 1), s));
-        AIXCHK(gp_counted(ctr, &hc, s, [&]() {
+        AIXCHK(ctr.run([&]() {
             AIX_TRY_LAUNCH(k_gp_search, dim3(chain_grid(J, 1, grid_cap)), dim3(kPW), 12 * (size_t)max_states, s, g, J, (const uint32_t*)list.p, (long long)tolerance,
-                           max_fill, max_states, d_close_status, (long long*)d_close_dist, d_close_states, (uint64_t*)plen.p, (uint32_t*)slot.p, d_fill_uses, ctr);
+                           max_fill, max_states, d_close_status, (long long*)d_close_dist, d_close_states, (uint64_t*)plen.p, (uint32_t*)slot.p, d_fill_uses, ctr.dev());
             return hipSuccess;
         }));
         for (int k = 0; k < 4; ++k) by_status[k] = hc.status[k];
@@ -569,20 +521,20 @@ extern "C" int aix_scaffold_fill_layout_dev(uint64_t U, const uint64_t* d_offset
     const dim3 blk(kCB);
     const GpGraph g{U, E, d_offsets, d_link_off, d_link_to, d_join, (const long long*)d_join_gap};
     const GfIn f{Sc, path_total, d_member_off, d_member, d_close_status, (const long long*)d_close_dist, d_path_off, d_path, min_gap};
-    DevArr ctr_a(s), seen(s), cnt(s), len(s), fo(s), gs(s), tmp(s), tmp2(s);
-    AIXCHK(ctr_a.alloc(sizeof(GpCounters)));
-    GpCounters* ctr = (GpCounters*)ctr_a.p;
-    GpCounters hc;
-    AIXCHK(gp_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gp_validate, dim3(chain_grid(std::max(NE + 1, E), 2 * kCB, grid_cap)), blk, 0, s, g, (uint64_t*)nullptr, ctr);
+    Counted<GpCounters> ctr(s);
+    DevArr seen(s), cnt(s), len(s), fo(s), gs(s), tmp(s), tmp2(s);
+    AIXCHK(ctr.init());
+    const GpCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gp_validate, dim3(chain_grid(std::max(NE + 1, E), 2 * kCB, grid_cap)), blk, 0, s, g, (uint64_t*)nullptr, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
     AIXCHK(seen.alloc(4 * U));
-    AIXCHK(gp_counted(ctr, &hc, s, [&]() {
+    AIXCHK(ctr.run([&]() {
         AIX_TRY(hipMemsetAsync(seen.p, 0, 4 * U, s));
-        AIX_TRY_LAUNCH(k_gf_members, dim3(chain_grid(std::max(U, Sc + 1), 2 * kCB, grid_cap)), blk, 0, s, g, f, (uint32_t*)seen.p, ctr);
-        AIX_TRY_LAUNCH(k_gf_ends, dim3(chain_grid(NE, kCB, grid_cap)), blk, 0, s, g, f, (const uint32_t*)seen.p, ctr);
+        AIX_TRY_LAUNCH(k_gf_members, dim3(chain_grid(std::max(U, Sc + 1), 2 * kCB, grid_cap)), blk, 0, s, g, f, (uint32_t*)seen.p, ctr.dev());
+        AIX_TRY_LAUNCH(k_gf_ends, dim3(chain_grid(NE, kCB, grid_cap)), blk, 0, s, g, f, (const uint32_t*)seen.p, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
@@ -613,7 +565,7 @@ extern "C" int aix_scaffold_fill_emit_dev(uint64_t U, const uint64_t* d_offsets,
                                           const uint64_t* d_fmember_off, uint64_t n_fmembers, const uint32_t* d_fmember, const uint8_t* d_fmember_flag,
                                           const int64_t* d_fmember_gap, const uint64_t* d_fmember_pos, const uint64_t* d_fscaffold_offsets, uint64_t total_bases,
                                           uint8_t* d_fscaffold_bases, void* stream) {
-    if (U > kPMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     const uint64_t Sc = n_scaffolds, Mf = n_fmembers;
     if (!d_offsets || !d_fmember_off || !d_fscaffold_offsets || min_gap < 1 || Sc > U || (U && !Sc) || Mf < U || Mf >= (1ull << 60)) return AIX_ERR_ARG;
     if (U && (!d_bases || !d_fmember || !d_fmember_flag || !d_fmember_gap || !d_fmember_pos || !d_fscaffold_bases)) return AIX_ERR_ARG;
@@ -623,17 +575,17 @@ extern "C" int aix_scaffold_fill_emit_dev(uint64_t U, const uint64_t* d_offsets,
     const uint64_t grid_cap = chain_test_grid();
     const dim3 blk(kCB);
     const GfMap m{U, Sc, Mf, total_bases, d_offsets, d_fmember_off, d_fmember, d_fmember_flag, (const long long*)d_fmember_gap, d_fmember_pos, d_fscaffold_offsets, min_gap};
-    DevArr ctr_a(s), mstart(s);
-    AIXCHK(ctr_a.alloc(sizeof(GpCounters)));
+    Counted<GpCounters> ctr(s);
+    DevArr mstart(s);
+    AIXCHK(ctr.init());
     AIXCHK(mstart.alloc(8 * Mf));
-    GpCounters* ctr = (GpCounters*)ctr_a.p;
-    GpCounters hc;
-    AIXCHK(gp_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gf_em_validate, dim3(chain_grid(std::max(std::max(Mf, Sc + 1), U), 2 * kCB, grid_cap)), blk, 0, s, m, (uint64_t*)mstart.p, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gf_em_validate, dim3(chain_grid(std::max(std::max(Mf, Sc + 1), U), 2 * kCB, grid_cap)), blk, 0, s, m, (uint64_t*)mstart.p, ctr.dev());
         return hipSuccess;
     }));
-    if (hc.bad) return AIX_ERR_ARG;
-    hipLaunchKernelGGL(k_gf_em_bases, dim3(chain_grid(total_bases, 4 * kCB, grid_cap)), blk, 0, s, m, d_bases, (const uint64_t*)mstart.p, d_fscaffold_bases);
+    if (ctr.host.bad) return AIX_ERR_ARG;
+    hipLaunchKernelGGL(k_graph_em_bases<true>, dim3(chain_grid(total_bases, 4 * kCB, grid_cap)), blk, 0, s, Mf, total_bases, d_offsets, d_bases, d_fmember, d_fmember_flag,
+                       (const uint64_t*)mstart.p, d_fscaffold_bases);
     AIXCHK(hipGetLastError());
     AIXCHK(hipStreamSynchronize(s));
     return AIX_OK;
@@ -658,12 +610,9 @@ extern "C" int aix_scaffold_fill(uint64_t U, const uint64_t* offsets, const uint
     const uint64_t total_in = offsets[U], Sc = n_scaffolds, NE = 2 * U;
     if (U && (total_in < 23 * U || total_in > (1ULL << 48))) return AIX_ERR_ARG;
     DevArr in[8], cs, cd, cn, po, pa, fu, ct, fo, fm, ff, fg, fp, so, sb;
-    const void* src[8] = {offsets, bases, link_off, link_to, join, join_gap, member_off, member};
-    const uint64_t bytes[8] = {8 * (U + 1), total_in, 8 * (NE + 1), 4 * E, 4 * NE, 8 * NE, 8 * (Sc + 1), 4 * U};
-    for (int i = 0; i < 8; ++i) {
-        AIXCHK(in[i].alloc(bytes[i]));
-        if (bytes[i]) AIXCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
-    }
+    const HostIn ins[8] = {{offsets, 8 * (U + 1)}, {bases, total_in}, {link_off, 8 * (NE + 1)}, {link_to, 4 * E}, {join, 4 * NE}, {join_gap, 8 * NE},
+                           {member_off, 8 * (Sc + 1)}, {member, 4 * U}};
+    AIXCHK(copy_in_host(in, ins, 8));
     const uint64_t* d_off = (const uint64_t*)in[0].p;
     const uint64_t* d_lo = (const uint64_t*)in[2].p;
     const uint32_t* d_lt = (const uint32_t*)in[3].p;

@@ -4,7 +4,8 @@
 // and the resources. No index handle: the arrays and the current device, like aix_unitig_bubbles_dev.
 //
 // The compaction is that of aix_unitigs.hip one level up: a node is a unitig, its two ports are its ends 2 u + 0 / 2 u + 1, at most one
-// link survives per merged port. What the two levels share is in aix_chains.hpp, and why their kernels are not. The chain (one plain
+// link survives per merged port. What the two levels share is in aix_chains.hpp, and why their kernels are not; what the graph files
+// share (the counters holder, the predicates of k_gc_validate, the bisection) is in aix_graph.hpp. The chain (one plain
 // launch per step and per round; every host loop is bounded by a count computed on the host; integer only, no LDS, no grid-wide barrier,
 // no spin-wait):
 //   validate k_gc_validate: one lane per end; offsets, degrees, link words, duality of the surviving links, the mates
@@ -27,11 +28,11 @@
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 
 namespace aix {
 
-static constexpr uint32_t kGNone = 0xFFFFFFFFu;                   // word: no single surviving link; contig: removed; mate: none
+// (kNoEnd, aix_graph.hpp, is here a word without a single surviving link, the contig of a removed unitig and the mate of a unitig without one)
 static constexpr uint64_t kGFlag = 1ULL << 63;                    // ranking state: terminal reached
 static constexpr uint64_t kGDead = ~0ULL;                         // sort key of a removed unitig / of a unitig that starts no contig
 static constexpr uint32_t kGMaxThreshold = 32767;
@@ -71,17 +72,15 @@ __global__ void __launch_bounds__(kCB) k_gc_validate(uint64_t U, const uint64_t*
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         const uint64_t u = e >> 1;
         if (!(e & 1)) {
-            const uint64_t a = offsets[u], b = offsets[u + 1];
-            bad += b < a || b - a < 23;
+            bad += span_bad(offsets[u], offsets[u + 1]);
             if (mate) {
                 const uint32_t w = mate[u];
-                if (w != kGNone) bad += w >= U || w == u || mate[w < U ? w : u] != u;
+                if (w != kNoEnd) bad += w >= U || w == u || mate[w < U ? w : u] != u;
             }
         }
         const uint64_t lo = link_off[e], hi = link_off[e + 1];
-        bad += e == 0 && lo != 0;
-        bad += e == NE - 1 && hi != E;
-        if (hi < lo || hi > E || hi - lo > 4) { ++bad; continue; }
+        bad += csr_bad(e, NE, lo, hi, E, 4);
+        if (!csr_in_range(lo, hi, E, 4)) continue;
         bad += circular[u] && hi > lo;
         for (uint64_t i = lo; i < hi; ++i) {
             const uint64_t t = link_to[i];
@@ -90,7 +89,7 @@ __global__ void __launch_bounds__(kCB) k_gc_validate(uint64_t U, const uint64_t*
             if (!gc_alive(remove, u) || !gc_alive(remove, t >> 1)) continue;
             const uint64_t lo2 = link_off[t ^ 1], hi2 = link_off[(t ^ 1) + 1];
             bool dual = false;
-            if (hi2 >= lo2 && hi2 <= E && hi2 - lo2 <= 4)
+            if (csr_in_range(lo2, hi2, E, 4))
                 for (uint64_t j = lo2; j < hi2; ++j) dual = dual || link_to[j] == (uint32_t)(e ^ 1);
             bad += !dual;
         }
@@ -107,14 +106,14 @@ __device__ __forceinline__ bool gc_outranks(const uint64_t* __restrict__ offsets
     return a > b || (a == b && w < u);
 }
 
-// the linked end of tip candidate u, or kGNone
+// the linked end of tip candidate u, or kNoEnd
 __device__ __forceinline__ uint32_t gc_attached(const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular, const uint64_t* __restrict__ link_off,
                                                 uint64_t u, uint32_t tip_max) {
-    if (circular[u] || gc_m(offsets, u) > tip_max) return kGNone;
+    if (circular[u] || gc_m(offsets, u) > tip_max) return kNoEnd;
     const uint64_t d0 = link_off[2 * u + 1] - link_off[2 * u], d1 = link_off[2 * u + 2] - link_off[2 * u + 1];
     if (d0 == 0 && d1 == 1) return (uint32_t)(2 * u + 1);
     if (d1 == 0 && d0 == 1) return (uint32_t)(2 * u);
-    return kGNone;
+    return kNoEnd;
 }
 
 __global__ void __launch_bounds__(kCB) k_gc_mark(uint64_t U, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ circular,
@@ -125,17 +124,17 @@ __global__ void __launch_bounds__(kCB) k_gc_mark(uint64_t U, const uint64_t* __r
     unsigned long long tips = 0, arms = 0;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         uint32_t res = 0;
-        const uint32_t a = tip_max ? gc_attached(offsets, circular, link_off, u, tip_max) : kGNone;
-        if (a != kGNone) {
+        const uint32_t a = tip_max ? gc_attached(offsets, circular, link_off, u, tip_max) : kNoEnd;
+        if (a != kNoEnd) {
             const uint32_t f = link_to[link_off[a]] ^ 1u;           // the fork: the end that faces u
             for (uint64_t i = link_off[f]; i < link_off[f + 1]; ++i) {
                 const uint64_t w = link_to[i] >> 1;
                 if (w == u) continue;
-                if (gc_attached(offsets, circular, link_off, w, tip_max) == kGNone || gc_outranks(offsets, tf_sum, w, u)) res = 1;
+                if (gc_attached(offsets, circular, link_off, w, tip_max) == kNoEnd || gc_outranks(offsets, tf_sum, w, u)) res = 1;
             }
         }
         const uint32_t w = mate[u];
-        if (bub_max && w != kGNone && gc_m(offsets, u) <= bub_max && gc_m(offsets, w) <= bub_max && gc_outranks(offsets, tf_sum, w, u)) res = 2;
+        if (bub_max && w != kNoEnd && gc_m(offsets, u) <= bub_max && gc_m(offsets, w) <= bub_max && gc_outranks(offsets, tf_sum, w, u)) res = 2;
         remove[u] = (uint8_t)res;
         tips += res == 1;
         arms += res == 2;
@@ -151,13 +150,13 @@ __global__ void __launch_bounds__(kCB) k_gc_words(uint64_t U, const uint64_t* __
                                                  const uint8_t* __restrict__ remove, uint32_t* __restrict__ word, uint8_t* __restrict__ degp) {
     const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
-        uint32_t d = 0, t1 = kGNone;
+        uint32_t d = 0, t1 = kNoEnd;
         if (gc_alive(remove, e >> 1))
             for (uint64_t i = link_off[e]; i < link_off[e + 1]; ++i) {
                 const uint32_t t = link_to[i];
                 if (gc_alive(remove, t >> 1)) { ++d; t1 = t; }
             }
-        word[e] = d == 1 ? (t1 ^ 1u) : kGNone;
+        word[e] = d == 1 ? (t1 ^ 1u) : kNoEnd;
         degp[e] = (uint8_t)d;
     }
 }
@@ -245,7 +244,7 @@ __global__ void __launch_bounds__(kCB) k_gc_place(uint64_t U, const uint64_t* __
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         start_id[u] = (uint32_t)u;
         if (remove[u]) {
-            start_of[u] = kGNone; pos_out[u] = 0; flag_out[u] = 0; start_code[u] = kGDead;
+            start_of[u] = kNoEnd; pos_out[u] = 0; flag_out[u] = 0; start_code[u] = kGDead;
             continue;
         }
         ++alive;
@@ -302,7 +301,7 @@ __global__ void __launch_bounds__(kCB) k_gc_assign(const uint32_t* __restrict__ 
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         const uint32_t st = start_of[u];
-        contig[u] = (uint64_t)st < U ? start_cid[st] : kGNone;
+        contig[u] = (uint64_t)st < U ? start_cid[st] : kNoEnd;
     }
 }
 
@@ -315,7 +314,7 @@ __global__ void __launch_bounds__(kCB) k_gc_mapcheck(uint64_t U, const uint64_t*
     unsigned long long alive = 0, starts = 0, bad = 0, total = 0, mx = 0;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         const uint32_t c = contig[u];
-        if (remove[u]) { bad += c != kGNone; continue; }
+        if (remove[u]) { bad += c != kNoEnd; continue; }
         ++alive;
         bad += (uint64_t)c >= C;
         starts += pos[u] == 0;
@@ -342,7 +341,7 @@ __global__ void __launch_bounds__(kCB) k_gc_mlen(uint64_t S, const uint32_t* __r
                                                 uint64_t* __restrict__ mlen) {
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t j = (uint64_t)blockIdx.x * kCB + threadIdx.x; j <= S; j += stride) {
-        const uint32_t u = j < S ? ms[j] : kGNone;
+        const uint32_t u = j < S ? ms[j] : kNoEnd;
         mlen[j] = (uint64_t)u < U ? gc_m(offsets, u) : 0;
     }
 }
@@ -469,11 +468,7 @@ __global__ void __launch_bounds__(kCB) k_gc_emit(uint64_t S, const uint64_t* __r
     const uint64_t chunks = (total + 15) >> 4, stride = (uint64_t)gridDim.x * kCB, mask = (1ULL << pos_bits) - 1;
     for (uint64_t ch = (uint64_t)blockIdx.x * kCB + threadIdx.x; ch < chunks; ch += stride) {
         const uint64_t o = ch << 4, end = o + 16 < total ? o + 16 : total;
-        uint64_t lo = 0, hi = S;                                   // the last member with begin <= o (begin[0] == 0)
-        while (hi - lo > 1) {                                      // at most 64 trips
-            const uint64_t mid = lo + ((hi - lo) >> 1);
-            if (begin[mid] <= o) lo = mid; else hi = mid;
-        }
+        const uint64_t lo = last_le(begin, 0, S, o);               // the last member with begin <= o (begin[0] == 0)
         unsigned __int128 acc = 0;
         uint64_t cur = o;
         for (uint64_t j = lo; cur < end && j < S; ++j) {           // at most 16 trips: every member contributes a byte
@@ -535,28 +530,28 @@ struct GcGraph {                                                  // a unitig se
 };
 
 // *bad: the arrays are no unitig set (with `remove`: one of its surviving links has no dual). Synchronises `s`.
-static hipError_t gc_validate(const GcGraph& g, const uint8_t* remove, const uint32_t* mate, GcCounters* ctr, bool* bad, hipStream_t s) {
-    GcCounters hc;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY_LAUNCH(k_gc_validate, dim3(chain_grid(2 * g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.link_off, g.link_to, g.E, remove, mate, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
-    *bad = hc.bad != 0;
+static hipError_t gc_validate(const GcGraph& g, const uint8_t* remove, const uint32_t* mate, Counted<GcCounters>& ctr, bool* bad, hipStream_t s) {
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gc_validate, dim3(chain_grid(2 * g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.link_off, g.link_to, g.E, remove, mate,
+                       ctr.dev());
+        return hipSuccess;
+    }));
+    *bad = ctr.host.bad != 0;
     return hipSuccess;
 }
 
 static hipError_t gc_mark(const GcGraph& g, const uint32_t* mate, uint32_t tip_max, uint32_t bub_max, uint8_t* remove, uint64_t out[2], bool* bad, hipStream_t s) {
-    DevArr ctr_a(s);
-    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
-    GcCounters* ctr = (GcCounters*)ctr_a.p;
+    Counted<GcCounters> ctr(s);
+    AIX_TRY(ctr.init());
     AIX_TRY(gc_validate(g, nullptr, mate, ctr, bad, s));
     if (*bad) return hipSuccess;
-    GcCounters hc;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY_LAUNCH(k_gc_mark, dim3(chain_grid(g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.tf_sum, g.link_off, g.link_to, mate, tip_max,
-        bub_max, remove, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
-    out[0] = hc.n_tips;
-    out[1] = hc.n_arms;
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gc_mark, dim3(chain_grid(g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.offsets, g.circular, g.tf_sum, g.link_off, g.link_to, mate, tip_max,
+                       bub_max, remove, ctr.dev());
+        return hipSuccess;
+    }));
+    out[0] = ctr.host.n_tips;
+    out[1] = ctr.host.n_arms;
     return hipSuccess;
 }
 
@@ -574,10 +569,10 @@ static hipError_t gc_merge_links(const GcGraph& g, const uint8_t* remove, uint32
 static hipError_t gc_layout(const GcGraph& g, const uint8_t* remove, uint32_t* contig, uint64_t* pos, uint8_t* flag, uint64_t out[4], bool* bad, hipStream_t s) {
     const uint64_t U = g.U, NE = 2 * U, cap = chain_test_grid();
     const dim3 blk(kCB);
-    DevArr ctr_a(s), word(s), degp(s), mg(s), n0(s), d0(s), n1(s), d1(s), ca0(s), cm0(s), cw0(s), ca1(s), cm1(s), cw1(s), so(s), sc(s), si(s), sc2(s), si2(s), cid(s), tmp(s);
-    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
-    GcCounters* ctr = (GcCounters*)ctr_a.p;
-    GcCounters hc;
+    Counted<GcCounters> ctr(s);
+    DevArr word(s), degp(s), mg(s), n0(s), d0(s), n1(s), d1(s), ca0(s), cm0(s), cw0(s), ca1(s), cm1(s), cw1(s), so(s), sc(s), si(s), sc2(s), si2(s), cid(s), tmp(s);
+    AIX_TRY(ctr.init());
+    const GcCounters& hc = ctr.host;
     AIX_TRY(gc_validate(g, remove, nullptr, ctr, bad, s));
     if (*bad) return hipSuccess;
     if (U == 0) return hipSuccess;
@@ -588,14 +583,12 @@ static hipError_t gc_layout(const GcGraph& g, const uint8_t* remove, uint32_t* c
     AIX_TRY(d0.alloc(8 * NE));
     AIX_TRY(n1.alloc(8 * NE));
     AIX_TRY(d1.alloc(8 * NE));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(ctr.run([&]() { return gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr.dev(), s); }));
     const uint64_t links = hc.links;
     uint64_t *cn = (uint64_t*)n0.p, *cd = (uint64_t*)d0.p, *on = (uint64_t*)n1.p, *od = (uint64_t*)d1.p;
     uint64_t open = hc.unflagged[0];
-    AIX_TRY(chain_rank(U, ctr->unflagged, &open, s, [&](int r) {
-        AIX_TRY_LAUNCH(k_gc_jump, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint64_t*)cd, NE, on, od, &ctr->unflagged[r]);
+    AIX_TRY(chain_rank(U, ctr.dev()->unflagged, &open, s, [&](int r) {
+        AIX_TRY_LAUNCH(k_gc_jump, dim3(chain_grid(NE, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cn, (const uint64_t*)cd, NE, on, od, &ctr.dev()->unflagged[r]);
         std::swap(cn, on);
         std::swap(cd, od);
         return hipSuccess;
@@ -623,10 +616,11 @@ static hipError_t gc_layout(const GcGraph& g, const uint8_t* remove, uint32_t* c
     AIX_TRY(so.alloc(4 * U));
     AIX_TRY(sc.alloc(8 * U));
     AIX_TRY(si.alloc(4 * U));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY_LAUNCH(k_gc_place, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, g.bases, g.circular, remove, (const uint64_t*)cn, (const uint64_t*)cd, cyc_a, cyc_md,
-        (uint32_t*)so.p, pos, flag, (uint64_t*)sc.p, (uint32_t*)si.p, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gc_place, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, g.bases, g.circular, remove, (const uint64_t*)cn, (const uint64_t*)cd, cyc_a,
+                       cyc_md, (uint32_t*)so.p, pos, flag, (uint64_t*)sc.p, (uint32_t*)si.p, ctr.dev());
+        return hipSuccess;
+    }));
     const uint64_t C = std::min<uint64_t>(hc.n_starts, U);
     AIX_TRY(sc2.alloc(8 * U));
     AIX_TRY(si2.alloc(4 * U));
@@ -659,19 +653,20 @@ static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_
     const uint64_t U = g.U, NE = 2 * U, cap = chain_test_grid();
     const dim3 blk(kCB);
     *status = AIX_ERR_ARG;
-    DevArr ctr_a(s), word(s), degp(s), mg(s), n0(s), d0(s), keys(s), ids(s), keys2(s), ms(s), tmp(s), mlen(s), kpre(s), begin(s), noff(s), ndeg(s), nlo(s), agg(s), uniq(s),
-        ragg(s), cnt(s);
-    AIX_TRY(ctr_a.alloc(sizeof(GcCounters)));
-    GcCounters* ctr = (GcCounters*)ctr_a.p;
-    GcCounters hc;
+    Counted<GcCounters> ctr(s);
+    DevArr word(s), degp(s), mg(s), n0(s), d0(s), keys(s), ids(s), keys2(s), ms(s), tmp(s), mlen(s), kpre(s), begin(s), noff(s), ndeg(s), nlo(s), agg(s), uniq(s), ragg(s),
+        cnt(s);
+    AIX_TRY(ctr.init());
+    const GcCounters& hc = ctr.host;
     bool bad = false;
     AIX_TRY(gc_validate(g, remove, nullptr, ctr, &bad, s));
     if (bad) return hipSuccess;
     uint64_t total_in = 0;
     AIX_TRY(hipMemcpyAsync(&total_in, g.offsets + U, 8, hipMemcpyDeviceToHost, s));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY_LAUNCH(k_gc_mapcheck, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, remove, contig, pos, C, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gc_mapcheck, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, U, g.offsets, remove, contig, pos, C, ctr.dev());
+        return hipSuccess;
+    }));
     const uint64_t S = hc.n_alive;
     if (hc.bad || hc.n_starts != C || S < C || (C == 0 && S) || hc.total_k + 22 * C != total || (S && hc.max_pos >= hc.total_k)) return hipSuccess;
     if (C == 0) {
@@ -688,8 +683,8 @@ static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_
     AIX_TRY(mg.alloc(NE));
     AIX_TRY(n0.alloc(8 * NE));
     AIX_TRY(d0.alloc(8 * NE));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr, s));
+    AIX_TRY(hipMemsetAsync(ctr.dev(), 0, sizeof(GcCounters), s));   // (its counters are not read here: no run())
+    AIX_TRY(gc_merge_links(g, remove, (uint32_t*)word.p, (uint8_t*)degp.p, (uint8_t*)mg.p, (uint64_t*)n0.p, (uint64_t*)d0.p, ctr.dev(), s));
     AIX_TRY(keys.alloc(8 * U));
     AIX_TRY(ids.alloc(4 * U));
     AIX_TRY(keys2.alloc(8 * U));
@@ -704,21 +699,22 @@ static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_
     AIX_TRY(noff.alloc(8 * (C + 1)));
     AIX_TRY_LAUNCH(k_gc_mlen, dim3(chain_grid(S + 1, 4 * kCB, cap)), blk, 0, s, S, (const uint32_t*)ms.p, U, g.offsets, (uint64_t*)mlen.p);
     AIX_TRY(scan_u64((const uint64_t*)mlen.p, (uint64_t*)kpre.p, S + 1, tmp, s));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GcCounters), s));
-    AIX_TRY(hipMemsetAsync(noff.p, 0, 8 * (C + 1), s));
-    AIX_TRY_LAUNCH(k_gc_begin, dim3(chain_grid(S, 4 * kCB, cap)), blk, 0, s, S, C, pos_bits, (const uint64_t*)keys2.p, (const uint64_t*)kpre.p, total, (uint64_t*)begin.p,
-        (uint64_t*)noff.p, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY(hipMemsetAsync(noff.p, 0, 8 * (C + 1), s));
+        AIX_TRY_LAUNCH(k_gc_begin, dim3(chain_grid(S, 4 * kCB, cap)), blk, 0, s, S, C, pos_bits, (const uint64_t*)keys2.p, (const uint64_t*)kpre.p, total, (uint64_t*)begin.p,
+                       (uint64_t*)noff.p, ctr.dev());
+        return hipSuccess;
+    }));
     if (hc.bad) return hipSuccess;
     AIX_TRY(ndeg.alloc(4 * (2 * C + 1)));
     AIX_TRY(nlo.alloc(8 * (2 * C + 1)));
     AIX_TRY(hipMemsetAsync(ndeg.p, 0, 4 * (2 * C + 1), s));
     AIX_TRY_LAUNCH(k_gc_ends, dim3(chain_grid(NE, 2 * kCB, cap)), blk, 0, s, U, C, g.offsets, g.circular, g.link_off, g.link_to, remove, (const uint32_t*)word.p,
-        (const uint8_t*)degp.p, (const uint8_t*)mg.p, contig, pos, flag, (const uint64_t*)noff.p, (uint32_t*)ndeg.p, ctr);
+        (const uint8_t*)degp.p, (const uint8_t*)mg.p, contig, pos, flag, (const uint64_t*)noff.p, (uint32_t*)ndeg.p, ctr.dev());   // (on top of the zero bad of k_gc_begin: no run())
     AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint32_t*)ndeg.p, Widen<uint32_t>()), (uint64_t*)nlo.p, 2 * C + 1, tmp, s));
     uint64_t E_new = 0;
     AIX_TRY(hipMemcpyAsync(&E_new, (const uint64_t*)nlo.p + 2 * C, 8, hipMemcpyDeviceToHost, s));
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(chain_read(&ctr.host, ctr.dev(), s));
     if (hc.bad || E_new != E2) return hipSuccess;
     // everything is validated: from here on the outputs are written
     AIX_TRY(hipMemcpyAsync(o.offsets, noff.p, 8 * (C + 1), hipMemcpyDeviceToDevice, s));
@@ -752,7 +748,7 @@ static hipError_t gc_emit(const GcGraph& g, const uint8_t* remove, const uint32_
 // ---------------------------------------------------------------------------------------------
 // the refusals every entry point shares, decided before anything is allocated or launched
 static int gc_check_sizes(uint64_t U, const void* offsets, const void* circular, const void* link_off, const void* link_to, uint64_t E) {
-    if (U > 0x7FFFFFFFull - 4) return AIX_ERR_UNSUPPORTED;       // an end (2 u + side) must fit its u32 word below the codes
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!offsets || !link_off) return AIX_ERR_ARG;
     if (U && !circular) return AIX_ERR_ARG;
     if (E && !link_to) return AIX_ERR_ARG;
@@ -842,13 +838,10 @@ extern "C" int aix_graph_clean(uint64_t U, const uint64_t* offsets, const uint8_
     // offsets are read on the host for the size of `bases` only; everything else about them is the device's to check
     const uint64_t total_in = offsets[U];
     if (U && (total_in < 23 * U || total_in > (1ULL << 48))) return AIX_ERR_ARG;
-    DevArr in[9], rm, uc, up, uf, oo, ob, oc, os, on, ox, ol, ot;
-    const void* src[9] = {offsets, bases, circular, tf_sum, tf_min, tf_max, link_off, link_to, nullptr};
-    const uint64_t bytes[9] = {8 * (U + 1), total_in, U, 8 * U, 4 * U, 4 * U, 8 * (2 * U + 1), 4 * E, 0};
-    for (int i = 0; i < 8; ++i) {
-        AIXCHK(in[i].alloc(bytes[i]));
-        if (bytes[i]) AIXCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
-    }
+    DevArr in[8], rm, uc, up, uf, oo, ob, oc, os, on, ox, ol, ot;
+    const HostIn ins[8] = {{offsets, 8 * (U + 1)}, {bases, total_in}, {circular, U}, {tf_sum, 8 * U}, {tf_min, 4 * U}, {tf_max, 4 * U}, {link_off, 8 * (2 * U + 1)},
+                           {link_to, 4 * E}};
+    AIXCHK(copy_in_host(in, ins, 8));
     AIXCHK(rm.alloc(U));
     AIXCHK(uc.alloc(4 * U));
     AIXCHK(up.alloc(8 * U));

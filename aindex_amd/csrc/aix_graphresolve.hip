@@ -3,9 +3,10 @@
 // splitting of a repeat unitig into one copy per consistent (entry, exit) pair. The result is a unitig set in exactly the format of the
 // input, so aix_graph_compact_* under an all-zero mask merges it into longer contigs. The contract is stated above the
 // aix_thread_pairs_dev / aix_graph_resolve_* declarations in include/aindex_hip.h; DESIGN 5m has the derivations and the resources. No
-// index handle: the arrays and the current device, like the cleaning. One plain launch per step; every call validates with counting
-// kernels that write nothing but their counters and writes only after the host has read them as clean; integer only, no LDS, no
-// grid-wide barrier, no spin-wait:
+// index handle: the arrays and the current device, like the cleaning. What the graph files share (the counters holder, the predicates
+// of the validate kernels, the link search and the bisection) is in aix_graph.hpp. One plain launch per step; every call validates
+// with counting kernels that write nothing but their counters and writes only after the host has read them as clean; integer only, no
+// LDS, no grid-wide barrier, no spin-wait:
 //   pairs    k_gr_linkoff, then k_gr_pairs<check> and k_gr_pairs<add>: one lane per step, a plain device-scope u64 atomicAdd per transition
 //   mark     k_gr_validate (one lane per end: the unitig set, duality, symmetric support), k_gr_weak (one lane per end), k_gr_split (one
 //            lane per unitig, reads the link_remove of the launch before)
@@ -17,14 +18,11 @@
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 
 namespace aix {
 
-static constexpr uint32_t kRNone = 0xFFFFFFFFu;                   // copy_base of an unsplit unitig; "no such link"
-static constexpr uint64_t kRMaxU = 0x7FFFFFFFull - 4;             // the limit of the graph calls: an end must fit a 32-bit word
-static constexpr uint64_t kRNoIndex = ~0ULL;
-
+// (kNoEnd is the copy_base of an unsplit unitig; the constants, the counters holder and the predicates of the validation: aix_graph.hpp)
 struct GrCounters {                                               // one zeroed record per call
     unsigned long long bad, n_pairs, removed, n_split, added, extra_bases;
 };
@@ -37,23 +35,12 @@ struct GrGraph {                                                  // a unitig se
     const uint32_t* link_to;
 };
 
-// index of the first link of end e whose word is t, kRNoIndex without one. link_off is validated: [lo, hi) lies in [0, E).
-__device__ __forceinline__ uint64_t gr_find(const uint64_t* __restrict__ link_off, const uint32_t* __restrict__ link_to, uint64_t e, uint64_t t) {
-    for (uint64_t j = link_off[e], hi = link_off[e + 1]; j < hi; ++j)
-        if ((uint64_t)link_to[j] == t) return j;
-    return kRNoIndex;
-}
-
 // link_off starts at 0, ascends, ends at E, and no end has more than 4 links
 __global__ void __launch_bounds__(kCB) k_gr_linkoff(uint64_t U, uint64_t E, const uint64_t* __restrict__ link_off, GrCounters* __restrict__ ctr) {
     const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
-    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
-        const uint64_t lo = link_off[e], hi = link_off[e + 1];
-        bad += e == 0 && lo != 0;
-        bad += e == NE - 1 && hi != E;
-        bad += hi < lo || hi > E || hi - lo > 4;
-    }
+    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride)
+        bad += csr_bad(e, NE, link_off[e], link_off[e + 1], E, 4);
     count_add(bad, &ctr->bad);
 }
 
@@ -81,8 +68,8 @@ __global__ void __launch_bounds__(kCB) k_gr_pairs(uint64_t U, uint64_t E, const 
         if (u >= U || up >= U) continue;                          // (counted by the lanes of those steps)
         const uint64_t s = step_flag[i] & 1u, e = 2 * u + s, ep = 2 * up + (step_flag[i - 1] & 1u);
         const bool ok = a >= link_off[ep] && a < link_off[ep + 1] && (uint64_t)link_to[a] == e && b >= link_off[e] && b < link_off[e + 1];
-        const uint64_t d = ok ? gr_find(link_off, link_to, e ^ 1, ep ^ 1) : kRNoIndex;
-        if (d == kRNoIndex) { ++bad; continue; }
+        const uint64_t d = ok ? link_find(link_to, link_off[e ^ 1], link_off[(e ^ 1) + 1], ep ^ 1) : kNoLink;   // (behind k_gr_linkoff: the list lies in [0, E))
+        if (d == kNoLink) { ++bad; continue; }
         ++n;
         if (!kCheck) {
             const uint64_t x = (s ? d : b) - link_off[2 * u], y = (s ? b : d) - link_off[2 * u + 1];
@@ -106,25 +93,21 @@ __global__ void __launch_bounds__(kCB) k_gr_validate(const GrGraph g, const uint
     unsigned long long bad = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
         const uint64_t u = e >> 1;
-        if (!(e & 1)) {
-            const uint64_t a = g.offsets[u], b = g.offsets[u + 1];
-            bad += b < a || b - a < 23;
-        }
+        if (!(e & 1)) bad += span_bad(g.offsets[u], g.offsets[u + 1]);
         const uint64_t lo = g.link_off[e], hi = g.link_off[e + 1];
-        bad += e == 0 && lo != 0;
-        bad += e == NE - 1 && hi != g.E;
-        if (hi < lo || hi > g.E || hi - lo > 4) { ++bad; continue; }
+        bad += csr_bad(e, NE, lo, hi, g.E, 4);
+        if (!csr_in_range(lo, hi, g.E, 4)) continue;
         bad += g.circular[u] && hi > lo;
         for (uint64_t i = lo; i < hi; ++i) {
             const uint64_t t = g.link_to[i];
             if (t >= NE) { ++bad; continue; }
             bad += g.circular[t >> 1] != 0;
             const uint64_t lo2 = g.link_off[t ^ 1], hi2 = g.link_off[(t ^ 1) + 1];
-            uint64_t dual = kRNoIndex;
-            if (hi2 >= lo2 && hi2 <= g.E && hi2 - lo2 <= 4)
+            uint64_t dual = kNoLink;
+            if (csr_in_range(lo2, hi2, g.E, 4))
                 for (uint64_t j = hi2; j > lo2; --j)
                     if (g.link_to[j - 1] == (uint32_t)(e ^ 1)) dual = j - 1;       // the first one
-            if (dual == kRNoIndex) { ++bad; continue; }
+            if (dual == kNoLink) { ++bad; continue; }
             if (support) bad += support[i] != support[dual];
             if (link_remove) bad += (link_remove[i] != 0) != (link_remove[dual] != 0);
         }
@@ -232,7 +215,7 @@ __global__ void __launch_bounds__(kCB) k_gr_count(uint64_t U, uint64_t E, const 
     for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i < work; i += stride) {
         if (i < U) {
             const uint64_t c = copies[i], a = offsets[i], b = offsets[i + 1];
-            const bool good = c >= 1 && c <= 4 && b >= a && b - a >= 23;
+            const bool good = c >= 1 && c <= 4 && !span_bad(a, b);
             bad += !good;
             extra[i] = good ? c - 1 : 0;
             if (good) { added += c - 1; bases += (c - 1) * (b - a); }
@@ -247,7 +230,7 @@ __global__ void __launch_bounds__(kCB) k_gr_count(uint64_t U, uint64_t E, const 
 
 __global__ void __launch_bounds__(kCB) k_gr_copybase(uint64_t U, const uint8_t* __restrict__ copies, const uint64_t* __restrict__ pre, uint32_t* __restrict__ copy_base) {
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
-    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) copy_base[u] = copies[u] > 1 ? (uint32_t)(U + pre[u]) : kRNone;
+    for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) copy_base[u] = copies[u] > 1 ? (uint32_t)(U + pre[u]) : kNoEnd;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -261,7 +244,7 @@ __global__ void __launch_bounds__(kCB) k_gr_checksplit(const GrGraph g, const ui
     unsigned long long bad = 0;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < g.U; u += stride) {
         const uint32_t c = copies[u];
-        bad += copy_base[u] != (c > 1 ? (uint32_t)(g.U + pre[u]) : kRNone);
+        bad += copy_base[u] != (c > 1 ? (uint32_t)(g.U + pre[u]) : kNoEnd);
         if (c == 1) continue;
         GrMatch m;
         const bool ok = pair && min_pair && !g.circular[u] && !gr_self(g.link_off, g.link_to, link_remove, u) &&
@@ -371,8 +354,8 @@ __global__ void __launch_bounds__(kCB) k_gr_links(const GrGraph g, const uint8_t
             const uint64_t t = g.link_to[j], v = t >> 1;
             uint64_t id = v;
             if (copies[v] > 1) {
-                const uint64_t dual = gr_find(g.link_off, g.link_to, t ^ 1, e ^ 1);
-                const uint32_t r = dual == kRNoIndex ? 0 : gr_owner(g, link_remove, copies, pair, min_pair, t ^ 1, (uint32_t)(dual - g.link_off[t ^ 1]));
+                const uint64_t dual = link_find(g.link_to, g.link_off[t ^ 1], g.link_off[(t ^ 1) + 1], e ^ 1);
+                const uint32_t r = dual == kNoLink ? 0 : gr_owner(g, link_remove, copies, pair, min_pair, t ^ 1, (uint32_t)(dual - g.link_off[t ^ 1]));
                 if (r) id = (uint64_t)copy_base[v] + r - 1;
             }
             if (at < E2) out_to[at] = (uint32_t)(2 * id + (t & 1));
@@ -387,44 +370,31 @@ __global__ void __launch_bounds__(kCB) k_gr_bases(uint64_t U, uint64_t U2, const
                                                  uint8_t* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t i = total_in + (uint64_t)blockIdx.x * kCB + threadIdx.x; i < total2; i += stride) {
-        uint64_t lo = U, hi = U2;                                  // new_off[U] == total_in <= i < new_off[U2]
-        while (hi - lo > 1) {                                      // at most 32 trips
-            const uint64_t mid = lo + ((hi - lo) >> 1);
-            if (new_off[mid] <= i) lo = mid; else hi = mid;
-        }
+        const uint64_t lo = last_le(new_off, U, U2, i);            // new_off[U] == total_in <= i < new_off[U2]; at most 32 trips
         const uint64_t u = origin[lo], src = offsets[u] + (i - new_off[lo]);
         if (src < offsets[u + 1]) out[i] = bases[src];
     }
 }
 
-// zeroes `ctr`, runs `launch`, reads it back. Synchronises `s`.
-template <class Launch>
-static hipError_t gr_counted(GrCounters* ctr, GrCounters* host, hipStream_t s, Launch&& launch) {
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GrCounters), s));
-    AIX_TRY(launch());
-    return chain_read(host, ctr, s);
-}
-
-static hipError_t gr_validate(const GrGraph& g, const uint64_t* support, const uint8_t* link_remove, GrCounters* ctr, bool* bad, hipStream_t s) {
-    GrCounters hc;
-    AIX_TRY(gr_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gr_validate, dim3(chain_grid(2 * g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g, support, link_remove, ctr);
+static hipError_t gr_validate(const GrGraph& g, const uint64_t* support, const uint8_t* link_remove, Counted<GrCounters>& ctr, bool* bad, hipStream_t s) {
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gr_validate, dim3(chain_grid(2 * g.U, 2 * kCB, chain_test_grid())), dim3(kCB), 0, s, g, support, link_remove, ctr.dev());
         return hipSuccess;
     }));
-    *bad = hc.bad != 0;
+    *bad = ctr.host.bad != 0;
     return hipSuccess;
 }
 
-// copies and offsets checked, extra[U + 1] scanned into pre[U + 1]; hc: added, extra_bases, removed. Synchronises `s`.
-static hipError_t gr_count(const GrGraph& g, const uint8_t* copies, const uint8_t* link_remove, GrCounters* ctr, GrCounters* hc, DevArr& extra, DevArr& pre, DevArr& tmp,
+// copies and offsets checked, extra[U + 1] scanned into pre[U + 1]; ctr.host: added, extra_bases, removed. Synchronises `s`.
+static hipError_t gr_count(const GrGraph& g, const uint8_t* copies, const uint8_t* link_remove, Counted<GrCounters>& ctr, DevArr& extra, DevArr& pre, DevArr& tmp,
                            hipStream_t s) {
     AIX_TRY(extra.alloc(8 * (g.U + 1)));
     AIX_TRY(pre.alloc(8 * (g.U + 1)));
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(GrCounters), s));
-    AIX_TRY_LAUNCH(k_gr_count, dim3(chain_grid(std::max(g.U + 1, g.E), 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.E, g.offsets, copies, link_remove,
-                   (uint64_t*)extra.p, ctr);
-    AIX_TRY(scan_u64((const uint64_t*)extra.p, (uint64_t*)pre.p, g.U + 1, tmp, s));
-    return chain_read(hc, ctr, s);
+    return ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gr_count, dim3(chain_grid(std::max(g.U + 1, g.E), 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, g.U, g.E, g.offsets, copies, link_remove,
+                       (uint64_t*)extra.p, ctr.dev());
+        return scan_u64((const uint64_t*)extra.p, (uint64_t*)pre.p, g.U + 1, tmp, s);
+    });
 }
 
 }  // namespace aix
@@ -434,7 +404,7 @@ static hipError_t gr_count(const GrGraph& g, const uint8_t* copies, const uint8_
 // ---------------------------------------------------------------------------------------------
 // the refusals every entry point shares, decided before anything is allocated or launched
 static int gr_check_sizes(uint64_t U, const void* offsets, const void* circular, const void* link_off, const void* link_to, uint64_t E) {
-    if (U > kRMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!offsets || !link_off) return AIX_ERR_ARG;
     if (U && !circular) return AIX_ERR_ARG;
     if (E && !link_to) return AIX_ERR_ARG;
@@ -444,7 +414,7 @@ static int gr_check_sizes(uint64_t U, const void* offsets, const void* circular,
 
 extern "C" int aix_thread_pairs_dev(uint64_t U, const uint64_t* d_link_off, const uint32_t* d_link_to, uint64_t E, uint64_t T, const uint32_t* d_step_unitig,
                                     const uint8_t* d_step_flag, const uint64_t* d_step_link, uint64_t* d_pair_support, uint64_t* n_pairs_out, void* stream) {
-    if (U > kRMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!n_pairs_out || E > 8 * U || T >= (1ull << 60)) return AIX_ERR_ARG;
     if (U && (!d_link_off || !d_pair_support)) return AIX_ERR_ARG;
     if (E && !d_link_to) return AIX_ERR_ARG;
@@ -452,23 +422,22 @@ extern "C" int aix_thread_pairs_dev(uint64_t U, const uint64_t* d_link_off, cons
     if (T == 0 || U == 0) { *n_pairs_out = 0; return AIX_OK; }
     hipStream_t s = (hipStream_t)stream;
     const uint64_t cap = chain_test_grid();
-    DevArr ctr_a(s);
-    AIXCHK(ctr_a.alloc(sizeof(GrCounters)));
-    GrCounters* ctr = (GrCounters*)ctr_a.p;
-    GrCounters hc;
-    AIXCHK(gr_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gr_linkoff, dim3(chain_grid(2 * U, 4 * kCB, cap)), dim3(kCB), 0, s, U, E, d_link_off, ctr);
+    Counted<GrCounters> ctr(s);
+    AIXCHK(ctr.init());
+    const GrCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gr_linkoff, dim3(chain_grid(2 * U, 4 * kCB, cap)), dim3(kCB), 0, s, U, E, d_link_off, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
     const dim3 grid(chain_grid(T, 2 * kCB, cap)), blk(kCB);
-    AIXCHK(gr_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_gr_pairs<true>, grid, blk, 0, s, U, E, d_link_off, d_link_to, T, d_step_unitig, d_step_flag, d_step_link, (unsigned long long*)d_pair_support, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_gr_pairs<true>, grid, blk, 0, s, U, E, d_link_off, d_link_to, T, d_step_unitig, d_step_flag, d_step_link, (unsigned long long*)d_pair_support, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
     if (hc.n_pairs) {
-        hipLaunchKernelGGL(k_gr_pairs<false>, grid, blk, 0, s, U, E, d_link_off, d_link_to, T, d_step_unitig, d_step_flag, d_step_link, (unsigned long long*)d_pair_support, ctr);
+        hipLaunchKernelGGL(k_gr_pairs<false>, grid, blk, 0, s, U, E, d_link_off, d_link_to, T, d_step_unitig, d_step_flag, d_step_link, (unsigned long long*)d_pair_support, ctr.dev());
         AIXCHK(hipGetLastError());
         AIXCHK(hipStreamSynchronize(s));
     }
@@ -490,18 +459,17 @@ extern "C" int aix_graph_resolve_mark_dev(uint64_t U, const uint64_t* d_offsets,
         hipStream_t s = (hipStream_t)stream;
         const uint64_t cap = chain_test_grid();
         const GrGraph g{U, E, d_offsets, d_circular, d_link_off, d_link_to};
-        DevArr ctr_a(s);
-        AIXCHK(ctr_a.alloc(sizeof(GrCounters)));
-        GrCounters* ctr = (GrCounters*)ctr_a.p;
-        GrCounters hc;
+        Counted<GrCounters> ctr(s);
+        AIXCHK(ctr.init());
+        const GrCounters& hc = ctr.host;
         bool bad = false;
         AIXCHK(gr_validate(g, d_link_support, nullptr, ctr, &bad, s));
         if (bad) return AIX_ERR_ARG;
-        AIXCHK(gr_counted(ctr, &hc, s, [&]() {
-            if (weak_on) AIX_TRY_LAUNCH(k_gr_weak, dim3(chain_grid(2 * U, 2 * kCB, cap)), dim3(kCB), 0, s, g, d_link_support, min_link_support, d_link_remove, ctr);
+        AIXCHK(ctr.run([&]() {
+            if (weak_on) AIX_TRY_LAUNCH(k_gr_weak, dim3(chain_grid(2 * U, 2 * kCB, cap)), dim3(kCB), 0, s, g, d_link_support, min_link_support, d_link_remove, ctr.dev());
             else if (E) AIX_TRY(hipMemsetAsync(d_link_remove, 0, E, s));
             AIX_TRY_LAUNCH(k_gr_split, dim3(chain_grid(U, 2 * kCB, cap)), dim3(kCB), 0, s, g, (const uint8_t*)d_link_remove, split_on ? d_pair_support : nullptr,
-                           min_pair_support, max_pair_noise, d_copies, ctr);
+                           min_pair_support, max_pair_noise, d_copies, ctr.dev());
             return hipSuccess;
         }));
         out[0] = hc.removed; out[1] = hc.n_split; out[2] = hc.added;
@@ -512,7 +480,7 @@ extern "C" int aix_graph_resolve_mark_dev(uint64_t U, const uint64_t* d_offsets,
 
 extern "C" int aix_graph_resolve_layout_dev(uint64_t U, const uint64_t* d_offsets, uint64_t E, const uint8_t* d_link_remove, const uint8_t* d_copies,
                                             uint32_t* d_copy_base, uint64_t* n_unitigs_out, uint64_t* total_bases_out, uint64_t* n_links_out, void* stream) {
-    if (U > kRMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_offsets || !n_unitigs_out || !total_bases_out || !n_links_out || E > 8 * U) return AIX_ERR_ARG;
     if ((U && (!d_copies || !d_copy_base)) || (E && !d_link_remove)) return AIX_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -521,14 +489,15 @@ extern "C" int aix_graph_resolve_layout_dev(uint64_t U, const uint64_t* d_offset
         return AIX_OK;
     }
     const GrGraph g{U, E, d_offsets, nullptr, nullptr, nullptr};
-    DevArr ctr_a(s), extra(s), pre(s), tmp(s);
-    AIXCHK(ctr_a.alloc(sizeof(GrCounters)));
-    GrCounters hc;
+    Counted<GrCounters> ctr(s);
+    DevArr extra(s), pre(s), tmp(s);
+    AIXCHK(ctr.init());
+    const GrCounters& hc = ctr.host;
     uint64_t total_in = 0;
     AIXCHK(hipMemcpyAsync(&total_in, d_offsets + U, 8, hipMemcpyDeviceToHost, s));
-    AIXCHK(gr_count(g, d_copies, d_link_remove, (GrCounters*)ctr_a.p, &hc, extra, pre, tmp, s));
+    AIXCHK(gr_count(g, d_copies, d_link_remove, ctr, extra, pre, tmp, s));
     if (hc.bad || hc.removed > E) return AIX_ERR_ARG;
-    if (U + hc.added > kRMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U + hc.added > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_gr_copybase, dim3(chain_grid(U, 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, U, d_copies, (const uint64_t*)pre.p, d_copy_base);
     AIXCHK(hipGetLastError());
     AIXCHK(hipStreamSynchronize(s));
@@ -547,7 +516,7 @@ extern "C" int aix_graph_resolve_emit_dev(uint64_t U, const uint64_t* d_offsets,
     const int st = gr_check_sizes(U, d_offsets, d_circular, d_link_off, d_link_to, E);
     if (st) return st;
     const uint64_t U2 = n_unitigs, E2 = n_links;
-    if (U2 > kRMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U2 > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_out_offsets || !d_out_link_off || U2 < U || U2 > 4 * U || E2 > E) return AIX_ERR_ARG;
     if (U && (!d_bases || !d_tf_sum || !d_tf_min || !d_tf_max || !d_copies || !d_copy_base || !d_out_bases || !d_out_circular || !d_out_tf_sum || !d_out_tf_min ||
               !d_out_tf_max || !d_unitig_origin))
@@ -566,20 +535,20 @@ extern "C" int aix_graph_resolve_emit_dev(uint64_t U, const uint64_t* d_offsets,
     const uint64_t cap = chain_test_grid();
     const dim3 blk(kCB);
     const GrGraph g{U, E, d_offsets, d_circular, d_link_off, d_link_to};
-    DevArr ctr_a(s), extra(s), pre(s), tmp(s), tmp2(s), rank(s), len(s), ndeg(s);
-    AIXCHK(ctr_a.alloc(sizeof(GrCounters)));
-    GrCounters* ctr = (GrCounters*)ctr_a.p;
-    GrCounters hc;
+    Counted<GrCounters> ctr(s);
+    DevArr extra(s), pre(s), tmp(s), tmp2(s), rank(s), len(s), ndeg(s);
+    AIXCHK(ctr.init());
+    const GrCounters& hc = ctr.host;
     bool bad = false;
     AIXCHK(gr_validate(g, nullptr, d_link_remove, ctr, &bad, s));
     if (bad) return AIX_ERR_ARG;
     uint64_t total_in = 0;
     AIXCHK(hipMemcpyAsync(&total_in, d_offsets + U, 8, hipMemcpyDeviceToHost, s));
-    AIXCHK(gr_count(g, d_copies, d_link_remove, ctr, &hc, extra, pre, tmp, s));
+    AIXCHK(gr_count(g, d_copies, d_link_remove, ctr, extra, pre, tmp, s));
     if (hc.bad || U + hc.added != U2 || total_in + hc.extra_bases != total_bases || hc.removed > E || E - hc.removed != E2) return AIX_ERR_ARG;
-    AIXCHK(gr_counted(ctr, &hc, s, [&]() {
+    AIXCHK(ctr.run([&]() {
         AIX_TRY_LAUNCH(k_gr_checksplit, dim3(chain_grid(U, 2 * kCB, cap)), blk, 0, s, g, d_link_remove, d_copies, (const uint64_t*)pre.p, d_copy_base, d_pair_support,
-                       min_pair_support, ctr);
+                       min_pair_support, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
@@ -629,13 +598,9 @@ extern "C" int aix_graph_resolve(uint64_t U, const uint64_t* offsets, const uint
     const uint64_t total_in = offsets[U];
     if (U && (total_in < 23 * U || total_in > (1ULL << 48))) return AIX_ERR_ARG;
     DevArr in[10], rm, cp, cb, oo, ob, oc, os, on, ox, ol, ot, og;
-    const void* src[10] = {offsets, bases, circular, tf_sum, tf_min, tf_max, link_off, link_to, link_support, pair_support};
-    const uint64_t bytes[10] = {8 * (U + 1), total_in, U, 8 * U, 4 * U, 4 * U, 8 * (2 * U + 1), 4 * E, 8 * E, 8 * 16 * U};
-    for (int i = 0; i < 10; ++i) {
-        if (!src[i]) continue;
-        AIXCHK(in[i].alloc(bytes[i]));
-        if (bytes[i]) AIXCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
-    }
+    const HostIn ins[10] = {{offsets, 8 * (U + 1)}, {bases, total_in}, {circular, U}, {tf_sum, 8 * U}, {tf_min, 4 * U}, {tf_max, 4 * U}, {link_off, 8 * (2 * U + 1)},
+                            {link_to, 4 * E}, {link_support, 8 * E}, {pair_support, 8 * 16 * U}};
+    AIXCHK(copy_in_host(in, ins, 10, true));                       // a null array (U == 0, E == 0, no support given) stays a null block
     AIXCHK(rm.alloc(E));
     AIXCHK(cp.alloc(U));
     AIXCHK(cb.alloc(4 * U));

@@ -1,7 +1,7 @@
 // aix_hostkit.hpp — private to the library: the host scaffolding that the subsystem files (one translation unit per subsystem behind the
-// C ABI) share. Error mapping, rocPRIM's two-call protocol, the epilogue of the host forms. Nothing here is on a hot path, and nothing
-// that only one file uses belongs here. The builder and counter files (aix_merge, aix_a2msd, aix_k1, aix_normalize, aix_count13,
-// aix_positions) keep raw pool blocks and their own error style and do not use it.
+// C ABI) share. Error mapping, rocPRIM's two-call protocol, the prologue and the epilogue of the host forms (copy_in_host, copy_out_host).
+// Nothing here is on a hot path, and nothing that only one file uses belongs here. The builder and counter files (aix_merge, aix_a2msd,
+// aix_k1, aix_normalize, aix_count13, aix_positions) keep raw pool blocks and their own error style and do not use it.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -86,6 +86,21 @@ static hipError_t scan_u64(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStr
 template <class KeyIt, class Key, class ValIt, class Val>
 static hipError_t sort_pairs(KeyIt keys_in, Key* keys_out, ValIt vals_in, Val* vals_out, uint64_t n, unsigned end_bit, DevArr& tmp, hipStream_t s) {
     return with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_pairs(t, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, s); });
+}
+
+// The prologue of a host form: in[i] becomes a device copy of block i of the table, on the null stream; zero bytes is still a block of its
+// own. skip_null: a null src is an input the caller did not give and its in[i] stays empty; without it every src is the caller's to check.
+struct HostIn {
+    const void* src;
+    uint64_t bytes;
+};
+static hipError_t copy_in_host(DevArr* in, const HostIn* ins, int n, bool skip_null = false) {
+    for (int i = 0; i < n; ++i) {
+        if (skip_null && !ins[i].src) continue;
+        AIX_TRY(in[i].alloc(ins[i].bytes));
+        if (ins[i].bytes) AIX_TRY(hipMemcpy(in[i].p, ins[i].src, ins[i].bytes, hipMemcpyHostToDevice));
+    }
+    return hipSuccess;
 }
 
 // The epilogue of a host form: every device block of the table as a malloc'd host copy (aix_free). A null dst is an output the caller

@@ -12,19 +12,19 @@
 //   layout   k_sc_ly_validate, k_sc_ly_init, k_sc_ly_jump per round (the host loop is chain_rank); on cycles k_sc_cy_init, k_sc_cy_jump per
 //            round, k_sc_cy_cut and the ranking again; k_sc_ly_place, a scan of the first members, k_sc_ly_assign
 //   emit     k_sc_ly_validate, k_sc_em_keys, a radix sort into member order, k_sc_em_validate, k_sc_em_ends; then a scan into
-//            scaffold_offsets, k_sc_em_members and k_sc_em_bases (one lane per output byte, a bisection over the members' first bytes)
+//            scaffold_offsets, k_sc_em_members and k_graph_em_bases<false> (one lane per output byte, a bisection over the members' first bytes)
+// What the graph files share (the counters holder, the predicates of the validate kernels, the written gap, that emit kernel) is in aix_graph.hpp.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 
 namespace aix {
 
-static constexpr uint32_t kSNone = 0xFFFFFFFFu;                   // join: none (AIX_BUBBLE_NONE)
+// (kNoEnd is the join of an unjoined end; the constants, the counters holder, the predicates of the validation and k_graph_em_bases: aix_graph.hpp)
 static constexpr uint64_t kSFlag = 1ULL << 63;                    // ranking state: terminal reached
-static constexpr uint64_t kSMaxU = 0x7FFFFFFFull - 4;             // the limit of the graph calls: an end must fit a 32-bit word
 static constexpr uint64_t kSNoKey = ~0ULL;                        // obs_key of a pair that is no observation
 static constexpr uint64_t kSLow = 0xFFFFFFFFull;
 
@@ -41,14 +41,6 @@ struct ScAggOp {
 struct ScAggOf {
     __host__ __device__ ScAgg operator()(uint32_t d) const { return ScAgg{1ull, (unsigned long long)d}; }
 };
-
-// zeroes `ctr`, runs `launch`, reads it back. Synchronises `s`.
-template <class Launch>
-static hipError_t sc_counted(ScCounters* ctr, ScCounters* host, hipStream_t s, Launch&& launch) {
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(ScCounters), s));
-    AIX_TRY(launch());
-    return chain_read(host, ctr, s);
-}
 
 // first index i in [lo, hi) with a[i] >= key (hi without one); a ascends on [lo, hi)
 __device__ __forceinline__ uint64_t sc_lower(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key) {
@@ -85,10 +77,7 @@ __global__ void __launch_bounds__(kCB) k_sc_ml_validate(uint64_t P, const uint64
                 bad += b >= a && b - a >= 23 && (uint64_t)step_pos[i] >= b - a - 22;      // (offsets that do not ascend: counted below)
             }
         }
-        if (i < U) {
-            const uint64_t a = offsets[i], b = offsets[i + 1];
-            bad += b < a || b - a < 23;
-        }
+        if (i < U) bad += span_bad(offsets[i], offsets[i + 1]);
     }
     count_add(bad, &ctr->bad);
 }
@@ -226,21 +215,17 @@ __global__ void __launch_bounds__(kCB) k_sc_mk_validate(const ScGraph g, ScCount
     const uint64_t NE = 2 * g.U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
-        if (!(e & 1)) {
-            const uint64_t a = g.offsets[e >> 1], b = g.offsets[(e >> 1) + 1];
-            bad += b < a || b - a < 23;
-        }
+        if (!(e & 1)) bad += span_bad(g.offsets[e >> 1], g.offsets[(e >> 1) + 1]);
         const uint64_t lo = g.off[e], hi = g.off[e + 1];
-        bad += e == 0 && lo != 0;
-        bad += e == NE - 1 && hi != g.S;
-        if (hi < lo || hi > g.S) { ++bad; continue; }
+        bad += csr_bad(e, NE, lo, hi, g.S, kAnyDegree);
+        if (!csr_in_range(lo, hi, g.S, kAnyDegree)) continue;
         for (uint64_t j = lo; j < hi; ++j) {
             const uint64_t t = g.to[j], c = g.count[j];
             if (t >= NE || (t >> 1) == (e >> 1) || c == 0) { ++bad; continue; }
             bad += j > lo && (uint64_t)g.to[j - 1] >= t;
             bad += g.dsum[j] / c > kSLow;
             const uint64_t lo2 = g.off[t ^ 1], hi2 = g.off[(t ^ 1) + 1];
-            if (hi2 < lo2 || hi2 > g.S) { ++bad; continue; }
+            if (!csr_in_range(lo2, hi2, g.S, kAnyDegree)) { ++bad; continue; }
             uint64_t a = lo2, b = hi2;                            // a bisection that ends whatever the list holds
             while (a < b) {
                 const uint64_t mid = a + ((b - a) >> 1);
@@ -281,7 +266,7 @@ __global__ void __launch_bounds__(kCB) k_sc_mk_join(const ScGraph g, uint32_t in
     const uint64_t NE = 2 * g.U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long n = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
-        uint32_t t = kSNone;
+        uint32_t t = kNoEnd;
         uint64_t c = 0, j = 0, j2 = 0;
         long long gap = 0;
         if (sc_best(g, e, min_pairs, dominance, min_bases, &j)) {
@@ -310,20 +295,14 @@ __global__ void __launch_bounds__(kCB) k_sc_ly_validate(uint64_t U, const uint64
     const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e < NE; e += stride) {
-        if (!(e & 1)) {
-            const uint64_t a = offsets[e >> 1], b = offsets[(e >> 1) + 1];
-            bad += b < a || b - a < 23;
-        }
+        if (!(e & 1)) bad += span_bad(offsets[e >> 1], offsets[(e >> 1) + 1]);
         const uint64_t t = join[e];
-        if (t == kSNone) continue;
-        if (t >= NE || (t >> 1) == (e >> 1) || (uint64_t)join[t ^ 1] != (e ^ 1)) { ++bad; continue; }
+        if (t == kNoEnd) continue;
+        if (!join_dual_ok(join, join_gap, NE, e, t)) { ++bad; continue; }
         if (join_count) bad += join_count[t ^ 1] != join_count[e];
-        bad += join_gap[t ^ 1] != join_gap[e];
     }
     count_add(bad, &ctr->bad);
 }
-
-__device__ __forceinline__ uint64_t sc_wgap(long long gap, uint32_t min_gap) { return (uint64_t)(gap > (long long)min_gap ? gap : (long long)min_gap); }
 
 // the state of the ranking per end p: nx = the exit end of the next contig (flagged: p is terminal), dist = the bases from the far side of
 // the join to there, hops = the members. cut (nullable): joins taken out of their cycles. total: the written gaps, each join once.
@@ -334,11 +313,11 @@ __global__ void __launch_bounds__(kCB) k_sc_ly_init(uint64_t NE, const uint64_t*
     unsigned long long open = 0, gaps = 0, ncut = 0;
     for (uint64_t p = (uint64_t)blockIdx.x * kCB + threadIdx.x; p < NE; p += stride) {
         const uint64_t t = join[p];
-        const bool is_cut = t != kSNone && cut && cut[p];
-        const bool linked = t != kSNone && !is_cut;
-        const uint64_t w = linked ? sc_wgap(join_gap[p], min_gap) : 0;
+        const bool is_cut = t != kNoEnd && cut && cut[p];
+        const bool linked = t != kNoEnd && !is_cut;
+        const uint64_t w = linked ? written_gap(join_gap[p], min_gap) : 0;
         nx[p] = linked ? t : (p | kSFlag);
-        dist[p] = linked ? w + (offsets[(t >> 1) + 1] - offsets[t >> 1]) : 0;
+        dist[p] = linked ? w + unit_len(offsets, t) : 0;
         hops[p] = linked;
         open += linked;
         if (linked && p < (t ^ 1)) gaps += w;
@@ -441,7 +420,7 @@ __global__ void __launch_bounds__(kCB) k_sc_ly_assign(uint64_t U, const uint32_t
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
         const uint64_t f = first_of[u];
-        scaffold[u] = f < U ? (uint32_t)sid[f] : kSNone;
+        scaffold[u] = f < U ? (uint32_t)sid[f] : kNoEnd;
     }
 }
 
@@ -493,7 +472,7 @@ __global__ void __launch_bounds__(kCB) k_sc_em_validate(const ScMap m, uint64_t*
         if (r != (pk & kSLow) + 1 || w >= m.U) { ++bad; continue; }
         const uint64_t e = 2 * w + (m.flag[w] & 1u);
         if ((uint64_t)m.join[e] != 2 * u + f) { ++bad; continue; }
-        bad += m.pos[u] != m.pos[w] + (m.offsets[w + 1] - m.offsets[w]) + sc_wgap(m.join_gap[e], m.min_gap);
+        bad += m.pos[u] != m.pos[w] + (m.offsets[w + 1] - m.offsets[w]) + written_gap(m.join_gap[e], m.min_gap);
     }
     count_add(bad, &ctr->bad);
 }
@@ -509,10 +488,10 @@ __global__ void __launch_bounds__(kCB) k_sc_em_ends(const ScMap m, const uint64_
         if (i0 >= i1 || i1 > m.U) { ++bad; slen[s] = 0; continue; }
         const uint64_t u = m.ids[i0], z = m.ids[i1 - 1], fu = m.flag[u] & 1u, fz = m.flag[z] & 1u;
         const uint64_t in = m.join[2 * u + (fu ^ 1)], out = m.join[2 * z + fz];
-        if (i1 - i0 == 1) bad += fu != 0 || in != kSNone || out != kSNone;
+        if (i1 - i0 == 1) bad += fu != 0 || in != kNoEnd || out != kNoEnd;
         else {
             bad += u >= z;
-            bad += !(in == kSNone && out == kSNone) && !(out == 2 * u + fu && in == ((2 * z + fz) ^ 1));
+            bad += !(in == kNoEnd && out == kNoEnd) && !(out == 2 * u + fu && in == ((2 * z + fz) ^ 1));
         }
         if (s) bad += (uint64_t)m.ids[moff[s - 1] < m.U ? moff[s - 1] : 0] >= u;
         const uint64_t len = m.pos[z] + (m.offsets[z + 1] - m.offsets[z]);
@@ -539,38 +518,20 @@ __global__ void __launch_bounds__(kCB) k_sc_em_members(const ScMap m, const uint
     }
 }
 
-// output byte i belongs to the last member whose first byte is at or before it: a base of that member, or the gap behind it
-__global__ void __launch_bounds__(kCB) k_sc_em_bases(uint64_t U, uint64_t total, const uint64_t* __restrict__ offsets, const uint8_t* __restrict__ bases,
-                                                    const uint32_t* __restrict__ member, const uint64_t* __restrict__ mstart, uint8_t* __restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kCB;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i < total; i += stride) {
-        uint64_t lo = 0, hi = U;                                   // mstart[0] == 0 <= i
-        while (hi - lo > 1) {                                      // at most 31 trips
-            const uint64_t mid = lo + ((hi - lo) >> 1);
-            if (mstart[mid] <= i) lo = mid; else hi = mid;
-        }
-        const uint64_t w = member[lo], u = w >> 1, a = offsets[u], len = offsets[u + 1] - a, x = i - mstart[lo];
-        uint8_t c = 'N';
-        if (x < len) {
-            c = bases[w & 1 ? a + len - 1 - x : a + x];
-            if (w & 1) c ^= (c & 2) ? 0x04 : 0x15;
-        }
-        out[i] = c;
-    }
-}
+// (the bases of the scaffolds: k_graph_em_bases<false>, aix_graph.hpp)
 
-// the ranking of the 2 U ends over `join` less `cut`: nx / dist / hops in the buffers *cn, *cd, *ch on return. hc: the counters of the init.
-static hipError_t sc_rank(uint64_t U, const uint64_t* offsets, const uint32_t* join, const long long* join_gap, uint32_t min_gap, const uint8_t* cut, ScCounters* ctr,
-                          ScCounters* hc, uint64_t** cn, uint64_t** cd, uint32_t** ch, uint64_t** on, uint64_t** od, uint32_t** oh, uint64_t* open, hipStream_t s) {
+// the ranking of the 2 U ends over `join` less `cut`: nx / dist / hops in the buffers *cn, *cd, *ch on return. ctr.host: the counters of the init.
+static hipError_t sc_rank(uint64_t U, const uint64_t* offsets, const uint32_t* join, const long long* join_gap, uint32_t min_gap, const uint8_t* cut,
+                          Counted<ScCounters>& ctr, uint64_t** cn, uint64_t** cd, uint32_t** ch, uint64_t** on, uint64_t** od, uint32_t** oh, uint64_t* open, hipStream_t s) {
     const uint64_t NE = 2 * U, cap = chain_test_grid();
     const dim3 blk(kCB), grid(chain_grid(NE, 4 * kCB, cap));
-    AIX_TRY(sc_counted(ctr, hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_ly_init, grid, blk, 0, s, NE, offsets, join, join_gap, min_gap, cut, *cn, *cd, *ch, ctr);
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_ly_init, grid, blk, 0, s, NE, offsets, join, join_gap, min_gap, cut, *cn, *cd, *ch, ctr.dev());
         return hipSuccess;
     }));
-    *open = hc->unflagged[0];
-    return chain_rank(U, ctr->unflagged, open, s, [&](int r) {
-        AIX_TRY_LAUNCH(k_sc_ly_jump, grid, blk, 0, s, NE, (const uint64_t*)*cn, (const uint64_t*)*cd, (const uint32_t*)*ch, *on, *od, *oh, &ctr->unflagged[r]);
+    *open = ctr.host.unflagged[0];
+    return chain_rank(U, ctr.dev()->unflagged, open, s, [&](int r) {
+        AIX_TRY_LAUNCH(k_sc_ly_jump, grid, blk, 0, s, NE, (const uint64_t*)*cn, (const uint64_t*)*cd, (const uint32_t*)*ch, *on, *od, *oh, &ctr.dev()->unflagged[r]);
         std::swap(*cn, *on);
         std::swap(*cd, *od);
         std::swap(*ch, *oh);
@@ -587,7 +548,7 @@ extern "C" int aix_mate_links_dev(uint64_t P, const uint64_t* d_offs, const uint
                                   const uint32_t* d_step_pos, const uint8_t* d_step_flag, const uint32_t* d_q_first, const uint32_t* d_q_last, uint64_t U,
                                   const uint64_t* d_offsets, const uint8_t* d_circular, uint32_t min_anchor_windows, uint32_t max_insert, uint64_t* d_insert_hist,
                                   uint64_t* d_obs_key, uint32_t* d_obs_d, uint64_t* d_counts, void* stream) {
-    if (U > kSMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_counts || !d_offsets || !d_insert_hist || min_anchor_windows < 1 || max_insert < 1 || max_insert > (1u << 20) || P >= (1ull << 60) || T >= (1ull << 60))
         return AIX_ERR_ARG;
     if (P && (!d_offs || !d_seq_step_off || !d_obs_key || !d_obs_d)) return AIX_ERR_ARG;
@@ -603,19 +564,18 @@ extern "C" int aix_mate_links_dev(uint64_t P, const uint64_t* d_offs, const uint
     }
     const uint64_t cap = chain_test_grid();
     const dim3 blk(kCB);
-    DevArr ctr_a(s);
-    AIXCHK(ctr_a.alloc(sizeof(ScCounters)));
-    ScCounters* ctr = (ScCounters*)ctr_a.p;
-    ScCounters hc;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
+    Counted<ScCounters> ctr(s);
+    AIXCHK(ctr.init());
+    const ScCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
         AIX_TRY_LAUNCH(k_sc_ml_validate, dim3(chain_grid(std::max(std::max(2 * P, T), U), 2 * kCB, cap)), blk, 0, s, P, d_offs, d_seq_step_off, T, d_step_unitig, d_step_pos,
-                       d_q_first, d_q_last, U, d_offsets, ctr);
+                       d_q_first, d_q_last, U, d_offsets, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
+    AIXCHK(ctr.run([&]() {
         AIX_TRY_LAUNCH(k_sc_ml_pairs, dim3(chain_grid(P, kCB, cap)), blk, 0, s, P, d_offs, d_seq_step_off, d_step_unitig, d_step_pos, d_step_flag, d_q_first, d_q_last,
-                       d_offsets, d_circular, (uint64_t)min_anchor_windows, (long long)max_insert, (unsigned long long*)d_insert_hist, d_obs_key, d_obs_d, ctr);
+                       d_offsets, d_circular, (uint64_t)min_anchor_windows, (long long)max_insert, (unsigned long long*)d_insert_hist, d_obs_key, d_obs_d, ctr.dev());
         return hipSuccess;
     }));
     const uint64_t kinds[4] = {hc.kind[0], hc.kind[1], hc.kind[2], hc.kind[3]};
@@ -626,7 +586,7 @@ extern "C" int aix_mate_links_dev(uint64_t P, const uint64_t* d_offs, const uint
 
 extern "C" int aix_mate_bundle_dev(uint64_t N, const uint64_t* d_obs_key, const uint32_t* d_obs_d, uint64_t U, uint64_t* d_slink_off, uint32_t* d_slink_to,
                                    uint64_t* d_slink_count, uint64_t* d_slink_dsum, uint64_t cap, uint64_t* total_out, void* stream) {
-    if (U > kSMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_slink_off || !total_out || N >= (1ull << 60)) return AIX_ERR_ARG;
     if (N && (!d_obs_key || !d_obs_d)) return AIX_ERR_ARG;
     if (cap && (!d_slink_to || !d_slink_count || !d_slink_dsum)) return AIX_ERR_ARG;
@@ -634,14 +594,14 @@ extern "C" int aix_mate_bundle_dev(uint64_t N, const uint64_t* d_obs_key, const 
     hipStream_t s = (hipStream_t)stream;
     const uint64_t NE = 2 * U, grid_cap = chain_test_grid();
     const dim3 blk(kCB);
-    DevArr ctr_a(s), k2(s), d2(s), uniq(s), agg(s), cnt(s), dk(s), di(s), dk2(s), di2(s), tmp(s), tmp2(s), tmp3(s);
+    Counted<ScCounters> ctr(s);
+    DevArr k2(s), d2(s), uniq(s), agg(s), cnt(s), dk(s), di(s), dk2(s), di2(s), tmp(s), tmp2(s), tmp3(s);
     uint64_t B = 0;
     if (N) {
-        AIXCHK(ctr_a.alloc(sizeof(ScCounters)));
-        ScCounters* ctr = (ScCounters*)ctr_a.p;
-        ScCounters hc;
-        AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-            AIX_TRY_LAUNCH(k_sc_bd_validate, dim3(chain_grid(N, 4 * kCB, grid_cap)), blk, 0, s, N, d_obs_key, d_obs_d, U, ctr);
+        AIXCHK(ctr.init());
+        const ScCounters& hc = ctr.host;
+        AIXCHK(ctr.run([&]() {
+            AIX_TRY_LAUNCH(k_sc_bd_validate, dim3(chain_grid(N, 4 * kCB, grid_cap)), blk, 0, s, N, d_obs_key, d_obs_d, U, ctr.dev());
             return hipSuccess;
         }));
         if (hc.bad) return AIX_ERR_ARG;
@@ -688,7 +648,7 @@ extern "C" int aix_mate_bundle_dev(uint64_t N, const uint64_t* d_obs_key, const 
 
 // the refusals the calls over a scaffold graph share, decided before anything is allocated or launched
 static int sc_check_sizes(uint64_t U, const void* offsets, const void* circular) {
-    if (U > kSMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!offsets || (U && !circular)) return AIX_ERR_ARG;
     return AIX_OK;
 }
@@ -707,17 +667,16 @@ extern "C" int aix_scaffold_mark_dev(uint64_t U, const uint64_t* d_offsets, cons
     const uint64_t cap = chain_test_grid();
     const dim3 blk(kCB), grid(chain_grid(2 * U, kCB, cap));
     const ScGraph g{U, S, d_offsets, d_circular, d_slink_off, d_slink_to, d_slink_count, d_slink_dsum};
-    DevArr ctr_a(s);
-    AIXCHK(ctr_a.alloc(sizeof(ScCounters)));
-    ScCounters* ctr = (ScCounters*)ctr_a.p;
-    ScCounters hc;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_mk_validate, grid, blk, 0, s, g, ctr);
+    Counted<ScCounters> ctr(s);
+    AIXCHK(ctr.init());
+    const ScCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_mk_validate, grid, blk, 0, s, g, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_mk_join, grid, blk, 0, s, g, insert_size, min_pairs, dominance, min_contig_bases, d_join, d_join_count, (long long*)d_join_gap, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_mk_join, grid, blk, 0, s, g, insert_size, min_pairs, dominance, min_contig_bases, d_join, d_join_count, (long long*)d_join_gap, ctr.dev());
         return hipSuccess;
     }));
     *n_joins_out = hc.n;
@@ -727,7 +686,7 @@ extern "C" int aix_scaffold_mark_dev(uint64_t U, const uint64_t* d_offsets, cons
 extern "C" int aix_scaffold_layout_dev(uint64_t U, const uint64_t* d_offsets, const uint32_t* d_join, const uint64_t* d_join_count, const int64_t* d_join_gap,
                                        uint32_t min_gap, uint32_t* d_contig_scaffold, uint32_t* d_contig_rank, uint64_t* d_contig_pos, uint8_t* d_contig_flag,
                                        uint64_t* n_scaffolds_out, uint64_t* total_bases_out, uint64_t* n_cut_out, void* stream) {
-    if (U > kSMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_offsets || !n_scaffolds_out || !total_bases_out || !n_cut_out || min_gap < 1) return AIX_ERR_ARG;
     if (U && (!d_join || !d_join_count || !d_join_gap || !d_contig_scaffold || !d_contig_rank || !d_contig_pos || !d_contig_flag)) return AIX_ERR_ARG;
     if (U == 0) { *n_scaffolds_out = 0; *total_bases_out = 0; *n_cut_out = 0; return AIX_OK; }
@@ -735,12 +694,12 @@ extern "C" int aix_scaffold_layout_dev(uint64_t U, const uint64_t* d_offsets, co
     const uint64_t NE = 2 * U, cap = chain_test_grid();
     const dim3 blk(kCB), grid(chain_grid(NE, 4 * kCB, cap));
     const long long* gap = (const long long*)d_join_gap;
-    DevArr ctr_a(s), n0(s), d0(s), h0(s), n1(s), d1(s), h1(s), cs0(s), ck0(s), cs1(s), ck1(s), cut(s), first(s), isf(s), sid(s), tmp(s);
-    AIXCHK(ctr_a.alloc(sizeof(ScCounters)));
-    ScCounters* ctr = (ScCounters*)ctr_a.p;
-    ScCounters hc;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_ly_validate, grid, blk, 0, s, U, d_offsets, d_join, d_join_count, gap, ctr);
+    Counted<ScCounters> ctr(s);
+    DevArr n0(s), d0(s), h0(s), n1(s), d1(s), h1(s), cs0(s), ck0(s), cs1(s), ck1(s), cut(s), first(s), isf(s), sid(s), tmp(s);
+    AIXCHK(ctr.init());
+    const ScCounters& hc = ctr.host;
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_ly_validate, grid, blk, 0, s, U, d_offsets, d_join, d_join_count, gap, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
@@ -753,7 +712,7 @@ extern "C" int aix_scaffold_layout_dev(uint64_t U, const uint64_t* d_offsets, co
     uint64_t *cn = (uint64_t*)n0.p, *cd = (uint64_t*)d0.p, *on = (uint64_t*)n1.p, *od = (uint64_t*)d1.p;
     uint32_t *ch = (uint32_t*)h0.p, *oh = (uint32_t*)h1.p;
     uint64_t open = 0;
-    AIXCHK(sc_rank(U, d_offsets, d_join, gap, min_gap, nullptr, ctr, &hc, &cn, &cd, &ch, &on, &od, &oh, &open, s));
+    AIXCHK(sc_rank(U, d_offsets, d_join, gap, min_gap, nullptr, ctr, &cn, &cd, &ch, &on, &od, &oh, &open, s));
     if (open) {                                                    // only ends on cycles are left: every cycle loses its weakest join
         AIXCHK(cs0.alloc(4 * NE));
         AIXCHK(ck0.alloc(8 * NE));
@@ -773,16 +732,16 @@ extern "C" int aix_scaffold_layout_dev(uint64_t U, const uint64_t* d_offsets, co
         }
         hipLaunchKernelGGL(k_sc_cy_cut, grid, blk, 0, s, NE, (const uint64_t*)cn, d_join, d_join_count, (const uint64_t*)k, (uint8_t*)cut.p);
         AIXCHK(hipGetLastError());
-        AIXCHK(sc_rank(U, d_offsets, d_join, gap, min_gap, (const uint8_t*)cut.p, ctr, &hc, &cn, &cd, &ch, &on, &od, &oh, &open, s));
+        AIXCHK(sc_rank(U, d_offsets, d_join, gap, min_gap, (const uint8_t*)cut.p, ctr, &cn, &cd, &ch, &on, &od, &oh, &open, s));
         if (open) { set_last_error("aix_scaffold_layout_dev: ends left open behind the cycle cut"); return AIX_ERR_HIP; }
     }
     const uint64_t gaps = hc.total, n_cut = hc.cut;
     AIXCHK(first.alloc(4 * U));
     AIXCHK(isf.alloc(8 * (U + 1)));
     AIXCHK(sid.alloc(8 * (U + 1)));
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
+    AIXCHK(ctr.run([&]() {
         AIX_TRY_LAUNCH(k_sc_ly_place, dim3(chain_grid(U + 1, 4 * kCB, cap)), blk, 0, s, U, d_offsets, (const uint64_t*)cn, (const uint64_t*)cd, (const uint32_t*)ch,
-                       (uint32_t*)first.p, d_contig_rank, d_contig_pos, d_contig_flag, (uint64_t*)isf.p, ctr);
+                       (uint32_t*)first.p, d_contig_rank, d_contig_pos, d_contig_flag, (uint64_t*)isf.p, ctr.dev());
         return hipSuccess;
     }));
     AIXCHK(scan_u64((const uint64_t*)isf.p, (uint64_t*)sid.p, U + 1, tmp, s));
@@ -799,7 +758,7 @@ extern "C" int aix_scaffold_emit_dev(uint64_t U, const uint64_t* d_offsets, cons
                                      const uint32_t* d_contig_scaffold, const uint32_t* d_contig_rank, const uint64_t* d_contig_pos, const uint8_t* d_contig_flag,
                                      uint64_t n_scaffolds, uint64_t total_bases, uint64_t* d_scaffold_offsets, uint8_t* d_scaffold_bases, uint64_t* d_member_off,
                                      uint32_t* d_member, int64_t* d_member_gap, void* stream) {
-    if (U > kSMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     const uint64_t Sc = n_scaffolds;
     if (!d_offsets || !d_scaffold_offsets || !d_member_off || min_gap < 1 || Sc > U || (U && !Sc)) return AIX_ERR_ARG;
     if (U && (!d_bases || !d_join || !d_join_gap || !d_contig_scaffold || !d_contig_rank || !d_contig_pos || !d_contig_flag || !d_scaffold_bases || !d_member ||
@@ -816,14 +775,14 @@ extern "C" int aix_scaffold_emit_dev(uint64_t U, const uint64_t* d_offsets, cons
     const uint64_t cap = chain_test_grid();
     const dim3 blk(kCB);
     const long long* gap = (const long long*)d_join_gap;
-    DevArr ctr_a(s), keys(s), keys2(s), ids2(s), moff(s), slen(s), mstart(s), tmp(s), tmp2(s);
-    AIXCHK(ctr_a.alloc(sizeof(ScCounters)));
-    ScCounters* ctr = (ScCounters*)ctr_a.p;
-    ScCounters hc;
+    Counted<ScCounters> ctr(s);
+    DevArr keys(s), keys2(s), ids2(s), moff(s), slen(s), mstart(s), tmp(s), tmp2(s);
+    AIXCHK(ctr.init());
+    const ScCounters& hc = ctr.host;
     AIXCHK(keys.alloc(8 * U));
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_ly_validate, dim3(chain_grid(2 * U, 4 * kCB, cap)), blk, 0, s, U, d_offsets, d_join, (const uint64_t*)nullptr, gap, ctr);
-        AIX_TRY_LAUNCH(k_sc_em_keys, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, U, Sc, d_contig_scaffold, d_contig_rank, d_contig_flag, (uint64_t*)keys.p, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_ly_validate, dim3(chain_grid(2 * U, 4 * kCB, cap)), blk, 0, s, U, d_offsets, d_join, (const uint64_t*)nullptr, gap, ctr.dev());
+        AIX_TRY_LAUNCH(k_sc_em_keys, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, U, Sc, d_contig_scaffold, d_contig_rank, d_contig_flag, (uint64_t*)keys.p, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
@@ -833,13 +792,13 @@ extern "C" int aix_scaffold_emit_dev(uint64_t U, const uint64_t* d_offsets, cons
     AIXCHK(slen.alloc(8 * (Sc + 1)));
     AIXCHK(sort_pairs((const uint64_t*)keys.p, (uint64_t*)keys2.p, rocprim::counting_iterator<uint32_t>(0), (uint32_t*)ids2.p, U, 64u, tmp, s));
     const ScMap m{U, Sc, d_offsets, d_join, gap, d_contig_pos, d_contig_flag, (const uint64_t*)keys2.p, (const uint32_t*)ids2.p, min_gap};
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_em_validate, dim3(chain_grid(U + 1, 2 * kCB, cap)), blk, 0, s, m, (uint64_t*)moff.p, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_em_validate, dim3(chain_grid(U + 1, 2 * kCB, cap)), blk, 0, s, m, (uint64_t*)moff.p, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad) return AIX_ERR_ARG;
-    AIXCHK(sc_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_sc_em_ends, dim3(chain_grid(Sc + 1, 2 * kCB, cap)), blk, 0, s, m, (const uint64_t*)moff.p, (uint64_t*)slen.p, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_sc_em_ends, dim3(chain_grid(Sc + 1, 2 * kCB, cap)), blk, 0, s, m, (const uint64_t*)moff.p, (uint64_t*)slen.p, ctr.dev());
         return hipSuccess;
     }));
     if (hc.bad || hc.total != total_bases) return AIX_ERR_ARG;
@@ -850,8 +809,8 @@ extern "C" int aix_scaffold_emit_dev(uint64_t U, const uint64_t* d_offsets, cons
     hipLaunchKernelGGL(k_sc_em_members, dim3(chain_grid(U, 4 * kCB, cap)), blk, 0, s, m, (const uint64_t*)d_scaffold_offsets, d_member, (long long*)d_member_gap,
                        (uint64_t*)mstart.p);
     AIXCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_sc_em_bases, dim3(chain_grid(total_bases, 4 * kCB, cap)), blk, 0, s, U, total_bases, d_offsets, d_bases, (const uint32_t*)d_member,
-                       (const uint64_t*)mstart.p, d_scaffold_bases);
+    hipLaunchKernelGGL(k_graph_em_bases<false>, dim3(chain_grid(total_bases, 4 * kCB, cap)), blk, 0, s, U, total_bases, d_offsets, d_bases, (const uint32_t*)d_member,
+                       (const uint8_t*)nullptr, (const uint64_t*)mstart.p, d_scaffold_bases);
     AIXCHK(hipGetLastError());
     AIXCHK(hipStreamSynchronize(s));
     return AIX_OK;
@@ -875,12 +834,8 @@ extern "C" int aix_scaffold(uint64_t U, const uint64_t* offsets, const uint8_t* 
     const uint64_t total_in = offsets[U];
     if (U && (total_in < 23 * U || total_in > (1ULL << 48))) return AIX_ERR_ARG;
     DevArr in[5], lo, lt, lc, ld, jn, jc, jg, cs, cr, cp, cf, so, sb, mo, mm, mg;
-    const void* src[5] = {offsets, bases, circular, obs_key, obs_d};
-    const uint64_t bytes[5] = {8 * (U + 1), total_in, U, 8 * N, 4 * N};
-    for (int i = 0; i < 5; ++i) {
-        AIXCHK(in[i].alloc(bytes[i]));
-        if (bytes[i]) AIXCHK(hipMemcpy(in[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
-    }
+    const HostIn ins[5] = {{offsets, 8 * (U + 1)}, {bases, total_in}, {circular, U}, {obs_key, 8 * N}, {obs_d, 4 * N}};
+    AIXCHK(copy_in_host(in, ins, 5));
     const uint64_t* d_off = (const uint64_t*)in[0].p;
     uint64_t S = 0, n_joins = 0, Sc = 0, total = 0, n_cut = 0;
     AIXCHK(lo.alloc(8 * (2 * U + 1)));

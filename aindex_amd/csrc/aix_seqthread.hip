@@ -2,8 +2,9 @@
 // maximal run of windows that follow each other on one unitig), the link traversed between adjacent records, and the number of sequences
 // that traverse every link. Two helpers carry the per-kid map there: aix_graph_kidmap_dev composes it with the map of one compaction
 // round, aix_thread_nodes_dev packs it into one word per kid. The contract is stated above the declarations in include/aindex_hip.h;
-// DESIGN 5l has the derivations and the resources. The chain of aix_seq_thread_dev (one plain launch per step; integer only, no LDS, no
-// grid-wide barrier, no spin-wait):
+// DESIGN 5l has the derivations and the resources. What the graph files share (the counters holder, the predicates of the validate
+// kernels, the link search and the bisection) is in aix_graph.hpp. The chain of aix_seq_thread_dev (one plain launch per step; integer
+// only, no LDS, no grid-wide barrier, no spin-wait):
 //   validate k_st_validate: one lane per node word, per unitig and per end; nothing below runs on arrays that fail it
 //   windows  k_st_windows: one lane per sequence, its windows max(0, L - 22); a scan gives woff[M + 1], the flat window space of W windows
 //   probe    k_st_probe: one lane per window, wave-uniform loop: the 23 bytes at their place in the sequence, the kid by slot23_wave, ONE
@@ -18,14 +19,13 @@
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 #include "aix_probe.hpp"
 #include "aix_seqhits.hpp"
 
 namespace aix {
 
 static constexpr uint64_t kStDead = ~0ULL;                        // node word of a dead kid, scratch word of a window without a node
-static constexpr uint64_t kStMaxU = 0x7FFFFFFFull - 4;            // the limit of the graph calls: an end must fit a 32-bit word
 static constexpr uint64_t kStPosMask = 0x7FFFFFFFull;
 
 struct StCounters {                                               // one zeroed record per call
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(kCB) k_st_kidmap(uint64_t n, const uint64_t* k
                 const uint64_t m = hi - lo - 22, base = unitig_pos[u];
                 const uint32_t f = kid_flag[kid], uf = unitig_flag[u];
                 const uint64_t add = (uf & 1u) ? m - 1 - p : p;
-                if ((uint64_t)c >= kStMaxU || base > 0xFFFFFFFFull - add) { ++bad; continue; }
+                if ((uint64_t)c >= kUnitLimit || base > 0xFFFFFFFFull - add) { ++bad; continue; }
                 nu = c;
                 np = (uint32_t)(base + add);
                 nf = ((f ^ uf) & 1u) | ((f | uf) & 2u);
@@ -127,16 +127,8 @@ __global__ void __launch_bounds__(kCB) k_st_validate(const StGraph g, StCounters
                 }
             }
         }
-        if (i < g.U) {
-            const uint64_t a = g.offsets[i], b = g.offsets[i + 1];
-            bad += b < a || b - a < 23;
-        }
-        if (i < NE) {
-            const uint64_t lo = g.link_off[i], hi = g.link_off[i + 1];
-            bad += i == 0 && lo != 0;
-            bad += i == NE - 1 && hi != g.E;
-            bad += hi < lo || hi > g.E || hi - lo > 4;
-        }
+        if (i < g.U) bad += span_bad(g.offsets[i], g.offsets[i + 1]);
+        if (i < NE) bad += csr_bad(i, NE, g.link_off[i], g.link_off[i + 1], g.E, 4);
     }
     count_add(bad, &ctr->bad);
 }
@@ -156,7 +148,7 @@ __global__ void __launch_bounds__(kCB) k_st_windows(const uint64_t* __restrict__
     count_add(bad, &ctr->bad);
 }
 
-// the last j in [from, n) with a[j] <= key; a[from] <= key < a[n]. A gallop from `from`, then a bisection.
+// the last j in [from, n) with a[j] <= key; a[from] <= key < a[n]. A gallop from `from`, then the bisection of aix_graph.hpp.
 __device__ __forceinline__ uint64_t st_last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t from, uint64_t key) {
     uint64_t lo = from, step = 1, hi;
     for (;;) {
@@ -165,11 +157,7 @@ __device__ __forceinline__ uint64_t st_last_le(const uint64_t* __restrict__ a, u
         lo = hi;
         step <<= 1;
     }
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= key) lo = mid; else hi = mid;
-    }
-    return lo;
+    return last_le(a, lo, hi, key);
 }
 
 // Pass 1. word[i]: the node of window i with bit 0 = the strand the window traverses its unitig in (flag bit 0 xor "the window is the
@@ -247,10 +235,8 @@ __global__ void __launch_bounds__(kCB) k_st_seqoff(const uint64_t* __restrict__ 
 __device__ __forceinline__ uint64_t st_find_link(const StGraph& g, uint64_t e, uint64_t t) {
     if (e >= 2 * g.U) return AIX_THREAD_BROKEN;
     const uint64_t lo = g.link_off[e], hi = g.link_off[e + 1];
-    if (hi < lo || hi > g.E || hi - lo > 4) return AIX_THREAD_BROKEN;
-    for (uint64_t j = lo; j < hi; ++j)
-        if ((uint64_t)g.link_to[j] == t) return j;
-    return AIX_THREAD_BROKEN;
+    if (!csr_in_range(lo, hi, g.E, 4)) return AIX_THREAD_BROKEN;
+    return link_find(g.link_to, lo, hi, t, AIX_THREAD_BROKEN);
 }
 
 struct StOut {
@@ -305,24 +291,14 @@ __global__ void __launch_bounds__(kCB) k_st_steps(const StGraph g, const uint64_
     }
 }
 
-// zeroes `ctr`, runs `launch`, reads it back. Synchronises `s`.
-template <class Launch>
-static hipError_t st_counted(StCounters* ctr, StCounters* host, hipStream_t s, Launch&& launch) {
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(StCounters), s));
-    AIX_TRY(launch());
-    return chain_read(host, ctr, s);
-}
-
 static hipError_t st_validate(const StGraph& g, bool* bad, hipStream_t s) {
-    DevArr ctr_a(s);
-    AIX_TRY(ctr_a.alloc(sizeof(StCounters)));
-    StCounters* ctr = (StCounters*)ctr_a.p;
-    StCounters hc;
-    AIX_TRY(st_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_st_validate, dim3(chain_grid(std::max(g.n, 2 * g.U), 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, g, ctr);
+    Counted<StCounters> ctr(s);
+    AIX_TRY(ctr.init());
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_st_validate, dim3(chain_grid(std::max(g.n, 2 * g.U), 4 * kCB, chain_test_grid())), dim3(kCB), 0, s, g, ctr.dev());
         return hipSuccess;
     }));
-    *bad = hc.bad != 0;
+    *bad = ctr.host.bad != 0;
     return hipSuccess;
 }
 
@@ -340,19 +316,18 @@ static hipError_t st_prepare(const aix_index* h, const StGraph& g, const uint8_t
     const dim3 blk(kCB);
     *bad = false;
     R.W = R.total = 0;
-    DevArr ctr_a(s), nwin(s);
-    AIX_TRY(ctr_a.alloc(sizeof(StCounters)));
+    Counted<StCounters> ctr(s);
+    DevArr nwin(s);
+    AIX_TRY(ctr.init());
     AIX_TRY(sh_alloc(nwin, M + 1, 8));
     AIX_TRY(sh_alloc(R.woff, M + 1, 8));
-    StCounters* ctr = (StCounters*)ctr_a.p;
-    StCounters hc;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(StCounters), s));
-    AIX_TRY_LAUNCH(k_st_windows, dim3(chain_grid(M + 1, 4 * kCB, cap)), blk, 0, s, d_offs, M, (uint64_t*)nwin.p, ctr);
-    AIX_TRY(scan_u64((const uint64_t*)nwin.p, (uint64_t*)R.woff.p, M + 1, R.tmp, s));
     uint64_t W = 0;
-    AIX_TRY(hipMemcpyAsync(&W, (const uint64_t*)R.woff.p + M, 8, hipMemcpyDeviceToHost, s));
-    AIX_TRY(chain_read(&hc, ctr, s));
-    if (hc.bad || (W && !d_seqs)) { *bad = true; return hipSuccess; }
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_st_windows, dim3(chain_grid(M + 1, 4 * kCB, cap)), blk, 0, s, d_offs, M, (uint64_t*)nwin.p, ctr.dev());
+        AIX_TRY(scan_u64((const uint64_t*)nwin.p, (uint64_t*)R.woff.p, M + 1, R.tmp, s));
+        return hipMemcpyAsync(&W, (const uint64_t*)R.woff.p + M, 8, hipMemcpyDeviceToHost, s);
+    }));
+    if (ctr.host.bad || (W && !d_seqs)) { *bad = true; return hipSuccess; }
     R.W = W;
     if (W == 0) {
         AIX_TRY(hipMemsetAsync(d_seq_step_off, 0, 8 * (M + 1), s));
@@ -392,19 +367,17 @@ extern "C" int aix_graph_kidmap_dev(uint64_t n, const uint64_t* d_kid_unitig, co
     if (U && (!d_unitig_contig || !d_unitig_pos || !d_unitig_flag)) return AIX_ERR_ARG;
     if (n == 0) return AIX_OK;
     hipStream_t s = (hipStream_t)stream;
-    DevArr ctr_a(s);
-    AIXCHK(ctr_a.alloc(sizeof(StCounters)));
-    StCounters* ctr = (StCounters*)ctr_a.p;
-    StCounters hc;
+    Counted<StCounters> ctr(s);
+    AIXCHK(ctr.init());
     const dim3 grid(chain_grid(n, 4 * kCB, chain_test_grid())), blk(kCB);
-    AIXCHK(st_counted(ctr, &hc, s, [&]() {
+    AIXCHK(ctr.run([&]() {
         AIX_TRY_LAUNCH(k_st_kidmap<true>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_unitig_contig, d_unitig_pos, d_unitig_flag, d_out_unitig,
-                       d_out_pos, d_out_flag, ctr);
+                       d_out_pos, d_out_flag, ctr.dev());
         return hipSuccess;
     }));
-    if (hc.bad) return AIX_ERR_ARG;
+    if (ctr.host.bad) return AIX_ERR_ARG;
     hipLaunchKernelGGL(k_st_kidmap<false>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_unitig_contig, d_unitig_pos, d_unitig_flag, d_out_unitig,
-                       d_out_pos, d_out_flag, ctr);
+                       d_out_pos, d_out_flag, ctr.dev());
     AIXCHK(hipGetLastError());
     AIXCHK(hipStreamSynchronize(s));
     return AIX_OK;
@@ -412,23 +385,21 @@ extern "C" int aix_graph_kidmap_dev(uint64_t n, const uint64_t* d_kid_unitig, co
 
 extern "C" int aix_thread_nodes_dev(uint64_t n, const uint64_t* d_kid_unitig, const uint32_t* d_kid_pos, const uint8_t* d_kid_flag, uint64_t U,
                                     const uint64_t* d_offsets, uint64_t* d_node, void* stream) {
-    if (U > kStMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_offsets) return AIX_ERR_ARG;
     if (n && (!d_kid_unitig || !d_kid_pos || !d_kid_flag || !d_node)) return AIX_ERR_ARG;
     if (n == 0) return AIX_OK;
     hipStream_t s = (hipStream_t)stream;
-    DevArr ctr_a(s);
-    AIXCHK(ctr_a.alloc(sizeof(StCounters)));
-    StCounters* ctr = (StCounters*)ctr_a.p;
-    StCounters hc;
+    Counted<StCounters> ctr(s);
+    AIXCHK(ctr.init());
     const dim3 grid(chain_grid(n, 4 * kCB, chain_test_grid())), blk(kCB);
-    AIXCHK(st_counted(ctr, &hc, s, [&]() {
-        AIX_TRY_LAUNCH(k_st_nodes<true>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_node, ctr);
+    AIXCHK(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_st_nodes<true>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_node, ctr.dev());
         return hipSuccess;
     }));
-    if (hc.bad) return AIX_ERR_ARG;
-    if (hc.wide) return AIX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_st_nodes<false>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_node, ctr);
+    if (ctr.host.bad) return AIX_ERR_ARG;
+    if (ctr.host.wide) return AIX_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_st_nodes<false>, grid, blk, 0, s, n, d_kid_unitig, d_kid_pos, d_kid_flag, U, d_offsets, d_node, ctr.dev());
     AIXCHK(hipGetLastError());
     AIXCHK(hipStreamSynchronize(s));
     return AIX_OK;
@@ -450,7 +421,7 @@ extern "C" int aix_seq_thread_dev(aix_index_t* h, const char* d_seqs, const uint
                                   uint32_t* d_q_first, uint32_t* d_q_last, uint64_t* d_step_link, uint64_t cap, uint64_t* total_out, void* stream) {
     const int st = st_check_handle(h);
     if (st) return st;
-    if (U > kStMaxU) return AIX_ERR_UNSUPPORTED;
+    if (U > kUnitLimit) return AIX_ERR_UNSUPPORTED;
     if (!d_node || !d_offsets || !d_link_off || !d_seq_step_off || !total_out || (M && !d_offs) || M >= (1ull << 56)) return AIX_ERR_ARG;
     if ((U && !d_circular) || (E && !d_link_to) || E > 8 * U) return AIX_ERR_ARG;
     if (cap && (!d_step_unitig || !d_step_pos || !d_step_flag || !d_q_first || !d_q_last || !d_step_link)) return AIX_ERR_ARG;

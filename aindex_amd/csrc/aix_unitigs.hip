@@ -22,13 +22,15 @@
 //            order: k_ug_emit writes offsets, bases, the circular flag and tf along every unitig; tf_sum / min / max come from one
 //            reduce-by-key over that array (no atomic on a per-unitig word).
 //   graph    section 7 below: the links between unitig ends and the simple bubbles, from a layout and the offsets of its emit.
+// What the two compaction levels share is in aix_chains.hpp; the counters holder of a call and the "no end" word are those of the graph
+// files, aix_graph.hpp.
 // Integer only, no LDS, no grid-wide barrier, no spin-wait. Every index derived from 2 n, from an offset or from the total is 64 bits wide.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "aix_chains.hpp"
+#include "aix_graph.hpp"
 #include "aix_probe.hpp"
 
 namespace aix {
@@ -310,21 +312,22 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
     const IndexDev ix = h->dev();
     const uint64_t n = ix.n, NP = 2 * n, cap = chain_test_grid();
     const dim3 blk(kCB);
-    DevArr ctr_a(s), word(s), r0(s), r1(s), ca0(s), ck0(s), ca1(s), ck1(s), sc(s), sk(s), sc2(s), sk2(s), tmp(s);
-    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
+    Counted<UgCounters> ctr(s);
+    DevArr word(s), r0(s), r1(s), ca0(s), ck0(s), ca1(s), ck1(s), sc(s), sk(s), sc2(s), sk2(s), tmp(s);
+    AIX_TRY(ctr.init());
     AIX_TRY(word.alloc(4 * NP));
     AIX_TRY(r0.alloc(8 * NP));
     AIX_TRY(r1.alloc(8 * NP));
-    UgCounters* ctr = (UgCounters*)ctr_a.p;
-    UgCounters hc;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    AIX_TRY_LAUNCH(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
-    AIX_TRY_LAUNCH(k_ug_links, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr->unflagged[0]);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    const UgCounters& hc = ctr.host;
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_ug_ports, dim3((unsigned)std::min<uint64_t>((NP + 63) / 64, cap)), blk, 0, s, ix, cutoff, ug_policy(), (uint32_t*)word.p);
+        AIX_TRY_LAUNCH(k_ug_links, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint32_t*)word.p, NP, (uint64_t*)r0.p, &ctr.dev()->unflagged[0]);
+        return hipSuccess;
+    }));
     uint64_t *cur = (uint64_t*)r0.p, *oth = (uint64_t*)r1.p;
     uint64_t open = hc.unflagged[0];
-    AIX_TRY(chain_rank(n, ctr->unflagged, &open, s, [&](int r) {
-        AIX_TRY_LAUNCH(k_ug_jump, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr->unflagged[r]);
+    AIX_TRY(chain_rank(n, ctr.dev()->unflagged, &open, s, [&](int r) {
+        AIX_TRY_LAUNCH(k_ug_jump, dim3(chain_grid(NP, 4 * kCB, cap)), blk, 0, s, (const uint64_t*)cur, NP, oth, &ctr.dev()->unflagged[r]);
         std::swap(cur, oth);
         return hipSuccess;
     }));                                                           // open: only cycle ports are left
@@ -353,8 +356,8 @@ static hipError_t ug_layout(const aix_index* h, uint32_t cutoff, uint64_t* kid_u
     AIX_TRY(sc.alloc(8 * n));
     AIX_TRY(sk.alloc(4 * n));
     AIX_TRY_LAUNCH(k_ug_place, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, (const uint64_t*)cur, cyc_a, cyc_k, kid_unitig, kid_pos, kid_flag, (uint64_t*)sc.p,
-        (uint32_t*)sk.p, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+        (uint32_t*)sk.p, ctr.dev());                              // (on top of the counters of the ranking: no run())
+    AIX_TRY(chain_read(&ctr.host, ctr.dev(), s));
     const uint64_t U = std::min<uint64_t>(hc.n_starts, n);
     if (U) {
         AIX_TRY(sc2.alloc(8 * U));
@@ -378,13 +381,14 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
     const uint64_t n = ix.n, cap = chain_test_grid();
     const dim3 blk(kCB);
     *bad = false;
-    DevArr ctr_a(s), keys(s), kids(s), keys2(s), kids2(s), tmp(s), tfs(s), uniq(s), agg(s), cnt(s), tmp2(s);
-    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
-    UgCounters* ctr = (UgCounters*)ctr_a.p;
-    UgCounters hc;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    Counted<UgCounters> ctr(s);
+    DevArr keys(s), kids(s), keys2(s), kids2(s), tmp(s), tfs(s), uniq(s), agg(s), cnt(s), tmp2(s);
+    AIX_TRY(ctr.init());
+    const UgCounters& hc = ctr.host;
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr.dev());
+        return hipSuccess;
+    }));
     if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
     const uint64_t n_live = hc.n_live, total = n_live + 22 * U;
     if (U == 0) {
@@ -431,7 +435,7 @@ static hipError_t ug_emit(const aix_index* h, uint32_t cutoff, const uint64_t* k
 //   scan     rocPRIM exclusive scan of deg[2 U + 1] (the last is 0) = link_off; link_off[2 U] = E
 //   fill     k_ul_fill: one lane per end copies its words to link_to + link_off[e]
 //   bubbles  k_ul_bubbles: one lane per unitig, the chain of gathers of the bubble rule over link_off / link_to; no handle
-static constexpr uint32_t kLNone = 0xFFFFFFFFu;                   // end_kid: no such end (circular unitig); cand: no word; bubble_mate: none
+// (kNoEnd, aix_graph.hpp, is here the end_kid of an end that does not exist (circular unitig), a cand without a word and the bubble_mate of a unitig without one)
 
 struct UlCounters {                                               // one zeroed record per call
     unsigned long long bad, n_ends, n_circular, n_none;
@@ -459,7 +463,7 @@ __global__ void __launch_bounds__(kCB) k_ul_ends(uint64_t n, uint64_t U, const u
     count_add(circ, &ctr->n_circular);
 }
 
-// One quad per end, 16 per wave. policy as k_ug_ports. cand[4 e + j] = the j-th link word of end e in base order (kLNone behind the degree).
+// One quad per end, 16 per wave. policy as k_ug_ports. cand[4 e + j] = the j-th link word of end e in base order (kNoEnd behind the degree).
 __global__ void __launch_bounds__(kCB) k_ul_probe(const IndexDev ix_, uint32_t cutoff, int policy, uint64_t U, const uint64_t* __restrict__ kid_unitig,
                                                  const uint32_t* __restrict__ kid_pos, const uint8_t* __restrict__ kid_flag, const uint64_t* __restrict__ offsets,
                                                  const uint32_t* __restrict__ end_kid, uint32_t* __restrict__ cand, uint32_t* __restrict__ deg,
@@ -473,10 +477,10 @@ __global__ void __launch_bounds__(kCB) k_ul_probe(const IndexDev ix_, uint32_t c
     for (uint64_t base = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 6) * 16; base < NE; base += stride) {    // wave-uniform
         const uint64_t e = base + (lane >> 2);
         const bool in = e < NE;
-        const uint32_t kid = in ? end_kid[e] : kLNone;
+        const uint32_t kid = in ? end_kid[e] : kNoEnd;
         const bool has = in && (uint64_t)kid < ix.n;
-        none += in && b == 0 && kid == kLNone;
-        bad += in && b == 0 && kid != kLNone && !has;
+        none += in && b == 0 && kid == kNoEnd;
+        bad += in && b == 0 && kid != kNoEnd && !has;
         KeyRec k;
         k.code = 0; k.tf = 0;
         uint32_t f = 0;
@@ -488,7 +492,7 @@ __global__ void __launch_bounds__(kCB) k_ul_probe(const IndexDev ix_, uint32_t c
         const Probe q = slot23_wave(ix, live, y, absence);
         if (policy == 0) fg.seen(live, q.found);
         bool ylive = live && q.found && q.tf > cutoff && q.slot < ix.n;
-        uint32_t w = kLNone;
+        uint32_t w = kNoEnd;
         if (ylive) {
             const uint64_t v = kid_unitig[q.slot];
             if (v < U) {
@@ -510,7 +514,7 @@ __global__ void __launch_bounds__(kCB) k_ul_probe(const IndexDev ix_, uint32_t c
         uint32_t c[4];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j)
-            c[j] = (l0 && j == 0) ? w0 : ((l1 && p1 == j) ? w1 : ((l2 && p2 == j) ? w2 : ((l3 && p3 == j) ? w3 : kLNone)));
+            c[j] = (l0 && j == 0) ? w0 : ((l1 && p1 == j) ? w1 : ((l2 && p2 == j) ? w2 : ((l3 && p3 == j) ? w3 : kNoEnd)));
         if (in && b == 0) {
             *reinterpret_cast<uint4*>(cand + 4 * e) = make_uint4(c[0], c[1], c[2], c[3]);
             deg[e] = d;
@@ -545,7 +549,7 @@ __global__ void __launch_bounds__(kCB) k_ul_bubbles(uint64_t U, const uint64_t* 
                                                    uint32_t* __restrict__ mate) {
     const uint64_t NE = 2 * U, stride = (uint64_t)gridDim.x * kCB;
     for (uint64_t u = (uint64_t)blockIdx.x * kCB + threadIdx.x; u < U; u += stride) {
-        uint32_t res = kLNone;
+        uint32_t res = kNoEnd;
         uint64_t aR, aL, aF, aS, aX, aY;
         do {
             if (ul_deg(link_off, E, 2 * u, aR) != 1 || ul_deg(link_off, E, 2 * u + 1, aL) != 1) break;
@@ -573,17 +577,18 @@ static hipError_t ul_links(const aix_index* h, uint32_t cutoff, const uint64_t* 
     const uint64_t n = ix.n, NE = 2 * U, cap = chain_test_grid();
     const dim3 blk(kCB);
     *bad = false;
-    DevArr ctr_a(s), lc_a(s), ek(s), cand(s), deg(s), tmp(s);
-    AIX_TRY(ctr_a.alloc(sizeof(UgCounters)));
+    Counted<UgCounters> ctr(s);
+    DevArr lc_a(s), ek(s), cand(s), deg(s), tmp(s);
+    AIX_TRY(ctr.init());
     AIX_TRY(lc_a.alloc(sizeof(UlCounters)));
-    UgCounters* ctr = (UgCounters*)ctr_a.p;
-    UlCounters* lc = (UlCounters*)lc_a.p;
-    UgCounters hc;
+    UlCounters* lc = (UlCounters*)lc_a.p;                          // zeroed once, read after each of its two kernels: no run()
+    const UgCounters& hc = ctr.host;
     UlCounters hl;
-    AIX_TRY(hipMemsetAsync(ctr, 0, sizeof(UgCounters), s));
-    AIX_TRY(hipMemsetAsync(lc, 0, sizeof(UlCounters), s));
-    AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr);
-    AIX_TRY(chain_read(&hc, ctr, s));
+    AIX_TRY(ctr.run([&]() {
+        AIX_TRY(hipMemsetAsync(lc, 0, sizeof(UlCounters), s));
+        AIX_TRY_LAUNCH(k_ug_check, dim3(chain_grid(n, 2 * kCB, cap)), blk, 0, s, ix, cutoff, U, kid_unitig, kid_pos, ctr.dev());
+        return hipSuccess;
+    }));
     if (hc.bad || hc.n_starts != U || hc.n_live < U || (U == 0 && hc.n_live)) { *bad = true; return hipSuccess; }
     if (U == 0) {
         AIX_TRY(hipMemsetAsync(link_off, 0, 8, s));
