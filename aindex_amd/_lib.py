@@ -114,6 +114,7 @@ SIGNATURES = {
     "aix_tf_batch_ascii": (i32, [vp, vp, u64, vp]),
     "aix_tf_batch_ascii_dev": (i32, [vp, vp, u64, vp, vp]),
     "aix_lookup_binned_stats": (i32, [vp, vp]),
+    "aix_lookup_binned_coarse_stats": (i32, [vp, vp]),
     "aix_tf_batch_codes": (i32, [vp, vp, u64, vp]),
     "aix_tf_batch_codes_dev": (i32, [vp, vp, u64, vp, vp]),
     "aix_tf_batch_ragged": (i32, [vp, vp, vp, u64, vp]),

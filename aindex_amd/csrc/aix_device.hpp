@@ -91,6 +91,14 @@ AIX_HD uint64_t bloom_mask(uint32_t hb) {
     const uint32_t lo = (1u << (hb & 15)) | (0x10000u << ((hb >> 4) & 15)), hi = (1u << ((hb >> 8) & 15)) | (0x10000u << ((hb >> 12) & 15));
     return (uint64_t)lo | ((uint64_t)hi << 32);
 }
+// One-byte coarse image of a filter word: quarter 0 folded onto 8 bits. A key sets bit hb & 15 of quarter 0, which lands on bit
+// hb & 7 of the image, so a word whose image has that bit clear cannot pass bloom_mask(hb) (the binned lookup's pass B tests the image,
+// held in LDS, before it reads the word).
+AIX_HD uint32_t bloom_fold(uint64_t word) {
+    const uint32_t q0 = (uint32_t)word & 0xFFFFu;
+    return (q0 & 0xFFu) | (q0 >> 8);
+}
+AIX_HD bool bloom_fold_test(uint32_t folded, uint32_t hb) { return ((folded >> (hb & 7u)) & 1u) != 0; }
 AIX_HD uint32_t bloom_word(uint32_t hw, uint32_t nwords) { return (uint32_t)(((uint64_t)hw * nwords) >> 32); }
 
 // ---------------------------------------------------------------------------------------------

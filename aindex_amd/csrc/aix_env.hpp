@@ -34,7 +34,9 @@
 //     AIX_LOOKUP_PIECE             H   1 .. 2^27                     2^27   queries per piece
 //     AIX_LOOKUP_TEST_BIN_CAP      H   records                       -      capacity of a bin's region (forces the overflow route)
 //     AIX_LOOKUP_TEST_GRID_A       H   1 .. 768                      768    workgroups of pass A at most (many tiles per workgroup on a small batch)
-//     AIX_LOOKUP_TEST_GRID_B       H   1 .. 1024                     1024   workgroups of pass B at most (many tickets per workgroup on a small batch)
+//     AIX_LOOKUP_TEST_GRID_B       H   1 .. 1024                     1024   workgroups of pass B at most (many tickets per workgroup on a small batch); with the coarse image at most 256
+//     AIX_LOOKUP_COARSE            AB  0 / 1                         1      pass B tests the coarse image of its slice in LDS before it reads the filter word
+//     AIX_LOOKUP_TEST_COARSE_MAX   H   0 .. 2^17 words               2^17   widest slice whose coarse image pass B takes into LDS (wider: pass B without the image)
 //   per call, elsewhere
 //     AIX_DISTINCT_PIECE           H   1 .. 2^31                     2^30   windows per K1 piece (aix_merge.hip entry points, aix_count.hip, aix_ingest.hip)
 //     AIX_POSITIONS_PIECE          H   1 .. 2^31                     2^30   windows per piece of the positions fill (aix_positions.hip)

@@ -101,7 +101,12 @@ struct aix_index {
     // of the index, so not in device_bytes. lb_done is recorded behind every call: a call on another stream waits for it first.
     void* lb_ws = nullptr;
     uint64_t lb_ws_bytes = 0;
-    uint64_t* lb_stats = nullptr;              // device: pieces binned, pieces direct, records that overflowed, survivors
+    uint64_t* lb_stats = nullptr;              // device: pieces binned, pieces direct, records that overflowed, survivors; records tested against the coarse image, records sent on
+    // the filter's coarse image (a byte per word, slice by slice) that pass B holds in LDS, and what it was folded from; grow-only like lb_ws
+    uint8_t* lb_coarse = nullptr;
+    uint64_t lb_coarse_bytes = 0;
+    const uint64_t* lb_coarse_src = nullptr;
+    uint32_t lb_coarse_nbloom = 0, lb_coarse_wps = 0;
     hipEvent_t lb_done = nullptr;
     hipStream_t lb_stream = nullptr;           // the stream of the last call
     bool lb_used = false;

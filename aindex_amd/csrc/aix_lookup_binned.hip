@@ -23,6 +23,11 @@
 //                 at a time and every XCD holds them in its L2. The chunks are handed out in order through eight ticket counters,
 //                 four chunks (1024 records) per ticket to a workgroup of 512 threads: ~107 000 returning atomics per 10^8
 //                 queries, 128 workgroups on a counter. A record that passes is appended to the survivor list.
+//   k_lb_filter_coarse  pass B as it runs by default (AIX_LOOKUP_COARSE): one workgroup of 1024 threads per CU holds the coarse image
+//                 of a slice (bloom_fold: one byte per filter word, 128 KiB at the shipped slice width) in LDS and reads the filter
+//                 word only of the records whose image bit is set, about 4 in 10 of an absent-heavy batch. Every ticket counter
+//                 owns the slices s with s % 8 == its number. The image is folded once per handle (k_lb_fold). k_lb_filter
+//                 remains for slices whose image does not fit (2 MiB slices) and as the A/B switch.
 //   k_lookup23_list (aix_kernels.hip) pass C: the survivors through the ordinary probe.
 // A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the 16 bits of the filter key from which
 // bloom_mask takes all four bit positions: 8 bytes, three bits spare. Pass B therefore lets exactly the filter's positives through
@@ -52,6 +57,17 @@ static constexpr int LB_FLUSH_AT = LB_SURV - LB_U * LB_FB;   // it appends them 
 static constexpr unsigned LB_GRID_B = 1024;            // four workgroups per CU: 1024 * 1024 ~ 10^6 records in flight, one slice's worth
 static_assert(LB_FB % LB_CH == 0 && LB_FB >= LB_MAXBINS && LB_FB % 64 == 0, "pass B scans the slices' chunk counts with one lane per slice");
 static_assert(LB_FLUSH_AT > 0, "LB_SURV holds the flush threshold plus one trip's records");
+// pass B with the coarse image of the slice in LDS (k_lb_filter_coarse): one workgroup of 1024 threads per CU
+static constexpr int LBC_FB = 1024;                    // threads: a lane takes one record of each chunk group of a ticket
+static constexpr int LBC_CPG = LBC_FB / LB_CH;         // chunks per chunk group
+static constexpr int LBC_U = 4;                        // chunk groups per ticket (independent loads)
+static constexpr int LBC_CPT = LBC_U * LBC_CPG;        // chunks per ticket: 4096 records
+static constexpr int LBC_SURV = 6144;                  // survivors a workgroup can hold in LDS
+static constexpr int LBC_FLUSH_AT = LBC_SURV - LBC_U * LBC_FB;
+static constexpr unsigned LBC_GRID = 256;              // one workgroup per CU
+static constexpr uint32_t LBC_MAX_WPS = 1u << 17;      // a slice's coarse image is one byte per filter word: 128 KiB of the CU's 160 KiB of LDS
+static_assert(LBC_FB % LB_CH == 0 && LBC_FB >= LB_MAXBINS && LBC_FLUSH_AT > 0, "as for pass B without the image");
+static_assert(LBC_MAX_WPS + 4 * (LBC_SURV + 2 * LB_MAXBINS + 1 + LBC_FB / 64 + 5) <= 160u << 10, "image, survivors and tables fit the LDS of a CU");
 static constexpr uint32_t LB_SAMPLES = 16384;
 static constexpr uint32_t LB_IDX_BITS = 27, LB_WORD_BITS = 18, LB_MASK_BITS = 16;
 static_assert(LB_MASK_BITS == 16 && LB_IDX_BITS + LB_WORD_BITS + LB_MASK_BITS <= 64, "the record holds the 16 bits bloom_mask reads");
@@ -59,6 +75,7 @@ static constexpr uint32_t LB_NONE = 0xFFFFFFFFu;
 static constexpr uint32_t LB_LO_BITS = 32 - LB_IDX_BITS, LB_META_LO = 9;   // pass A's per-query word: slice (9 bits) | the word-field bits of a record's low dword | rank << 16
 static_assert(LB_IDX_BITS < 32 && LB_MAXBINS < (1 << LB_META_LO) && LB_META_LO + LB_LO_BITS <= 16 && LB_TILE <= (1 << 13), "that word never equals LB_NONE");
 static constexpr uint64_t LB_HDR_BYTES = 4096;         // header (4 words) + cursors (LB_MAXBINS words) + ticket counters (a 128-byte line each), zeroed per piece
+static constexpr int LB_NSTATS = 6;                    // counters of a handle (LbWs::stats)
 enum { LB_FLAG = 0, LB_PASSED = 1, LB_DONE = 2, LB_NSURV = 3, LB_CURSOR = 16, LB_TICKET = 512 };
 
 static constexpr uint32_t LB_NO_SHIFT = 32;
@@ -74,7 +91,7 @@ struct LbWs {
     uint32_t* list;                // survivor list: query indices of the piece
     uint32_t* cnt;                 // [nbins * cap] records in each chunk
     uint64_t* rec;                 // [nbins * cap * LB_CH]
-    unsigned long long* stats;     // pieces binned, pieces direct, records that overflowed, survivors
+    unsigned long long* stats;     // pieces binned, pieces direct, records that overflowed, survivors; records tested against the coarse image, records sent on to the filter word
 };
 
 // the filter key of the code query23 (aix_kernels.hip) probes: that of the canonical strand; false = other bytes
@@ -435,6 +452,139 @@ __global__ void __launch_bounds__(LB_FB) k_lb_filter(const uint64_t* __restrict_
     if (s_n) flush();
 }
 
+// the coarse image (bloom_fold, aix_device.hpp) of every filter word, slice by slice: slice s starts at byte s * stride (stride = the
+// slice width rounded up to 16 bytes, so that a slice is loaded with aligned 16-byte loads); bytes behind a slice's words are zero
+__global__ void __launch_bounds__(256) k_lb_fold(const uint64_t* __restrict__ bloom, uint32_t nbloom, uint32_t wps, uint32_t stride, uint32_t nbins,
+                                                 uint8_t* __restrict__ coarse) {
+    const uint32_t total = nbins * stride;                      // <= LB_MAXBINS * LBC_MAX_WPS = 2^25
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const uint32_t s = i / stride, wi = i - s * stride;
+        const uint64_t word = (uint64_t)s * wps + wi;
+        coarse[i] = (wi < wps && word < nbloom) ? (uint8_t)bloom_fold(bloom[word]) : (uint8_t)0;
+    }
+}
+
+// Pass B with the coarse image of the slice in LDS. A record first tests bit hb & 7 of its word's image byte; only where it is set
+// (about 4 records in 10 of an absent-heavy batch at 16 filter bits per key) is the filter word read from L2 and the full mask
+// tested, so the survivors are those of k_lb_filter. One workgroup of LBC_FB threads per CU holds one slice's image (<= 128 KiB of
+// dynamic LDS). Ticket counter x of the nt in use owns the slices s with s % nt == x and hands their chunks out in slice order, a
+// ticket of LBC_CPT chunks at a time; a ticket does not span slices (a slice's chunks are rounded up to whole tickets), and a
+// workgroup whose ticket lies in another slice than the one it holds loads that slice's image first. A workgroup sends for the
+// records of its next ticket as soon as the current one's survivors are stored, so that they travel across the barriers and the
+// next pull; under ownership a ticket held ahead widens no window that matters.
+__global__ void __launch_bounds__(LBC_FB) k_lb_filter_coarse(const uint64_t* __restrict__ bloom, uint32_t nbloom, const uint8_t* __restrict__ coarse,
+                                                             uint32_t stride, LbGeom g, LbWs w) {
+    if (!w.hdr[LB_FLAG]) return;
+    extern __shared__ __attribute__((aligned(16))) uint8_t image[];   // [stride]: the coarse image of slice `held`
+    __shared__ uint32_t tpre[LB_MAXBINS + 1];                   // this counter's tickets in the slices before this one
+    __shared__ uint32_t nch[LB_MAXBINS];                        // chunks of the slice
+    __shared__ uint32_t surv[LBC_SURV];
+    __shared__ uint32_t wsum[LBC_FB / 64];
+    __shared__ uint32_t s_n, s_base, s_ticket, s_cnt[2];
+    const uint32_t t = threadIdx.x, NB = g.nbins;
+    const uint32_t nt = min(gridDim.x, (uint32_t)LB_TICKETS);   // counters in use: each of them has a workgroup that pulls on it
+    const uint32_t lane_x = blockIdx.x % nt;
+    uint32_t* const ticket = w.hdr + LB_TICKET + 32 * lane_x;
+    const uint32_t mine = t < NB ? min(w.hdr[LB_CURSOR + t], g.cap) : 0u;
+    uint32_t total;                                             // tickets of this counter
+    const uint32_t excl = lb_scan_excl<LBC_FB>(t % nt == lane_x ? (mine + LBC_CPT - 1) / LBC_CPT : 0u, wsum, total);
+    if (t < (uint32_t)LB_MAXBINS) { tpre[t] = excl; nch[t] = mine; }
+    if (t == 0) { tpre[LB_MAXBINS] = total; s_n = 0; s_cnt[0] = 0; s_cnt[1] = 0; }
+    __syncthreads();
+    auto flush = [&]() {                                         // every lane of the workgroup calls it
+        if (t == 0) s_base = atomicAdd(&w.hdr[LB_NSURV], s_n);
+        __syncthreads();
+        for (uint32_t i = t; i < s_n; i += LBC_FB) w.list[s_base + i] = surv[i];
+        __syncthreads();
+        if (t == 0) s_n = 0;
+        __syncthreads();
+    };
+    // ticket k of this counter -> its slice (`bin`, which only ever increases) and its first chunk there; false = past the end.
+    // tpre[s] = total for every s >= NB, so the walk stops at a slice that has tickets of this counter.
+    uint32_t bin = 0;
+    auto locate = [&](uint32_t k, uint32_t& c0) -> bool {
+        if (k >= total) return false;
+        while (k >= tpre[bin + 1]) ++bin;
+        c0 = (k - tpre[bin]) * LBC_CPT;
+        return true;
+    };
+    // lane t takes record t % LB_CH of chunk c0 + u * LBC_CPG + t / LB_CH of slice b, u < LBC_U. No branch around the loads (behind
+    // one, hipcc waits for every load in flight where it needs the oldest, and the records fetched ahead would be waited for with
+    // the filter words): a chunk behind the slice's last is clamped to the last and its count set to zero, and so is every chunk
+    // of a ticket that is not `live`. The slice has a chunk (the caller has located a ticket in it).
+    auto fetch = [&](uint32_t b, uint32_t c0, bool live, uint64_t (&r)[LBC_U], uint32_t (&cn)[LBC_U]) {
+        const uint32_t last = nch[b] - 1;
+#pragma unroll
+        for (int u = 0; u < LBC_U; ++u) {
+            const uint32_t ci = c0 + u * LBC_CPG + t / LB_CH;
+            const uint64_t ch = (uint64_t)b * g.cap + min(ci, last);
+            const uint32_t c = w.cnt[ch];
+            r[u] = __builtin_nontemporal_load(&w.rec[ch * LB_CH + t % LB_CH]);       // streamed once: keep the slice in L2
+            cn[u] = live && ci <= last ? c : 0u;
+        }
+    };
+    uint64_t rn[LBC_U];                                          // the records of the next ticket, of slice bn
+    uint32_t cnn[LBC_U], bn, c0 = 0;
+    if (t == 0) s_ticket = atomicAdd(ticket, 1u);
+    __syncthreads();
+    bool more = locate(s_ticket, c0);
+    bn = bin;
+    if (more) fetch(bn, c0, true, rn, cnn);
+    __syncthreads();                                            // s_ticket is written again below
+    uint32_t held = LB_NONE, n_tested = 0, n_on = 0;            // the wave's records tested against the image / sent on to the filter word
+    while (more) {
+        uint64_t r[LBC_U], wd[LBC_U];
+        uint32_t cn[LBC_U];
+        bool on[LBC_U];
+        const uint32_t b = bn;
+#pragma unroll
+        for (int u = 0; u < LBC_U; ++u) { r[u] = rn[u]; cn[u] = cnn[u]; }
+        if (t == 0) s_ticket = atomicAdd(ticket, 1u);
+        if (b != held) {                                         // nobody reads the image between the barrier that ended the last ticket and the one below
+            const uint4* const src = (const uint4*)(coarse + (uint64_t)b * stride);
+            for (uint32_t i = t; i < stride / 16; i += LBC_FB) ((uint4*)image)[i] = src[i];
+            held = b;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < LBC_U; ++u) {
+            const uint32_t wi = (uint32_t)(r[u] >> LB_IDX_BITS) & ((1u << LB_WORD_BITS) - 1), word = b * g.wps + wi;
+            const bool valid = t % LB_CH < cn[u] && wi < g.wps && word < nbloom;
+            on[u] = valid && bloom_fold_test(image[valid ? wi : 0u], (uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));
+            wd[u] = bloom[on[u] ? word : b * g.wps];             // the others read the slice's first word together: one request per wave
+            n_tested += (uint32_t)__popcll(__ballot(valid));
+            n_on += (uint32_t)__popcll(__ballot(on[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < LBC_U; ++u) {
+            const uint64_t mk = bloom_mask((uint32_t)(r[u] >> (LB_IDX_BITS + LB_WORD_BITS)));   // all four positions: the low LB_MASK_BITS bits
+            const bool pass = on[u] && (wd[u] & mk) == mk;
+            const uint64_t m = __ballot(pass);
+            if (m) {
+                uint32_t r0 = 0;
+                if ((t & 63u) == 0) r0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
+                r0 = __shfl(r0, 0);
+                if (pass) surv[r0 + (uint32_t)__popcll(m & ((1ull << (t & 63u)) - 1))] = (uint32_t)r[u] & ((1u << LB_IDX_BITS) - 1);
+            }
+        }
+        // the next ticket's records go out behind this ticket's survivors and come back across the barriers, a flush and the next
+        // ticket pull. Sent out behind the filter reads instead, before the mask test, they cost 0.05 ms
+        // (profiles/lookup_binned/README.md).
+        more = locate(s_ticket, c0);
+        bn = bin;                                                // past the end: still this ticket's slice
+        fetch(bn, more ? c0 : 0u, more, rn, cnn);
+        __syncthreads();
+        if (s_n > (uint32_t)LBC_FLUSH_AT) flush();
+    }
+    if ((t & 63u) == 0 && n_tested) { atomicAdd(&s_cnt[0], n_tested); atomicAdd(&s_cnt[1], n_on); }
+    if (s_n) flush();                                           // the same for every lane: nobody appends behind the loop's last barrier
+    __syncthreads();
+    if (t == 0 && s_cnt[0]) {
+        atomicAdd(&w.stats[4], (unsigned long long)s_cnt[0]);
+        atomicAdd(&w.stats[5], (unsigned long long)s_cnt[1]);
+    }
+}
+
 }  // namespace aix
 
 // ---------------------------------------------------------------------------------------------
@@ -446,6 +596,7 @@ void lookup_binned_release(aix_index* h) {
     if (h->lb_done) { (void)hipEventSynchronize(h->lb_done); (void)hipEventDestroy(h->lb_done); h->lb_done = nullptr; }
     if (h->lb_ws) { (void)hipFree(h->lb_ws); h->lb_ws = nullptr; h->lb_ws_bytes = 0; }
     if (h->lb_stats) { (void)hipFree(h->lb_stats); h->lb_stats = nullptr; }
+    if (h->lb_coarse) { (void)hipFree(h->lb_coarse); h->lb_coarse = nullptr; h->lb_coarse_bytes = 0; h->lb_coarse_src = nullptr; }
 }
 
 // AIX_TAKEN: the batch is enqueued (binned kernels and, in auto mode, the gated direct kernel); AIX_NOT_TAKEN: the caller runs the
@@ -472,12 +623,25 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     g.cap = (uint32_t)cap;
     const uint64_t off_list = LB_HDR_BYTES, off_cnt = align_up(off_list + 4 * piece, 256), off_rec = align_up(off_cnt + 4ull * g.nbins * cap, 256);
     const uint64_t need = off_rec + 8ull * g.nbins * cap * LB_CH;
+    // pass B tests the coarse image of a slice in LDS first (k_lb_filter_coarse) where a slice's image fits there
+    const uint64_t coarse_max = std::min<uint64_t>(env_u64("AIX_LOOKUP_TEST_COARSE_MAX", 0, LBC_MAX_WPS, LBC_MAX_WPS), LBC_MAX_WPS);
+    bool coarse = env_int("AIX_LOOKUP_COARSE", 0, 1, 1) == 1 && g.wps <= coarse_max;
+    const uint32_t cstride = (uint32_t)align_up(g.wps, 16);
+    const uint64_t need_coarse = (uint64_t)g.nbins * cstride;
 
     std::lock_guard<std::mutex> lk(h->lb_mutex);               // orders the enqueueing; the event orders the streams
     if (!h->lb_done && hipEventCreateWithFlags(&h->lb_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); h->lb_done = nullptr; return AIX_LB_NOT_TAKEN; }
     if (!h->lb_stats) {
-        if (hipMalloc((void**)&h->lb_stats, 32) != hipSuccess) { (void)hipGetLastError(); h->lb_stats = nullptr; return AIX_LB_NOT_TAKEN; }
-        HIPCHK(hipMemset(h->lb_stats, 0, 32));
+        if (hipMalloc((void**)&h->lb_stats, 8 * LB_NSTATS) != hipSuccess) { (void)hipGetLastError(); h->lb_stats = nullptr; return AIX_LB_NOT_TAKEN; }
+        HIPCHK(hipMemset(h->lb_stats, 0, 8 * LB_NSTATS));
+    }
+    if (coarse && need_coarse > h->lb_coarse_bytes) {          // as the workspace below: grow only, behind the kernels of earlier calls
+        if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
+        if (h->lb_coarse) { (void)hipFree(h->lb_coarse); h->lb_coarse = nullptr; }
+        h->lb_coarse_bytes = 0;
+        h->lb_coarse_src = nullptr;
+        if (hipMalloc((void**)&h->lb_coarse, need_coarse) != hipSuccess) { (void)hipGetLastError(); h->lb_coarse = nullptr; coarse = false; }   // no room: pass B without the image
+        else h->lb_coarse_bytes = need_coarse;
     }
     if (need > h->lb_ws_bytes) {                               // grow only; the kernels of earlier calls may still be using the old block
         if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
@@ -504,6 +668,21 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     w.stats = (unsigned long long*)h->lb_stats;
     const uint64_t test_grid_b = env_u64("AIX_LOOKUP_TEST_GRID_B", 1, LB_GRID_B, LB_GRID_B);   // fewer workgroups: many tickets each on a small batch
     const unsigned grid_b = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)g.nbins * cap + LB_CPT - 1) / LB_CPT, 1), test_grid_b);
+    const unsigned grid_c = (unsigned)std::min<uint64_t>(std::max<uint64_t>((uint64_t)g.nbins * ((cap + LBC_CPT - 1) / LBC_CPT), 1), std::min<uint64_t>(test_grid_b, LBC_GRID));
+    if (coarse) {
+        // the image is folded once per filter and slice width, on the stream of the first call that needs it: a handle's filter does not
+        // change while it is open (switching it off and on again, or moving it, leaves its words as they were)
+        if (h->lb_coarse_src != d.bloom || h->lb_coarse_nbloom != d.nbloom || h->lb_coarse_wps != g.wps) {
+            hipLaunchKernelGGL(k_lb_fold, dim3((unsigned)std::min<uint64_t>((need_coarse + 255) / 256, 4096)), dim3(256), 0, s, d.bloom, d.nbloom, g.wps, cstride,
+                               g.nbins, h->lb_coarse);
+            HIPCHK(hipGetLastError());
+            h->lb_coarse_src = d.bloom;
+            h->lb_coarse_nbloom = d.nbloom;
+            h->lb_coarse_wps = g.wps;
+        }
+        // 26 KiB of static LDS beside the image
+        if (cstride > (16u << 10)) HIPCHK(hipFuncSetAttribute((const void*)k_lb_filter_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cstride));
+    }
     for (uint64_t lo = 0; lo < N; lo += piece) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(piece, N - lo);
         const uint8_t* qp = q + 23 * lo;
@@ -516,7 +695,8 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
         if (sw != 2) HIPCHK(launch_lookup23_ascii(d, qp, m, MODE_TF, LookupOut{op, nullptr, nullptr, nullptr}, s, w.hdr + LB_FLAG));
         hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), carry_bytes, s, d.nbloom, qp, m, g, w, op);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
+        if (coarse) hipLaunchKernelGGL(k_lb_filter_coarse, dim3(grid_c), dim3(LBC_FB), cstride, s, d.bloom, d.nbloom, (const uint8_t*)h->lb_coarse, cstride, g, w);
+        else hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
         HIPCHK(hipGetLastError());
         HIPCHK(launch_lookup23_list(d, qp, w.list, w.hdr + LB_NSURV, m, w.hdr + LB_FLAG, op, w.stats + 3, s));
     }
@@ -531,5 +711,16 @@ extern "C" int aix_lookup_binned_stats(aix_index_t* h, uint64_t out[4]) {
     if (!h->lb_stats) return AIX_OK;
     if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
     HIPCHK(hipMemcpy(out, h->lb_stats, 32, hipMemcpyDeviceToHost));
+    return AIX_OK;
+}
+
+extern "C" int aix_lookup_binned_coarse_stats(aix_index_t* h, uint64_t out[2]) {
+    if (!h || !out) return AIX_ERR_ARG;
+    DevGuard g(h->device);
+    std::lock_guard<std::mutex> lk(h->lb_mutex);
+    out[0] = out[1] = 0;
+    if (!h->lb_stats) return AIX_OK;
+    if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
+    HIPCHK(hipMemcpy(out, h->lb_stats + 4, 16, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

@@ -179,6 +179,9 @@ int aix_tf_batch_ascii_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint
  * has done on this handle so far. Synchronises. out = pieces binned, pieces answered directly, records that overflowed their bin,
  * queries that reached the survivor probe. */
 int aix_lookup_binned_stats(aix_index_t* h, uint64_t out[4]);
+/* The same for pass B's coarse filter image (AIX_LOOKUP_COARSE): out = records tested against the image of their slice in LDS, records
+ * that went on to the filter word. Both stay as they are where pass B runs without the image. Synchronises. */
+int aix_lookup_binned_coarse_stats(aix_index_t* h, uint64_t out[2]);
 /* pre-encoded 2-bit codes (first base most significant; ACGT only), same answers as the ASCII call */
 int aix_tf_batch_codes(aix_index_t* h, const uint64_t* codes, uint64_t N, uint32_t* out);
 int aix_tf_batch_codes_dev(aix_index_t* h, const uint64_t* d_codes, uint64_t N, uint32_t* d_out, void* stream);
