@@ -1,10 +1,13 @@
 // aix_hostkit.hpp — private to the library: the host scaffolding that the subsystem files (one translation unit per subsystem behind the
 // C ABI) share. Error mapping, rocPRIM's two-call protocol, the prologue and the epilogue of the host forms (copy_in_host, copy_out_host).
-// Nothing here is on a hot path, and nothing that only one file uses belongs here. The builder and counter files (aix_merge, aix_a2msd,
-// aix_k1, aix_normalize, aix_count13, aix_positions) keep raw pool blocks and their own error style and do not use it.
+// The query files (aix_posquery, aix_readsquery, aix_seqhits, aix_seqfind, aix_seqedit), the graph files and aix_seqthread use all of it:
+// their chains are AIX_TRY / AIX_TRY_LAUNCH, their host forms hold DevArr and publish through one HostOut table. Nothing here is on a hot
+// path, and nothing that only one file uses belongs here. The builder and counter files (aix_merge, aix_a2msd, aix_k1, aix_normalize,
+// aix_count13, aix_positions) keep raw pool blocks and their own error style and do not use it.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>                                                // (rocPRIM's headers use memset without including it)
 #include <string>
 
 #include <rocprim/rocprim.hpp>
@@ -57,6 +60,9 @@ static inline int bit_length(uint64_t v) {
     while (v) { ++r; v >>= 1; }
     return r;
 }
+static inline unsigned sort_bits(uint64_t v) {                    // end_bit of a radix sort whose keys are <= v: at least one bit (v == 0)
+    return (unsigned)std::max(1, bit_length(v));
+}
 
 template <class T>
 struct Widen {                                                    // an integer as the u64 a scan sums
@@ -86,6 +92,12 @@ static hipError_t scan_u64(It in, uint64_t* out, uint64_t n, DevArr& tmp, hipStr
 template <class KeyIt, class Key, class ValIt, class Val>
 static hipError_t sort_pairs(KeyIt keys_in, Key* keys_out, ValIt vals_in, Val* vals_out, uint64_t n, unsigned end_bit, DevArr& tmp, hipStream_t s) {
     return with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_pairs(t, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, s); });
+}
+
+// the answer to a batch without entries: n + 1 offsets, all zero, and `s` synchronised
+static hipError_t zero_offsets(uint64_t* d_offsets, uint64_t n, hipStream_t s) {
+    AIX_TRY(hipMemsetAsync(d_offsets, 0, 8 * (n + 1), s));
+    return hipStreamSynchronize(s);
 }
 
 // The prologue of a host form: in[i] becomes a device copy of block i of the table, on the null stream; zero bytes is still a block of its

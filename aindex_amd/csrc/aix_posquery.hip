@@ -22,8 +22,6 @@
 // Zeros are skipped wherever they sit (the fill leaves them wherever a window was not placed). Every size, offset and flat index is 64 bits wide.
 // No atomics; all stores are plain vector stores.
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 #include <vector>
 
@@ -211,53 +209,44 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     *total_out = 0;
     if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);
     DevArr fo(s), nj(s), t0(s), t1(s), t2(s), t3(s), ne(s), nfo(s), nlo(s), nraw(s), bits(s), cnt(s), wr(s), kept(s);
-    hipError_t e = fo.alloc(8 * (N + 1));
-    if (e == hipSuccess) e = nj.alloc(8 * (N + 1));
-    if (e != hipSuccess) return e;
-    e = scan_u64(d_ub, (uint64_t*)fo.p, N + 1, t0, s);
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator(d_ub, PqNonEmpty()), (uint64_t*)nj.p, N + 1, t1, s);
-    uint64_t T = 0, J = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&T, (const uint64_t*)fo.p + N, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&J, (const uint64_t*)nj.p + N, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(fo.alloc(8 * (N + 1)));
+    AIX_TRY(nj.alloc(8 * (N + 1)));
+    AIX_TRY(scan_u64(d_ub, (uint64_t*)fo.p, N + 1, t0, s));
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator(d_ub, PqNonEmpty()), (uint64_t*)nj.p, N + 1, t1, s));
+    uint64_t T = 0, J = 0;        // read back asynchronously: declared after the DevArrs, whose destructors synchronise `s` before an early return leaves the frame
+    AIX_TRY(hipMemcpyAsync(&T, (const uint64_t*)fo.p + N, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipMemcpyAsync(&J, (const uint64_t*)nj.p + N, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     if (T == 0) return hipMemsetAsync(d_offsets, 0, 8 * (N + 1), s);
     const uint64_t C = (T + 63) / 64;
-    e = ne.alloc(8 * J);
-    if (e == hipSuccess) e = nfo.alloc(8 * (J + kPad));
-    if (e == hipSuccess) e = nlo.alloc(8 * J);
-    if (e == hipSuccess) e = nraw.alloc(8 * J);
-    if (e == hipSuccess) e = bits.alloc(8 * (C + 1));
-    if (e == hipSuccess) e = cnt.alloc(4 * (C + 1));
-    if (e == hipSuccess) e = wr.alloc(8 * (C + 1));
-    if (e == hipSuccess) e = kept.alloc(8 * (N + 1));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pq_compact, dim3(flat_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, d_lo, J, T,
-                       (uint64_t*)ne.p, (uint64_t*)nfo.p, (uint64_t*)nlo.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemsetAsync((uint64_t*)bits.p + C, 0, 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync((uint32_t*)cnt.p + C, 0, 4, s);
-    if (e == hipSuccess) e = hipMemsetAsync(kept.p, 0, 8 * (N + 1), s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(ne.alloc(8 * J));
+    AIX_TRY(nfo.alloc(8 * (J + kPad)));
+    AIX_TRY(nlo.alloc(8 * J));
+    AIX_TRY(nraw.alloc(8 * J));
+    AIX_TRY(bits.alloc(8 * (C + 1)));
+    AIX_TRY(cnt.alloc(4 * (C + 1)));
+    AIX_TRY(wr.alloc(8 * (C + 1)));
+    AIX_TRY(kept.alloc(8 * (N + 1)));
+    AIX_TRY_LAUNCH(k_pq_compact, dim3(flat_grid(std::max(N, kPad))), dim3(kB), 0, s, N, d_ub, (const uint64_t*)fo.p, (const uint64_t*)nj.p, d_lo, J, T,
+                   (uint64_t*)ne.p, (uint64_t*)nfo.p, (uint64_t*)nlo.p);
+    AIX_TRY(hipMemsetAsync((uint64_t*)bits.p + C, 0, 8, s));
+    AIX_TRY(hipMemsetAsync((uint32_t*)cnt.p + C, 0, 4, s));
+    AIX_TRY(hipMemsetAsync(kept.p, 0, 8 * (N + 1), s));
     PqFlat P{};
     P.positions = h->ai_positions; P.ne = (const uint64_t*)ne.p; P.nfo = (const uint64_t*)nfo.p; P.nlo = (const uint64_t*)nlo.p;
     P.J = J; P.T = T; P.C = C; P.bits = (uint64_t*)bits.p; P.cnt = (uint32_t*)cnt.p; P.wr = (const uint64_t*)wr.p; P.nraw = (const uint64_t*)nraw.p;
     P.offsets = d_offsets; P.m = m;
-    hipLaunchKernelGGL(k_pq_flat<false>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint32_t*)cnt.p, Widen<uint32_t>()), (uint64_t*)wr.p, C + 1, t2, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pq_segrank, dim3(flat_grid(J)), dim3(kB), 0, s, (const uint64_t*)bits.p, (const uint64_t*)wr.p, (const uint64_t*)nfo.p, (const uint64_t*)ne.p, J, m,
-                       (uint64_t*)nraw.p, (uint64_t*)kept.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64((const uint64_t*)kept.p, d_offsets, N + 1, t3, s);
+    AIX_TRY_LAUNCH(k_pq_flat<false>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint32_t*)cnt.p, Widen<uint32_t>()), (uint64_t*)wr.p, C + 1, t2, s));
+    AIX_TRY_LAUNCH(k_pq_segrank, dim3(flat_grid(J)), dim3(kB), 0, s, (const uint64_t*)bits.p, (const uint64_t*)wr.p, (const uint64_t*)nfo.p, (const uint64_t*)ne.p, J, m,
+                   (uint64_t*)nraw.p, (uint64_t*)kept.p);
+    AIX_TRY(scan_u64((const uint64_t*)kept.p, d_offsets, N + 1, t3, s));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_offsets + N, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(hipMemcpyAsync(&total, d_offsets + N, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     *total_out = total;
     if (own_pos && total) {
-        if ((e = own_pos->alloc(8 * total)) != hipSuccess) return e;
+        AIX_TRY(own_pos->alloc(8 * total));
         d_positions = (uint64_t*)own_pos->p;
         cap = total;
     }
@@ -267,10 +256,8 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
         P.rid_out = d_rid; P.local_out = d_local;
         P.rs = h->rx; P.re = h->rx + h->rx_n; P.rr = h->rx + 2 * h->rx_n; P.rn = h->rx_n;
     }
-    hipLaunchKernelGGL(k_pq_flat<true>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);         // the scratch blocks go back to the pool idle
-    return e;
+    AIX_TRY_LAUNCH(k_pq_flat<true>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
+    return hipStreamSynchronize(s);                            // the scratch blocks go back to the pool idle
 }
 
 // The whole chain. d_offsets (N + 1) and *total_out are always produced; entries only when *total_out <= cap.
@@ -280,18 +267,14 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);
     const IndexDev ix = h->dev();
     DevArr lo(s), ub(s);
-    hipError_t e = lo.alloc(8 * N);
-    if (e == hipSuccess) e = ub.alloc(8 * (N + 1));
-    if (e != hipSuccess) return e;
+    AIX_TRY(lo.alloc(8 * N));
+    AIX_TRY(ub.alloc(8 * (N + 1)));
     uint64_t* d_ub = (uint64_t*)ub.p;
-    e = hipMemsetAsync(d_ub + N, 0, 8, s);
-    if (e != hipSuccess) return e;
-    if (h->k == 13) hipLaunchKernelGGL(k_pq_resolve13, dim3(flat_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 2) hipLaunchKernelGGL(k_pq_resolve23<2>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 4) hipLaunchKernelGGL(k_pq_resolve23<4>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else hipLaunchKernelGGL(k_pq_resolve23<8>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    AIX_TRY(hipMemsetAsync(d_ub + N, 0, 8, s));
+    if (h->k == 13) AIX_TRY_LAUNCH(k_pq_resolve13, dim3(flat_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 2) AIX_TRY_LAUNCH(k_pq_resolve23<2>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 4) AIX_TRY_LAUNCH(k_pq_resolve23<4>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    else AIX_TRY_LAUNCH(k_pq_resolve23<8>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
     return posquery_lists(h, (const uint64_t*)lo.p, d_ub, N, m, d_offsets, d_positions, d_rid, d_local, cap, total_out, s);
 }
 
@@ -429,11 +412,9 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
     if (!h->ai_attached || (rid_out && !h->rx_attached)) return AIX_ERR_ARG;
     if (h->k == 23 && h->n == 0) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
-    const uint64_t qb = N * h->k;
-    DevBuf dq, doff, dpos, drid, dloc;
-    AIXCHK(dq.alloc(qb + 16));
+    DevArr dq, doff, dpos, drid, dloc;
+    AIXCHK(upload_padded(dq, kmers, N * h->k));
     AIXCHK(doff.alloc(8 * (N + 1)));
-    if (qb) AIXCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
     uint64_t total = 0;
     AIXCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, nullptr, nullptr, nullptr, 0, &total, 0));
     if (total) {
@@ -443,18 +424,9 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
         AIXCHK(posquery_run(h, (const uint8_t*)dq.p, N, max_per_kmer, (uint64_t*)doff.p, (uint64_t*)dpos.p, (uint64_t*)drid.p, (uint64_t*)dloc.p, total, &again, 0));
         if (again != total) { set_last_error("aix_positions_query: the index changed between the sizing and the filling pass"); return AIX_ERR_HIP; }
     }
-    uint64_t* ho = (uint64_t*)malloc(8 * (N + 1));
-    uint64_t* hp = (uint64_t*)malloc(total ? 8 * total : 8);
-    uint64_t* hr = rid_out ? (uint64_t*)malloc(total ? 8 * total : 8) : nullptr;
-    uint64_t* hl = rid_out ? (uint64_t*)malloc(total ? 8 * total : 8) : nullptr;
-    hipError_t e = (ho && hp && (!rid_out || (hr && hl))) ? hipSuccess : hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpy(ho, doff.p, 8 * (N + 1), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && total) e = hipMemcpy(hp, dpos.p, 8 * total, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && total && rid_out) e = hipMemcpy(hr, drid.p, 8 * total, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && total && rid_out) e = hipMemcpy(hl, dloc.p, 8 * total, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(ho); free(hp); free(hr); free(hl); AIXCHK(e); }
-    *offsets_out = ho; *positions_out = hp;
-    if (rid_out) { *rid_out = hr; *local_out = hl; }
+    const HostOut outs[] = {{(void**)offsets_out, doff.p, 8 * (N + 1)}, {(void**)positions_out, dpos.p, 8 * total}, {(void**)rid_out, drid.p, 8 * total},
+                            {(void**)local_out, dloc.p, 8 * total}};
+    AIXCHK(copy_out_host(outs, 4));
     return AIX_OK;
 }
 
@@ -473,11 +445,11 @@ extern "C" int aix_positions_locate(aix_index_t* h, const uint64_t* pos, uint64_
     if (!h->rx_attached) return AIX_ERR_ARG;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    DevBuf dp, dr, ds;
-    AIXCHK(dp.alloc(8 * N));
+    DevArr dp, dr, ds;
+    const HostIn in{pos, 8 * N};
+    AIXCHK(copy_in_host(&dp, &in, 1));
     AIXCHK(dr.alloc(8 * N));
     AIXCHK(ds.alloc(8 * N));
-    AIXCHK(hipMemcpy(dp.p, pos, 8 * N, hipMemcpyHostToDevice));
     const int st = aix_positions_locate_dev(h, (const uint64_t*)dp.p, N, (uint64_t*)dr.p, (uint64_t*)ds.p, nullptr);
     if (st) return st;
     AIXCHK(hipMemcpy(rid_out, dr.p, 8 * N, hipMemcpyDeviceToHost));

@@ -5,6 +5,16 @@
 
 namespace aix {
 
+// load23 (aix_device.hpp) reads whole aligned dwords around a 23-byte window, so its last dword may reach past the final window of a
+// batch. Query bytes that a host form uploads therefore sit in a block with kQueryPad spare bytes behind them: `bytes` bytes of src in a
+// block of bytes + kQueryPad, on the null stream.
+static constexpr uint64_t kQueryPad = 16;
+static hipError_t upload_padded(DevArr& d, const void* src, uint64_t bytes) {
+    AIX_TRY(d.alloc(bytes + kQueryPad));
+    if (bytes) AIX_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return hipSuccess;
+}
+
 __device__ __forceinline__ uint64_t pq_bswap(uint64_t x) { return __builtin_bswap64(x); }
 
 __device__ __forceinline__ void pq_emit(const uint64_t* __restrict__ indices, uint64_t total, uint64_t n, uint64_t h, uint64_t& lo, uint64_t& ub) {

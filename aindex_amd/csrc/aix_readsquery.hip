@@ -21,10 +21,8 @@
 // through two stable radix sorts (by interval, then by list) —, and two scans that rank the first occurrences inside their list for the
 // max_reads rule. Every size, offset and byte index is 64 bits wide. No atomics; all stores are plain vector stores.
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
-#include "aix_hostkit.hpp"
+#include "aix_posquery.hpp"                                       // upload_padded; the rest is aix_hostkit.hpp
 
 namespace aix {
 
@@ -180,20 +178,17 @@ static hipError_t rq_gather_run(aix_index* h, const uint64_t* d_src, const uint6
                                 uint64_t cap, uint64_t* total_out, hipStream_t s) {
     *total_out = 0;
     DevArr tmp(s);
-    hipError_t e = scan_u64(d_len, d_offsets, R + 1, tmp, s);
-    uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_offsets + R, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(scan_u64(d_len, d_offsets, R + 1, tmp, s));
+    uint64_t total = 0;           // read back asynchronously: declared after the DevArrs, whose destructors synchronise `s` before an early return leaves the frame
+    AIX_TRY(hipMemcpyAsync(&total, d_offsets + R, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     *total_out = total;
     if (total == 0 || total > cap || !d_bytes) return hipSuccess;
     RqGather P{};
     P.reads = h->rd; P.src = d_src; P.off = d_offsets; P.rc = d_rc; P.R = R; P.total = total; P.out = d_bytes;
-    if (d_rc) hipLaunchKernelGGL(k_rq_gather<true>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
-    else hipLaunchKernelGGL(k_rq_gather<false>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // the scratch blocks go back to the pool idle
-    return e;
+    if (d_rc) AIX_TRY_LAUNCH(k_rq_gather<true>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
+    else AIX_TRY_LAUNCH(k_rq_gather<false>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
+    return hipStreamSynchronize(s);                            // the scratch blocks go back to the pool idle
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -306,8 +301,6 @@ struct RkFlagBit {
     __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)((v >> bit) & 1u); }
 };
 
-static int rk_bits(uint64_t v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }
-
 // the positions of every k-mer (posquery_run), then the dedup. Outputs in pool blocks the caller owns: d_koff (N + 1), and — R reads —
 // rid / src (R) and len (R + 1, last 0).
 static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_koff, DevArr& rid, DevArr& src, DevArr& len, uint64_t* R_out,
@@ -315,77 +308,64 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     *R_out = 0;
     if (N == 0) return hipMemsetAsync(d_koff, 0, 8, s);
     DevArr off(s), pos(s), lst(s), key(s), flag(s), perm(s), k2(s), k3(s), p2(s), tmp(s), flags(s), rank(s), keep(s), orank(s), t1(s), t2(s);
-    hipError_t e = off.alloc(8 * (N + 1));
+    AIX_TRY(off.alloc(8 * (N + 1)));
     uint64_t T = 0, again = 0;
-    if (e == hipSuccess) e = posquery_run(h, d_kmers, N, 0, (uint64_t*)off.p, nullptr, nullptr, nullptr, 0, &T, s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(posquery_run(h, d_kmers, N, 0, (uint64_t*)off.p, nullptr, nullptr, nullptr, 0, &T, s));
     if (T == 0) return hipMemsetAsync(d_koff, 0, 8 * (N + 1), s);
-    e = pos.alloc(8 * T);
-    if (e == hipSuccess) e = posquery_run(h, d_kmers, N, 0, (uint64_t*)off.p, (uint64_t*)pos.p, nullptr, nullptr, T, &again, s);
-    if (e == hipSuccess && again != T) e = hipErrorUnknown;
-    if (e == hipSuccess) e = lst.alloc(8 * T);
-    if (e == hipSuccess) e = key.alloc(8 * T);
-    if (e == hipSuccess) e = flag.alloc(4);
-    if (e == hipSuccess) e = flags.alloc(T + 1);
-    if (e == hipSuccess) e = rank.alloc(8 * (T + 1));
-    if (e == hipSuccess) e = keep.alloc(T + 1);
-    if (e == hipSuccess) e = orank.alloc(8 * (T + 1));
-    if (e == hipSuccess) e = hipMemsetAsync(flag.p, 0, 4, s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(pos.alloc(8 * T));
+    AIX_TRY(posquery_run(h, d_kmers, N, 0, (uint64_t*)off.p, (uint64_t*)pos.p, nullptr, nullptr, T, &again, s));
+    if (again != T) return hipErrorUnknown;
+    AIX_TRY(lst.alloc(8 * T));
+    AIX_TRY(key.alloc(8 * T));
+    AIX_TRY(flag.alloc(4));
+    AIX_TRY(flags.alloc(T + 1));
+    AIX_TRY(rank.alloc(8 * (T + 1)));
+    AIX_TRY(keep.alloc(T + 1));
+    AIX_TRY(orank.alloc(8 * (T + 1)));
+    AIX_TRY(hipMemsetAsync(flag.p, 0, 4, s));
     const uint64_t rn = h->rx_n;
     const uint64_t *rs = h->rx, *re = h->rx + rn, *rr = h->rx + 2 * rn;
     const uint64_t *d_off = (const uint64_t*)off.p, *d_lst = (const uint64_t*)lst.p, *d_key = (const uint64_t*)key.p;
-    hipLaunchKernelGGL(k_rk_locate, dim3(flat_grid(T)), dim3(kRB), 0, s, d_off, N, (const uint64_t*)pos.p, T, rs, re, rn, (uint64_t*)lst.p, (uint64_t*)key.p);
-    hipLaunchKernelGGL(k_rk_ascending, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, d_key, T, (uint32_t*)flag.p);
-    e = hipGetLastError();
+    AIX_TRY_LAUNCH(k_rk_locate, dim3(flat_grid(T)), dim3(kRB), 0, s, d_off, N, (const uint64_t*)pos.p, T, rs, re, rn, (uint64_t*)lst.p, (uint64_t*)key.p);
+    AIX_TRY_LAUNCH(k_rk_ascending, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, d_key, T, (uint32_t*)flag.p);
     uint32_t unsorted = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&unsorted, flag.p, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(hipMemcpyAsync(&unsorted, flag.p, 4, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     const uint64_t* d_perm = nullptr;
     if (unsorted) {
         // some bucket's slots are not in ascending order (files written by a multi-threaded compute_aindex): entries ordered by
-        // (list, interval, entry) through two stable radix sorts of the entry numbers, by interval and then by list
-        e = perm.alloc(8 * T);
-        if (e == hipSuccess) e = k2.alloc(8 * T);
-        if (e == hipSuccess) e = p2.alloc(8 * T);
-        if (e == hipSuccess) e = k3.alloc(8 * T);
-        if (e != hipSuccess) return e;
+        // (list, interval, entry) through two stable radix sorts of the entry numbers, by interval and then by list. Both passes are
+        // sized first and share one block of the larger size (so not with_temp, which takes a block per call).
+        AIX_TRY(perm.alloc(8 * T));
+        AIX_TRY(k2.alloc(8 * T));
+        AIX_TRY(p2.alloc(8 * T));
+        AIX_TRY(k3.alloc(8 * T));
         size_t tb = 0, tb2 = 0;
-        const unsigned kb = (unsigned)rk_bits(rn), lb = (unsigned)rk_bits(N);
+        const unsigned kb = sort_bits(rn), lb = sort_bits(N);
         rocprim::counting_iterator<uint64_t> iota(0);
-        e = rocprim::radix_sort_pairs(nullptr, tb, d_key, (uint64_t*)k2.p, iota, (uint64_t*)perm.p, (size_t)T, 0u, kb, s);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s);
-        if (e == hipSuccess) e = tmp.alloc(std::max<size_t>(std::max(tb, tb2), 1));
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, d_key, (uint64_t*)k2.p, iota, (uint64_t*)perm.p, (size_t)T, 0u, kb, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rk_gather_lst, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, (const uint64_t*)perm.p, T, (uint64_t*)k3.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s);
-        if (e != hipSuccess) return e;
+        AIX_TRY(rocprim::radix_sort_pairs(nullptr, tb, d_key, (uint64_t*)k2.p, iota, (uint64_t*)perm.p, (size_t)T, 0u, kb, s));
+        AIX_TRY(rocprim::radix_sort_pairs(nullptr, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s));
+        AIX_TRY(tmp.alloc(std::max<size_t>(std::max(tb, tb2), 1)));
+        AIX_TRY(rocprim::radix_sort_pairs(tmp.p, tb, d_key, (uint64_t*)k2.p, iota, (uint64_t*)perm.p, (size_t)T, 0u, kb, s));
+        AIX_TRY_LAUNCH(k_rk_gather_lst, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, (const uint64_t*)perm.p, T, (uint64_t*)k3.p);
+        AIX_TRY(rocprim::radix_sort_pairs(tmp.p, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s));
         d_perm = (const uint64_t*)p2.p;
     }
-    hipLaunchKernelGGL(k_rk_first, dim3(flat_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->rd_len, (uint8_t*)flags.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)flags.p + T, 0, 1, s);
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)flags.p, RkFlagBit{(uint8_t)(m ? 1 : 0)}), (uint64_t*)rank.p, T + 1, t1, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rk_keep, dim3(flat_grid(T + 1)), dim3(kRB), 0, s, (const uint8_t*)flags.p, (const uint64_t*)rank.p, d_lst, d_off, T, m, (uint8_t*)keep.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)orank.p, T + 1, t2, s);
+    AIX_TRY_LAUNCH(k_rk_first, dim3(flat_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->rd_len, (uint8_t*)flags.p);
+    AIX_TRY(hipMemsetAsync((uint8_t*)flags.p + T, 0, 1, s));
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)flags.p, RkFlagBit{(uint8_t)(m ? 1 : 0)}), (uint64_t*)rank.p, T + 1, t1, s));
+    AIX_TRY_LAUNCH(k_rk_keep, dim3(flat_grid(T + 1)), dim3(kRB), 0, s, (const uint8_t*)flags.p, (const uint64_t*)rank.p, d_lst, d_off, T, m, (uint8_t*)keep.p);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)orank.p, T + 1, t2, s));
     uint64_t R = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&R, (const uint64_t*)orank.p + T, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = rid.alloc(8 * std::max<uint64_t>(R, 1));
-    if (e == hipSuccess) e = src.alloc(8 * std::max<uint64_t>(R, 1));
-    if (e == hipSuccess) e = len.alloc(8 * (R + 1));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rk_emit, dim3(flat_grid(std::max(T, N + 1))), dim3(kRB), 0, s, (const uint8_t*)keep.p, (const uint64_t*)orank.p, d_key, d_off, N, T, rs, re, rr, rn,
-                       h->rd_len, R, d_koff, (uint64_t*)rid.p, (uint64_t*)src.p, (uint64_t*)len.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    AIX_TRY(hipMemcpyAsync(&R, (const uint64_t*)orank.p + T, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    AIX_TRY(rid.alloc(8 * std::max<uint64_t>(R, 1)));
+    AIX_TRY(src.alloc(8 * std::max<uint64_t>(R, 1)));
+    AIX_TRY(len.alloc(8 * (R + 1)));
     *R_out = R;
-    return e;
+    AIX_TRY_LAUNCH(k_rk_emit, dim3(flat_grid(std::max(T, N + 1))), dim3(kRB), 0, s, (const uint8_t*)keep.p, (const uint64_t*)orank.p, d_key, d_off, N, T, rs, re, rr, rn,
+                   h->rd_len, R, d_koff, (uint64_t*)rid.p, (uint64_t*)src.p, (uint64_t*)len.p);
+    return hipStreamSynchronize(s);
 }
 
 }  // namespace aix
@@ -511,29 +491,16 @@ extern "C" int aix_reads_by_kmers_dev(aix_index_t* h, const char* d_kmers, uint6
             AIXCHK(hipStreamSynchronize(s));
         }
     } else if (d_read_offsets) {
-        AIXCHK(hipMemsetAsync(d_read_offsets, 0, 8, s));        // read_offsets = {0}
-        AIXCHK(hipStreamSynchronize(s));
+        AIXCHK(zero_offsets(d_read_offsets, 0, s));            // read_offsets = {0}
     }
     totals_out[0] = R; totals_out[1] = total;
-    return AIX_OK;
-}
-
-// device buffer -> malloc'd host copy (aix_free)
-static int rq_to_host(const void* d, uint64_t bytes, void** out) {
-    void* p = malloc(bytes ? bytes : 1);
-    if (!p) return AIX_ERR_NOMEM;
-    if (bytes) {
-        const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(p); AIXCHK(e); }
-    }
-    *out = p;
     return AIX_OK;
 }
 
 template <class Sizer>
 static int rq_host_fetch(uint64_t N, uint64_t** offsets_out, char** bytes_out, Sizer run) {
     *offsets_out = nullptr; *bytes_out = nullptr;
-    DevBuf doff, dby;
+    DevArr doff, dby;
     AIXCHK(doff.alloc(8 * (N + 1)));
     uint64_t total = 0, again = 0;
     if (const int st = run((uint64_t*)doff.p, nullptr, 0, &total)) return st;
@@ -542,10 +509,8 @@ static int rq_host_fetch(uint64_t N, uint64_t** offsets_out, char** bytes_out, S
         if (const int st = run((uint64_t*)doff.p, (char*)dby.p, total, &again)) return st;
         if (again != total) { set_last_error("aix_reads_fetch: the attachment changed between the sizing and the filling pass"); return AIX_ERR_HIP; }
     }
-    void *ho = nullptr, *hb = nullptr;
-    if (const int st = rq_to_host(doff.p, 8 * (N + 1), &ho)) return st;
-    if (const int st = rq_to_host(dby.p, total, &hb)) { free(ho); return st; }
-    *offsets_out = (uint64_t*)ho; *bytes_out = (char*)hb;
+    const HostOut outs[] = {{(void**)offsets_out, doff.p, 8 * (N + 1)}, {(void**)bytes_out, dby.p, total}};
+    AIXCHK(copy_out_host(outs, 2));
     return AIX_OK;
 }
 
@@ -555,14 +520,12 @@ extern "C" int aix_reads_fetch(aix_index_t* h, const uint64_t* start, const uint
     *offsets_out = nullptr; *bytes_out = nullptr;
     if (!h->rd_attached) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    DevBuf ds, de, dr;
-    AIXCHK(ds.alloc(8 * N));
-    AIXCHK(de.alloc(8 * N));
-    if (N) AIXCHK(hipMemcpy(ds.p, start, 8 * N, hipMemcpyHostToDevice));
-    if (N) AIXCHK(hipMemcpy(de.p, end, 8 * N, hipMemcpyHostToDevice));
-    if (revcomp && N) { AIXCHK(dr.alloc(N)); AIXCHK(hipMemcpy(dr.p, revcomp, N, hipMemcpyHostToDevice)); }
+    DevArr in[3];                                              // start, end, revcomp (no block when none is given or N == 0)
+    const HostIn ins[3] = {{start, 8 * N}, {end, 8 * N}, {N ? revcomp : nullptr, N}};
+    AIXCHK(copy_in_host(in, ins, 2));
+    AIXCHK(copy_in_host(in + 2, ins + 2, 1, true));
     return rq_host_fetch(N, offsets_out, bytes_out, [&](uint64_t* off, char* by, uint64_t cap, uint64_t* tot) {
-        return aix_reads_fetch_dev(h, (const uint64_t*)ds.p, (const uint64_t*)de.p, (const uint8_t*)dr.p, N, off, by, cap, tot, nullptr);
+        return aix_reads_fetch_dev(h, (const uint64_t*)in[0].p, (const uint64_t*)in[1].p, (const uint8_t*)in[2].p, N, off, by, cap, tot, nullptr);
     });
 }
 
@@ -571,9 +534,9 @@ extern "C" int aix_reads_fetch_rid(aix_index_t* h, const uint64_t* rid, uint64_t
     *offsets_out = nullptr; *bytes_out = nullptr;
     if (!h->rd_attached || !h->rx_attached) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    DevBuf dr;
-    AIXCHK(dr.alloc(8 * N));
-    if (N) AIXCHK(hipMemcpy(dr.p, rid, 8 * N, hipMemcpyHostToDevice));
+    DevArr dr;
+    const HostIn in{rid, 8 * N};
+    AIXCHK(copy_in_host(&dr, &in, 1));
     return rq_host_fetch(N, offsets_out, bytes_out, [&](uint64_t* off, char* by, uint64_t cap, uint64_t* tot) {
         return aix_reads_fetch_rid_dev(h, (const uint64_t*)dr.p, N, off, by, cap, tot, nullptr);
     });
@@ -586,12 +549,9 @@ extern "C" int aix_reads_by_kmers(aix_index_t* h, const char* kmers, uint64_t N,
     *bytes_out = nullptr;
     if (const int st = rk_check(h)) return st;
     DevGuard g(h->device);
-    const uint64_t qb = N * h->k;
-    DevBuf dq, dko, dby;
-    DevArr rid, src, len, roff;
-    AIXCHK(dq.alloc(qb + 16));
+    DevArr dq, dko, dby, rid, src, len, roff;
+    AIXCHK(upload_padded(dq, kmers, N * h->k));
     AIXCHK(dko.alloc(8 * (N + 1)));
-    if (qb) AIXCHK(hipMemcpy(dq.p, kmers, qb, hipMemcpyHostToDevice));
     uint64_t R = 0, total = 0, again = 0;
     AIXCHK(rk_run(h, (const uint8_t*)dq.p, N, max_reads, (uint64_t*)dko.p, rid, src, len, &R, nullptr));
     AIXCHK(roff.alloc(8 * (R + 1)));
@@ -602,12 +562,8 @@ extern "C" int aix_reads_by_kmers(aix_index_t* h, const char* kmers, uint64_t N,
     } else {
         AIXCHK(hipMemset(roff.p, 0, 8));
     }
-    void *hk = nullptr, *hr = nullptr, *ho = nullptr, *hb = nullptr;
-    int st = rq_to_host(dko.p, 8 * (N + 1), &hk);
-    if (!st) st = rq_to_host(rid.p, 8 * R, &hr);
-    if (!st) st = rq_to_host(roff.p, 8 * (R + 1), &ho);
-    if (!st) st = rq_to_host(dby.p, total, &hb);
-    if (st) { free(hk); free(hr); free(ho); free(hb); return st; }
-    *kmer_offsets_out = (uint64_t*)hk; *rid_out = (uint64_t*)hr; *read_offsets_out = (uint64_t*)ho; *bytes_out = (char*)hb;
+    const HostOut outs[] = {{(void**)kmer_offsets_out, dko.p, 8 * (N + 1)}, {(void**)rid_out, rid.p, 8 * R}, {(void**)read_offsets_out, roff.p, 8 * (R + 1)},
+                            {(void**)bytes_out, dby.p, total}};
+    AIXCHK(copy_out_host(outs, 4));
     return AIX_OK;
 }

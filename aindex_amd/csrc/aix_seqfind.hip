@@ -210,27 +210,20 @@ static hipError_t sf_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     F.S = F.R = 0;
     ShBufs B(s);
     DevArr soff(s), keep(s), hseq(s), srank(s), ts(s), ckey(s), csrc(s), kout(s), kin(s), pa(s), tmp(s), ts2(s);
-    hipError_t e = sh_alloc(soff, M + 1, 8);
-    if (e != hipSuccess) return e;
-    e = sh_run(h, d_seqs, d_offs, M, m, (uint64_t*)soff.p, nullptr, false, B, bad, s, step, false);   // containment here is not the interval rule of the hits
-    if (e != hipSuccess || *bad) return e;
+    AIX_TRY(sh_alloc(soff, M + 1, 8));
+    AIX_TRY(sh_run(h, d_seqs, d_offs, M, m, (uint64_t*)soff.p, nullptr, false, B, bad, s, step, false));   // containment here is not the interval rule of the hits
+    if (*bad) return hipSuccess;
     const uint64_t T = B.T;
-    auto none = [&]() {
-        hipError_t r = hipMemsetAsync(d_find_offsets, 0, 8 * (M + 1), s);
-        if (r == hipSuccess) r = hipStreamSynchronize(s);
-        return r;
-    };
-    if (T == 0) return none();
+    if (T == 0) return zero_offsets(d_find_offsets, M, s);
     B.koff.drop(); B.woff.drop();
-    e = sh_alloc(keep, T + 1, 1);
-    if (e == hipSuccess) e = sh_alloc(F.key, T, 8);
-    if (e == hipSuccess) e = sh_alloc(hseq, T, 8);
-    if (e == hipSuccess) e = sh_alloc(F.rid, T, 8);
-    if (e == hipSuccess) e = sh_alloc(F.local, T, 8);
-    if (e == hipSuccess) e = sh_alloc(F.dist, T, 4);
-    if (e == hipSuccess) e = sh_alloc(srank, T + 1, 8);
-    if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)keep.p + T, 0, 1, s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sh_alloc(keep, T + 1, 1));
+    AIX_TRY(sh_alloc(F.key, T, 8));
+    AIX_TRY(sh_alloc(hseq, T, 8));
+    AIX_TRY(sh_alloc(F.rid, T, 8));
+    AIX_TRY(sh_alloc(F.local, T, 8));
+    AIX_TRY(sh_alloc(F.dist, T, 4));
+    AIX_TRY(sh_alloc(srank, T + 1, 8));
+    AIX_TRY(hipMemsetAsync((uint8_t*)keep.p + T, 0, 1, s));
     SfVerify P{};
     P.seqs = d_seqs; P.offs = d_offs; P.soff = (const uint64_t*)soff.p; P.M = M; P.T = T;
     P.pos = (const uint64_t*)B.pos.p; P.qoff = (const uint32_t*)B.qoff.p; P.flag = (const uint8_t*)B.flag.p;
@@ -239,56 +232,43 @@ static hipError_t sf_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     P.hd = hd;
     P.keep = (uint8_t*)keep.p; P.key = (uint64_t*)F.key.p; P.hseq = (uint64_t*)hseq.p; P.rid = (uint64_t*)F.rid.p; P.local = (uint64_t*)F.local.p;
     P.dist = (uint32_t*)F.dist.p;
-    hipLaunchKernelGGL(k_sf_verify, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)srank.p, T + 1, ts, s);
-    uint64_t S = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&S, (const uint64_t*)srank.p + T, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY_LAUNCH(k_sf_verify, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)keep.p, Widen<uint8_t>()), (uint64_t*)srank.p, T + 1, ts, s));
+    uint64_t S = 0;               // read back asynchronously: declared after the DevArrs, whose destructors synchronise `s` before an early return leaves the frame
+    AIX_TRY(hipMemcpyAsync(&S, (const uint64_t*)srank.p + T, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     B.pos.drop(); B.qoff.drop(); B.flag.drop();
-    if (S == 0) return none();
+    if (S == 0) return zero_offsets(d_find_offsets, M, s);
     F.S = S;
-    e = sh_alloc(ckey, S, 8);
-    if (e == hipSuccess) e = sh_alloc(csrc, S, 8);
-    if (e == hipSuccess) e = sh_alloc(kout, S, 8);
-    if (e == hipSuccess) e = sh_alloc(kin, S, 8);
-    if (e == hipSuccess) e = sh_alloc(pa, S, 8);
-    if (e == hipSuccess) e = sh_alloc(F.perm, S, 8);
-    if (e == hipSuccess) e = sh_alloc(F.head, S + 1, 1);
-    if (e == hipSuccess) e = sh_alloc(F.orank, S + 1, 8);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sh_alloc(ckey, S, 8));
+    AIX_TRY(sh_alloc(csrc, S, 8));
+    AIX_TRY(sh_alloc(kout, S, 8));
+    AIX_TRY(sh_alloc(kin, S, 8));
+    AIX_TRY(sh_alloc(pa, S, 8));
+    AIX_TRY(sh_alloc(F.perm, S, 8));
+    AIX_TRY(sh_alloc(F.head, S + 1, 1));
+    AIX_TRY(sh_alloc(F.orank, S + 1, 8));
     const dim3 blk(kSB), gS(flat_grid(S));
-    hipLaunchKernelGGL(k_sf_compact, dim3(flat_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
-                       (uint64_t*)csrc.p);
-    e = hipGetLastError();
+    AIX_TRY_LAUNCH(k_sf_compact, dim3(flat_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
+                   (uint64_t*)csrc.p);
     // least significant key first: (a, strand), then the sequence; a <= reads_len, so the key needs the bits of 2 reads_len + 1
-    if (e == hipSuccess) e = sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sv_bits((h->rd_len << 1) | 1ull), tmp, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gS, blk, 0, s, (const uint64_t*)hseq.p, (const uint64_t*)pa.p, S, SvSame(), (uint64_t*)kin.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = sort_pairs((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sv_bits(M), tmp, s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sort_bits((h->rd_len << 1) | 1ull), tmp, s));
+    AIX_TRY_LAUNCH((k_sv_gather<uint64_t, SvSame>), gS, blk, 0, s, (const uint64_t*)hseq.p, (const uint64_t*)pa.p, S, SvSame(), (uint64_t*)kin.p);
+    AIX_TRY(sort_pairs((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sort_bits(M), tmp, s));
     const uint64_t* sseq = (const uint64_t*)kout.p;
-    hipLaunchKernelGGL(k_sf_heads, dim3(flat_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)F.head.p, Widen<uint8_t>()), (uint64_t*)F.orank.p, S + 1, ts2, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&F.R, (const uint64_t*)F.orank.p + S, 8, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sf_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e;
+    AIX_TRY_LAUNCH(k_sf_heads, dim3(flat_grid(S + 1)), blk, 0, s, (const uint64_t*)F.perm.p, sseq, (const uint64_t*)F.key.p, S, (uint8_t*)F.head.p);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)F.head.p, Widen<uint8_t>()), (uint64_t*)F.orank.p, S + 1, ts2, s));
+    AIX_TRY(hipMemcpyAsync(&F.R, (const uint64_t*)F.orank.p + S, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY_LAUNCH(k_sf_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)F.orank.p, S, M, d_find_offsets);
+    return hipStreamSynchronize(s);
 }
 
 // the F.R records into buffers that hold them. Synchronises `s`.
 static hipError_t sf_write(const SfState& F, const SfOut& O, hipStream_t s) {
     if (F.R == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sf_write, dim3(flat_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
-                       (const uint64_t*)F.key.p, (const uint64_t*)F.rid.p, (const uint64_t*)F.local.p, (const uint32_t*)F.dist.p, O);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e;
+    AIX_TRY_LAUNCH(k_sf_write, dim3(flat_grid(F.S)), dim3(kSB), 0, s, (const uint8_t*)F.head.p, (const uint64_t*)F.orank.p, (const uint64_t*)F.perm.p, F.S,
+                   (const uint64_t*)F.key.p, (const uint64_t*)F.rid.p, (const uint64_t*)F.local.p, (const uint32_t*)F.dist.p, O);
+    return hipStreamSynchronize(s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -327,29 +307,23 @@ __global__ void __launch_bounds__(kSB) k_ks_counts(const uint64_t* __restrict__ 
 static hipError_t ks_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64_t m, uint64_t* d_plus, uint64_t* d_minus, uint64_t* d_total, hipStream_t s) {
     ShBufs B(s);
     DevArr offs(s), soff(s), sp(s), sm(s), t0(s), t1(s);
-    hipError_t e = sh_alloc(offs, N + 1, 8);
-    if (e == hipSuccess) e = sh_alloc(soff, N + 1, 8);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ks_offs, dim3(flat_grid(N + 1)), dim3(kSB), 0, s, N, (uint64_t*)offs.p);
-    e = hipGetLastError();
+    AIX_TRY(sh_alloc(offs, N + 1, 8));
+    AIX_TRY(sh_alloc(soff, N + 1, 8));
+    AIX_TRY_LAUNCH(k_ks_offs, dim3(flat_grid(N + 1)), dim3(kSB), 0, s, N, (uint64_t*)offs.p);
     bool bad = false;
-    if (e == hipSuccess) e = sh_run(h, d_kmers, (const uint64_t*)offs.p, N, m, (uint64_t*)soff.p, nullptr, false, B, &bad, s, 1, false);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sh_run(h, d_kmers, (const uint64_t*)offs.p, N, m, (uint64_t*)soff.p, nullptr, false, B, &bad, s, 1, false));
     if (bad) return hipErrorInvalidValue;                      // 23-byte sequences cannot be: kept for the day they can
     const uint64_t T = B.T;
     if (T) {
         B.pos.drop(); B.qoff.drop();
-        e = sh_alloc(sp, T, 8);
-        if (e == hipSuccess) e = sh_alloc(sm, T, 8);
-        if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{0}), (uint64_t*)sp.p, T, t0, s);
-        if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{1}), (uint64_t*)sm.p, T, t1, s);
-        if (e != hipSuccess) return e;
+        AIX_TRY(sh_alloc(sp, T, 8));
+        AIX_TRY(sh_alloc(sm, T, 8));
+        AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{0}), (uint64_t*)sp.p, T, t0, s));
+        AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)B.flag.p, KsIsStrand{1}), (uint64_t*)sm.p, T, t1, s));
     }
-    hipLaunchKernelGGL(k_ks_counts, dim3(flat_grid(N)), dim3(kSB), 0, s, (const uint64_t*)soff.p, (const uint64_t*)sp.p, (const uint64_t*)sm.p,
-                       (const uint8_t*)B.flag.p, T, N, d_plus, d_minus, d_total);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e;
+    AIX_TRY_LAUNCH(k_ks_counts, dim3(flat_grid(N)), dim3(kSB), 0, s, (const uint64_t*)soff.p, (const uint64_t*)sp.p, (const uint64_t*)sm.p,
+                   (const uint8_t*)B.flag.p, T, N, d_plus, d_minus, d_total);
+    return hipStreamSynchronize(s);
 }
 
 }  // namespace aix
@@ -369,7 +343,7 @@ extern "C" int aix_seq_find_dev(aix_index_t* h, const char* d_seqs, const uint64
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { AIXCHK(hipMemsetAsync(d_find_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(zero_offsets(d_find_offsets, 0, s)); return AIX_OK; }
     SfState F(s);
     bool bad = false;
     AIXCHK(sf_run(h, (const uint8_t*)d_seqs, d_offs, M, hd, seed_step ? seed_step : 23, max_per_kmer, d_find_offsets, F, &bad, s));
@@ -387,7 +361,7 @@ extern "C" int aix_seq_find(aix_index_t* h, const char* seqs, const uint64_t* of
     if (const int st = sh_check(h)) return st;
     if (h->rd_len >= (1ull << 62)) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
-    DevBuf ds, dof, dfo, dp, dr, dl, dst, dd;
+    DevArr ds, dof, dfo, dp, dr, dl, dst, dd;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
     AIXCHK(dfo.alloc(8 * (M + 1)));
     AIXCHK(hipMemset(dfo.p, 0, 8 * (M + 1)));
@@ -400,16 +374,9 @@ extern "C" int aix_seq_find(aix_index_t* h, const char* seqs, const uint64_t* of
         AIXCHK(dp.alloc(8 * R)); AIXCHK(dr.alloc(8 * R)); AIXCHK(dl.alloc(8 * R)); AIXCHK(dst.alloc(R)); AIXCHK(dd.alloc(4 * R));
         AIXCHK(sf_write(F, SfOut{(uint64_t*)dp.p, (uint64_t*)dr.p, (uint64_t*)dl.p, (uint8_t*)dst.p, (uint32_t*)dd.p}, nullptr));
     }
-    void *ho = nullptr, *hp = nullptr, *hr = nullptr, *hl = nullptr, *hs = nullptr, *hdd = nullptr;
-    int st = sh_to_host(dfo.p, 8 * (M + 1), &ho);
-    if (!st) st = sh_to_host(dp.p, 8 * R, &hp);
-    if (!st) st = sh_to_host(dr.p, 8 * R, &hr);
-    if (!st) st = sh_to_host(dl.p, 8 * R, &hl);
-    if (!st) st = sh_to_host(dst.p, R, &hs);
-    if (!st) st = sh_to_host(dd.p, 4 * R, &hdd);
-    if (st) { free(ho); free(hp); free(hr); free(hl); free(hs); free(hdd); return st; }
-    *find_offsets_out = (uint64_t*)ho; *pos_out = (uint64_t*)hp; *rid_out = (uint64_t*)hr; *local_out = (uint64_t*)hl; *strand_out = (uint8_t*)hs;
-    *dist_out = (uint32_t*)hdd;
+    const HostOut outs[] = {{(void**)find_offsets_out, dfo.p, 8 * (M + 1)}, {(void**)pos_out, dp.p, 8 * R}, {(void**)rid_out, dr.p, 8 * R},
+                            {(void**)local_out, dl.p, 8 * R},               {(void**)strand_out, dst.p, R}, {(void**)dist_out, dd.p, 4 * R}};
+    AIXCHK(copy_out_host(outs, 6));
     return AIX_OK;
 }
 
@@ -428,10 +395,9 @@ extern "C" int aix_kmer_strands(aix_index_t* h, const char* kmers, uint64_t N, u
     if (const int st = sh_check(h)) return st;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    DevBuf dq, dc;
-    AIXCHK(dq.alloc(23 * N + 16));                              // padded for load23
+    DevArr dq, dc;
+    AIXCHK(upload_padded(dq, kmers, 23 * N));
     AIXCHK(dc.alloc(24 * N));
-    AIXCHK(hipMemcpy(dq.p, kmers, 23 * N, hipMemcpyHostToDevice));
     uint64_t* c = (uint64_t*)dc.p;
     AIXCHK(ks_run(h, (const uint8_t*)dq.p, N, max_per_kmer, c, c + N, c + 2 * N, nullptr));
     AIXCHK(hipMemcpy(plus_out, c, 8 * N, hipMemcpyDeviceToHost));

@@ -171,55 +171,41 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
     *bad = false;
     B.W = B.T = 0;
     DevArr nwin(s), fl(s), tmp(s), lo(s), ub(s), wseq(s), wsrc(s);
-    hipError_t e = sh_alloc(nwin, M + 1, 8);
-    if (e == hipSuccess) e = sh_alloc(B.woff, M + 1, 8);
-    if (e == hipSuccess) e = fl.alloc(4);
-    if (e == hipSuccess) e = hipMemsetAsync(fl.p, 0, 4, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sh_windows, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, step, (uint64_t*)nwin.p, (uint32_t*)fl.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64((const uint64_t*)nwin.p, (uint64_t*)B.woff.p, M + 1, tmp, s);
-    uint64_t W = 0;
+    AIX_TRY(sh_alloc(nwin, M + 1, 8));
+    AIX_TRY(sh_alloc(B.woff, M + 1, 8));
+    AIX_TRY(fl.alloc(4));
+    AIX_TRY(hipMemsetAsync(fl.p, 0, 4, s));
+    AIX_TRY_LAUNCH(k_sh_windows, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, d_offs, M, step, (uint64_t*)nwin.p, (uint32_t*)fl.p);
+    AIX_TRY(scan_u64((const uint64_t*)nwin.p, (uint64_t*)B.woff.p, M + 1, tmp, s));
+    uint64_t W = 0;               // read back asynchronously: declared after the DevArrs, whose destructors synchronise `s` before an early return leaves the frame
     uint32_t flag = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&W, (const uint64_t*)B.woff.p + M, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, fl.p, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(hipMemcpyAsync(&W, (const uint64_t*)B.woff.p + M, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipMemcpyAsync(&flag, fl.p, 4, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
     if (flag || (W && !d_seqs)) { *bad = true; return hipSuccess; }     // (no bytes are needed when no sequence has a window: M empty sequences)
     B.W = W;
-    if (W == 0) {
-        if (d_seq_offsets) e = hipMemsetAsync(d_seq_offsets, 0, 8 * (M + 1), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        return e;
-    }
-    e = sh_alloc(lo, W, 8);
-    if (e == hipSuccess) e = sh_alloc(ub, W + 1, 8);
-    if (e == hipSuccess) e = sh_alloc(wseq, W, 8);
-    if (e == hipSuccess) e = sh_alloc(wsrc, W, 8);
-    if (e == hipSuccess) e = sh_alloc(B.koff, W + 1, 8);
-    if (e == hipSuccess) e = hipMemsetAsync((uint64_t*)ub.p + W, 0, 8, s);
-    if (e != hipSuccess) return e;
+    if (W == 0) return d_seq_offsets ? zero_offsets(d_seq_offsets, M, s) : hipStreamSynchronize(s);
+    AIX_TRY(sh_alloc(lo, W, 8));
+    AIX_TRY(sh_alloc(ub, W + 1, 8));
+    AIX_TRY(sh_alloc(wseq, W, 8));
+    AIX_TRY(sh_alloc(wsrc, W, 8));
+    AIX_TRY(sh_alloc(B.koff, W + 1, 8));
+    AIX_TRY(hipMemsetAsync((uint64_t*)ub.p + W, 0, 8, s));
     const IndexDev ix = h->dev();
     const uint64_t* woff = (const uint64_t*)B.woff.p;
-#define AIX_SH_RESOLVE(L)                                                                                                                                  \
-    hipLaunchKernelGGL(k_sh_resolve<L>, dim3(flat_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
-                       (uint64_t*)wsrc.p, (uint64_t*)lo.p, (uint64_t*)ub.p)
+#define AIX_SH_RESOLVE(L)                                                                                                                              \
+    AIX_TRY_LAUNCH(k_sh_resolve<L>, dim3(flat_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
+                   (uint64_t*)wsrc.p, (uint64_t*)lo.p, (uint64_t*)ub.p)
     if (ix.bk_lpp == 2) AIX_SH_RESOLVE(2);
     else if (ix.bk_lpp == 4) AIX_SH_RESOLVE(4);
     else AIX_SH_RESOLVE(8);
 #undef AIX_SH_RESOLVE
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
     uint64_t T = 0;
-    e = posquery_lists(h, (const uint64_t*)lo.p, (const uint64_t*)ub.p, W, m, (uint64_t*)B.koff.p, user ? user->pos : nullptr, nullptr, nullptr, user ? user->cap : 0, &T, s,
-                       user ? nullptr : &B.pos);
-    if (e != hipSuccess) return e;
+    AIX_TRY(posquery_lists(h, (const uint64_t*)lo.p, (const uint64_t*)ub.p, W, m, (uint64_t*)B.koff.p, user ? user->pos : nullptr, nullptr, nullptr, user ? user->cap : 0, &T, s,
+                           user ? nullptr : &B.pos));
     B.T = T;
-    if (d_seq_offsets) {
-        hipLaunchKernelGGL(k_sh_seqoff, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, woff, (const uint64_t*)B.koff.p, M, d_seq_offsets);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && T && (!user || (T <= user->cap && user->pos))) {
+    if (d_seq_offsets) AIX_TRY_LAUNCH(k_sh_seqoff, dim3(flat_grid(M + 1)), dim3(kSB), 0, s, woff, (const uint64_t*)B.koff.p, M, d_seq_offsets);
+    if (T && (!user || (T <= user->cap && user->pos))) {
         ShHits P{};
         P.seqs = d_seqs; P.woff = woff; P.koff = (const uint64_t*)B.koff.p; P.wseq = (const uint64_t*)wseq.p; P.wsrc = (const uint64_t*)wsrc.p;
         P.M = M; P.W = W; P.T = T; P.step = step;
@@ -228,22 +214,19 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
         if (user) {
             P.pos = user->pos; P.qoff = user->qoff; P.rid = user->rid; P.local = user->local; P.flag = user->flag;
         } else {
-            e = sh_alloc(B.qoff, T, 4);
-            if (e == hipSuccess && locate) e = sh_alloc(B.rid, T, 8);
-            if (e == hipSuccess && locate) e = sh_alloc(B.local, T, 8);
-            if (e == hipSuccess) e = sh_alloc(B.flag, T, 1);
-            if (e == hipSuccess && votes) e = sh_alloc(B.hseq, T, 8);
-            if (e == hipSuccess && votes) e = sh_alloc(B.diag, T, 8);
-            if (e != hipSuccess) return e;
+            AIX_TRY(sh_alloc(B.qoff, T, 4));
+            if (locate) AIX_TRY(sh_alloc(B.rid, T, 8));
+            if (locate) AIX_TRY(sh_alloc(B.local, T, 8));
+            AIX_TRY(sh_alloc(B.flag, T, 1));
+            if (votes) AIX_TRY(sh_alloc(B.hseq, T, 8));
+            if (votes) AIX_TRY(sh_alloc(B.diag, T, 8));
             P.pos = (const uint64_t*)B.pos.p; P.qoff = (uint32_t*)B.qoff.p; P.rid = (uint64_t*)B.rid.p; P.local = (int64_t*)B.local.p; P.flag = (uint8_t*)B.flag.p;
             P.hseq = (uint64_t*)B.hseq.p; P.diag = (int64_t*)B.diag.p;
         }
-        if (locate) hipLaunchKernelGGL(k_sh_hits<true>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
-        else hipLaunchKernelGGL(k_sh_hits<false>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
-        e = hipGetLastError();
+        if (locate) AIX_TRY_LAUNCH(k_sh_hits<true>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
+        else AIX_TRY_LAUNCH(k_sh_hits<false>, dim3(flat_grid(T)), dim3(kSB), 0, s, P);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // the scratch blocks go back to the pool idle
-    return e;
+    return hipStreamSynchronize(s);                            // the scratch blocks go back to the pool idle
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -347,90 +330,64 @@ __global__ void __launch_bounds__(kSB) k_sv_write(const uint64_t* __restrict__ g
 static hipError_t sv_run(const ShBufs& B, uint64_t M, uint64_t min_votes, uint64_t* d_vote_offsets, const SvOut& O, uint64_t cap, uint64_t* total_out, hipStream_t s) {
     *total_out = 0;
     const uint64_t T = B.T;
-    if (T == 0) {
-        hipError_t e = hipMemsetAsync(d_vote_offsets, 0, 8 * (M + 1), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        return e;
-    }
+    if (T == 0) return zero_offsets(d_vote_offsets, M, s);
     const uint64_t* hseq = (const uint64_t*)B.hseq.p;
     const int64_t* diag = (const int64_t*)B.diag.p;
     const uint64_t* rid = (const uint64_t*)B.rid.p;
     const uint8_t* flag = (const uint8_t*)B.flag.p;
     DevArr rng(s), rt(s), pa(s), pb(s), kin(s), kout(s), k8in(s), k8out(s), tmp(s), head(s), gid(s), ts(s), gstart(s), emit(s), orank(s), ts2(s);
-    hipError_t e = rng.alloc(sizeof(SvRange));
-    if (e == hipSuccess) e = sh_alloc(pa, T, 8);
-    if (e == hipSuccess) e = sh_alloc(pb, T, 8);
-    if (e == hipSuccess) e = sh_alloc(kin, T + 1, 8);           // (T + 1: the blocks of kin and k8in fit gid and head afterwards)
-    if (e == hipSuccess) e = sh_alloc(kout, T + 1, 8);
-    if (e == hipSuccess) e = sh_alloc(k8in, T + 1, 1);
-    if (e == hipSuccess) e = sh_alloc(k8out, T + 1, 1);
-    if (e != hipSuccess) return e;
+    AIX_TRY(rng.alloc(sizeof(SvRange)));
+    AIX_TRY(sh_alloc(pa, T, 8));
+    AIX_TRY(sh_alloc(pb, T, 8));
+    AIX_TRY(sh_alloc(kin, T + 1, 8));                          // (T + 1: the blocks of kin and k8in fit gid and head afterwards)
+    AIX_TRY(sh_alloc(kout, T + 1, 8));
+    AIX_TRY(sh_alloc(k8in, T + 1, 1));
+    AIX_TRY(sh_alloc(k8out, T + 1, 1));
     const SvRange none{INT64_MAX, INT64_MIN, 0};
     SvRange r = none;
     {
         auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), SvRangeOf{hseq, diag, rid, M});
-        e = with_temp(rt, [&](void* t, size_t& tb) { return rocprim::reduce(t, tb, in, (SvRange*)rng.p, none, (size_t)T, SvRangeJoin(), s); });
-        if (e == hipSuccess) e = hipMemcpyAsync(&r, rng.p, sizeof(SvRange), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return e;
+        AIX_TRY(with_temp(rt, [&](void* t, size_t& tb) { return rocprim::reduce(t, tb, in, (SvRange*)rng.p, none, (size_t)T, SvRangeJoin(), s); }));
+        AIX_TRY(hipMemcpyAsync(&r, rng.p, sizeof(SvRange), hipMemcpyDeviceToHost, s));
+        AIX_TRY(hipStreamSynchronize(s));
     }
-    if (r.dlo > r.dhi) {                                       // no hit is kept
-        e = hipMemsetAsync(d_vote_offsets, 0, 8 * (M + 1), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        return e;
-    }
+    if (r.dlo > r.dhi) return zero_offsets(d_vote_offsets, M, s);          // no hit is kept
     uint64_t *d_pa = (uint64_t*)pa.p, *d_pb = (uint64_t*)pb.p, *d_kin = (uint64_t*)kin.p, *d_kout = (uint64_t*)kout.p;
     const dim3 gT(flat_grid(T)), blk(kSB);
     // least significant key first: diagonal, strand, read id, sequence
-    e = sort_pairs(rocprim::make_transform_iterator(diag, SvDiagKey{r.dlo}), d_kout, rocprim::counting_iterator<uint64_t>(0), d_pa, T,
-                sv_bits((uint64_t)r.dhi - (uint64_t)r.dlo), tmp, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sv_gather<uint8_t, SvStrandOf>), gT, blk, 0, s, flag, (const uint64_t*)d_pa, T, SvStrandOf(), (uint8_t*)k8in.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = sort_pairs((const uint8_t*)k8in.p, (uint8_t*)k8out.p, (const uint64_t*)d_pa, d_pb, T, 2u, tmp, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, rid, (const uint64_t*)d_pb, T, SvSame(), d_kin);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pb, d_pa, T, sv_bits(r.rmax), tmp, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, hseq, (const uint64_t*)d_pa, T, SvSame(), d_kin);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pa, d_pb, T, sv_bits(M), tmp, s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sort_pairs(rocprim::make_transform_iterator(diag, SvDiagKey{r.dlo}), d_kout, rocprim::counting_iterator<uint64_t>(0), d_pa, T,
+                       sort_bits((uint64_t)r.dhi - (uint64_t)r.dlo), tmp, s));
+    AIX_TRY_LAUNCH((k_sv_gather<uint8_t, SvStrandOf>), gT, blk, 0, s, flag, (const uint64_t*)d_pa, T, SvStrandOf(), (uint8_t*)k8in.p);
+    AIX_TRY(sort_pairs((const uint8_t*)k8in.p, (uint8_t*)k8out.p, (const uint64_t*)d_pa, d_pb, T, 2u, tmp, s));
+    AIX_TRY_LAUNCH((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, rid, (const uint64_t*)d_pb, T, SvSame(), d_kin);
+    AIX_TRY(sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pb, d_pa, T, sort_bits(r.rmax), tmp, s));
+    AIX_TRY_LAUNCH((k_sv_gather<uint64_t, SvSame>), gT, blk, 0, s, hseq, (const uint64_t*)d_pa, T, SvSame(), d_kin);
+    AIX_TRY(sort_pairs((const uint64_t*)d_kin, d_kout, (const uint64_t*)d_pa, d_pb, T, sort_bits(M), tmp, s));
     const uint64_t *perm = d_pb, *sseq = d_kout;               // the hits by (sequence, read, strand, diagonal, hit number); dropped hits last
     pa.drop(); kin.drop(); k8in.drop(); k8out.drop(); tmp.drop();          // (waits for the sorts) their blocks serve the passes below
-    e = sh_alloc(head, T + 1, 1);
-    if (e == hipSuccess) e = sh_alloc(gid, T + 1, 8);
-    if (e != hipSuccess) return e;
+    AIX_TRY(sh_alloc(head, T + 1, 1));
+    AIX_TRY(sh_alloc(gid, T + 1, 8));
     const dim3 gT1(flat_grid(T + 1));
-    hipLaunchKernelGGL(k_sv_heads, gT1, blk, 0, s, perm, sseq, rid, flag, diag, T, M, (uint8_t*)head.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)head.p, Widen<uint8_t>()), (uint64_t*)gid.p, T + 1, ts, s);
+    AIX_TRY_LAUNCH(k_sv_heads, gT1, blk, 0, s, perm, sseq, rid, flag, diag, T, M, (uint8_t*)head.p);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)head.p, Widen<uint8_t>()), (uint64_t*)gid.p, T + 1, ts, s));
     uint64_t G = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&G, (const uint64_t*)gid.p + T, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = sh_alloc(gstart, G + 1, 8);
-    if (e == hipSuccess) e = sh_alloc(emit, G + 1, 1);
-    if (e == hipSuccess) e = sh_alloc(orank, G + 1, 8);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sv_starts, gT1, blk, 0, s, (const uint8_t*)head.p, (const uint64_t*)gid.p, sseq, T, M, G, (uint64_t*)gstart.p);
-    hipLaunchKernelGGL(k_sv_emit, dim3(flat_grid(G + 1)), blk, 0, s, (const uint64_t*)gstart.p, G, min_votes, (uint8_t*)emit.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = scan_u64(rocprim::make_transform_iterator((const uint8_t*)emit.p, Widen<uint8_t>()), (uint64_t*)orank.p, G + 1, ts2, s);
+    AIX_TRY(hipMemcpyAsync(&G, (const uint64_t*)gid.p + T, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    AIX_TRY(sh_alloc(gstart, G + 1, 8));
+    AIX_TRY(sh_alloc(emit, G + 1, 1));
+    AIX_TRY(sh_alloc(orank, G + 1, 8));
+    AIX_TRY_LAUNCH(k_sv_starts, gT1, blk, 0, s, (const uint8_t*)head.p, (const uint64_t*)gid.p, sseq, T, M, G, (uint64_t*)gstart.p);
+    AIX_TRY_LAUNCH(k_sv_emit, dim3(flat_grid(G + 1)), blk, 0, s, (const uint64_t*)gstart.p, G, min_votes, (uint8_t*)emit.p);
+    AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)emit.p, Widen<uint8_t>()), (uint64_t*)orank.p, G + 1, ts2, s));
     uint64_t R = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&R, (const uint64_t*)orank.p + G, 8, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sv_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)gid.p, (const uint64_t*)orank.p, T, M, d_vote_offsets);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
+    AIX_TRY(hipMemcpyAsync(&R, (const uint64_t*)orank.p + G, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY_LAUNCH(k_sv_seqoff, dim3(flat_grid(M + 1)), blk, 0, s, sseq, (const uint64_t*)gid.p, (const uint64_t*)orank.p, T, M, d_vote_offsets);
+    AIX_TRY(hipStreamSynchronize(s));
     *total_out = R;
     if (R == 0 || R > cap || !O.rid) return hipSuccess;
-    hipLaunchKernelGGL(k_sv_write, dim3(flat_grid(G)), blk, 0, s, (const uint64_t*)gstart.p, (const uint8_t*)emit.p, (const uint64_t*)orank.p, G, perm, rid, flag, diag,
-                       (const uint32_t*)B.qoff.p, O);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e;
+    AIX_TRY_LAUNCH(k_sv_write, dim3(flat_grid(G)), blk, 0, s, (const uint64_t*)gstart.p, (const uint8_t*)emit.p, (const uint64_t*)orank.p, G, perm, rid, flag, diag,
+                   (const uint32_t*)B.qoff.p, O);
+    return hipStreamSynchronize(s);
 }
 
 }  // namespace aix
@@ -446,7 +403,7 @@ extern "C" int aix_seq_hits_dev(aix_index_t* h, const char* d_seqs, const uint64
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { AIXCHK(hipMemsetAsync(d_seq_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(zero_offsets(d_seq_offsets, 0, s)); return AIX_OK; }
     const ShUser u{d_qoff, cap ? d_pos : nullptr, d_rid, d_local, d_flag, cap};
     ShBufs B(s);
     bool bad = false;
@@ -465,7 +422,7 @@ extern "C" int aix_seq_votes_dev(aix_index_t* h, const char* d_seqs, const uint6
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
-    if (M == 0) { AIXCHK(hipMemsetAsync(d_vote_offsets, 0, 8, s)); AIXCHK(hipStreamSynchronize(s)); return AIX_OK; }
+    if (M == 0) { AIXCHK(zero_offsets(d_vote_offsets, 0, s)); return AIX_OK; }
     ShBufs B(s);
     bool bad = false;
     AIXCHK(sh_run(h, (const uint8_t*)d_seqs, d_offs, M, max_per_kmer, nullptr, nullptr, true, B, &bad, s));
@@ -483,7 +440,7 @@ extern "C" int aix_seq_hits(aix_index_t* h, const char* seqs, const uint64_t* of
     if (M && offs[M] && !seqs) return AIX_ERR_ARG;
     if (const int st = sh_check(h)) return st;
     DevGuard g(h->device);
-    DevBuf ds, dof, dso;
+    DevArr ds, dof, dso;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
     AIXCHK(dso.alloc(8 * (M + 1)));
     AIXCHK(hipMemset(dso.p, 0, 8 * (M + 1)));
@@ -492,15 +449,9 @@ extern "C" int aix_seq_hits(aix_index_t* h, const char* seqs, const uint64_t* of
     if (M) AIXCHK(sh_run(h, (const uint8_t*)ds.p, (const uint64_t*)dof.p, M, max_per_kmer, (uint64_t*)dso.p, nullptr, false, B, &bad, nullptr));
     if (bad) return AIX_ERR_ARG;
     const uint64_t T = B.T;
-    void *ho = nullptr, *hq = nullptr, *hp = nullptr, *hr = nullptr, *hl = nullptr, *hf = nullptr;
-    int st = sh_to_host(dso.p, 8 * (M + 1), &ho);
-    if (!st) st = sh_to_host(B.qoff.p, 4 * T, &hq);
-    if (!st) st = sh_to_host(B.pos.p, 8 * T, &hp);
-    if (!st) st = sh_to_host(B.rid.p, 8 * T, &hr);
-    if (!st) st = sh_to_host(B.local.p, 8 * T, &hl);
-    if (!st) st = sh_to_host(B.flag.p, T, &hf);
-    if (st) { free(ho); free(hq); free(hp); free(hr); free(hl); free(hf); return st; }
-    *seq_offsets_out = (uint64_t*)ho; *qoff_out = (uint32_t*)hq; *pos_out = (uint64_t*)hp; *rid_out = (uint64_t*)hr; *local_out = (int64_t*)hl; *flag_out = (uint8_t*)hf;
+    const HostOut outs[] = {{(void**)seq_offsets_out, dso.p, 8 * (M + 1)}, {(void**)qoff_out, B.qoff.p, 4 * T}, {(void**)pos_out, B.pos.p, 8 * T},
+                            {(void**)rid_out, B.rid.p, 8 * T},             {(void**)local_out, B.local.p, 8 * T}, {(void**)flag_out, B.flag.p, T}};
+    AIXCHK(copy_out_host(outs, 6));
     return AIX_OK;
 }
 
@@ -512,7 +463,7 @@ extern "C" int aix_seq_votes(aix_index_t* h, const char* seqs, const uint64_t* o
     if (M && offs[M] && !seqs) return AIX_ERR_ARG;
     if (const int st = sh_check(h)) return st;
     DevGuard g(h->device);
-    DevBuf ds, dof, dvo, dr, dst, dd, dv, dqf, dql;
+    DevArr ds, dof, dvo, dr, dst, dd, dv, dqf, dql;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;
     AIXCHK(dvo.alloc(8 * (M + 1)));
     AIXCHK(hipMemset(dvo.p, 0, 8 * (M + 1)));
@@ -530,16 +481,9 @@ extern "C" int aix_seq_votes(aix_index_t* h, const char* seqs, const uint64_t* o
         const SvOut O{(uint64_t*)dr.p, (uint8_t*)dst.p, (int64_t*)dd.p, (uint32_t*)dv.p, (uint32_t*)dqf.p, (uint32_t*)dql.p};
         AIXCHK(sv_run(B, M, min_votes, (uint64_t*)dvo.p, O, cap, &R, nullptr));
     }
-    void *ho = nullptr, *hr = nullptr, *hs = nullptr, *hd = nullptr, *hv = nullptr, *hf = nullptr, *hl = nullptr;
-    int st = sh_to_host(dvo.p, 8 * (M + 1), &ho);
-    if (!st) st = sh_to_host(dr.p, 8 * R, &hr);
-    if (!st) st = sh_to_host(dst.p, R, &hs);
-    if (!st) st = sh_to_host(dd.p, 8 * R, &hd);
-    if (!st) st = sh_to_host(dv.p, 4 * R, &hv);
-    if (!st) st = sh_to_host(dqf.p, 4 * R, &hf);
-    if (!st) st = sh_to_host(dql.p, 4 * R, &hl);
-    if (st) { free(ho); free(hr); free(hs); free(hd); free(hv); free(hf); free(hl); return st; }
-    *vote_offsets_out = (uint64_t*)ho; *rid_out = (uint64_t*)hr; *strand_out = (uint8_t*)hs; *diag_out = (int64_t*)hd; *votes_out = (uint32_t*)hv;
-    *qfirst_out = (uint32_t*)hf; *qlast_out = (uint32_t*)hl;
+    const HostOut outs[] = {{(void**)vote_offsets_out, dvo.p, 8 * (M + 1)}, {(void**)rid_out, dr.p, 8 * R},    {(void**)strand_out, dst.p, R},
+                            {(void**)diag_out, dd.p, 8 * R},                {(void**)votes_out, dv.p, 4 * R},  {(void**)qfirst_out, dqf.p, 4 * R},
+                            {(void**)qlast_out, dql.p, 4 * R}};
+    AIXCHK(copy_out_host(outs, 7));
     return AIX_OK;
 }

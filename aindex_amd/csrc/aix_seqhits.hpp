@@ -1,11 +1,11 @@
 // aix_seqhits.hpp — what more than one translation unit uses of the chain sequences -> windows -> seed hits (aix_seqhits.hip: hits and
 // diagonal votes; aix_seqfind.hip: Hamming-verified alignments and strand counts; aix_seqedit.hip: edit-distance alignments): the hit
-// buffers, steps 1 to 4 with a window stride, the gather of a permutation, the device helpers of the verification kernels and the host
-// ends of the C ABI. (Scans, the stable sort passes and the error mapping are those of aix_hostkit.hpp.)
+// buffers, steps 1 to 4 with a window stride, the gather of a permutation, the device helpers of the verification kernels, and of the host
+// ends of the C ABI the two steps that are the sequence files' own: sh_check (what must be attached) and sh_upload (ragged sequences into
+// HBM). Everything else of a host form — error mapping, scans, the stable sort passes, zero_offsets, the HostOut epilogue — is that of
+// aix_hostkit.hpp.
 #pragma once
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 #include "aix_posquery.hpp"
 
@@ -56,9 +56,7 @@ __global__ void __launch_bounds__(kSB) k_sv_gather(const T* __restrict__ in, con
 }
 struct SvSame { template <class T> __host__ __device__ T operator()(T v) const { return v; } };
 
-static unsigned sv_bits(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) ++b; return b; }
-
-// A stable pass of a permutation is sort_pairs (aix_hostkit.hpp): keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary
+// A stable pass of a permutation is sort_pairs over sort_bits(largest key) (aix_hostkit.hpp): keys (any iterator) in the order of perm_in -> perm_out. rocPRIM's temporary
 // storage is as large as the keys and values together: the passes of a chain share ONE block (tmp.alloc waits for the pass before it, then
 // takes the block back from the pool)
 
@@ -101,25 +99,12 @@ static int sh_check(const aix_index* h) {
     return AIX_OK;
 }
 
-// device buffer -> malloc'd host copy (aix_free)
-static int sh_to_host(const void* d, uint64_t bytes, void** out) {
-    void* p = malloc(bytes ? bytes : 1);
-    if (!p) return AIX_ERR_NOMEM;
-    if (bytes) {
-        const hipError_t e = hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(p); AIXCHK(e); }
-    }
-    *out = p;
-    return AIX_OK;
-}
-
-// the sequences of a host call in HBM: bytes (padded for load23) and offsets
-static int sh_upload(const char* seqs, const uint64_t* offs, uint64_t M, DevBuf& ds, DevBuf& dof) {
+// the sequences of a host call in HBM: bytes (upload_padded, aix_posquery.hpp) and offsets
+static int sh_upload(const char* seqs, const uint64_t* offs, uint64_t M, DevArr& ds, DevArr& dof) {
     const uint64_t bytes = M ? offs[M] : 0;
     if (bytes >= (1ull << 60)) return AIX_ERR_NOMEM;
-    AIXCHK(ds.alloc(bytes + 16));
-    AIXCHK(dof.alloc(8 * (M + 1)));
-    if (bytes) AIXCHK(hipMemcpy(ds.p, seqs, bytes, hipMemcpyHostToDevice));
-    AIXCHK(hipMemcpy(dof.p, offs, 8 * (M + 1), hipMemcpyHostToDevice));
+    const HostIn in{offs, 8 * (M + 1)};
+    AIXCHK(upload_padded(ds, seqs, bytes));
+    AIXCHK(copy_in_host(&dof, &in, 1));
     return AIX_OK;
 }

@@ -486,7 +486,7 @@ extern "C" int aix_seq_thread(aix_index_t* h, uint32_t cutoff, const char* seqs,
     ku.drop(); kp.drop(); kf.drop();
     AIXCHK(sup.alloc(8 * E));
     AIXCHK(hipMemset(sup.p, 0, 8 * E));
-    DevBuf ds, dof;
+    DevArr ds, dof;
     if (const int su_st = sh_upload(seqs, offs, M, ds, dof)) return su_st;
     AIXCHK(sso.alloc(8 * (M + 1)));
     AIXCHK(hipMemset(sso.p, 0, 8 * (M + 1)));

@@ -359,11 +359,15 @@ class Index:
         return True
 
     @staticmethod
-    def _take(p, n: int) -> np.ndarray:
+    def _take(p, n: int, dtype=np.uint64) -> np.ndarray:
+        """n entries of a malloc'd output block of the C ABI as a numpy array of its own; the block is freed."""
+        dt = np.dtype(dtype)
         try:
-            return np.frombuffer(C.string_at(p, 8 * n), dtype=np.uint64).copy() if n else np.zeros(0, np.uint64)
+            return np.frombuffer(C.string_at(p, dt.itemsize * n), dtype=dt).copy() if n else np.zeros(0, dt)
         finally:
             lib().aix_free(p)
+
+    _take_as = _take                                          # the name with the dtype spelt out, as tests/test_gpu_seqedit.py calls it
 
     def positions_batch(self, kmers, max_per_kmer: int = 0, locate: bool = False):
         """(offsets[N + 1], positions[offsets[N]][, rid, offset_in_read]) as numpy uint64: list i = positions[offsets[i]:offsets[i + 1]] =
@@ -433,13 +437,6 @@ class Index:
         return int(out[0]), int(out[1])
 
     @staticmethod
-    def _take_u8(p, n: int) -> np.ndarray:
-        try:
-            return np.frombuffer(C.string_at(p, n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
-        finally:
-            lib().aix_free(p)
-
-    @staticmethod
     def _rc_arg(revcomp, n: int) -> Optional[np.ndarray]:
         if revcomp is None or revcomp is False:
             return None
@@ -462,7 +459,7 @@ class Index:
         check(lib().aix_reads_fetch(self._h, _np_ptr(s) if n else None, _np_ptr(e) if n else None, _np_ptr(r) if n else None, n, C.byref(po), C.byref(pb)),
               "aix_reads_fetch")
         offsets = self._take(po, n + 1)
-        return offsets, self._take_u8(pb, int(offsets[n]))
+        return offsets, self._take(pb, int(offsets[n]), np.uint8)
 
     def fetch_reads_by_rid(self, rids):
         """(offsets, bytes): item i = get_read_by_rid(rids[i]) over the intervals of attach_ridx."""
@@ -471,7 +468,7 @@ class Index:
         po, pb = vp(), vp()
         check(lib().aix_reads_fetch_rid(self._h, _np_ptr(r) if n else None, n, C.byref(po), C.byref(pb)), "aix_reads_fetch_rid")
         offsets = self._take(po, n + 1)
-        return offsets, self._take_u8(pb, int(offsets[n]))
+        return offsets, self._take(pb, int(offsets[n]), np.uint8)
 
     def reads_by_kmers(self, kmers, max_reads: int = 100):
         """(kmer_offsets uint64[N + 1], rid uint64[R], read_offsets uint64[R + 1], bytes uint8): the reads of k-mer i are
@@ -484,7 +481,7 @@ class Index:
         nr = int(koff[n])
         rid = self._take(pr, nr)
         roff = self._take(po, nr + 1)
-        return koff, rid, roff, self._take_u8(pb, int(roff[nr]))
+        return koff, rid, roff, self._take(pb, int(roff[nr]), np.uint8)
 
     def _fetch_t(self, what: str, n: int, dev, call):
         """The sizing call, then the filling call into a tensor of exactly that size (int64 offsets, uint8 bytes)."""
@@ -545,41 +542,28 @@ class Index:
         return koff, rid, roff, by
 
     # ---- sequences against the indexed reads (aix_seqhits.hip) ---------------------------------
-    @staticmethod
-    def _take_as(p, n: int, dtype) -> np.ndarray:
-        dt = np.dtype(dtype)
-        try:
-            return np.frombuffer(C.string_at(p, dt.itemsize * n), dtype=dt).copy() if n else np.zeros(0, dt)
-        finally:
-            lib().aix_free(p)
+    def _seq_host(self, what: str, seqs: Sequence, dtypes, *args):
+        """offsets + one array per dtype through a host form: ragged sequences in, one malloc'd block per output back; the first is the
+        offsets[M + 1], every other one holds offsets[M] entries."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(1 + len(dtypes))]
+        check(getattr(lib(), what)(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, *args, *[C.byref(p) for p in ps]), what)
+        offsets = self._take(ps[0], m + 1)
+        return (offsets, *[self._take(p, int(offsets[m]), dt) for p, dt in zip(ps[1:], dtypes)])
 
     def seq_hits(self, seqs: Sequence, max_per_kmer: int = 0):
         """Seed hits of every 23-window of every sequence against the attached positions index, intervals and reads:
         (seq_offsets u64[M + 1], qoff u32, pos u64, rid u64, local i64, flag u8). The hits of sequence i are
         [seq_offsets[i], seq_offsets[i + 1]), by window, then slot; flag = strand (0 as stored, 1 reverse complement, 2 neither) | 4 when
         an interval was found."""
-        data, offs = _ragged(seqs)
-        m = len(seqs)
-        ps = [vp() for _ in range(6)]
-        check(lib().aix_seq_hits(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, max_per_kmer, *[C.byref(p) for p in ps]), "aix_seq_hits")
-        so = self._take_as(ps[0], m + 1, np.uint64)
-        t = int(so[m])
-        return (so, self._take_as(ps[1], t, np.uint32), self._take_as(ps[2], t, np.uint64), self._take_as(ps[3], t, np.uint64),
-                self._take_as(ps[4], t, np.int64), self._take_as(ps[5], t, np.uint8))
+        return self._seq_host("aix_seq_hits", seqs, [np.uint32, np.uint64, np.uint64, np.int64, np.uint8], max_per_kmer)
 
     def seq_votes(self, seqs: Sequence, min_votes: int = 1, max_per_kmer: int = 0):
         """Votes per (read, strand, diagonal) of every sequence: (vote_offsets u64[M + 1], rid u64, strand u8, diag i64, votes u32,
         q_first u32, q_last u32); the records of sequence i ascend by (rid, strand, diag). diag = local - qoff (strand 0), local + qoff
         (strand 1); only groups of at least min_votes hits are reported."""
-        data, offs = _ragged(seqs)
-        m = len(seqs)
-        ps = [vp() for _ in range(7)]
-        check(lib().aix_seq_votes(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, max_per_kmer, min_votes, *[C.byref(p) for p in ps]),
-              "aix_seq_votes")
-        vo = self._take_as(ps[0], m + 1, np.uint64)
-        r = int(vo[m])
-        return (vo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint8), self._take_as(ps[3], r, np.int64),
-                self._take_as(ps[4], r, np.uint32), self._take_as(ps[5], r, np.uint32), self._take_as(ps[6], r, np.uint32))
+        return self._seq_host("aix_seq_votes", seqs, [np.uint64, np.uint8, np.int64, np.uint32, np.uint32, np.uint32], max_per_kmer, min_votes)
 
     def _seq_t(self, what: str, seqs_t, offs_t, dtypes, cap_hint: int, call):
         """offsets + one tensor per dtype through a `_dev` twin: filled in one call when cap_hint entries suffice, else sized, then filled."""
@@ -623,15 +607,7 @@ class Index:
         local u64, strand u8, dist u32). The records of sequence i are [find_offsets[i], find_offsets[i + 1]), ascending by (pos, strand);
         pos is where the alignment starts in the reads file, local = pos - start of the read that contains it whole. Complete when
         hd < len // 23 and seed_step is 1 or 23 (include/aindex_hip.h)."""
-        data, offs = _ragged(seqs)
-        m = len(seqs)
-        ps = [vp() for _ in range(6)]
-        check(lib().aix_seq_find(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, hd, seed_step, max_per_kmer, *[C.byref(p) for p in ps]),
-              "aix_seq_find")
-        fo = self._take_as(ps[0], m + 1, np.uint64)
-        r = int(fo[m])
-        return (fo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint64), self._take_as(ps[3], r, np.uint64),
-                self._take_as(ps[4], r, np.uint8), self._take_as(ps[5], r, np.uint32))
+        return self._seq_host("aix_seq_find", seqs, [np.uint64, np.uint64, np.uint64, np.uint8, np.uint32], hd, seed_step, max_per_kmer)
 
     def seq_find_t(self, seqs_t, offs_t, hd: int = 0, seed_step: int = 23, max_per_kmer: int = 0, cap_hint: int = 0):
         """seq_find on device tensors (uint8 bytes, int64 offsets[M + 1] into them), on torch's current stream:
@@ -649,15 +625,7 @@ class Index:
         hit: (find_offsets u64[M + 1], start u64, end u64, rid u64, local u64, strand u8, dist u32). The records of sequence i are
         [find_offsets[i], find_offsets[i + 1]), ascending by (start, strand); the alignment is reads[start:end], local = start - start of
         the read that holds the seed. Complete when ed < len // 23 and seed_step is 1 or 23 (include/aindex_hip.h)."""
-        data, offs = _ragged(seqs)
-        m = len(seqs)
-        ps = [vp() for _ in range(7)]
-        check(lib().aix_seq_edit(self._h, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, ed, seed_step, max_per_kmer, *[C.byref(p) for p in ps]),
-              "aix_seq_edit")
-        fo = self._take_as(ps[0], m + 1, np.uint64)
-        r = int(fo[m])
-        return (fo, self._take_as(ps[1], r, np.uint64), self._take_as(ps[2], r, np.uint64), self._take_as(ps[3], r, np.uint64),
-                self._take_as(ps[4], r, np.uint64), self._take_as(ps[5], r, np.uint8), self._take_as(ps[6], r, np.uint32))
+        return self._seq_host("aix_seq_edit", seqs, [np.uint64, np.uint64, np.uint64, np.uint64, np.uint8, np.uint32], ed, seed_step, max_per_kmer)
 
     def seq_edit_t(self, seqs_t, offs_t, ed: int = 1, seed_step: int = 23, max_per_kmer: int = 0, cap_hint: int = 0):
         """seq_edit on device tensors (uint8 bytes, int64 offsets[M + 1] into them), on torch's current stream:
@@ -835,14 +803,14 @@ class Index:
             refs[6] = None
         check(lib().aix_unitigs(self._h, cutoff, C.byref(u), *refs), "aix_unitigs")
         U = u.value
-        off = self._take_as(ps[0], U + 1, np.uint64)
+        off = self._take(ps[0], U + 1, np.uint64)
         total = int(off[U])
         live = total - 22 * U
         sizes = (None, total, U, U, U, U, live, self.n, self.n, self.n)
         types = (None, np.uint8, np.uint8, np.uint64, np.uint32, np.uint32, np.uint32, np.uint64, np.uint32, np.uint8)
         out = {"offsets": off}
         for i in range(1, 10):
-            out[self.UNITIG_KEYS[i]] = self._take_as(ps[i], sizes[i], types[i]) if refs[i] is not None else None
+            out[self.UNITIG_KEYS[i]] = self._take(ps[i], sizes[i], types[i]) if refs[i] is not None else None
         out.update(U=U, n_live=live, n_circular=int(out["circular"].sum()))
         return out
 
@@ -875,8 +843,8 @@ class Index:
         ps = [vp() for _ in range(3)]
         u, e = C.c_uint64(), C.c_uint64()
         check(lib().aix_unitig_links(self._h, cutoff, C.byref(u), C.byref(e), *[C.byref(q) for q in ps]), "aix_unitig_links")
-        return {"link_off": self._take_as(ps[0], 2 * u.value + 1, np.uint64), "link_to": self._take_as(ps[1], e.value, np.uint32),
-                "bubble_mate": self._take_as(ps[2], u.value, np.uint32), "U": u.value, "E": e.value}
+        return {"link_off": self._take(ps[0], 2 * u.value + 1, np.uint64), "link_to": self._take(ps[1], e.value, np.uint32),
+                "bubble_mate": self._take(ps[2], u.value, np.uint32), "U": u.value, "E": e.value}
 
     # ---- graph cleaning (aix_graphclean.hip) ------------------------------------------------------
     GRAPH_KEYS = ("offsets", "bases", "circular", "tf_sum", "tf_min", "tf_max", "link_off", "link_to")
@@ -975,13 +943,13 @@ class Index:
             check(lib().aix_graph_clean(u, *[x.ctypes.data_as(vp) for x in a], e, tip_max_kmers, bubble_max_kmers, *[C.byref(x) for x in n],
                                         *[C.byref(x) for x in ps]), "aix_graph_clean")
         c, e2 = n[0].value, n[1].value
-        off = self._take_as(ps[0], c + 1, np.uint64)
+        off = self._take(ps[0], c + 1, np.uint64)
         sizes = (None, int(off[c]), c, c, c, c, 2 * c + 1, e2, u, u, u, u)
         names = self.GRAPH_KEYS + ("remove", "unitig_contig", "unitig_pos", "unitig_flag")
         types = self.GRAPH_DTYPES + (np.uint8, np.uint32, np.uint64, np.uint8)
         out = {"offsets": off}
         for i in range(1, 12):
-            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+            out[names[i]] = self._take(ps[i], sizes[i], types[i])
         out.update(U=c, E=e2, n_tips=n[2].value, n_arms=n[3].value)
         return out
 
@@ -1097,11 +1065,11 @@ class Index:
         u, e = C.c_uint64(), C.c_uint64()
         check(lib().aix_seq_thread(self._h, cutoff, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, *[C.byref(p) for p in ps], C.byref(u), C.byref(e)),
               "aix_seq_thread")
-        out = {"seq_step_off": self._take_as(ps[0], m + 1, np.uint64)}
+        out = {"seq_step_off": self._take(ps[0], m + 1, np.uint64)}
         t = int(out["seq_step_off"][m])
         for i in range(1, 7):
-            out[self.THREAD_KEYS[i]] = self._take_as(ps[i], t, self.THREAD_DTYPES[i])
-        out.update(link_support=self._take_as(ps[7], e.value, np.uint64), U=u.value, E=e.value)
+            out[self.THREAD_KEYS[i]] = self._take(ps[i], t, self.THREAD_DTYPES[i])
+        out.update(link_support=self._take(ps[7], e.value, np.uint64), U=u.value, E=e.value)
         return out
 
     # ---- repeat resolution (aix_graphresolve.hip) -------------------------------------------------
@@ -1210,13 +1178,13 @@ class Index:
             check(lib().aix_graph_resolve(u, *[x.ctypes.data_as(vp) for x in a], e, _np_ptr(sup), _np_ptr(pair), min_link_support, min_pair_support, max_pair_noise,
                                           *[C.byref(x) for x in n], *[C.byref(x) for x in ps]), "aix_graph_resolve")
         u2, e2 = n[0].value, n[1].value
-        off = self._take_as(ps[0], u2 + 1, np.uint64)
+        off = self._take(ps[0], u2 + 1, np.uint64)
         sizes = (None, int(off[u2]), u2, u2, u2, u2, 2 * u2 + 1, e2, e, u, u2)
         names = self.GRAPH_KEYS + ("link_remove", "copies", "unitig_origin")
         types = self.GRAPH_DTYPES + (np.uint8, np.uint8, np.uint32)
         out = {"offsets": off}
         for i in range(1, 11):
-            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+            out[names[i]] = self._take(ps[i], sizes[i], types[i])
         out.update(U=u2, E=e2, n_links_removed=n[2].value, n_split=n[3].value)
         return out
 
@@ -1354,14 +1322,14 @@ class Index:
                                      _np_ptr(a[4]) if nobs else None, insert_size, min_pairs, dominance, min_contig_bases, min_gap, *[C.byref(x) for x in n],
                                      *[C.byref(x) for x in ps]), "aix_scaffold")
         sc = n[0].value
-        so = self._take_as(ps[0], sc + 1, np.uint64)
+        so = self._take(ps[0], sc + 1, np.uint64)
         names = ("scaffold_offsets", "scaffold_bases", "member_off", "member", "member_gap", "join", "join_count", "join_gap", "contig_scaffold", "contig_rank",
                  "contig_pos", "contig_flag")
         sizes = (None, int(so[sc]), sc + 1, u, u, 2 * u, 2 * u, 2 * u, u, u, u, u)
         types = (np.uint64, np.uint8, np.uint64, np.uint32, np.int64, np.uint32, np.uint64, np.int64, np.uint32, np.uint32, np.uint64, np.uint8)
         out = {"scaffold_offsets": so}
         for i in range(1, 12):
-            out[names[i]] = self._take_as(ps[i], sizes[i], types[i])
+            out[names[i]] = self._take(ps[i], sizes[i], types[i])
         out.update(n_scaffolds=sc, n_joins=n[1].value, n_cut=n[2].value, S=n[3].value, total_bases=int(so[sc]))
         return out
 
@@ -1458,7 +1426,7 @@ class Index:
                  "close_states", "path_off", "path", "fill_uses", "counts")
         sizes = (sc + 1, total, sc + 1, mf, mf, mf, mf, 2 * u, 2 * u, 2 * u, 2 * u + 1, pt, u, 5)
         types = (np.uint64, np.uint8, np.uint64, np.uint32, np.uint8, np.int64, np.uint64, np.uint8, np.int64, np.uint32, np.uint64, np.uint32, np.uint32, np.uint64)
-        out = {k: self._take_as(q, s, t) for k, q, s, t in zip(names, ps, sizes, types)}
+        out = {k: self._take(q, s, t) for k, q, s, t in zip(names, ps, sizes, types)}
         out.update(n_fmembers=mf, total_bases=total, total=pt, counts=[int(x) for x in out["counts"]])
         return out
 
@@ -1589,8 +1557,8 @@ class Index:
         m, total = C.c_uint64(), C.c_uint64()
         check(lib().aix_top_kmers(self._h, min_tf, n, C.byref(pk), C.byref(pt), C.byref(ps) if want_kmers else None, C.byref(m), C.byref(total)),
               "aix_top_kmers")
-        kid, tf = self._take_as(pk, m.value, np.uint32), self._take_as(pt, m.value, np.uint32)
-        kmers = self._take_as(ps, m.value * self.k, np.uint8).reshape(m.value, self.k) if want_kmers else None
+        kid, tf = self._take(pk, m.value, np.uint32), self._take(pt, m.value, np.uint32)
+        kmers = self._take(ps, m.value * self.k, np.uint8).reshape(m.value, self.k) if want_kmers else None
         return kid, tf, kmers, total.value
 
     def kmers_by_kid(self, kids, want_rc: bool = False, want_tf: bool = False):
