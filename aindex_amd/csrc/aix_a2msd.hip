@@ -295,7 +295,6 @@ __global__ void __launch_bounds__(256) k_a2_advance64(const uint64_t* __restrict
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
 static inline unsigned grid256(uint64_t work) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((work + 255) / 256, 1), 8192); }
 
 bool a2_msd_eligible(uint64_t nwin, uint64_t n) {
@@ -318,101 +317,48 @@ hipError_t a2_msd_place(const IndexDev& ix, const uint32_t* keys, uint64_t nwin,
     int D2 = (int)Bh - K1_PBITS - (int)rbits;
     if (D2 > 11) { D2 = 11; rbits = Bh - K1_PBITS - 11; }
     if (D2 < 1) { D2 = 1; rbits = Bh - K1_PBITS - 1; }
-    const uint32_t s2 = 32 + rbits, s1 = s2 + (uint32_t)D2, nb2 = 1u << D2;
-    const uint32_t nbuckets = (uint32_t)K1_P * nb2;
+    const uint32_t s2 = 32 + rbits, s1 = s2 + (uint32_t)D2;
     const uint32_t cap_e = (uint32_t)env_int("AIX_A2_TEST_CAP", 1, A2_CAP - 1, A2_CAP);   // test hook: force the set-aside path
-    const uint64_t ntiles = (nwin + K1_TILE - 1) / K1_TILE;
-    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, K1_MAXGRID);
-    const uint32_t region = (uint32_t)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P);
-    const uint32_t cap = grid * region;
-    size_t sort_tmp = 0, scan_tmp = 0;
-    {
-        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{nullptr});
-        (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (const uint16_t*)nullptr, (uint16_t*)nullptr, vals, (uint64_t*)nullptr, (size_t)cap, 0u, 12u, s);
-        (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
-    }
-    // one block: head | dir_part | dir_cnt | spart | sdesc | sort / scan temp | bucket_cnt | bucket_base | over_b | over_off | rem (8 B per window) | parts
-    const uint64_t o_dirp = 256, o_dirc = o_dirp + up256(2ull * cap), o_spart = o_dirc + up256(2ull * cap), o_sdesc = o_spart + up256(2ull * cap),
-                   o_stmp = o_sdesc + up256(8ull * cap), o_bcnt = o_stmp + up256(std::max(sort_tmp, scan_tmp)), o_bbase = o_bcnt + up256(4ull * (nbuckets + 1)),
-                   o_ob = o_bbase + up256(4ull * (nbuckets + 1)), o_oo = o_ob + up256(4ull * nbuckets), o_rem = o_oo + up256(8ull * nbuckets),
-                   o_parts = o_rem + up256(8ull * nwin), total = o_parts + 8ull * cap * K1_CH;
-    uint8_t* w = nullptr;
-    hipError_t e = env_flag("AIX_A2_TEST_NOMEM") ? hipErrorOutOfMemory : pool_alloc((void**)&w, total);      // test hook: the workspace "does not fit"
-    if (e != hipSuccess) { if (untouched) *untouched = true; return e; }     // the workspace did not fit: the caller may take the sort path, nothing was written
+    const MsdPlan P(nwin, 1u << D2, 0, s);
+    const uint32_t nbuckets = P.nbuckets;
+    // behind the head (an A2Over): over_b | over_off | rem (8 B per window) | parts
+    const uint64_t o_ob = P.head_bytes, o_oo = o_ob + up256(4ull * nbuckets), o_rem = o_oo + up256(8ull * nbuckets), o_parts = o_rem + up256(8ull * nwin);
+    DevArr work(s);
+    const hipError_t ea = env_flag("AIX_A2_TEST_NOMEM") ? hipErrorOutOfMemory : work.alloc(o_parts + P.parts_bytes());      // test hook: the workspace "does not fit"
+    if (ea != hipSuccess) { if (untouched) *untouched = true; return ea; }     // the caller may take the sort path, nothing was written
+    uint8_t* w = (uint8_t*)work.p;
     A2Over* over = (A2Over*)w;
-    uint16_t* dir_part = (uint16_t*)(w + o_dirp);
-    uint16_t* dir_cnt = (uint16_t*)(w + o_dirc);
-    uint16_t* spart = (uint16_t*)(w + o_spart);
-    uint64_t* sdesc = (uint64_t*)(w + o_sdesc);
-    void* tmp = w + o_stmp;
-    uint32_t* bucket_cnt = (uint32_t*)(w + o_bcnt);
-    uint32_t* bucket_base = (uint32_t*)(w + o_bbase);
+    uint32_t* bucket_base = P.bucket_base(w);
     uint32_t* over_b = (uint32_t*)(w + o_ob);
     uint64_t* over_off = (uint64_t*)(w + o_oo);
     uint64_t* rem = (uint64_t*)(w + o_rem);
     uint64_t* parts = (uint64_t*)(w + o_parts);
+    AIX_TRY(msd_partition(P, w, A2Keys{keys, nwin, (uint32_t)std::min<uint64_t>(n, 0xFFFFFFFFull)}, s1, s2, parts, rem, s));
+    int per_cu = 4, cus = 256;                                  // persistent grid: exactly what is resident at once
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_a2_final, A2_FB, 0);
+    { int dev = 0; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
+    const uint32_t fgrid = std::min<uint32_t>(nbuckets, (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(cus, 1));
+    AIX_TRY_LAUNCH(k_a2_final, dim3(fgrid), dim3(A2_FB), 0, s, ix, (const uint64_t*)rem, (const uint32_t*)bucket_base, nbuckets, rbits, cap_e, piece_first, filled,
+                   advance ? 1 : 0, d_indices, d_positions, over, over_b, over_off);
     A2Over head{0, 0, 0};
-    uint64_t *gathered = nullptr, *sorted = nullptr;
-    uint32_t* first = nullptr;
-    void* tmp2 = nullptr;
-    do {
-        e = hipFuncSetAttribute((const void*)k_k1_split<A2Keys>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_k1_scatter<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS);
-        if (e == hipSuccess) e = hipMemsetAsync(w, 0, 256, s);
-        if (e == hipSuccess) e = hipMemsetD16Async((hipDeviceptr_t)dir_part, (unsigned short)K1_P, cap, s);      // "no partition": sorts behind every real one
-        if (e == hipSuccess) e = hipMemsetD16Async((hipDeviceptr_t)dir_cnt, (unsigned short)K1_CH, cap, s);      // chunks are full unless the split says otherwise
-        if (e == hipSuccess) e = hipMemsetAsync(bucket_cnt, 0, 4ull * (nbuckets + 1), s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_k1_split<A2Keys>, dim3(grid), dim3(K1_TB), K1_TILE_LDS, s, A2Keys{keys, nwin, (uint32_t)std::min<uint64_t>(n, 0xFFFFFFFFull)}, s1, ntiles,
-                           region, dir_part, dir_cnt, parts, &over->err);
-        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{dir_cnt});
-        size_t tb = sort_tmp;
-        e = rocprim::radix_sort_pairs(tmp, tb, (const uint16_t*)dir_part, spart, vals, sdesc, (size_t)cap, 0u, 12u, s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_k1_count, dim3(K1_P), dim3(K1_TB), 0, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, cap, s2, nb2, bucket_cnt);
-        tb = scan_tmp;
-        e = rocprim::exclusive_scan(tmp, tb, bucket_cnt, bucket_base, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_k1_scatter<uint64_t>, dim3(K1_P), dim3(K1_TB), K1_TILE_LDS, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, cap, s2,
-                           nb2, (const uint32_t*)bucket_base, rem);
-        int per_cu = 4, cus = 256;                                // persistent grid: exactly what is resident at once
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_a2_final, A2_FB, 0);
-        { int dev = 0; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
-        const uint32_t fgrid = std::min<uint32_t>(nbuckets, (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(cus, 1));
-        hipLaunchKernelGGL(k_a2_final, dim3(fgrid), dim3(A2_FB), 0, s, ix, (const uint64_t*)rem, (const uint32_t*)bucket_base, nbuckets,
-                           rbits, cap_e, piece_first, filled, advance ? 1 : 0, d_indices, d_positions, over, over_b, over_off);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&head, over, sizeof(head), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) break;
-        if (head.err) { e = hipErrorAssert; break; }            // chunk region exhausted: never silent
-        if (head.n == 0) break;
-        // the buckets that did not fit: radix sort of their pairs (slot in the high word, offset in the low word), then run placement
-        const uint64_t m = head.elems;
-        e = pool_alloc((void**)&gathered, 8 * m);
-        if (e == hipSuccess) e = pool_alloc((void**)&sorted, 8 * m);
-        if (e == hipSuccess) e = pool_alloc((void**)&first, 4 * n);
-        size_t tb2 = 0;
-        if (e == hipSuccess) e = rocprim::radix_sort_keys(nullptr, tb2, gathered, sorted, (size_t)m, 0u, 32u + Bh, s);
-        if (e == hipSuccess) e = pool_alloc(&tmp2, tb2 ? tb2 : 1);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_a2_over_gather, dim3(std::min<uint32_t>(head.n, 4096u)), dim3(256), 0, s, (const uint64_t*)rem, (const uint32_t*)bucket_base,
-                           (const uint32_t*)over_b, (const uint64_t*)over_off, head.n, s2, gathered);
-        e = rocprim::radix_sort_keys(tmp2, tb2, gathered, sorted, (size_t)m, 0u, 32u + Bh, s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_a2_first64, dim3(grid256(m)), dim3(256), 0, s, (const uint64_t*)sorted, m, first);
-        hipLaunchKernelGGL(k_a2_place64, dim3(grid256(m)), dim3(256), 0, s, ix, (const uint64_t*)sorted, m, piece_first, (const uint32_t*)first, (const uint32_t*)filled,
-                           d_indices, d_positions);
-        if (advance) hipLaunchKernelGGL(k_a2_advance64, dim3(grid256(m)), dim3(256), 0, s, (const uint64_t*)sorted, m, (const uint32_t*)first, filled);
-        e = hipGetLastError();
-    } while (false);
-    { const hipError_t es = hipStreamSynchronize(s); if (e == hipSuccess) e = es; }
-    if (tmp2) pool_free(tmp2);
-    if (first) pool_free(first);
-    if (sorted) pool_free(sorted);
-    if (gathered) pool_free(gathered);
-    pool_free(w);
-    return e;
+    AIX_TRY(hipMemcpyAsync(&head, over, sizeof(head), hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    if (head.err) return hipErrorAssert;                        // chunk region exhausted: never silent
+    if (head.n == 0) return hipSuccess;
+    // the buckets that did not fit: radix sort of their pairs (slot in the high word, offset in the low word), then run placement
+    const uint64_t m = head.elems;
+    DevArr gathered(s), sorted(s), first(s), tmp(s);
+    AIX_TRY(gathered.alloc(8 * m));
+    AIX_TRY(sorted.alloc(8 * m));
+    AIX_TRY(first.alloc(4 * n));
+    AIX_TRY_LAUNCH(k_a2_over_gather, dim3(std::min<uint32_t>(head.n, 4096u)), dim3(256), 0, s, (const uint64_t*)rem, (const uint32_t*)bucket_base, (const uint32_t*)over_b,
+                   (const uint64_t*)over_off, head.n, s2, (uint64_t*)gathered.p);
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, (uint64_t*)gathered.p, (uint64_t*)sorted.p, (size_t)m, 0u, 32u + Bh, s); }));
+    AIX_TRY_LAUNCH(k_a2_first64, dim3(grid256(m)), dim3(256), 0, s, (const uint64_t*)sorted.p, m, (uint32_t*)first.p);
+    AIX_TRY_LAUNCH(k_a2_place64, dim3(grid256(m)), dim3(256), 0, s, ix, (const uint64_t*)sorted.p, m, piece_first, (const uint32_t*)first.p, (const uint32_t*)filled, d_indices,
+                   d_positions);
+    if (advance) AIX_TRY_LAUNCH(k_a2_advance64, dim3(grid256(m)), dim3(256), 0, s, (const uint64_t*)sorted.p, m, (const uint32_t*)first.p, filled);
+    return hipStreamSynchronize(s);
 }
 
 }  // namespace aix

@@ -145,15 +145,13 @@ static int count23_atomics(aix_index* h, const char* d_plain, uint64_t len, int 
 // counted under the same canonical form, skipped for the same bytes, and two distinct k-mers never share a slot.
 // AIX_ERR_NOMEM: K1's scratch does not fit, nothing was counted and the caller goes on with (2).
 static int count23_via_k1(aix_index* h, const char* d_plain, uint64_t len, int canon_mode, uint32_t* d_tf_out, hipStream_t s) {
-    uint64_t *dk = nullptr, *dc = nullptr, dn = 0;
-    const hipError_t e = distinct_from_plain((const uint8_t*)d_plain, len, 23, canon_mode, 1, env_distinct_piece(), &dk, &dc, &dn, s);
+    DistinctRun d;
+    const hipError_t e = distinct_from_plain((const uint8_t*)d_plain, len, 23, canon_mode, 1, env_distinct_piece(), d, s);
     if (e != hipSuccess) (void)hipGetLastError();
     if (e == hipErrorOutOfMemory) return AIX_ERR_NOMEM;
     if (e != hipSuccess) { set_last_error(std::string("count23 through K1: ") + hipGetErrorString(e)); return AIX_ERR_HIP; }
-    const hipError_t e2 = launch_add_counts23(h->dev_slots(), dk, dc, dn, d_tf_out, s);
+    const hipError_t e2 = launch_add_counts23(h->dev_slots(), d.k, d.c, d.n, d_tf_out, s);
     const hipError_t e3 = hipStreamSynchronize(s);                             // the K1 result goes back to the block cache idle
-    if (dk) pool_free(dk);
-    if (dc) pool_free(dc);
     HIPCHK(e2);
     HIPCHK(e3);
     record_count23(h, 3, 0);

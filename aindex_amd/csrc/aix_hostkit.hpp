@@ -1,9 +1,11 @@
 // aix_hostkit.hpp — private to the library: the host scaffolding that the subsystem files (one translation unit per subsystem behind the
 // C ABI) share. Error mapping, rocPRIM's two-call protocol, the prologue and the epilogue of the host forms (copy_in_host, copy_out_host).
 // The query files (aix_posquery, aix_readsquery, aix_seqhits, aix_seqfind, aix_seqedit), the graph files and aix_seqthread use all of it:
-// their chains are AIX_TRY / AIX_TRY_LAUNCH, their host forms hold DevArr and publish through one HostOut table. Nothing here is on a hot
-// path, and nothing that only one file uses belongs here. The builder and counter files (aix_merge, aix_a2msd, aix_k1, aix_normalize,
-// aix_count13, aix_positions) keep raw pool blocks and their own error style and do not use it.
+// their chains are AIX_TRY / AIX_TRY_LAUNCH, their host forms hold DevArr and publish through one HostOut table. The distinct-k-mer chain
+// and the positions fill (aix_k1, aix_merge, aix_positions, aix_a2msd, and aix_msd.hpp between them) use the chain half: AIX_TRY /
+// AIX_TRY_LAUNCH over DevArr, with_temp, flat_grid; their extern "C" halves keep HIPCHK and DevBuf. Nothing here is on a hot path, and
+// nothing that only one file uses belongs here. aix_normalize, aix_count13, aix_count, aix_ingest, aix_index and aix_lookup* keep raw
+// pool blocks and their own error style and do not use it.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -750,9 +750,8 @@ __global__ void k_move_tail(uint8_t* __restrict__ buf, uint64_t fill, uint32_t k
     if (i < keep) buf[i] = c;
 }
 
-static int distinct_source(const ByteSource& src, int format, int k, int canon_mode, uint64_t min_count, int device, hipStream_t s, uint64_t** dk, uint64_t** dc,
-                           uint64_t* n_out, aix_ingest_stats_t* stats) {
-    *dk = nullptr; *dc = nullptr; *n_out = 0;
+static int distinct_source(const ByteSource& src, int format, int k, int canon_mode, uint64_t min_count, int device, hipStream_t s, DistinctRun& out,
+                           aix_ingest_stats_t* stats) {
     const uint64_t piece_win = env_distinct_piece();         // as distinct_from_plain (aix_merge.hip); test hook: merges at small sizes
     PlainStream ps(src, format, 1, k, device, s);
     int st = ps.start();
@@ -789,7 +788,7 @@ static int distinct_source(const ByteSource& src, int format, int k, int canon_m
     }
     if (r < 0) return r;
     if (fill >= (uint64_t)k) { st = flush(); if (st) return st; }
-    const hipError_t e = acc.finish(min_count ? min_count : 1, dk, dc, n_out);
+    const hipError_t e = acc.finish(min_count ? min_count : 1, out);
     if (e != hipSuccess) { set_last_error(std::string("count_distinct: ") + hipGetErrorString(e)); return AIX_ERR_HIP; }
     ps.fill_stats(stats);
     if (stats) { stats->device_bytes += cap + 64; stats->pieces = acc.pieces; }
@@ -804,8 +803,9 @@ static int count_distinct_any(const ByteSource& src, int format, int k, int cano
     DevGuard g(device);
     hipStream_t s = nullptr;
     HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    uint64_t *dk = nullptr, *dc = nullptr, m = 0;
-    int st = distinct_source(src, format, k, canon_mode, min_count, device, s, &dk, &dc, &m, stats);
+    DistinctRun d;
+    int st = distinct_source(src, format, k, canon_mode, min_count, device, s, d, stats);
+    const uint64_t m = d.n;
     uint64_t *hk = nullptr, *hc = nullptr;
     if (!st) {
         const double t1 = now_s();
@@ -813,16 +813,14 @@ static int count_distinct_any(const ByteSource& src, int format, int k, int cano
         hc = (uint64_t*)malloc(8 * (m ? m : 1));
         if (!hk || !hc) st = AIX_ERR_NOMEM;
         if (!st && m) {
-            hipError_t e = hipMemcpyAsync(hk, dk, 8 * m, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(hc, dc, 8 * m, hipMemcpyDeviceToHost, s);
+            hipError_t e = hipMemcpyAsync(hk, d.k, 8 * m, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(hc, d.c, 8 * m, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) { set_last_error(std::string("count_distinct: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
         }
         if (stats) stats->seconds_output += now_s() - t1;
     }
-    (void)hipStreamSynchronize(s);
-    if (dk) pool_free(dk);
-    if (dc) pool_free(dc);
+    (void)hipStreamSynchronize(s);                           // the copies above may still read d on a failure: it is freed idle
     (void)hipStreamDestroy(s);
     if (st) { free(hk); free(hc); return st; }
     *keys_out = hk; *counts_out = hc; *n_out = m;

@@ -137,48 +137,8 @@ hipError_t a2_msd_place(const IndexDev& ix, const uint32_t* keys, uint64_t nwin,
                         uint64_t* d_positions, hipStream_t s, bool* untouched = nullptr /* set when the call failed before writing anything (workspace allocation) */);
 hipError_t positions_bucket_counts(const IndexDev& ix, const uint8_t* d_reads, uint64_t len, uint64_t start, unsigned long long* d_counts, hipStream_t s);
 
-// distinct k-mers = sort + run-length of window codes; outputs hipMalloc'd (caller frees), d_codes is clobbered
-hipError_t distinct_from_codes(uint64_t* d_codes, uint64_t nwin, int k, uint64_t min_count, uint64_t** d_keys_out, uint32_t** d_counts_out, uint64_t* n_out,
-                               hipStream_t s);
-// the same without a full-width sort (aix_k1.hip): MSD partition in two levels + per-bucket LDS hash / sort. d_codes is clobbered.
-// *fell_back: a bucket held too many distinct remainders; nothing was produced and the caller takes the radix-sort path.
-bool k1_msd_eligible(uint64_t nwin, int k);
-// The two big temporaries of a K1 piece (8 B per window of code / remainder staging, ~8 B per window of partition chunks: 16 + 17 GiB for a
-// 2^31-window piece), kept by whoever counts piece after piece: a hipMalloc / hipFree pair of that size costs ~0.2 s, more than the kernels
-// of the piece (measured: 60 M reads in 5 pieces took 2.5 s of wall clock around 0.16 s of kernels before the blocks were kept).
-struct K1Scratch {
-    void* codes = nullptr;
-    size_t codes_bytes = 0;
-    void* work = nullptr;
-    size_t work_bytes = 0;
-    hipStream_t s = nullptr;
-    K1Scratch() = default;
-    K1Scratch(const K1Scratch&) = delete;
-    K1Scratch& operator=(const K1Scratch&) = delete;
-    hipError_t need(void** p, size_t* have, size_t bytes) {
-        if (bytes <= *have) return hipSuccess;
-        if (*p) { (void)hipStreamSynchronize(s); pool_free(*p); *p = nullptr; *have = 0; }
-        const hipError_t e = pool_alloc(p, bytes);              // from the block cache: a process that counts buffer after buffer finds them there again
-        if (e == hipSuccess) *have = bytes;
-        return e;
-    }
-    ~K1Scratch() {
-        if (codes || work) (void)hipStreamSynchronize(s);
-        if (codes) pool_free(codes);
-        if (work) pool_free(work);
-    }
-};
-hipError_t distinct_from_codes_msd(uint64_t* d_codes, uint64_t nwin, int k, uint64_t** d_keys_out, uint32_t** d_counts_out, uint64_t* n_out, bool* fell_back,
-                                   hipStream_t s, const uint8_t* d_plain = nullptr /* encode inside level 1 */, uint64_t plen = 0, int canon_mode = 0,
-                                   uint64_t** d_counts64_out = nullptr /* non-null: the counts come back as u64 here, *d_counts_out stays null */,
-                                   K1Scratch* scratch = nullptr /* non-null: the partition workspace lives there, kept for the next piece */);
-hipError_t distinct_from_plain(const uint8_t* d_plain, uint64_t plen, int k, int canon_mode, uint64_t min_count, uint64_t piece, uint64_t** d_keys_out,
-                               uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s);
-hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64_t n, uint64_t min_count, uint64_t** d_keys_out, uint64_t** d_counts_out,
-                        uint64_t* n_out, hipStream_t s);
-
-// sorted (key, count) runs merged without a sort (aix_merge.hip)
-struct DevArr {                       // RAII holder of a pool block used on stream `st`: the stream is synchronised before the block goes back
+// RAII holder of a pool block used on stream `st`: the stream is synchronised before the block goes back (also by alloc on a live block)
+struct DevArr {
     void* p = nullptr;
     hipStream_t st = nullptr;
     DevArr() = default;
@@ -190,10 +150,74 @@ struct DevArr {                       // RAII holder of a pool block used on str
     hipError_t alloc(size_t bytes) { drop(); return pool_alloc(&p, bytes ? bytes : 1); }
     void* release() { void* q = p; p = nullptr; return q; }
 };
-hipError_t merge_sum_runs(const uint64_t* ak, const uint64_t* ac, uint64_t na, const uint64_t* bk, const uint64_t* bc, uint64_t nb, uint64_t** d_keys_out,
-                          uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s);
+
+// (keys ascending, counts, n) of a distinct-k-mer set in HBM. RunView borrows, DistinctRun owns its two pool blocks.
+struct RunView {
+    const uint64_t* k;
+    const uint64_t* c;
+    uint64_t n;
+};
+// THE CONTRACT: the blocks go back to the pool WITHOUT a synchronise (an aix_distinct_t outlives the stream its producer ran on). So
+// every producer synchronises its stream before it returns (all do: n has to be known), and whoever enqueues work that reads the blocks
+// synchronises before the holder dies or is assigned to.
+struct DistinctRun {
+    uint64_t* k = nullptr;
+    uint64_t* c = nullptr;
+    uint64_t n = 0;
+    DistinctRun() = default;
+    DistinctRun(const DistinctRun&) = delete;
+    DistinctRun& operator=(const DistinctRun&) = delete;
+    DistinctRun(DistinctRun&& o) noexcept : k(o.k), c(o.c), n(o.n) { o.k = o.c = nullptr; o.n = 0; }
+    DistinctRun& operator=(DistinctRun&& o) noexcept {
+        if (this != &o) { reset(); k = o.k; c = o.c; n = o.n; o.k = o.c = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DistinctRun() { reset(); }
+    void reset() {
+        if (k) pool_free(k);
+        if (c) pool_free(c);
+        k = c = nullptr;
+        n = 0;
+    }
+    // takes over two finished blocks (their stream synchronised) of m entries
+    void adopt(DevArr& keys, DevArr& counts, uint64_t m) { reset(); k = (uint64_t*)keys.release(); c = (uint64_t*)counts.release(); n = m; }
+    RunView view() const { return RunView{k, c, n}; }
+};
+
+// K1's two back ends for one piece (aix_k1.hip). Both leave keys ascending in `keys` and one count per key in `counts`, on the blocks'
+// stream, synchronised; *n_out = 0 leaves the blocks empty.
+// Radix sort + run-length of the nwin window codes in d_codes (~0 = no k-mer), which is clobbered; u32 counts.
+hipError_t distinct_from_codes(uint64_t* d_codes, uint64_t nwin, int k, DevArr& keys, DevArr& counts, uint64_t* n_out, hipStream_t s);
+bool k1_msd_eligible(uint64_t nwin, int k);
+// The two big temporaries of a K1 piece (8 B per window of code / remainder staging, ~8 B per window of partition chunks: 16 + 17 GiB for a
+// 2^31-window piece), kept by whoever counts piece after piece: a hipMalloc / hipFree pair of that size costs ~0.2 s, more than the kernels
+// of the piece (measured: 60 M reads in 5 pieces took 2.5 s of wall clock around 0.16 s of kernels before the blocks were kept).
+struct K1Scratch {
+    DevArr codes, work;
+    size_t codes_bytes = 0, work_bytes = 0;
+    explicit K1Scratch(hipStream_t s) : codes(s), work(s) {}
+    static hipError_t need(DevArr& a, size_t& have, size_t bytes) {             // grow only
+        if (bytes <= have) return hipSuccess;
+        have = 0;
+        const hipError_t e = a.alloc(bytes);                    // from the block cache: a process that counts buffer after buffer finds them there again
+        if (e == hipSuccess) have = bytes;
+        return e;
+    }
+};
+// The same without a full-width sort: MSD partition in two levels + per-bucket LDS hash / sort; u64 counts. The windows of the PLAIN
+// buffer are encoded inside level 1; d_staging (8 B per window) is only what the later stages write their remainders and per-bucket
+// counts to, and the partition workspace lives in scratch.work, kept for the next piece.
+// *fell_back: a bucket held too many distinct remainders; nothing was produced and the caller takes the radix-sort path.
+hipError_t distinct_from_codes_msd(const uint8_t* d_plain, uint64_t plen, uint64_t nwin, int k, int canon_mode, uint64_t* d_staging, K1Scratch& scratch, DevArr& keys,
+                                   DevArr& counts, uint64_t* n_out, bool* fell_back, hipStream_t s);
+
+// sorted (key, count) runs merged without a sort (aix_merge.hip). Every producer below synchronises `s`; on a failure `out` is empty.
+// (A, B) -> keys ascending, equal keys summed. A and B are each sorted and free of repeats.
+hipError_t merge_sum_runs(RunView a, RunView b, DistinctRun& out, hipStream_t s);
 hipError_t merge_runs(const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* offs /* host, nruns + 1 */, uint32_t nruns, uint64_t min_count,
-                      uint64_t** d_keys_out, uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s);
+                      DistinctRun& out, hipStream_t s);
+hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64_t n, uint64_t min_count, DistinctRun& out, hipStream_t s);
+hipError_t distinct_from_plain(const uint8_t* d_plain, uint64_t plen, int k, int canon_mode, uint64_t min_count, uint64_t piece, DistinctRun& out, hipStream_t s);
 // the distinct k-mers of everything added so far; a piece = all k-windows of one PLAIN buffer (<= 2^31 windows)
 class DistinctAcc {
 public:
@@ -202,16 +226,14 @@ public:
     DistinctAcc(const DistinctAcc&) = delete;
     DistinctAcc& operator=(const DistinctAcc&) = delete;
     hipError_t add_plain(const uint8_t* d_plain, uint64_t plen);
-    hipError_t finish(uint64_t min_count, uint64_t** d_keys_out, uint64_t** d_counts_out, uint64_t* n_out);   // pool blocks, the caller frees
-    uint64_t size() const { return acc_n; }
+    hipError_t finish(uint64_t min_count, DistinctRun& out);
+    uint64_t size() const { return acc.n; }
     uint64_t pieces = 0, merges = 0;
 private:
     int k, canon_mode;
     hipStream_t s;
     K1Scratch scratch;
-    uint64_t* acc_k = nullptr;
-    uint64_t* acc_c = nullptr;
-    uint64_t acc_n = 0;
+    DistinctRun acc;
 };
 
 // record normalisation on the device (aix_normalize.hip); d_out holds len + 1 bytes

@@ -16,35 +16,20 @@
 //   k_k1_gather   buckets closed up into the final arrays (bucket order = key order)
 //
 // D2 is chosen so that a bucket holds ~10^3 codes. A bucket with more than K1_DMAX distinct remainders (possible only when
-// the codes are far from uniform in their top 11 + D2 bits) raises a flag and the caller falls back to the radix-sort path:
-// the result never depends on which path ran.
+// the codes are far from uniform in their top 11 + D2 bits) raises a flag and the caller falls back to the radix-sort path
+// (distinct_from_codes, at the end of this file): the result never depends on which path ran.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "aix_env.hpp"
-#include "aix_internal.hpp"
 #include "aix_msd.hpp"
 
 namespace aix {
 
 // ---------------------------------------------------------------------------------------------
-// level 1 sources: sixteen codes per lane and tile
+// level 1 source: sixteen codes per lane and tile
 // ---------------------------------------------------------------------------------------------
-struct K1Codes {                                      // an array of window codes (~0 = no k-mer), e.g. written by k_window_codes
-    const uint64_t* codes;
-    uint64_t n;
-    __device__ __forceinline__ void load(uint64_t tile, int t, uint64_t (&c)[K1_WPT]) const {
-        const uint64_t base = tile * K1_TILE + (uint64_t)t;   // code j of this lane = base + j * 1024: coalesced 8 KiB per load instruction
-#pragma unroll
-        for (int j = 0; j < K1_WPT; ++j) {
-            const uint64_t i = base + (uint64_t)j * K1_TB;
-            c[j] = i < n ? codes[i] : K1_INVALID;
-        }
-    }
-};
 // The windows of a PLAIN buffer, encoded here (count_kmers.cpp:93-136,297-308: A/C/G/T/U either case, canonical form by
 // canon_mode): a lane owns 16 consecutive window starts, its 16 + k - 1 bytes are turned ONCE into a 2-bit stream (4 bytes per
 // step) and every window is a shift of it — no 8-byte code per window is written to and read back from HBM.
@@ -249,7 +234,7 @@ __global__ void __launch_bounds__(K1_FB) k_k1_final(const uint32_t* __restrict__
 }
 
 // buckets closed up: bucket b's m entries move from its base to dm_off[b]; one wave per bucket
-// CNT = uint32_t (the ABI's per-piece result) or uint64_t (what the merge of pieces and kmer_counter's output carry: written here, no widening pass)
+// CNT = uint64_t: what the merge of pieces and kmer_counter's output carry is written here, no widening pass
 template <typename CNT>
 __global__ void __launch_bounds__(256) k_k1_gather(const uint64_t* __restrict__ keys_st, const uint32_t* __restrict__ cnt_st, const uint32_t* __restrict__ bucket_base,
                                                   const uint32_t* __restrict__ dm_off, uint32_t nbuckets, uint64_t* __restrict__ keys, CNT* __restrict__ counts) {
@@ -264,127 +249,112 @@ __global__ void __launch_bounds__(256) k_k1_gather(const uint64_t* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
-
 bool k1_msd_eligible(uint64_t nwin, int k) {
     if (env_flag("AIX_K1_ROCPRIM")) return false;      // A/B switch: the radix-sort path
     return k >= 9 && k <= 23 && nwin > 0 && nwin <= (1ull << 31);
 }
 
-// d_codes: nwin window codes (~0 = no k-mer), clobbered (re-used as staging). Outputs are pool blocks (caller releases).
-// *fell_back = true: a bucket overflowed, nothing was produced (the caller runs the radix-sort path on d_codes — intact in that case
-// only if it re-creates the codes, so the caller keeps a way to regenerate them).
-// d_plain != nullptr: the windows are encoded inside level 1 (no code array is read; d_codes is then only the 8 B-per-window
-// scratch the later stages re-use). plen = bytes of the PLAIN buffer.
-hipError_t distinct_from_codes_msd(uint64_t* d_codes, uint64_t nwin, int k, uint64_t** d_keys_out, uint32_t** d_counts_out, uint64_t* n_out, bool* fell_back,
-                                   hipStream_t s, const uint8_t* d_plain, uint64_t plen, int canon_mode, uint64_t** d_counts64_out, K1Scratch* scratch) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0; *fell_back = false;
-    if (d_counts64_out) *d_counts64_out = nullptr;
+hipError_t distinct_from_codes_msd(const uint8_t* d_plain, uint64_t plen, uint64_t nwin, int k, int canon_mode, uint64_t* d_staging, K1Scratch& scratch, DevArr& keys,
+                                   DevArr& counts, uint64_t* n_out, bool* fell_back, hipStream_t s) {
+    *n_out = 0; *fell_back = false;
     const uint32_t B = 2u * (uint32_t)k, s1 = B - K1_PBITS;
     // D2: ~768 codes per bucket on average; the remainder must fit 32 bits
     uint32_t D2 = 3;
     while (D2 < 11 && (nwin >> (K1_PBITS + D2)) > 900) ++D2;
     while (s1 - D2 > 31) ++D2;                                  // remainder + 1 must not wrap (0 marks an empty hash slot)
     if (D2 > s1) D2 = s1;
-    const uint32_t s2 = s1 - D2, nb2 = 1u << D2;
-    const uint32_t nbuckets = (uint32_t)K1_P * nb2;
-    const uint64_t ntiles = (nwin + K1_TILE - 1) / K1_TILE;
-    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, K1_MAXGRID);
-    const uint32_t region = (uint32_t)env_int("AIX_K1_TEST_REGION", 1, LONG_MAX, (long)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P));   // test hook: an undersized region must fail loudly
-    const uint32_t cap = grid * region;
-    // one block: err | overflow | dir_part | dir_cnt | spart | sdesc | sort temp | bucket_cnt (nbuckets + 1) | bucket_base | distinct_m | dm_off | out32 | parts
-    size_t sort_tmp = 0;
-    {
-        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{nullptr});
-        (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (const uint16_t*)nullptr, (uint16_t*)nullptr, vals, (uint64_t*)nullptr, (size_t)cap, 0u, 12u, s);
-    }
-    size_t scan_tmp = 0;
-    (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
-    const uint64_t o_flags = 0, o_dirp = 256, o_dirc = o_dirp + up256(2ull * cap), o_spart = o_dirc + up256(2ull * cap), o_sdesc = o_spart + up256(2ull * cap),
-                   o_stmp = o_sdesc + up256(8ull * cap), o_bcnt = o_stmp + up256(std::max(sort_tmp, scan_tmp)), o_bbase = o_bcnt + up256(4ull * (nbuckets + 1)),
-                   o_dm = o_bbase + up256(4ull * (nbuckets + 1)), o_dmo = o_dm + up256(4ull * (nbuckets + 1)), o_parts = o_dmo + up256(4ull * (nbuckets + 1)),
-                   total = o_parts + 8ull * cap * K1_CH;
-    uint8_t* w = nullptr;
-    hipError_t e = scratch ? scratch->need(&scratch->work, &scratch->work_bytes, total) : pool_alloc((void**)&w, total);
-    if (e != hipSuccess) return e;
-    if (scratch) w = (uint8_t*)scratch->work;
-    uint32_t* err = (uint32_t*)(w + o_flags);
-    uint32_t* overflow = err + 1;
-    uint16_t* dir_part = (uint16_t*)(w + o_dirp);
-    uint16_t* dir_cnt = (uint16_t*)(w + o_dirc);
-    uint16_t* spart = (uint16_t*)(w + o_spart);
-    uint64_t* sdesc = (uint64_t*)(w + o_sdesc);
-    void* tmp = w + o_stmp;
-    uint32_t* bucket_cnt = (uint32_t*)(w + o_bcnt);
-    uint32_t* bucket_base = (uint32_t*)(w + o_bbase);
+    const uint32_t s2 = s1 - D2;
+    const MsdPlan P(nwin, 1u << D2, (uint32_t)env_int("AIX_K1_TEST_REGION", 1, LONG_MAX, 0), s);   // test hook: an undersized region must fail loudly
+    const uint32_t nbuckets = P.nbuckets;
+    // behind the head (word 0: region exhausted, word 1: a bucket overflowed): distinct_m (nbuckets + 1) | dm_off | parts
+    const uint64_t o_dm = P.head_bytes, o_dmo = o_dm + up256(4ull * (nbuckets + 1)), o_parts = o_dmo + up256(4ull * (nbuckets + 1));
+    AIX_TRY(K1Scratch::need(scratch.work, scratch.work_bytes, o_parts + P.parts_bytes()));
+    uint8_t* w = (uint8_t*)scratch.work.p;
+    uint32_t* overflow = (uint32_t*)w + 1;
+    uint32_t* bucket_base = P.bucket_base(w);
     uint32_t* distinct_m = (uint32_t*)(w + o_dm);
     uint32_t* dm_off = (uint32_t*)(w + o_dmo);
-    // the code array (8 B per window) is free once level 1 has read it: its first half takes the 32-bit remainders of level 2,
-    // its second half the per-bucket counts; the chunk array (>= 8 B per window) is free after level 2 and takes the per-bucket keys
-    uint32_t* out32 = (uint32_t*)d_codes;
-    uint32_t* cnt_st = (uint32_t*)d_codes + nwin;
+    // the staging (8 B per window): its first half takes the 32-bit remainders of level 2, its second half the per-bucket counts;
+    // the chunk array (>= 8 B per window) is free after level 2 and takes the per-bucket keys
+    uint32_t* out32 = (uint32_t*)d_staging;
+    uint32_t* cnt_st = (uint32_t*)d_staging + nwin;
     uint64_t* parts = (uint64_t*)(w + o_parts);
     uint64_t* keys_st = parts;
-    uint64_t* keys = nullptr;
-    uint32_t* counts = nullptr;
-    uint32_t flags[2] = {0, 0};
-    uint32_t total_distinct = 0;
-    do {
-        e = hipFuncSetAttribute((const void*)k_k1_split<K1Codes>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_k1_split<K1Plain>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_k1_scatter<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS);
-        if (e == hipSuccess) e = hipMemsetAsync(w, 0, 256, s);
-        if (e == hipSuccess) e = hipMemsetD16Async((hipDeviceptr_t)dir_part, (unsigned short)K1_P, cap, s);      // "no partition": sorts behind every real one
-        if (e == hipSuccess) e = hipMemsetD16Async((hipDeviceptr_t)dir_cnt, (unsigned short)K1_CH, cap, s);      // chunks are full unless the split says otherwise
-        if (e == hipSuccess) e = hipMemsetAsync(bucket_cnt, 0, 4ull * (nbuckets + 1), s);
-        if (e == hipSuccess) e = hipMemsetAsync(distinct_m, 0, 4ull * (nbuckets + 1), s);
-        if (e != hipSuccess) break;
-        if (d_plain) hipLaunchKernelGGL(k_k1_split<K1Plain>, dim3(grid), dim3(K1_TB), K1_TILE_LDS, s, K1Plain{d_plain, plen, nwin, k, canon_mode}, s1, ntiles, region,
-                                        dir_part, dir_cnt, parts, err);
-        else hipLaunchKernelGGL(k_k1_split<K1Codes>, dim3(grid), dim3(K1_TB), K1_TILE_LDS, s, K1Codes{(const uint64_t*)d_codes, nwin}, s1, ntiles, region, dir_part,
-                                dir_cnt, parts, err);
-        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{dir_cnt});
-        size_t tb = sort_tmp;
-        e = rocprim::radix_sort_pairs(tmp, tb, (const uint16_t*)dir_part, spart, vals, sdesc, (size_t)cap, 0u, 12u, s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_k1_count, dim3(K1_P), dim3(K1_TB), 0, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, cap, s2, nb2, bucket_cnt);
-        tb = scan_tmp;
-        e = rocprim::exclusive_scan(tmp, tb, bucket_cnt, bucket_base, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_k1_scatter<uint32_t>, dim3(K1_P), dim3(K1_TB), K1_TILE_LDS, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, cap, s2, nb2,
-                           (const uint32_t*)bucket_base, out32);
-        hipLaunchKernelGGL(k_k1_final, dim3(std::min<uint32_t>(nbuckets, 256u * 5u)), dim3(K1_FB), 0, s, (const uint32_t*)out32, (const uint32_t*)bucket_base, nbuckets, s2,
-                           keys_st, cnt_st, distinct_m, overflow);
-        tb = scan_tmp;
-        e = rocprim::exclusive_scan(tmp, tb, distinct_m, dm_off, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
-        if (e == hipSuccess) e = hipMemcpyAsync(flags, w, 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&total_distinct, dm_off + nbuckets, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) break;
-        if (flags[0]) { e = hipErrorAssert; break; }             // chunk region exhausted: never silent (the caller reports it)
-        if (flags[1]) { *fell_back = true; break; }
-        if (total_distinct == 0) break;
-        e = pool_alloc((void**)&keys, 8ull * total_distinct);
-        if (e == hipSuccess) e = pool_alloc((void**)&counts, (d_counts64_out ? 8ull : 4ull) * total_distinct);
-        if (e != hipSuccess) break;
-        const dim3 ggrid(std::min<uint32_t>((nbuckets + 3) / 4, 1u << 16));
-        if (d_counts64_out) hipLaunchKernelGGL(k_k1_gather<uint64_t>, ggrid, dim3(256), 0, s, (const uint64_t*)keys_st, (const uint32_t*)cnt_st, (const uint32_t*)bucket_base,
-                                               (const uint32_t*)dm_off, nbuckets, keys, (uint64_t*)counts);
-        else hipLaunchKernelGGL(k_k1_gather<uint32_t>, ggrid, dim3(256), 0, s, (const uint64_t*)keys_st, (const uint32_t*)cnt_st, (const uint32_t*)bucket_base,
-                                (const uint32_t*)dm_off, nbuckets, keys, counts);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    } while (false);
-    { const hipError_t es = hipStreamSynchronize(s); if (e == hipSuccess) e = es; }
-    if (!scratch) pool_free(w);
-    if (e != hipSuccess || *fell_back) {
-        if (keys) pool_free(keys);
-        if (counts) pool_free(counts);
-        return e;
-    }
-    *d_keys_out = keys; *n_out = total_distinct;
-    if (d_counts64_out) { *d_counts64_out = (uint64_t*)counts; *d_counts_out = nullptr; } else *d_counts_out = counts;
+    AIX_TRY(hipMemsetAsync(distinct_m, 0, 4ull * (nbuckets + 1), s));
+    AIX_TRY(msd_partition(P, w, K1Plain{d_plain, plen, nwin, k, canon_mode}, s1, s2, parts, out32, s));
+    AIX_TRY_LAUNCH(k_k1_final, dim3(std::min<uint32_t>(nbuckets, 256u * 5u)), dim3(K1_FB), 0, s, (const uint32_t*)out32, (const uint32_t*)bucket_base, nbuckets, s2, keys_st,
+                   cnt_st, distinct_m, overflow);
+    AIX_TRY(P.scan(w, distinct_m, dm_off, s));
+    uint32_t flags[2] = {0, 0}, total_distinct = 0;
+    AIX_TRY(hipMemcpyAsync(flags, w, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipMemcpyAsync(&total_distinct, dm_off + nbuckets, 4, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    if (flags[0]) return hipErrorAssert;                        // chunk region exhausted: never silent (the caller reports it)
+    if (flags[1]) { *fell_back = true; return hipSuccess; }
+    if (total_distinct == 0) return hipSuccess;
+    AIX_TRY(keys.alloc(8ull * total_distinct));
+    AIX_TRY(counts.alloc(8ull * total_distinct));
+    AIX_TRY_LAUNCH(k_k1_gather<uint64_t>, dim3(std::min<uint32_t>((nbuckets + 3) / 4, 1u << 16)), dim3(256), 0, s, (const uint64_t*)keys_st, (const uint32_t*)cnt_st,
+                   (const uint32_t*)bucket_base, (const uint32_t*)dm_off, nbuckets, (uint64_t*)keys.p, (uint64_t*)counts.p);
+    AIX_TRY(hipStreamSynchronize(s));
+    *n_out = total_distinct;
     return hipSuccess;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The radix-sort back end: sort + run-length of the window codes (k_window_codes: invalid windows = ~0).
+// ---------------------------------------------------------------------------------------------
+static constexpr int kB = kFlatBlock;
+
+__global__ void __launch_bounds__(kB) k_mark_invalid(uint64_t* __restrict__ codes, uint64_t nwin, uint64_t sentinel) {
+    const uint64_t stride = (uint64_t)gridDim.x * kB;
+    for (uint64_t i = (uint64_t)blockIdx.x * kB + threadIdx.x; i < nwin; i += stride)
+        if (codes[i] == ~0ULL) codes[i] = sentinel;
+}
+__global__ void __launch_bounds__(kB) k_flag_min(const uint32_t* __restrict__ counts, uint64_t runs, const uint64_t* __restrict__ keys, uint64_t sentinel,
+                                                uint32_t min_count, uint8_t* __restrict__ flags) {
+    const uint64_t stride = (uint64_t)gridDim.x * kB;
+    for (uint64_t i = (uint64_t)blockIdx.x * kB + threadIdx.x; i < runs; i += stride)
+        flags[i] = (keys[i] != sentinel && counts[i] >= min_count) ? 1 : 0;
+}
+
+hipError_t distinct_from_codes(uint64_t* d_codes, uint64_t nwin, int k, DevArr& keys, DevArr& counts, uint64_t* n_out, hipStream_t s) {
+    *n_out = 0;
+    if (nwin == 0) return hipSuccess;
+    const uint64_t sentinel = 1ULL << (2 * k);                 // k <= 31: one bit above every valid code
+    AIX_TRY_LAUNCH(k_mark_invalid, dim3(flat_grid(nwin)), dim3(kB), 0, s, d_codes, nwin, sentinel);
+    DevArr sorted(s), tmp(s), ucnt(s), d_runs(s);
+    AIX_TRY(sorted.alloc(8 * nwin));
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, d_codes, (uint64_t*)sorted.p, (size_t)nwin, 0u, (unsigned)(2 * k + 1), s); }));
+    tmp.drop();
+    // run-length encode into the (now free) input buffer as unique keys, plus counts. rocPRIM takes the input size as unsigned int:
+    // nwin < 2^32 here (a piece holds at most 2^31 windows)
+    uint64_t* ukeys = d_codes;
+    AIX_TRY(ucnt.alloc(4 * nwin));
+    AIX_TRY(d_runs.alloc(8));
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) {
+        return rocprim::run_length_encode(t, tb, (uint64_t*)sorted.p, (unsigned int)nwin, ukeys, (uint32_t*)ucnt.p, (uint64_t*)d_runs.p, s);
+    }));
+    uint64_t runs = 0, kept = 0;
+    AIX_TRY(hipMemcpyAsync(&runs, d_runs.p, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    tmp.drop();                                                 // the sorted codes and the temporary go back before the filter's blocks are taken
+    sorted.drop();
+    if (runs == 0) return hipSuccess;
+    // filter: drop the sentinel run (every real run counts at least 1)
+    DevArr flags(s), d_sel(s), tmp_c(s);
+    AIX_TRY(flags.alloc(runs));
+    AIX_TRY(keys.alloc(8 * runs));
+    AIX_TRY(counts.alloc(4 * runs));
+    AIX_TRY(d_sel.alloc(8));
+    AIX_TRY_LAUNCH(k_flag_min, dim3(flat_grid(runs)), dim3(kB), 0, s, (uint32_t*)ucnt.p, runs, ukeys, sentinel, 1u, (uint8_t*)flags.p);
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) { return rocprim::select(t, tb, ukeys, (uint8_t*)flags.p, (uint64_t*)keys.p, (uint64_t*)d_sel.p, (size_t)runs, s); }));
+    AIX_TRY(with_temp(tmp_c, [&](void* t, size_t& tb) { return rocprim::select(t, tb, (uint32_t*)ucnt.p, (uint8_t*)flags.p, (uint32_t*)counts.p, (uint64_t*)d_sel.p, (size_t)runs, s); }));
+    AIX_TRY(hipMemcpyAsync(&kept, d_sel.p, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    *n_out = kept;
+    return hipSuccess;
+}
+
 
 }  // namespace aix

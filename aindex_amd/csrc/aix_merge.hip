@@ -15,13 +15,11 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include <new>
 #include <string>
 
 #include "aix_env.hpp"
-#include "aix_handle.hpp"
+#include "aix_hostkit.hpp"
 
 namespace aix {
 
@@ -128,44 +126,30 @@ __global__ void __launch_bounds__(MG_TB) k_merge_tile(const uint64_t* __restrict
     }
 }
 
-// (A, B) -> keys ascending, equal keys summed. A and B are each sorted and free of repeats. Outputs from the scratch pool (caller frees);
-// *n_out is known when this returns (the stream is synchronised).
-hipError_t merge_sum_runs(const uint64_t* ak, const uint64_t* ac, uint64_t na, const uint64_t* bk, const uint64_t* bc, uint64_t nb, uint64_t** d_keys_out,
-                          uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0;
-    const uint64_t tot = na + nb;
+hipError_t merge_sum_runs(RunView a, RunView b, DistinctRun& out, hipStream_t s) {
+    out.reset();
+    const uint64_t tot = a.n + b.n;
     if (tot == 0) return hipSuccess;
     const uint64_t ntiles = (tot + MG_T - 1) / MG_T;
     DevArr split(s), counts(s), bases(s), tmp(s), ok(s), oc(s);
-    hipError_t e = split.alloc(16 * (ntiles + 1));
-    if (e == hipSuccess) e = counts.alloc(8 * (ntiles + 1));
-    if (e == hipSuccess) e = bases.alloc(8 * (ntiles + 1));
-    if (e != hipSuccess) return e;
-    size_t tb = 0;
-    e = rocprim::exclusive_scan(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(ntiles + 1), rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e != hipSuccess) return e;
+    AIX_TRY(split.alloc(16 * (ntiles + 1)));
+    AIX_TRY(counts.alloc(8 * (ntiles + 1)));
+    AIX_TRY(bases.alloc(8 * (ntiles + 1)));
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 1u << 20);
-    hipLaunchKernelGGL(k_merge_split, dim3((unsigned)((ntiles + 1 + kB - 1) / kB)), dim3(kB), 0, s, ak, na, bk, nb, ntiles, (uint64_t*)split.p);
-    e = hipMemsetAsync((uint64_t*)counts.p + ntiles, 0, 8, s);   // the scan runs over ntiles + 1 words: its last output is the total
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_merge_tile<false>), dim3(grid), dim3(MG_TB), 0, s, ak, ac, bk, bc, (const uint64_t*)split.p, ntiles, (uint64_t*)counts.p,
-                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, (uint64_t*)counts.p, (uint64_t*)bases.p, (uint64_t)0, (size_t)(ntiles + 1), rocprim::plus<uint64_t>(), s);
+    AIX_TRY_LAUNCH(k_merge_split, dim3((unsigned)((ntiles + 1 + kB - 1) / kB)), dim3(kB), 0, s, a.k, a.n, b.k, b.n, ntiles, (uint64_t*)split.p);
+    AIX_TRY(hipMemsetAsync((uint64_t*)counts.p + ntiles, 0, 8, s));   // the scan runs over ntiles + 1 words: its last output is the total
+    AIX_TRY_LAUNCH((k_merge_tile<false>), dim3(grid), dim3(MG_TB), 0, s, a.k, a.c, b.k, b.c, (const uint64_t*)split.p, ntiles, (uint64_t*)counts.p,
+                   (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    AIX_TRY(scan_u64((uint64_t*)counts.p, (uint64_t*)bases.p, ntiles + 1, tmp, s));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, (uint64_t*)bases.p + ntiles, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    e = ok.alloc(8 * (total ? total : 1));
-    if (e == hipSuccess) e = oc.alloc(8 * (total ? total : 1));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_merge_tile<true>), dim3(grid), dim3(MG_TB), 0, s, ak, ac, bk, bc, (const uint64_t*)split.p, ntiles, (uint64_t*)nullptr,
-                       (const uint64_t*)bases.p, (uint64_t*)ok.p, (uint64_t*)oc.p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    *d_keys_out = (uint64_t*)ok.release(); *d_counts_out = (uint64_t*)oc.release(); *n_out = total;
+    AIX_TRY(hipMemcpyAsync(&total, (uint64_t*)bases.p + ntiles, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    AIX_TRY(ok.alloc(8 * total));
+    AIX_TRY(oc.alloc(8 * total));
+    AIX_TRY_LAUNCH((k_merge_tile<true>), dim3(grid), dim3(MG_TB), 0, s, a.k, a.c, b.k, b.c, (const uint64_t*)split.p, ntiles, (uint64_t*)nullptr, (const uint64_t*)bases.p,
+                   (uint64_t*)ok.p, (uint64_t*)oc.p);
+    AIX_TRY(hipStreamSynchronize(s));
+    out.adopt(ok, oc, total);
     return hipSuccess;
 }
 
@@ -178,38 +162,31 @@ __global__ void __launch_bounds__(kB) k_flag_min64(const uint64_t* __restrict__ 
     for (uint64_t i = (uint64_t)blockIdx.x * kB + threadIdx.x; i < n; i += stride) flags[i] = counts[i] >= min_count ? 1 : 0;
 }
 
-// keep the entries with count >= min_count (order kept). In: pool blocks k / c of n entries (freed here when replaced).
-static hipError_t filter_min_count(uint64_t** k, uint64_t** c, uint64_t* n, uint64_t min_count, hipStream_t s) {
-    if (min_count <= 1 || *n == 0) return hipSuccess;
-    DevArr flags(s), fk(s), fc(s), d_sel(s), tmp(s);
-    hipError_t e = flags.alloc(*n);
-    if (e == hipSuccess) e = fk.alloc(8 * *n);
-    if (e == hipSuccess) e = fc.alloc(8 * *n);
-    if (e == hipSuccess) e = d_sel.alloc(8);
-    size_t tb = 0;
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_flag_min64, dim3(grid_of(*n)), dim3(kB), 0, s, (const uint64_t*)*c, *n, min_count, (uint8_t*)flags.p); e = hipGetLastError(); }
-    if (e == hipSuccess) e = rocprim::select(nullptr, tb, *k, (uint8_t*)flags.p, (uint64_t*)fk.p, (uint64_t*)d_sel.p, (size_t)*n, s);
-    if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::select(tmp.p, tb, *k, (uint8_t*)flags.p, (uint64_t*)fk.p, (uint64_t*)d_sel.p, (size_t)*n, s);
-    if (e == hipSuccess) e = rocprim::select(tmp.p, tb, *c, (uint8_t*)flags.p, (uint64_t*)fc.p, (uint64_t*)d_sel.p, (size_t)*n, s);
+// keeps the entries of r with count >= min_count (order kept); synchronises `s`. On a failure r is as it was.
+static hipError_t filter_min_count(DistinctRun& r, uint64_t min_count, hipStream_t s) {
+    if (min_count <= 1 || r.n == 0) return hipSuccess;
+    DevArr flags(s), fk(s), fc(s), d_sel(s), tmp_k(s), tmp_c(s);
+    AIX_TRY(flags.alloc(r.n));
+    AIX_TRY(fk.alloc(8 * r.n));
+    AIX_TRY(fc.alloc(8 * r.n));
+    AIX_TRY(d_sel.alloc(8));
+    AIX_TRY_LAUNCH(k_flag_min64, dim3(grid_of(r.n)), dim3(kB), 0, s, (const uint64_t*)r.c, r.n, min_count, (uint8_t*)flags.p);
+    AIX_TRY(with_temp(tmp_k, [&](void* t, size_t& tb) { return rocprim::select(t, tb, r.k, (uint8_t*)flags.p, (uint64_t*)fk.p, (uint64_t*)d_sel.p, (size_t)r.n, s); }));
+    AIX_TRY(with_temp(tmp_c, [&](void* t, size_t& tb) { return rocprim::select(t, tb, r.c, (uint8_t*)flags.p, (uint64_t*)fc.p, (uint64_t*)d_sel.p, (size_t)r.n, s); }));
     uint64_t kept = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&kept, d_sel.p, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    pool_free(*k); pool_free(*c);
-    *k = (uint64_t*)fk.release(); *c = (uint64_t*)fc.release(); *n = kept;
+    AIX_TRY(hipMemcpyAsync(&kept, d_sel.p, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    r.adopt(fk, fc, kept);
     return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------------------
 // DistinctAcc: the distinct set of everything added so far (K1 for buffers / files of any length). A piece = every k-window of one
-// PLAIN buffer of at most 2^31 windows; its distinct set (aix_k1.hip, or the radix-sort path) is merged into the accumulated one.
+// PLAIN buffer of at most 2^31 windows; its distinct set (aix_k1.hip: the MSD path, or the radix-sort path) is merged into the accumulated one.
 // ---------------------------------------------------------------------------------------------
-DistinctAcc::DistinctAcc(int kk, int canon, hipStream_t st) : k(kk), canon_mode(canon), s(st) { scratch.s = st; }
+DistinctAcc::DistinctAcc(int kk, int canon, hipStream_t st) : k(kk), canon_mode(canon), s(st), scratch(st) {}
 DistinctAcc::~DistinctAcc() {
-    if (acc_k || acc_c) (void)hipStreamSynchronize(s);
-    if (acc_k) pool_free(acc_k);
-    if (acc_c) pool_free(acc_c);
+    if (acc.k || acc.c) (void)hipStreamSynchronize(s);          // the last merge or the caller's copies may still read the set
 }
 
 hipError_t DistinctAcc::add_plain(const uint8_t* d_plain, uint64_t plen) {
@@ -218,58 +195,45 @@ hipError_t DistinctAcc::add_plain(const uint8_t* d_plain, uint64_t plen) {
     if (nwin > (1ull << 31)) return hipErrorInvalidValue;
     ++pieces;
     // the 8 B-per-window staging and the partition workspace stay with the accumulator from piece to piece (K1Scratch)
-    struct { void* p; } codes{nullptr};
-    hipError_t e = scratch.need(&scratch.codes, &scratch.codes_bytes, 8 * nwin);
-    codes.p = scratch.codes;
-    uint64_t* pk = nullptr; uint32_t* pc = nullptr; uint64_t pm = 0;
-    uint64_t* pc64 = nullptr;                                             // the MSD path hands its counts over as u64 (no widening pass)
+    AIX_TRY(K1Scratch::need(scratch.codes, scratch.codes_bytes, 8 * nwin));
+    uint64_t* codes = (uint64_t*)scratch.codes.p;
+    DevArr pk(s), pc(s), pc32(s);
+    uint64_t pm = 0;
     bool sorted_path = !k1_msd_eligible(nwin, k);
-    if (e == hipSuccess && sorted_path) e = launch_window_codes(d_plain, plen, k, canon_mode, (uint64_t*)codes.p, s);
-    if (e == hipSuccess && !sorted_path) {                                // MSD partition + per-bucket LDS hash / sort (aix_k1.hip); windows encoded inside level 1
-        bool fell_back = false;
-        e = distinct_from_codes_msd((uint64_t*)codes.p, nwin, k, &pk, &pc, &pm, &fell_back, s, d_plain, plen, canon_mode, &pc64, &scratch);
-        if (e == hipSuccess && fell_back) {                               // a bucket too rich for LDS: the codes were used as staging, make them again
-            sorted_path = true;
-            e = launch_window_codes(d_plain, plen, k, canon_mode, (uint64_t*)codes.p, s);
+    // MSD partition + per-bucket LDS hash / sort, windows encoded inside level 1, counts as u64. A bucket too rich for LDS: nothing was
+    // produced and the piece takes the sort path
+    if (!sorted_path) AIX_TRY(distinct_from_codes_msd(d_plain, plen, nwin, k, canon_mode, codes, scratch, pk, pc, &pm, &sorted_path, s));
+    if (sorted_path) {                                                    // counts in 32 bits, widened here
+        AIX_TRY(launch_window_codes(d_plain, plen, k, canon_mode, codes, s));
+        AIX_TRY(distinct_from_codes(codes, nwin, k, pk, pc32, &pm, s));
+        if (pm) {
+            AIX_TRY(pc.alloc(8 * pm));
+            AIX_TRY_LAUNCH(k_widen_counts, dim3(grid_of(pm)), dim3(kB), 0, s, (const uint32_t*)pc32.p, pm, (uint64_t*)pc.p);
         }
     }
-    if (e == hipSuccess && sorted_path) e = distinct_from_codes((uint64_t*)codes.p, nwin, k, 1, &pk, &pc, &pm, s);
-    DevArr hold_k(s), hold_c(s), hold_c64(s); hold_k.p = pk; hold_c.p = pc; hold_c64.p = pc64;
-    if (e != hipSuccess || pm == 0) return e;
-    if (!pc64) {                                                          // the sort path counts in 32 bits
-        e = hold_c64.alloc(8 * pm);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_widen_counts, dim3(grid_of(pm)), dim3(kB), 0, s, pc, pm, (uint64_t*)hold_c64.p);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (acc_n == 0) {                                                     // the first non-empty piece: sorted, distinct, u64 counts — taken as it is
+    if (pm == 0) return hipSuccess;
+    if (acc.n == 0) {                                                     // the first non-empty piece: sorted, distinct, u64 counts — taken as it is
         (void)hipStreamSynchronize(s);
-        acc_k = (uint64_t*)hold_k.release(); acc_c = (uint64_t*)hold_c64.release(); acc_n = pm;
+        acc.adopt(pk, pc, pm);
         return hipSuccess;
     }
-    uint64_t *mk = nullptr, *mc = nullptr, mn = 0;
-    e = merge_sum_runs(acc_k, acc_c, acc_n, (const uint64_t*)hold_k.p, (const uint64_t*)hold_c64.p, pm, &mk, &mc, &mn, s);
-    if (e != hipSuccess) return e;
+    DistinctRun merged;
+    AIX_TRY(merge_sum_runs(acc.view(), RunView{(const uint64_t*)pk.p, (const uint64_t*)pc.p, pm}, merged, s));
     ++merges;
-    pool_free(acc_k); pool_free(acc_c);
-    acc_k = mk; acc_c = mc; acc_n = mn;
+    acc = std::move(merged);
     return hipSuccess;
 }
 
-hipError_t DistinctAcc::finish(uint64_t min_count, uint64_t** d_keys_out, uint64_t** d_counts_out, uint64_t* n_out) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0;
-    if (acc_n == 0) return hipSuccess;
-    const hipError_t e = filter_min_count(&acc_k, &acc_c, &acc_n, min_count, s);
-    if (e != hipSuccess) return e;
-    *d_keys_out = acc_k; *d_counts_out = acc_c; *n_out = acc_n;
-    acc_k = nullptr; acc_c = nullptr; acc_n = 0;
+hipError_t DistinctAcc::finish(uint64_t min_count, DistinctRun& out) {
+    out.reset();
+    if (acc.n == 0) return hipSuccess;
+    AIX_TRY(filter_min_count(acc, min_count, s));
+    out = std::move(acc);
     return hipSuccess;
 }
 
-hipError_t distinct_from_plain(const uint8_t* d_plain, uint64_t plen, int k, int canon_mode, uint64_t min_count, uint64_t piece, uint64_t** d_keys_out,
-                               uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0;
+hipError_t distinct_from_plain(const uint8_t* d_plain, uint64_t plen, int k, int canon_mode, uint64_t min_count, uint64_t piece, DistinctRun& out, hipStream_t s) {
+    out.reset();
     if (plen < (uint64_t)k) return hipSuccess;
     const uint64_t nwin_all = plen - k + 1;
     // 32-bit window indices inside a piece allow 2^31 windows; the default is 2^30: the two big temporaries of a piece are then 8 and 8.5 GiB
@@ -279,82 +243,70 @@ hipError_t distinct_from_plain(const uint8_t* d_plain, uint64_t plen, int k, int
     DistinctAcc acc(k, canon_mode, s);
     for (uint64_t w0 = 0; w0 < nwin_all; w0 += piece) {                      // a window belongs to the piece that holds its first byte
         const uint64_t nwin = std::min(piece, nwin_all - w0);
-        const hipError_t e = acc.add_plain(d_plain + w0, nwin + k - 1);
-        if (e != hipSuccess) return e;
+        AIX_TRY(acc.add_plain(d_plain + w0, nwin + k - 1));
     }
-    return acc.finish(min_count, d_keys_out, d_counts_out, n_out);
+    return acc.finish(min_count, out);
 }
 
 // (key, count) pairs in `nruns` runs, run r = entries [offs[r], offs[r + 1]), each run sorted by key and free of repeats (what a rank
 // holds after the K1 exchange: one run per peer) -> keys ascending, counts of equal keys summed, counts >= min_count. A tree of
 // two-way merges: every entry is read and written log2(nruns) times, nothing is sorted. Inputs are not modified.
-hipError_t merge_runs(const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* offs, uint32_t nruns, uint64_t min_count, uint64_t** d_keys_out,
-                      uint64_t** d_counts_out, uint64_t* n_out, hipStream_t s) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0;
-    struct Run { const uint64_t* k; const uint64_t* c; uint64_t n; bool owned; };
+hipError_t merge_runs(const uint64_t* d_keys, const uint64_t* d_counts, const uint64_t* offs, uint32_t nruns, uint64_t min_count, DistinctRun& out, hipStream_t s) {
+    out.reset();
+    struct Run { RunView v; DistinctRun own; };                             // own: empty for a run of the caller's, else what v looks at
     std::vector<Run> cur;
     for (uint32_t r = 0; r < nruns; ++r)
-        if (offs[r + 1] > offs[r]) cur.push_back(Run{d_keys + offs[r], d_counts + offs[r], offs[r + 1] - offs[r], false});
-    auto drop = [&](std::vector<Run>& v) { for (Run& x : v) if (x.owned) { pool_free((void*)x.k); pool_free((void*)x.c); } v.clear(); };
-    hipError_t e = hipSuccess;
-    while (cur.size() > 1 && e == hipSuccess) {
+        if (offs[r + 1] > offs[r]) cur.push_back(Run{RunView{d_keys + offs[r], d_counts + offs[r], offs[r + 1] - offs[r]}, DistinctRun{}});
+    while (cur.size() > 1) {
         std::vector<Run> nxt;
-        for (size_t i = 0; i + 1 < cur.size() && e == hipSuccess; i += 2) {
-            uint64_t *mk = nullptr, *mc = nullptr, mn = 0;
-            e = merge_sum_runs(cur[i].k, cur[i].c, cur[i].n, cur[i + 1].k, cur[i + 1].c, cur[i + 1].n, &mk, &mc, &mn, s);
-            if (e == hipSuccess) nxt.push_back(Run{mk, mc, mn, true});
+        for (size_t i = 0; i + 1 < cur.size(); i += 2) {
+            Run m;
+            AIX_TRY(merge_sum_runs(cur[i].v, cur[i + 1].v, m.own, s));
+            m.v = m.own.view();
+            nxt.push_back(std::move(m));
         }
-        if (e == hipSuccess && (cur.size() & 1)) { nxt.push_back(cur.back()); cur.back().owned = false; }
-        drop(cur);
-        cur.swap(nxt);
+        if (cur.size() & 1) nxt.push_back(std::move(cur.back()));
+        cur.swap(nxt);                                                      // the merged inputs die here: merge_sum_runs has synchronised
     }
-    if (e != hipSuccess) { drop(cur); return e; }
     if (cur.empty()) return hipSuccess;
-    uint64_t *k = nullptr, *c = nullptr, n = cur[0].n;
-    if (cur[0].owned) { k = (uint64_t*)cur[0].k; c = (uint64_t*)cur[0].c; }
-    else {                                                                  // a single run: the result is a copy (inputs stay the caller's)
+    DistinctRun res = std::move(cur[0].own);
+    if (!res.k) {                                                           // a single run: the result is a copy (inputs stay the caller's)
+        const RunView v = cur[0].v;
         DevArr ck(s), cc(s);
-        e = ck.alloc(8 * n);
-        if (e == hipSuccess) e = cc.alloc(8 * n);
-        if (e == hipSuccess) e = hipMemcpyAsync(ck.p, cur[0].k, 8 * n, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(cc.p, cur[0].c, 8 * n, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return e;
-        k = (uint64_t*)ck.release(); c = (uint64_t*)cc.release();
+        AIX_TRY(ck.alloc(8 * v.n));
+        AIX_TRY(cc.alloc(8 * v.n));
+        AIX_TRY(hipMemcpyAsync(ck.p, v.k, 8 * v.n, hipMemcpyDeviceToDevice, s));
+        AIX_TRY(hipMemcpyAsync(cc.p, v.c, 8 * v.n, hipMemcpyDeviceToDevice, s));
+        AIX_TRY(hipStreamSynchronize(s));
+        res.adopt(ck, cc, v.n);
     }
-    e = filter_min_count(&k, &c, &n, min_count, s);
-    if (e != hipSuccess) { pool_free(k); pool_free(c); return e; }
-    *d_keys_out = k; *d_counts_out = c; *n_out = n;
+    AIX_TRY(filter_min_count(res, min_count, s));
+    out = std::move(res);
     return hipSuccess;
 }
 
 // the same for pairs in ANY order (repeated keys anywhere): sort by key + reduce-by-key. Kept for callers that cannot name their runs.
-hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64_t n, uint64_t min_count, uint64_t** d_keys_out, uint64_t** d_counts_out,
-                        uint64_t* n_out, hipStream_t s) {
-    *d_keys_out = nullptr; *d_counts_out = nullptr; *n_out = 0;
+hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64_t n, uint64_t min_count, DistinctRun& out, hipStream_t s) {
+    out.reset();
     if (n == 0) return hipSuccess;
     DevArr srt_k(s), srt_c(s), out_k(s), out_c(s), d_n(s), tmp(s);
-    hipError_t e = srt_k.alloc(8 * n);
-    if (e == hipSuccess) e = srt_c.alloc(8 * n);
-    size_t tb = 0;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, d_keys, (uint64_t*)srt_k.p, d_counts, (uint64_t*)srt_c.p, (size_t)n, 0u, 64u, s);
-    if (e == hipSuccess) e = tmp.alloc(tb);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, d_keys, (uint64_t*)srt_k.p, d_counts, (uint64_t*)srt_c.p, (size_t)n, 0u, 64u, s);
-    if (e == hipSuccess) e = out_k.alloc(8 * n);
-    if (e == hipSuccess) e = out_c.alloc(8 * n);
-    if (e == hipSuccess) e = d_n.alloc(8);
-    tb = 0;
-    if (e == hipSuccess) e = rocprim::reduce_by_key(nullptr, tb, (uint64_t*)srt_k.p, (uint64_t*)srt_c.p, (size_t)n, (uint64_t*)out_k.p, (uint64_t*)out_c.p, (uint64_t*)d_n.p, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), s);
-    if (e == hipSuccess) e = tmp.alloc(tb);
-    if (e == hipSuccess) e = rocprim::reduce_by_key(tmp.p, tb, (uint64_t*)srt_k.p, (uint64_t*)srt_c.p, (size_t)n, (uint64_t*)out_k.p, (uint64_t*)out_c.p, (uint64_t*)d_n.p, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), s);
+    AIX_TRY(srt_k.alloc(8 * n));
+    AIX_TRY(srt_c.alloc(8 * n));
+    AIX_TRY(sort_pairs(d_keys, (uint64_t*)srt_k.p, d_counts, (uint64_t*)srt_c.p, n, 64u, tmp, s));
+    AIX_TRY(out_k.alloc(8 * n));
+    AIX_TRY(out_c.alloc(8 * n));
+    AIX_TRY(d_n.alloc(8));
+    AIX_TRY(with_temp(tmp, [&](void* t, size_t& tb) {                       // tmp is live: its alloc waits for the sort, as before
+        return rocprim::reduce_by_key(t, tb, (uint64_t*)srt_k.p, (uint64_t*)srt_c.p, (size_t)n, (uint64_t*)out_k.p, (uint64_t*)out_c.p, (uint64_t*)d_n.p,
+                                      rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), s);
+    }));
     uint64_t merged = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&merged, d_n.p, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    uint64_t *k = (uint64_t*)out_k.release(), *c = (uint64_t*)out_c.release();
-    e = filter_min_count(&k, &c, &merged, min_count, s);
-    if (e != hipSuccess) { pool_free(k); pool_free(c); return e; }
-    *d_keys_out = k; *d_counts_out = c; *n_out = merged;
+    AIX_TRY(hipMemcpyAsync(&merged, d_n.p, 8, hipMemcpyDeviceToHost, s));
+    AIX_TRY(hipStreamSynchronize(s));
+    DistinctRun res;
+    res.adopt(out_k, out_c, merged);
+    AIX_TRY(filter_min_count(res, min_count, s));
+    out = std::move(res);
     return hipSuccess;
 }
 
@@ -365,9 +317,9 @@ hipError_t merge_counts(const uint64_t* d_keys, const uint64_t* d_counts, uint64
 // ---------------------------------------------------------------------------------------------
 // device-resident twin: the PLAIN buffer is already in HBM; the result stays in HBM inside an opaque object until the caller
 // has copied it into arrays of its own (two steps because the number of distinct k-mers is only known afterwards)
-struct aix_distinct { uint64_t* keys = nullptr; uint64_t* counts = nullptr; uint64_t n = 0; int device = 0; };
+struct aix_distinct { DistinctRun r; int device = 0; };
 
-// what the three producers share: device check, guard, the object, and `what` in front of a HIP error. run(keys, counts, n) fills the result.
+// what the three producers share: device check, guard, the object, and `what` in front of a HIP error. run(result) fills the result.
 template <typename F>
 static int make_distinct(int device, const char* what, aix_distinct_t** out, F&& run) {
     const int st = check_device(device);
@@ -376,7 +328,7 @@ static int make_distinct(int device, const char* what, aix_distinct_t** out, F&&
     aix_distinct* r = new (std::nothrow) aix_distinct();
     if (!r) return AIX_ERR_NOMEM;
     r->device = device;
-    const hipError_t e = run(&r->keys, &r->counts, &r->n);
+    const hipError_t e = run(r->r);
     if (e != hipSuccess) { delete r; set_last_error(std::string(what) + ": " + hipGetErrorString(e)); return AIX_ERR_HIP; }
     *out = r;
     return AIX_OK;
@@ -386,8 +338,8 @@ extern "C" int aix_count_distinct_dev(const char* d_plain, uint64_t len, int k, 
                                       aix_distinct_t** out) {
     if (!out || (len && !d_plain) || k < 1 || k > 31 || canon_mode < 0 || canon_mode > 2) return AIX_ERR_ARG;
     *out = nullptr;
-    return make_distinct(device, "count_distinct", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* n) {
-        return distinct_from_plain((const uint8_t*)d_plain, len, k, canon_mode, min_count ? min_count : 1, env_distinct_piece(), keys, counts, n, (hipStream_t)stream);
+    return make_distinct(device, "count_distinct", out, [&](DistinctRun& r) {
+        return distinct_from_plain((const uint8_t*)d_plain, len, k, canon_mode, min_count ? min_count : 1, env_distinct_piece(), r, (hipStream_t)stream);
     });
 }
 // K1 across GPUs: after the exchange a rank holds (key, count) pairs from every rank; equal keys are summed here
@@ -395,8 +347,8 @@ extern "C" int aix_merge_counts_dev(const uint64_t* d_keys, const uint64_t* d_co
                                     aix_distinct_t** out) {
     if (!out || (n && (!d_keys || !d_counts))) return AIX_ERR_ARG;
     *out = nullptr;
-    return make_distinct(device, "merge_counts", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* m) {
-        return merge_counts(d_keys, d_counts, n, min_count ? min_count : 1, keys, counts, m, (hipStream_t)stream);
+    return make_distinct(device, "merge_counts", out, [&](DistinctRun& r) {
+        return merge_counts(d_keys, d_counts, n, min_count ? min_count : 1, r, (hipStream_t)stream);
     });
 }
 // the same when the caller knows its runs: run r = entries [run_offsets[r], run_offsets[r + 1]), each sorted by key and free of repeats
@@ -407,21 +359,21 @@ extern "C" int aix_merge_runs_dev(const uint64_t* d_keys, const uint64_t* d_coun
     *out = nullptr;
     for (uint32_t r = 0; r < nruns; ++r) if (run_offsets[r + 1] < run_offsets[r]) return AIX_ERR_ARG;
     if (run_offsets[nruns] > run_offsets[0] && (!d_keys || !d_counts)) return AIX_ERR_ARG;
-    return make_distinct(device, "merge_runs", out, [&](uint64_t** keys, uint64_t** counts, uint64_t* m) {
-        return merge_runs(d_keys, d_counts, run_offsets, nruns, min_count ? min_count : 1, keys, counts, m, (hipStream_t)stream);
+    return make_distinct(device, "merge_runs", out, [&](DistinctRun& r) {
+        return merge_runs(d_keys, d_counts, run_offsets, nruns, min_count ? min_count : 1, r, (hipStream_t)stream);
     });
 }
 extern "C" int aix_distinct_size(const aix_distinct_t* r, uint64_t* n_out) {
     if (!r || !n_out) return AIX_ERR_ARG;
-    *n_out = r->n;
+    *n_out = r->r.n;
     return AIX_OK;
 }
 extern "C" int aix_distinct_copy_dev(const aix_distinct_t* r, uint64_t* d_keys, uint64_t* d_counts, void* stream) {
-    if (!r || (r->n && (!d_keys || !d_counts))) return AIX_ERR_ARG;
+    if (!r || (r->r.n && (!d_keys || !d_counts))) return AIX_ERR_ARG;
     DevGuard g(r->device);
-    if (r->n) {
-        HIPCHK(hipMemcpyAsync(d_keys, r->keys, 8 * r->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        HIPCHK(hipMemcpyAsync(d_counts, r->counts, 8 * r->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (r->r.n) {
+        HIPCHK(hipMemcpyAsync(d_keys, r->r.k, 8 * r->r.n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIPCHK(hipMemcpyAsync(d_counts, r->r.c, 8 * r->r.n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     }
     return AIX_OK;
@@ -429,7 +381,5 @@ extern "C" int aix_distinct_copy_dev(const aix_distinct_t* r, uint64_t* d_keys, 
 extern "C" void aix_distinct_free(aix_distinct_t* r) {
     if (!r) return;
     DevGuard g(r->device);
-    if (r->keys) pool_free(r->keys);
-    if (r->counts) pool_free(r->counts);
-    delete r;
+    delete r;                                                   // a plain free of the two blocks: the copies above have synchronised
 }

@@ -1,11 +1,14 @@
 // aix_msd.hpp — the two-level most-significant-digit partition shared by K1 (aix_k1.hip: distinct k-mers) and A2
 // (aix_a2msd.hip: positions fill): 64-bit elements are split by their top 11 bits into chunk lists (level 1), every level-1
 // partition is split again by the next D2 bits into exactly sized, contiguous buckets (level 2: count, scan, scatter).
-// The final per-bucket stage differs (hash aggregation for K1, counting sort + rank by offset for A2) and lives with its caller.
+// The kernels of the two levels come first; the host half follows them: MsdPlan (geometry, the sizes of the two rocPRIM temporaries and
+// the layout of the workspace's common head) and msd_partition, which enqueues split -> directory sort -> count -> scan -> scatter.
+// The final per-bucket stage differs (hash aggregation for K1, counting sort + rank by offset for A2) and lives with its caller, as do
+// the tail of the workspace behind the head, the choice of D2 and the test hooks.
 #pragma once
 #include <cstdint>
 
-#include "aix_internal.hpp"
+#include "aix_hostkit.hpp"
 
 namespace aix {
 
@@ -268,5 +271,74 @@ struct K1Desc {
     const uint16_t* dir_cnt;
     __host__ __device__ uint64_t operator()(uint32_t i) const { return (uint64_t)i | ((uint64_t)dir_cnt[i] << 32); }
 };
+
+// ---------------------------------------------------------------------------------------------
+// host side: the plan of a partition of nwin elements into K1_P x nb2 buckets, and the chain of the two levels
+// ---------------------------------------------------------------------------------------------
+static inline uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
+
+// One workspace block per call; its head is the same for both callers:
+//     256 B of flags (word 0: a chunk id left its region) | dir_part | dir_cnt | spart | sdesc | sort / scan temp | bucket_cnt | bucket_base
+// (bucket_cnt and bucket_base hold nbuckets + 1 words). The caller's own regions start at head_bytes; `parts` (8 B x chunks()) is one of them.
+struct MsdPlan {
+    uint64_t ntiles;
+    unsigned grid;
+    uint32_t region, cap, nb2, nbuckets;                         // chunks per workgroup of the split, chunks in all, level-2 digits, buckets
+    size_t sort_tmp, scan_tmp;
+    uint64_t o_dirp, o_dirc, o_spart, o_sdesc, o_tmp, o_bcnt, o_bbase, head_bytes;
+    MsdPlan(uint64_t nwin, uint32_t nb2_, uint32_t region_override /* 0: sized for any input */, hipStream_t s) : nb2(nb2_) {
+        ntiles = (nwin + K1_TILE - 1) / K1_TILE;
+        grid = (unsigned)std::min<uint64_t>(ntiles, K1_MAXGRID);
+        region = region_override ? region_override : (uint32_t)((ntiles + grid - 1) / grid * (K1_TILE / K1_CH) + K1_P);
+        cap = grid * region;
+        nbuckets = (uint32_t)K1_P * nb2;
+        sort_tmp = scan_tmp = 0;
+        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{nullptr});
+        (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (const uint16_t*)nullptr, (uint16_t*)nullptr, vals, (uint64_t*)nullptr, (size_t)cap, 0u, 12u, s);
+        (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
+        o_dirp = 256;
+        o_dirc = o_dirp + up256(2ull * cap);
+        o_spart = o_dirc + up256(2ull * cap);
+        o_sdesc = o_spart + up256(2ull * cap);
+        o_tmp = o_sdesc + up256(8ull * cap);
+        o_bcnt = o_tmp + up256(std::max(sort_tmp, scan_tmp));
+        o_bbase = o_bcnt + up256(4ull * (nbuckets + 1));
+        head_bytes = o_bbase + up256(4ull * (nbuckets + 1));
+    }
+    uint64_t parts_bytes() const { return 8ull * cap * K1_CH; }
+    uint32_t* bucket_base(uint8_t* w) const { return (uint32_t*)(w + o_bbase); }
+    // out = exclusive prefix sums of nbuckets + 1 words, in the head's temporary
+    hipError_t scan(uint8_t* w, uint32_t* in, uint32_t* out, hipStream_t s) const {
+        size_t tb = scan_tmp;
+        return rocprim::exclusive_scan((void*)(w + o_tmp), tb, in, out, 0u, (size_t)nbuckets + 1, rocprim::plus<uint32_t>(), s);
+    }
+};
+
+// Enqueues the two levels on `s`: the elements of `src` leave as remainders (their low s2 bits) in out[bucket_base[b] .. bucket_base[b + 1])
+// for bucket b = the bits above s2; s1 = s2 + log2(nb2) is where the top 11 bits start. `parts` takes the chunk lists of level 1 and is
+// free again afterwards. Word 0 of w is set when a chunk id left its region: the caller reads it back with its own flags.
+template <class Src, class Rem>
+static hipError_t msd_partition(const MsdPlan& p, uint8_t* w, const Src& src, uint32_t s1, uint32_t s2, uint64_t* parts, Rem* out, hipStream_t s) {
+    uint16_t* dir_part = (uint16_t*)(w + p.o_dirp);
+    uint16_t* dir_cnt = (uint16_t*)(w + p.o_dirc);
+    uint16_t* spart = (uint16_t*)(w + p.o_spart);
+    uint64_t* sdesc = (uint64_t*)(w + p.o_sdesc);
+    uint32_t* bucket_cnt = (uint32_t*)(w + p.o_bcnt);
+    AIX_TRY(hipFuncSetAttribute((const void*)k_k1_split<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS));
+    AIX_TRY(hipFuncSetAttribute((const void*)k_k1_scatter<Rem>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_TILE_LDS));
+    AIX_TRY(hipMemsetAsync(w, 0, 256, s));
+    AIX_TRY(hipMemsetD16Async((hipDeviceptr_t)dir_part, (unsigned short)K1_P, p.cap, s));      // "no partition": sorts behind every real one
+    AIX_TRY(hipMemsetD16Async((hipDeviceptr_t)dir_cnt, (unsigned short)K1_CH, p.cap, s));      // chunks are full unless the split says otherwise
+    AIX_TRY(hipMemsetAsync(bucket_cnt, 0, 4ull * (p.nbuckets + 1), s));
+    AIX_TRY_LAUNCH(k_k1_split<Src>, dim3(p.grid), dim3(K1_TB), K1_TILE_LDS, s, src, s1, p.ntiles, p.region, dir_part, dir_cnt, parts, (uint32_t*)w);
+    auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), K1Desc{dir_cnt});
+    size_t tb = p.sort_tmp;
+    AIX_TRY(rocprim::radix_sort_pairs((void*)(w + p.o_tmp), tb, (const uint16_t*)dir_part, spart, vals, sdesc, (size_t)p.cap, 0u, 12u, s));
+    AIX_TRY_LAUNCH(k_k1_count, dim3(K1_P), dim3(K1_TB), 0, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, p.cap, s2, p.nb2, bucket_cnt);
+    AIX_TRY(p.scan(w, bucket_cnt, p.bucket_base(w), s));
+    AIX_TRY_LAUNCH(k_k1_scatter<Rem>, dim3(K1_P), dim3(K1_TB), K1_TILE_LDS, s, (const uint64_t*)parts, (const uint16_t*)spart, (const uint64_t*)sdesc, p.cap, s2, p.nb2,
+                   (const uint32_t*)p.bucket_base(w), out);
+    return hipSuccess;
+}
 
 }  // namespace aix

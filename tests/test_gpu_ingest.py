@@ -201,6 +201,43 @@ def test_count_distinct_file_pieces_and_parts(gold, monkeypatch, tmp_path):
         assert np.array_equal(keys, okeys) and np.array_equal(counts, ocnt), (k, canon)
 
 
+def fallback_pieces_input():
+    """PLAIN lines for pieces of 60 000 windows at k = 23: 2 500 ordinary 47-base reads (two pieces the MSD path answers), 12 000 lines
+    that share their first ten bases (a bucket is the top 15 bits of the code at this size, so every piece of ~2 500 such lines puts more
+    than 1 536 distinct remainders into one bucket and falls back to the radix-sort path), then 500 ordinary reads again."""
+    rng = np.random.default_rng(17)
+    asc = synth.genome_ascii(77, 400_000)
+    rows = synth.reads_plain(43, asc, 3000, 150).reshape(-1, 151)
+    ordinary = [bytes(r[:47]) + b"\n" for r in rows]
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    narrow = [b"AAAAAAAAAA" + bytes(acgt[rng.integers(0, 4, 13)]) + b"\n" for _ in range(12_000)]
+    return b"".join(ordinary[:2500] + narrow + ordinary[2500:])
+
+
+def test_count_distinct_merges_pieces_that_fell_back_with_pieces_that_did_not(monkeypatch):
+    """The accumulator of the distinct-k-mer pieces when the back end changes from piece to piece: MSD pieces first, then several pieces
+    in a row that fall back to the radix sort (the scratch is kept between them), then a mixed piece. Host buffer and device buffer
+    (aix_distinct_t) against the oracle and against the radix-sort path alone, min_count 1 and 2."""
+    import torch
+    buf = fallback_pieces_input()
+    monkeypatch.setenv("AIX_DISTINCT_PIECE", "60000")
+    t = torch.frombuffer(bytearray(buf), dtype=torch.uint8).cuda()
+    for mc in (1, 2):
+        okeys, ocnt = O.count_distinct(b">r\n" + buf.replace(b"\n", b"\n>r\n"), 23, _lib.CANON_NONE, mc)
+        ocnt = ocnt.astype(np.uint64)
+        assert mc > 1 or okeys.shape[0] > 12_000
+        monkeypatch.delenv("AIX_K1_ROCPRIM", raising=False)
+        keys, counts = counting.count_distinct(buf, 23, _lib.CANON_NONE, mc, fmt=_lib.FMT_PLAIN)
+        assert np.array_equal(keys, okeys) and np.array_equal(counts, ocnt), mc
+        tk, tc = counting.count_distinct_t(t, 23, _lib.CANON_NONE, mc)
+        assert np.array_equal(tk.cpu().numpy().view(np.uint64), okeys) and np.array_equal(tc.cpu().numpy().view(np.uint64), ocnt), mc
+        monkeypatch.setenv("AIX_K1_ROCPRIM", "1")
+        rkeys, rcounts = counting.count_distinct(buf, 23, _lib.CANON_NONE, mc, fmt=_lib.FMT_PLAIN)
+        assert np.array_equal(rkeys, keys) and np.array_equal(rcounts, counts), mc
+        rk, rc = counting.count_distinct_t(t, 23, _lib.CANON_NONE, mc)
+        assert torch.equal(rk, tk) and torch.equal(rc, tc), mc
+
+
 def test_merge_runs_equals_sort_and_reduce():
     """aix_merge_runs_dev (tree of two-way merges with summation) against numpy on runs of every shape: empty runs, one run, runs that
     share all / none of their keys, a pair split across a tile boundary of the merge kernel (2 048 entries), 64-bit counts."""
