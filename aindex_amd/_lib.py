@@ -196,6 +196,10 @@ SIGNATURES = {
     "aix_scaffold_fill_layout_dev": (i32, [u64, vp, vp, vp, u64, vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, u64] + [vp] * 6 + [C.POINTER(u64)] * 2 + [vp]),
     "aix_scaffold_fill_emit_dev": (i32, [u64, vp, vp, u32, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp]),
     "aix_scaffold_fill": (i32, [u64, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, u32, u32, u32, u32] + [C.POINTER(u64)] * 3 + [C.POINTER(vp)] * 14),
+    "aix_pile_place_dev": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, u32, u32] + [vp] * 7 + [C.POINTER(u64)] * 2 + [vp]),
+    "aix_pileup_dev": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
+    "aix_pile_call_dev": (i32, [u64, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u64)] + [vp] * 7 + [u64, C.POINTER(u64), vp, vp, vp]),
+    "aix_pileup": (i32, [vp, u32, vp, vp, u64, u32, u32] + [C.POINTER(u64)] * 3 + [C.POINTER(vp)] * 12),
     "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
     "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

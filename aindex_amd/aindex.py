@@ -81,6 +81,20 @@ def format_gfa(unitigs: dict, links: dict) -> Iterator[str]:
             yield f"L\tu{i}\t+\tu{i}\t+\t22M"
 
 
+def format_vcf(variants, contig_lengths=None) -> Iterator[str]:
+    """The lines (no line ends) of a VCF 4.2 file of the variant sites of AIndex.get_variants, [(contig, pos, ref, alt, ref_count,
+    alt_count, depth)]: the header (one ##contig line per entry of contig_lengths, when given), then per site c{id}, the 1-based
+    position, '.', REF, ALT, '.', '.', and DP={depth};AD={ref_count},{alt_count}. Host only."""
+    yield "##fileformat=VCFv4.2"
+    for i, ln in enumerate(contig_lengths if contig_lengths is not None else ()):
+        yield f"##contig=<ID=c{i},length={ln}>"
+    yield '##INFO=<ID=DP,Number=1,Type=Integer,Description="Reads piled on the base">'
+    yield '##INFO=<ID=AD,Number=R,Type=Integer,Description="Reads showing the contig base and the alternative base">'
+    yield "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"
+    for c, pos, ref, alt, rn, an, dp in variants:
+        yield f"c{c}\t{pos + 1}\t.\t{ref}\t{alt}\t.\t.\tDP={dp};AD={rn},{an}"
+
+
 def format_gfa_paths(unitigs: dict, links: dict, support, thread: dict, names: List[str]) -> Iterator[str]:
     """format_gfa with the read evidence of Index.seq_thread: every L line carries RC:i:{support of the link} (the closing link of a
     circular unitig: the number of times a step wound round it), and one P line per maximal stretch of linked steps of every sequence —
@@ -749,6 +763,113 @@ class AIndex:
                 if ln - 22 < min_kmers:
                     continue
                 f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
+                written += 1
+        return written
+
+    # ---- pile-up (Index.pile_place_t .. pile_call_t; aix_pileup.hip) -------------------------------------
+    def _pile(self, reads, graph, cutoff: int, tip_max_kmers: int, bubble_max_kmers: int, rounds: int, max_gap: int, extend: int, want_places: bool = False):
+        """(graph, counts int32[4 B] on the device, stats, per-read placement rows | None): the cleaned graph built once (or `graph`, what
+        Index.thread_graph_t returned), `reads` threaded, placed and piled in batches of RESOLVE_BATCH_BYTES into one counts array"""
+        self._req()
+        import torch
+        ix = self._wrapper._need23()
+        if graph is None:
+            graph = ix.thread_graph_t(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
+        dev = graph["node"].device
+        counts = torch.zeros(4 * graph["bases"].numel(), dtype=torch.int32, device=dev)
+        stats, rows = [0, 0, 0], []
+        reads = list(reads)
+        batch, size = [], 0
+        for i, r in enumerate(reads):
+            batch.append(r)
+            size += len(r)
+            if size >= self.RESOLVE_BATCH_BYTES or i + 1 == len(reads):
+                from .engine import _ragged
+                data, offs = _ragged(batch)
+                st = torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev)
+                so = torch.from_numpy(offs.astype(np.int64)).to(dev)
+                places = ix.pile_place_t(graph, so, ix.seq_thread_t(graph, st, so), max_gap, extend)
+                got = ix.pileup_t(graph, st, so, places, counts)
+                stats = [a + b for a, b in zip(stats, got["stats"])]
+                if want_places:
+                    p = ix._graph_to_host({k: places[k] for k in ix.PLACE_KEYS})
+                    mism = ix._graph_to_host({"m": got["place_mism"]})["m"].tolist()
+                    spo = p["seq_place_off"].tolist()
+                    flat = list(zip(p["place_unitig"].tolist(), ["+-"[f & 1] for f in p["place_flag"].tolist()], p["place_pos"].tolist(), p["place_q0"].tolist(),
+                                    p["place_len"].tolist(), mism))
+                    rows += [flat[spo[j]:spo[j + 1]] for j in range(len(batch))]
+                batch, size = [], 0
+        return graph, counts, stats, rows if want_places else None
+
+    def get_read_placements(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                            extend: int = 22) -> List[List[tuple]]:
+        """Per read its placements on the contigs of get_contigs (or on `graph`, what Index.thread_graph_t returned):
+        [(contig, '+' | '-', contig_pos, read_from, length, mismatches)] — `length` read bases from read_from on lie on the contig from
+        contig_pos on, forwards (+) or reverse-complemented (-); steps on one diagonal at most max_gap windows apart are one placement,
+        grown by at most `extend` bases at either end."""
+        return self._pile(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, True)[3]
+
+    def get_pileup(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                   extend: int = 22) -> dict:
+        """The reads piled onto the contigs: offsets uint64[U + 1], bases uint8[B], counts uint32[B, 4] (reads showing A, C, G, T at every
+        contig base), depth_sum uint64[U], uncovered uint32[U] (bases no read covers) and stats (bases counted, other bytes, mismatches)."""
+        graph, counts, stats, _ = self._pile(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend)
+        ix = self._wrapper._need23()
+        called = ix.pile_call_t(graph, counts)
+        out = ix._graph_to_host({"offsets": graph["offsets"], "bases": graph["bases"], "counts": counts, "depth_sum": called["depth_sum"], "uncovered": called["uncovered"]})
+        out["counts"] = out["counts"].reshape(-1, 4)
+        out["stats"] = stats
+        return out
+
+    def _called(self, reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, min_alt_count, min_alt_permille):
+        graph, counts, _, _ = self._pile(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend)
+        ix = self._wrapper._need23()
+        called = ix.pile_call_t(graph, counts, min_depth, min_major_permille, min_alt_count, min_alt_permille)
+        return ix._graph_to_host({k: graph[k] for k in ix.GRAPH_KEYS}), ix._graph_to_host(called)
+
+    def get_variants(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                     extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200) -> List[tuple]:
+        """[(contig, pos, ref, alt, ref_count, alt_count, depth)] in contig order: the contig bases where at least min_depth reads are piled
+        and another base than the contig's is shown by min_alt_count reads or more, min_alt_permille of the depth or more. pos is 0-based."""
+        _, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, 700, min_alt_count, min_alt_permille)
+        return list(zip(c["var_unitig"].tolist(), c["var_pos"].tolist(), [chr(x) for x in c["var_ref"].tolist()], [chr(x) for x in c["var_alt"].tolist()],
+                        c["var_ref_count"].tolist(), c["var_alt_count"].tolist(), c["var_depth"].tolist()))
+
+    def write_variants_vcf(self, path: str, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
+                           max_gap: int = 46, extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200) -> int:
+        """VCF of get_variants (format_vcf): c{id}, the 1-based position, REF, ALT, DP= and AD=ref,alt; returns the number of records written."""
+        g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, 700, min_alt_count, min_alt_permille)
+        rows = zip(c["var_unitig"].tolist(), c["var_pos"].tolist(), [chr(x) for x in c["var_ref"].tolist()], [chr(x) for x in c["var_alt"].tolist()],
+                   c["var_ref_count"].tolist(), c["var_alt_count"].tolist(), c["var_depth"].tolist())
+        written = 0
+        with open(path, "w") as f:
+            for line in format_vcf(rows, np.diff(g["offsets"].astype(np.int64)).tolist()):
+                written += line[0] != "#"
+                f.write(line + "\n")
+        return written
+
+    def get_polished_contigs(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                             extend: int = 22, min_depth: int = 8, min_major_permille: int = 700, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
+        """get_contigs with every base replaced where at least min_depth reads are piled and min_major_permille of them or more show one
+        other base: [(sequence, tf_sum, circular)]. An end product: the overlaps between linked contigs are not kept consistent."""
+        g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, 3, 200)
+        off, text = g["offsets"].tolist(), c["polished"].tobytes().decode("ascii")
+        return [(text[off[i]:off[i + 1]], s, bool(ci)) for i, (s, ci) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
+                if off[i + 1] - off[i] - 22 >= min_kmers]
+
+    def write_polished_contigs(self, path: str, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
+                               max_gap: int = 46, extend: int = 22, min_depth: int = 8, min_major_permille: int = 700, min_kmers: int = 1) -> int:
+        """FASTA of get_polished_contigs: the header of write_contigs plus PC:i:{bases changed}; returns the number of records written."""
+        g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, 3, 200)
+        off, text, old = g["offsets"].tolist(), c["polished"].tobytes().decode("ascii"), g["bases"]
+        written = 0
+        with open(path, "w") as f:
+            for i, (s, ci) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
+                ln = off[i + 1] - off[i]
+                if ln - 22 < min_kmers:
+                    continue
+                changed = int((c["polished"][off[i]:off[i + 1]] != old[off[i]:off[i + 1]]).sum())
+                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if ci else ''} PC:i:{changed}\n{text[off[i]:off[i + 1]]}\n")
                 written += 1
         return written
 

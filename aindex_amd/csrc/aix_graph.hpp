@@ -1,7 +1,8 @@
 // aix_graph.hpp — private to the library: what the graph files share. The graph layer is everything that works on arrays over the 2 U
 // ends of unitigs or contigs: the links half of aix_unitigs.hip, aix_graphclean.hip, aix_seqthread.hip, aix_graphresolve.hip,
-// aix_scaffold.hip and aix_gapclose.hip. Shared here, and only what at least two of them use: the two constants, the counters holder of a
-// call, the predicates the validate kernels repeat, a handful of device helpers, and the kernel that writes the bases of scaffolds.
+// aix_scaffold.hip and aix_gapclose.hip, and aix_pileup.hip on the contigs themselves. Shared here, and only what at least two of them
+// use: the two constants, the counters holder of a call, the predicates the validate kernels repeat, a handful of device helpers, and
+// the kernel that writes the bases of scaffolds.
 //
 // THE RULE OF A VALIDATE KERNEL: it runs on arrays that may hold anything, so a value is compared with its bound before it is used as an
 // index, and the predicates below read nothing themselves: they take the loaded words. (join_dual_ok is the one that gathers, and it
@@ -14,8 +15,6 @@
 //   - k_gp_search: one wave per join with its states in LDS; nothing else in the layer has that shape.
 //   - the ranking and cycle kernels of the scaffold layout: the note in aix_chains.hpp covers them (a third state layout: next end, 64-bit
 //     distance in bases and a hop count).
-//   - the gallop of st_last_le (aix_seqthread.hip): its windows ascend with the lane, so it starts next to the answer; its tail is the
-//     bisection below.
 #pragma once
 #include "aix_chains.hpp"
 
@@ -87,6 +86,19 @@ __device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ a, uint
         if (a[mid] <= key) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// the last j in [from, n) with a[j] <= key; a[from] <= key < a[n]. A gallop from `from`, then the bisection above: for keys that ascend
+// with the lane, so that the search starts next to the answer (the windows of aix_seqthread.hip, the read bases of aix_pileup.hip).
+__device__ __forceinline__ uint64_t gallop_last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t from, uint64_t key) {
+    uint64_t lo = from, step = 1, hi;
+    for (;;) {
+        hi = n - lo > step ? lo + step : n;
+        if (hi == n || a[hi] > key) break;
+        lo = hi;
+        step <<= 1;
+    }
+    return last_le(a, lo, hi, key);
 }
 
 // the 'N' run written for an estimated gap

@@ -148,18 +148,6 @@ __global__ void __launch_bounds__(kCB) k_st_windows(const uint64_t* __restrict__
     count_add(bad, &ctr->bad);
 }
 
-// the last j in [from, n) with a[j] <= key; a[from] <= key < a[n]. A gallop from `from`, then the bisection of aix_graph.hpp.
-__device__ __forceinline__ uint64_t st_last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t from, uint64_t key) {
-    uint64_t lo = from, step = 1, hi;
-    for (;;) {
-        hi = n - lo > step ? lo + step : n;
-        if (hi == n || a[hi] > key) break;
-        lo = hi;
-        step <<= 1;
-    }
-    return last_le(a, lo, hi, key);
-}
-
 // Pass 1. word[i]: the node of window i with bit 0 = the strand the window traverses its unitig in (flag bit 0 xor "the window is the
 // reverse complement of the stored key"), kStDead without a node. qv[i]: the window's offset in its sequence.
 __global__ void __launch_bounds__(kCB) k_st_probe(const IndexDev ix_, const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ offs,
@@ -174,7 +162,7 @@ __global__ void __launch_bounds__(kCB) k_st_probe(const IndexDev ix_, const uint
         const uint64_t s0 = wave_count_le(woff, M + 1, base) - 1;            // woff[0] == 0: the last sequence that starts at or before window `base`
         uint64_t w0 = 0, w1 = 0, w2 = 0, q = 0;
         if (in) {
-            const uint64_t sq = st_last_le(woff, M, s0, i);                  // woff[M] == W > i; a sequence without windows is never the last one <= i
+            const uint64_t sq = gallop_last_le(woff, M, s0, i);                  // woff[M] == W > i; a sequence without windows is never the last one <= i
             q = i - woff[sq];
             load23(seqs + offs[sq] + q, w0, w1, w2);
         }

@@ -1430,6 +1430,118 @@ class Index:
         out.update(n_fmembers=mf, total_bases=total, total=pt, counts=[int(x) for x in out["counts"]])
         return out
 
+    # ---- pile-up (aix_pileup.hip) ----------------------------------------------------------------------
+    PLACE_KEYS = ("seq_place_off", "place_unitig", "place_flag", "place_pos", "place_q0", "place_len", "place_steps")
+    PLACE_DTYPES = (np.uint64, np.uint32, np.uint8, np.uint32, np.uint32, np.uint32, np.uint32)
+    VAR_KEYS = ("var_unitig", "var_pos", "var_ref", "var_alt", "var_ref_count", "var_alt_count", "var_depth")
+    VAR_DTYPES = (np.uint32, np.uint32, np.uint8, np.uint8, np.uint32, np.uint32, np.uint32)
+
+    def pile_place_t(self, graph: dict, offs_t, steps, max_gap: int = 46, extend: int = 22) -> dict:
+        """The steps of M threaded sequences merged into placements, on torch's current stream: `steps` is what seq_thread_t returned for
+        `graph` and the offsets int64[M + 1] of the same batch. -> seq_place_off int64[M + 1], place_unitig int32, place_flag uint8 (bit 0:
+        the read lies backwards), place_pos int32 (the leftmost contig base, local), place_q0 int32 (the first read base), place_len int32,
+        place_steps int32 — bit patterns of the unsigned fields — and the ints n_place, n_circular_steps."""
+        import torch
+        off = graph["offsets"]
+        sso, su, sp, sf, qf, ql = steps[:6]
+        for t in (off, offs_t, sso, su, sp, sf, qf, ql):
+            self._chk_dev(t)
+        m, n, u = offs_t.numel() - 1, su.numel(), off.numel() - 1
+        if m < 0 or u < 0 or sso.numel() != m + 1 or any(t.numel() != n for t in (sp, sf, qf, ql)):
+            raise ValueError("the step arrays hold T entries each, seq_step_off M + 1")
+        dev = off.device
+        spo = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        types = (torch.int32, torch.uint8, torch.int32, torch.int32, torch.int32, torch.int32)
+        outs = [torch.empty(n, dtype=ty, device=dev) for ty in types]
+        got, circ = C.c_uint64(), C.c_uint64()
+        p = lambda t: vp(t.data_ptr()) if t.numel() else None
+        with torch.cuda.device(self.device):
+            check(lib().aix_pile_place_dev(m, p(offs_t), p(sso), n, p(su), p(sp), p(sf), p(qf), p(ql), u, vp(off.data_ptr()), max_gap, extend, vp(spo.data_ptr()),
+                                           *[p(o) for o in outs], C.byref(got), C.byref(circ), _stream_ptr(self.device)), "aix_pile_place_dev")
+        out = dict(zip(self.PLACE_KEYS, [spo] + [o[:got.value] for o in outs]))
+        out.update(n_place=got.value, n_circular_steps=circ.value)
+        return out
+
+    def pileup_t(self, graph: dict, seqs_t, offs_t, places: dict, counts=None) -> dict:
+        """The read bases of `places` (what pile_place_t returned for this batch) counted at the contig bases of `graph`, on torch's
+        current stream. counts: int32[4 B] (or [B, 4], contiguous), cell 4 g + c = the reads showing base c (A, C, G, T) at global base g;
+        accumulated across calls, a zeroed one is made when None. -> counts, place_mism int32[R] (the counted bases of a placement that
+        differ from the contig) and stats (ints: bases counted, other bytes, mismatches of this call)."""
+        import torch
+        off, bases = graph["offsets"], graph["bases"]
+        arrs = [places[k] for k in self.PLACE_KEYS[:6]]
+        for t in (off, bases, seqs_t, offs_t, *arrs):
+            self._chk_dev(t)
+        m, r, u, b = offs_t.numel() - 1, arrs[1].numel(), off.numel() - 1, bases.numel()
+        if m < 0 or u < 0 or arrs[0].numel() != m + 1 or any(t.numel() != r for t in arrs[2:]):
+            raise ValueError("the placement arrays hold R entries each, seq_place_off M + 1")
+        dev = off.device
+        if counts is None:
+            counts = torch.zeros(4 * b, dtype=torch.int32, device=dev)
+        self._chk_dev(counts)
+        if counts.numel() != 4 * b or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError("counts must be contiguous int32 with four cells per contig base")
+        mism = torch.empty(r, dtype=torch.int32, device=dev)
+        stats = torch.empty(3, dtype=torch.int64, device=dev)
+        p = lambda t: vp(t.data_ptr()) if t.numel() else None
+        with torch.cuda.device(self.device):
+            check(lib().aix_pileup_dev(p(seqs_t), p(offs_t), m, p(arrs[0]), r, *[p(t) for t in arrs[1:]], u, vp(off.data_ptr()), p(bases), p(counts), p(mism),
+                                       vp(stats.data_ptr()), _stream_ptr(self.device)), "aix_pileup_dev")
+        return {"counts": counts, "place_mism": mism, "stats": [int(x) for x in stats.tolist()]}
+
+    def pile_call_t(self, graph: dict, counts, min_depth: int = 8, min_major_permille: int = 700, min_alt_count: int = 3, min_alt_permille: int = 200,
+                    cap_hint: int = 0) -> dict:
+        """The counts of pileup_t read out, on torch's current stream: polished uint8[B] (the contig bases, replaced where a clear majority
+        of at least min_depth reads disagrees) and the int n_changed; the variant sites in ascending order — var_unitig, var_pos int32,
+        var_ref, var_alt uint8 (ASCII), var_ref_count, var_alt_count, var_depth int32 — and the int total; depth_sum int64[U] and uncovered
+        int32[U]. cap_hint: the variants to make room for at once; below the total the call runs twice."""
+        import torch
+        off, bases = graph["offsets"], graph["bases"]
+        for t in (off, bases, counts):
+            self._chk_dev(t)
+        u, b = off.numel() - 1, bases.numel()
+        if u < 0 or counts.numel() != 4 * b or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError("counts must be contiguous int32 with four cells per contig base")
+        dev = off.device
+        polished = torch.empty(b, dtype=torch.uint8, device=dev)
+        dsum = torch.empty(u, dtype=torch.int64, device=dev)
+        unc = torch.empty(u, dtype=torch.int32, device=dev)
+        changed, total = C.c_uint64(), C.c_uint64()
+        types = (torch.int32, torch.int32, torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32)
+        p = lambda t: vp(t.data_ptr()) if t.numel() else None
+        with torch.cuda.device(self.device):
+            cap = max(int(cap_hint), 0)
+            while True:
+                outs = [torch.empty(max(cap, 1), dtype=ty, device=dev) for ty in types]
+                check(lib().aix_pile_call_dev(u, vp(off.data_ptr()), p(bases), p(counts), min_depth, min_major_permille, min_alt_count, min_alt_permille, p(polished),
+                                              C.byref(changed), *[vp(o.data_ptr()) if cap else None for o in outs], cap, C.byref(total), p(dsum), p(unc),
+                                              _stream_ptr(self.device)), "aix_pile_call_dev")
+                if total.value <= cap:
+                    break
+                cap = total.value
+        out = dict(zip(self.VAR_KEYS, [o[:total.value] for o in outs]))
+        out.update(polished=polished, n_changed=changed.value, total=total.value, depth_sum=dsum, uncovered=unc)
+        return out
+
+    def pileup(self, seqs: Sequence, cutoff: int = 0, max_gap: int = 46, extend: int = 22) -> dict:
+        """pile_place_t and pileup_t through host memory, on the unitig graph at `cutoff` (built inside, the sequences threaded through
+        it): numpy arrays offsets uint64[U + 1], bases uint8[B], counts uint32[4 B] (counted from zero), the seven placement arrays,
+        place_mism uint32[R], stats uint64[3], and the ints U, n_place, n_circular_steps."""
+        data, offs = _ragged(seqs)
+        m = len(seqs)
+        ps = [vp() for _ in range(12)]
+        n = [C.c_uint64() for _ in range(3)]
+        check(lib().aix_pileup(self._h, cutoff, _np_ptr(data) if data.shape[0] else None, _np_ptr(offs), m, max_gap, extend, *[C.byref(x) for x in n],
+                               *[C.byref(p) for p in ps]), "aix_pileup")
+        u, r, circ = (x.value for x in n)
+        out = {"offsets": self._take(ps[0], u + 1, np.uint64)}
+        b = int(out["offsets"][u])
+        out.update(bases=self._take(ps[1], b, np.uint8), counts=self._take(ps[2], 4 * b, np.uint32), seq_place_off=self._take(ps[3], m + 1, np.uint64))
+        for i in range(1, 7):
+            out[self.PLACE_KEYS[i]] = self._take(ps[3 + i], r, self.PLACE_DTYPES[i])
+        out.update(place_mism=self._take(ps[10], r, np.uint32), stats=self._take(ps[11], 3, np.uint64), U=u, n_place=r, n_circular_steps=circ)
+        return out
+
     def _device_ctx(self):
         """the handle-less calls run on the current device: make it this index's when torch is in the process (it owns the current device then)"""
         import contextlib

@@ -1082,6 +1082,93 @@ int aix_scaffold_fill(uint64_t U, const uint64_t* offsets, const uint8_t* bases,
                       uint64_t** counts_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Pile-up: the reads laid back over the contigs they thread through — per-base A/C/G/T counts, variant sites, a polished consensus.
+ * (The reference has no counterpart; the notation is that of the threading block. tests/pileup_ref.py restates this block.)
+ *
+ * L_u = offsets[u + 1] - offsets[u] and m_u = L_u - 22; B = offsets[U]; global base g of contig u at local position x is offsets[u] + x.
+ * Sequences as aix_seq_thread_dev takes them. The three device calls take no index handle: they work on device arrays of the current
+ * device, are asynchronous on `stream` and return after their work on it has completed. Every call validates first and writes second: a
+ * violation is AIX_ERR_ARG with no output (and no in/out array) touched. Every index read from an input array is compared with its bound
+ * before it is used. U > 2^31 - 4 is AIX_ERR_UNSUPPORTED, a NULL pointer where one is needed AIX_ERR_ARG, decided before anything is
+ * allocated or launched. In all three, offsets start at 0 and ascend by at least 23, and sequence offsets ascend by less than 2^32.
+ * Scratch comes from the pool and goes back on every path; see DESIGN 5p. Integer only; no result depends on the launch geometry.
+ *
+ * 1. aix_pile_place_dev: steps become placements. Inputs M and d_offs[M + 1] of the threaded batch; d_seq_step_off[M + 1], T and
+ *    step_unitig / step_pos / step_flag / q_first / q_last [T] as aix_seq_thread_dev wrote them (step_link is not read); U and
+ *    offsets[U + 1]; max_gap and extend.
+ *    Diagonal. A step with flag bit 1 (circular) makes no placement, ends a merge and is counted in *n_circular_steps_out. A linear step
+ *      (u, p, s, a = q_first, b = q_last) lies on diagonal d = p - a (s = 0: read base j lies on contig base d + j) or d = p + a + 22
+ *      (s = 1: read base j lies on contig base d - j, complemented). d is signed.
+ *    Merging. Consecutive steps t - 1, t of one sequence belong to one placement iff both are linear, have the same u, s and d, and
+ *      a_t - b_{t-1} - 1 <= max_gap (the windows between them: 23 for one substitution).
+ *    End extension. The core of a placement is read bases [a_first, b_last + 22]. It grows on each side by at most `extend` bases, and
+ *      no further than the end of the read, the end of the contig, and its neighbour among the placements of the same sequence (cores, in
+ *      step order): on the left it stays beyond b_last + 22 of the placement before it, on the right below a_first of the placement after
+ *      it. A limit that comes out negative is 0. (The windows next to a read's end that hold a substitution have no node; the extension
+ *      is what brings that base into the pile. Both rules are measured from the neighbour's core, so read bases between two cores that
+ *      did not merge may be claimed from both sides, and then count once per placement.)
+ *    Outputs, room for T records each (the count never exceeds T: no sizing pass): seq_place_off u64[M + 1], a CSR over sequences, in
+ *      step order; place_unitig u32; place_flag u8 (bit 0: the read lies backwards on the contig); place_pos u32, the leftmost contig
+ *      base covered, local to the contig; place_q0 u32, the first read base; place_len u32; place_steps u32, the steps merged;
+ *      *n_place_out, and *n_circular_steps_out (nullable). A backward placement covers read base q0 + x at contig base pos + len - 1 - x.
+ *    Validation: seq_step_off starts at 0, ascends and ends at T; u < U; q_first <= q_last and q_last + 23 <= the sequence's length; a
+ *      linear step fits its contig (s = 0: p + (b - a) < m_u; s = 1: b - a <= p < m_u); within a sequence q_first exceeds the q_last of
+ *      the step before. M == 0 or T == 0 is AIX_OK with seq_place_off all zero (the step arrays and the record arrays may be NULL when
+ *      T == 0); T > 0 with M == 0 is AIX_ERR_ARG.
+ *
+ * 2. aix_pileup_dev: placements and read bytes become counts. Inputs d_seqs, d_offs[M + 1], M; seq_place_off[M + 1], R and
+ *    place_unitig / place_flag / place_pos / place_q0 / place_len [R]; U, offsets[U + 1], bases[B].
+ *    In/out counts u32[4 B], 16-byte aligned: cell 4 g + c counts the read bases showing c (A, C, G, T = 0 .. 3) at global base g. It is
+ *      accumulated, never zeroed: a caller adds batch after batch. Counters wrap at 2^32.
+ *    Per read base of a placement: only an upper-case A, C, G or T is counted, complemented first when the placement lies backwards; any
+ *      other byte counts nowhere and adds to stats[1].
+ *    Outputs (nullable): place_mism u32[R], the counted bases of a placement that differ from the contig base; stats u64[3] = bases
+ *      counted, other bytes, mismatches of this call (written, not accumulated).
+ *    Validation: seq_place_off starts at 0, ascends and ends at R; u < U; len >= 1; pos + len <= L_u; q0 + len <= the read's length;
+ *      every contig byte is an upper-case A, C, G or T. R == 0 is AIX_OK with counts untouched (the contig bytes are still checked).
+ *    Integer adds commute: the result does not depend on the launch geometry, and a batch and its reverse complement give equal counts.
+ *
+ * 3. aix_pile_call_dev: counts become consensus, variant sites and depth. Inputs U, offsets, bases, counts (16-byte aligned) and
+ *    min_depth, min_major_permille, min_alt_count, min_alt_permille.
+ *    Per base g: r = the code of the contig base, c[0 .. 3] its cell, D = c[0] + c[1] + c[2] + c[3], alt = the channel other than r with
+ *      the largest count, ties to the smaller code; every comparison in 64-bit integers.
+ *      polished[g] = ACGT[alt] iff D >= min_depth, c[alt] > c[r] and 1000 c[alt] >= min_major_permille D; else the contig's base.
+ *      g is a variant site iff D >= min_depth, c[alt] >= min_alt_count and 1000 c[alt] >= min_alt_permille D.
+ *    Outputs, each nullable: polished u8[B] and *n_changed_out; the variant sites in ascending g — var_unitig u32, var_pos u32 (local),
+ *      var_ref and var_alt u8 (ASCII), var_ref_count = c[r], var_alt_count = c[alt], var_depth u32 (D, 2^32 - 1 when it does not fit);
+ *      depth_sum u64[U] (the sum of D over the contig) and uncovered u32[U] (its bases with D == 0).
+ *    Sizing of the variants, as aix_seq_hits_dev: *total_out is always written, the entries only when *total_out <= cap, never at or
+ *      beyond cap (the seven arrays may be NULL when cap == 0); AIX_OK either way. total_out == NULL (then cap must be 0): no variants.
+ *    Validation: the offsets, and every contig byte an upper-case A, C, G or T.
+ *    The polished bases keep the offsets of the input and are an end product: the 22-base overlaps between linked contigs and the
+ *    k-mer map are NOT kept consistent with them, so they are not to be fed back into the graph calls.
+ *
+ * The host form builds layout, emit, links and nodes of the unitig graph at `cutoff` inside (as aix_seq_thread does), threads host
+ * sequences through it, places them and piles them once from zero, and returns malloc'd arrays (aix_free): offsets[U + 1], bases[B],
+ * counts[4 B], seq_place_off[M + 1] and the six placement arrays, optionally place_mism[R] and stats[3]. Handle and statuses as
+ * aix_seq_thread. Piling onto contigs after cleaning is a device-form feature.
+ * ------------------------------------------------------------------------------------------ */
+int aix_pile_place_dev(uint64_t M, const uint64_t* d_offs, const uint64_t* d_seq_step_off, uint64_t T, const uint32_t* d_step_unitig,
+                       const uint32_t* d_step_pos, const uint8_t* d_step_flag, const uint32_t* d_q_first, const uint32_t* d_q_last, uint64_t U,
+                       const uint64_t* d_offsets, uint32_t max_gap, uint32_t extend, uint64_t* d_seq_place_off, uint32_t* d_place_unitig,
+                       uint8_t* d_place_flag, uint32_t* d_place_pos, uint32_t* d_place_q0, uint32_t* d_place_len, uint32_t* d_place_steps,
+                       uint64_t* n_place_out, uint64_t* n_circular_steps_out /* nullable */, void* stream);
+int aix_pileup_dev(const char* d_seqs, const uint64_t* d_offs, uint64_t M, const uint64_t* d_seq_place_off, uint64_t R,
+                   const uint32_t* d_place_unitig, const uint8_t* d_place_flag, const uint32_t* d_place_pos, const uint32_t* d_place_q0,
+                   const uint32_t* d_place_len, uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, uint32_t* d_counts,
+                   uint32_t* d_place_mism /* nullable */, uint64_t* d_stats /* nullable */, void* stream);
+int aix_pile_call_dev(uint64_t U, const uint64_t* d_offsets, const uint8_t* d_bases, const uint32_t* d_counts, uint32_t min_depth,
+                      uint32_t min_major_permille, uint32_t min_alt_count, uint32_t min_alt_permille, uint8_t* d_polished /* nullable */,
+                      uint64_t* n_changed_out /* nullable */, uint32_t* d_var_unitig, uint32_t* d_var_pos, uint8_t* d_var_ref, uint8_t* d_var_alt,
+                      uint32_t* d_var_ref_count, uint32_t* d_var_alt_count, uint32_t* d_var_depth, uint64_t cap, uint64_t* total_out /* nullable */,
+                      uint64_t* d_depth_sum /* nullable */, uint32_t* d_uncovered /* nullable */, void* stream);
+int aix_pileup(aix_index_t* h, uint32_t cutoff, const char* seqs, const uint64_t* offs, uint64_t M, uint32_t max_gap, uint32_t extend,
+               uint64_t* n_unitigs_out, uint64_t* n_place_out, uint64_t* n_circular_steps_out /* nullable */, uint64_t** offsets_out,
+               uint8_t** bases_out, uint32_t** counts_out, uint64_t** seq_place_off_out, uint32_t** place_unitig_out, uint8_t** place_flag_out,
+               uint32_t** place_pos_out, uint32_t** place_q0_out, uint32_t** place_len_out, uint32_t** place_steps_out,
+               uint32_t** place_mism_out /* nullable */, uint64_t** stats_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
