@@ -67,16 +67,15 @@ extern "C" uint64_t aix_selftest_revcomp(uint64_t code, int k) { return revcomp(
 // Move the verification table of a 23-mer handle into another block of HBM: d_dst (nb * 128 bytes, caller-owned and kept alive by the caller
 // for the life of the handle) or, with d_dst == NULL, a block allocated now. Placement experiments only (scripts/gpu_r3_relocate.py).
 extern "C" int aix_debug_relocate_table(aix_index_t* h, void* d_dst) {
-    if (!h || h->k != 23 || !h->bk) return AIX_ERR_ARG;
+    if (!h || h->k != 23 || !h->bk.p) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    const uint64_t bytes = (uint64_t)h->nb * 8 * sizeof(BkEntry);
-    BkEntry* nb_ = (BkEntry*)d_dst;
-    if (!nb_) HIPCHK(hipMalloc((void**)&nb_, bytes));
-    HIPCHK(hipMemcpy(nb_, h->bk, bytes, hipMemcpyDeviceToDevice));
+    const uint64_t bytes = (uint64_t)h->nb * 8 * sizeof(BkEntry), counted = h->bk.counted;   // the ledger keeps the table wherever it lives
+    HBlock own;
+    if (!d_dst) HIPCHK(own.alloc(bytes, counted));
+    HIPCHK(hipMemcpy(d_dst ? d_dst : own.p, h->bk.p, bytes, hipMemcpyDeviceToDevice));
     HIPCHK(hipDeviceSynchronize());
-    if (!h->bk_borrowed) (void)hipFree(h->bk);
-    h->bk = nb_;
-    h->bk_borrowed = d_dst != nullptr;
+    if (d_dst) h->bk.attach_borrowed(d_dst, counted);
+    else h->bk.attach_owned(std::move(own));
     return AIX_OK;
 }
 
@@ -86,34 +85,45 @@ extern "C" int aix_debug_relocate_bloom(aix_index_t* h, uint64_t pad_bytes) {
     DevGuard g(h->device);
     void* pad = nullptr;
     if (pad_bytes) HIPCHK(hipMalloc(&pad, pad_bytes));               // leaked on purpose: shifts where the next block lands
-    uint64_t* nb_ = nullptr;
-    HIPCHK(hipMalloc((void**)&nb_, 8ull * h->nbloom));
-    HIPCHK(hipMemcpy(nb_, h->bloom, 8ull * h->nbloom, hipMemcpyDeviceToDevice));
+    HBlock nb_;
+    HIPCHK(nb_.alloc(8ull * h->nbloom, h->bloom.counted));
+    HIPCHK(hipMemcpy(nb_.p, h->bloom.p, 8ull * h->nbloom, hipMemcpyDeviceToDevice));
     HIPCHK(hipDeviceSynchronize());
-    h->bloom = nb_;
+    (void)h->bloom.leak();
+    h->bloom = std::move(nb_);
     return AIX_OK;
 }
 
 // Move any subset of a 23-mer handle's device arrays into freshly allocated blocks (mask: 1 MPHF records, 2 side index, 4 unfiled keys, 8 verification
-// table, 16 absence filter); the old blocks are NOT freed, so that the new ones come from other memory. Placement experiments only
-// (scripts/experiments/r3/rehome.py).
+// table, 16 absence filter); the old blocks are NOT freed (the table's only behind the new one's allocation), so that the new ones come
+// from other memory. Placement experiments only (scripts/experiments/r3/rehome.py).
 extern "C" int aix_debug_rehome(aix_index_t* h, uint32_t mask) {
     if (!h || h->k != 23) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    auto move = [&](void** field, uint64_t bytes) -> int {
-        if (!*field || !bytes) return AIX_OK;
-        void* nb_ = nullptr;
-        HIPCHK(hipMalloc(&nb_, bytes));
-        HIPCHK(hipMemcpy(nb_, *field, bytes, hipMemcpyDeviceToDevice));
-        *field = nb_;
+    auto copy = [&](const void* from, uint64_t bytes, uint64_t counted, HBlock& to) -> int {
+        HIPCHK(to.alloc(bytes, counted));
+        HIPCHK(hipMemcpy(to.p, from, bytes, hipMemcpyDeviceToDevice));
+        return AIX_OK;
+    };
+    auto move = [&](HBlock& field, uint64_t bytes) -> int {
+        if (!field || !bytes) return AIX_OK;
+        HBlock nb_;
+        if (const int st = copy(field.p, bytes, field.counted, nb_)) return st;
+        (void)field.leak();
+        field = std::move(nb_);
         return AIX_OK;
     };
     int st = AIX_OK;
-    if (!st && (mask & 1)) st = move((void**)&h->recs, (uint64_t)((h->B + 15) / 16) * sizeof(BvRec));
-    if (!st && (mask & 2)) st = move((void**)&h->side, 4ull * h->n);
-    if (!st && (mask & 4)) st = move((void**)&h->unfiled, (uint64_t)h->n_unfiled * sizeof(KeyRec));
-    if (!st && (mask & 8) && !h->bk_borrowed) st = move((void**)&h->bk, (uint64_t)h->nb * 8 * sizeof(BkEntry));
-    if (!st && (mask & 16)) st = move((void**)&h->bloom, 8ull * h->nbloom);
+    if (!st && (mask & 1)) st = move(h->mphf.recs, (uint64_t)((h->mphf.B + 15) / 16) * sizeof(BvRec));
+    if (!st && (mask & 2)) st = move(h->side, 4ull * h->n);
+    if (!st && (mask & 4)) st = move(h->unfiled, (uint64_t)h->n_unfiled * sizeof(KeyRec));
+    if (!st && (mask & 8) && h->bk.owned && h->nb) {
+        HBlock nb_;
+        const uint64_t counted = h->bk.counted;
+        st = copy(h->bk.p, (uint64_t)h->nb * 8 * sizeof(BkEntry), counted, nb_);
+        if (!st) h->bk.attach_owned(std::move(nb_));          // (the old table goes back only now, behind the new one's allocation)
+    }
+    if (!st && (mask & 16)) st = move(h->bloom, 8ull * h->nbloom);
     HIPCHK(hipDeviceSynchronize());
     return st;
 }
@@ -123,7 +133,7 @@ extern "C" int aix_debug_filter_words(aix_index_t* h, uint64_t* out, uint64_t nw
     if (!h || !out || !h->bloom || h->nbloom == 0 || nwords != h->nbloom) return AIX_ERR_ARG;
     DevGuard g(h->device);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->bloom, 8ull * h->nbloom, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, h->bloom.p, 8ull * h->nbloom, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
 
@@ -138,8 +148,8 @@ extern "C" int aix_selftest_lower_bound_dev(const uint16_t* d_sorted, uint32_t n
 // device addresses of a handle's arrays (same order as the mask bits of aix_debug_rehome): experiments only
 extern "C" int aix_debug_pointers(const aix_index_t* h, uint64_t out[5]) {
     if (!h || !out) return AIX_ERR_ARG;
-    out[0] = (uint64_t)(uintptr_t)h->recs; out[1] = (uint64_t)(uintptr_t)h->side; out[2] = (uint64_t)(uintptr_t)h->unfiled;
-    out[3] = (uint64_t)(uintptr_t)h->bk; out[4] = (uint64_t)(uintptr_t)h->bloom;
+    out[0] = (uint64_t)(uintptr_t)h->mphf.recs.p; out[1] = (uint64_t)(uintptr_t)h->side.p; out[2] = (uint64_t)(uintptr_t)h->unfiled.p;
+    out[3] = (uint64_t)(uintptr_t)h->bk.p; out[4] = (uint64_t)(uintptr_t)h->bloom.p;
     return AIX_OK;
 }
 

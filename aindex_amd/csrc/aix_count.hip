@@ -7,41 +7,35 @@
 #include "aix_env.hpp"
 #include "aix_handle.hpp"
 
-// What both counters share; every function here is called with h->count_mutex held.
+// What both counters share (CountState, aix_handle.hpp); every function here is called with c.mutex held.
 // the scratch table / workspace belong to the handle: counting calls are ordered behind one another even when they come in on
-// different streams (the mutex only orders the enqueueing). The caller records h->count_done on `s` when it is through.
-static int order_behind_last_count(aix_index* h, hipStream_t s) {
-    if (h->count_done) HIPCHK(hipStreamWaitEvent(s, h->count_done, 0));
-    else HIPCHK(hipEventCreateWithFlags(&h->count_done, hipEventDisableTiming));
+// different streams (the mutex only orders the enqueueing). The caller records c.done on `s` when it is through.
+static int order_behind_last_count(CountState& c, hipStream_t s) {
+    if (c.done) HIPCHK(hipStreamWaitEvent(s, c.done, 0));
+    else HIPCHK(c.done.create());
     return AIX_OK;
 }
 
 // grow-only per-handle workspace of the counting paths (13-mer partitions; 23-mer slot stream + partitions)
-static int ensure_count_workspace(aix_index* h, uint64_t need, hipStream_t s) {
-    if (need <= h->count_ws_bytes) return AIX_OK;
-    HIPCHK(hipStreamSynchronize(s));
-    if (h->count_ws) { (void)hipFree(h->count_ws); h->device_bytes -= h->count_ws_bytes; h->count_ws = nullptr; h->count_ws_bytes = 0; }
+static int ensure_count_workspace(CountState& c, uint64_t need, hipStream_t s) {
     // AIX_COUNT_TEST_WORKSPACE_MAX: test hook, requests above this many bytes "do not fit"
-    const hipError_t e = need > env_u64("AIX_COUNT_TEST_WORKSPACE_MAX", 0, ~0ull, ~0ull) ? hipErrorOutOfMemory : hipMalloc(&h->count_ws, need);
+    const bool fits = need <= env_u64("AIX_COUNT_TEST_WORKSPACE_MAX", 0, ~0ull, ~0ull);
+    const hipError_t e = c.ws.ensure(need, need, [&] { return hipStreamSynchronize(s); }, fits);
     if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();                                               // the failed request is not a sticky error
-        h->count_ws = nullptr;
         set_last_error("count workspace of " + std::to_string(need) + " bytes does not fit in device memory");
         return AIX_ERR_NOMEM;
     }
     HIPCHK(e);
-    h->count_ws_bytes = need;
-    h->device_bytes += need;
     return AIX_OK;
 }
 
 // Buffers are counted in pieces of at most *piece windows, and the workspace grows with the piece (bytes_for(windows)): one that does not
 // fit halves the piece instead of failing the call, down to 4096 windows. On AIX_OK *piece is the piece to use (at most nwin).
 template <typename F>
-static int fit_count_workspace(aix_index* h, uint64_t nwin, uint64_t* piece, hipStream_t s, F&& bytes_for) {
+static int fit_count_workspace(CountState& c, uint64_t nwin, uint64_t* piece, hipStream_t s, F&& bytes_for) {
     for (;;) {
         const uint64_t pw = std::min(nwin, *piece);
-        const int st = ensure_count_workspace(h, bytes_for(pw), s);
+        const int st = ensure_count_workspace(c, bytes_for(pw), s);
         if (st == AIX_OK) { *piece = pw; return AIX_OK; }
         if (st != AIX_ERR_NOMEM || pw <= 4096) return st;
         *piece = pw / 2;
@@ -51,9 +45,9 @@ static int fit_count_workspace(aix_index* h, uint64_t nwin, uint64_t* piece, hip
 // Word 0 of the workspace is the partition kernels' error word (zeroed by the caller before the first launch): a chunk id outside a
 // workgroup's region would have dropped counts, so the kernels raise it instead of staying silent and the call fails (costs one stream
 // wait per call; the table is complete when this returns).
-static int check_chunk_regions(aix_index* h, const char* who, hipStream_t s) {
+static int check_chunk_regions(CountState& c, const char* who, hipStream_t s) {
     uint32_t dropped = 0;
-    HIPCHK(hipMemcpyAsync(&dropped, h->count_ws, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&dropped, c.ws.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (dropped) { set_last_error(std::string(who) + ": chunk region exhausted (partition workspace undersized)"); return AIX_ERR_UNSUPPORTED; }
     return AIX_OK;
@@ -61,28 +55,27 @@ static int check_chunk_regions(aix_index* h, const char* who, hipStream_t s) {
 
 // K13 in three steps, so that a file can be counted part by part (aix_ingest.hip) as well as in one call: begin() orders the call behind
 // the previous user of the handle's workspace and zeroes the output, add() counts one PLAIN buffer into it (any number of times; every
-// window of the concatenated stream must lie inside exactly one of the buffers), end() finishes the table. The caller holds count_mutex
+// window of the concatenated stream must lie inside exactly one of the buffers), end() finishes the table. The caller holds cnt.mutex
 // from begin to end.
 int count13_begin_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s) {
-    { const int st = order_behind_last_count(h, s); if (st) return st; }
-    h->c13_atomics = env_flag("AIX_COUNT13_ATOMICS") || !h->perm13_bijective;   // env: A/B switch for measurements / tests
-    h->c13_added = false;
-    if (h->c13_atomics) {
-        if (!h->scratch13) {
-            HIPCHK(hipMalloc((void**)&h->scratch13, 8 * AIX_TOTAL_13MERS));
-            h->device_bytes += 8 * AIX_TOTAL_13MERS;
-        }
-        HIPCHK(hipMemsetAsync(h->scratch13, 0, 8 * AIX_TOTAL_13MERS, s));
+    CountState& c = h->cnt;
+    { const int st = order_behind_last_count(c, s); if (st) return st; }
+    c.c13_atomics = env_flag("AIX_COUNT13_ATOMICS") || !h->perm13_bijective;   // env: A/B switch for measurements / tests
+    c.c13_added = false;
+    if (c.c13_atomics) {
+        if (!c.scratch13) HIPCHK(c.scratch13.alloc(8 * AIX_TOTAL_13MERS));
+        HIPCHK(hipMemsetAsync(c.scratch13.p, 0, 8 * AIX_TOTAL_13MERS, s));
     }
     HIPCHK(hipMemsetAsync(d_tf_out, 0, 8 * AIX_TOTAL_13MERS, s));
     return AIX_OK;
 }
 
 int count13_add_locked(aix_index* h, const char* d_plain, uint64_t len, uint64_t* d_tf_out, hipStream_t s) {
-    if (h->c13_atomics) {
+    CountState& c = h->cnt;
+    if (c.c13_atomics) {
         // scattered u64 memory-side atomics into the code-ordered table (slower; kept as the independent cross-check)
-        HIPCHK(launch_count13_plain((const uint8_t*)d_plain, len, h->scratch13, s));
-        h->c13_added = true;
+        HIPCHK(launch_count13_plain((const uint8_t*)d_plain, len, c.scratch13.as<unsigned long long>(), s));
+        c.c13_added = true;
         return AIX_OK;
     }
     // The partitioned path indexes windows and chunks with 32 bits: buffers are cut into pieces of at most `piece` (2^31) window starts.
@@ -91,23 +84,23 @@ int count13_add_locked(aix_index* h, const char* d_plain, uint64_t len, uint64_t
     uint64_t piece = env_count_piece("AIX_COUNT13_PIECE", 1ull << 31);
     const uint64_t nwin = len >= 13 ? len - 12 : 0;
     if (nwin == 0) return AIX_OK;
-    { const int st = fit_count_workspace(h, nwin, &piece, s, [](uint64_t pw) { return count13_workspace_bytes(pw + 12); }); if (st) return st; }
-    HIPCHK(hipMemsetAsync(h->count_ws, 0, 4, s));                             // the error word of the workspace
+    { const int st = fit_count_workspace(c, nwin, &piece, s, [](uint64_t pw) { return count13_workspace_bytes(pw + 12); }); if (st) return st; }
+    HIPCHK(hipMemsetAsync(c.ws.p, 0, 4, s));                                  // the error word of the workspace
     for (uint64_t first = 0; first < nwin; first += piece) {
         const uint64_t w = std::min(piece, nwin - first);
-        HIPCHK(launch_count13_partitioned((const uint8_t*)d_plain + first, w + 12, h->count_ws, nullptr, h->perm13, d_tf_out, h->c13_added ? 1 : 0, s));   // fused permutation
-        h->c13_added = true;
+        HIPCHK(launch_count13_partitioned((const uint8_t*)d_plain + first, w + 12, c.ws.p, nullptr, h->perm13.as<uint32_t>(), d_tf_out, c.c13_added ? 1 : 0, s));   // fused permutation
+        c.c13_added = true;
     }
-    return check_chunk_regions(h, "count13", s);
+    return check_chunk_regions(c, "count13", s);
 }
 
 int count13_end_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s) {
     int st = AIX_OK;
-    if (h->c13_atomics) {
-        const hipError_t e = launch_scatter13_to_mphf(h->perm13, h->scratch13, d_tf_out, h->perm13_bijective ? 0 : 1, s);
+    if (h->cnt.c13_atomics) {
+        const hipError_t e = launch_scatter13_to_mphf(h->perm13.as<uint32_t>(), h->cnt.scratch13.as<unsigned long long>(), d_tf_out, h->perm13_bijective ? 0 : 1, s);
         if (e != hipSuccess) { set_last_error(std::string("count13 scatter: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
     }
-    (void)hipEventRecord(h->count_done, s);
+    (void)hipEventRecord(h->cnt.done, s);
     return st;
 }
 
@@ -115,7 +108,7 @@ extern "C" int aix_count13_dev(aix_index_t* h, const char* d_plain, uint64_t len
     if (!h || !d_tf_out || (len && !d_plain)) return AIX_ERR_ARG;
     if (h->k != 13) return AIX_ERR_MODE;
     DevGuard g(h->device);
-    std::lock_guard<std::mutex> lk(h->count_mutex);
+    std::lock_guard<std::mutex> lk(h->cnt.mutex);
     hipStream_t s = (hipStream_t)stream;
     int st = count13_begin_locked(h, d_tf_out, s);
     if (st) return st;
@@ -125,10 +118,10 @@ extern "C" int aix_count13_dev(aix_index_t* h, const char* d_plain, uint64_t len
 }
 
 // count23: three back ends, same result. Which one ran is reported by aix_index_info (count23_backend / count23_passes). Back ends 1 and 3
-// use nothing of the handle but its tables, so they run outside count_mutex and take it for these two stores only.
+// use nothing of the handle but its tables, so they run outside cnt.mutex and take it for these two stores only.
 static void record_count23(aix_index* h, uint32_t backend, uint32_t passes) {
-    std::lock_guard<std::mutex> lk(h->count_mutex);
-    h->c23_backend = backend; h->c23_passes = passes;
+    std::lock_guard<std::mutex> lk(h->cnt.mutex);
+    h->cnt.c23_backend = backend; h->cnt.c23_passes = passes;
 }
 
 // (1) one memory-side atomic per found window: ~23 G scattered atomics/s on MI355X, which bounds the kernel once a probe costs a single line
@@ -158,54 +151,49 @@ static int count23_via_k1(aix_index* h, const char* d_plain, uint64_t len, int c
     return AIX_OK;
 }
 
-// The second stream of (2) and the events both ways, made by the first multi-piece call of a handle (under count_mutex).
+// The second stream of (2) and the events both ways, made by the first multi-piece call of a handle (under cnt.mutex).
 // AIX_COUNT23_HIST_CUS=n[,style] (A/B switch, read here): the partition + histogram kernels get n of the 256 CUs and the probe the others,
 // through CU-masked streams. The split kernel takes a whole CU (152 KiB of LDS, 16 waves of 128 VGPRs), so on shared CUs the two kernels
 // alternate workgroup by workgroup instead of running side by side. style 0: the low n bits of the mask, 1: every (256 / n)-th bit.
-static int ensure_count23_streams(aix_index* h) {
-    if (h->probe_stream) return AIX_OK;
+// They are built into locals and handed to the handle together: a failure on the way leaves the handle without any of them, and the next
+// call starts over.
+static int ensure_count23_streams(CountState& c) {
+    if (c.probe_stream) return AIX_OK;
+    Stream probe, hist;
+    Event probe_ev[2], hist_ev[2], start_ev;
     int hist_cus = 0, style = 0;
     env_int_pair("AIX_COUNT23_HIST_CUS", &hist_cus, &style);
     if (hist_cus >= 8 && hist_cus <= 224) {
         uint32_t mh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mp[8];
         const int step = style ? 256 / hist_cus : 1;
-        for (int i = 0, c = 0; c < hist_cus && i < 256; i += step, ++c) mh[i >> 5] |= 1u << (i & 31);
+        for (int i = 0, n = 0; n < hist_cus && i < 256; i += step, ++n) mh[i >> 5] |= 1u << (i & 31);
         for (int w = 0; w < 8; ++w) mp[w] = ~mh[w];
-        HIPCHK(hipExtStreamCreateWithCUMask(&h->probe_stream, 8, mp));
-        HIPCHK(hipExtStreamCreateWithCUMask(&h->hist_stream, 8, mh));
+        HIPCHK(probe.create_cu_mask(8, mp));
+        HIPCHK(hist.create_cu_mask(8, mh));
     } else {
-        HIPCHK(hipStreamCreateWithFlags(&h->probe_stream, hipStreamNonBlocking));
+        HIPCHK(probe.create());
     }
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&h->probe_ev[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->hist_ev[i], hipEventDisableTiming));
+        HIPCHK(probe_ev[i].create());
+        HIPCHK(hist_ev[i].create());
     }
-    HIPCHK(hipEventCreateWithFlags(&h->start_ev, hipEventDisableTiming));
+    HIPCHK(start_ev.create());
+    c.probe_stream = std::move(probe);
+    c.hist_stream = std::move(hist);
+    for (int i = 0; i < 2; ++i) { c.probe_ev[i] = std::move(probe_ev[i]); c.hist_ev[i] = std::move(hist_ev[i]); }
+    c.start_ev = std::move(start_ev);
     return AIX_OK;
 }
-
-namespace {
-struct RecordOnExit {                   // the next counting call may touch the workspace once the caller's stream has reached this point
-    hipEvent_t ev; hipStream_t st;
-    ~RecordOnExit() { (void)hipEventRecord(ev, st); }
-};
-// an error in the middle of the piece loop would return with the probe stream still writing into the workspace, and the event recorded on
-// exit (caller's stream only) would let the next counting call in under it: a failing call waits for the probe stream first
-struct ProbeDrainOnError {
-    aix_index* h;
-    bool armed = true;
-    ~ProbeDrainOnError() { if (armed && h->probe_stream) (void)hipStreamSynchronize(h->probe_stream); if (armed && h->hist_stream) (void)hipStreamSynchronize(h->hist_stream); }
-};
-}  // namespace
 
 // (2) the slots are streamed out (4 B per window) and added into tf[] by the chunked-partition + LDS histogram of the 13-mer counter: no
 // global atomics at all. Handles 2^26 slots per pass over the slot stream (2048 partitions of 32 768 bins; a larger key set takes
 // ceil(n / 2^26) passes) and pays a fixed cost, so short buffers keep (1).
 static int count23_histogram(aix_index* h, const char* d_plain, uint64_t nwin, int canon_mode, uint32_t* d_tf_out, hipStream_t s) {
     const uint32_t range_bits = (uint32_t)env_int("AIX_COUNT23_TEST_RANGE_BITS", 4, 26, 26);   // test hook, several slot ranges on a small key set
-    std::lock_guard<std::mutex> lk(h->count_mutex);
-    { const int st = order_behind_last_count(h, s); if (st) return st; }
-    RecordOnExit record_on_exit{h->count_done, s};
+    CountState& c = h->cnt;
+    std::lock_guard<std::mutex> lk(c.mutex);
+    { const int st = order_behind_last_count(c, s); if (st) return st; }
+    RecordOnExit record_on_exit{c.done, s};                                    // the next counting call may touch the workspace once the caller's stream has reached this point
     // windows per pass. Every pass pays for its chunk directory (sort, clears) and leaves one partly filled 512-byte chunk per (workgroup,
     // partition) pair — up to 2^20 of them — for the histogram kernel to read, so long passes win: 200 M reads in 809 / 788 / 775 / 772 ms with
     // 2^28 / 2^29 / 2^30 / 2^31 windows per pass (same box). 2^30: 4 GiB of slots (twice with the second stream) + ~2.6 GiB of partitions.
@@ -218,21 +206,23 @@ static int count23_histogram(aix_index* h, const char* d_plain, uint64_t nwin, i
     const bool may_overlap = !d.mk && env_bool("AIX_COUNT23_OVERLAP", true);
     uint64_t part_bytes = 0, slot_bytes = 0;
     bool overlap = false;
-    { const int st = fit_count_workspace(h, nwin, &pw, s, [&](uint64_t w) {
+    { const int st = fit_count_workspace(c, nwin, &pw, s, [&](uint64_t w) {
           part_bytes = (count13_workspace_bytes(w + 12) + 255) / 256 * 256;
           slot_bytes = (4 * w + 255) / 256 * 256;
           overlap = may_overlap && nwin > w;
           return part_bytes + (overlap ? 2 : 1) * slot_bytes;
       }); if (st) return st; }
-    uint32_t* slot_buf[2] = {(uint32_t*)((uint8_t*)h->count_ws + part_bytes), (uint32_t*)((uint8_t*)h->count_ws + part_bytes + (overlap ? slot_bytes : 0))};
-    ProbeDrainOnError probe_drain{h};
-    HIPCHK(hipMemsetAsync(h->count_ws, 0, 4, s));                             // the error word of the partition workspace
+    uint32_t* slot_buf[2] = {(uint32_t*)(c.ws.as<uint8_t>() + part_bytes), (uint32_t*)(c.ws.as<uint8_t>() + part_bytes + (overlap ? slot_bytes : 0))};
+    // an error in the middle of the piece loop would return with the probe stream still writing into the workspace, and the event recorded on
+    // exit (caller's stream only) would let the next counting call in under it: a failing call waits for the side streams first
+    DrainOnError<2> probe_drain{{&c.probe_stream, &c.hist_stream}};
+    HIPCHK(hipMemsetAsync(c.ws.p, 0, 4, s));                                  // the error word of the partition workspace
     hipStream_t hs = s;
     if (overlap) {
-        { const int st = ensure_count23_streams(h); if (st) return st; }
-        HIPCHK(hipEventRecord(h->start_ev, s));                                // the reads (and whatever else the caller queued) are ready when the first probe starts
-        HIPCHK(hipStreamWaitEvent(h->probe_stream, h->start_ev, 0));
-        if (h->hist_stream) { hs = h->hist_stream; HIPCHK(hipStreamWaitEvent(hs, h->start_ev, 0)); }
+        { const int st = ensure_count23_streams(c); if (st) return st; }
+        HIPCHK(hipEventRecord(c.start_ev, s));                                 // the reads (and whatever else the caller queued) are ready when the first probe starts
+        HIPCHK(hipStreamWaitEvent(c.probe_stream, c.start_ev, 0));
+        if (c.hist_stream) { hs = c.hist_stream; HIPCHK(hipStreamWaitEvent(hs, c.start_ev, 0)); }
     }
     // the slot-stream probe of the counter runs best with two lanes per bucket line (38.7-40.4 against 42.5-42.7 ms per 10 M reads with
     // eight, same box): nothing but the 4-byte slot leaves the kernel, so fewer, wider reads per probe win; lookups keep eight
@@ -249,23 +239,23 @@ static int count23_histogram(aix_index* h, const char* d_plain, uint64_t nwin, i
         const uint64_t w = std::min(pw, nwin - first);
         const int b = overlap ? (int)(ip & 1) : 0;
         if (d.mk) {                                                            // 32 consecutive windows per lane; word 1 of the workspace = "undecided windows" flag
-            HIPCHK(hipMemsetAsync((uint32_t*)h->count_ws + 1, 0, 4, s));
-            HIPCHK(launch_stream23_slots(d, (const uint8_t*)d_plain + first, w + 22, canon_mode, slot_buf[b], (uint32_t*)h->count_ws + 1, s));
+            HIPCHK(hipMemsetAsync(c.ws.as<uint32_t>() + 1, 0, 4, s));
+            HIPCHK(launch_stream23_slots(d, (const uint8_t*)d_plain + first, w + 22, canon_mode, slot_buf[b], c.ws.as<uint32_t>() + 1, s));
         } else if (overlap) {
-            if (ip >= 2) HIPCHK(hipStreamWaitEvent(h->probe_stream, h->hist_ev[b], 0));      // piece ip - 2 has been read out of this buffer
-            HIPCHK(probe((const uint8_t*)d_plain + first, w + 22, slot_buf[b], h->probe_stream));
-            HIPCHK(hipEventRecord(h->probe_ev[b], h->probe_stream));
-            HIPCHK(hipStreamWaitEvent(hs, h->probe_ev[b], 0));
+            if (ip >= 2) HIPCHK(hipStreamWaitEvent(c.probe_stream, c.hist_ev[b], 0));        // piece ip - 2 has been read out of this buffer
+            HIPCHK(probe((const uint8_t*)d_plain + first, w + 22, slot_buf[b], c.probe_stream));
+            HIPCHK(hipEventRecord(c.probe_ev[b], c.probe_stream));
+            HIPCHK(hipStreamWaitEvent(hs, c.probe_ev[b], 0));
         } else {
             HIPCHK(probe((const uint8_t*)d_plain + first, w + 22, slot_buf[b], s));
         }
         uint32_t passes = 0;
-        HIPCHK(launch_histogram_slots(slot_buf[b], w, h->count_ws, d_tf_out, h->n, hs, range_bits, &passes));
-        h->c23_backend = 2; h->c23_passes = passes;
-        if (overlap) HIPCHK(hipEventRecord(h->hist_ev[b], hs));
+        HIPCHK(launch_histogram_slots(slot_buf[b], w, c.ws.p, d_tf_out, h->n, hs, range_bits, &passes));
+        c.c23_backend = 2; c.c23_passes = passes;
+        if (overlap) HIPCHK(hipEventRecord(c.hist_ev[b], hs));
     }
-    if (hs != s && ip) HIPCHK(hipStreamWaitEvent(s, h->hist_ev[(ip - 1) & 1], 0));
-    { const int st = check_chunk_regions(h, "count23", s); if (st) return st; }
+    if (hs != s && ip) HIPCHK(hipStreamWaitEvent(s, c.hist_ev[(ip - 1) & 1], 0));
+    { const int st = check_chunk_regions(c, "count23", s); if (st) return st; }
     probe_drain.armed = false;                                                 // every probe has been waited for by a histogram on the caller's stream
     return AIX_OK;
 }

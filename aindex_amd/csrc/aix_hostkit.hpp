@@ -4,8 +4,10 @@
 // their chains are AIX_TRY / AIX_TRY_LAUNCH, their host forms hold DevArr and publish through one HostOut table. The distinct-k-mer chain
 // and the positions fill (aix_k1, aix_merge, aix_positions, aix_a2msd, and aix_msd.hpp between them) use the chain half: AIX_TRY /
 // AIX_TRY_LAUNCH over DevArr, with_temp, flat_grid; their extern "C" halves keep HIPCHK and DevBuf. Nothing here is on a hot path, and
-// nothing that only one file uses belongs here. aix_normalize, aix_count13, aix_count, aix_ingest, aix_index and aix_lookup* keep raw
-// pool blocks and their own error style and do not use it.
+// nothing that only one file uses belongs here. The files that work on the index handle (aix_index, aix_count, aix_lookup*, and the
+// attach halves of aix_posquery and aix_readsquery) and aix_ingest keep HIPCHK and their own error style, so they do not use this
+// header; what they hold lives in the owners of aix_owned.hpp (blocks, streams, events, the two exit guards), through which the handle
+// frees itself. aix_normalize and aix_count13 keep raw pool blocks.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -58,15 +58,15 @@ extern "C" int aix_pf_check(const void* pf_bytes, uint64_t pf_len, uint64_t hdr_
 }
 
 // parse a .pf image (mphf.hpp:99-113) and lay it out as BvRec records in HBM
-static int upload_mphf(aix_index* h, const uint8_t* pf, uint64_t len) {
+static int upload_mphf(MphfImage* img, const uint8_t* pf, uint64_t len) {
     uint64_t hdr[4];
     const int chk = aix_pf_check(pf, len, hdr);
     if (chk) return chk;
-    h->mphf_n = hdr[0]; h->D = hdr[1]; h->seed = hdr[2]; h->B = hdr[3];
-    h->W = (h->B + 31) / 32;
-    if (h->mphf_n >> 32) return AIX_ERR_UNSUPPORTED;          // 32-bit rank prefixes
+    img->mphf_n = hdr[0]; img->D = hdr[1]; img->seed = hdr[2]; img->B = hdr[3];
+    img->W = (img->B + 31) / 32;
+    if (img->mphf_n >> 32) return AIX_ERR_UNSUPPORTED;        // 32-bit rank prefixes
     const uint64_t* words = (const uint64_t*)(pf + 32);
-    const uint64_t nrec = (h->B + 15) / 16;                      // two records per 64-bit word
+    const uint64_t nrec = (img->B + 15) / 16;                    // two records per 64-bit word
     std::vector<BvRec> recs;
     try { recs.resize(nrec ? nrec : 1); } catch (const std::bad_alloc&) { return AIX_ERR_NOMEM; }
     uint64_t run = 0;
@@ -81,9 +81,8 @@ static int upload_mphf(aix_index* h, const uint8_t* pf, uint64_t len) {
     }
     if (run >> 32) return AIX_ERR_UNSUPPORTED;
     const uint64_t bytes = sizeof(BvRec) * recs.size();
-    HIPCHK(hipMalloc((void**)&h->recs, bytes));
-    h->device_bytes += bytes;
-    HIPCHK(hipMemcpy(h->recs, recs.data(), bytes, hipMemcpyHostToDevice));
+    HIPCHK(img->recs.alloc(bytes));
+    HIPCHK(hipMemcpy(img->recs.p, recs.data(), bytes, hipMemcpyHostToDevice));
     return AIX_OK;
 }
 
@@ -93,39 +92,6 @@ int check_device(int device) {
     if (st) return st;
     if (device < 0 || device >= c) return AIX_ERR_ARG;
     return AIX_OK;
-}
-
-static void destroy(aix_index* h) {
-    if (!h) return;
-    DevGuard g(h->device);
-    if (h->recs) (void)hipFree(h->recs);
-    if (h->ee) (void)hipFree(h->ee);
-    if (h->keys) (void)hipFree(h->keys);
-    if (h->side) (void)hipFree(h->side);
-    if (h->unfiled) (void)hipFree(h->unfiled);
-    if (h->bk && !h->bk_borrowed) (void)hipFree(h->bk);
-    if (h->bloom) (void)hipFree(h->bloom);
-    if (h->mk) (void)hipFree(h->mk);
-    if (h->mk_off) (void)hipFree(h->mk_off);
-    if (h->tf13_mphf) (void)hipFree(h->tf13_mphf);
-    if (h->tf13_code) (void)hipFree(h->tf13_code);
-    if (h->perm13) (void)hipFree(h->perm13);
-    if (h->scratch13) (void)hipFree(h->scratch13);
-    if (h->count_ws) (void)hipFree(h->count_ws);
-    lookup_binned_release(h);
-    posquery_release(h);
-    readsquery_release(h);
-    if (h->pipe) { free_host_pipe(h->pipe); h->pipe = nullptr; }
-    if (h->count_done) (void)hipEventDestroy(h->count_done);
-    for (int i = 0; i < 2; ++i) { if (h->probe_ev[i]) (void)hipEventDestroy(h->probe_ev[i]); if (h->hist_ev[i]) (void)hipEventDestroy(h->hist_ev[i]); }
-    if (h->start_ev) (void)hipEventDestroy(h->start_ev);
-    if (h->probe_stream) (void)hipStreamDestroy(h->probe_stream);
-    if (h->hist_stream) (void)hipStreamDestroy(h->hist_stream);
-    if (h->small_stream) (void)hipStreamDestroy(h->small_stream);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->pin_cov) (void)hipHostFree(h->pin_cov);
-    for (void* p : h->pin_out) if (p) (void)hipHostFree(p);
-    delete h;
 }
 
 // Verification table: n / load buckets of one 128-byte line. AIX_BUCKET_LOAD = mean keys per 8-entry bucket
@@ -142,9 +108,12 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
     const uint64_t bytes = nb * 8 * sizeof(BkEntry);
     DevBuf fill(s);
     HIPCHK(fill.alloc_once(4 * nb));
-    HIPCHK(hipMalloc((void**)&h->bk, bytes));
+    {
+        HBlock table;
+        HIPCHK(table.alloc(bytes));
+        h->bk.attach_owned(std::move(table));
+    }
     h->nb = (uint32_t)nb;
-    h->device_bytes += bytes;
     HIPCHK(hipMemsetAsync(fill.p, 0, 4 * nb, s));
     // absence filter: AIX_BLOOM_BITS bits per key (default 16: 2 B of Infinity-Cache-resident filter per key, < 1 % of the absent
     // keys pass; 0 = no filter)
@@ -153,10 +122,9 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
     if (bloom_bits > 0) {
         uint64_t nw = (uint64_t)((double)h->n * bloom_bits / 64.0) + 1;
         if (nw > 0xFFFFFFF0ull) nw = 0xFFFFFFF0ull;
-        HIPCHK(hipMalloc((void**)&h->bloom, 8 * nw));
+        HIPCHK(h->bloom.alloc(8 * nw));
         h->nbloom = (uint32_t)nw;
-        h->device_bytes += 8 * nw;
-        HIPCHK(hipMemsetAsync(h->bloom, 0, 8 * nw, s));
+        HIPCHK(hipMemsetAsync(h->bloom.p, 0, 8 * nw, s));
     }
     // minimizer-keyed copy for the streaming counter (aix_stream23.hip): built only on request (AIX_MINIMIZER_TABLE=1). Every filed key
     // once more, grouped by the bucket of its minimizer (offsets + entries: a bucket is as long as its content, 16 B per key + 4 B per
@@ -171,17 +139,16 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
     DevBuf mfill(s);
     HIPCHK(mfill.alloc_once(4 * (nbm + 1)));
     HIPCHK(hipMemsetAsync(mfill.p, 0, 4 * (nbm + 1), s));
-    HIPCHK(hipMalloc((void**)&h->side, 4 * h->n));
-    h->device_bytes += 4 * h->n;
-    HIPCHK(launch_build_buckets(h->dev().m, h->keys, h->n, h->bk, h->nb, (uint32_t*)fill.p, h->bloom, h->nbloom, (uint32_t)nbm, (uint32_t*)mfill.p, h->side, s));
+    HIPCHK(h->side.alloc(4 * h->n));
+    HIPCHK(launch_build_buckets(h->dev().m, h->keys.as<KeyRec>(), h->n, h->bk.as<BkEntry>(), h->nb, (uint32_t*)fill.p, h->bloom.as<uint64_t>(), h->nbloom, (uint32_t)nbm,
+                                (uint32_t*)mfill.p, h->side.as<uint32_t>(), s));
     h->mk_cap = (uint32_t)env_int("AIX_MINIMIZER_CAP", 1, AIX_MK_ENTRIES, AIX_MK_ENTRIES);   // test hook: short buckets -> many undecided windows
     if (want_mk) {
         // offsets = exclusive scan of the bucket sizes (a bucket holds < 2^32 keys in total: n < 2^32), then the entries
-        HIPCHK(hipMalloc((void**)&h->mk_off, 4 * (nbm + 1)));
-        h->device_bytes += 4 * (nbm + 1);
-        HIPCHK(exclusive_scan_u32((const uint32_t*)mfill.p, h->mk_off, nbm + 1, s));
+        HIPCHK(h->mk_off.alloc(4 * (nbm + 1)));
+        HIPCHK(exclusive_scan_u32((const uint32_t*)mfill.p, h->mk_off.as<uint32_t>(), nbm + 1, s));
         uint32_t filed = 0;
-        HIPCHK(hipMemcpyAsync(&filed, h->mk_off + nbm, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&filed, h->mk_off.as<uint32_t>() + nbm, 4, hipMemcpyDeviceToHost, s));
         // keys the streaming counter cannot answer from their bucket (longer than the cap): host side, once per open
         std::vector<uint32_t> mf;
         try { mf.resize(nbm); } catch (const std::bad_alloc&) { return AIX_ERR_NOMEM; }
@@ -190,11 +157,10 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
         uint64_t left = 0;
         for (uint64_t i = 0; i < nbm; ++i) if (mf[i] > h->mk_cap) left += mf[i];
         h->mk_unfiled = left;
-        HIPCHK(hipMalloc((void**)&h->mk, (uint64_t)(filed ? filed : 1) * sizeof(BkEntry)));
-        h->device_bytes += (uint64_t)filed * sizeof(BkEntry);
+        HIPCHK(h->mk.alloc((uint64_t)(filed ? filed : 1) * sizeof(BkEntry), (uint64_t)filed * sizeof(BkEntry)));
         h->nbm = (uint32_t)nbm;
         HIPCHK(hipMemsetAsync(mfill.p, 0, 4 * (nbm + 1), s));
-        HIPCHK(launch_fill_minimizer_table(h->dev().m, h->keys, h->n, h->mk, h->mk_off, h->nbm, (uint32_t*)mfill.p, s));
+        HIPCHK(launch_fill_minimizer_table(h->dev().m, h->keys.as<KeyRec>(), h->n, h->mk.as<BkEntry>(), h->mk_off.as<uint32_t>(), h->nbm, (uint32_t*)mfill.p, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     // keys left to the MPHF path: sum over buckets of max(fill - 8, 0) (host side: once per open, nb words)
@@ -211,14 +177,13 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
         DevBuf cnt(s);
         HIPCHK(cnt.alloc_once(8));
         HIPCHK(hipMemsetAsync(cnt.p, 0, 8, s));
-        HIPCHK(launch_count_unfiled(h->side, h->n, (uint32_t*)cnt.p, s));
+        HIPCHK(launch_count_unfiled(h->side.as<uint32_t>(), h->n, (uint32_t*)cnt.p, s));
         uint32_t nu = 0;
         HIPCHK(hipMemcpyAsync(&nu, cnt.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMalloc((void**)&h->unfiled, sizeof(KeyRec) * (uint64_t)(nu ? nu : 1)));
+        HIPCHK(h->unfiled.alloc(sizeof(KeyRec) * (uint64_t)(nu ? nu : 1), sizeof(KeyRec) * (uint64_t)nu));
         h->n_unfiled = nu;
-        h->device_bytes += sizeof(KeyRec) * (uint64_t)nu;
-        HIPCHK(launch_side_unfiled(h->keys, h->n, h->side, h->unfiled, (uint32_t*)cnt.p + 1, s));
+        HIPCHK(launch_side_unfiled(h->keys.as<KeyRec>(), h->n, h->side.as<uint32_t>(), h->unfiled.as<KeyRec>(), (uint32_t*)cnt.p + 1, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return AIX_OK;
@@ -227,14 +192,12 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
 // presence masks of the early-exit MPHF walk (aix_device.hpp: EeRec), from the handle's keys
 static int build_early_exit_table(aix_index* h, hipStream_t s) {
     if (h->ee || h->n == 0) return AIX_OK;
-    const uint64_t nrec = (h->B + 15) / 16;
-    HIPCHK(hipMalloc((void**)&h->ee, sizeof(EeRec) * (nrec ? nrec : 1)));
-    h->device_bytes += sizeof(EeRec) * nrec;
-    EeRec* ee = h->ee;
-    h->ee = nullptr;                                                            // not visible to dev() until it is complete
-    const hipError_t e = launch_set_fingerprints(h->dev(), h->recs, ee, false, s);
+    const uint64_t nrec = (h->mphf.B + 15) / 16;
+    HBlock ee;                                                                  // not visible to dev() until it is complete
+    HIPCHK(ee.alloc(sizeof(EeRec) * (nrec ? nrec : 1), sizeof(EeRec) * nrec));
+    const hipError_t e = launch_set_fingerprints(h->dev(), h->mphf.recs.as<BvRec>(), ee.as<EeRec>(), false, s);
     const hipError_t e2 = hipStreamSynchronize(s);
-    h->ee = ee;
+    h->ee = std::move(ee);
     HIPCHK(e);
     HIPCHK(e2);
     return AIX_OK;
@@ -243,31 +206,26 @@ static int build_early_exit_table(aix_index* h, hipStream_t s) {
 // interleave device-resident checker[]/tf[] into KeyRec records and detect an all-canonical key set
 static int adopt_device_arrays(aix_index* h, const uint64_t* d_checker, const uint32_t* d_tf, uint64_t n, hipStream_t s) {
     if (n == 0) return AIX_OK;
-    uint32_t* d_flag = nullptr;
-    HIPCHK(hipMalloc((void**)&h->keys, sizeof(KeyRec) * n));
-    h->device_bytes += sizeof(KeyRec) * n;
-    HIPCHK(hipMalloc((void**)&d_flag, 4));
-    hipError_t e = hipMemsetAsync(d_flag, 0, 4, s);
-    if (e == hipSuccess) e = launch_build_keyrecs(d_checker, d_tf, n, h->keys, d_flag, s);
+    HIPCHK(h->keys.alloc(sizeof(KeyRec) * n));
     uint32_t flag = 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_flag);
-    HIPCHK(e);
+    {
+        DevBuf d_flag(s);
+        HIPCHK(d_flag.alloc_once(4));
+        HIPCHK(hipMemsetAsync(d_flag.p, 0, 4, s));
+        HIPCHK(launch_build_keyrecs(d_checker, d_tf, n, h->keys.as<KeyRec>(), (uint32_t*)d_flag.p, s));
+        HIPCHK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
     h->canonical_only = (flag == 0);
     // The early-exit table (32 B per 16 bit-pairs: 2.5 B per key) serves the MPHF walk; with a verification table in front that walk only runs
     // behind overflowed buckets, so the table is then built on request (aix_index_set_early_exit) instead of at every open.
     if (!env_bucket_table()) { const int st = build_early_exit_table(h, s); if (st) return st; }
-    HIPCHK(launch_set_fingerprints(h->dev(), h->recs, nullptr, true, s));
+    HIPCHK(launch_set_fingerprints(h->dev(), h->mphf.recs.as<BvRec>(), nullptr, true, s));
     HIPCHK(hipStreamSynchronize(s));
     h->has_fp = true;
     const int st = build_bucket_table(h, s);
     if (st) return st;
-    if (h->bk && h->side) {                                                     // every key is reachable through the table / the unfiled list: drop the duplicate
-        (void)hipFree(h->keys);
-        h->keys = nullptr;
-        h->device_bytes -= sizeof(KeyRec) * n;
-    }
+    if (h->bk.p && h->side) h->keys.drop();                                     // every key is reachable through the table / the unfiled list: drop the duplicate
     return AIX_OK;
 }
 
@@ -278,11 +236,11 @@ extern "C" int aix_index_create_23(const void* pf_bytes, uint64_t pf_len, const 
     int st = check_device(device);
     if (st) return st;
     if (n >> 32) return AIX_ERR_UNSUPPORTED;
-    aix_index* h = new (std::nothrow) aix_index();
+    HandlePtr h(new (std::nothrow) aix_index());
     if (!h) return AIX_ERR_NOMEM;
     h->device = device; h->k = 23; h->n = n;
     DevGuard g(device);
-    st = upload_mphf(h, (const uint8_t*)pf_bytes, pf_len);
+    st = upload_mphf(&h->mphf, (const uint8_t*)pf_bytes, pf_len);
     if (!st && n) {
         DevBuf dc, dt;
         hipError_t e = dc.alloc_once(8 * n);
@@ -290,17 +248,17 @@ extern "C" int aix_index_create_23(const void* pf_bytes, uint64_t pf_len, const 
         if (e == hipSuccess) e = hipMemcpy(dc.p, checker, 8 * n, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(dt.p, tf, 4 * n, hipMemcpyHostToDevice);
         if (e != hipSuccess) { set_last_error(std::string("index upload: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
-        else st = adopt_device_arrays(h, (const uint64_t*)dc.p, (const uint32_t*)dt.p, n, 0);
+        else st = adopt_device_arrays(h.get(), (const uint64_t*)dc.p, (const uint32_t*)dt.p, n, 0);
     }
-    if (st) { destroy(h); return st; }
-    *out = h;
+    if (st) return st;
+    *out = h.release();
     return AIX_OK;
 }
 
 // I1 on the device: scatter (key, count) pairs through the MPHF. Exactly one of d_keys / d_codes is set.
 // n keys into nslots slots (nslots == n for a whole key set; a shard of the keys scatters into the full-size arrays).
 // occ_out (optional, device, ceil(nslots/32) words): bit h set <=> slot h was written by this call.
-static int scatter_device(aix_index* h, uint64_t n, uint64_t nslots, const uint8_t* d_keys, const uint64_t* d_codes, const uint32_t* d_counts,
+static int scatter_device(const MphfImage& mphf, uint64_t n, uint64_t nslots, const uint8_t* d_keys, const uint64_t* d_codes, const uint32_t* d_counts,
                           uint64_t* d_checker, uint32_t* d_tf, uint32_t* occ_out, hipStream_t s) {
     DevBuf occ(s), flag(s);
     const uint64_t occ_bytes = 4 * ((nslots + 31) / 32);
@@ -310,8 +268,7 @@ static int scatter_device(aix_index* h, uint64_t n, uint64_t nslots, const uint8
     HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
     HIPCHK(hipMemsetAsync(d_checker, 0, 8 * nslots, s));       // hash.cpp:836-844: arrays start zeroed
     HIPCHK(hipMemsetAsync(d_tf, 0, 4 * nslots, s));
-    const IndexDev d = h->dev();
-    HIPCHK(launch_scatter23(d.m, n, nslots, d_keys, d_codes, d_counts, d_checker, d_tf, (uint32_t*)occ.p, (uint32_t*)flag.p, s));
+    HIPCHK(launch_scatter23(mphf.view(), n, nslots, d_keys, d_codes, d_counts, d_checker, d_tf, (uint32_t*)occ.p, (uint32_t*)flag.p, s));
     uint32_t conflicts = 0;
     HIPCHK(hipMemcpyAsync(&conflicts, flag.p, 4, hipMemcpyDeviceToHost, s));
     if (occ_out) HIPCHK(hipMemcpyAsync(occ_out, occ.p, occ_bytes, hipMemcpyDeviceToDevice, s));
@@ -323,10 +280,9 @@ static int scatter_host(const void* pf_bytes, uint64_t pf_len, const char* keys,
                         uint64_t* checker_out, uint32_t* tf_out, uint32_t* occupied_out) {
     int st = check_device(device);
     if (st) return st;
-    aix_index tmp;
-    tmp.device = device; tmp.k = 23; tmp.n = nslots;
     DevGuard g(device);
-    st = upload_mphf(&tmp, (const uint8_t*)pf_bytes, pf_len);
+    MphfImage mphf;                                                // declared behind the guard: freed on `device`
+    st = upload_mphf(&mphf, (const uint8_t*)pf_bytes, pf_len);
     if (!st) {
         DevBuf dk, dcnt, dc, dt, docc;
         const uint64_t occ_bytes = 4 * ((nslots + 31) / 32);
@@ -338,7 +294,7 @@ static int scatter_host(const void* pf_bytes, uint64_t pf_len, const char* keys,
         if (e == hipSuccess && n) e = hipMemcpy(dk.p, keys, 23 * n, hipMemcpyHostToDevice);
         if (e == hipSuccess && counts && n) e = hipMemcpy(dcnt.p, counts, 4 * n, hipMemcpyHostToDevice);
         if (e != hipSuccess) { set_last_error(std::string("scatter staging: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
-        if (!st) st = scatter_device(&tmp, n, nslots, (const uint8_t*)dk.p, nullptr, (counts && n) ? (const uint32_t*)dcnt.p : nullptr, (uint64_t*)dc.p,
+        if (!st) st = scatter_device(mphf, n, nslots, (const uint8_t*)dk.p, nullptr, (counts && n) ? (const uint32_t*)dcnt.p : nullptr, (uint64_t*)dc.p,
                                      (uint32_t*)dt.p, occupied_out ? (uint32_t*)docc.p : nullptr, 0);
         if (!st || st == AIX_ERR_CONFLICT) {                       // a shard reports its conflict AND hands back what it wrote
             const int keep = st;
@@ -349,8 +305,6 @@ static int scatter_host(const void* pf_bytes, uint64_t pf_len, const char* keys,
             else st = keep;
         }
     }
-    if (tmp.recs) (void)hipFree(tmp.recs);
-    tmp.recs = nullptr;
     return st;
 }
 
@@ -374,21 +328,21 @@ extern "C" int aix_index_build_23_codes_dev(const void* pf_bytes, uint64_t pf_le
     int st = check_device(device);
     if (st) return st;
     if (n >> 32) return AIX_ERR_UNSUPPORTED;
-    aix_index* h = new (std::nothrow) aix_index();
+    HandlePtr h(new (std::nothrow) aix_index());
     if (!h) return AIX_ERR_NOMEM;
     h->device = device; h->k = 23; h->n = n;
     DevGuard g(device);
-    st = upload_mphf(h, (const uint8_t*)pf_bytes, pf_len);
+    st = upload_mphf(&h->mphf, (const uint8_t*)pf_bytes, pf_len);
     if (!st) {
         DevBuf dc((hipStream_t)stream), dt((hipStream_t)stream);
         hipError_t e = dc.alloc(8 * n);
         if (e == hipSuccess) e = dt.alloc(4 * n);
         if (e != hipSuccess) { set_last_error(std::string("index build: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
-        if (!st) st = scatter_device(h, n, n, nullptr, d_codes, d_counts, (uint64_t*)dc.p, (uint32_t*)dt.p, nullptr, (hipStream_t)stream);
-        if (!st) st = adopt_device_arrays(h, (const uint64_t*)dc.p, (const uint32_t*)dt.p, n, (hipStream_t)stream);
+        if (!st) st = scatter_device(h->mphf, n, n, nullptr, d_codes, d_counts, (uint64_t*)dc.p, (uint32_t*)dt.p, nullptr, (hipStream_t)stream);
+        if (!st) st = adopt_device_arrays(h.get(), (const uint64_t*)dc.p, (const uint32_t*)dt.p, n, (hipStream_t)stream);
     }
-    if (st) { destroy(h); return st; }
-    *out = h;
+    if (st) return st;
+    *out = h.release();
     return AIX_OK;
 }
 
@@ -409,15 +363,14 @@ extern "C" int aix_index_open_23(const char* pf, const char* tf_bin, const char*
 
 static int build_13_tables(aix_index* h, const uint64_t* tf_host) {
     const uint64_t N13 = AIX_TOTAL_13MERS;
-    HIPCHK(hipMalloc((void**)&h->tf13_mphf, 8 * N13));
-    HIPCHK(hipMalloc((void**)&h->tf13_code, 8 * N13));
-    HIPCHK(hipMalloc((void**)&h->perm13, 4 * N13));
-    h->device_bytes += 20 * N13;
-    if (tf_host) HIPCHK(hipMemcpy(h->tf13_mphf, tf_host, 8 * N13, hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(h->tf13_mphf, 0, 8 * N13));
+    HIPCHK(h->tf13_mphf.alloc(8 * N13));
+    HIPCHK(h->tf13_code.alloc(8 * N13));
+    HIPCHK(h->perm13.alloc(4 * N13));
     const IndexDev d = h->dev();
-    HIPCHK(launch_perm13(d.m, h->perm13, 0));
-    HIPCHK(launch_tf13_to_code_order(h->perm13, h->tf13_mphf, h->tf13_code, 0));
+    if (tf_host) HIPCHK(hipMemcpy(h->tf13_mphf.p, tf_host, 8 * N13, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(h->tf13_mphf.p, 0, 8 * N13));
+    HIPCHK(launch_perm13(d.m, h->perm13.as<uint32_t>(), 0));
+    HIPCHK(launch_tf13_to_code_order(d.perm13, d.tf13_mphf, h->tf13_code.as<uint64_t>(), 0));
     // The streaming counter writes each bin's total to out[perm[code]] with a plain store: right only when code -> slot is a
     // bijection, which holds for the all-13-mers .pf and not for a foreign one. Checked once here; a handle that fails the check
     // counts through the atomics path, which adds (the reference's fetch_add at mphf(window), count_kmers13.cpp:147-152).
@@ -427,7 +380,7 @@ static int build_13_tables(aix_index* h, const uint64_t* tf_host) {
         HIPCHK(bad.alloc_once(4));
         HIPCHK(hipMemsetAsync(bits.p, 0, AIX_TOTAL_13MERS / 8, 0));
         HIPCHK(hipMemsetAsync(bad.p, 0, 4, 0));
-        HIPCHK(launch_perm13_check(h->perm13, (uint32_t*)bits.p, (uint32_t*)bad.p, 0));
+        HIPCHK(launch_perm13_check(d.perm13, (uint32_t*)bits.p, (uint32_t*)bad.p, 0));
         uint32_t nbad = 1;
         HIPCHK(hipMemcpy(&nbad, bad.p, 4, hipMemcpyDeviceToHost));
         h->perm13_bijective = (nbad == 0);
@@ -441,14 +394,14 @@ extern "C" int aix_index_create_13(const void* pf_bytes, uint64_t pf_len, const 
     *out = nullptr;
     int st = check_device(device);
     if (st) return st;
-    aix_index* h = new (std::nothrow) aix_index();
+    HandlePtr h(new (std::nothrow) aix_index());
     if (!h) return AIX_ERR_NOMEM;
     h->device = device; h->k = 13; h->n = AIX_TOTAL_13MERS;
     DevGuard g(device);
-    st = upload_mphf(h, (const uint8_t*)pf_bytes, pf_len);
-    if (!st) st = build_13_tables(h, tf);
-    if (st) { destroy(h); return st; }
-    *out = h;
+    st = upload_mphf(&h->mphf, (const uint8_t*)pf_bytes, pf_len);
+    if (!st) st = build_13_tables(h.get(), tf);
+    if (st) return st;
+    *out = h.release();
     return AIX_OK;
 }
 
@@ -467,7 +420,7 @@ extern "C" int aix_index_open_13(const char* pf, const char* tf_bin, int device,
 
 extern "C" int aix_index_close(aix_index_t* h) {
     if (!h) return AIX_ERR_ARG;
-    destroy(h);
+    HandleDelete()(h);                // every owner on the handle releases what it holds, on the handle's device
     pool_trim();                      // scratch blocks cached for this handle's calls go back to the driver with it
     return AIX_OK;
 }
@@ -475,23 +428,23 @@ extern "C" int aix_index_close(aix_index_t* h) {
 extern "C" int aix_index_info(const aix_index_t* h, aix_info_t* info) {
     if (!h || !info) return AIX_ERR_ARG;
     memset(info, 0, sizeof(*info));
-    info->k = h->k; info->device = (uint32_t)h->device; info->n = h->n; info->mphf_n = h->mphf_n;
-    info->hash_domain = h->D; info->seed = h->seed; info->bitpairs = h->B; info->device_bytes = h->device_bytes;
+    info->k = h->k; info->device = (uint32_t)h->device; info->n = h->n; info->mphf_n = h->mphf.mphf_n;
+    info->hash_domain = h->mphf.D; info->seed = h->mphf.seed; info->bitpairs = h->mphf.B; info->device_bytes = h->device_bytes;
     info->canonical_only = h->canonical_only ? 1 : 0;
-    info->bucket_table = (h->bk && h->bk_enabled) ? 1 : 0;
+    info->bucket_table = (h->bk.p && h->bk_enabled) ? 1 : 0;
     info->bucket_lanes = h->bk_lpp;
-    info->buckets = h->bk ? h->nb : 0;
+    info->buckets = h->bk.p ? h->nb : 0;
     info->bucket_unfiled_keys = h->bk_unfiled;
-    info->absence_filter_words = (h->bk && h->bk_enabled && h->bloom && h->bloom_enabled) ? h->nbloom : 0;
-    info->minimizer_lines = (h->bk && h->bk_enabled && h->mk && h->mk_enabled) ? h->nbm : 0;
+    info->absence_filter_words = (h->bk.p && h->bk_enabled && h->bloom && h->bloom_enabled) ? h->nbloom : 0;
+    info->minimizer_lines = (h->bk.p && h->bk_enabled && h->mk && h->mk_enabled) ? h->nbm : 0;
     info->minimizer_unfiled_keys = h->mk_unfiled;
-    info->count23_backend = h->c23_backend;
-    info->count23_passes = h->c23_passes;
+    info->count23_backend = h->cnt.c23_backend;
+    info->count23_passes = h->cnt.c23_passes;
     info->positions_backend = h->a2_backend;
-    info->aindex_attached = h->ai_attached ? (h->ai_owned ? 1u : 2u) : 0u;
-    info->ridx_on_device = h->rx_attached ? 1u : 0u;
-    info->aindex_entries = h->ai_attached ? h->ai_total : 0;
-    info->ridx_reads = h->rx_attached ? h->rx_n : 0;
+    info->aindex_attached = h->att.ai_indices.attached ? (h->att.ai_indices.owned ? 1u : 2u) : 0u;
+    info->ridx_on_device = h->att.rx ? 1u : 0u;
+    info->aindex_entries = h->att.ai_indices.attached ? h->att.ai_total : 0;
+    info->ridx_reads = h->att.rx ? h->att.rx_n : 0;
     return AIX_OK;
 }
 
@@ -542,9 +495,9 @@ extern "C" int aix_index_set_tf_13(aix_index_t* h, const uint64_t* tf) {
     if (!h || !tf) return AIX_ERR_ARG;
     if (h->k != 13) return AIX_ERR_MODE;
     DevGuard g(h->device);
-    HIPCHK(hipMemcpy(h->tf13_mphf, tf, 8 * AIX_TOTAL_13MERS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tf13_mphf.p, tf, 8 * AIX_TOTAL_13MERS, hipMemcpyHostToDevice));
     h->pos_total_known = false;
-    HIPCHK(launch_tf13_to_code_order(h->perm13, h->tf13_mphf, h->tf13_code, 0));
+    HIPCHK(launch_tf13_to_code_order(h->perm13.as<uint32_t>(), h->tf13_mphf.as<uint64_t>(), h->tf13_code.as<uint64_t>(), 0));
     HIPCHK(hipStreamSynchronize(0));
     return AIX_OK;
 }
@@ -554,17 +507,15 @@ extern "C" int aix_index_get_tf(const aix_index_t* h, void* out, uint64_t out_by
     DevGuard g(h->device);
     if (h->k == 13) {
         if (out_bytes < 8 * AIX_TOTAL_13MERS) return AIX_ERR_ARG;
-        HIPCHK(hipMemcpy(out, h->tf13_mphf, 8 * AIX_TOTAL_13MERS, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, h->tf13_mphf.p, 8 * AIX_TOTAL_13MERS, hipMemcpyDeviceToHost));
         return AIX_OK;
     }
     if (out_bytes < 4 * h->n) return AIX_ERR_ARG;
     if (h->n == 0) return AIX_OK;
-    uint32_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, 4 * h->n));
-    hipError_t e = launch_extract_tf(h->dev(), d, nullptr, 0);
-    if (e == hipSuccess) e = hipMemcpy(out, d, 4 * h->n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIPCHK(e);
+    DevBuf d;
+    HIPCHK(d.alloc_once(4 * h->n));
+    HIPCHK(launch_extract_tf(h->dev(), (uint32_t*)d.p, nullptr, 0));
+    HIPCHK(hipMemcpy(out, d.p, 4 * h->n, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
 
@@ -574,12 +525,10 @@ extern "C" int aix_index_get_checker(const aix_index_t* h, uint64_t* out, uint64
     if (n < h->n) return AIX_ERR_ARG;
     if (h->n == 0) return AIX_OK;
     DevGuard g(h->device);
-    uint64_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, 8 * h->n));
-    hipError_t e = launch_extract_tf(h->dev(), nullptr, d, 0);
-    if (e == hipSuccess) e = hipMemcpy(out, d, 8 * h->n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIPCHK(e);
+    DevBuf d;
+    HIPCHK(d.alloc_once(8 * h->n));
+    HIPCHK(launch_extract_tf(h->dev(), nullptr, (uint64_t*)d.p, 0));
+    HIPCHK(hipMemcpy(out, d.p, 8 * h->n, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
 
@@ -591,12 +540,10 @@ extern "C" int aix_index_scatter_shard_codes_dev(const void* pf_bytes, uint64_t 
     if (n_slots >> 32) return AIX_ERR_UNSUPPORTED;
     int st = check_device(device);
     if (st) return st;
-    aix_index tmp;
-    tmp.device = device; tmp.k = 23; tmp.n = n_slots;
     DevGuard g(device);
-    st = upload_mphf(&tmp, (const uint8_t*)pf_bytes, pf_len);
-    if (!st) st = scatter_device(&tmp, n_keys, n_slots, nullptr, d_codes, d_counts, d_checker_out, d_tf_out, d_occupied_out, (hipStream_t)stream);
-    if (tmp.recs) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(tmp.recs); }
-    tmp.recs = nullptr;
+    MphfImage mphf;
+    st = upload_mphf(&mphf, (const uint8_t*)pf_bytes, pf_len);
+    if (!st) st = scatter_device(mphf, n_keys, n_slots, nullptr, d_codes, d_counts, d_checker_out, d_tf_out, d_occupied_out, (hipStream_t)stream);
+    if (mphf.recs) (void)hipStreamSynchronize((hipStream_t)stream);          // the records are freed idle
     return st;
 }

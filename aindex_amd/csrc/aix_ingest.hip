@@ -233,15 +233,15 @@ int Ingest::start(uint8_t* direct_dst) {
     direct = direct_dst;
     // (copies of consecutive parts on two alternating streams were measured: 41.9 / 38.9 / 32.7 GB/s with 32 / 64 / 128 MiB parts against
     // 43.8 GB/s with one stream and 64 MiB parts on the same box — one stream it is)
-    if (hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return AIX_ERR_HIP; }
+    if (copy_stream.create() != hipSuccess) { (void)hipGetLastError(); return AIX_ERR_HIP; }
     for (int b = 0; b < NB; ++b) {
-        if (hipEventCreate(&h2d_ev[b]) != hipSuccess || hipEventCreate(&h2d_t0[b]) != hipSuccess || hipEventCreateWithFlags(&used_ev[b], hipEventDisableTiming) != hipSuccess) {
+        if (h2d_ev[b].create(hipEventDefault) != hipSuccess || h2d_t0[b].create(hipEventDefault) != hipSuccess || used_ev[b].create() != hipSuccess) {
             (void)hipGetLastError();
             return AIX_ERR_HIP;
         }
         if (!direct) {
             if (pool_alloc((void**)&dbuf[b], HDR + part_bytes + 64) != hipSuccess) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }
-            device_bytes += HDR + part_bytes + 64;
+            device_bytes = (uint64_t)(b + 1) * (HDR + part_bytes + 64);
         }
     }
     started = true;
@@ -358,11 +358,7 @@ Ingest::~Ingest() {
     for (int b = 0; b < NB; ++b) {
         if (pin[b]) pinned_pool().put(pin[b], part_bytes);
         if (dbuf[b]) pool_free(dbuf[b]);
-        if (h2d_ev[b]) (void)hipEventDestroy(h2d_ev[b]);
-        if (h2d_t0[b]) (void)hipEventDestroy(h2d_t0[b]);
-        if (used_ev[b]) (void)hipEventDestroy(used_ev[b]);
     }
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
 }
 
 uint64_t ingest_part_bytes() {
@@ -477,7 +473,7 @@ void PlainStream::fill_stats(aix_ingest_stats_t* st) const {
 // C ABI: files in, tables out
 // ---------------------------------------------------------------------------------------------
 static int count13_source(aix_index_t* h, const ByteSource& src, int format, uint64_t* d_tf, hipStream_t s, aix_ingest_stats_t* stats) {
-    std::lock_guard<std::mutex> lk(h->count_mutex);
+    std::lock_guard<std::mutex> lk(h->cnt.mutex);
     int st = count13_begin_locked(h, d_tf, s);
     if (st) return st;
     {
@@ -493,7 +489,7 @@ static int count13_source(aix_index_t* h, const ByteSource& src, int format, uin
         }
         if (!st && r < 0) st = r;
         ps.fill_stats(stats);
-        if (stats) stats->workspace_bytes = h->count_ws_bytes;
+        if (stats) stats->workspace_bytes = h->cnt.ws.bytes;
     }
     const int st2 = count13_end_locked(h, d_tf, s);
     return st ? st : st2;
@@ -513,7 +509,7 @@ static int count23_source(aix_index_t* h, const ByteSource& src, int format, int
     }
     if (!st && r < 0) st = r;
     ps.fill_stats(stats);
-    if (stats) stats->workspace_bytes = h->count_ws_bytes;
+    if (stats) stats->workspace_bytes = h->cnt.ws.bytes;
     return st;
 }
 
@@ -596,10 +592,10 @@ static int download(void* host_dst, OutputFile* of, const void* d_src, uint64_t 
     if (!st && staged) {
         const uint64_t slice = std::min<uint64_t>(bytes, 32ull << 20);
         void* pin[2] = {pinned_pool().get(slice), pinned_pool().get(slice)};
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        Event ev[2];
         if (!pin[0] || !pin[1]) st = AIX_ERR_NOMEM;
         for (int b = 0; b < 2 && !st; ++b)
-            if (hipEventCreateWithFlags(&ev[b], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); st = AIX_ERR_HIP; }
+            if (ev[b].create() != hipSuccess) { (void)hipGetLastError(); st = AIX_ERR_HIP; }
         const uint64_t nsl = (bytes + slice - 1) / slice;
         auto issue = [&](uint64_t i) -> int {
             const uint64_t lo = i * slice, m = std::min(slice, bytes - lo);
@@ -618,7 +614,7 @@ static int download(void* host_dst, OutputFile* of, const void* d_src, uint64_t 
             if (of) st = of->put(lo, from, m);
         }
         (void)hipStreamSynchronize(s);
-        for (int b = 0; b < 2; ++b) { pinned_pool().put(pin[b], slice); if (ev[b]) (void)hipEventDestroy(ev[b]); }
+        for (int b = 0; b < 2; ++b) pinned_pool().put(pin[b], slice);
     } else if (!st && of && host_dst && bytes) {                 // pinned destination and a file: the file is written from the caller's copy
         of->ready();
         st = of->put(0, (const char*)host_dst, bytes);
@@ -654,18 +650,14 @@ static int count13_any(aix_index_t* h, const ByteSource& src, int format, const 
     DevGuard g(h->device);
     OutputFile of;
     if (out_path) { const int os_ = of.open_and_reserve(out_path, 8 * AIX_TOTAL_13MERS); if (os_) return os_; }
-    hipStream_t s = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    int st;
-    {
-        DevBuf dout(s);
-        st = dout.alloc(8 * AIX_TOTAL_13MERS) == hipSuccess ? AIX_OK : AIX_ERR_NOMEM;
-        if (!st) st = count13_source(h, src, format, (uint64_t*)dout.p, s, stats);
-        if (!st && hipStreamSynchronize(s) != hipSuccess) st = AIX_ERR_HIP;
-        if (!st) st = download(tf_out, out_path ? &of : nullptr, dout.p, 8 * AIX_TOTAL_13MERS, s, stats);
-        if (stats) stats->device_bytes += 8 * AIX_TOTAL_13MERS;
-    }
-    (void)hipStreamDestroy(s);
+    Stream s;                                                   // declared before the result block: the block is freed idle, then the stream goes
+    HIPCHK(s.create());
+    DevBuf dout(s);
+    int st = dout.alloc(8 * AIX_TOTAL_13MERS) == hipSuccess ? AIX_OK : AIX_ERR_NOMEM;
+    if (!st) st = count13_source(h, src, format, (uint64_t*)dout.p, s, stats);
+    if (!st && hipStreamSynchronize(s) != hipSuccess) st = AIX_ERR_HIP;
+    if (!st) st = download(tf_out, out_path ? &of : nullptr, dout.p, 8 * AIX_TOTAL_13MERS, s, stats);
+    if (stats) stats->device_bytes += 8 * AIX_TOTAL_13MERS;
     if (stats) stats->seconds_total = now_s() - t0;
     return st;
 }
@@ -702,18 +694,14 @@ static int count23_any(aix_index_t* h, const ByteSource& src, int format, int ca
     if (stats) memset(stats, 0, sizeof(*stats));
     if (h->n == 0) return AIX_OK;
     DevGuard g(h->device);
-    hipStream_t s = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    int st;
-    {
-        DevBuf dout(s);
-        st = dout.alloc(4 * h->n) == hipSuccess ? AIX_OK : AIX_ERR_NOMEM;
-        if (!st && hipMemsetAsync(dout.p, 0, 4 * h->n, s) != hipSuccess) st = AIX_ERR_HIP;
-        if (!st) st = count23_source(h, src, format, canon_mode, (uint32_t*)dout.p, s, stats);
-        if (!st) st = download(tf_out, (OutputFile*)nullptr, dout.p, 4 * h->n, s, stats);
-        if (stats) stats->device_bytes += 4 * h->n;
-    }
-    (void)hipStreamDestroy(s);
+    Stream s;                                                   // as in count13_any
+    HIPCHK(s.create());
+    DevBuf dout(s);
+    int st = dout.alloc(4 * h->n) == hipSuccess ? AIX_OK : AIX_ERR_NOMEM;
+    if (!st && hipMemsetAsync(dout.p, 0, 4 * h->n, s) != hipSuccess) st = AIX_ERR_HIP;
+    if (!st) st = count23_source(h, src, format, canon_mode, (uint32_t*)dout.p, s, stats);
+    if (!st) st = download(tf_out, (OutputFile*)nullptr, dout.p, 4 * h->n, s, stats);
+    if (stats) stats->device_bytes += 4 * h->n;
     if (stats) stats->seconds_total = now_s() - t0;
     return st;
 }
@@ -801,8 +789,8 @@ static int count_distinct_any(const ByteSource& src, int format, int k, int cano
     if (stats) memset(stats, 0, sizeof(*stats));
     *keys_out = nullptr; *counts_out = nullptr; *n_out = 0;
     DevGuard g(device);
-    hipStream_t s = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    Stream s;                                                // outlives the result: d goes back idle (synchronised below), then the stream
+    HIPCHK(s.create());
     DistinctRun d;
     int st = distinct_source(src, format, k, canon_mode, min_count, device, s, d, stats);
     const uint64_t m = d.n;
@@ -821,7 +809,6 @@ static int count_distinct_any(const ByteSource& src, int format, int k, int cano
         if (stats) stats->seconds_output += now_s() - t1;
     }
     (void)hipStreamSynchronize(s);                           // the copies above may still read d on a failure: it is freed idle
-    (void)hipStreamDestroy(s);
     if (st) { free(hk); free(hc); return st; }
     *keys_out = hk; *counts_out = hc; *n_out = m;
     if (stats) stats->seconds_total = now_s() - t0;

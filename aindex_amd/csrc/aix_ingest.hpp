@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "../../include/aindex_hip.h"
+#include "aix_owned.hpp"
 
 namespace aix {
 
@@ -59,8 +60,8 @@ private:
     uint8_t* direct = nullptr;
     void* pin[NB] = {};
     uint8_t* dbuf[NB] = {};
-    hipEvent_t h2d_ev[NB] = {}, h2d_t0[NB] = {}, used_ev[NB] = {};
-    hipStream_t copy_stream = nullptr;
+    Event h2d_ev[NB], h2d_t0[NB], used_ev[NB];
+    Stream copy_stream;
     Part meta[NB] = {};
     std::thread producer;
     std::mutex mu;

@@ -153,51 +153,26 @@ CopyPool& copy_pool() {
 }
 }  // namespace
 
-// Large host-buffer batches: three staging sets (pinned host + device buffers + a stream + an event each). While set b's
+// Large host-buffer batches: the three staging sets of HostPipe (aix_handle.hpp). While set b's
 // chunk is on the wire / in the kernel, the host threads fill the next set and drain the one before: H2D, kernel, D2H and the
 // two host copies of different chunks overlap. (Round 1 staged synchronously from pageable memory: 25-35 GB/s in.)
-struct HostPipe {
-    static constexpr int S = 3;
-    static constexpr uint64_t kChunkQ = 2ull << 20;          // queries per chunk
-    static constexpr uint64_t kInBytes = kChunkQ * 23 + 64, kOutBytes = kChunkQ * 8;
-    void* hin[S] = {};
-    void* din[S] = {};
-    void* hout[S][3] = {};
-    void* dout[S][3] = {};
-    hipStream_t st[S] = {};
-    hipEvent_t ev[S] = {};
-    bool ok = false;
-    int init() {
-        for (int b = 0; b < S; ++b) {
-            if (hipHostMalloc(&hin[b], kInBytes, hipHostMallocDefault) != hipSuccess) return AIX_ERR_NOMEM;
-            if (hipMalloc(&din[b], kInBytes) != hipSuccess) return AIX_ERR_NOMEM;
-            if (hipStreamCreateWithFlags(&st[b], hipStreamNonBlocking) != hipSuccess) return AIX_ERR_HIP;
-            if (hipEventCreateWithFlags(&ev[b], hipEventDisableTiming) != hipSuccess) return AIX_ERR_HIP;
-        }
-        ok = true;
-        return AIX_OK;
+static int pipe_init(HostPipe& P) {
+    for (int b = 0; b < HostPipe::S; ++b) {
+        if (P.hin[b].alloc(HostPipe::kInBytes, hipHostMallocDefault) != hipSuccess) return AIX_ERR_NOMEM;
+        if (P.din[b].alloc(HostPipe::kInBytes) != hipSuccess) return AIX_ERR_NOMEM;
+        if (P.st[b].create() != hipSuccess) return AIX_ERR_HIP;
+        if (P.ev[b].create() != hipSuccess) return AIX_ERR_HIP;
     }
-    int need_out(int j) {
-        for (int b = 0; b < S; ++b) {
-            if (hout[b][j]) continue;
-            if (hipHostMalloc(&hout[b][j], kOutBytes, hipHostMallocDefault) != hipSuccess) return AIX_ERR_NOMEM;
-            if (hipMalloc(&dout[b][j], kOutBytes) != hipSuccess) return AIX_ERR_NOMEM;
-        }
-        return AIX_OK;
+    return AIX_OK;
+}
+static int pipe_need_out(HostPipe& P, int j) {
+    for (int b = 0; b < HostPipe::S; ++b) {
+        if (P.hout[b][j].p) continue;
+        if (P.hout[b][j].alloc(HostPipe::kOutBytes, hipHostMallocDefault) != hipSuccess) return AIX_ERR_NOMEM;
+        if (P.dout[b][j].alloc(HostPipe::kOutBytes) != hipSuccess) return AIX_ERR_NOMEM;
     }
-    ~HostPipe() {
-        for (int b = 0; b < S; ++b) {
-            if (st[b]) (void)hipStreamSynchronize(st[b]);
-            if (hin[b]) (void)hipHostFree(hin[b]);
-            if (din[b]) (void)hipFree(din[b]);
-            for (int j = 0; j < 3; ++j) { if (hout[b][j]) (void)hipHostFree(hout[b][j]); if (dout[b][j]) (void)hipFree(dout[b][j]); }
-            if (ev[b]) (void)hipEventDestroy(ev[b]);
-            if (st[b]) (void)hipStreamDestroy(st[b]);
-        }
-    }
-};
-
-void free_host_pipe(HostPipe* p) { delete p; }
+    return AIX_OK;
+}
 
 static uint64_t pipe_fail_chunk() {                       // test hook, read once: the chunk of a large host batch whose launch "fails"
     static const uint64_t c = env_u64("AIX_PIPE_TEST_FAIL_CHUNK", 0, ~0ull, ~0ull);
@@ -209,21 +184,19 @@ template <typename F>
 static int pipelined_host_batch(aix_index_t* h, const char* in, uint32_t in_elem, uint64_t N, const uint32_t out_elem[3], void* const outs[3], F&& call) {
     std::lock_guard<std::mutex> lk(h->pipe_mutex);          // one large host batch per handle at a time (they would share the wire anyway)
     if (!h->pipe) {
-        h->pipe = new (std::nothrow) HostPipe();
-        if (!h->pipe) return AIX_ERR_NOMEM;
-        const int st = h->pipe->init();
-        if (st) { delete h->pipe; h->pipe = nullptr; (void)hipGetLastError(); return st; }
+        std::unique_ptr<HostPipe> fresh(new (std::nothrow) HostPipe());
+        if (!fresh) return AIX_ERR_NOMEM;
+        const int st = pipe_init(*fresh);
+        if (st) { fresh.reset(); (void)hipGetLastError(); return st; }
+        h->pipe = std::move(fresh);
     }
     HostPipe& P = *h->pipe;
     for (int j = 0; j < 3; ++j)
-        if (outs[j]) { const int st = P.need_out(j); if (st) { (void)hipGetLastError(); return st; } }
+        if (outs[j]) { const int st = pipe_need_out(P, j); if (st) { (void)hipGetLastError(); return st; } }
     // every exit but the last one leaves with copies / kernels possibly queued on the pipe's streams; they touch the handle's staging
     // buffers (and caller-pinned outputs), which the next call reuses at once: a failing call drains the streams before it returns
-    struct DrainOnError {
-        HostPipe& P;
-        bool armed = true;
-        ~DrainOnError() { if (armed) for (int i = 0; i < HostPipe::S; ++i) (void)hipStreamSynchronize(P.st[i]); }
-    } drain_on_error{P};
+    static_assert(HostPipe::S == 3, "the guard names every stream of the pipe");
+    DrainOnError<3> drain_on_error{{&P.st[0], &P.st[1], &P.st[2]}};
     CopyPool& pool = copy_pool();
     // buffers the caller has already pinned (hipHostMalloc / hipHostRegister, e.g. torch pinned tensors) go over the wire as they
     // are; only pageable memory is staged through the pipe's own pinned buffers
@@ -242,7 +215,7 @@ static int pipelined_host_batch(aix_index_t* h, const char* in, uint32_t in_elem
         HIPCHK(hipEventSynchronize(P.ev[b]));
         const uint64_t lo = c * chunk, m = std::min(chunk, N - lo);
         for (int j = 0; j < 3; ++j)
-            if (outs[j] && !out_pinned[j]) pool.copy((char*)outs[j] + lo * out_elem[j], P.hout[b][j], m * out_elem[j]);
+            if (outs[j] && !out_pinned[j]) pool.copy((char*)outs[j] + lo * out_elem[j], P.hout[b][j].p, m * out_elem[j]);
         return AIX_OK;
     };
     for (uint64_t c = 0; c < nchunks; ++c) {
@@ -250,16 +223,16 @@ static int pipelined_host_batch(aix_index_t* h, const char* in, uint32_t in_elem
         if (c >= (uint64_t)HostPipe::S) { const int st = drain(c - HostPipe::S); if (st) return st; }
         const uint64_t lo = c * chunk, m = std::min(chunk, N - lo);
         if (in_pinned) {
-            HIPCHK(hipMemcpyAsync(P.din[b], in + lo * in_elem, m * in_elem, hipMemcpyHostToDevice, P.st[b]));
+            HIPCHK(hipMemcpyAsync(P.din[b].p, in + lo * in_elem, m * in_elem, hipMemcpyHostToDevice, P.st[b]));
         } else {
-            pool.copy(P.hin[b], in + lo * in_elem, m * in_elem);
-            HIPCHK(hipMemcpyAsync(P.din[b], P.hin[b], m * in_elem, hipMemcpyHostToDevice, P.st[b]));
+            pool.copy(P.hin[b].p, in + lo * in_elem, m * in_elem);
+            HIPCHK(hipMemcpyAsync(P.din[b].p, P.hin[b].p, m * in_elem, hipMemcpyHostToDevice, P.st[b]));
         }
-        int st = call((const char*)P.din[b], m, P.dout[b][0], P.dout[b][1], P.dout[b][2], (void*)P.st[b]);
+        int st = call((const char*)P.din[b].p, m, P.dout[b][0].p, P.dout[b][1].p, P.dout[b][2].p, (void*)P.st[b].s);
         if (!st && c == pipe_fail_chunk()) st = AIX_ERR_HIP;                  // AIX_PIPE_TEST_FAIL_CHUNK: fault injection (tests)
         if (st) return st;
         for (int j = 0; j < 3; ++j)
-            if (outs[j]) HIPCHK(hipMemcpyAsync(out_pinned[j] ? (void*)((char*)outs[j] + lo * out_elem[j]) : P.hout[b][j], P.dout[b][j], m * out_elem[j],
+            if (outs[j]) HIPCHK(hipMemcpyAsync(out_pinned[j] ? (void*)((char*)outs[j] + lo * out_elem[j]) : P.hout[b][j].p, P.dout[b][j].p, m * out_elem[j],
                                                hipMemcpyDeviceToHost, P.st[b]));
         HIPCHK(hipEventRecord(P.ev[b], P.st[b]));
     }
@@ -273,19 +246,12 @@ static int pipelined_host_batch(aix_index_t* h, const char* in, uint32_t in_elem
 // ---------------------------------------------------------------------------------------------
 static constexpr uint64_t kSmall = 4096;         // up to here a host batch goes through the pinned, device-mapped staging of the handle
 
-static int ensure_pinned(aix_index_t* h) {
-    if (h->pin_in) return AIX_OK;
-    void* in = nullptr;
-    if (hipHostMalloc(&in, kSmall * 23 + 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }
-    for (int j = 0; j < 3; ++j)
-        if (hipHostMalloc(&h->pin_out[j], kSmall * 8, hipHostMallocMapped) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int i = 0; i < j; ++i) { (void)hipHostFree(h->pin_out[i]); h->pin_out[i] = nullptr; }
-            (void)hipHostFree(in);
-            return AIX_ERR_NOMEM;
-        }
-    memset(in, '\n', kSmall * 23 + 64);
-    h->pin_in = in;
+static int ensure_pinned(SmallBatch& sm) {
+    if (sm.out[2].p) return AIX_OK;                        // the last one taken: all four are there
+    hipError_t e = sm.in.alloc(kSmall * 23 + 64, hipHostMallocMapped);
+    for (int j = 0; j < 3 && e == hipSuccess; ++j) e = sm.out[j].alloc(kSmall * 8, hipHostMallocMapped);
+    if (e != hipSuccess) { (void)hipGetLastError(); return AIX_ERR_NOMEM; }   // what was taken stays with the handle; the next call asks for the rest
+    memset(sm.in.p, '\n', kSmall * 23 + 64);
     return AIX_OK;
 }
 
@@ -295,19 +261,20 @@ static int chunked_ascii(aix_index_t* h, const char* kmers, uint64_t N, const ui
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
     if (N <= kSmall) {                                     // latency path: the kernel reads the queries from, and writes the answers to, host memory
-        std::lock_guard<std::mutex> lk(h->small_mutex);
-        if (ensure_pinned(h) == AIX_OK) {
+        SmallBatch& sm = h->small;
+        std::lock_guard<std::mutex> lk(sm.mutex);
+        if (ensure_pinned(sm) == AIX_OK) {
             void *din = nullptr, *dout[3] = {nullptr, nullptr, nullptr};
-            hipError_t e = hipHostGetDevicePointer(&din, h->pin_in, 0);
-            for (int j = 0; j < 3 && e == hipSuccess; ++j) e = hipHostGetDevicePointer(&dout[j], h->pin_out[j], 0);
+            hipError_t e = hipHostGetDevicePointer(&din, sm.in.p, 0);
+            for (int j = 0; j < 3 && e == hipSuccess; ++j) e = hipHostGetDevicePointer(&dout[j], sm.out[j].p, 0);
             if (e == hipSuccess) {
-                memcpy(h->pin_in, kmers, N * h->k);
-                if (!h->small_stream && hipStreamCreateWithFlags(&h->small_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); h->small_stream = nullptr; }
-                int st = call((const char*)din, N, dout[0], dout[1], dout[2], (void*)h->small_stream);   // own stream: no implicit ordering with the null stream
+                memcpy(sm.in.p, kmers, N * h->k);
+                if (sm.stream.create() != hipSuccess) (void)hipGetLastError();                 // (then the null stream)
+                int st = call((const char*)din, N, dout[0], dout[1], dout[2], (void*)sm.stream.s);   // own stream: no implicit ordering with the null stream
                 if (st) return st;
-                HIPCHK(hipStreamSynchronize(h->small_stream));
+                HIPCHK(hipStreamSynchronize(sm.stream));
                 for (int j = 0; j < 3; ++j)
-                    if (outs[j]) memcpy(outs[j], h->pin_out[j], N * out_elem_bytes[j]);
+                    if (outs[j]) memcpy(outs[j], sm.out[j].p, N * out_elem_bytes[j]);
                 return AIX_OK;
             }
             (void)hipGetLastError();
@@ -405,12 +372,13 @@ extern "C" int aix_coverage_batch(aix_index_t* h, const char* seqs, const uint64
     // latency path (one read, one contig window...): sequences, offsets and the profile live in pinned, device-mapped memory
     constexpr uint64_t kCovSeq = 128u << 10, kCovM = 1024, kCovPin = kCovSeq + 64 + 2 * 8 * (kCovM + 1) + 4 * kCovSeq;
     if (total <= kCovSeq && M <= kCovM && ototal <= kCovSeq) {
-        std::lock_guard<std::mutex> lk(h->small_mutex);
-        if (!h->pin_cov && hipHostMalloc(&h->pin_cov, kCovPin, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); h->pin_cov = nullptr; }
+        SmallBatch& sm = h->small;
+        std::lock_guard<std::mutex> lk(sm.mutex);
+        if (sm.cov.alloc(kCovPin, hipHostMallocMapped) != hipSuccess) (void)hipGetLastError();
         void* dbase = nullptr;
-        if (h->pin_cov && hipHostGetDevicePointer(&dbase, h->pin_cov, 0) == hipSuccess) {
-            if (!h->small_stream && hipStreamCreateWithFlags(&h->small_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); h->small_stream = nullptr; }
-            char* hp = (char*)h->pin_cov;
+        if (sm.cov.p && hipHostGetDevicePointer(&dbase, sm.cov.p, 0) == hipSuccess) {
+            if (sm.stream.create() != hipSuccess) (void)hipGetLastError();                     // (then the null stream)
+            char* hp = (char*)sm.cov.p;
             uint64_t* hoffs = (uint64_t*)(hp + kCovSeq + 64);
             uint64_t* hooffs = hoffs + (kCovM + 1);
             uint32_t* hout = (uint32_t*)(hooffs + (kCovM + 1));
@@ -420,9 +388,9 @@ extern "C" int aix_coverage_batch(aix_index_t* h, const char* seqs, const uint64
             memset(hout, 0, 4 * ototal);
             char* dp = (char*)dbase;
             int st = aix_coverage_batch_dev(h, dp, (const uint64_t*)(dp + ((char*)hoffs - hp)), M, total, cutoff, (uint32_t*)(dp + ((char*)hout - hp)),
-                                            (const uint64_t*)(dp + ((char*)hooffs - hp)), (void*)h->small_stream);
+                                            (const uint64_t*)(dp + ((char*)hooffs - hp)), (void*)sm.stream.s);
             if (st) return st;
-            HIPCHK(hipStreamSynchronize(h->small_stream));
+            HIPCHK(hipStreamSynchronize(sm.stream));
             memcpy(out + obase, hout, 4 * ototal);
             return AIX_OK;
         }

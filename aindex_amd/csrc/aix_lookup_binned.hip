@@ -592,13 +592,6 @@ __global__ void __launch_bounds__(LBC_FB) k_lb_filter_coarse(const uint64_t* __r
 // ---------------------------------------------------------------------------------------------
 static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-void lookup_binned_release(aix_index* h) {
-    if (h->lb_done) { (void)hipEventSynchronize(h->lb_done); (void)hipEventDestroy(h->lb_done); h->lb_done = nullptr; }
-    if (h->lb_ws) { (void)hipFree(h->lb_ws); h->lb_ws = nullptr; h->lb_ws_bytes = 0; }
-    if (h->lb_stats) { (void)hipFree(h->lb_stats); h->lb_stats = nullptr; }
-    if (h->lb_coarse) { (void)hipFree(h->lb_coarse); h->lb_coarse = nullptr; h->lb_coarse_bytes = 0; h->lb_coarse_src = nullptr; }
-}
-
 // AIX_TAKEN: the batch is enqueued (binned kernels and, in auto mode, the gated direct kernel); AIX_NOT_TAKEN: the caller runs the
 // direct path; anything else is an error status
 int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t N, uint32_t* out, hipStream_t s) {
@@ -629,56 +622,52 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
     const uint32_t cstride = (uint32_t)align_up(g.wps, 16);
     const uint64_t need_coarse = (uint64_t)g.nbins * cstride;
 
-    std::lock_guard<std::mutex> lk(h->lb_mutex);               // orders the enqueueing; the event orders the streams
-    if (!h->lb_done && hipEventCreateWithFlags(&h->lb_done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); h->lb_done = nullptr; return AIX_LB_NOT_TAKEN; }
-    if (!h->lb_stats) {
-        if (hipMalloc((void**)&h->lb_stats, 8 * LB_NSTATS) != hipSuccess) { (void)hipGetLastError(); h->lb_stats = nullptr; return AIX_LB_NOT_TAKEN; }
-        HIPCHK(hipMemset(h->lb_stats, 0, 8 * LB_NSTATS));
+    BinnedState& lb = h->lb;
+    std::lock_guard<std::mutex> lk(lb.mutex);                  // orders the enqueueing; the event orders the streams
+    if (lb.done.create() != hipSuccess) { (void)hipGetLastError(); return AIX_LB_NOT_TAKEN; }
+    if (!lb.stats) {
+        if (lb.stats.alloc(8 * LB_NSTATS) != hipSuccess) { (void)hipGetLastError(); return AIX_LB_NOT_TAKEN; }
+        HIPCHK(hipMemset(lb.stats.p, 0, 8 * LB_NSTATS));
     }
-    if (coarse && need_coarse > h->lb_coarse_bytes) {          // as the workspace below: grow only, behind the kernels of earlier calls
-        if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
-        if (h->lb_coarse) { (void)hipFree(h->lb_coarse); h->lb_coarse = nullptr; }
-        h->lb_coarse_bytes = 0;
-        h->lb_coarse_src = nullptr;
-        if (hipMalloc((void**)&h->lb_coarse, need_coarse) != hipSuccess) { (void)hipGetLastError(); h->lb_coarse = nullptr; coarse = false; }   // no room: pass B without the image
-        else h->lb_coarse_bytes = need_coarse;
+    // both blocks grow only, behind the kernels of earlier calls, which may still be using the old block
+    hipError_t waited = hipSuccess;                            // a failed wait is an error; a block that cannot be had is not
+    auto wait = [&] { return waited = lb.used ? hipEventSynchronize(lb.done) : hipSuccess; };
+    if (coarse && need_coarse > lb.coarse.bytes) {
+        const hipError_t e = lb.coarse.ensure(need_coarse, 0, wait);
+        HIPCHK(waited);
+        lb.coarse_src = nullptr;
+        if (e != hipSuccess) { (void)hipGetLastError(); coarse = false; }   // no room: pass B without the image
     }
-    if (need > h->lb_ws_bytes) {                               // grow only; the kernels of earlier calls may still be using the old block
-        if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
-        if (h->lb_ws) { (void)hipFree(h->lb_ws); h->lb_ws = nullptr; h->lb_ws_bytes = 0; }
-        if (hipMalloc(&h->lb_ws, need) != hipSuccess) { (void)hipGetLastError(); h->lb_ws = nullptr; return AIX_LB_NOT_TAKEN; }
-        h->lb_ws_bytes = need;
-    }
-    if (h->lb_used && h->lb_stream != s) HIPCHK(hipStreamWaitEvent(s, h->lb_done, 0));
-    h->lb_used = true;
-    h->lb_stream = s;
-    struct RecordOnExit {                                       // also behind a failed launch: what was enqueued before it uses the workspace
-        hipEvent_t ev; hipStream_t s;
-        ~RecordOnExit() { (void)hipEventRecord(ev, s); }
-    } record_on_exit{h->lb_done, s};
+    const hipError_t e_ws = lb.ws.ensure(need, 0, wait);
+    HIPCHK(waited);
+    if (e_ws != hipSuccess) { (void)hipGetLastError(); return AIX_LB_NOT_TAKEN; }
+    if (lb.used && lb.stream != s) HIPCHK(hipStreamWaitEvent(s, lb.done, 0));
+    lb.used = true;
+    lb.stream = s;
+    RecordOnExit record_on_exit{lb.done, s};                    // also behind a failed launch: what was enqueued before it uses the workspace
 
     // pass A's static LDS is 38 KiB: with the carry of more than 128 slices it may pass 64 KiB (two workgroups per CU then)
     if (carry_bytes > (16u << 10)) HIPCHK(hipFuncSetAttribute((const void*)k_lb_bin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)carry_bytes));
-    uint8_t* const base = (uint8_t*)h->lb_ws;
+    uint8_t* const base = lb.ws.as<uint8_t>();
     LbWs w;
     w.hdr = (uint32_t*)base;
     w.list = (uint32_t*)(base + off_list);
     w.cnt = (uint32_t*)(base + off_cnt);
     w.rec = (uint64_t*)(base + off_rec);
-    w.stats = (unsigned long long*)h->lb_stats;
+    w.stats = lb.stats.as<unsigned long long>();
     const uint64_t test_grid_b = env_u64("AIX_LOOKUP_TEST_GRID_B", 1, LB_GRID_B, LB_GRID_B);   // fewer workgroups: many tickets each on a small batch
     const unsigned grid_b = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)g.nbins * cap + LB_CPT - 1) / LB_CPT, 1), test_grid_b);
     const unsigned grid_c = (unsigned)std::min<uint64_t>(std::max<uint64_t>((uint64_t)g.nbins * ((cap + LBC_CPT - 1) / LBC_CPT), 1), std::min<uint64_t>(test_grid_b, LBC_GRID));
     if (coarse) {
         // the image is folded once per filter and slice width, on the stream of the first call that needs it: a handle's filter does not
         // change while it is open (switching it off and on again, or moving it, leaves its words as they were)
-        if (h->lb_coarse_src != d.bloom || h->lb_coarse_nbloom != d.nbloom || h->lb_coarse_wps != g.wps) {
+        if (lb.coarse_src != d.bloom || lb.coarse_nbloom != d.nbloom || lb.coarse_wps != g.wps) {
             hipLaunchKernelGGL(k_lb_fold, dim3((unsigned)std::min<uint64_t>((need_coarse + 255) / 256, 4096)), dim3(256), 0, s, d.bloom, d.nbloom, g.wps, cstride,
-                               g.nbins, h->lb_coarse);
+                               g.nbins, lb.coarse.as<uint8_t>());
             HIPCHK(hipGetLastError());
-            h->lb_coarse_src = d.bloom;
-            h->lb_coarse_nbloom = d.nbloom;
-            h->lb_coarse_wps = g.wps;
+            lb.coarse_src = d.bloom;
+            lb.coarse_nbloom = d.nbloom;
+            lb.coarse_wps = g.wps;
         }
         // 26 KiB of static LDS beside the image
         if (cstride > (16u << 10)) HIPCHK(hipFuncSetAttribute((const void*)k_lb_filter_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cstride));
@@ -695,7 +684,7 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
         if (sw != 2) HIPCHK(launch_lookup23_ascii(d, qp, m, MODE_TF, LookupOut{op, nullptr, nullptr, nullptr}, s, w.hdr + LB_FLAG));
         hipLaunchKernelGGL(k_lb_bin, dim3(std::min<unsigned>(grid_a, (m + LB_TILE - 1) / LB_TILE)), dim3(LB_TB), carry_bytes, s, d.nbloom, qp, m, g, w, op);
         HIPCHK(hipGetLastError());
-        if (coarse) hipLaunchKernelGGL(k_lb_filter_coarse, dim3(grid_c), dim3(LBC_FB), cstride, s, d.bloom, d.nbloom, (const uint8_t*)h->lb_coarse, cstride, g, w);
+        if (coarse) hipLaunchKernelGGL(k_lb_filter_coarse, dim3(grid_c), dim3(LBC_FB), cstride, s, d.bloom, d.nbloom, lb.coarse.as<const uint8_t>(), cstride, g, w);
         else hipLaunchKernelGGL(k_lb_filter, dim3(grid_b), dim3(LB_FB), 0, s, d.bloom, d.nbloom, g, w);
         HIPCHK(hipGetLastError());
         HIPCHK(launch_lookup23_list(d, qp, w.list, w.hdr + LB_NSURV, m, w.hdr + LB_FLAG, op, w.stats + 3, s));
@@ -706,21 +695,21 @@ int lookup23_binned(aix_index* h, const IndexDev& d, const uint8_t* q, uint64_t 
 extern "C" int aix_lookup_binned_stats(aix_index_t* h, uint64_t out[4]) {
     if (!h || !out) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    std::lock_guard<std::mutex> lk(h->lb_mutex);
+    std::lock_guard<std::mutex> lk(h->lb.mutex);
     for (int i = 0; i < 4; ++i) out[i] = 0;
-    if (!h->lb_stats) return AIX_OK;
-    if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
-    HIPCHK(hipMemcpy(out, h->lb_stats, 32, hipMemcpyDeviceToHost));
+    if (!h->lb.stats) return AIX_OK;
+    if (h->lb.used) HIPCHK(hipEventSynchronize(h->lb.done));
+    HIPCHK(hipMemcpy(out, h->lb.stats.p, 32, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
 
 extern "C" int aix_lookup_binned_coarse_stats(aix_index_t* h, uint64_t out[2]) {
     if (!h || !out) return AIX_ERR_ARG;
     DevGuard g(h->device);
-    std::lock_guard<std::mutex> lk(h->lb_mutex);
+    std::lock_guard<std::mutex> lk(h->lb.mutex);
     out[0] = out[1] = 0;
-    if (!h->lb_stats) return AIX_OK;
-    if (h->lb_used) HIPCHK(hipEventSynchronize(h->lb_done));
-    HIPCHK(hipMemcpy(out, h->lb_stats + 4, 16, hipMemcpyDeviceToHost));
+    if (!h->lb.stats) return AIX_OK;
+    if (h->lb.used) HIPCHK(hipEventSynchronize(h->lb.done));
+    HIPCHK(hipMemcpy(out, h->lb.stats.as<uint64_t>() + 4, 16, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

@@ -233,7 +233,7 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     AIX_TRY(hipMemsetAsync((uint32_t*)cnt.p + C, 0, 4, s));
     AIX_TRY(hipMemsetAsync(kept.p, 0, 8 * (N + 1), s));
     PqFlat P{};
-    P.positions = h->ai_positions; P.ne = (const uint64_t*)ne.p; P.nfo = (const uint64_t*)nfo.p; P.nlo = (const uint64_t*)nlo.p;
+    P.positions = h->att.ai_positions.as<uint64_t>(); P.ne = (const uint64_t*)ne.p; P.nfo = (const uint64_t*)nfo.p; P.nlo = (const uint64_t*)nlo.p;
     P.J = J; P.T = T; P.C = C; P.bits = (uint64_t*)bits.p; P.cnt = (uint32_t*)cnt.p; P.wr = (const uint64_t*)wr.p; P.nraw = (const uint64_t*)nraw.p;
     P.offsets = d_offsets; P.m = m;
     AIX_TRY_LAUNCH(k_pq_flat<false>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
@@ -254,7 +254,8 @@ hipError_t posquery_lists(aix_index* h, const uint64_t* d_lo, const uint64_t* d_
     P.out = d_positions;
     if (d_rid) {
         P.rid_out = d_rid; P.local_out = d_local;
-        P.rs = h->rx; P.re = h->rx + h->rx_n; P.rr = h->rx + 2 * h->rx_n; P.rn = h->rx_n;
+        const uint64_t* const rx = h->att.rx.as<uint64_t>();
+        P.rs = rx; P.re = rx + h->att.rx_n; P.rr = rx + 2 * h->att.rx_n; P.rn = h->att.rx_n;
     }
     AIX_TRY_LAUNCH(k_pq_flat<true>, dim3(pq_flat_grid(C)), dim3(kB), 0, s, P);
     return hipStreamSynchronize(s);                            // the scratch blocks go back to the pool idle
@@ -266,15 +267,17 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
     *total_out = 0;
     if (N == 0) return hipMemsetAsync(d_offsets, 0, 8, s);
     const IndexDev ix = h->dev();
+    const uint64_t* const indices = h->att.ai_indices.as<uint64_t>();
+    const uint64_t total = h->att.ai_total;
     DevArr lo(s), ub(s);
     AIX_TRY(lo.alloc(8 * N));
     AIX_TRY(ub.alloc(8 * (N + 1)));
     uint64_t* d_ub = (uint64_t*)ub.p;
     AIX_TRY(hipMemsetAsync(d_ub + N, 0, 8, s));
-    if (h->k == 13) AIX_TRY_LAUNCH(k_pq_resolve13, dim3(flat_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 2) AIX_TRY_LAUNCH(k_pq_resolve23<2>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else if (ix.bk_lpp == 4) AIX_TRY_LAUNCH(k_pq_resolve23<4>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
-    else AIX_TRY_LAUNCH(k_pq_resolve23<8>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, h->ai_indices, h->ai_total, (uint64_t*)lo.p, d_ub);
+    if (h->k == 13) AIX_TRY_LAUNCH(k_pq_resolve13, dim3(flat_grid(N)), dim3(kB), 0, s, ix.perm13, d_kmers, N, indices, total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 2) AIX_TRY_LAUNCH(k_pq_resolve23<2>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, indices, total, (uint64_t*)lo.p, d_ub);
+    else if (ix.bk_lpp == 4) AIX_TRY_LAUNCH(k_pq_resolve23<4>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, indices, total, (uint64_t*)lo.p, d_ub);
+    else AIX_TRY_LAUNCH(k_pq_resolve23<8>, dim3(flat_grid(N)), dim3(kB), 0, s, ix, d_kmers, N, indices, total, (uint64_t*)lo.p, d_ub);
     return posquery_lists(h, (const uint64_t*)lo.p, d_ub, N, m, d_offsets, d_positions, d_rid, d_local, cap, total_out, s);
 }
 
@@ -283,23 +286,10 @@ hipError_t posquery_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint64
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-static void pq_detach_aindex(aix_index* h) {
-    if (h->ai_owned) {
-        if (h->ai_indices) (void)hipFree(h->ai_indices);
-        if (h->ai_positions) (void)hipFree(h->ai_positions);
-        h->device_bytes -= 8 * (h->n + 1) + 8 * h->ai_total;
-    }
-    h->ai_indices = h->ai_positions = nullptr;
-    h->ai_total = 0;
-    h->ai_attached = h->ai_owned = false;
-}
-
-void posquery_release(aix_index* h) {
-    pq_detach_aindex(h);
-    if (h->rx) { (void)hipFree(h->rx); h->device_bytes -= 24 * h->rx_n; }
-    h->rx = nullptr;
-    h->rx_n = 0;
-    h->rx_attached = false;
+static void pq_detach_aindex(Attachments& a) {
+    a.ai_indices.reset();
+    a.ai_positions.reset();
+    a.ai_total = 0;
 }
 
 static int pq_validate(aix_index* h, const uint64_t* d_indices, uint64_t total, hipStream_t s) {
@@ -318,26 +308,23 @@ extern "C" int aix_aindex_attach(aix_index_t* h, const uint64_t* indices, const 
     if (!h || !indices || (total && !positions)) return AIX_ERR_ARG;
     if (total >= (1ull << 60)) return AIX_ERR_NOMEM;
     DevGuard g(h->device);
-    uint64_t *di = nullptr, *dp = nullptr;
-    hipError_t e = hipMalloc((void**)&di, 8 * (h->n + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dp, total ? 8 * total : 8);
-    if (e != hipSuccess) {                                     // never a partial copy
+    HBlock di, dp;                                             // never a partial copy: what is not attached below is freed here
+    hipError_t e = di.alloc(8 * (h->n + 1));
+    if (e == hipSuccess) e = dp.alloc(total ? 8 * total : 8, 8 * total);
+    if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (di) (void)hipFree(di);
         if (e == hipErrorOutOfMemory) return AIX_ERR_NOMEM;
         set_last_error(std::string("hipMalloc: ") + hipGetErrorString(e));
         return AIX_ERR_HIP;
     }
-    e = hipMemcpy(di, indices, 8 * (h->n + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess && total) e = hipMemcpy(dp, positions, 8 * total, hipMemcpyHostToDevice);
-    int st = AIX_OK;
-    if (e != hipSuccess) { set_last_error(std::string("hipMemcpy: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
-    if (!st) st = pq_validate(h, di, total, 0);
-    if (st) { (void)hipFree(di); (void)hipFree(dp); return st; }
-    pq_detach_aindex(h);
-    h->ai_indices = di; h->ai_positions = dp; h->ai_total = total;
-    h->ai_attached = h->ai_owned = true;
-    h->device_bytes += 8 * (h->n + 1) + 8 * total;
+    e = hipMemcpy(di.p, indices, 8 * (h->n + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess && total) e = hipMemcpy(dp.p, positions, 8 * total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_last_error(std::string("hipMemcpy: ") + hipGetErrorString(e)); return AIX_ERR_HIP; }
+    if (const int st = pq_validate(h, di.as<uint64_t>(), total, 0)) return st;
+    pq_detach_aindex(h->att);
+    h->att.ai_indices.attach_owned(std::move(di));
+    h->att.ai_positions.attach_owned(std::move(dp));
+    h->att.ai_total = total;
     return AIX_OK;
 }
 
@@ -346,9 +333,10 @@ extern "C" int aix_aindex_attach_dev(aix_index_t* h, const uint64_t* d_indices, 
     DevGuard g(h->device);
     const int st = pq_validate(h, d_indices, total, (hipStream_t)stream);
     if (st) return st;
-    pq_detach_aindex(h);
-    h->ai_indices = const_cast<uint64_t*>(d_indices); h->ai_positions = const_cast<uint64_t*>(d_positions); h->ai_total = total;
-    h->ai_attached = true; h->ai_owned = false;
+    pq_detach_aindex(h->att);
+    h->att.ai_indices.attach_borrowed(d_indices);
+    h->att.ai_positions.attach_borrowed(d_positions);
+    h->att.ai_total = total;
     return AIX_OK;
 }
 
@@ -356,7 +344,9 @@ extern "C" int aix_aindex_detach(aix_index_t* h) {
     if (!h) return AIX_ERR_ARG;
     DevGuard g(h->device);
     (void)hipDeviceSynchronize();
-    posquery_release(h);
+    pq_detach_aindex(h->att);
+    h->att.rx.drop();
+    h->att.rx_n = 0;
     return AIX_OK;
 }
 
@@ -381,23 +371,19 @@ extern "C" int aix_ridx_attach(aix_index_t* h, const uint64_t* triples, uint64_t
         soa[n_reads + i] = triples[3 * i + 2];
         soa[2 * n_reads + i] = triples[3 * i];
     }
-    uint64_t* d = nullptr;
-    AIXCHK(hipMalloc((void**)&d, n_reads ? 24 * n_reads : 8));
-    if (n_reads) {
-        const hipError_t e = hipMemcpy(d, soa.data(), 24 * n_reads, hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(d);
-        AIXCHK(e);
-    }
-    if (h->rx) { (void)hipDeviceSynchronize(); (void)hipFree(h->rx); h->device_bytes -= 24 * h->rx_n; }
-    h->rx = d; h->rx_n = n_reads; h->rx_attached = true;
-    h->device_bytes += 24 * n_reads;
+    HBlock d;
+    AIXCHK(d.alloc(n_reads ? 24 * n_reads : 8, 24 * n_reads));
+    if (n_reads) AIXCHK(hipMemcpy(d.p, soa.data(), 24 * n_reads, hipMemcpyHostToDevice));
+    if (h->att.rx) (void)hipDeviceSynchronize();
+    h->att.rx = std::move(d);
+    h->att.rx_n = n_reads;
     return AIX_OK;
 }
 
 extern "C" int aix_positions_query_dev(aix_index_t* h, const char* d_kmers, uint64_t N, uint64_t max_per_kmer, uint64_t* d_offsets, uint64_t* d_positions,
                                        uint64_t* d_rid, uint64_t* d_local, uint64_t cap, uint64_t* total_out, void* stream) {
     if (!h || !d_offsets || !total_out || (N && !d_kmers) || ((d_rid == nullptr) != (d_local == nullptr))) return AIX_ERR_ARG;
-    if (!h->ai_attached || (d_rid && !h->rx_attached)) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
+    if (!h->att.ai_indices.attached || (d_rid && !h->att.rx)) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
     if (h->k == 23 && h->n == 0) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
     AIXCHK(posquery_run(h, (const uint8_t*)d_kmers, N, max_per_kmer, d_offsets, cap ? d_positions : nullptr, d_rid, d_local, cap, total_out, (hipStream_t)stream));
@@ -409,7 +395,7 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
     if (!h || !offsets_out || !positions_out || (N && !kmers) || ((rid_out == nullptr) != (local_out == nullptr))) return AIX_ERR_ARG;
     *offsets_out = *positions_out = nullptr;
     if (rid_out) *rid_out = *local_out = nullptr;
-    if (!h->ai_attached || (rid_out && !h->rx_attached)) return AIX_ERR_ARG;
+    if (!h->att.ai_indices.attached || (rid_out && !h->att.rx)) return AIX_ERR_ARG;
     if (h->k == 23 && h->n == 0) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
     DevArr dq, doff, dpos, drid, dloc;
@@ -432,17 +418,17 @@ extern "C" int aix_positions_query(aix_index_t* h, const char* kmers, uint64_t N
 
 extern "C" int aix_positions_locate_dev(aix_index_t* h, const uint64_t* d_pos, uint64_t N, uint64_t* d_rid, uint64_t* d_start, void* stream) {
     if (!h || (N && (!d_pos || !d_rid || !d_start))) return AIX_ERR_ARG;
-    if (!h->rx_attached) return AIX_ERR_ARG;
+    if (!h->att.rx) return AIX_ERR_ARG;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
-    hipLaunchKernelGGL(k_pq_locate, dim3(flat_grid(N)), dim3(kB), 0, (hipStream_t)stream, d_pos, N, h->rx, h->rx + h->rx_n, h->rx + 2 * h->rx_n, h->rx_n, d_rid, d_start);
+    hipLaunchKernelGGL(k_pq_locate, dim3(flat_grid(N)), dim3(kB), 0, (hipStream_t)stream, d_pos, N, h->att.rx.as<uint64_t>(), h->att.rx.as<uint64_t>() + h->att.rx_n, h->att.rx.as<uint64_t>() + 2 * h->att.rx_n, h->att.rx_n, d_rid, d_start);
     AIXCHK(hipGetLastError());
     return AIX_OK;
 }
 
 extern "C" int aix_positions_locate(aix_index_t* h, const uint64_t* pos, uint64_t N, uint64_t* rid_out, uint64_t* start_out) {
     if (!h || (N && (!pos || !rid_out || !start_out))) return AIX_ERR_ARG;
-    if (!h->rx_attached) return AIX_ERR_ARG;
+    if (!h->att.rx) return AIX_ERR_ARG;
     if (N == 0) return AIX_OK;
     DevGuard g(h->device);
     DevArr dp, dr, ds;

@@ -185,7 +185,7 @@ static hipError_t rq_gather_run(aix_index* h, const uint64_t* d_src, const uint6
     *total_out = total;
     if (total == 0 || total > cap || !d_bytes) return hipSuccess;
     RqGather P{};
-    P.reads = h->rd; P.src = d_src; P.off = d_offsets; P.rc = d_rc; P.R = R; P.total = total; P.out = d_bytes;
+    P.reads = h->att.rd.as<uint8_t>(); P.src = d_src; P.off = d_offsets; P.rc = d_rc; P.R = R; P.total = total; P.out = d_bytes;
     if (d_rc) AIX_TRY_LAUNCH(k_rq_gather<true>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
     else AIX_TRY_LAUNCH(k_rq_gather<false>, dim3(rq_gather_grid(total)), dim3(kRB), 0, s, P);
     return hipStreamSynchronize(s);                            // the scratch blocks go back to the pool idle
@@ -323,8 +323,8 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     AIX_TRY(keep.alloc(T + 1));
     AIX_TRY(orank.alloc(8 * (T + 1)));
     AIX_TRY(hipMemsetAsync(flag.p, 0, 4, s));
-    const uint64_t rn = h->rx_n;
-    const uint64_t *rs = h->rx, *re = h->rx + rn, *rr = h->rx + 2 * rn;
+    const uint64_t rn = h->att.rx_n;
+    const uint64_t *rs = h->att.rx.as<uint64_t>(), *re = rs + rn, *rr = rs + 2 * rn;
     const uint64_t *d_off = (const uint64_t*)off.p, *d_lst = (const uint64_t*)lst.p, *d_key = (const uint64_t*)key.p;
     AIX_TRY_LAUNCH(k_rk_locate, dim3(flat_grid(T)), dim3(kRB), 0, s, d_off, N, (const uint64_t*)pos.p, T, rs, re, rn, (uint64_t*)lst.p, (uint64_t*)key.p);
     AIX_TRY_LAUNCH(k_rk_ascending, dim3(flat_grid(T)), dim3(kRB), 0, s, d_lst, d_key, T, (uint32_t*)flag.p);
@@ -351,7 +351,7 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
         AIX_TRY(rocprim::radix_sort_pairs(tmp.p, tb2, (const uint64_t*)k3.p, (uint64_t*)k2.p, (const uint64_t*)perm.p, (uint64_t*)p2.p, (size_t)T, 0u, lb, s));
         d_perm = (const uint64_t*)p2.p;
     }
-    AIX_TRY_LAUNCH(k_rk_first, dim3(flat_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->rd_len, (uint8_t*)flags.p);
+    AIX_TRY_LAUNCH(k_rk_first, dim3(flat_grid(T)), dim3(kRB), 0, s, d_perm, d_lst, d_key, T, rs, re, rr, rn, h->att.rd_len, (uint8_t*)flags.p);
     AIX_TRY(hipMemsetAsync((uint8_t*)flags.p + T, 0, 1, s));
     AIX_TRY(scan_u64(rocprim::make_transform_iterator((const uint8_t*)flags.p, RkFlagBit{(uint8_t)(m ? 1 : 0)}), (uint64_t*)rank.p, T + 1, t1, s));
     AIX_TRY_LAUNCH(k_rk_keep, dim3(flat_grid(T + 1)), dim3(kRB), 0, s, (const uint8_t*)flags.p, (const uint64_t*)rank.p, d_lst, d_off, T, m, (uint8_t*)keep.p);
@@ -364,7 +364,7 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
     AIX_TRY(len.alloc(8 * (R + 1)));
     *R_out = R;
     AIX_TRY_LAUNCH(k_rk_emit, dim3(flat_grid(std::max(T, N + 1))), dim3(kRB), 0, s, (const uint8_t*)keep.p, (const uint64_t*)orank.p, d_key, d_off, N, T, rs, re, rr, rn,
-                   h->rd_len, R, d_koff, (uint64_t*)rid.p, (uint64_t*)src.p, (uint64_t*)len.p);
+                   h->att.rd_len, R, d_koff, (uint64_t*)rid.p, (uint64_t*)src.p, (uint64_t*)len.p);
     return hipStreamSynchronize(s);
 }
 
@@ -373,38 +373,27 @@ static hipError_t rk_run(aix_index* h, const uint8_t* d_kmers, uint64_t N, uint6
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-void readsquery_release(aix_index* h) {
-    if (h->rd_owned) {
-        if (h->rd) (void)hipFree(h->rd);
-        h->device_bytes -= h->rd_len;
-    }
-    h->rd = nullptr;
-    h->rd_len = 0;
-    h->rd_attached = h->rd_owned = false;
+static void rq_detach(Attachments& a) {
+    a.rd.reset();
+    a.rd_len = 0;
 }
 
 extern "C" int aix_reads_attach(aix_index_t* h, const char* reads, uint64_t len) {
     if (!h || (len && !reads)) return AIX_ERR_ARG;
     if (len >= (1ull << 60)) return AIX_ERR_NOMEM;
     DevGuard g(h->device);
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, len ? len : 1);
+    HBlock d;
+    hipError_t e = d.alloc(len ? len : 1, len);
     if (e != hipSuccess) {                                     // nothing is kept; an earlier attachment stays
         (void)hipGetLastError();
         if (e == hipErrorOutOfMemory) return AIX_ERR_NOMEM;
         set_last_error(std::string("hipMalloc: ") + hipGetErrorString(e));
         return AIX_ERR_HIP;
     }
-    if (len) {
-        e = hipMemcpy(d, reads, len, hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(d);
-        AIXCHK(e);
-    }
+    if (len) AIXCHK(hipMemcpy(d.p, reads, len, hipMemcpyHostToDevice));
     (void)hipDeviceSynchronize();
-    readsquery_release(h);
-    h->rd = d; h->rd_len = len;
-    h->rd_attached = h->rd_owned = true;
-    h->device_bytes += len;
+    h->att.rd.attach_owned(std::move(d));
+    h->att.rd_len = len;
     return AIX_OK;
 }
 
@@ -413,9 +402,8 @@ extern "C" int aix_reads_attach_dev(aix_index_t* h, const char* d_reads, uint64_
     DevGuard g(h->device);
     AIXCHK(hipStreamSynchronize((hipStream_t)stream));          // what filled the buffer on `stream` has completed before any query reads it
     (void)hipDeviceSynchronize();
-    readsquery_release(h);
-    h->rd = reinterpret_cast<uint8_t*>(const_cast<char*>(d_reads)); h->rd_len = len;
-    h->rd_attached = true; h->rd_owned = false;
+    h->att.rd.attach_borrowed(d_reads);
+    h->att.rd_len = len;
     return AIX_OK;
 }
 
@@ -423,27 +411,27 @@ extern "C" int aix_reads_detach(aix_index_t* h) {
     if (!h) return AIX_ERR_ARG;
     DevGuard g(h->device);
     (void)hipDeviceSynchronize();
-    readsquery_release(h);
+    rq_detach(h->att);
     return AIX_OK;
 }
 
 extern "C" int aix_reads_info(const aix_index_t* h, uint64_t out[2]) {
     if (!h || !out) return AIX_ERR_ARG;
-    out[0] = h->rd_attached ? (h->rd_owned ? 1 : 2) : 0;
-    out[1] = h->rd_len;
+    out[0] = h->att.rd.attached ? (h->att.rd.owned ? 1 : 2) : 0;
+    out[1] = h->att.rd_len;
     return AIX_OK;
 }
 
 extern "C" int aix_reads_fetch_dev(aix_index_t* h, const uint64_t* d_start, const uint64_t* d_end, const uint8_t* d_revcomp, uint64_t N, uint64_t* d_offsets,
                                    char* d_bytes, uint64_t cap, uint64_t* total_out, void* stream) {
     if (!h || !d_offsets || !total_out || (N && (!d_start || !d_end))) return AIX_ERR_ARG;
-    if (!h->rd_attached) return AIX_ERR_ARG;                   // nothing attached: a defined error, never a fault
+    if (!h->att.rd.attached) return AIX_ERR_ARG;                   // nothing attached: a defined error, never a fault
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     DevArr src(s), len(s);
     AIXCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
     AIXCHK(len.alloc(8 * (N + 1)));
-    hipLaunchKernelGGL(k_rq_spans_fetch, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_start, d_end, N, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
+    hipLaunchKernelGGL(k_rq_spans_fetch, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_start, d_end, N, h->att.rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
     AIXCHK(hipGetLastError());
     AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, d_revcomp, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
     return AIX_OK;
@@ -452,20 +440,20 @@ extern "C" int aix_reads_fetch_dev(aix_index_t* h, const uint64_t* d_start, cons
 extern "C" int aix_reads_fetch_rid_dev(aix_index_t* h, const uint64_t* d_rid, uint64_t N, uint64_t* d_offsets, char* d_bytes, uint64_t cap, uint64_t* total_out,
                                        void* stream) {
     if (!h || !d_offsets || !total_out || (N && !d_rid)) return AIX_ERR_ARG;
-    if (!h->rd_attached || !h->rx_attached) return AIX_ERR_ARG;
+    if (!h->att.rd.attached || !h->att.rx) return AIX_ERR_ARG;
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     DevArr src(s), len(s);
     AIXCHK(src.alloc(8 * std::max<uint64_t>(N, 1)));
     AIXCHK(len.alloc(8 * (N + 1)));
-    hipLaunchKernelGGL(k_rq_spans_rid, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_rid, N, h->rx, h->rx + h->rx_n, h->rx_n, h->rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
+    hipLaunchKernelGGL(k_rq_spans_rid, dim3(flat_grid(N + 1)), dim3(kRB), 0, s, d_rid, N, h->att.rx.as<uint64_t>(), h->att.rx.as<uint64_t>() + h->att.rx_n, h->att.rx_n, h->att.rd_len, (uint64_t*)src.p, (uint64_t*)len.p);
     AIXCHK(hipGetLastError());
     AIXCHK(rq_gather_run(h, (const uint64_t*)src.p, (const uint64_t*)len.p, nullptr, N, d_offsets, cap ? (uint8_t*)d_bytes : nullptr, cap, total_out, s));
     return AIX_OK;
 }
 
 static int rk_check(const aix_index* h) {
-    if (!h->rd_attached || !h->rx_attached || !h->ai_attached) return AIX_ERR_ARG;
+    if (!h->att.rd.attached || !h->att.rx || !h->att.ai_indices.attached) return AIX_ERR_ARG;
     if (h->k == 23 && h->n == 0) return AIX_ERR_UNSUPPORTED;
     return AIX_OK;
 }
@@ -518,7 +506,7 @@ extern "C" int aix_reads_fetch(aix_index_t* h, const uint64_t* start, const uint
                                char** bytes_out) {
     if (!h || !offsets_out || !bytes_out || (N && (!start || !end))) return AIX_ERR_ARG;
     *offsets_out = nullptr; *bytes_out = nullptr;
-    if (!h->rd_attached) return AIX_ERR_ARG;
+    if (!h->att.rd.attached) return AIX_ERR_ARG;
     DevGuard g(h->device);
     DevArr in[3];                                              // start, end, revcomp (no block when none is given or N == 0)
     const HostIn ins[3] = {{start, 8 * N}, {end, 8 * N}, {N ? revcomp : nullptr, N}};
@@ -532,7 +520,7 @@ extern "C" int aix_reads_fetch(aix_index_t* h, const uint64_t* start, const uint
 extern "C" int aix_reads_fetch_rid(aix_index_t* h, const uint64_t* rid, uint64_t N, uint64_t** offsets_out, char** bytes_out) {
     if (!h || !offsets_out || !bytes_out || (N && !rid)) return AIX_ERR_ARG;
     *offsets_out = nullptr; *bytes_out = nullptr;
-    if (!h->rd_attached || !h->rx_attached) return AIX_ERR_ARG;
+    if (!h->att.rd.attached || !h->att.rx) return AIX_ERR_ARG;
     DevGuard g(h->device);
     DevArr dr;
     const HostIn in{rid, 8 * N};

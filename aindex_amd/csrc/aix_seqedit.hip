@@ -271,8 +271,8 @@ static hipError_t se_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     SeVerify P{};
     P.seqs = d_seqs; P.offs = d_offs; P.soff = (const uint64_t*)soff.p; P.M = M; P.T = T;
     P.pos = (const uint64_t*)B.pos.p; P.qoff = (const uint32_t*)B.qoff.p; P.flag = (const uint8_t*)B.flag.p;
-    P.reads = h->rd; P.reads_len = h->rd_len;
-    P.rs = h->rx; P.re = h->rx + h->rx_n; P.rr = h->rx + 2 * h->rx_n; P.rn = h->rx_n;
+    P.reads = h->att.rd.as<uint8_t>(); P.reads_len = h->att.rd_len;
+    P.rs = h->att.rx.as<uint64_t>(); P.re = P.rs + h->att.rx_n; P.rr = P.rs + 2 * h->att.rx_n; P.rn = h->att.rx_n;
     P.ed = ed;
     P.keep = (uint8_t*)keep.p; P.key = (uint64_t*)F.key.p; P.hseq = (uint64_t*)hseq.p; P.end = (uint64_t*)F.end.p; P.rid = (uint64_t*)F.rid.p;
     P.local = (uint64_t*)F.local.p;
@@ -296,7 +296,7 @@ static hipError_t se_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_
     AIX_TRY_LAUNCH(k_se_compact, dim3(flat_grid(T)), blk, 0, s, (const uint8_t*)keep.p, (const uint64_t*)srank.p, (const uint64_t*)F.key.p, T, (uint64_t*)ckey.p,
                    (uint64_t*)csrc.p);
     // least significant key first: (start, strand, dist, end), then the sequence; start < reads_len, so the key needs the bits of reads_len << 9
-    AIX_TRY(sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sort_bits((h->rd_len << (kSeLowBits + 1)) | 0x1FFull), tmp, s));
+    AIX_TRY(sort_pairs((const uint64_t*)ckey.p, (uint64_t*)kout.p, (const uint64_t*)csrc.p, (uint64_t*)pa.p, S, sort_bits((h->att.rd_len << (kSeLowBits + 1)) | 0x1FFull), tmp, s));
     AIX_TRY_LAUNCH((k_sv_gather<uint64_t, SvSame>), gS, blk, 0, s, (const uint64_t*)hseq.p, (const uint64_t*)pa.p, S, SvSame(), (uint64_t*)kin.p);
     AIX_TRY(sort_pairs((const uint64_t*)kin.p, (uint64_t*)kout.p, (const uint64_t*)pa.p, (uint64_t*)F.perm.p, S, sort_bits(M), tmp, s));
     const uint64_t* sseq = (const uint64_t*)kout.p;
@@ -328,7 +328,7 @@ extern "C" int aix_seq_edit_dev(aix_index_t* h, const char* d_seqs, const uint64
     if (!h || !d_find_offsets || !total_out || (M && !d_offs) || M >= (1ull << 56) || ed > AIX_SEQEDIT_MAX_ED) return AIX_ERR_ARG;
     if (cap && (!d_start || !d_end || !d_rid || !d_local || !d_strand || !d_dist)) return AIX_ERR_ARG;
     if (const int st = sh_check(h)) return st;
-    if (h->rd_len >= (1ull << 54)) return AIX_ERR_UNSUPPORTED;                 // start << 9 | .. is the sort key
+    if (h->att.rd_len >= (1ull << 54)) return AIX_ERR_UNSUPPORTED;                 // start << 9 | .. is the sort key
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     *total_out = 0;
@@ -353,7 +353,7 @@ extern "C" int aix_seq_edit(aix_index_t* h, const char* seqs, const uint64_t* of
     if (!offs) offs = &none;                                   // M == 0: find_offsets = {0}
     if (M && offs[M] && !seqs) return AIX_ERR_ARG;
     if (const int st = sh_check(h)) return st;
-    if (h->rd_len >= (1ull << 54)) return AIX_ERR_UNSUPPORTED;
+    if (h->att.rd_len >= (1ull << 54)) return AIX_ERR_UNSUPPORTED;
     DevGuard g(h->device);
     DevArr ds, dof, dfo, dp, de, dr, dl, dst, dd;
     if (const int st = sh_upload(seqs, offs, M, ds, dof)) return st;

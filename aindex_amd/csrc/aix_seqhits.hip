@@ -194,7 +194,7 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
     const IndexDev ix = h->dev();
     const uint64_t* woff = (const uint64_t*)B.woff.p;
 #define AIX_SH_RESOLVE(L)                                                                                                                              \
-    AIX_TRY_LAUNCH(k_sh_resolve<L>, dim3(flat_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->ai_indices, h->ai_total, (uint64_t*)wseq.p, \
+    AIX_TRY_LAUNCH(k_sh_resolve<L>, dim3(flat_grid(W)), dim3(kSB), 0, s, ix, d_seqs, d_offs, woff, M, W, step, h->att.ai_indices.as<uint64_t>(), h->att.ai_total, (uint64_t*)wseq.p, \
                    (uint64_t*)wsrc.p, (uint64_t*)lo.p, (uint64_t*)ub.p)
     if (ix.bk_lpp == 2) AIX_SH_RESOLVE(2);
     else if (ix.bk_lpp == 4) AIX_SH_RESOLVE(4);
@@ -209,8 +209,8 @@ hipError_t sh_run(aix_index* h, const uint8_t* d_seqs, const uint64_t* d_offs, u
         ShHits P{};
         P.seqs = d_seqs; P.woff = woff; P.koff = (const uint64_t*)B.koff.p; P.wseq = (const uint64_t*)wseq.p; P.wsrc = (const uint64_t*)wsrc.p;
         P.M = M; P.W = W; P.T = T; P.step = step;
-        P.reads = h->rd; P.reads_len = h->rd_len;
-        P.rs = h->rx; P.re = h->rx + h->rx_n; P.rr = h->rx + 2 * h->rx_n; P.rn = h->rx_n;
+        P.reads = h->att.rd.as<uint8_t>(); P.reads_len = h->att.rd_len;
+        P.rs = h->att.rx.as<uint64_t>(); P.re = P.rs + h->att.rx_n; P.rr = P.rs + 2 * h->att.rx_n; P.rn = h->att.rx_n;
         if (user) {
             P.pos = user->pos; P.qoff = user->qoff; P.rid = user->rid; P.local = user->local; P.flag = user->flag;
         } else {

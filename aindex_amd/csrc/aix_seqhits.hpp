@@ -94,7 +94,7 @@ __device__ __forceinline__ uint64_t sf_shfl64(uint64_t v, uint32_t src) {
 
 static int sh_check(const aix_index* h) {
     if (h->k != 23) return AIX_ERR_MODE;
-    if (!h->ai_attached || !h->rx_attached || !h->rd_attached) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
+    if (!h->att.ai_indices.attached || !h->att.rx || !h->att.rd.attached) return AIX_ERR_ARG;     // nothing attached: a defined error, never a fault
     if (h->n == 0) return AIX_ERR_UNSUPPORTED;
     return AIX_OK;
 }

@@ -340,7 +340,7 @@ __global__ void __launch_bounds__(kSB) k_sp_decode(const IndexDev ix_, const uin
 static hipError_t sp_values(const aix_index* h, uint32_t* d_out, hipStream_t s) {
     if (h->n == 0) return hipSuccess;
     const IndexDev ix = h->dev();
-    if (h->k == 13) hipLaunchKernelGGL(k_sp_narrow, dim3(sp_grid(h->n, 4 * kSB)), dim3(kSB), 0, s, h->tf13_mphf, h->n, d_out);
+    if (h->k == 13) hipLaunchKernelGGL(k_sp_narrow, dim3(sp_grid(h->n, 4 * kSB)), dim3(kSB), 0, s, h->tf13_mphf.as<uint64_t>(), h->n, d_out);
     else if (ix.canonical_only) hipLaunchKernelGGL(k_sp_values23<true>, dim3(sp_grid(h->n, kSB) * 8), dim3(kSB), 0, s, ix, d_out);
     else hipLaunchKernelGGL(k_sp_values23<false>, dim3(sp_grid(h->n, kSB) * 8), dim3(kSB), 0, s, ix, d_out);
     return hipGetLastError();
@@ -472,7 +472,7 @@ extern "C" int aix_tf_spectrum_dev(aix_index_t* h, uint64_t nbins, uint64_t* d_h
     DevGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     if (h->k == 13) {                                             // the table itself: the u32 view and the full-width statistics in one pass
-        AIXCHK(sp_spectrum((const uint64_t*)h->tf13_mphf, h->n, nbins, d_hist, d_stats, s));
+        AIXCHK(sp_spectrum(h->tf13_mphf.as<const uint64_t>(), h->n, nbins, d_hist, d_stats, s));
         return AIX_OK;
     }
     DevArr vals(s);
