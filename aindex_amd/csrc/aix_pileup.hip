@@ -259,8 +259,9 @@ __global__ void __launch_bounds__(kCB) k_pl_edges(const PlPlaces g, uint32_t* __
 }
 
 // One lane per read base of the flat space poff[R]: base i belongs to the last placement r with poff[r] <= i. The wave's first base is
-// searched by bisection (the same addresses in every lane), every lane gallops from there: a placement holds 23 bases or more, so a wave
-// meets at most three.
+// searched by bisection (the same addresses in every lane), every lane gallops from there. The cost, not a precondition: a placement that
+// aix_pile_place_dev made holds 23 bases or more, so a wave meets at most three and the gallop ends after a step or two. Shorter ones (the
+// validation admits len >= 1) only make it longer: poff ascends strictly, so the last r with poff[r] <= i is found whatever the lengths.
 __global__ void __launch_bounds__(kCB) k_pl_bases(uint64_t R, const uint64_t* __restrict__ poff, const uint64_t* __restrict__ rd0, const uint64_t* __restrict__ gs,
                                                  const uint8_t* __restrict__ seqs, const uint8_t* __restrict__ bases, uint32_t* __restrict__ counts,
                                                  uint32_t* __restrict__ place_mism, PlCounters* __restrict__ ctr) {
@@ -325,6 +326,10 @@ struct PlSite {
     bool polish, variant;
 };
 
+// 1000 c[alt] >= permille D, exactly, in 64 bits: a 32-bit threshold times D (up to 2^34 - 4) can pass 2^64 and wrap, but c[alt] <= D, so
+// above 1000 permille only D == 0 reaches it (0 >= 0), and up to 1000 the product stays below 2^44. The first test is wave-uniform.
+__device__ __forceinline__ bool pl_reaches(uint64_t a1000, uint32_t permille, uint64_t D) { return (permille <= 1000u || D == 0) && a1000 >= (uint64_t)permille * D; }
+
 __device__ __forceinline__ PlSite pl_site(const uint4 cell, uint32_t r, const PlThr& th) {
     const uint32_t c[4] = {cell.x, cell.y, cell.z, cell.w};
     PlSite s;
@@ -338,8 +343,8 @@ __device__ __forceinline__ PlSite pl_site(const uint4 cell, uint32_t r, const Pl
     s.c_alt = c[s.alt];
     const uint64_t a1000 = 1000ull * s.c_alt;
     const bool deep = s.D >= th.min_depth;
-    s.polish = deep && s.c_alt > s.c_ref && a1000 >= (uint64_t)th.min_major_permille * s.D;
-    s.variant = deep && s.c_alt >= th.min_alt_count && a1000 >= (uint64_t)th.min_alt_permille * s.D;
+    s.polish = deep && s.c_alt > s.c_ref && pl_reaches(a1000, th.min_major_permille, s.D);
+    s.variant = deep && s.c_alt >= th.min_alt_count && pl_reaches(a1000, th.min_alt_permille, s.D);
     return s;
 }
 

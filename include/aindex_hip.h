@@ -1131,7 +1131,8 @@ int aix_scaffold_fill(uint64_t U, const uint64_t* offsets, const uint8_t* bases,
  * 3. aix_pile_call_dev: counts become consensus, variant sites and depth. Inputs U, offsets, bases, counts (16-byte aligned) and
  *    min_depth, min_major_permille, min_alt_count, min_alt_permille.
  *    Per base g: r = the code of the contig base, c[0 .. 3] its cell, D = c[0] + c[1] + c[2] + c[3], alt = the channel other than r with
- *      the largest count, ties to the smaller code; every comparison in 64-bit integers.
+ *      the largest count, ties to the smaller code. D is summed in 64 bits, and both permille comparisons are exact whatever the
+ *      thresholds are: a product that passes 2^64 (a threshold near 2^32 on a D near 2^34) does not wrap.
  *      polished[g] = ACGT[alt] iff D >= min_depth, c[alt] > c[r] and 1000 c[alt] >= min_major_permille D; else the contig's base.
  *      g is a variant site iff D >= min_depth, c[alt] >= min_alt_count and 1000 c[alt] >= min_alt_permille D.
  *    Outputs, each nullable: polished u8[B] and *n_changed_out; the variant sites in ascending g — var_unitig u32, var_pos u32 (local),

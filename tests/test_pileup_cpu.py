@@ -189,6 +189,20 @@ def test_call_ties_thresholds_and_64_bit_sums():
     assert [out[k].tolist() for k in PR.VAR_KEYS] == [[0, 0, 0], [0, 1, 2], [65, 67, 71], [67, 65, 84], [2, 1, 0xFFFFFFFF], [5, 7, 0xFFFFFFFF],
                                                       [12, 8, 0xFFFFFFFF]]
     assert out["depth_sum"].tolist() == [12 + 8 + 2 * 0xFFFFFFFF + 7 + 8 + 16] and out["uncovered"].tolist() == [17]
+    # permille products beyond 2^64 are exact, not wrapped: at a threshold of 2^31 and D = 2^33 the product is 2^64, which 64 bits
+    # would store as 0, below 1000 c[alt] = 1000 (2^32 - 1)
+    M = 0xFFFFFFFF
+    cnt[:] = 0
+    cnt[4] = (M, M, 1, 1)                                          # A: D = 2^33, alt C; no variant site at min_alt_permille 2^31
+    cnt[8] = (M - 1, M, 2, 1)                                      # A: D = 2^33, alt C with c[alt] > c[r]; not polished at min_major_permille 2^31
+    loose = PR.call(off, bases, cnt.reshape(-1), 1, 400, 1, 50)
+    assert loose["var_pos"].tolist() == [4, 8] and loose["var_alt"].tolist() == [67, 67] and loose["var_depth"].tolist() == [M, M]
+    assert loose["polished"].tobytes() == b"ACGTACGTCCGT" + (b"ACGT" * 5 + b"ACG")[12:] and loose["n_changed"] == 1
+    out = PR.call(off, bases, cnt.reshape(-1), 1, 400, 1, 1 << 31)
+    assert out["total"] == 0 and out["n_changed"] == 1
+    out = PR.call(off, bases, cnt.reshape(-1), 1, 1 << 31, 1, 50)
+    assert out["n_changed"] == 0 and out["polished"].tobytes() == bases.tobytes() and out["var_pos"].tolist() == [4, 8]
+    assert out["depth_sum"].tolist() == [1 << 34] and out["uncovered"].tolist() == [21]
 
 
 @pytest.fixture(scope="module", params=(0, 3))
