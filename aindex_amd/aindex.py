@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import logging
 import os
+from collections import Counter
 from enum import IntEnum
 from typing import Iterator, List, Optional, Tuple
 
@@ -130,6 +131,42 @@ def format_gfa_paths(unitigs: dict, links: dict, support, thread: dict, names: L
                     yield f"P\t{name if part == 1 else f'{name}.{part}'}\t{','.join(seg[start:j])}\t*"
                     part += 1
                 start = j
+
+
+def _records(g: dict, text: Optional[str], min_kmers: int) -> Iterator[Tuple[int, str, int, bool]]:
+    """(id, sequence, tf_sum, circular) of the unitigs of `g` (numpy arrays offsets, bases, tf_sum, circular) with at least min_kmers
+    k-mers, in order; text: the bases to cut the sequences from when they are not g's own."""
+    off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii") if text is None else text
+    for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
+        if off[i + 1] - off[i] - 22 >= min_kmers:
+            yield i, text[off[i]:off[i + 1]], s, bool(c)
+
+
+def _contig_rows(g: dict, text: Optional[str] = None, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
+    """[(sequence, tf_sum, circular)] of _records"""
+    return [r[1:] for r in _records(g, text, min_kmers)]
+
+
+def _write_fasta(path: str, prefix: str, g: dict, text: Optional[str] = None, min_kmers: int = 1, suffix=None) -> int:
+    """One record >{prefix}{id} LN:i:{len} KC:i:{tf_sum} km:f:{tf_sum/m:.1f}[ circular]{suffix(id)} per entry of _records; returns the number
+    of records written."""
+    written = 0
+    with open(path, "w") as f:
+        for i, seq, s, c in _records(g, text, min_kmers):
+            ln = len(seq)
+            f.write(f">{prefix}{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}{suffix(i) if suffix else ''}\n{seq}\n")
+            written += 1
+    return written
+
+
+def _write_lines(path: str, lines) -> Counter:
+    """`lines` written with line ends; returns how many of them begin with each character."""
+    first = Counter()
+    with open(path, "w") as f:
+        for line in lines:
+            first[line[0]] += 1
+            f.write(line + "\n")
+    return first
 
 
 def iter_reads_by_kmer(kmer: str, aindex: "AIndex", k: int = 23):
@@ -552,10 +589,7 @@ class AIndex:
     def get_unitigs(self, cutoff: int = 0, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
         """[(sequence, tf_sum, circular)] of every maximal unitig with at least min_kmers k-mers, in unitig order (ascending first k-mer)."""
         self._req()
-        u = self._wrapper._need23().unitigs(cutoff)
-        off, text = u["offsets"].tolist(), u["bases"].tobytes().decode("ascii")
-        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(u["tf_sum"].tolist(), u["circular"].tolist()))
-                if off[i + 1] - off[i] - 22 >= min_kmers]
+        return _contig_rows(self._wrapper._need23().unitigs(cutoff), None, min_kmers)
 
     def get_unitig_of_kmers(self, kmers, cutoff: int = 0) -> List[Optional[Tuple[int, int, int]]]:
         """[(unitig, pos, strand)] per 23-mer through the kid lookup: the k-mer occupies bases [pos, pos + 23) of that unitig, as given
@@ -579,17 +613,7 @@ class AIndex:
     def write_unitigs(self, path: str, cutoff: int = 0, min_kmers: int = 1) -> int:
         """FASTA of get_unitigs: >u{id} LN:i:{len} KC:i:{tf_sum} km:f:{tf_sum/m:.1f}[ circular]; returns the number of records written."""
         self._req()
-        u = self._wrapper._need23().unitigs(cutoff)
-        off, text = u["offsets"].tolist(), u["bases"].tobytes().decode("ascii")
-        written = 0
-        with open(path, "w") as f:
-            for i, (s, c) in enumerate(zip(u["tf_sum"].tolist(), u["circular"].tolist())):
-                ln = off[i + 1] - off[i]
-                if ln - 22 < min_kmers:
-                    continue
-                f.write(f">u{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
-                written += 1
-        return written
+        return _write_fasta(path, "u", self._wrapper._need23().unitigs(cutoff), None, min_kmers)
 
     # ---- the unitig graph (Index.unitig_links; aix_unitigs.hip) ------------------------------------------
     def get_unitig_links(self, cutoff: int = 0) -> List[Tuple[int, str, int, str]]:
@@ -609,13 +633,8 @@ class AIndex:
         """GFA 1 of the unitig graph (format_gfa); returns (segments, links) written."""
         self._req()
         ix = self._wrapper._need23()
-        segments = links = 0
-        with open(path, "w") as f:
-            for line in format_gfa(ix.unitigs(cutoff), ix.unitig_links(cutoff)):
-                segments += line[0] == "S"
-                links += line[0] == "L"
-                f.write(line + "\n")
-        return segments, links
+        first = _write_lines(path, format_gfa(ix.unitigs(cutoff), ix.unitig_links(cutoff)))
+        return first["S"], first["L"]
 
     # ---- contigs (Index.graph_clean_t; aix_graphclean.hip) -----------------------------------------------
     def _contig_graph(self, cutoff: int, tip_max_kmers: int, bubble_max_kmers: int, rounds: int) -> dict:
@@ -630,36 +649,18 @@ class AIndex:
                     min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
         """[(sequence, tf_sum, circular)] of every contig with at least min_kmers k-mers, in contig order: the unitigs at `cutoff` after up to
         `rounds` rounds of tip clipping (tips of at most tip_max_kmers k-mers), bubble popping and recompaction."""
-        g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
-        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
-        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
-                if off[i + 1] - off[i] - 22 >= min_kmers]
+        return _contig_rows(self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds), None, min_kmers)
 
     def write_contigs(self, path: str, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, min_kmers: int = 1) -> int:
         """FASTA of get_contigs: >c{id} LN:i:{len} KC:i:{tf_sum} km:f:{tf_sum/m:.1f}[ circular]; returns the number of records written."""
-        g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
-        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
-        written = 0
-        with open(path, "w") as f:
-            for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
-                ln = off[i + 1] - off[i]
-                if ln - 22 < min_kmers:
-                    continue
-                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
-                written += 1
-        return written
+        return _write_fasta(path, "c", self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds), None, min_kmers)
 
     def write_contigs_gfa(self, path: str, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3) -> Tuple[int, int]:
         """GFA 1 of the cleaned graph through format_gfa (segments are named u{contig id}, as format_gfa names them); returns (segments,
         links) written."""
         g = self._contig_graph(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
-        segments = links = 0
-        with open(path, "w") as f:
-            for line in format_gfa(g, g):
-                segments += line[0] == "S"
-                links += line[0] == "L"
-                f.write(line + "\n")
-        return segments, links
+        first = _write_lines(path, format_gfa(g, g))
+        return first["S"], first["L"]
 
     # ---- threading (Index.seq_thread_t; aix_seqthread.hip) ------------------------------------------------
     def _thread(self, seqs, graph, cutoff: int, want_support: bool):
@@ -677,7 +678,7 @@ class AIndex:
         sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev) if want_support else None
         got = ix.seq_thread_t(graph, st, so, link_support=sup)
         thread = ix._graph_to_host(dict(zip(ix.THREAD_KEYS, got)))
-        return graph, thread, (ix._graph_to_host({"s": sup})["s"] if want_support else None)
+        return graph, thread, (ix._to_host(sup) if want_support else None)
 
     def thread_sequences(self, seqs, graph=None, cutoff: int = 0) -> List[List[tuple]]:
         """Per sequence its path through the graph: [(unitig, '+' | '-', pos, q_first, q_last, linked)] — windows q_first .. q_last follow
@@ -704,12 +705,7 @@ class AIndex:
         names = list(names) if names is not None else [f"seq{i}" for i in range(len(seqs))]
         if len(names) != len(seqs):
             raise ValueError("one name per sequence")
-        written = 0
-        with open(path, "w") as f:
-            for line in format_gfa_paths(g, g, sup, t, names):
-                written += line[0] == "P"
-                f.write(line + "\n")
-        return written
+        return _write_lines(path, format_gfa_paths(g, g, sup, t, names))["P"]
 
     # ---- repeat resolution (Index.graph_resolve_t; aix_graphresolve.hip) ---------------------------------
     RESOLVE_BATCH_BYTES = 64 << 20                                 # reads threaded per call
@@ -720,23 +716,13 @@ class AIndex:
         link support and transitions accumulated, weak links removed and repeats split, then one compaction under a zero mask"""
         self._req()
         import torch
-        from .engine import _ragged
         ix = self._wrapper._need23()
         graph = ix.thread_graph_t(cutoff, tip_max_kmers, bubble_max_kmers, rounds)
         dev = graph["node"].device
         sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev)
         pair = torch.zeros(16 * int(graph["U"]), dtype=torch.int64, device=dev)
-        batch, size = [], 0
-        reads = list(reads)
-        for i, r in enumerate(reads):
-            batch.append(r)
-            size += len(r)
-            if size >= self.RESOLVE_BATCH_BYTES or i + 1 == len(reads):
-                data, offs = _ragged(batch)
-                st = torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev)
-                steps = ix.seq_thread_t(graph, st, torch.from_numpy(offs.astype(np.int64)).to(dev), link_support=sup)
-                ix.thread_pairs_t(graph, steps, pair)
-                batch, size = [], 0
+        for st, so in self._batches(list(reads), dev, self.RESOLVE_BATCH_BYTES):
+            ix.thread_pairs_t(graph, ix.seq_thread_t(graph, st, so, link_support=sup), pair)
         g = ix.graph_resolve_t(graph, sup, pair, min_link_support, min_pair_support, max_pair_noise, compact=True)
         return ix._graph_to_host({k: g[k] for k in ix.GRAPH_KEYS})
 
@@ -747,24 +733,13 @@ class AIndex:
         and exit links pair up one to one (every pair seen min_pair_support times or more, every other combination at most
         max_pair_noise times) is split into one copy per pair, which the final compaction merges into its two neighbours."""
         g = self._resolved_graph(reads, cutoff, tip_max_kmers, bubble_max_kmers, rounds, min_link_support, min_pair_support, max_pair_noise)
-        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
-        return [(text[off[i]:off[i + 1]], s, bool(c)) for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
-                if off[i + 1] - off[i] - 22 >= min_kmers]
+        return _contig_rows(g, None, min_kmers)
 
     def write_resolved_contigs(self, path: str, reads, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
                                min_link_support: int = 2, min_pair_support: int = 2, max_pair_noise: int = 0, min_kmers: int = 1) -> int:
         """FASTA of get_resolved_contigs in the form of write_contigs; returns the number of records written."""
         g = self._resolved_graph(reads, cutoff, tip_max_kmers, bubble_max_kmers, rounds, min_link_support, min_pair_support, max_pair_noise)
-        off, text = g["offsets"].tolist(), g["bases"].tobytes().decode("ascii")
-        written = 0
-        with open(path, "w") as f:
-            for i, (s, c) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
-                ln = off[i + 1] - off[i]
-                if ln - 22 < min_kmers:
-                    continue
-                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if c else ''}\n{text[off[i]:off[i + 1]]}\n")
-                written += 1
-        return written
+        return _write_fasta(path, "c", g, None, min_kmers)
 
     # ---- pile-up (Index.pile_place_t .. pile_call_t; aix_pileup.hip) -------------------------------------
     def _pile(self, reads, graph, cutoff: int, tip_max_kmers: int, bubble_max_kmers: int, rounds: int, max_gap: int, extend: int, want_places: bool = False):
@@ -778,27 +753,16 @@ class AIndex:
         dev = graph["node"].device
         counts = torch.zeros(4 * graph["bases"].numel(), dtype=torch.int32, device=dev)
         stats, rows = [0, 0, 0], []
-        reads = list(reads)
-        batch, size = [], 0
-        for i, r in enumerate(reads):
-            batch.append(r)
-            size += len(r)
-            if size >= self.RESOLVE_BATCH_BYTES or i + 1 == len(reads):
-                from .engine import _ragged
-                data, offs = _ragged(batch)
-                st = torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev)
-                so = torch.from_numpy(offs.astype(np.int64)).to(dev)
-                places = ix.pile_place_t(graph, so, ix.seq_thread_t(graph, st, so), max_gap, extend)
-                got = ix.pileup_t(graph, st, so, places, counts)
-                stats = [a + b for a, b in zip(stats, got["stats"])]
-                if want_places:
-                    p = ix._graph_to_host({k: places[k] for k in ix.PLACE_KEYS})
-                    mism = ix._graph_to_host({"m": got["place_mism"]})["m"].tolist()
-                    spo = p["seq_place_off"].tolist()
-                    flat = list(zip(p["place_unitig"].tolist(), ["+-"[f & 1] for f in p["place_flag"].tolist()], p["place_pos"].tolist(), p["place_q0"].tolist(),
-                                    p["place_len"].tolist(), mism))
-                    rows += [flat[spo[j]:spo[j + 1]] for j in range(len(batch))]
-                batch, size = [], 0
+        for st, so in self._batches(list(reads), dev, self.RESOLVE_BATCH_BYTES):
+            places = ix.pile_place_t(graph, so, ix.seq_thread_t(graph, st, so), max_gap, extend)
+            got = ix.pileup_t(graph, st, so, places, counts)
+            stats = [a + b for a, b in zip(stats, got["stats"])]
+            if want_places:
+                p = ix._graph_to_host({k: places[k] for k in ix.PLACE_KEYS})
+                spo = p["seq_place_off"].tolist()
+                flat = list(zip(p["place_unitig"].tolist(), ["+-"[f & 1] for f in p["place_flag"].tolist()], p["place_pos"].tolist(), p["place_q0"].tolist(),
+                                p["place_len"].tolist(), ix._to_host(got["place_mism"]).tolist()))
+                rows += [flat[spo[j]:spo[j + 1]] for j in range(so.numel() - 1)]
         return graph, counts, stats, rows if want_places else None
 
     def get_read_placements(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
@@ -841,37 +805,22 @@ class AIndex:
         g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, 700, min_alt_count, min_alt_permille)
         rows = zip(c["var_unitig"].tolist(), c["var_pos"].tolist(), [chr(x) for x in c["var_ref"].tolist()], [chr(x) for x in c["var_alt"].tolist()],
                    c["var_ref_count"].tolist(), c["var_alt_count"].tolist(), c["var_depth"].tolist())
-        written = 0
-        with open(path, "w") as f:
-            for line in format_vcf(rows, np.diff(g["offsets"].astype(np.int64)).tolist()):
-                written += line[0] != "#"
-                f.write(line + "\n")
-        return written
+        first = _write_lines(path, format_vcf(rows, np.diff(g["offsets"].astype(np.int64)).tolist()))
+        return sum(first.values()) - first["#"]
 
     def get_polished_contigs(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
                              extend: int = 22, min_depth: int = 8, min_major_permille: int = 700, min_kmers: int = 1) -> List[Tuple[str, int, bool]]:
         """get_contigs with every base replaced where at least min_depth reads are piled and min_major_permille of them or more show one
         other base: [(sequence, tf_sum, circular)]. An end product: the overlaps between linked contigs are not kept consistent."""
         g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, 3, 200)
-        off, text = g["offsets"].tolist(), c["polished"].tobytes().decode("ascii")
-        return [(text[off[i]:off[i + 1]], s, bool(ci)) for i, (s, ci) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist()))
-                if off[i + 1] - off[i] - 22 >= min_kmers]
+        return _contig_rows(g, c["polished"].tobytes().decode("ascii"), min_kmers)
 
     def write_polished_contigs(self, path: str, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
                                max_gap: int = 46, extend: int = 22, min_depth: int = 8, min_major_permille: int = 700, min_kmers: int = 1) -> int:
         """FASTA of get_polished_contigs: the header of write_contigs plus PC:i:{bases changed}; returns the number of records written."""
         g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, 3, 200)
-        off, text, old = g["offsets"].tolist(), c["polished"].tobytes().decode("ascii"), g["bases"]
-        written = 0
-        with open(path, "w") as f:
-            for i, (s, ci) in enumerate(zip(g["tf_sum"].tolist(), g["circular"].tolist())):
-                ln = off[i + 1] - off[i]
-                if ln - 22 < min_kmers:
-                    continue
-                changed = int((c["polished"][off[i]:off[i + 1]] != old[off[i]:off[i + 1]]).sum())
-                f.write(f">c{i} LN:i:{ln} KC:i:{s} km:f:{s / (ln - 22):.1f}{' circular' if ci else ''} PC:i:{changed}\n{text[off[i]:off[i + 1]]}\n")
-                written += 1
-        return written
+        off, differs = g["offsets"].tolist(), c["polished"] != g["bases"]
+        return _write_fasta(path, "c", g, c["polished"].tobytes().decode("ascii"), min_kmers, lambda i: f" PC:i:{int(differs[off[i]:off[i + 1]].sum())}")
 
     # ---- scaffolding (Index.mate_links_t .. scaffold_t; aix_scaffold.hip) --------------------------------
     def _pairs(self, pairs) -> list:
@@ -889,15 +838,17 @@ class AIndex:
             out.append((a.encode("latin-1") if isinstance(a, str) else bytes(a), b.encode("latin-1") if isinstance(b, str) else bytes(b)))
         return out
 
-    def _batches(self, seqs, dev):
-        """device (bytes, offsets) of `seqs` in batches of RESOLVE_BATCH_BYTES, each an even number of sequences"""
+    @staticmethod
+    def _batches(seqs, dev, limit: int, even: bool = False):
+        """(bytes, offsets) tensors on `dev` of `seqs` (a list) in batches: one closes with the sequence that brings it to `limit` bytes
+        (callers pass RESOLVE_BATCH_BYTES) — with `even` only on an even number of sequences, so that mates stay together — and with the last"""
         import torch
         from .engine import _ragged
         batch, size = [], 0
         for i, r in enumerate(seqs):
             batch.append(r)
             size += len(r)
-            if (size >= self.RESOLVE_BATCH_BYTES and len(batch) % 2 == 0) or i + 1 == len(seqs):
+            if (size >= limit and not (even and len(batch) % 2)) or i + 1 == len(seqs):
                 data, offs = _ragged(batch)
                 yield torch.from_numpy(data.copy() if data.shape[0] else np.zeros(0, np.uint8)).to(dev), torch.from_numpy(offs.astype(np.int64)).to(dev)
                 batch, size = [], 0
@@ -915,7 +866,7 @@ class AIndex:
         dev = graph["node"].device
         sup = torch.zeros(int(graph["E"]), dtype=torch.int64, device=dev)
         pair = torch.zeros(16 * int(graph["U"]), dtype=torch.int64, device=dev)
-        for st, so in self._batches([m for p in self._pairs(pairs) for m in p], dev):
+        for st, so in self._batches([m for p in self._pairs(pairs) for m in p], dev, self.RESOLVE_BATCH_BYTES, even=True):
             ix.thread_pairs_t(graph, ix.seq_thread_t(graph, st, so, link_support=sup), pair)
         merged = ix.graph_resolve_t(graph, sup, pair, compact=True)
         ku = graph["kid_unitig"].clone()
@@ -936,7 +887,7 @@ class AIndex:
         graph = self.scaffold_graph(pairs, cutoff, tip_max_kmers, bubble_max_kmers, rounds, resolve)
         dev = graph["node"].device
         hist, keys, ds = None, [], []
-        for st, so in self._batches([m for p in pairs for m in p], dev):
+        for st, so in self._batches([m for p in pairs for m in p], dev, self.RESOLVE_BATCH_BYTES, even=True):
             key, d, _, hist = ix.mate_links_t(graph, ix.seq_thread_t(graph, st, so), so, min_anchor_windows, max_insert, hist)
             keys.append(key)
             ds.append(d)

@@ -113,7 +113,7 @@ def test_shapes(acc, ref, pats):
     assert ix.seq_edit([b"", b"", b""])[0].tolist() == [0, 0, 0, 0] and ix.seq_edit([])[0].tolist() == [0]
     ps = [_lib.vp() for _ in range(7)]                          # M = 0 without sequences or offsets: find_offsets = {0}
     _lib.check(_lib.lib().aix_seq_edit(ix._h, None, None, 0, 1, 23, 0, *[C.byref(p) for p in ps]), "aix_seq_edit")
-    assert ix._take_as(ps[0], 1, np.uint64).tolist() == [0] and all(ix._take_as(p, 0, np.uint8).shape == (0,) for p in ps[1:])
+    assert ix._take(ps[0], 1, np.uint64).tolist() == [0] and all(ix._take(p, 0, np.uint8).shape == (0,) for p in ps[1:])
 
 
 BAND_LENGTHS = (23, 24, 63, 64, 65, 127, 128, 129, 255, 256, 257, 699, 700)
