@@ -22,6 +22,7 @@ AIX_ERR_CONFLICT = -12
 AIX_ERR_ARG = -1
 AIX_ERR_FORMAT = -3
 AIX_ERR_NOMEM = -4
+AIX_ERR_HIP = -5
 AIX_ERR_UNSUPPORTED = -6
 AIX_ERR_MODE = -7
 FMT_AUTO, FMT_PLAIN, FMT_FASTA, FMT_FASTQ = -1, 0, 1, 2

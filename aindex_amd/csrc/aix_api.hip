@@ -1,15 +1,16 @@
 // aix_api.hip — what the C ABI of libaindex_hip.so (include/aindex_hip.h) has outside the subsystems: version and error text, device
-// count, pinned host memory, scratch trim, self-test and debug hooks, the synthetic generators and two stand-alone kernels' entry points.
+// count, pinned host memory, scratch trim, self-test and debug hooks, the synthetic generators and two stand-alone kernels (window codes,
+// the random-gather roofline probe), each kernel above its entry point.
 // Every subsystem keeps its own entry points: aix_index.hip (handles), aix_lookup.hip, aix_count.hip, aix_normalize.hip,
 // aix_positions.hip, aix_posquery.hip, aix_merge.hip (distinct k-mers), aix_ingest.hip (files and host buffers of the counters).
 #include <string>
 
 #include "aix_handle.hpp"
 #include "aix_ingest.hpp"
+#include "aix_launch.hpp"
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
-
 
 // ---------------------------------------------------------------------------------------------
 extern "C" const char* aix_version(void) { return "aindex_hip 0.1.0 (gfx950)"; }
@@ -137,11 +138,20 @@ extern "C" int aix_debug_filter_words(aix_index_t* h, uint64_t* out, uint64_t nw
     return AIX_OK;
 }
 
+namespace aix {
+// self-test of wave_lower_bound_pair (aix_device.hpp): wave w of the grid looks up keys[w] and keys[w] + 1 in the sorted array
+__global__ void __launch_bounds__(64) k_selftest_lower_bound(const uint16_t* __restrict__ a, uint32_t n, const uint32_t* __restrict__ keys, uint32_t* __restrict__ out) {
+    const uint32_t r = wave_lower_bound_pair(a, n, keys[blockIdx.x]);
+    if ((threadIdx.x & 31u) == 0) out[2 * blockIdx.x + (threadIdx.x >> 5)] = r;
+}
+}  // namespace aix
 // GPU self-test hook of the suite: lower bounds of keys[i] and keys[i] + 1 in a sorted u16 array, by the wave-wide search the partition kernels
 // use to find a partition's chunks (out[2 i], out[2 i + 1]); all pointers are device pointers
 extern "C" int aix_selftest_lower_bound_dev(const uint16_t* d_sorted, uint32_t n, const uint32_t* d_keys, uint32_t nkeys, uint32_t* d_out, void* stream) {
     if ((n && !d_sorted) || (nkeys && (!d_keys || !d_out))) return AIX_ERR_ARG;
-    HIPCHK(launch_selftest_lower_bound(d_sorted, n, d_keys, nkeys, d_out, (hipStream_t)stream));
+    if (nkeys == 0) return AIX_OK;
+    hipLaunchKernelGGL(k_selftest_lower_bound, dim3(nkeys), dim3(64), 0, (hipStream_t)stream, d_sorted, n, d_keys, d_out);
+    HIPCHK(hipGetLastError());
     return AIX_OK;
 }
 
@@ -153,6 +163,56 @@ extern "C" int aix_debug_pointers(const aix_index_t* h, uint64_t out[5]) {
     return AIX_OK;
 }
 
+namespace aix {
+// K1 front end (count_kmers.cpp:93-136,297-308): the canonical 2-bit code of every window of a PLAIN
+// buffer, ~0 where the window holds a non-base byte. Distinct counting = sort + run-length of this.
+template <int K>
+__global__ void __launch_bounds__(kBlock) k_window_codes(const uint8_t* __restrict__ buf, uint64_t len, int k, int canon_mode, uint64_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    if (len < (uint64_t)k) return;
+    const uint64_t nwin = len - k + 1;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < nwin; p += stride) {
+        uint64_t code = 0;
+        bool valid = true;
+        if (K == 23) {
+            uint64_t w0, w1, w2;
+            load23(buf + p, w0, w1, w2);
+            w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+            w1 = u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
+            w2 = u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
+            const Enc23 e = encode23_words(w0, w1, w2);
+            code = e.code; valid = e.valid;
+        } else if (K == 13) {
+            uint64_t w0, w1;
+            load13(buf + p, w0, w1);
+            w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+            w1 = u_to_t(w1 & 0x000000DFDFDFDFDFULL);
+            const Enc13 e = encode13_words(w0, w1);
+            code = e.code; valid = e.valid;
+        } else {
+            for (int j = 0; j < k; ++j) {
+                uint32_t c = buf[p + j] & 0xDFu;
+                c = c == 'U' ? 'T' : c;
+                const uint32_t v = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+                if (v == 4u) { valid = false; break; }
+                code = (code << 2) | v;
+            }
+        }
+        if (valid) {
+            if (canon_mode == 1) { const uint64_t x = revcomp_refx86(code, k); code = code < x ? code : x; }
+            else if (canon_mode == 2) { const uint64_t x = revcomp(code, k); code = code < x ? code : x; }
+        }
+        out[p] = valid ? code : ~0ULL;
+    }
+}
+hipError_t launch_window_codes(const uint8_t* buf, uint64_t len, int k, int canon_mode, uint64_t* out, hipStream_t s) {
+    if (len < (uint64_t)k) return hipSuccess;
+    if (k == 23) return launch_flat(k_window_codes<23>, len - k + 1, s, buf, len, k, canon_mode, out);
+    if (k == 13) return launch_flat(k_window_codes<13>, len - k + 1, s, buf, len, k, canon_mode, out);
+    return launch_flat(k_window_codes<0>, len - k + 1, s, buf, len, k, canon_mode, out);
+}
+}  // namespace aix
+
 extern "C" int aix_window_codes_dev(const char* d_plain, uint64_t len, int k, int canon_mode, uint64_t* d_codes, void* stream) {
     if ((len && !d_plain) || k < 1 || k > 32 || canon_mode < 0 || canon_mode > 2) return AIX_ERR_ARG;
     if (len < (uint64_t)k) return AIX_OK;
@@ -161,32 +221,145 @@ extern "C" int aix_window_codes_dev(const char* d_plain, uint64_t len, int k, in
     return AIX_OK;
 }
 
+namespace aix {
+// ---------------------------------------------------------------------------------------------
+// synthetic inputs (bit-identical to aindex_amd/synth.py)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t sm64(uint64_t seed, uint64_t idx) {
+    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+__global__ void __launch_bounds__(kBlock) k_synth_genome(uint64_t seed, uint64_t length, uint8_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < length; j += stride) {
+        const uint64_t v = sm64(seed, j >> 5);
+        out[j] = (uint8_t)(AIX_LUT_ACGT >> (8 * ((v >> (2 * (j & 31))) & 3)));
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_synth_kmers(uint64_t seed, uint64_t first, uint64_t N, int k, uint8_t* __restrict__ out) {
+    const uint64_t total = N * (uint64_t)k, stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t i = t / (uint64_t)k, j = t - i * (uint64_t)k;
+        const uint64_t v = sm64(seed, first + i);
+        out[t] = (uint8_t)(AIX_LUT_ACGT >> (8 * ((v >> (2 * (k - 1 - (int)j))) & 3)));
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_synth_reads(uint64_t seed, const uint8_t* __restrict__ genome, uint64_t glen, uint64_t first_read, uint64_t n_reads,
+                                                       uint32_t read_len, int rc_half, uint32_t n_ppm, uint8_t* __restrict__ out) {
+    const uint64_t rec = (uint64_t)read_len + 1, total = n_reads * rec, stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t span = glen - read_len + 1;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t ri = t / rec, j = t - ri * rec;
+        if (j == read_len) { out[t] = '\n'; continue; }
+        const uint64_t r = first_read + ri;
+        const uint64_t v = sm64(seed, 2 * r);
+        const uint64_t start = ((v >> 32) * span) >> 32;
+        uint8_t ch;
+        if (rc_half && (sm64(seed, 2 * r + 1) & 1)) {
+            const uint8_t g = genome[start + (read_len - 1 - j)];
+            ch = g == 'A' ? 'T' : g == 'C' ? 'G' : g == 'G' ? 'C' : g == 'T' ? 'A' : g;
+        } else {
+            ch = genome[start + j];
+        }
+        if (n_ppm) {
+            const uint64_t h = sm64(seed ^ 0x5851F42D4C957F2DULL, r * read_len + j);
+            if ((((h >> 32) * 1000000ULL) >> 32) < n_ppm) ch = 'N';
+        }
+        out[t] = ch;
+    }
+}
+
+// Q_mix of SURVEY §8d: query i is, with probability 1/2, a 23-mer window of the genome at a uniform position on a
+// uniform strand, else a uniform-random 23-mer.
+__global__ void __launch_bounds__(kBlock) k_synth_mix23(uint64_t seed, const uint8_t* __restrict__ genome, uint64_t glen, uint64_t first, uint64_t N,
+                                                       uint8_t* __restrict__ out) {
+    const uint64_t total = N * 23, stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t span = glen - 22;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t i = t / 23, j = t - i * 23;
+        const uint64_t v = sm64(seed, first + i);
+        uint8_t ch;
+        if (v & 1) {
+            const uint64_t r = sm64(seed ^ 0xA5A5A5A5ULL, first + i);
+            ch = (uint8_t)(AIX_LUT_ACGT >> (8 * ((r >> (2 * (22 - (int)j))) & 3)));
+        } else {
+            const uint64_t pos = ((v >> 32) * span) >> 32;
+            if (v & 2) {
+                const uint8_t g = genome[pos + 22 - j];
+                ch = g == 'A' ? 'T' : g == 'C' ? 'G' : g == 'G' ? 'C' : g == 'T' ? 'A' : g;
+            } else {
+                ch = genome[pos + j];
+            }
+        }
+        out[t] = ch;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// random-gather roofline probe: uniform-random ELEM-byte reads over a large table,
+// UNROLL independent reads in flight per lane. The denominator the lookup kernels are judged against.
+// ---------------------------------------------------------------------------------------------
+template <int ELEM, int UNROLL>
+__global__ void __launch_bounds__(kBlock) k_gather(const uint8_t* __restrict__ table, uint64_t n_elems, uint64_t n_access, uint64_t seed, uint64_t* __restrict__ sink) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock * UNROLL;
+    uint64_t acc = 0;
+    for (uint64_t i = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * UNROLL; i < n_access; i += stride) {
+        uint64_t idx[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) idx[u] = ((sm64(seed, i + u) >> 32) * n_elems) >> 32;
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            if (ELEM >= 32) {                                   // the whole element: ELEM / 16 loads of 16 bytes (a 64-byte half line, a 128-byte line)
+                const uint4* p = (const uint4*)(table + idx[u] * (uint64_t)ELEM);
+#pragma unroll
+                for (int t = 0; t < ELEM / 16; ++t) { const uint4 v = p[t]; acc += (uint64_t)v.x ^ v.w; }
+            } else if (ELEM == 16) {
+                const BvRec r = ((const BvRec*)table)[idx[u]];
+                acc += r.fp ^ r.prefix;
+            } else if (ELEM == 8) {
+                acc += ((const uint64_t*)table)[idx[u]];
+            } else {
+                acc += ((const uint32_t*)table)[idx[u]];
+            }
+        }
+    }
+    if (acc == 0x1234567887654321ULL) sink[0] = acc;   // keeps the loads alive; practically never taken
+}
+}  // namespace aix
+
 extern "C" int aix_bench_gather_dev(const void* d_table, uint64_t n_elems, int elem_bytes, int unroll, uint64_t n_access, uint64_t seed, uint64_t* d_sink,
                                     void* stream) {
     if (!d_table || !d_sink || n_elems == 0 || (n_elems >> 32)) return AIX_ERR_ARG;
-    HIPCHK(launch_gather((const uint8_t*)d_table, n_elems, elem_bytes, unroll, n_access, seed, d_sink, (hipStream_t)stream));
+    if (n_access == 0) return AIX_OK;
+    hipError_t gather_launch = hipErrorInvalidValue;                           // an (elem_bytes, unroll) pair that is not instantiated
+#define G(E, U) if (elem_bytes == E && unroll == U) gather_launch = launch_flat(k_gather<E, U>, (n_access + U - 1) / U, (hipStream_t)stream, (const uint8_t*)d_table, n_elems, n_access, seed, d_sink)
+    G(16, 1); G(16, 4); G(8, 1); G(8, 4); G(4, 1); G(4, 4); G(32, 1); G(64, 1); G(128, 1);
+#undef G
+    HIPCHK(gather_launch);
     return AIX_OK;
 }
 
 extern "C" int aix_synth_genome_dev(uint64_t seed, uint64_t length, char* d_out, void* stream) {
     if (length && !d_out) return AIX_ERR_ARG;
-    HIPCHK(launch_synth_genome(seed, length, (uint8_t*)d_out, (hipStream_t)stream));
+    if (length) HIPCHK(launch_flat(k_synth_genome, length, (hipStream_t)stream, seed, length, (uint8_t*)d_out));
     return AIX_OK;
 }
 extern "C" int aix_synth_kmers_dev(uint64_t seed, uint64_t first, uint64_t N, int k, char* d_out, void* stream) {
     if ((N && !d_out) || k < 1 || k > 32) return AIX_ERR_ARG;
-    HIPCHK(launch_synth_kmers(seed, first, N, k, (uint8_t*)d_out, (hipStream_t)stream));
+    if (N) HIPCHK(launch_flat(k_synth_kmers, N * (uint64_t)k, (hipStream_t)stream, seed, first, N, k, (uint8_t*)d_out));
     return AIX_OK;
 }
 extern "C" int aix_synth_mix23_dev(uint64_t seed, const char* d_genome, uint64_t genome_len, uint64_t first, uint64_t N, char* d_out, void* stream) {
     if (!d_genome || (N && !d_out) || genome_len < 23) return AIX_ERR_ARG;
-    HIPCHK(launch_synth_mix23(seed, (const uint8_t*)d_genome, genome_len, first, N, (uint8_t*)d_out, (hipStream_t)stream));
+    if (N) HIPCHK(launch_flat(k_synth_mix23, N * 23, (hipStream_t)stream, seed, (const uint8_t*)d_genome, genome_len, first, N, (uint8_t*)d_out));
     return AIX_OK;
 }
 extern "C" int aix_synth_reads_dev(uint64_t seed, const char* d_genome, uint64_t genome_len, uint64_t first_read, uint64_t n_reads, uint32_t read_len,
                                    int rc_half, uint32_t n_rate_ppm, char* d_out, void* stream) {
     if (!d_genome || (n_reads && !d_out) || read_len == 0 || genome_len < read_len) return AIX_ERR_ARG;
-    HIPCHK(launch_synth_reads(seed, (const uint8_t*)d_genome, genome_len, first_read, n_reads, read_len, rc_half, n_rate_ppm, (uint8_t*)d_out,
-                              (hipStream_t)stream));
+    if (n_reads) HIPCHK(launch_flat(k_synth_reads, n_reads * ((uint64_t)read_len + 1), (hipStream_t)stream, seed, (const uint8_t*)d_genome, genome_len, first_read, n_reads,
+                                    read_len, rc_half, n_rate_ppm, (uint8_t*)d_out));
     return AIX_OK;
 }

@@ -1,11 +1,130 @@
 // aix_count.hip — the counters' device-pointer entry points: K13 in steps (also driven part by part from aix_ingest.hip) and count23 with
-// its three back ends, on the handle's grow-only count workspace. No kernel lives here (aix_count13.hip, aix_kernels.hip, aix_stream23.hip).
+// its three back ends, on the handle's grow-only count workspace. The one-window-per-lane kernels come first; the partitioned counter and
+// the run / streaming probes are subsystems of their own (aix_count13.hip, aix_stream23.hip).
 #include <algorithm>
 #include <mutex>
 #include <string>
 
 #include "aix_env.hpp"
 #include "aix_handle.hpp"
+#include "aix_launch.hpp"
+#include "aix_probe.hpp"
+
+namespace aix {
+
+// ---------------------------------------------------------------------------------------------
+// counting (PLAIN form: any byte that is not a base breaks the window; '\n' separates sequences)
+// ---------------------------------------------------------------------------------------------
+// count_kmers13.cpp:113-161: upper-case, ACGT only, forward strand; one lane per window start
+__global__ void __launch_bounds__(kBlock) k_count13(const uint8_t* __restrict__ buf, uint64_t len, unsigned long long* __restrict__ table) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    if (len < 13) return;
+    const uint64_t nwin = len - 12;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < nwin; p += stride) {
+        uint64_t w0, w1;
+        load13(buf + p, w0, w1);
+        w0 &= 0xDFDFDFDFDFDFDFDFULL;                            // toupper for letters; nothing else maps onto ACGT
+        w1 &= 0xDFDFDFDFDFDFDFDFULL;
+        const Enc13 e = encode13_words(w0, w1);
+        if (e.valid) atomicAdd(&table[e.code], 1ULL);
+    }
+}
+// the code-ordered table of k_count13 into the mphf-ordered output.
+// ADD: the MPHF is not a bijection on the 13-mers (a foreign .pf): several codes may share a slot, and the reference's
+// counts[mphf(window)].fetch_add(1) (count_kmers13.cpp:147-152) then sums them; slots >= 4^13 are skipped as there.
+template <bool ADD>
+__global__ void __launch_bounds__(kBlock) k_scatter13(const uint32_t* __restrict__ perm, const unsigned long long* __restrict__ table_code, uint64_t* __restrict__ out_mphf) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t code = (uint64_t)blockIdx.x * kBlock + threadIdx.x; code < 67108864ull; code += stride) {
+        const uint32_t h = perm[code];
+        if (h >= 67108864u) continue;
+        if (ADD) { const unsigned long long c = table_code[code]; if (c) atomicAdd((unsigned long long*)&out_mphf[h], c); }
+        else out_mphf[h] = table_code[code];
+    }
+}
+
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) k_count23_fixed(const IndexDev ix, const uint8_t* __restrict__ buf, uint64_t len, int canon_mode, uint32_t* __restrict__ tf_out) {
+    if (len < 23) return;
+    const uint64_t nwin = len - 22;
+    IndexDev ixn = ix;
+    ixn.bloom = nullptr;          // no absence filter in front of the table: it would be one more read for nearly every window
+    ixn.early_exit = 0;           // windows of reads drawn from the indexed genome are mostly hits. With the verification table: one line
+                                  // per window; without it (and for the overflow fall-back): the parallel three-read evaluation, whose
+                                  // fingerprint (same 16 bytes as the pairs) still spares the key-record read of a window that is NOT a key
+    AIX_WAVE_LOOP(p, nwin) {
+        const bool in = p < nwin;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (in) load23(buf + p, w0, w1, w2);
+        w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+        w1 = u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
+        w2 = u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
+        const Enc23 e = encode23_words(w0, w1, w2);
+        uint64_t key = e.code;
+        if (canon_mode == 1) { const uint64_t x = revcomp_refx86(e.code, 23); key = e.code < x ? e.code : x; }
+        else if (canon_mode == 2) { const uint64_t x = revcomp(e.code, 23); key = e.code < x ? e.code : x; }
+        uint64_t s0, s1, s2;
+        ascii23_of_rc(revcomp(key, 23), s0, s1, s2);
+        const Probe pr = probe23_wave<LPP>(ixn, in && e.valid, s0, s1, s2, key);
+        if (pr.found) atomicAdd(&tf_out[pr.slot], 1u);
+    }
+}
+
+// count23 without global atomics, front end: the MPHF slot of every window (0xFFFFFFFF: not a key / not a clean window) as a
+// coalesced 4-byte stream; aix_count13.hip's chunked-partition + LDS histogram then adds the stream into tf[] (1.3e9 scattered
+// memory-side atomics per 10 M reads run at ~23 G/s and were what bounded k_count23_fixed once a probe cost one line).
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) k_probe23_slots(const IndexDev ix, const uint8_t* __restrict__ buf, uint64_t len, int canon_mode, uint32_t* __restrict__ slots) {
+    if (len < 23) return;
+    const uint64_t nwin = len - 22;
+    IndexDev ixn = ix;
+    ixn.bloom = nullptr;
+    ixn.early_exit = 0;
+    AIX_WAVE_LOOP(p, nwin) {
+        const bool in = p < nwin;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (in) load23(buf + p, w0, w1, w2);
+        w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+        w1 = u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
+        w2 = u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
+        const Enc23 e = encode23_words(w0, w1, w2);
+        uint64_t key = e.code;
+        if (canon_mode == 1) { const uint64_t x = revcomp_refx86(e.code, 23); key = e.code < x ? e.code : x; }
+        else if (canon_mode == 2) { const uint64_t x = revcomp(e.code, 23); key = e.code < x ? e.code : x; }
+        uint64_t s0, s1, s2;
+        ascii23_of_rc(revcomp(key, 23), s0, s1, s2);
+        const Probe pr = probe23_wave<LPP>(ixn, in && e.valid, s0, s1, s2, key);
+        if (in) slots[p] = pr.found ? (uint32_t)pr.slot : 0xFFFFFFFFu;
+    }
+}
+
+// count23 through K1: the distinct k-mers of the reads (already in the call's canonical form) with their counts; one probe per DISTINCT k-mer, and a plain
+// read-modify-write of its slot — two distinct k-mers never share a slot
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) k_add_counts23(const IndexDev ix, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ counts, uint64_t n,
+                                                        uint32_t* __restrict__ tf_out) {
+    IndexDev ixn = ix;
+    ixn.bloom = nullptr;
+    ixn.early_exit = 0;
+    AIX_WAVE_LOOP(i, n) {
+        const bool in = i < n;
+        const uint64_t key = in ? keys[i] : 0ull;
+        uint64_t s0, s1, s2;
+        ascii23_of_rc(revcomp(key, 23), s0, s1, s2);
+        const Probe pr = probe23_wave<LPP>(ixn, in, s0, s1, s2, key);
+        if (in && pr.found) tf_out[pr.slot] += (uint32_t)counts[i];          // u32 histogram: wraps like the per-window adds of the other back ends
+    }
+}
+
+// the slot stream of a PLAIN buffer, one window per lane: slots[p] for p < len - 22; asynchronous on `s`, returns hipGetLastError()
+static hipError_t launch_probe23_slots(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* slots, hipStream_t s) {
+    if (len < 23 || ix.n == 0) return hipSuccess;
+    // AIX_PROBE_LDS_PAD=bytes (experiment): unused dynamic LDS per workgroup, to run the probe at a chosen number of waves per CU
+    static const unsigned pad = (unsigned)env_int("AIX_PROBE_LDS_PAD", INT_MIN, INT_MAX, 0);
+    return with_lpp(ix.bk_lpp, [&](auto L) { return launch_flat_lds(k_probe23_slots<decltype(L)::value>, len - 22, pad, s, ix, buf, len, canon_mode, slots); });
+}
+
+}  // namespace aix
 
 // What both counters share (CountState, aix_handle.hpp); every function here is called with c.mutex held.
 // the scratch table / workspace belong to the handle: counting calls are ordered behind one another even when they come in on
@@ -74,7 +193,7 @@ int count13_add_locked(aix_index* h, const char* d_plain, uint64_t len, uint64_t
     CountState& c = h->cnt;
     if (c.c13_atomics) {
         // scattered u64 memory-side atomics into the code-ordered table (slower; kept as the independent cross-check)
-        HIPCHK(launch_count13_plain((const uint8_t*)d_plain, len, c.scratch13.as<unsigned long long>(), s));
+        if (len >= 13) HIPCHK(launch_flat(k_count13, len - 12, s, (const uint8_t*)d_plain, len, c.scratch13.as<unsigned long long>()));
         c.c13_added = true;
         return AIX_OK;
     }
@@ -97,7 +216,10 @@ int count13_add_locked(aix_index* h, const char* d_plain, uint64_t len, uint64_t
 int count13_end_locked(aix_index* h, uint64_t* d_tf_out, hipStream_t s) {
     int st = AIX_OK;
     if (h->cnt.c13_atomics) {
-        const hipError_t e = launch_scatter13_to_mphf(h->perm13.as<uint32_t>(), h->cnt.scratch13.as<unsigned long long>(), d_tf_out, h->perm13_bijective ? 0 : 1, s);
+        const uint32_t* perm = h->perm13.as<uint32_t>();
+        const unsigned long long* table = h->cnt.scratch13.as<unsigned long long>();
+        const hipError_t e = h->perm13_bijective ? launch_flat(k_scatter13<false>, AIX_TOTAL_13MERS, s, perm, table, d_tf_out)
+                                                 : launch_flat(k_scatter13<true>, AIX_TOTAL_13MERS, s, perm, table, d_tf_out);
         if (e != hipSuccess) { set_last_error(std::string("count13 scatter: ") + hipGetErrorString(e)); st = AIX_ERR_HIP; }
     }
     (void)hipEventRecord(h->cnt.done, s);
@@ -126,7 +248,8 @@ static void record_count23(aix_index* h, uint32_t backend, uint32_t passes) {
 
 // (1) one memory-side atomic per found window: ~23 G scattered atomics/s on MI355X, which bounds the kernel once a probe costs a single line
 static int count23_atomics(aix_index* h, const char* d_plain, uint64_t len, int canon_mode, uint32_t* d_tf_out, hipStream_t s) {
-    HIPCHK(launch_count23_fixed(h->dev(), (const uint8_t*)d_plain, len, canon_mode, d_tf_out, s));
+    const IndexDev d = h->dev();
+    if (len >= 23 && d.n) HIPCHK(with_lpp(d.bk_lpp, [&](auto L) { return launch_flat(k_count23_fixed<decltype(L)::value>, len - 22, s, d, (const uint8_t*)d_plain, len, canon_mode, d_tf_out); }));
     record_count23(h, 1, 0);
     return AIX_OK;
 }
@@ -143,7 +266,7 @@ static int count23_via_k1(aix_index* h, const char* d_plain, uint64_t len, int c
     if (e != hipSuccess) (void)hipGetLastError();
     if (e == hipErrorOutOfMemory) return AIX_ERR_NOMEM;
     if (e != hipSuccess) { set_last_error(std::string("count23 through K1: ") + hipGetErrorString(e)); return AIX_ERR_HIP; }
-    const hipError_t e2 = launch_add_counts23(h->dev_slots(), d.k, d.c, d.n, d_tf_out, s);
+    const hipError_t e2 = d.n ? launch_flat(k_add_counts23<2>, d.n, s, h->dev_slots(), d.k, d.c, d.n, d_tf_out) : hipSuccess;
     const hipError_t e3 = hipStreamSynchronize(s);                             // the K1 result goes back to the block cache idle
     HIPCHK(e2);
     HIPCHK(e3);

@@ -374,6 +374,12 @@ __device__ __forceinline__ void load13(const uint8_t* p, uint64_t& w0, uint64_t&
     w0 = e0 | ((uint64_t)e1 << 32);
     w1 = e2 | ((uint64_t)e3 << 32);
 }
+// every 'U' byte of an upper-cased word becomes 'T' (count_kmers.cpp:71-88 maps U/u to 3)
+__device__ __forceinline__ uint64_t u_to_t(uint64_t x) {
+    const uint64_t z = x ^ 0x5555555555555555ULL;
+    const uint64_t nz = (((z & 0x7F7F7F7F7F7F7F7FULL) + 0x7F7F7F7F7F7F7F7FULL) | z) & 0x8080808080808080ULL;
+    return x ^ ((~nz & 0x8080808080808080ULL) >> 7);
+}
 
 // ---------------------------------------------------------------------------------------------
 // MPHF evaluation against the device layout

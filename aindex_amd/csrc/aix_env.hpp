@@ -56,7 +56,7 @@
 //     AIX_INGEST_THREADS           T   1 .. 64                       auto   host threads of the ingestion (aix_ingest.hip)
 //     AIX_PINNED_CACHE_MB          T   MiB                           1024   pinned staging blocks kept between calls
 //     AIX_SCRATCH_CACHE_GB         T   GiB (below 0 = 0)             40     device scratch kept between calls (aix_pool.hip)
-//     AIX_GRID_PER_CU              AB  1 .. 1024                     256    workgroups per CU of the grid-stride kernels (aix_kernels.hip)
+//     AIX_GRID_PER_CU              AB  1 .. 1024                     256    workgroups per CU of the grid-stride kernels (aix_launch.hpp)
 //     AIX_PROBE_LDS_PAD            AB  bytes                         0      unused LDS per workgroup of the slot probe
 //     AIX_A2_PROBE_LANES           AB  2, 4, 8                       handle lanes per bucket read of the positions probe (aix_positions.hip)
 //     AIX_C13_SHAPE                AB  s...                          -      the small workgroup shape of the split kernel (aix_count13.hip)

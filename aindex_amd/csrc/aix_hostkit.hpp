@@ -6,7 +6,7 @@
 // AIX_TRY_LAUNCH over DevArr, with_temp, flat_grid; their extern "C" halves keep HIPCHK and DevBuf. Nothing here is on a hot path, and
 // nothing that only one file uses belongs here. The files that work on the index handle (aix_index, aix_count, aix_lookup*, and the
 // attach halves of aix_posquery and aix_readsquery) and aix_ingest keep HIPCHK and their own error style, so they do not use this
-// header; what they hold lives in the owners of aix_owned.hpp (blocks, streams, events, the two exit guards), through which the handle
+// header (their kernels are launched through aix_launch.hpp); what they hold lives in the owners of aix_owned.hpp (blocks, streams, events, the two exit guards), through which the handle
 // frees itself. aix_normalize and aix_count13 keep raw pool blocks.
 #pragma once
 #include <algorithm>

@@ -1,6 +1,6 @@
 // aix_index.hip — the index handle's life in HBM: .pf parsing and upload, the tables built at open (verification table, absence
 // filter, minimizer-keyed copy, early-exit masks, 13-mer permutation), scatter, create / open / close / info and the setters.
-// No kernel lives here (aix_kernels.hip has them).
+// The kernels of index construction and re-layout come first; each is launched from the one host function below that needs it.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -13,6 +13,228 @@
 
 #include "aix_env.hpp"
 #include "aix_handle.hpp"
+#include "aix_launch.hpp"
+
+namespace aix {
+
+// ---------------------------------------------------------------------------------------------
+// index re-layout
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_build_keyrecs(const uint64_t* __restrict__ checker, const uint32_t* __restrict__ tf, uint64_t n, KeyRec* __restrict__ recs,
+                                                         uint32_t* __restrict__ noncanon) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t bad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        KeyRec r;
+        r.code = checker[i];
+        r.tf = tf[i];
+        r.pad = 0;
+        recs[i] = r;
+        bad |= (r.code > revcomp(r.code & ((1ULL << 46) - 1), 23)) || (r.code >> 46);
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicAdd(noncanon, 1u);
+}
+__global__ void __launch_bounds__(kBlock) k_extract(const IndexDev ix, uint32_t* __restrict__ tf, uint64_t* __restrict__ checker) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ix.n; i += stride) {
+        const KeyRec r = key_at(ix, i);
+        if (tf) tf[i] = r.tf;
+        if (checker) checker[i] = r.code;
+    }
+}
+// Fingerprints: for every stored code that sits in its own MPHF slot, write its 4-bit fingerprint into the nibble
+// of its assigned node. Entries that are not where the MPHF puts them (corrupt / foreign index) are skipped, so a
+// fingerprint mismatch always implies checker[rank] != query.
+__global__ void __launch_bounds__(kBlock) k_init_ee(const BvRec* __restrict__ recs, uint64_t nrecs, EeRec* __restrict__ ee) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nrecs; i += stride) {
+        EeRec e;
+        e.pairs = recs[i].pairs;
+        e.prefix = recs[i].prefix;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) e.mask[k] = 0;
+        ee[i] = e;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_set_fp(const IndexDev ix, BvRec* __restrict__ recs, EeRec* __restrict__ ee, int do_fp) {
+    const MphfDev& m = ix.m;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ix.n; i += stride) {
+        const uint64_t code = key_at(ix, i).code;
+        if (code >> 46) continue;
+        uint64_t w0, w1, w2, a, b, c, node;
+        uint32_t fps;
+        ascii23_of_rc(revcomp(code, 23), w0, w1, w2);
+        jenkins23(w0, w1, w2, m.seed, a, b, c);
+        if (mphf_from_hash_fp(m, a, b, c, fps, node) != i) continue;
+        if (do_fp) atomicOr((unsigned long long*)&recs[node >> 4].fp, (unsigned long long)fp_of_hash(a, b, c) << (4 * (uint32_t)(node & 15)));
+        if (!ee) continue;
+        const uint64_t nd[3] = {fastmod(a, m.fm), m.D + fastmod(b, m.fm), 2 * m.D + fastmod(c, m.fm)};
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {                     // the key's two presence bits at each of its three nodes
+            const uint32_t bit = (uint32_t)(nd[t] & 15) * 12u, sh = bit & 31u;
+            const uint32_t q = present_mask(a, b, c, t);
+            uint32_t* w = ee[nd[t] >> 4].mask + (bit >> 5);
+            atomicOr(w, q << sh);
+            if (sh > 20u) atomicOr(w + 1, q >> (32u - sh));
+        }
+    }
+}
+
+// Verification table (aix_device.hpp: BkEntry). Filed: every stored code that sits in its own MPHF slot, under the bucket its
+// Jenkins hash selects; the first eight arrivals of a bucket get an entry, the rest are left to the MPHF path (pass 2 raises
+// the bucket's overflow bit). Which eight is decided by the order of the atomics — the answers do not depend on it.
+__global__ void __launch_bounds__(kBlock) k_bk_init(BkEntry* __restrict__ bk, uint64_t nent) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nent; i += stride) {
+        BkEntry e;
+        e.code_lo = 0xFFFFFFFFu; e.code_hi = AIX_BK_EMPTY_HI; e.tf = 0; e.slot = 0;
+        bk[i] = e;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_bk_fill(const MphfDev m, const KeyRec* __restrict__ keys, uint64_t n, BkEntry* __restrict__ bk, uint32_t nb,
+                                                   uint32_t* __restrict__ fill, uint64_t* __restrict__ bloom, uint32_t nbloom, uint32_t nbm, uint32_t* __restrict__ mfill,
+                                                   uint32_t* __restrict__ side) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const KeyRec kr = keys[i];
+        side[i] = 0xFFFFFFFFu;                                   // not filed until the entry has been written below
+        if (kr.code >> 46) continue;
+        uint64_t w0, w1, w2, a, b, c;
+        ascii23_of_rc(revcomp(kr.code, 23), w0, w1, w2);
+        jenkins23(w0, w1, w2, m.seed, a, b, c);
+        if (mphf_from_hash(m, a, b, c) != i) continue;         // not where the MPHF puts it: the reference cannot find it, neither can a probe
+        if (bloom) {                                           // keyed by the code itself (aix_device.hpp: filter_key)
+            uint32_t hw, hb;
+            filter_key(kr.code, hw, hb);
+            atomicOr((unsigned long long*)&bloom[bloom_word(hw, nbloom)], (unsigned long long)bloom_mask(hb));
+        }
+        const uint32_t bi = bucket_of(a, nb);
+        const uint32_t pos = atomicAdd(&fill[bi], 1u);
+        BkEntry e;
+        e.code_lo = (uint32_t)kr.code; e.code_hi = (uint32_t)(kr.code >> 32); e.tf = kr.tf; e.slot = (uint32_t)i;
+        if (pos < 8u) { bk[(uint64_t)bi * 8 + pos] = e; side[i] = bi * 8u + pos; }      // (nb * 8 < 2^31: nb = n / load + 1 with n < 2^32 ... checked by the caller)
+        if (nbm) atomicAdd(&mfill[mk_home(minimizer23(kr.code, revcomp(kr.code, 23)), nbm)], 1u);    // the minimizer-keyed copy: sized here, written by k_mk_fill
+    }
+}
+// The same entries once more, grouped by the bucket of their minimizer: bucket b = mk[off[b], off[b + 1]) holds EVERY filed key whose
+// minimizer hashes to b (the keys of one minimizer arrive together, ~8 at a time, so fixed-size buckets overflowed for 15-30 % of the
+// windows; a bucket sized by its content never does). Same filing condition as k_bk_fill.
+__global__ void __launch_bounds__(kBlock) k_mk_fill(const MphfDev m, const KeyRec* __restrict__ keys, uint64_t n, BkEntry* __restrict__ mk, const uint32_t* __restrict__ off,
+                                                   uint32_t nbm, uint32_t* __restrict__ mcur) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const KeyRec kr = keys[i];
+        if (kr.code >> 46) continue;
+        uint64_t w0, w1, w2, a, b, c;
+        ascii23_of_rc(revcomp(kr.code, 23), w0, w1, w2);
+        jenkins23(w0, w1, w2, m.seed, a, b, c);
+        if (mphf_from_hash(m, a, b, c) != i) continue;
+        const uint32_t home = mk_home(minimizer23(kr.code, revcomp(kr.code, 23)), nbm);
+        BkEntry e;
+        e.code_lo = (uint32_t)kr.code; e.code_hi = (uint32_t)(kr.code >> 32); e.tf = kr.tf; e.slot = (uint32_t)i;
+        mk[(uint64_t)off[home] + atomicAdd(&mcur[home], 1u)] = e;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_side_count(const uint32_t* __restrict__ side, uint64_t n, uint32_t* __restrict__ counter) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) c += side[i] == 0xFFFFFFFFu ? 1u : 0u;
+    if (c) atomicAdd(counter, c);
+}
+__global__ void __launch_bounds__(kBlock) k_side_unfiled(const KeyRec* __restrict__ keys, uint64_t n, uint32_t* __restrict__ side, KeyRec* __restrict__ unfiled,
+                                                        uint32_t* __restrict__ counter) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        if (side[i] != 0xFFFFFFFFu) continue;
+        const uint32_t idx = atomicAdd(counter, 1u);
+        unfiled[idx] = keys[i];
+        side[i] = AIX_SIDE_UNFILED | idx;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_bk_flag(BkEntry* __restrict__ bk, uint32_t nb, const uint32_t* __restrict__ fill) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t bi = (uint64_t)blockIdx.x * kBlock + threadIdx.x; bi < nb; bi += stride)
+        if (fill[bi] > 8u) bk[bi * 8 + 7].code_hi |= AIX_BK_OVERFLOW;
+}
+
+// I1 (hash.cpp:671-723): checker[h] = code, tf[h] = count with h = mphf(key). Keys arrive either as
+// n x 23 ASCII bytes (the .dat lines) or as 2-bit codes. A slot hit twice raises `conflict`
+// (the reference detects it only when the earlier tf was non-zero, then exit(12)).
+template <bool ASCII>
+__global__ void __launch_bounds__(kBlock) k_scatter23(const MphfDev m, uint64_t n, uint64_t nslots, const uint8_t* __restrict__ keys, const uint64_t* __restrict__ codes,
+                                                     const uint32_t* __restrict__ counts, uint64_t* __restrict__ checker, uint32_t* __restrict__ tf,
+                                                     uint32_t* __restrict__ occupied, uint32_t* __restrict__ conflict) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        uint64_t w0, w1, w2, code;
+        if (ASCII) {
+            load23(keys + 23 * i, w0, w1, w2);
+            code = encode23_words(w0, w1, w2).code;                 // get_dna23_bitset(kmer), hash.cpp:715
+        } else {
+            code = codes[i] & ((1ULL << 46) - 1);
+            ascii23_of_rc(revcomp(code, 23), w0, w1, w2);
+        }
+        uint64_t a, b, c;
+        jenkins23(w0, w1, w2, m.seed, a, b, c);
+        const uint64_t h = mphf_from_hash(m, a, b, c);
+        if (h >= nslots) { atomicAdd(conflict, 1u); continue; }
+        const uint32_t bit = 1u << (h & 31);
+        if (atomicOr(&occupied[h >> 5], bit) & bit) { atomicAdd(conflict, 1u); continue; }
+        checker[h] = code;
+        tf[h] = counts ? counts[i] : 0u;
+    }
+}
+
+// perm[code] = mphf13(ASCII(code)) for all 4^13 codes
+__global__ void __launch_bounds__(kBlock) k_perm13(const MphfDev m, uint32_t* __restrict__ perm) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t code = (uint64_t)blockIdx.x * kBlock + threadIdx.x; code < 67108864ull; code += stride) {
+        uint64_t w0, w1, a, b, c;
+        ascii13_of_rc((uint32_t)revcomp(code, 13), w0, w1);
+        jenkins13(w0, w1, m.seed, a, b, c);
+        perm[code] = (uint32_t)mphf_from_hash(m, a, b, c);
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_tf13_to_code(const uint32_t* __restrict__ perm, const uint64_t* __restrict__ tf_mphf, uint64_t* __restrict__ tf_code) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t code = (uint64_t)blockIdx.x * kBlock + threadIdx.x; code < 67108864ull; code += stride) {
+        const uint32_t h = perm[code];
+        tf_code[code] = h < 67108864u ? tf_mphf[h] : 0ull;
+    }
+}
+// is code -> slot a bijection of [0, 4^13)? every slot in range and claimed once (bits: 4^13 / 32 zeroed words)
+__global__ void __launch_bounds__(kBlock) k_perm13_check(const uint32_t* __restrict__ perm, uint32_t* __restrict__ bits, uint32_t* __restrict__ bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t b = 0;
+    for (uint64_t code = (uint64_t)blockIdx.x * kBlock + threadIdx.x; code < 67108864ull; code += stride) {
+        const uint32_t h = perm[code];
+        if (h >= 67108864u) { b = 1; continue; }
+        const uint32_t bit = 1u << (h & 31);
+        if (atomicOr(&bits[h >> 5], bit) & bit) b = 1;
+    }
+    if (__any(b) && (threadIdx.x & 63) == 0) atomicAdd(bad, 1u);
+}
+
+// The two launchers that enqueue more than one kernel: asynchronous on `s`, one hipGetLastError() at the end.
+// fp nibbles of the MPHF records (do_fp) and / or the presence masks of the early-exit table (ee_rw non-null, initialised here); keys through key_at(ix, .)
+static hipError_t launch_set_fingerprints(const IndexDev& ix, BvRec* recs_rw, EeRec* ee_rw, bool do_fp, hipStream_t s) {
+    if (ix.n == 0) return hipSuccess;
+    if (ee_rw) hipLaunchKernelGGL(k_init_ee, dim3(grid_for(ix.m.nrecs)), dim3(kBlock), 0, s, (const BvRec*)recs_rw, ix.m.nrecs, ee_rw);
+    return launch_flat(k_set_fp, ix.n, s, ix, recs_rw, ee_rw, do_fp ? 1 : 0);
+}
+// verification table: bk (nb * 8 entries) is initialised and filled from the keys that sit in their own MPHF slot; fill = nb zeroed u32 counters
+// (scratch); bloom = zeroed, nullable; nbm = 0: no minimizer-keyed copy, else mfill = nbm zeroed words that take the keys per minimizer bucket;
+// side = n words: entry index of every filed key, 0xFFFFFFFF for the others
+static hipError_t launch_build_buckets(const MphfDev& m, const KeyRec* keys, uint64_t n, BkEntry* bk, uint32_t nb, uint32_t* fill, uint64_t* bloom, uint32_t nbloom, uint32_t nbm,
+                                       uint32_t* mfill, uint32_t* side, hipStream_t s) {
+    if (n == 0 || nb == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bk_init, dim3(grid_for((uint64_t)nb * 8)), dim3(kBlock), 0, s, bk, (uint64_t)nb * 8);
+    hipLaunchKernelGGL(k_bk_fill, dim3(grid_for(n)), dim3(kBlock), 0, s, m, keys, n, bk, nb, fill, bloom, nbloom, nbm, mfill, side);
+    return launch_flat(k_bk_flag, nb, s, bk, nb, (const uint32_t*)fill);
+}
+
+}  // namespace aix
 
 // ---------------------------------------------------------------------------------------------
 // files
@@ -160,7 +382,8 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
         HIPCHK(h->mk.alloc((uint64_t)(filed ? filed : 1) * sizeof(BkEntry), (uint64_t)filed * sizeof(BkEntry)));
         h->nbm = (uint32_t)nbm;
         HIPCHK(hipMemsetAsync(mfill.p, 0, 4 * (nbm + 1), s));
-        HIPCHK(launch_fill_minimizer_table(h->dev().m, h->keys.as<KeyRec>(), h->n, h->mk.as<BkEntry>(), h->mk_off.as<uint32_t>(), h->nbm, (uint32_t*)mfill.p, s));
+        // second pass of the minimizer-keyed copy: entries written at mk[off[bucket] + arrival]; mfill = nbm zeroed words again (n and nbm are not 0 here)
+        HIPCHK(launch_flat(k_mk_fill, h->n, s, h->dev().m, h->keys.as<KeyRec>(), h->n, h->mk.as<BkEntry>(), h->mk_off.as<uint32_t>(), h->nbm, (uint32_t*)mfill.p));
         HIPCHK(hipStreamSynchronize(s));
     }
     // keys left to the MPHF path: sum over buckets of max(fill - 8, 0) (host side: once per open, nb words)
@@ -177,13 +400,14 @@ static int build_bucket_table(aix_index* h, hipStream_t s) {
         DevBuf cnt(s);
         HIPCHK(cnt.alloc_once(8));
         HIPCHK(hipMemsetAsync(cnt.p, 0, 8, s));
-        HIPCHK(launch_count_unfiled(h->side.as<uint32_t>(), h->n, (uint32_t*)cnt.p, s));
+        HIPCHK(launch_flat(k_side_count, h->n, s, h->side.as<uint32_t>(), h->n, (uint32_t*)cnt.p));
         uint32_t nu = 0;
         HIPCHK(hipMemcpyAsync(&nu, cnt.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(h->unfiled.alloc(sizeof(KeyRec) * (uint64_t)(nu ? nu : 1), sizeof(KeyRec) * (uint64_t)nu));
         h->n_unfiled = nu;
-        HIPCHK(launch_side_unfiled(h->keys.as<KeyRec>(), h->n, h->side.as<uint32_t>(), h->unfiled.as<KeyRec>(), (uint32_t*)cnt.p + 1, s));
+        // unfiled[idx] = keys[i], side[i] = AIX_SIDE_UNFILED | idx for every side[i] == 0xFFFFFFFF; the counter is the second, still zeroed word
+        HIPCHK(launch_flat(k_side_unfiled, h->n, s, h->keys.as<KeyRec>(), h->n, h->side.as<uint32_t>(), h->unfiled.as<KeyRec>(), (uint32_t*)cnt.p + 1));
         HIPCHK(hipStreamSynchronize(s));
     }
     return AIX_OK;
@@ -212,7 +436,7 @@ static int adopt_device_arrays(aix_index* h, const uint64_t* d_checker, const ui
         DevBuf d_flag(s);
         HIPCHK(d_flag.alloc_once(4));
         HIPCHK(hipMemsetAsync(d_flag.p, 0, 4, s));
-        HIPCHK(launch_build_keyrecs(d_checker, d_tf, n, h->keys.as<KeyRec>(), (uint32_t*)d_flag.p, s));
+        HIPCHK(launch_flat(k_build_keyrecs, n, s, d_checker, d_tf, n, h->keys.as<KeyRec>(), (uint32_t*)d_flag.p));
         HIPCHK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -268,7 +492,8 @@ static int scatter_device(const MphfImage& mphf, uint64_t n, uint64_t nslots, co
     HIPCHK(hipMemsetAsync(flag.p, 0, 4, s));
     HIPCHK(hipMemsetAsync(d_checker, 0, 8 * nslots, s));       // hash.cpp:836-844: arrays start zeroed
     HIPCHK(hipMemsetAsync(d_tf, 0, 4 * nslots, s));
-    HIPCHK(launch_scatter23(mphf.view(), n, nslots, d_keys, d_codes, d_counts, d_checker, d_tf, (uint32_t*)occ.p, (uint32_t*)flag.p, s));
+    if (n) HIPCHK(d_keys ? launch_flat(k_scatter23<true>, n, s, mphf.view(), n, nslots, d_keys, d_codes, d_counts, d_checker, d_tf, (uint32_t*)occ.p, (uint32_t*)flag.p)
+                         : launch_flat(k_scatter23<false>, n, s, mphf.view(), n, nslots, d_keys, d_codes, d_counts, d_checker, d_tf, (uint32_t*)occ.p, (uint32_t*)flag.p));
     uint32_t conflicts = 0;
     HIPCHK(hipMemcpyAsync(&conflicts, flag.p, 4, hipMemcpyDeviceToHost, s));
     if (occ_out) HIPCHK(hipMemcpyAsync(occ_out, occ.p, occ_bytes, hipMemcpyDeviceToDevice, s));
@@ -369,8 +594,8 @@ static int build_13_tables(aix_index* h, const uint64_t* tf_host) {
     const IndexDev d = h->dev();
     if (tf_host) HIPCHK(hipMemcpy(h->tf13_mphf.p, tf_host, 8 * N13, hipMemcpyHostToDevice));
     else HIPCHK(hipMemset(h->tf13_mphf.p, 0, 8 * N13));
-    HIPCHK(launch_perm13(d.m, h->perm13.as<uint32_t>(), 0));
-    HIPCHK(launch_tf13_to_code_order(d.perm13, d.tf13_mphf, h->tf13_code.as<uint64_t>(), 0));
+    HIPCHK(launch_flat(k_perm13, N13, 0, d.m, h->perm13.as<uint32_t>()));              // perm[code] = mphf slot
+    HIPCHK(launch_flat(k_tf13_to_code, N13, 0, d.perm13, d.tf13_mphf, h->tf13_code.as<uint64_t>()));
     // The streaming counter writes each bin's total to out[perm[code]] with a plain store: right only when code -> slot is a
     // bijection, which holds for the all-13-mers .pf and not for a foreign one. Checked once here; a handle that fails the check
     // counts through the atomics path, which adds (the reference's fetch_add at mphf(window), count_kmers13.cpp:147-152).
@@ -380,7 +605,7 @@ static int build_13_tables(aix_index* h, const uint64_t* tf_host) {
         HIPCHK(bad.alloc_once(4));
         HIPCHK(hipMemsetAsync(bits.p, 0, AIX_TOTAL_13MERS / 8, 0));
         HIPCHK(hipMemsetAsync(bad.p, 0, 4, 0));
-        HIPCHK(launch_perm13_check(d.perm13, (uint32_t*)bits.p, (uint32_t*)bad.p, 0));
+        HIPCHK(launch_flat(k_perm13_check, N13, 0, d.perm13, (uint32_t*)bits.p, (uint32_t*)bad.p));
         uint32_t nbad = 1;
         HIPCHK(hipMemcpy(&nbad, bad.p, 4, hipMemcpyDeviceToHost));
         h->perm13_bijective = (nbad == 0);
@@ -497,7 +722,7 @@ extern "C" int aix_index_set_tf_13(aix_index_t* h, const uint64_t* tf) {
     DevGuard g(h->device);
     HIPCHK(hipMemcpy(h->tf13_mphf.p, tf, 8 * AIX_TOTAL_13MERS, hipMemcpyHostToDevice));
     h->pos_total_known = false;
-    HIPCHK(launch_tf13_to_code_order(h->perm13.as<uint32_t>(), h->tf13_mphf.as<uint64_t>(), h->tf13_code.as<uint64_t>(), 0));
+    HIPCHK(launch_flat(k_tf13_to_code, AIX_TOTAL_13MERS, 0, h->perm13.as<uint32_t>(), h->tf13_mphf.as<uint64_t>(), h->tf13_code.as<uint64_t>()));
     HIPCHK(hipStreamSynchronize(0));
     return AIX_OK;
 }
@@ -514,7 +739,7 @@ extern "C" int aix_index_get_tf(const aix_index_t* h, void* out, uint64_t out_by
     if (h->n == 0) return AIX_OK;
     DevBuf d;
     HIPCHK(d.alloc_once(4 * h->n));
-    HIPCHK(launch_extract_tf(h->dev(), (uint32_t*)d.p, nullptr, 0));
+    HIPCHK(launch_flat(k_extract, h->n, 0, h->dev(), (uint32_t*)d.p, (uint64_t*)nullptr));
     HIPCHK(hipMemcpy(out, d.p, 4 * h->n, hipMemcpyDeviceToHost));
     return AIX_OK;
 }
@@ -527,7 +752,7 @@ extern "C" int aix_index_get_checker(const aix_index_t* h, uint64_t* out, uint64
     DevGuard g(h->device);
     DevBuf d;
     HIPCHK(d.alloc_once(8 * h->n));
-    HIPCHK(launch_extract_tf(h->dev(), nullptr, (uint64_t*)d.p, 0));
+    HIPCHK(launch_flat(k_extract, h->n, 0, h->dev(), (uint32_t*)nullptr, (uint64_t*)d.p));
     HIPCHK(hipMemcpy(out, d.p, 8 * h->n, hipMemcpyDeviceToHost));
     return AIX_OK;
 }

@@ -1,4 +1,4 @@
-// aix_internal.hpp — host-side view of an index resident in HBM + kernel launcher prototypes.
+// aix_internal.hpp — host-side view of an index resident in HBM + the prototypes that cross translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,42 +64,15 @@ hipError_t pool_alloc(void** out, size_t bytes);
 void pool_free(void* p);
 void pool_trim();
 
-// launchers (aix_kernels.hip). All asynchronous on `stream`; return hipGetLastError().
+// The launchers that cross files (every other one is static beside its kernel). All asynchronous on `stream`; return hipGetLastError().
+// aix_lookup.hip, also called by aix_lookup_binned.hip.
 // gate (nullable): a device word read at the start of the kernel; non-zero = the binned path answers this batch and the kernel returns at once
 hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s, const uint32_t* gate = nullptr);
 // canonical index: out[list[j]] = tf of query list[j] for j < *count (<= max_count, which sizes the grid), when *gate is non-zero; *survivors_stat += *count
 hipError_t launch_lookup23_list(const IndexDev& ix, const uint8_t* q, const uint32_t* list, const uint32_t* count, uint64_t max_count, const uint32_t* gate,
                                 uint32_t* out, unsigned long long* survivors_stat, hipStream_t s);
-hipError_t launch_lookup23_codes(const IndexDev& ix, const uint64_t* codes, uint64_t N, uint32_t* out, hipStream_t s);
-hipError_t launch_selftest_lower_bound(const uint16_t* a, uint32_t n, const uint32_t* keys, uint32_t nkeys, uint32_t* out, hipStream_t s);
-hipError_t launch_lookup23_ragged(const IndexDev& ix, const uint8_t* bytes, const uint64_t* offs, uint64_t N, uint32_t* out, hipStream_t s);
-hipError_t launch_lookup13_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s);
-hipError_t launch_lookup13_ragged(const IndexDev& ix, const uint8_t* bytes, const uint64_t* offs, uint64_t N, uint32_t* out, hipStream_t s);
-hipError_t launch_coverage(const IndexDev& ix, const uint8_t* seqs, const uint64_t* offs, uint64_t M, uint64_t total_bytes,
-                           uint32_t cutoff, uint32_t* out, const uint64_t* out_offs, hipStream_t s);
 
-// index construction helpers
-hipError_t launch_build_keyrecs(const uint64_t* checker, const uint32_t* tf, uint64_t n, KeyRec* recs, uint32_t* noncanon_count, hipStream_t s);
-// fp nibbles of the MPHF records (do_fp) and / or the presence masks of the early-exit table (ee_rw non-null, initialised here); keys through key_at(ix, .)
-hipError_t launch_set_fingerprints(const IndexDev& ix, BvRec* recs_rw, EeRec* ee_rw, bool do_fp, hipStream_t s);
-// verification table: bk (nb * 8 entries) is initialised and filled from the keys that sit in their own MPHF slot;
-// fill = nb zeroed u32 counters (scratch)
-hipError_t launch_build_buckets(const MphfDev& m, const KeyRec* keys, uint64_t n, BkEntry* bk, uint32_t nb, uint32_t* fill, uint64_t* bloom /* zeroed, nullable */,
-                                uint32_t nbloom, uint32_t nbm /* 0: no minimizer-keyed copy */, uint32_t* mfill /* nbm zeroed words: keys per minimizer bucket */,
-                                uint32_t* side /* n words: entry index of every filed key, 0xFFFFFFFF for the others */, hipStream_t s);
-// the keys the table does not hold, closed up: unfiled[idx] = keys[i], side[i] = AIX_SIDE_UNFILED | idx for every side[i] == 0xFFFFFFFF; *counter = zeroed word
-hipError_t launch_side_unfiled(const KeyRec* keys, uint64_t n, uint32_t* side, KeyRec* unfiled, uint32_t* counter, hipStream_t s);
-hipError_t launch_count_unfiled(const uint32_t* side, uint64_t n, uint32_t* counter, hipStream_t s);
-// second pass of the minimizer-keyed copy: entries written at mk[off[bucket] + arrival]; mcur = nbm zeroed words
-hipError_t launch_fill_minimizer_table(const MphfDev& m, const KeyRec* keys, uint64_t n, BkEntry* mk, const uint32_t* off, uint32_t nbm, uint32_t* mcur, hipStream_t s);
-hipError_t launch_scatter23(const MphfDev& m, uint64_t n, uint64_t nslots, const uint8_t* keys_ascii /* or */, const uint64_t* codes, const uint32_t* counts,
-                            uint64_t* checker, uint32_t* tf, uint32_t* occupied_bits, uint32_t* conflict, hipStream_t s);
-hipError_t launch_perm13(const MphfDev& m, uint32_t* perm /* [4^13]: code -> mphf index */, hipStream_t s);
-hipError_t launch_tf13_to_code_order(const uint32_t* perm, const uint64_t* tf_mphf, uint64_t* tf_code, hipStream_t s);
-hipError_t launch_extract_tf(const IndexDev& ix, uint32_t* tf, uint64_t* checker, hipStream_t s);
-
-// counting
-hipError_t launch_count13_plain(const uint8_t* buf, uint64_t len, unsigned long long* table_code /* [4^13] */, hipStream_t s);
+// counting (aix_count13.hip)
 uint64_t count13_workspace_bytes(uint64_t len);
 // perm/out_mphf set: counters are written straight into the (pre-zeroed) mphf-ordered output; else into table_code
 hipError_t launch_count13_partitioned(const uint8_t* buf, uint64_t len, void* workspace, unsigned long long* table_code, const uint32_t* perm,
@@ -110,18 +83,10 @@ hipError_t launch_histogram_slots(const uint32_t* d_slots, uint64_t nslots, void
 // the same slot stream from the minimizer-keyed table (aix_stream23.hip): a lane owns 32 consecutive windows; needs ix.mk
 hipError_t launch_stream23_slots(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* slots /* [len - 22] */,
                                  uint32_t* flag /* zeroed word: set when a window stayed undecided */, hipStream_t s);
-hipError_t launch_probe23_slots(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* slots /* [len - 22] */, hipStream_t s);
 // the same slot stream with a run of w (16 / 32) consecutive windows per lane (aix_stream23.hip: the bytes are encoded once per run); needs ix.bk
 hipError_t launch_run23_slots(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* slots, int w, hipStream_t s);
-hipError_t launch_scatter13_to_mphf(const uint32_t* perm, const unsigned long long* table_code, uint64_t* out_mphf, int add, hipStream_t s);
-hipError_t launch_perm13_check(const uint32_t* perm, uint32_t* bits /* 4^13 / 32 zeroed words */, uint32_t* bad /* zeroed */, hipStream_t s);
-hipError_t launch_count23_fixed(const IndexDev& ix, const uint8_t* buf, uint64_t len, int canon_mode, uint32_t* tf_out, hipStream_t s);
-hipError_t launch_add_counts23(const IndexDev& ix, const uint64_t* keys /* distinct, in the call's canonical form */, const uint64_t* counts, uint64_t n, uint32_t* tf_out,
-                               hipStream_t s);
-
+// K1 front end (aix_api.hip, also called by aix_merge.hip): the canonical code of every k-window of a PLAIN buffer, ~0 where there is none
 hipError_t launch_window_codes(const uint8_t* buf, uint64_t len, int k, int canon_mode, uint64_t* out /* [len-k+1] */, hipStream_t s);
-
-hipError_t launch_gather(const uint8_t* table, uint64_t n_elems, int elem_bytes, int unroll, uint64_t n_access, uint64_t seed, uint64_t* sink, hipStream_t s);
 
 // out[i] = in[0] + ... + in[i - 1] (device arrays of n words; synchronises the stream)
 hipError_t exclusive_scan_u32(const uint32_t* d_in, uint32_t* d_out, uint64_t n, hipStream_t s);
@@ -242,12 +207,5 @@ hipError_t normalise_device(const uint8_t* d_raw, uint64_t len, int format, int 
 static constexpr uint32_t AIX_NORM_START = 0xFFFFFFFFu;
 hipError_t normalise_device_part(const uint8_t* d_raw, uint64_t len, int format, int fasta_mode, uint8_t* d_out, uint64_t* out_len, uint32_t* state_io, int last,
                                  hipStream_t s);
-
-// synthetic generators
-hipError_t launch_synth_genome(uint64_t seed, uint64_t length, uint8_t* out, hipStream_t s);
-hipError_t launch_synth_kmers(uint64_t seed, uint64_t first, uint64_t N, int k, uint8_t* out, hipStream_t s);
-hipError_t launch_synth_mix23(uint64_t seed, const uint8_t* genome, uint64_t glen, uint64_t first, uint64_t N, uint8_t* out, hipStream_t s);
-hipError_t launch_synth_reads(uint64_t seed, const uint8_t* genome, uint64_t genome_len, uint64_t first_read, uint64_t n_reads,
-                              uint32_t read_len, int rc_half, uint32_t n_rate_ppm, uint8_t* out, hipStream_t s);
 
 }  // namespace aix

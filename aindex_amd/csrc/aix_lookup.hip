@@ -1,6 +1,10 @@
 // aix_lookup.hip — lookups and coverage: the device-pointer entry points, and their host-pointer twins with the two staging paths (tiny
 // batches through pinned, device-mapped memory of the handle; large ones through a three-deep pipeline of pinned blocks and streams).
-// No kernel lives here (aix_kernels.hip has them).
+// The kernels come first: batch MPHF lookups (23-/13-mer) and per-position coverage, with their launchers.
+//
+// All kernels are HBM/latency-bound integer work (no MFMA): one query / window per lane, three
+// independent 16-byte MPHF record reads + one 16-byte key record read per probe, grid-stride
+// launches of >= 8 workgroups per CU so that ~2k probes per CU are in flight.
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -11,6 +15,465 @@
 
 #include "aix_env.hpp"
 #include "aix_handle.hpp"
+#include "aix_launch.hpp"
+#include "aix_probe.hpp"
+
+namespace aix {
+
+// Result of get_tf_value_23mer-style probing (python_wrapper.cpp:610-627): strand 0 absent, 1 fwd, 2 rc
+struct Q23 {
+    uint64_t slot;
+    uint32_t tf;
+    uint32_t strand;
+    uint32_t lines;
+};
+// wave-cooperative (all lanes call it; `active` = this lane holds a query)
+// `reload(a, b, c)` fetches the query's 23 bytes again: the rare lane-by-lane path of a canonical index takes them from memory a second time instead
+// of holding the original words, their code and its reverse complement (10 VGPRs) across the wave's probe for a case that almost never comes
+template <bool CANON, int LPP, class RELOAD>
+__device__ __forceinline__ Q23 query23(const IndexDev& ix, bool active, uint64_t w0, uint64_t w1, uint64_t w2, FilterGauge& fg, RELOAD&& reload) {
+    const Enc23 e = encode23_words(w0, w1, w2);
+    const uint64_t r = revcomp(e.code, 23);
+    Q23 out;
+    out.slot = 0; out.tf = 0; out.strand = 0; out.lines = 0;
+    if (CANON) {
+        // every stored code is canonical: only the canonical strand of a pure-ACGT query can match. ONE probe call site: with the
+        // strands chosen per lane first, a wave runs Jenkins + the probe once, not once per strand with half its lanes idle
+        const bool fwd = e.code <= r;
+        const bool clean = active && e.valid, other = active && !e.valid;
+        uint64_t x0 = w0, x1 = w1, x2 = w2;
+        if (!fwd) ascii23_of_rc(e.code, x0, x1, x2);
+        const Probe p = probe23_wave<LPP>(ix, clean, x0, x1, x2, fwd ? e.code : r, true, fg.on);
+        fg.seen(clean, p.found);
+        if (clean) {
+            out.lines = p.lines;
+            if (p.found) { out.slot = p.slot; out.tf = p.tf; out.strand = fwd ? 1u : 2u; }
+        }
+        if (other) {                                            // other bytes: the reference's two probes, lane by lane (rare)
+            uint64_t v0, v1, v2;
+            reload(v0, v1, v2);
+            const Enc23 e2 = encode23_words(v0, v1, v2);
+            uint64_t a, b, c;
+            jenkins23(v0, v1, v2, ix.m.seed, a, b, c);
+            const Probe f = probe23_mphf(ix, a, b, c, e2.code, false);   // raw bytes hashed, sanitised code compared
+            out.lines = f.lines;
+            if (f.found) { out.slot = f.slot; out.tf = f.tf; out.strand = 1; }
+            else {
+                uint64_t r0, r1, r2;
+                ascii23_of_rc(e2.code, r0, r1, r2);             // decode(reverseDNA(u)), :615-616
+                const Probe g = probe23(ix, r0, r1, r2, revcomp(e2.code, 23));
+                out.lines += g.lines;
+                if (g.found) { out.slot = g.slot; out.tf = g.tf; out.strand = 2; }
+            }
+        }
+        return out;
+    }
+    const Probe f = probe23_wave<LPP>(ix, active, w0, w1, w2, e.code, e.valid, fg.on);   // raw bytes hashed, sanitised code compared
+    uint64_t r0, r1, r2;
+    ascii23_of_rc(e.code, r0, r1, r2);                          // decode(reverseDNA(u)), :615-616
+    const Probe g = probe23_wave<LPP>(ix, active && !f.found, r0, r1, r2, r, true, fg.on);
+    fg.seen(active, f.found || g.found);
+    if (active) {
+        out.lines = f.lines;
+        if (f.found) { out.slot = f.slot; out.tf = f.tf; out.strand = 1; }
+        else {
+            out.lines += g.lines;
+            if (g.found) { out.slot = g.slot; out.tf = g.tf; out.strand = 2; }
+        }
+    }
+    return out;
+}
+template <bool CANON, int LPP>
+__device__ __forceinline__ Q23 query23(const IndexDev& ix, bool active, uint64_t w0, uint64_t w1, uint64_t w2, FilterGauge& fg) {
+    return query23<CANON, LPP>(ix, active, w0, w1, w2, fg, [&](uint64_t& a, uint64_t& b, uint64_t& c) { a = w0; b = w1; c = w2; });
+}
+
+// get_tf_both_directions_23mer (python_wrapper.cpp:1259-1275): Q1(q) and Q1(decode(rc(q))); wave-cooperative like query23
+template <bool CANON, int LPP>
+__device__ __forceinline__ void both23(const IndexDev& ix, bool active, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t& fwd, uint32_t& rc, FilterGauge& fg) {
+    const Enc23 e = encode23_words(w0, w1, w2);
+    const uint64_t r = revcomp(e.code, 23);
+    fwd = 0; rc = 0;
+    const bool fast = CANON && e.valid;                         // canonical index, pure-ACGT query: both directions see the one canonical key
+    const Q23 q = query23<CANON, LPP>(ix, active && fast, w0, w1, w2, fg);
+    if (active && fast) { fwd = q.tf; rc = q.tf; }
+    const bool slow = active && !fast;
+    if (CANON) {
+        if (slow) {                                             // non-ACGT bytes on a canonical index: lane by lane, MPHF path
+            uint64_t r0, r1, r2, s0, s1, s2;
+            ascii23_of_rc(e.code, r0, r1, r2);
+            ascii23_of_rc(r, s0, s1, s2);
+            uint64_t a, b, c;
+            jenkins23(w0, w1, w2, ix.m.seed, a, b, c);
+            const Probe F = probe23_mphf(ix, a, b, c, e.code, false);
+            const Probe R = probe23(ix, r0, r1, r2, r);
+            const Probe S = probe23(ix, s0, s1, s2, e.code);    // second call's fallback decodes the sanitised code
+            fwd = F.found ? F.tf : (R.found ? R.tf : 0u);
+            rc = R.found ? R.tf : (S.found ? S.tf : 0u);
+        }
+        return;
+    }
+    uint64_t r0, r1, r2, s0, s1, s2;
+    ascii23_of_rc(e.code, r0, r1, r2);
+    ascii23_of_rc(r, s0, s1, s2);
+    const Probe F = probe23_wave<LPP>(ix, slow, w0, w1, w2, e.code, e.valid, fg.on);
+    const Probe R = probe23_wave<LPP>(ix, slow, r0, r1, r2, r, true, fg.on);
+    const Probe S2 = probe23_wave<LPP>(ix, slow && !e.valid, s0, s1, s2, e.code, true, fg.on);
+    fg.seen(slow, F.found || R.found);
+    if (slow) {
+        const Probe S = e.valid ? F : S2;
+        fwd = F.found ? F.tf : (R.found ? R.tf : 0u);
+        rc = R.found ? R.tf : (S.found ? S.tf : 0u);
+    }
+}
+
+template <int MODE, bool CANON, int LPP>
+__global__ void __launch_bounds__(kBlock) k_lookup23_ascii(const IndexDev ix_, const uint8_t* __restrict__ q, uint64_t N, LookupOut out,
+                                                          const uint32_t* __restrict__ gate /* nullable: non-zero = the binned path answers this batch */) {
+    if (gate && *gate) return;
+    const IndexDev& ix = ix_;
+    FilterGauge fg;
+    AIX_WAVE_LOOP(i, N) {
+        const bool in = i < N;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (in) load23(q + 23 * i, w0, w1, w2);
+        auto again = [&](uint64_t& a, uint64_t& b, uint64_t& c) { load23(q + 23 * i, a, b, c); };
+        if (MODE == MODE_TF) {
+            const uint32_t v = query23<CANON, LPP>(ix, in, w0, w1, w2, fg, again).tf;
+            if (in) out.tf[i] = v;
+        } else if (MODE == MODE_LINES) {
+            const uint32_t v = query23<CANON, LPP>(ix, in, w0, w1, w2, fg).lines;   // instrumentation: records read for this query
+            if (in) out.tf[i] = v;
+        } else if (MODE == MODE_HASH) {
+            if (in) {
+                uint64_t a, b, c;
+                jenkins23(w0, w1, w2, ix.m.seed, a, b, c);
+                out.u64a[i] = mphf_from_hash(ix.m, a, b, c);
+            }
+        } else if (MODE == MODE_KIDSTRAND) {
+            const Q23 r = query23<CANON, LPP>(ix, in, w0, w1, w2, fg, again);
+            if (in) {
+                if (out.u64a) out.u64a[i] = r.slot;             // get_kid_by_kmer: 0 when absent (:700-716)
+                if (out.strand) out.strand[i] = (uint8_t)r.strand;
+            }
+        } else {
+            uint32_t f, r;
+            both23<CANON, LPP>(ix, in, w0, w1, w2, f, r, fg);
+            if (in) {
+                if (MODE == MODE_TOTAL) {
+                    out.u64a[i] = (uint64_t)f + (uint64_t)r;
+                } else {
+                    if (out.u64a) out.u64a[i] = f;
+                    if (out.u64b) out.u64b[i] = r;
+                }
+            }
+        }
+    }
+}
+
+// pass C of the binned lookup (aix_lookup_binned.hip): the queries list[0 .. *count) of a canonical index through the same probe
+// as above. The grid is sized for the worst case; *count and the gate word are read on the device.
+template <int LPP>
+__global__ void __launch_bounds__(kBlock) k_lookup23_list(const IndexDev ix_, const uint8_t* __restrict__ q, const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ count, const uint32_t* __restrict__ gate, uint32_t* __restrict__ out,
+                                                         unsigned long long* __restrict__ survivors_stat) {
+    if (!*gate) return;
+    const IndexDev& ix = ix_;
+    const uint64_t n = *count;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(survivors_stat, (unsigned long long)n);
+    FilterGauge fg;
+    AIX_WAVE_LOOP(j, n) {
+        const bool in = j < n;
+        const uint64_t i = in ? list[j] : 0;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (in) load23(q + 23 * i, w0, w1, w2);
+        auto again = [&](uint64_t& a, uint64_t& b, uint64_t& c) { load23(q + 23 * i, a, b, c); };
+        const uint32_t v = query23<true, LPP>(ix, in, w0, w1, w2, fg, again).tf;
+        if (in) out[i] = v;
+    }
+}
+
+template <bool CANON, int LPP>
+__global__ void __launch_bounds__(kBlock) k_lookup23_codes(const IndexDev ix_, const uint64_t* __restrict__ codes, uint64_t N, uint32_t* __restrict__ out) {
+    const IndexDev& ix = ix_;
+    FilterGauge fg;
+    AIX_WAVE_LOOP(i, N) {
+        const bool in = i < N;
+        const uint64_t u = in ? (codes[i] & ((1ULL << 46) - 1)) : 0ull;
+        const uint64_t r = revcomp(u, 23);
+        uint64_t w0, w1, w2;
+        uint32_t tf = 0;
+        if (CANON) {
+            const uint64_t key = u <= r ? u : r;
+            ascii23_of_rc(u <= r ? r : u, w0, w1, w2);           // string of `key`
+            const Probe p = probe23_wave<LPP>(ix, in, w0, w1, w2, key, true, fg.on);
+            fg.seen(in, p.found);
+            tf = p.found ? p.tf : 0u;
+        } else {
+            ascii23_of_rc(r, w0, w1, w2);
+            const Probe f = probe23_wave<LPP>(ix, in, w0, w1, w2, u, true, fg.on);
+            ascii23_of_rc(u, w0, w1, w2);
+            const Probe g = probe23_wave<LPP>(ix, in && !f.found, w0, w1, w2, r, true, fg.on);
+            fg.seen(in, f.found || g.found);
+            tf = f.found ? f.tf : (g.found ? g.tf : 0u);
+        }
+        if (in) out[i] = tf;
+    }
+}
+
+// variable-length queries: the reference hashes ALL bytes of the std::string but encodes the first 23
+__global__ void __launch_bounds__(kBlock) k_lookup23_ragged(const IndexDev ix, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offs,
+                                                           uint64_t N, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride) {
+        const uint64_t lo = offs[i], len = offs[i + 1] - lo;
+        uint32_t tf = 0;
+        if (len >= 23) {
+            uint64_t w0, w1, w2;
+            load23(bytes + lo, w0, w1, w2);
+            if (len == 23) {                                     // lane by lane (lengths differ inside a wave): the MPHF path, both probes
+                const Enc23 e = encode23_words(w0, w1, w2);
+                const Probe f = probe23(ix, w0, w1, w2, e.code, e.valid);
+                if (f.found) tf = f.tf;
+                else {
+                    uint64_t r0, r1, r2;
+                    ascii23_of_rc(e.code, r0, r1, r2);
+                    const Probe g = probe23(ix, r0, r1, r2, revcomp(e.code, 23));
+                    tf = g.found ? g.tf : 0u;
+                }
+            } else {
+                const Enc23 e = encode23_words(w0, w1, w2);
+                uint64_t a, b, c;
+                jenkins_bytes(bytes + lo, len, ix.m.seed, a, b, c);
+                const Probe f = probe23_hashed(ix, a, b, c, e.code);
+                if (f.found) tf = f.tf;
+                else {
+                    uint64_t r0, r1, r2;
+                    ascii23_of_rc(e.code, r0, r1, r2);
+                    const Probe g = probe23(ix, r0, r1, r2, revcomp(e.code, 23));
+                    tf = g.found ? g.tf : 0u;
+                }
+            }
+        }
+        out[i] = tf;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 13-mer mode: the MPHF over all 4^13 13-mers is a bijection code -> slot, so the table is kept in
+// 2-bit-code order in HBM (tf13_code) and a valid query is one 8-byte read. Queries with bytes
+// outside ACGT take the reference's raw-bytes MPHF path against the mphf-ordered copy.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t tf13_raw(const IndexDev& ix, uint64_t w0, uint64_t w1) {
+    uint64_t a, b, c;
+    jenkins13(w0, w1, ix.m.seed, a, b, c);
+    const uint64_t h = mphf_from_hash(ix.m, a, b, c);
+    return h < 67108864ull ? ix.tf13_mphf[h] : 0ull;            // reference indexes unguarded (:534); OOB -> 0
+}
+// get_reverse_complement_13mer (python_wrapper.cpp:505-517) on raw bytes: reverse; A<->T, C<->G; others kept
+__device__ __forceinline__ void rc13_raw(uint64_t w0, uint64_t w1, uint64_t& r0, uint64_t& r1) {
+    r0 = 0; r1 = 0;
+#pragma unroll
+    for (int i = 0; i < 13; ++i) {
+        const int j = 12 - i;
+        uint32_t ch = (uint32_t)((j < 8 ? (w0 >> (8 * j)) : (w1 >> (8 * (j - 8)))) & 0xff);
+        ch = ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'G' ? 'C' : ch == 'C' ? 'G' : ch;
+        if (i < 8) r0 |= (uint64_t)ch << (8 * i);
+        else r1 |= (uint64_t)ch << (8 * (i - 8));
+    }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_lookup13_ascii(const IndexDev ix, const uint8_t* __restrict__ q, uint64_t N, LookupOut out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride) {
+        uint64_t w0, w1;
+        load13(q + 13 * i, w0, w1);
+        const Enc13 e = encode13_words(w0, w1);
+        if (MODE == MODE_TF) {                                  // get_tf_values_13mer :938-980: strict, u32 truncation
+            out.tf[i] = e.valid ? (uint32_t)ix.tf13_code[e.code] : 0u;
+        } else if (MODE == MODE_HASH) {                         // hasher_13mer.lookup(kmer) (:1087): the tabulated slot, or the MPHF of the raw bytes
+            uint64_t hval;
+            if (e.valid) hval = ix.perm13[e.code];
+            else { uint64_t a, b, c; jenkins13(w0, w1, ix.m.seed, a, b, c); hval = mphf_from_hash(ix.m, a, b, c); }
+            out.u64a[i] = hval;
+        } else {
+            uint64_t f, r;
+            if (e.valid) {
+                f = ix.tf13_code[e.code];
+                r = ix.tf13_code[(uint32_t)revcomp(e.code, 13)];
+            } else {                                            // :522-543 has no validation: raw bytes are hashed
+                uint64_t r0, r1;
+                rc13_raw(w0, w1, r0, r1);
+                f = tf13_raw(ix, w0, w1);
+                r = tf13_raw(ix, r0, r1);
+            }
+            if (MODE == MODE_TOTAL) out.u64a[i] = f + r;
+            else {
+                if (out.u64a) out.u64a[i] = f;
+                if (out.u64b) out.u64b[i] = r;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_lookup13_ragged(const IndexDev ix, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offs,
+                                                           uint64_t N, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride) {
+        const uint64_t lo = offs[i], len = offs[i + 1] - lo;
+        uint32_t tf = 0;
+        if (len == 13) {                                        // is_13mer(): length check first (:943)
+            uint64_t w0, w1;
+            load13(bytes + lo, w0, w1);
+            const Enc13 e = encode13_words(w0, w1);
+            if (e.valid) tf = (uint32_t)ix.tf13_code[e.code];
+        }
+        out[i] = tf;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// coverage: one lane per byte position of the concatenated sequences (aindex.py:314-322)
+// ---------------------------------------------------------------------------------------------
+// (eight waves per SIMD: 64 VGPRs with two spilled words instead of 69 and seven waves — 268-270 against 280-282 ms per 10^10 positions on one box;
+// the same limit on k_lookup23_ascii costs 5-7 %, so it is set here only)
+template <bool CANON, int LPP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) k_coverage(const IndexDev ix_, const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ offs, uint64_t M,
+                                                    uint64_t total, double seqs_per_byte, uint32_t cutoff, uint32_t* __restrict__ out,
+                                                    const uint64_t* __restrict__ out_offs) {
+    const IndexDev& ix = ix_;
+    const uint32_t k = ix.k;
+    FilterGauge fg;
+    AIX_WAVE_LOOP(p, total) {
+        // sequence containing byte p: largest s with offs[s] <= p. The lanes of a wave hold consecutive p, so the binary search
+        // runs once per wave for its first position (wave-uniform: scalar loads), and a lane then walks forward from there —
+        // zero or one step unless the sequences are shorter than a wave is wide (then a bounded walk, then its own search).
+        // (the builtin returns int: without the cast a low half with bit 31 set sign-extends over the high half, the search lands on the last
+        // sequence and the positions [2^31, 2^32) mod 2^32 of a batch come back 0 — rounds 1 and 2 did that to 43 % of config 5 at full size)
+        const uint64_t p0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p_base >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p_base);
+        // the window's bytes are requested before anything is known about the sequence they belong to (a window inside the buffer can be read
+        // whether or not it lies inside ONE sequence): the loads fly while the search below waits for its offsets
+        const bool inb = p + k <= total;
+        uint64_t w0 = 0, w1 = 0, w2 = 0;
+        if (inb) { if (k == 23) load23(seqs + p, w0, w1, w2); else load13(seqs + p, w0, w1); }     // (k = 13, same box: 185 against 198 ms per 10^10 positions; k = 23 within noise)
+        // The search starts from where p0 would lie if all sequences had the mean length — exact for equal lengths, the usual batch — and
+        // gallops from there: two independent loads instead of log2(M) dependent ones per trip of every wave (20 round trips at 10^6 sequences,
+        // several times the latency of the probe itself). Any guess gives the same s.
+        uint64_t lo, hi;                                        // invariant offs[lo] <= p0 < offs[hi] (or lo == 0)
+        {
+            uint64_t g = (uint64_t)((double)p0 * seqs_per_byte);
+            if (g >= M) g = M - 1;
+            const uint64_t og = offs[g], og1 = offs[g + 1];
+            if (og <= p0) {
+                lo = g; hi = g + 1;
+                if (og1 <= p0) {
+                    uint64_t step = 1;
+                    while (hi < M && offs[hi] <= p0) { lo = hi; step <<= 1; hi = (M - lo > step) ? lo + step : M; }
+                }
+            } else {
+                hi = g; lo = g ? g - 1 : 0;
+                uint64_t step = 1;
+                while (lo > 0 && offs[lo] > p0) { hi = lo; step <<= 1; lo = lo > step ? lo - step : 0; }
+            }
+        }
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (offs[mid] <= p0) lo = mid; else hi = mid;
+        }
+        const uint64_t begin0 = offs[lo], end0 = offs[lo + 1];
+        // one probe per lane either way; the two cases are kept apart so that the usual one carries nothing per lane across the probe but the
+        // window words (its output address is a wave-uniform base plus the lane number)
+        auto answer = [&](bool active) -> uint32_t {
+            if (k == 23) return query23<CANON, LPP>(ix, active, w0, w1, w2, fg, [&](uint64_t& a, uint64_t& b, uint64_t& c) { load23(seqs + p, a, b, c); }).tf;
+            if (!active) return 0u;
+            const Enc13 e = encode13_words(w0, w1);
+            return e.valid ? (uint32_t)ix.tf13_code[e.code] : 0u;
+        };
+        if (begin0 <= p0 && end0 > p0 + 63) {                   // all 64 positions of the wave lie in sequence lo (the usual case): nothing is looked up per lane
+            uint32_t* const wdst = out + (out_offs[lo] + (p0 - begin0));      // wave-uniform
+            const bool active = inb && p + k <= end0;
+            const uint32_t tf = answer(active);
+            if (active) wdst[threadIdx.x & 63u] = tf >= cutoff ? tf : 0u;
+        } else {
+            bool active = inb;
+            uint64_t s = lo;
+            uint32_t* dst = out;
+            if (active) {
+                for (int step = 0; step < 4 && s + 1 < M && offs[s + 1] <= p; ++step) ++s;
+                if (s + 1 < M && offs[s + 1] <= p) {
+                    uint64_t l2 = s + 1, h2 = M;                // offs[l2] <= p < offs[h2]
+                    while (h2 - l2 > 1) {
+                        const uint64_t mid = (l2 + h2) >> 1;
+                        if (offs[mid] <= p) l2 = mid; else h2 = mid;
+                    }
+                    s = l2;
+                }
+                const uint64_t begin = offs[s], end = offs[s + 1];
+                if (p < begin || p + k > end) active = false;   // p < begin: gaps between sequences are allowed
+                dst = out + (out_offs[s] + (p - begin));
+            }
+            const uint32_t tf = answer(active);
+            if (active) *dst = tf >= cutoff ? tf : 0u;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// launchers: all asynchronous on `s`, return hipGetLastError(). The two that aix_lookup_binned.hip calls too are in aix_internal.hpp.
+// ---------------------------------------------------------------------------------------------
+template <bool CANON>
+static hipError_t lookup23_ascii_mode(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, const uint32_t* gate, hipStream_t s) {
+    switch (mode) {
+        case MODE_TF: return with_lpp(ix.bk_lpp, [&](auto L) { return launch_flat(k_lookup23_ascii<MODE_TF, CANON, decltype(L)::value>, N, s, ix, q, N, out, gate); });
+        case MODE_LINES: return launch_flat(k_lookup23_ascii<MODE_LINES, CANON, 8>, N, s, ix, q, N, out, gate);
+        case MODE_HASH: return launch_flat(k_lookup23_ascii<MODE_HASH, CANON, 8>, N, s, ix, q, N, out, gate);
+        case MODE_KIDSTRAND: return launch_flat(k_lookup23_ascii<MODE_KIDSTRAND, CANON, 8>, N, s, ix, q, N, out, gate);
+        case MODE_BOTH: return launch_flat(k_lookup23_ascii<MODE_BOTH, CANON, 8>, N, s, ix, q, N, out, gate);
+        case MODE_TOTAL: return launch_flat(k_lookup23_ascii<MODE_TOTAL, CANON, 8>, N, s, ix, q, N, out, gate);
+    }
+    return hipErrorInvalidValue;
+}
+hipError_t launch_lookup23_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s, const uint32_t* gate) {
+    if (N == 0) return hipSuccess;
+    return ix.canonical_only ? lookup23_ascii_mode<true>(ix, q, N, mode, out, gate, s) : lookup23_ascii_mode<false>(ix, q, N, mode, out, gate, s);
+}
+hipError_t launch_lookup23_list(const IndexDev& ix, const uint8_t* q, const uint32_t* list, const uint32_t* count, uint64_t max_count, const uint32_t* gate,
+                                uint32_t* out, unsigned long long* survivors_stat, hipStream_t s) {
+    return with_lpp(ix.bk_lpp, [&](auto L) { return launch_flat(k_lookup23_list<decltype(L)::value>, max_count, s, ix, q, list, count, gate, out, survivors_stat); });
+}
+static hipError_t launch_lookup23_codes(const IndexDev& ix, const uint64_t* codes, uint64_t N, uint32_t* out, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    return ix.canonical_only ? launch_flat(k_lookup23_codes<true, 8>, N, s, ix, codes, N, out) : launch_flat(k_lookup23_codes<false, 8>, N, s, ix, codes, N, out);
+}
+static hipError_t launch_lookup23_ragged(const IndexDev& ix, const uint8_t* bytes, const uint64_t* offs, uint64_t N, uint32_t* out, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    return launch_flat(k_lookup23_ragged, N, s, ix, bytes, offs, N, out);
+}
+static hipError_t launch_lookup13_ascii(const IndexDev& ix, const uint8_t* q, uint64_t N, int mode, LookupOut out, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    switch (mode) {
+        case MODE_TF: return launch_flat(k_lookup13_ascii<MODE_TF>, N, s, ix, q, N, out);
+        case MODE_HASH: return launch_flat(k_lookup13_ascii<MODE_HASH>, N, s, ix, q, N, out);
+        case MODE_BOTH: return launch_flat(k_lookup13_ascii<MODE_BOTH>, N, s, ix, q, N, out);
+        case MODE_TOTAL: return launch_flat(k_lookup13_ascii<MODE_TOTAL>, N, s, ix, q, N, out);
+    }
+    return hipErrorInvalidValue;
+}
+static hipError_t launch_lookup13_ragged(const IndexDev& ix, const uint8_t* bytes, const uint64_t* offs, uint64_t N, uint32_t* out, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    return launch_flat(k_lookup13_ragged, N, s, ix, bytes, offs, N, out);
+}
+static hipError_t launch_coverage(const IndexDev& ix, const uint8_t* seqs, const uint64_t* offs, uint64_t M, uint64_t total, uint32_t cutoff, uint32_t* out,
+                                  const uint64_t* out_offs, hipStream_t s) {
+    if (M == 0 || total == 0) return hipSuccess;
+    const double seqs_per_byte = (double)M / (double)total;
+    if (ix.k == 23 && ix.canonical_only)
+        return with_lpp(ix.bk_lpp, [&](auto L) { return launch_flat(k_coverage<true, decltype(L)::value>, total, s, ix, seqs, offs, M, total, seqs_per_byte, cutoff, out, out_offs); });
+    return launch_flat(k_coverage<false, 8>, total, s, ix, seqs, offs, M, total, seqs_per_byte, cutoff, out, out_offs);
+}
+
+}  // namespace aix
 
 // ---------------------------------------------------------------------------------------------
 // device-pointer entry points

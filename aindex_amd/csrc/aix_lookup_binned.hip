@@ -28,7 +28,7 @@
 //                 word only of the records whose image bit is set, about 4 in 10 of an absent-heavy batch. Every ticket counter
 //                 owns the slices s with s % 8 == its number. The image is folded once per handle (k_lb_fold). k_lb_filter
 //                 remains for slices whose image does not fit (2 MiB slices) and as the A/B switch.
-//   k_lookup23_list (aix_kernels.hip) pass C: the survivors through the ordinary probe.
+//   k_lookup23_list (aix_lookup.hip) pass C: the survivors through the ordinary probe.
 // A record = query index in the piece (27 bits) | filter word inside the slice (18 bits) | the 16 bits of the filter key from which
 // bloom_mask takes all four bit positions: 8 bytes, three bits spare. Pass B therefore lets exactly the filter's positives through
 // (~0.5 % of absent queries); pass C goes through the ordinary probe, which consults the filter again, so answers do not depend on it.
@@ -94,7 +94,7 @@ struct LbWs {
     unsigned long long* stats;     // pieces binned, pieces direct, records that overflowed, survivors; records tested against the coarse image, records sent on to the filter word
 };
 
-// the filter key of the code query23 (aix_kernels.hip) probes: that of the canonical strand; false = other bytes
+// the filter key of the code query23 (aix_lookup.hip) probes: that of the canonical strand; false = other bytes
 __device__ __forceinline__ bool lb_hash(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t& hw, uint32_t& hb) {
     uint64_t code;
     if (!encode23_clean(w0, w1, w2, code)) return false;

@@ -1,5 +1,5 @@
 // aix_probe.hpp — private: the probe of the batch kernels (verification table, side index, unfiled keys, MPHF fallback) and the
-// absence-filter gauge, shared by the translation units whose kernels look 23-mers up (aix_kernels.hip, aix_debruijn.hip, aix_unitigs.hip).
+// absence-filter gauge, shared by the translation units whose kernels look 23-mers up (aix_lookup.hip, aix_count.hip, aix_debruijn.hip, aix_unitigs.hip).
 #pragma once
 #include "aix_internal.hpp"
 

@@ -26,13 +26,6 @@ static constexpr int S23_TB = 256;
 static constexpr uint32_t S23_NONE = 0xFFFFFFFFu;     // no k-mer / not a key
 static constexpr uint32_t S23_UND = 0xFFFFFFFEu;      // the table could not decide
 
-// every 'U' byte of an upper-cased word becomes 'T' (count_kmers.cpp:71-88 maps U/u to 3)
-__device__ __forceinline__ uint64_t s23_u_to_t(uint64_t x) {
-    const uint64_t z = x ^ 0x5555555555555555ULL;
-    const uint64_t nz = (((z & 0x7F7F7F7F7F7F7F7FULL) + 0x7F7F7F7F7F7F7F7FULL) | z) & 0x8080808080808080ULL;
-    return x ^ ((~nz & 0x8080808080808080ULL) >> 7);
-}
-
 struct Run23 {
     uint64_t hi, lo;      // 2-bit stream of bases 0..55, base 0 in the top two bits of hi
     uint64_t vmask;       // bit i: byte i is a base (A/C/G/T/U, either case)
@@ -195,9 +188,9 @@ __global__ void __launch_bounds__(S23_TB) k_stream23_slots(const IndexDev ix, co
         if (__ballot(need) != 0ull) {                                                 // uniform
             uint64_t w0 = 0, w1 = 0, w2 = 0;
             if (need) load23(buf + p, w0, w1, w2);
-            w0 = s23_u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
-            w1 = s23_u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
-            w2 = s23_u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
+            w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+            w1 = u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
+            w2 = u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
             const Enc23 e = encode23_words(w0, w1, w2);
             uint64_t key = e.code;
             if (canon_mode == 1) { const uint64_t x = revcomp_refx86(e.code, 23); key = e.code < x ? e.code : x; }
@@ -330,9 +323,9 @@ __global__ void __launch_bounds__(S23_TB) k_run23_slots(const IndexDev ix, const
             if (need) {
                 uint64_t w0, w1, w2;
                 load23(buf + p, w0, w1, w2);
-                w0 = s23_u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
-                w1 = s23_u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
-                w2 = s23_u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
+                w0 = u_to_t(w0 & 0xDFDFDFDFDFDFDFDFULL);
+                w1 = u_to_t(w1 & 0xDFDFDFDFDFDFDFDFULL);
+                w2 = u_to_t(w2 & 0x00DFDFDFDFDFDFDFULL);
                 const Enc23 e = encode23_words(w0, w1, w2);
                 uint64_t key = e.code;
                 if (canon_mode == 1) { const uint64_t x = revcomp_refx86(e.code, 23); key = e.code < x ? e.code : x; }

@@ -1,6 +1,6 @@
 """Deterministic synthetic inputs: genomes, reads, k-mer queries.
 
-Host (numpy) mirror of the device generators in csrc/aix_kernels.hip — both compute exactly the
+Host (numpy) mirror of the device generators in csrc/aix_api.hip — both compute exactly the
 same bytes from the same seeds, so tests can build small cases on the host and the benchmark can
 build the full-size ones directly in HBM. PRNG = counter-based splitmix64:
 

@@ -1167,6 +1167,24 @@ def test_wave_lower_bound_of_the_partition_kernels():
             assert np.array_equal(got, want), (n, nv, keys[np.nonzero((got != want).any(axis=1))[0][:4]])
 
 
+def test_gather_probe_entry_point():
+    """aix_bench_gather_dev, the roofline probe that only the benchmark calls: 2^16 uniform-random reads over a 1 MiB table. Each of the nine
+    instantiated (element bytes, reads in flight) pairs runs and writes nothing (the table and the sink are as before); a pair that is not
+    instantiated is refused with AIX_ERR_HIP."""
+    import torch
+    from aindex_amd._lib import lib, vp, AIX_OK, AIX_ERR_HIP
+    table = torch.empty((1 << 20) // 8, dtype=torch.int64, device="cuda")
+    table.random_(0, 1 << 40)
+    sink = torch.zeros(8, dtype=torch.int64, device="cuda")
+    before = table.clone()
+    run = lambda elem, unroll: lib().aix_bench_gather_dev(vp(table.data_ptr()), (1 << 20) // elem, elem, unroll, 1 << 16, 99, vp(sink.data_ptr()), None)
+    for elem, unroll in ((16, 1), (16, 4), (8, 1), (8, 4), (4, 1), (4, 4), (32, 1), (64, 1), (128, 1)):
+        assert run(elem, unroll) == AIX_OK, (elem, unroll)
+    assert run(16, 2) == AIX_ERR_HIP
+    torch.cuda.synchronize()
+    assert torch.equal(table, before) and int(sink.count_nonzero()) == 0
+
+
 def test_config5_coverage_full_size_properties(config3_index, ix13):
     """Config 5 at its FULL size (1 M sequences x 10 kbp, as the bench runs it; round 2 tested a tenth): the per-position profile equals
     the batch lookup of every window, checked on sampled sequences, for k = 23 (index of config 3) and k = 13. 10 GB of sequences and a
