@@ -37,6 +37,7 @@ BUBBLE_NONE = 0xFFFFFFFF                                           # AIX_BUBBLE_
 GRAPH_MAX_THRESHOLD = 32767                                        # AIX_GRAPH_MAX_THRESHOLD
 THREAD_NO_LINK = (1 << 64) - 1                                     # AIX_THREAD_NO_LINK
 THREAD_BROKEN = (1 << 64) - 2                                      # AIX_THREAD_BROKEN
+PHASE_NONE = 0xFF                                                  # AIX_PHASE_NONE
 SPECTRUM_STATS = 8                                                 # AIX_SPECTRUM_STATS
 STATS_FIELDS = ("n", "non_zero", "max", "min_non_zero", "sum", "non_zero_wide", "max_wide", "sum_wide")
 FIX_NAMES = ("clean", "fixed", "partial", "unfixed", "short", "too_long", "bad_range")   # AIX_FIX_*
@@ -201,6 +202,12 @@ SIGNATURES = {
     "aix_pileup_dev": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
     "aix_pile_call_dev": (i32, [u64, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u64)] + [vp] * 7 + [u64, C.POINTER(u64), vp, vp, vp]),
     "aix_pileup": (i32, [vp, u32, vp, vp, u64, u32, u32] + [C.POINTER(u64)] * 3 + [C.POINTER(vp)] * 12),
+    "aix_phase_observe_dev": (i32, [vp, vp, u64, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, vp, u64,
+                                    C.POINTER(u64), vp, vp]),
+    "aix_phase_bundle_dev": (i32, [u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]),
+    "aix_phase_solve_dev": (i32, [u64, vp, vp, u64, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+    "aix_phase_tag_dev": (i32, [u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+    "aix_phase_solve": (i32, [u64, vp, u64, vp, vp, vp, u32, u32, C.POINTER(u64)] + [C.POINTER(vp)] * 10),
     "aix_reads_fix": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp]),
     "aix_reads_fix_dev": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]),
     "aix_seq_hits": (i32, [vp, vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

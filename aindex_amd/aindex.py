@@ -96,6 +96,23 @@ def format_vcf(variants, contig_lengths=None) -> Iterator[str]:
         yield f"c{c}\t{pos + 1}\t.\t{ref}\t{alt}\t.\t.\tDP={dp};AD={rn},{an}"
 
 
+def format_vcf_phased(variants, contig_lengths=None, sample: str = "sample") -> Iterator[str]:
+    """The lines of format_vcf for the rows of AIndex.get_phased_variants, [(contig, pos, ref, alt, ref_count, alt_count, depth, block,
+    phase)], plus a FORMAT column GT:PS and one sample: 0|1 (phase 0: the alternative base on haplotype 1) or 1|0 with PS the 1-based
+    position of the first site of the block, and 0/1:. for an unphased site. Host only."""
+    variants = list(variants)
+    tails = iter(["GT:PS\t0/1:." if p is None else f"GT:PS\t{'1|0' if p else '0|1'}:{b + 1}" for *_, b, p in variants])
+    for line in format_vcf([v[:7] for v in variants], contig_lengths):
+        if line.startswith("#CHROM"):
+            yield '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">'
+            yield '##FORMAT=<ID=PS,Number=1,Type=Integer,Description="Phase set: the position of the first site of the phase block">'
+            yield f"{line}\tFORMAT\t{sample}"
+        elif line.startswith("#"):
+            yield line
+        else:
+            yield f"{line}\t{next(tails)}"
+
+
 def format_gfa_paths(unitigs: dict, links: dict, support, thread: dict, names: List[str]) -> Iterator[str]:
     """format_gfa with the read evidence of Index.seq_thread: every L line carries RC:i:{support of the link} (the closing link of a
     circular unitig: the number of times a step wound round it), and one P line per maximal stretch of linked steps of every sequence —
@@ -821,6 +838,99 @@ class AIndex:
         g, c = self._called(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_major_permille, 3, 200)
         off, differs = g["offsets"].tolist(), c["polished"] != g["bases"]
         return _write_fasta(path, "c", g, c["polished"].tobytes().decode("ascii"), min_kmers, lambda i: f" PC:i:{int(differs[off[i]:off[i + 1]].sum())}")
+
+    # ---- phasing (Index.phase_observe_t .. phase_tag_t; aix_phase.hip) -----------------------------------
+    def _phased(self, reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_alt_count, min_alt_permille, paired,
+                min_link_reads, min_link_permille, want_tags: bool = False):
+        """(graph arrays, called sites, edges, solved — numpy — and the per-fragment tag arrays | None). The reads are piled once to fix the
+        sites, then threaded and placed a second time, batch by batch, to be read at those sites (and a third time when tags are wanted,
+        after the solve): memory stays independent of the number of reads. Only the raw links, 9 bytes each, are kept across batches."""
+        import torch
+        seqs = [m for pair in self._pairs(reads) for m in pair] if paired else list(reads)
+        graph, counts, _, _ = self._pile(seqs, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend)
+        ix = self._wrapper._need23()
+        dev = graph["node"].device
+        called = ix.pile_call_t(graph, counts, min_depth, 700, min_alt_count, min_alt_permille)
+        group = 2 if paired else 1
+
+        def observed():
+            for st, so in self._batches(seqs, dev, self.RESOLVE_BATCH_BYTES, even=paired):
+                places = ix.pile_place_t(graph, so, ix.seq_thread_t(graph, st, so), max_gap, extend)
+                yield ix.phase_observe_t(graph, st, so, places, called, group)
+
+        kept = [[o[k] for k in ix.LINK_KEYS] for o in observed()]
+        empty = [torch.empty(0, dtype=ty, device=dev) for ty in (torch.int32, torch.int32, torch.uint8)]
+        links = {k: torch.cat([b[i] for b in kept] + [empty[i]]) for i, k in enumerate(ix.LINK_KEYS)}
+        edges = ix.phase_bundle_t(called["total"], links)
+        solved = ix.phase_solve_t(called, edges, min_link_reads, min_link_permille)
+        tags = None
+        if want_tags:
+            got = [ix._graph_to_host(ix.phase_tag_t(o, solved)) for o in observed()]
+            tags = {k: np.concatenate([t[k] for t in got] + [np.zeros(0, np.uint32)]) for k in ("tag_block", "tag_h0", "tag_h1", "tag_other")}
+        host = ix._graph_to_host
+        return host({k: graph[k] for k in ix.GRAPH_KEYS}), host(called), host(edges), host(solved), tags
+
+    @staticmethod
+    def _phased_rows(c: dict, s: dict) -> List[tuple]:
+        pos, none = c["var_pos"].tolist(), _lib.PHASE_NONE
+        tail = [(None, None) if p == none else (pos[b], p) for b, p in zip(s["site_block"].tolist(), s["site_phase"].tolist())]
+        rows = zip(c["var_unitig"].tolist(), pos, [chr(x) for x in c["var_ref"].tolist()], [chr(x) for x in c["var_alt"].tolist()],
+                   c["var_ref_count"].tolist(), c["var_alt_count"].tolist(), c["var_depth"].tolist())
+        return [r + t for r, t in zip(rows, tail)]
+
+    def get_phased_variants(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                            extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200, paired: bool = False,
+                            min_link_reads: int = 2, min_link_permille: int = 800) -> List[tuple]:
+        """get_variants with the sites phased by the reads that cover two of them: [(contig, pos, ref, alt, ref_count, alt_count, depth,
+        block, phase)]. block is the 0-based position of the first site of the phase block on the contig, phase 0 when the alternative
+        base lies on haplotype 1 of that block and 1 when it lies on haplotype 0; both are None for a site no decided link reaches. Two
+        sites are linked by every fragment that shows the contig's or the alternative base at both and at no called site between them; a
+        link is decided by min_link_reads fragments or more, min_link_permille of them or more agreeing. paired: `reads` are pairs as
+        get_scaffolds takes them, and both mates of a pair are one fragment. The reads are threaded and placed a second time after the
+        call has fixed the sites, so memory stays independent of their number: only the raw links, 9 bytes each, are kept across batches."""
+        _, c, _, s, _ = self._phased(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_alt_count, min_alt_permille,
+                                     paired, min_link_reads, min_link_permille)
+        return self._phased_rows(c, s)
+
+    def get_phase_blocks(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                         extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200, paired: bool = False,
+                         min_link_reads: int = 2, min_link_permille: int = 800) -> List[tuple]:
+        """The phase blocks of get_phased_variants, in contig order: [(contig, first_pos, last_pos, n_sites, edges_agree,
+        edges_conflict)] — the decided links inside the block that agree with its phases and that contradict them."""
+        _, c, e, s, _ = self._phased(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_alt_count, min_alt_permille,
+                                     paired, min_link_reads, min_link_permille)
+        rows = {}
+        for v, (b, p) in enumerate(zip(s["site_block"].tolist(), s["site_phase"].tolist())):
+            if p != _lib.PHASE_NONE:
+                r = rows.setdefault(b, [v, v, 0, 0, 0])
+                r[1], r[2] = v, r[2] + 1
+        for hi, st in zip(e["edge_hi"].tolist(), s["edge_state"].tolist()):
+            if st in (1, 2):
+                rows[int(s["site_block"][hi])][2 + st] += 1
+        pos, unit = c["var_pos"].tolist(), c["var_unitig"].tolist()
+        return [(unit[b], pos[first], pos[last], n, agree, conflict) for b, (first, last, n, agree, conflict) in sorted(rows.items())]
+
+    def get_read_haplotags(self, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3, max_gap: int = 46,
+                           extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200, paired: bool = False,
+                           min_link_reads: int = 2, min_link_permille: int = 800) -> List[Optional[tuple]]:
+        """Per fragment (a read, or with paired=True a pair) its place in the phase blocks of get_phased_variants: (contig, block_pos, h0,
+        h1, other) — the block of its first observation on a phased site, its observations there on haplotype 0 and on haplotype 1, and
+        those on phased sites of other blocks — or None for a fragment that observes no phased site. This threads the reads a third time."""
+        _, c, _, _, t = self._phased(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_alt_count, min_alt_permille,
+                                     paired, min_link_reads, min_link_permille, True)
+        pos, unit = c["var_pos"].tolist(), c["var_unitig"].tolist()
+        return [None if b == _lib.BUBBLE_NONE else (unit[b], pos[b], h0, h1, o)
+                for b, h0, h1, o in zip(t["tag_block"].tolist(), t["tag_h0"].tolist(), t["tag_h1"].tolist(), t["tag_other"].tolist())]
+
+    def write_phased_vcf(self, path: str, reads, graph=None, cutoff: int = 0, tip_max_kmers: int = 46, bubble_max_kmers: int = 46, rounds: int = 3,
+                         max_gap: int = 46, extend: int = 22, min_depth: int = 8, min_alt_count: int = 3, min_alt_permille: int = 200, paired: bool = False,
+                         min_link_reads: int = 2, min_link_permille: int = 800) -> int:
+        """VCF of get_phased_variants (format_vcf_phased): the records of write_variants_vcf with GT:PS of one sample; returns the number
+        of records written."""
+        g, c, _, s, _ = self._phased(reads, graph, cutoff, tip_max_kmers, bubble_max_kmers, rounds, max_gap, extend, min_depth, min_alt_count, min_alt_permille,
+                                     paired, min_link_reads, min_link_permille)
+        first = _write_lines(path, format_vcf_phased(self._phased_rows(c, s), np.diff(g["offsets"].astype(np.int64)).tolist()))
+        return sum(first.values()) - first["#"]
 
     # ---- scaffolding (Index.mate_links_t .. scaffold_t; aix_scaffold.hip) --------------------------------
     def _pairs(self, pairs) -> list:

@@ -88,6 +88,16 @@ __device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ a, uint
     return lo;
 }
 
+// first index i in [lo, hi) with a[i] >= key (hi without one); a ascends on [lo, hi) (the CSRs cut from sorted keys in aix_scaffold.hip
+// and aix_phase.hip, the sites under a placement)
+__device__ __forceinline__ uint64_t first_ge(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // the last j in [from, n) with a[j] <= key; a[from] <= key < a[n]. A gallop from `from`, then the bisection above: for keys that ascend
 // with the lane, so that the search starts next to the answer (the windows of aix_seqthread.hip, the read bases of aix_pileup.hip).
 __device__ __forceinline__ uint64_t gallop_last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t from, uint64_t key) {

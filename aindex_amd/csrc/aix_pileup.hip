@@ -1,8 +1,8 @@
 // aix_pileup.hip — reads piled onto the contigs they thread through: the steps of aix_seq_thread_dev merged into placements (one per
 // run of steps on one diagonal of one contig), the bases of every placement counted per contig base and channel, and the counts read out
 // as polished bases, variant sites and per-contig depth. The contract is stated above the declarations in include/aindex_hip.h; DESIGN 5p
-// has the derivations and the resources. What the graph files share is in aix_graph.hpp. Integer only, no LDS, no grid-wide barrier, no
-// spin-wait; one plain launch per step:
+// has the derivations and the resources. What the graph files share is in aix_graph.hpp, what this file shares with aix_phase.hip in
+// aix_pile.hpp. Integer only, no LDS, no grid-wide barrier, no spin-wait; one plain launch per step:
 //   aix_pile_place_dev
 //     validate k_pl_place_validate: one lane per sequence, per step and per contig; nothing below runs on arrays that fail it
 //     heads    k_pl_heads: one lane per step: head[t] = the step is linear and does not merge with step t - 1; circular steps are counted
@@ -25,7 +25,7 @@
 #include <cstring>
 #include <string>
 
-#include "aix_graph.hpp"
+#include "aix_pile.hpp"
 #include "aix_seqhits.hpp"
 
 namespace aix {
@@ -38,34 +38,8 @@ struct PlThr {
     uint32_t min_depth, min_major_permille, min_alt_count, min_alt_permille;
 };
 
-__device__ __forceinline__ bool pl_is_base(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 // A, C, G, T -> 0 .. 3 (bits 2 .. 1 of the byte are 0, 1, 3, 2)
 __device__ __forceinline__ uint32_t pl_code(uint32_t c) { const uint32_t x = (c >> 1) & 3u; return x ^ (x >> 1); }
-
-// The entry j of a CSR over M sequences that holds item t: csr[j] <= t < csr[j + 1]. Whatever the array holds, j <= M and only entries
-// 0 .. M are read; false when no entry holds t (a broken CSR).
-__device__ __forceinline__ bool pl_seq_of(const uint64_t* __restrict__ csr, uint64_t M, uint64_t t, uint64_t& j, uint64_t& lo, uint64_t& hi) {
-    j = last_le(csr, 0, M + 1, t);
-    if (j >= M) return false;
-    lo = csr[j];
-    hi = csr[j + 1];
-    return lo <= t && t < hi;
-}
-
-// what both validations repeat for entry i of max(M, U) + 1: sequence offsets ascend by less than 2^32, the CSR starts at 0, ascends and
-// ends at `total`, contig offsets start at 0 and ascend by at least 23
-__device__ __forceinline__ unsigned pl_frame_bad(uint64_t i, uint64_t M, const uint64_t* __restrict__ offs, const uint64_t* __restrict__ csr, uint64_t total, uint64_t U,
-                                                 const uint64_t* __restrict__ offsets) {
-    unsigned bad = 0;
-    if (i < M) {
-        const uint64_t a = offs[i], b = offs[i + 1];
-        bad += b < a || b - a >= (1ull << 32);
-        bad += csr_bad(i, M, csr[i], csr[i + 1], total, kAnyDegree);
-    }
-    if (i < U) bad += span_bad(offsets[i], offsets[i + 1]);
-    if (i == 0) bad += offsets[0] != 0;
-    return bad;
-}
 
 // ---------------------------------------------------------------------------------------------
 // 1. steps -> placements
@@ -207,28 +181,10 @@ static hipError_t pl_place(const PlSteps& g, uint32_t max_gap, uint32_t extend, 
 // ---------------------------------------------------------------------------------------------
 // 2. placements and read bytes -> counts
 // ---------------------------------------------------------------------------------------------
-struct PlPlaces {
-    uint64_t M, R, U;
-    const uint64_t *offs, *spo;
-    const uint32_t* unitig;
-    const uint8_t* flag;
-    const uint32_t *pos, *q0, *len;
-    const uint64_t* offsets;
-};
-
 __global__ void __launch_bounds__(kCB) k_pl_pile_validate(const PlPlaces g, PlCounters* __restrict__ ctr) {
     const uint64_t work = std::max(std::max(g.M, g.U) + 1, g.R), stride = (uint64_t)gridDim.x * kCB;
     unsigned long long bad = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i < work; i += stride) {
-        bad += pl_frame_bad(i, g.M, g.offs, g.spo, g.R, g.U, g.offsets);
-        if (i >= g.R) continue;
-        uint64_t j, lo, hi;
-        if (!pl_seq_of(g.spo, g.M, i, j, lo, hi)) { ++bad; continue; }
-        const uint64_t sa = g.offs[j], sb = g.offs[j + 1], u = g.unitig[i], len = g.len[i];
-        if (sb < sa || u >= g.U || len < 1 || (uint64_t)g.q0[i] + len > sb - sa) { ++bad; continue; }
-        const uint64_t ulo = g.offsets[u], uhi = g.offsets[u + 1];
-        bad += uhi < ulo || (uint64_t)g.pos[i] + len > uhi - ulo;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kCB + threadIdx.x; i < work; i += stride) bad += pl_places_bad(g, i);
     count_add(bad, &ctr->bad);
 }
 
@@ -325,10 +281,6 @@ struct PlSite {
     uint64_t D;
     bool polish, variant;
 };
-
-// 1000 c[alt] >= permille D, exactly, in 64 bits: a 32-bit threshold times D (up to 2^34 - 4) can pass 2^64 and wrap, but c[alt] <= D, so
-// above 1000 permille only D == 0 reaches it (0 >= 0), and up to 1000 the product stays below 2^44. The first test is wave-uniform.
-__device__ __forceinline__ bool pl_reaches(uint64_t a1000, uint32_t permille, uint64_t D) { return (permille <= 1000u || D == 0) && a1000 >= (uint64_t)permille * D; }
 
 __device__ __forceinline__ PlSite pl_site(const uint4 cell, uint32_t r, const PlThr& th) {
     const uint32_t c[4] = {cell.x, cell.y, cell.z, cell.w};

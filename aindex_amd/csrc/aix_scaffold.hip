@@ -42,15 +42,6 @@ struct ScAggOf {
     __host__ __device__ ScAgg operator()(uint32_t d) const { return ScAgg{1ull, (unsigned long long)d}; }
 };
 
-// first index i in [lo, hi) with a[i] >= key (hi without one); a ascends on [lo, hi)
-__device__ __forceinline__ uint64_t sc_lower(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key) {
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // ---------------------------------------------------------------------------------------------
 // 1. one observation per pair
 // ---------------------------------------------------------------------------------------------
@@ -180,7 +171,7 @@ __global__ void __launch_bounds__(kCB) k_sc_bd_expand(uint64_t B, const uint64_t
 // slink_off[e] = the number of directed links whose source is below e
 __global__ void __launch_bounds__(kCB) k_sc_bd_off(uint64_t NE, const uint64_t* __restrict__ dkey, uint64_t S, uint64_t* __restrict__ slink_off) {
     const uint64_t stride = (uint64_t)gridDim.x * kCB;
-    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e <= NE; e += stride) slink_off[e] = sc_lower(dkey, 0, S, e << 32);
+    for (uint64_t e = (uint64_t)blockIdx.x * kCB + threadIdx.x; e <= NE; e += stride) slink_off[e] = first_ge(dkey, 0, S, e << 32);
 }
 
 __global__ void __launch_bounds__(kCB) k_sc_bd_emit(uint64_t S, uint64_t B, const uint64_t* __restrict__ dkey, const uint32_t* __restrict__ didx,

@@ -1,5 +1,5 @@
-"""The assembly pipeline of Index: unitigs and their links, graph cleaning, threading, repeat resolution, scaffolding, gap closing and
-pile-up, on device tensors (`*_t`) and through host memory."""
+"""The assembly pipeline of Index: unitigs and their links, graph cleaning, threading, repeat resolution, scaffolding, gap closing,
+pile-up and phasing, on device tensors (`*_t`) and through host memory."""
 from __future__ import annotations
 
 import ctypes as C
@@ -727,6 +727,131 @@ class GraphMethods:
         out.update(take_table(ps[1:], ("bases", "counts") + self.PLACE_KEYS + ("place_mism", "stats"), (b, 4 * b, m + 1) + (r,) * 7 + (3,),
                               (np.uint8, np.uint32) + self.PLACE_DTYPES + (np.uint32, np.uint64)))
         out.update(U=u, n_place=r, n_circular_steps=circ)
+        return out
+
+    # ---- phasing (aix_phase.hip) -----------------------------------------------------------------------
+    LINK_KEYS = ("link_lo", "link_hi", "link_rel")
+    EDGE_KEYS = ("edge_lo", "edge_hi", "edge_cis", "edge_trans")
+
+    def phase_observe_t(self, graph: dict, seqs_t, offs_t, places: dict, sites: dict, group: int = 1, cap_hint: int = 0) -> dict:
+        """The read bytes of `places` (what pile_place_t returned for this batch) at the variant `sites` (var_unitig, var_pos, var_ref,
+        var_alt of pile_call_t), on torch's current stream. group 2: sequences 2 i and 2 i + 1 are one fragment. -> frag_obs_off
+        int64[F + 1], obs_site int32, obs_allele uint8 (per fragment, ascending sites), link_lo, link_hi int32, link_rel uint8 (consecutive
+        observations of one fragment on one contig), stats (ints: raw observations, groups, dropped as other, dropped as discordant,
+        observations, links) and the ints n_obs, n_links. cap_hint: the entries of either kind to make room for at once; a kind whose
+        total is larger makes the call run a second time."""
+        import torch
+        off = graph["offsets"]
+        arrs = [places[k] for k in self.PLACE_KEYS[:6]]
+        var = [sites[k] for k in self.VAR_KEYS[:4]]
+        for t in (off, seqs_t, offs_t, *arrs, *var):
+            self._chk_dev(t)
+        m, r, u, v = offs_t.numel() - 1, arrs[1].numel(), off.numel() - 1, var[0].numel()
+        if m < 0 or u < 0 or arrs[0].numel() != m + 1 or any(t.numel() != r for t in arrs[2:]) or any(t.numel() != v for t in var[1:]):
+            raise ValueError("the placement arrays hold R entries each, seq_place_off M + 1, the site arrays V each")
+        if group not in (1, 2) or m % group:
+            raise ValueError("group is 1 or 2 and divides the number of sequences")
+        dev = off.device
+        foff = torch.empty(m // group + 1, dtype=torch.int64, device=dev)
+        stats = torch.empty(6, dtype=torch.int64, device=dev)
+        n_obs, n_links = C.c_uint64(), C.c_uint64()
+        caps = [max(int(cap_hint), 0)] * 2
+        p = tptr_filled
+        while True:
+            obs = [torch.empty(max(caps[0], 1), dtype=ty, device=dev) for ty in (torch.int32, torch.uint8)]
+            links = [torch.empty(max(caps[1], 1), dtype=ty, device=dev) for ty in (torch.int32, torch.int32, torch.uint8)]
+            dev_call(self.device, "aix_phase_observe_dev", p(seqs_t), p(offs_t), m, group, p(arrs[0]), r, *[p(t) for t in arrs[1:]], u, tptr(off), v,
+                     *[p(t) for t in var], tptr(foff), *[tptr(o) if caps[0] else None for o in obs], caps[0], C.byref(n_obs),
+                     *[tptr(o) if caps[1] else None for o in links], caps[1], C.byref(n_links), tptr(stats))
+            if n_obs.value <= caps[0] and n_links.value <= caps[1]:
+                break
+            caps = [max(caps[0], n_obs.value), max(caps[1], n_links.value)]
+        out = {"frag_obs_off": foff, "obs_site": obs[0][:n_obs.value], "obs_allele": obs[1][:n_obs.value]}
+        out.update(zip(self.LINK_KEYS, [t[:n_links.value] for t in links]))
+        out.update(stats=[int(x) for x in stats.tolist()], n_obs=n_obs.value, n_links=n_links.value)
+        return out
+
+    def phase_bundle_t(self, V: int, links: dict) -> dict:
+        """The links of any number of phase_observe_t calls (link_lo, link_hi, link_rel, concatenated in any order) counted per pair of
+        sites, on torch's current stream: the distinct (lo, hi) in ascending (hi, lo) as edge_lo, edge_hi int32 with edge_cis, edge_trans
+        int32 (links with rel 0 and 1), edge_off int64[V + 1] (a CSR over hi) and the int n_edges."""
+        import torch
+        lo, hi, rel = (links[k] for k in self.LINK_KEYS)
+        for t in (lo, hi, rel):
+            self._chk_dev(t)
+        n = lo.numel()
+        if hi.numel() != n or rel.numel() != n:
+            raise ValueError("the link arrays hold N entries each")
+        dev = lo.device
+        outs = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4)]
+        eoff = torch.empty(V + 1, dtype=torch.int64, device=dev)
+        got = C.c_uint64()
+        p = tptr_filled
+        dev_call(self.device, "aix_phase_bundle_dev", V, n, p(lo), p(hi), p(rel), *[p(o) for o in outs], tptr(eoff), C.byref(got))
+        out = dict(zip(self.EDGE_KEYS, [o[:got.value] for o in outs]))
+        out.update(edge_off=eoff, n_edges=got.value)
+        return out
+
+    def phase_solve_t(self, sites: dict, edges: dict, min_link_reads: int = 2, min_link_permille: int = 800) -> dict:
+        """The edges of phase_bundle_t solved, on torch's current stream: every site hangs itself on its best decided edge (at least
+        min_link_reads links, min_link_permille of them or more agreeing), and the forest is read out as site_block int32[V] (the first
+        site of the block), site_phase uint8[V] (0, 1, or _lib.PHASE_NONE for a site alone), site_parent int32[V] (-1 for a root),
+        edge_state uint8[E] (0 undecided, 1 agrees, 2 contradicts, 3 across blocks) and counts (ints: blocks, phased sites, decided
+        edges, edges of state 1, 2, 3)."""
+        import torch
+        vu, eoff = sites["var_unitig"], edges["edge_off"]
+        lo, cis, trans = edges["edge_lo"], edges["edge_cis"], edges["edge_trans"]
+        for t in (vu, eoff, lo, cis, trans):
+            self._chk_dev(t)
+        v, e = vu.numel(), lo.numel()
+        if eoff.numel() != v + 1 or cis.numel() != e or trans.numel() != e:
+            raise ValueError("edge_off holds V + 1 entries, the edge arrays E each")
+        dev = eoff.device
+        block = torch.empty(v, dtype=torch.int32, device=dev)
+        phase = torch.empty(v, dtype=torch.uint8, device=dev)
+        parent = torch.empty(v, dtype=torch.int32, device=dev)
+        state = torch.empty(e, dtype=torch.uint8, device=dev)
+        counts = torch.empty(6, dtype=torch.int64, device=dev)
+        p = tptr_filled
+        dev_call(self.device, "aix_phase_solve_dev", v, p(vu), tptr(eoff), e, p(lo), p(cis), p(trans), min_link_reads, min_link_permille, p(block), p(phase),
+                 p(parent), p(state), tptr(counts))
+        return {"site_block": block, "site_phase": phase, "site_parent": parent, "edge_state": state, "counts": [int(x) for x in counts.tolist()]}
+
+    def phase_tag_t(self, obs: dict, solved: dict) -> dict:
+        """The fragments of a phase_observe_t call tagged with the blocks and phases of phase_solve_t, on torch's current stream:
+        tag_block int32[F] (the block of the fragment's first observation on a phased site, -1 without one), tag_h0, tag_h1 (its
+        observations in that block on haplotype 0 and 1) and tag_other (those on phased sites of other blocks)."""
+        import torch
+        foff, site, allele = obs["frag_obs_off"], obs["obs_site"], obs["obs_allele"]
+        block, phase = solved["site_block"], solved["site_phase"]
+        for t in (foff, site, allele, block, phase):
+            self._chk_dev(t)
+        f, n, v = foff.numel() - 1, site.numel(), block.numel()
+        if f < 0 or allele.numel() != n or phase.numel() != v:
+            raise ValueError("the observation arrays hold n_obs entries each, the site arrays V each")
+        outs = [torch.empty(f, dtype=torch.int32, device=foff.device) for _ in range(4)]
+        p = tptr_filled
+        dev_call(self.device, "aix_phase_tag_dev", f, tptr(foff), n, p(site), p(allele), v, p(block), p(phase), *[p(o) for o in outs])
+        return dict(zip(("tag_block", "tag_h0", "tag_h1", "tag_other"), outs))
+
+    def phase_solve(self, var_unitig, link_lo, link_hi, link_rel, min_link_reads: int = 2, min_link_permille: int = 800) -> dict:
+        """phase_bundle_t and phase_solve_t through host memory: numpy arrays edge_lo, edge_hi, edge_cis, edge_trans uint32[E], edge_off
+        uint64[V + 1], edge_state uint8[E], site_block uint32[V], site_phase uint8[V], site_parent uint32[V], counts uint64[6], and the
+        int n_edges."""
+        vu, lo, hi = (np.ascontiguousarray(a, dtype=np.uint32) for a in (var_unitig, link_lo, link_hi))
+        rel = np.ascontiguousarray(link_rel, dtype=np.uint8)
+        v, n = vu.shape[0], lo.shape[0]
+        if hi.shape[0] != n or rel.shape[0] != n:
+            raise ValueError("the link arrays hold N entries each")
+        ps = [vp() for _ in range(10)]
+        e = C.c_uint64()
+        ptr = lambda a: _np_ptr(a) if a.shape[0] else None
+        with self._device_ctx():
+            call("aix_phase_solve", v, ptr(vu), n, ptr(lo), ptr(hi), ptr(rel), min_link_reads, min_link_permille, C.byref(e), *[C.byref(p) for p in ps])
+        ne = e.value
+        out = take_table(ps, self.EDGE_KEYS + ("edge_off", "edge_state", "site_block", "site_phase", "site_parent", "counts"),
+                         (ne,) * 4 + (v + 1, ne, v, v, v, 6), (np.uint32,) * 4 + (np.uint64, np.uint8, np.uint32, np.uint8, np.uint32, np.uint64))
+        out["n_edges"] = ne
         return out
 
     def _device_ctx(self):

@@ -1170,6 +1170,95 @@ int aix_pileup(aix_index_t* h, uint32_t cutoff, const char* seqs, const uint64_t
                uint32_t** place_mism_out /* nullable */, uint64_t** stats_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------
+ * Phasing: the variant sites of aix_pile_call_dev linked by the reads that cover two of them — allele links, phase blocks, haplotype
+ * tags. (The reference has no counterpart; notation and conventions are those of the pile-up block. tests/phase_ref.py restates this
+ * block.) The four device calls take no index handle, work on device arrays of the current device, are asynchronous on `stream` and
+ * return after their work on it has completed. Every call validates first and writes second: a violation is AIX_ERR_ARG with no output
+ * touched. Every index read from an input array is compared with its bound before it is used. A NULL pointer where one is needed is
+ * AIX_ERR_ARG, decided before anything is allocated or launched. Scratch comes from the pool and goes back on every path; see DESIGN
+ * 5q. Integer only; no result depends on the launch geometry.
+ *
+ * Sites. V sites var_unitig u32[V], var_pos u32[V], var_ref u8[V], var_alt u8[V] as aix_pile_call_dev writes them; site v lies at
+ *   global base g_v = offsets[var_unitig[v]] + var_pos[v]. Validation: var_unitig < U and var_pos < L_u; g strictly ascending; ref and
+ *   alt are upper-case A, C, G or T and differ. V > 2^31 - 4 is AIX_ERR_UNSUPPORTED (all five calls).
+ * Fragments. group is 1 or 2; anything else, or M not a multiple of group, is AIX_ERR_ARG. Fragment f is sequences group f ..
+ *   group f + group - 1 (the mate convention of aix_mate_links_dev); F = M / group. F > 2^32 - 1 is AIX_ERR_UNSUPPORTED.
+ *
+ * 1. aix_phase_observe_dev: placements and read bytes become allele observations and links. Inputs d_seqs, d_offs[M + 1], M, group;
+ *    seq_place_off[M + 1], R and place_unitig / place_flag / place_pos / place_q0 / place_len [R], validated exactly as aix_pileup_dev
+ *    validates them (contig bytes are not read); U, offsets[U + 1]; the sites.
+ *    Raw observation: one for every placement r = (u, pos, len, q0) and every site v with offsets[u] + pos <= g_v < offsets[u] + pos +
+ *      len. With x = g_v - (offsets[u] + pos) its byte is seq[q0 + x] when the placement lies forwards and the complement of
+ *      seq[q0 + len - 1 - x] when it lies backwards (an upper-case A, C, G, T is complemented, any other byte stays what it is). Its
+ *      allele is 0 if the byte equals var_ref[v], 1 if it equals var_alt[v], 2 otherwise (a third base, lower case, N).
+ *    Observation: fragment f observes site v with allele a iff it has at least one raw observation of v and all of them have the same
+ *      allele a in {0, 1} (both mates, and overlapping placements of one read, may see the site). A (f, v) group that holds an allele 2
+ *      is dropped as "other"; one that holds both 0 and 1 and no 2 is dropped as "discordant".
+ *    Link: two observations (v, a), (w, b) of one fragment that follow each other in site order, with var_unitig[v] == var_unitig[w],
+ *      give the link (lo = v, hi = w, rel = a ^ b). Consecutive observations on different contigs give none.
+ *    Outputs: frag_obs_off u64[F + 1], always written; obs_site u32, obs_allele u8, per fragment in ascending site order; link_lo u32,
+ *      link_hi u32, link_rel u8, in fragment order, then site order; stats u64[6] (nullable) = raw observations, (f, v) groups, groups
+ *      dropped as other, groups dropped as discordant, observations, links.
+ *    Sizing, as aix_seq_hits_dev, with two independent caps and totals: *obs_total_out and *link_total_out are always written, the
+ *      entries of a kind only when its total <= its cap, never at or beyond the cap (its arrays may be NULL at cap 0); AIX_OK either way.
+ *    M == 0 or R == 0 or V == 0 is AIX_OK with frag_obs_off all zero and both totals 0 (what is given is still validated).
+ *
+ * 2. aix_phase_bundle_dev: links become counted edges. Inputs V, N and link_lo / link_hi / link_rel [N], in any order (the caller
+ *    concatenates what the batches wrote). Validation: lo < hi < V and rel <= 1. N > 2^32 - 1 is AIX_ERR_UNSUPPORTED, so the counters
+ *    cannot wrap. Outputs, room for N each (the count never exceeds N: no sizing pass): the distinct (lo, hi) in ascending (hi, lo) —
+ *    edge_lo u32, edge_hi u32 — with edge_cis u32 (links with rel 0) and edge_trans u32 (rel 1); edge_off u64[V + 1], a CSR over hi;
+ *    *n_edges_out. N == 0 gives edge_off all zero.
+ *
+ * 3. aix_phase_solve_dev: edges become blocks and phases. Inputs V, var_unitig[V]; edge_off[V + 1], E, edge_lo, edge_cis, edge_trans
+ *    [E] (edge_hi is the row); min_link_reads, min_link_permille.
+ *    Validation: edge_off starts at 0, ascends and ends at E; in row w every lo < w, the lo ascend strictly, and var_unitig[lo] ==
+ *      var_unitig[w]; var_unitig does not descend.
+ *    Decided. n = cis + trans and m = max(cis, trans), in 64 bits. An edge is decided iff n >= max(min_link_reads, 1), cis != trans and
+ *      1000 m >= min_link_permille n, exactly whatever the threshold (above 1000 no edge is decided). Its sign is 1 iff trans > cis.
+ *    Parent. The parent of site w is, among the decided edges of its row, the lo of the one with the largest n; ties go to the larger
+ *      m, then to the larger lo (the nearest site). A site whose row has no decided edge is a root. Parents have smaller indices.
+ *    Block and phase. site_block[w] is the root reached from w, site_phase[w] the XOR of the signs on the way, so a root has phase 0.
+ *      A root without children is unphased: its block is itself and its phase AIX_PHASE_NONE. Phase p at site v means: the alternative
+ *      base lies on haplotype 1 ^ p and the contig's base on haplotype p; an observation (v, a) lies on haplotype a ^ p.
+ *    Outputs: site_block u32[V], site_phase u8[V]; nullable site_parent u32[V] (0xFFFFFFFF for a root); nullable edge_state u8[E]: 0
+ *      undecided, 1 decided with both ends in one block and phase[lo] ^ phase[hi] == sign, 2 decided, one block, contradicting the
+ *      phases, 3 decided with the ends in different blocks (not used); nullable counts u64[6] = blocks of two or more sites, phased
+ *      sites, decided edges, edges of state 1, 2 and 3.
+ *
+ * 4. aix_phase_tag_dev: fragments get a haplotype. Inputs F, frag_obs_off[F + 1], n_obs, obs_site, obs_allele [n_obs]; V, site_block,
+ *    site_phase [V]. Validation: frag_obs_off starts at 0, ascends and ends at n_obs; site < V; allele <= 1; site_block[v] <= v;
+ *    site_phase[v] is 0, 1 or AIX_PHASE_NONE. Per fragment the first observation in the order of the arrays whose site is phased names
+ *    tag_block (0xFFFFFFFF without one); tag_h0 / tag_h1 count the observations in that block with a ^ p = 0 / 1, tag_other those on
+ *    phased sites of other blocks. All four are u32[F].
+ *
+ * The host form takes host arrays (V, var_unitig, N and the three link arrays, the two thresholds), runs bundle and solve on the null
+ * stream of the current device and returns malloc'd arrays (aix_free): the four edge arrays [E], edge_off[V + 1], edge_state[E]
+ * (nullable), site_block[V], site_phase[V], site_parent[V] (nullable), counts[6] (nullable); *n_edges_out = E.
+ * ------------------------------------------------------------------------------------------ */
+#define AIX_PHASE_NONE 0xFFu
+int aix_phase_observe_dev(const char* d_seqs, const uint64_t* d_offs, uint64_t M, uint32_t group, const uint64_t* d_seq_place_off, uint64_t R,
+                          const uint32_t* d_place_unitig, const uint8_t* d_place_flag, const uint32_t* d_place_pos, const uint32_t* d_place_q0,
+                          const uint32_t* d_place_len, uint64_t U, const uint64_t* d_offsets, uint64_t V, const uint32_t* d_var_unitig,
+                          const uint32_t* d_var_pos, const uint8_t* d_var_ref, const uint8_t* d_var_alt, uint64_t* d_frag_obs_off,
+                          uint32_t* d_obs_site, uint8_t* d_obs_allele, uint64_t obs_cap, uint64_t* obs_total_out, uint32_t* d_link_lo,
+                          uint32_t* d_link_hi, uint8_t* d_link_rel, uint64_t link_cap, uint64_t* link_total_out, uint64_t* d_stats /* nullable */,
+                          void* stream);
+int aix_phase_bundle_dev(uint64_t V, uint64_t N, const uint32_t* d_link_lo, const uint32_t* d_link_hi, const uint8_t* d_link_rel, uint32_t* d_edge_lo,
+                         uint32_t* d_edge_hi, uint32_t* d_edge_cis, uint32_t* d_edge_trans, uint64_t* d_edge_off, uint64_t* n_edges_out, void* stream);
+int aix_phase_solve_dev(uint64_t V, const uint32_t* d_var_unitig, const uint64_t* d_edge_off, uint64_t E, const uint32_t* d_edge_lo,
+                        const uint32_t* d_edge_cis, const uint32_t* d_edge_trans, uint32_t min_link_reads, uint32_t min_link_permille,
+                        uint32_t* d_site_block, uint8_t* d_site_phase, uint32_t* d_site_parent /* nullable */, uint8_t* d_edge_state /* nullable */,
+                        uint64_t* d_counts /* nullable */, void* stream);
+int aix_phase_tag_dev(uint64_t F, const uint64_t* d_frag_obs_off, uint64_t n_obs, const uint32_t* d_obs_site, const uint8_t* d_obs_allele, uint64_t V,
+                      const uint32_t* d_site_block, const uint8_t* d_site_phase, uint32_t* d_tag_block, uint32_t* d_tag_h0, uint32_t* d_tag_h1,
+                      uint32_t* d_tag_other, void* stream);
+int aix_phase_solve(uint64_t V, const uint32_t* var_unitig, uint64_t N, const uint32_t* link_lo, const uint32_t* link_hi, const uint8_t* link_rel,
+                    uint32_t min_link_reads, uint32_t min_link_permille, uint64_t* n_edges_out, uint32_t** edge_lo_out, uint32_t** edge_hi_out,
+                    uint32_t** edge_cis_out, uint32_t** edge_trans_out, uint64_t** edge_off_out, uint8_t** edge_state_out /* nullable */,
+                    uint32_t** site_block_out, uint8_t** site_phase_out, uint32_t** site_parent_out /* nullable */,
+                    uint64_t** counts_out /* nullable */);
+
+/* ------------------------------------------------------------------------------------------
  * Read cleaning: the weak-window profile of a read, its longest solid span, and single-base substitution fixes.
  * replaces, M reads at a time, the scaffolding of the reference's read-cleaning layer: READ::set_fm / STUPID_READ::set_fm
  *          (read.hpp:286-307, :392-402: fm[i] = get_freq of 23-window i; an error window iff fm[i] <= Settings::TRUE_ERRORS,
